@@ -8,11 +8,14 @@ ranks (row r -> rank r % N, camera.go:119-122) and gathered to rank 0 with one
 RCCL gather over xGMI.  The scene is uploaded to HBM during warmup; the timed region
 holds only render + gather.
 
-After the headline, `extra_configs` times BASELINE configs C3 (book1), C4 (book2)
-and C5 (model) the same way (row shares on every rank, barrier + max over ranks),
-each with its own roofline, so every GPU config has a measured line.
+A plain run does only that: it sets up, warms up, times the K steps, writes the last
+step's outputs when --dump-outputs DIR is given, and prints the line.  Everything else
+is behind --full: after the headline, `extra_configs` times BASELINE configs C3 (book1),
+C4 (book2) and C5 (model) the same way (row shares on every rank, barrier + max over
+ranks), each with its own roofline, so every GPU config has a measured line; then the
+CPU baseline, the on-device PPM timing and (torchrun jobs) the distinct-device check.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
 Prints one JSON line (rank 0).  Roofline (DESIGN.md "Roofline"): the fused kernel
@@ -62,8 +65,16 @@ def parse():
     ap.add_argument("--spp", type=int, default=1024)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--mode", default="auto", choices=["auto", "fused", "wavefront"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the extra configs (C3-C5), the CPU "
+                         "baseline, the on-device PPM timing and (torchrun jobs) the "
+                         "distinct-device check; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one returned as "
+                         "DIR/<name>.npy: image.npy (float32 H x W x 3, rank 0's gathered "
+                         "image) and stats.npy (float64 samples, segments, rows of rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra-configs", action="store_true", help="--full: skip C3-C5")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline work")
     ap.add_argument("--devices", default=None,
                     help="single-process multi-GPU: comma-separated HIP devices rendered through "
@@ -78,7 +89,10 @@ def parse():
                     help="torchrun jobs: skip rank 0's rt_render_multi check over distinct devices")
     ap.add_argument("--multi-device-check", type=int, default=0, metavar="N",
                     help=argparse.SUPPRESS)  # child-process mode of that check
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def multi_device_check(ndev):
@@ -115,6 +129,27 @@ def run_multi_device_check(ndev):
         return {"devices": list(range(ndev)), "error": f"exit {r.returncode}: {r.stderr[-300:]}"}
     except Exception as e:  # timeout or spawn failure
         return {"devices": list(range(ndev)), "error": str(e)[:300]}
+
+
+DUMP_CAP_BYTES = 64 * 10 ** 6  #--dump-outputs: everything written stays under this
+
+
+def dump_outputs(path, img, stat):
+    """--dump-outputs: the image the last timed step left with its caller and that step's
+    deterministic counters.  The inputs (scene, camera, seed) are fixed by the arguments, so
+    two builds can be compared array for array.  An image above the cap is cut to a fixed,
+    seeded sample of its rows (their indices go to image_rows.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    a = np.ascontiguousarray(img.detach().cpu().numpy(), dtype=np.float32)
+    keep = max(1, (DUMP_CAP_BYTES - (1 << 20)) // (a[0].nbytes + 8))
+    if a.shape[0] > keep:
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+        np.save(os.path.join(path, "image_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(path, "image.npy"), a)
+    np.save(os.path.join(path, "stats.npy"),
+            np.array([stat[k] for k in ("samples", "segments", "rows")], dtype=np.float64))
 
 
 def cpu_model():
@@ -369,11 +404,10 @@ def main():
             roof["frac"] = round(roof["achieved"] / PEAK_HBM_GBS, 4)
         from go_raytracer_amd import shard
         torch.cuda.synchronize()
-        t_ppm0 = time.perf_counter()
-        ppm = rt.format_ppm_device(buf if world_size == 1 else
-                                   shard.assemble(gathered, H, world_size))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, buf if world_size == 1 else
+                         shard.assemble(gathered, H, world_size), stats[-1])
         n_gpus = len(set(devices)) if devices else world_size
-        t_ppm = time.perf_counter() - t_ppm0
         value = total_samples / elapsed / 1e6
         line = {
             "metric": "Msamples/sec (pixels×spp/s) + wall-clock, Cornell Box 800×800×1024spp",
@@ -396,14 +430,19 @@ def main():
             "roofline": roof,
             "wall_clock": {"scene_build_s": round(t_build, 3),
                            "first_step_s": None if t_first is None else round(t_first, 3),
-                           "render_step_s": round(elapsed / args.steps, 4),
-                           "ppm_on_device_s": round(t_ppm, 4), "ppm_bytes": len(ppm)},
+                           "render_step_s": round(elapsed / args.steps, 4)},
         }
+        if args.full:
+            t_ppm0 = time.perf_counter()
+            ppm = rt.format_ppm_device(buf if world_size == 1 else
+                                       shard.assemble(gathered, H, world_size))
+            line["wall_clock"].update(ppm_on_device_s=round(time.perf_counter() - t_ppm0, 4),
+                                      ppm_bytes=len(ppm))
     scene.close()
 
     # ------------------------------------------------------- C3, C4, C5 lines
     extra = {}
-    if not args.no_extra_configs:
+    if args.full and not args.no_extra_configs:
         import tempfile
         for name, sname, width, spp, steps in EXTRA:
             setup = {}
@@ -464,18 +503,19 @@ def main():
         if extra:
             line["extra_configs"] = extra
         cpu = None
-        if world_size == 1 and not devices and not args.no_cpu_baseline:
+        if args.full and world_size == 1 and not devices and not args.no_cpu_baseline:
             tree, cam, w, l = rt.demo_scene(args.scene)
             cam.Width, cam.SamplesPerPixel = args.width, args.spp
             if args.scene == "book1":
                 cam.AspectRatio = 1.5
             cpu = cpu_baseline(tree, w, l, cam, args.cpu_seconds)
-        line["cpu_baseline"] = cpu
+        if args.full:
+            line["cpu_baseline"] = cpu
         if cpu:
             line["speedup_vs_cpu"] = round(line["value"] / cpu["value"], 1)
             line["speedup_vs_host_extrapolated"] = round(
                 line["value"] / cpu["host"]["extrapolated_all_cores_Msamples_s"], 1)
-        if world_size > 1 and not args.no_multi_check:
+        if args.full and world_size > 1 and not args.no_multi_check:
             ndev = torch.cuda.device_count()
             line["checks"] = {"render_multi_distinct_devices":
                               run_multi_device_check(min(ndev, 8)) if ndev >= 2 else

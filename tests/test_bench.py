@@ -49,6 +49,56 @@ def test_devices_mode_rccl_gather_line(gpu):
     assert line["value"] > 0 and line["steps"] == 2
 
 
+def test_steps_must_be_positive():
+    p = _bench("--steps", "0")
+    assert p.returncode != 0 and "--steps must be >= 1" in p.stderr
+
+
+@pytest.mark.gpu
+def test_plain_line_and_dumped_outputs(rt, gpu, tmp_path):
+    """A plain run prints the headline only (nothing of --full) and --dump-outputs writes
+    what the last timed step returned: the image equals the harness render of the same
+    scene, camera and seed bit for bit, and stats.npy holds that render's counters."""
+    import numpy as np
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+                        "--scene", "cornell", "--width", "160", "--spp", "64", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line
+    assert line["steps"] == 3 and line["roofline"]["launches"] == 3
+    assert line["ms_per_step"] > 0 and line["unit"] == "Msamples/s" and line["dtype"] == "f32"
+    samples = 160 * 160 * 64
+    assert line["value"] == pytest.approx(samples / line["ms_per_step"] / 1e3, rel=1e-3)
+    for k in ("extra_configs", "cpu_baseline", "speedup_vs_cpu", "checks"):
+        assert k not in line
+    assert "ppm_on_device_s" not in line["wall_clock"]
+    assert sorted(f.name for f in out.iterdir()) == ["image.npy", "stats.npy"]
+    img, st = np.load(out / "image.npy"), np.load(out / "stats.npy")
+    assert img.dtype == np.float32 and img.shape == (160, 160, 3) and st.dtype == np.float64
+    t, cam, w, l = rt.demo_scene("cornell")
+    cam.Width, cam.SamplesPerPixel = 160, 64
+    with rt.Scene(t, w, l) as sc:
+        ref, rst = sc.render(cam, seed=1)
+    assert np.array_equal(img.view(np.uint32), ref.view(np.uint32))
+    assert list(st) == [rst["samples"], rst["segments"], rst["rows"]] and st[0] == samples
+
+
+@pytest.mark.gpu
+def test_full_line_keeps_the_moved_fields(gpu):
+    """--full runs what a plain run leaves out (here with the long legs switched off: the
+    on-device PPM timing stays, and the CPU baseline's slot is in the line)."""
+    p = _bench("--gpus", "1", "--full")
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line["wall_clock"]["ppm_bytes"] > 0 and line["wall_clock"]["ppm_on_device_s"] >= 0
+    assert "cpu_baseline" in line and line["cpu_baseline"] is None
+    assert line["value"] > 0 and line["steps"] == 2
+
+
 def test_gather_option_rejects_unknown():
     p = _bench("--gather", "nccl-allgather")
     assert p.returncode != 0 and "invalid choice" in p.stderr
