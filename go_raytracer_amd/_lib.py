@@ -139,6 +139,7 @@ SIGNATURES = {
     "rt_tune_set": (_I, [C.c_char_p, C.c_char_p]),
     "rt_tune_get": (_I, [C.c_char_p, C.c_char_p, C.c_int32]),
     "rt_tune_list": (_I, [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
+    "rt_brute_shape": (_I, [C.POINTER(C.c_int32)]),
     "rt_tree_create": (_I, [C.POINTER(_P)]),
     "rt_tree_destroy": (_I, [_P]),
     "rt_tree_seed": (_I, [_P, C.c_uint64]),

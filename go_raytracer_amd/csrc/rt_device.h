@@ -203,4 +203,36 @@ struct DevScene {
   int32_t n_big;        // world spheres tested before the BVH (big_recs, fp64)
 };
 
+// ---- record-loop layout ----------------------------------------------------
+// The seven group counts of a scene's record pairs (DevScene brute_*), fixed at upload.
+struct BruteCounts {
+  int32_t ng;     // general pairs
+  int32_t vy;     // y-parallel pairs
+  int32_t ax[3];  // axis-aligned pairs per axis
+  int32_t mx;     // mixed-pair code, 0 = none
+  int32_t box;    // box descriptor pairs
+};
+// Layouts the lean LDS record-loop kernel is compiled for (k_fused<true, 0, 0, SHAPE>): with
+// the counts known at compile time the loop has no bounds to read and no loop to test.
+// Shape 0 is the generic kernel, which takes any layout.
+//   1: a Cornell room with one or two boxes (walls x, floor/ceiling y, light|back wall mixed,
+//      one box pair; a single box fills both halves of its pair)
+//   2: the same room without boxes
+constexpr int kBruteShapeCount = 3;
+inline constexpr BruteCounts brute_shape(int id) {
+  return id == 1   ? BruteCounts{0, 0, {1, 1, 0}, 2 | (3 << 2), 1}
+         : id == 2 ? BruteCounts{0, 0, {1, 1, 0}, 2 | (3 << 2), 0}
+                   : BruteCounts{0, 0, {0, 0, 0}, 0, 0};
+}
+inline constexpr bool brute_counts_equal(const BruteCounts& a, const BruteCounts& b) {
+  return a.ng == b.ng && a.vy == b.vy && a.ax[0] == b.ax[0] && a.ax[1] == b.ax[1] &&
+         a.ax[2] == b.ax[2] && a.mx == b.mx && a.box == b.box;
+}
+// the listed shape whose counts equal c exactly, or 0 (generic)
+inline constexpr int brute_shape_of(const BruteCounts& c) {
+  for (int id = 1; id < kBruteShapeCount; ++id)
+    if (brute_counts_equal(c, brute_shape(id))) return id;
+  return 0;
+}
+
 }  // namespace rt

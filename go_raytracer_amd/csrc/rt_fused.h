@@ -174,9 +174,11 @@ __shared__ unsigned long long g_tdrain[4];  // debug builds: when the wave's gra
 __shared__ unsigned long long g_dinfo[4][3];  // ... and then: samples left, busy lanes, segments
 #endif
 // TREE: 4 = BVH4, 5 = compressed BVH4 (64-B nodes, global only), 2 = BVH2, 0 = no tree
-// (every record tested, tiny scenes)
-template <bool LDS, uint32_t FT, int TREE>
+// (every record tested, tiny scenes).  SHAPE (TREE 0, FT 0, LDS only): the record layout the
+// loop is compiled for (rt_device.h brute_shape), 0 = any
+template <bool LDS, uint32_t FT, int TREE, int SHAPE = 0>
 __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) {
+  static_assert(SHAPE == 0 || (LDS && FT == 0u && TREE == 0), "shapes: the lean LDS record loop only");
   extern __shared__ F4 lnodes[];  // LDS scene cache, sized at launch (scene_lds_bytes)
   __shared__ uint32_t lstack[(fused_short(FT, TREE) > 0 ? fused_short(FT, TREE) : 1) * 256];
   __shared__ float lw[3 * fused_wlds(FT, TREE) * 256];
@@ -281,7 +283,7 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
       PH_CNT(PH_TRAV_LANES, __popcll(__ballot(1)));
       PH_CNT(PH_TRAV_ROUNDS, 1);
       if constexpr (TREE == 0)
-        trav_brute<FT, !LDS>(P.sc, lnodes, s.o, s.d, s.time, 0.001f, tr);
+        trav_brute<FT, !LDS, SHAPE>(P.sc, lnodes, s.o, s.d, s.time, 0.001f, tr);
       else if constexpr (TREE == 8)
       {
         const int nsteps = trav_steps8<FT>(P.sc, ts, s.o, s.d, s.time, 0.001f, tr, P.step_budget);

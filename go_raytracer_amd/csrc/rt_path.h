@@ -1305,18 +1305,32 @@ RT_D uint32_t box_face(const DevScene& sc, const F4* lrec, uint32_t code, f3 o, 
                                                                  2 * (8 + slot));
   return ((const lds_u32*)lrec)[base + 2 * (8 + slot)];
 }
-template <uint32_t FT, bool SMEM>
+// SHAPE: 0 = any layout, the group bounds read from the scene's parameters; else the
+// listed layout brute_shape(SHAPE) (rt_device.h), chosen by the host when the uploaded
+// scene's counts equal it: every bound below is then a constant, so the group loops
+// disappear, every record address is an immediate offset from the record base, and the
+// pairs' loads and tests are one straight block that the scheduler interleaves ahead of
+// the ordered best / bk selects.  Same operations on the same operands in the same record
+// order either way: the same hits bit for bit.
+template <uint32_t FT, bool SMEM, int SHAPE = 0>
 RT_D void trav_brute(const DevScene& sc, const F4* lrec, f3 o, f3 d, float time, float tmin,
                      Trav& tr) {
   static_assert(!HAS(FT_SPHERE | FT_TRI), "record loop: quad-only feature sets");
-  // the group bounds re-read from the kernel-argument segment on every call (kparams): held
-  // in SGPRs across the kernel's loop they were spilled to VGPR lanes, ~15 v_readlane per
-  // segment in the loops' prologues
-  const cst_params* kp = kparams();
-  const int nax = kp->sc.brute_ax[0], nay = kp->sc.brute_ax[1], naz = kp->sc.brute_ax[2];
-  const int nvy = kp->sc.brute_vt[1];  // y-parallel pairs only (RotateY is the only rotation)
+  static_assert(SHAPE >= 0 && SHAPE < kBruteShapeCount, "record loop: unlisted shape");
+  // generic: the group bounds re-read from the kernel-argument segment on every call
+  // (kparams): held in SGPRs across the kernel's loop they were spilled to VGPR lanes, ~15
+  // v_readlane per segment in the loops' prologues
+  const cst_params* kp = SHAPE == 0 ? kparams() : nullptr;
+  BruteCounts bc = brute_shape(SHAPE);
+  if constexpr (SHAPE == 0) {
+    bc.ax[0] = kp->sc.brute_ax[0], bc.ax[1] = kp->sc.brute_ax[1], bc.ax[2] = kp->sc.brute_ax[2];
+    bc.vy = kp->sc.brute_vt[1];
+    bc.ng = kp->sc.brute_ng;
+  }
+  const int nax = bc.ax[0], nay = bc.ax[1], naz = bc.ax[2];
+  const int nvy = bc.vy;  // y-parallel pairs only (RotateY is the only rotation)
   // general pairs first, then the y-parallel and the axis-aligned groups
-  const int ng = kp->sc.brute_ng;
+  const int ng = bc.ng;
   const v2f ox = {o.x, o.x}, oy = {o.y, o.y}, oz = {o.z, o.z};
   const v2f dx = {d.x, d.x}, dy = {d.y, d.y}, dz = {d.z, d.z};
   float best = tr.best.t;
@@ -1349,13 +1363,13 @@ RT_D void trav_brute(const DevScene& sc, const F4* lrec, f3 o, f3 d, float time,
   brute_axis<0, SMEM>(sc, lrec, q, q + nax, O, Dv, tmin, best, bk);
   brute_axis<1, SMEM>(sc, lrec, q + nax, q + nax + nay, O, Dv, tmin, best, bk);
   brute_axis<2, SMEM>(sc, lrec, q + nax + nay, q + nax + nay + naz, O, Dv, tmin, best, bk);
-  const int qm = q + nax + nay + naz, mx = kp->sc.brute_mx;  // the mixed pair (0 or 1)
+  const int qm = q + nax + nay + naz, mx = SHAPE == 0 ? kp->sc.brute_mx : bc.mx;  // the mixed pair (0 or 1)
   if (mx == (1 | (2 << 2))) brute_mixed<0, 1, SMEM>(sc, lrec, qm, o, d, tmin, best, bk);
   else if (mx == (1 | (3 << 2))) brute_mixed<0, 2, SMEM>(sc, lrec, qm, o, d, tmin, best, bk);
   else if (mx == (2 | (3 << 2))) brute_mixed<1, 2, SMEM>(sc, lrec, qm, o, d, tmin, best, bk);
   const int qb = qm + (mx != 0 ? 1 : 0);
   const float iy = rcp(d.y);
-  brute_box<SMEM>(sc, lrec, qb, qb + kp->sc.brute_box, O, Dv, iy, tmin, best, bk);
+  brute_box<SMEM>(sc, lrec, qb, qb + (SHAPE == 0 ? kp->sc.brute_box : bc.box), O, Dv, iy, tmin, best, bk);
   if (bk != 0xFFFFFFFFu) {
     if (bk & kBoxCode) bk = box_face<SMEM>(sc, lrec, bk, o, d, iy, best);
     // the winner's fields (pair bk/2, half bk&1): Q at floats 8/10/12, A at

@@ -208,6 +208,7 @@ struct DeviceScene {
   size_t brute_slots = 0;           // records in brute_pairs, pads included (even)
   int32_t shade_n = 0;              // F4s of the lean shade table after the pairs (0: none)
   int32_t brute_boxes = 0;          // boxes among them tested as slabs (rt_path.h brute_box)
+  int brute_shape = 0;              // the listed layout the pair counts equal (rt_device.h), 0 = none
   uint32_t root2 = PRIM_NONE;
   int32_t n_nodes2 = 0;
   const F4* qnodes = nullptr;       // compressed BVH4 (host_qbvh.cpp): 64-B items, root item 0
@@ -736,6 +737,11 @@ static int upload_scene(const Scene* s, DeviceScene* ds) {
                            r[2].y, r[2].z, r[3].x, r[3].y, r[3].z, kb,     r[0].w};
       for (int e = 0; e < 15; ++e) f[2 * e] = v[e];
     }
+    {
+      const BruteCounts bc = {d.brute_ng, d.brute_vt[1], {d.brute_ax[0], d.brute_ax[1], d.brute_ax[2]},
+                              d.brute_mx, d.brute_box};
+      ds->brute_shape = brute_shape_of(bc);
+    }
     ds->brute_slots = slots.size();
     // The lean set's shade table, after the pairs: per quad its normal and material kind,
     // and its texture's solid colour (2 F4), so the record-loop kernel shades from LDS
@@ -884,7 +890,11 @@ static const void* fused_for(uint32_t set) {
 }
 static uint32_t pick_set(uint32_t feats) { return pick_ft_set(feats); }
 // BVH2 kernels exist for the two smallest sets with the tree in LDS (tiny scenes)
-static const void* pick_fused(bool lds, uint32_t set, int tree) {
+// (shape: the lean LDS record loop compiled for a listed record layout, rt_device.h brute_shape)
+static const void* pick_fused(bool lds, uint32_t set, int tree, int shape = 0) {
+  static_assert(kBruteShapeCount == 3, "pick_fused: one kernel per listed shape");
+  if (tree == 0 && lds && set == kFtSets[0] && shape == 1) return (const void*)k_fused<true, kFtSets[0], 0, 1>;
+  if (tree == 0 && lds && set == kFtSets[0] && shape == 2) return (const void*)k_fused<true, kFtSets[0], 0, 2>;
   if (tree == 0 && lds && set == kFtSets[0]) return (const void*)k_fused<true, kFtSets[0], 0>;
   if (tree == 0 && lds && set == kFtSets[1]) return (const void*)k_fused<true, kFtSets[1], 0>;
   if (tree == 0 && !lds && set == kFtSets[0]) return (const void*)k_fused<false, kFtSets[0], 0>;
@@ -1062,7 +1072,12 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     if ((rc = ensure_qbvh(s, ds))) return rc;
     if (ds->qnodes) tree = 5;
   }
-  const void* fused_kernel = pick_fused(f_lds, ft_set, tree);
+  // The lean LDS record loop compiled for the scene's record layout, when it is a listed one
+  // (fixed at upload: the same for every render of the scene).  RT_BRUTE_SHAPE=0: the generic
+  // kernel (A/B; the same hits bit for bit).
+  const int brute_shape_id = tree == 0 && f_lds && ft_set == kFtSets[0] && env_int("RT_BRUTE_SHAPE", 1) != 0
+                                 ? ds->brute_shape : 0;
+  const void* fused_kernel = pick_fused(f_lds, ft_set, tree, brute_shape_id);
   if (!fused_kernel) return set_error(RT_ERR_UNSUPPORTED, "internal: no fused kernel for this scene");
 #ifdef RT_QTOP
   const size_t fused_lds = f_lds ? 64 * (node_slots * n_nodes + (f_recs ? rec_slots : 0))

@@ -56,6 +56,11 @@ int rt_tune_get(const char* name, char* buf, int32_t cap);
 /* Knob i's name and whether it may change image bits (the others move work only); returns
  * the number of knobs (i < 0: just the count). */
 int rt_tune_list(int32_t i, const char** name, int32_t* changes_bits);
+/* The record loop's layout matcher, as render uses it (host only, no device): counts = the pair
+ * counts of a tiny scene's record groups {general, y-parallel, x, y, z axis-aligned, mixed-pair
+ * code, box pairs}.  Returns the id (>= 1) of the compiled-in layout whose counts equal them
+ * exactly, 0 when only the generic kernel takes them. */
+int rt_brute_shape(const int32_t counts[7]);
 
 /* ------------------------------------------------------------------------ */
 /* Scene tree: one constructor per reference constructor.                    */
