@@ -14,14 +14,14 @@ import numpy as np
 
 from . import _lib
 from ._lib import (RT_FT_ALL, RT_FT_BOX, RT_NOISE_MARBLE, RT_NOISE_PERLIN,  # noqa: F401
-                   RT_NOISE_TURBULENT, RtCamera,
+                   RT_NOISE_TURBULENT, RtAov, RtCamera, RtDenoiseOpts,
                    RtCameraDerived, RtError, RtRenderOpts, RtSceneInfo, RtStats, RtTreeView,
                    check, lib)
 
 __all__ = ["Tree", "Camera", "Scene", "quantize", "format_ppm", "device_count", "RtError",
            "tune", "untune", "tuning", "tune_knobs", "tune_from_env",
            "demo_scene", "DEMO_SCENES", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
-           "format_ppm_device"]
+           "format_ppm_device", "denoise", "denoise_device"]
 
 DEMO_SCENES = ("book1", "book2", "book3", "simple_light", "quads", "cornell", "cornell_smoke",
                "model")
@@ -510,6 +510,39 @@ class Scene:
                                      C.byref(st)))
         return {f: getattr(st, f) for f, _ in RtStats._fields_}
 
+    def render_aov(self, camera, n_samples=1, seed=1, device=0, rank=0, nranks=1):
+        """Feature buffers of this rank's rows (rt_render_aov): the first hit of the camera
+        rays render() gives samples 0 .. n_samples-1 of every pixel, averaged.  Returns
+        {"albedo": float32 [rows, W, 3], "normal": float32 [rows, W, 3] (world space, facing
+        the ray, 0 on a miss), "depth": float32 [rows, W], "material": int32 [rows, W]
+        (RT_MAT_* of sample 0, -1 on a miss), "stats": dict}."""
+        d = camera.derived()
+        rows = len(range(rank, d.height, nranks))
+        res = {"albedo": np.zeros((rows, d.width, 3), np.float32),
+               "normal": np.zeros((rows, d.width, 3), np.float32),
+               "depth": np.zeros((rows, d.width), np.float32),
+               "material": np.full((rows, d.width), -1, np.int32)}
+        a = RtAov(*[res[k].ctypes.data for k in ("albedo", "normal", "depth", "material")])
+        st = RtStats()
+        c = camera.to_c()
+        o = self._opts(seed, device, rank, nranks, 0, 0, False, None)
+        check(lib().rt_render_aov(self._p, C.byref(c), C.byref(o), n_samples, C.byref(a),
+                                  C.byref(st)))
+        res["stats"] = {f: getattr(st, f) for f, _ in RtStats._fields_}
+        return res
+
+    def render_aov_device(self, camera, albedo=None, normal=None, depth=None, material=None,
+                          n_samples=1, seed=1, device=0, rank=0, nranks=1, stream=None):
+        """rt_render_aov_device: the same buffers written to device pointers (e.g. torch
+        tensors' .data_ptr(); None = not wanted) on `stream`.  Returns the stats dict."""
+        a = RtAov(albedo, normal, depth, material)
+        st = RtStats()
+        c = camera.to_c()
+        o = self._opts(seed, device, rank, nranks, 0, 0, False, stream)
+        check(lib().rt_render_aov_device(self._p, C.byref(c), C.byref(o), n_samples, C.byref(a),
+                                         C.byref(st)))
+        return {f: getattr(st, f) for f, _ in RtStats._fields_}
+
 
 def _multi(scene, camera, devices, out_ptr, seed, path_slots, chunk, profile, mode, rccl=False):
     devs = (C.c_int32 * len(devices))(*[int(d) for d in devices])
@@ -595,6 +628,60 @@ def format_ppm_device(rgb, to_host=True):
     out = torch.empty(n, dtype=torch.uint8, device=a.device)
     check(int(lib().rt_format_ppm_device(a.data_ptr(), w, h, out.data_ptr(), n, dev, st)))
     return out.cpu().numpy().tobytes() if to_host else out
+
+
+def _denoise_opts(iterations=0, demodulate=None, sigma_color=0.0, sigma_normal=0.0,
+                  sigma_depth=0.0, has_albedo=False):
+    o = RtDenoiseOpts()
+    o.iterations = iterations
+    o.demodulate = int(has_albedo if demodulate is None else demodulate)
+    o.sigma_color, o.sigma_normal, o.sigma_depth = sigma_color, sigma_normal, sigma_depth
+    return o
+
+
+def denoise(rgb, aov=None, **opts):
+    """Edge-avoiding a-trous denoise (rt_denoise) of a host float32 [H, W, 3] image guided by
+    `aov`, a dict as Scene.render_aov returns it (any of "albedo", "normal", "depth"; None or
+    missing = that guide off).  opts: iterations (0 = 5), demodulate (default: on when an
+    albedo is given), sigma_color / sigma_normal / sigma_depth (0 = the library defaults).
+    Returns a new float32 [H, W, 3] array."""
+    a = np.ascontiguousarray(rgb, dtype=np.float32)
+    h, w = a.shape[:2]
+    aov = aov or {}
+    keep = [None if aov.get(k) is None else np.ascontiguousarray(aov[k], dtype=np.float32)
+            for k in ("albedo", "normal", "depth")]
+    f = RtAov(*[None if k is None else k.ctypes.data for k in keep], None)
+    o = _denoise_opts(has_albedo=keep[0] is not None, **opts)
+    out = np.empty_like(a)
+    check(lib().rt_denoise(a.ctypes.data, C.byref(f), w, h, C.byref(o), out.ctypes.data))
+    return out
+
+
+def denoise_device(rgb, aov=None, out=None, **opts):
+    """rt_denoise_device on device float32 torch tensors: rgb [H, W, 3], aov a dict of
+    "albedo" [H, W, 3] / "normal" [H, W, 3] / "depth" [H, W] tensors on the same device.
+    `out` may be rgb itself (in place); by default a new tensor.  Runs on the tensor's
+    current stream and returns after the work completes."""
+    import torch
+    a = rgb if (rgb.is_contiguous() and rgb.dtype == torch.float32) else \
+        rgb.contiguous().to(torch.float32)
+    h, w = a.shape[:2]
+    aov = aov or {}
+    keep = [None if aov.get(k) is None else aov[k].contiguous().to(torch.float32)
+            for k in ("albedo", "normal", "depth")]
+    f = RtAov(*[None if k is None else k.data_ptr() for k in keep], None)
+    o = _denoise_opts(has_albedo=keep[0] is not None, **opts)
+    if out is None:
+        out = torch.empty_like(a)
+    elif (out.dtype != torch.float32 or not out.is_contiguous() or out.shape != a.shape
+          or out.device != a.device):
+        raise ValueError("denoise_device: out must be a contiguous float32 tensor of rgb's shape "
+                         "on rgb's device")
+    elif out is rgb and a is not rgb:
+        raise ValueError("denoise_device: in place needs a contiguous float32 rgb")
+    check(lib().rt_denoise_device(a.data_ptr(), C.byref(f), w, h, C.byref(o), out.data_ptr(),
+                                  a.device.index or 0, _stream_of(a)))
+    return out
 
 
 def device_count():

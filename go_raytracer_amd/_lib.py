@@ -94,6 +94,17 @@ class RtStats(C.Structure):
     ]
 
 
+class RtAov(C.Structure):  # rt_aov: feature buffers (any pointer may be NULL)
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p),
+                ("material", C.c_void_p)]
+
+
+class RtDenoiseOpts(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("_pad", C.c_int32)]
+
+
 class RtTreeView(C.Structure):
     _fields_ = [
         ("nodes", C.c_void_p), ("n_nodes", C.c_int32),
@@ -201,6 +212,14 @@ SIGNATURES = {
     "rt_quantize_device": (_I, [C.c_void_p, C.c_int64, C.c_void_p, _I, C.c_void_p]),
     "rt_format_ppm_device": (C.c_int64, [C.c_void_p, _I, _I, C.c_void_p, C.c_int64, _I,
                                          C.c_void_p]),
+    "rt_render_aov": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
+                           C.POINTER(RtAov), C.POINTER(RtStats)]),
+    "rt_render_aov_device": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
+                                  C.POINTER(RtAov), C.POINTER(RtStats)]),
+    "rt_denoise": (_I, [C.c_void_p, C.POINTER(RtAov), _I, _I, C.POINTER(RtDenoiseOpts),
+                        C.c_void_p]),
+    "rt_denoise_device": (_I, [C.c_void_p, C.POINTER(RtAov), _I, _I, C.POINTER(RtDenoiseOpts),
+                               C.c_void_p, _I, C.c_void_p]),
     "rt_demo_scene": (_I, [_P, C.c_char_p, C.c_char_p, C.POINTER(RtCamera), C.POINTER(_I),
                            C.POINTER(_I)]),
     "rt_demo_scene_name": (_I, [_I, C.POINTER(C.c_char_p)]),

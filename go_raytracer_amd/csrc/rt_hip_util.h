@@ -1,0 +1,67 @@
+// rt_hip_util.h — host-side helpers shared by the HIP translation units of the feature pass
+// and the denoiser (rt_aov.hip, rt_denoise.hip): the error macro, the current-device guard
+// and the grow-only per-device scratch.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "rt_internal.h"
+
+namespace rt {
+
+#define HIP_OK(expr)                                                                    \
+  do {                                                                                  \
+    hipError_t _e = (expr);                                                             \
+    if (_e != hipSuccess)                                                               \
+      return set_error(RT_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(_e));   \
+  } while (0)
+
+// Restores the calling thread's current device on scope exit.
+struct DeviceGuard {
+  int prev = -1;
+  DeviceGuard() {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+// RT_OK when `device` is a visible HIP device; RT_ERR_DEVICE without any, RT_ERR_INVALID else
+inline int device_ok(const char* who, int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    return set_error(RT_ERR_DEVICE, "%s: no HIP device available", who);
+  }
+  if (device < 0 || device >= ndev)
+    return set_error(RT_ERR_INVALID, "%s: device %d of %d", who, device, ndev);
+  return RT_OK;
+}
+
+// Grow-only device scratch, one buffer per device ordinal (as rt_output.hip's): no allocation
+// per call once warm.  The caller serialises its users, and no work that reads an old buffer
+// may be in flight when a larger one is asked for (the old one is freed).
+struct DeviceScratch {
+  std::vector<void*> buf;
+  std::vector<size_t> cap;
+  int get(int device, size_t bytes, void** out, const char* who) {
+    if ((int)buf.size() <= device) {
+      buf.resize(device + 1, nullptr);
+      cap.resize(device + 1, 0);
+    }
+    if (cap[device] < bytes) {
+      if (buf[device]) (void)hipFree(buf[device]);
+      buf[device] = nullptr;
+      cap[device] = 0;
+      if (hipMalloc(&buf[device], bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_error(RT_ERR_OOM, "%s: scratch of %zu bytes", who, bytes);
+      }
+      cap[device] = bytes;
+    }
+    *out = buf[device];
+    return RT_OK;
+  }
+};
+
+}  // namespace rt

@@ -161,6 +161,15 @@ constexpr size_t kBoxLeafMinPrims = 256;
 uint32_t scene_features(const HostScene& h, bool* noise_table0 = nullptr);
 // rt_render.hip
 void release_device(Scene* s);
+// rt_render.hip, for the feature pass (rt_aov.hip): the scene's copy on `device` (the
+// calling thread's current device; uploaded on first use) set up for the structure the fused
+// render of this scene traverses -- tree 0 record loop, 2 BVH2, 4 BVH4, 5 compressed BVH4
+// (built and uploaded on demand), chosen by render_impl's rules
+struct AovView {
+  DevScene sc;
+  int tree;
+};
+int aov_view(Scene* s, int device, AovView* out);
 
 }  // namespace rt
 

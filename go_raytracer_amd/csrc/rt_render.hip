@@ -340,7 +340,7 @@ static int upload(DeviceScene* ds, const std::vector<T>& v, const T** out) {
 static int env_int(const char* name, int dflt) { return tune_int(name, dflt); }
 
 
-static FastDiv make_fastdiv(uint32_t d) {
+FastDiv make_fastdiv(uint32_t d) {  // (also rt_aov.hip)
   FastDiv f{1u, 0u, 0u, d};
   if (d <= 1) return f;  // d == 1: t = 0, q = n
   const uint32_t l = 32u - (uint32_t)__builtin_clz(d - 1u);
@@ -959,6 +959,77 @@ static int ensure_qbvh(Scene* s, DeviceScene* ds) {
   return RT_OK;
 }
 
+// The fused kernels' LDS scene-cache budget in 64-B slots at the kernel's waves per SIMD
+// (160 KB per CU, less the static stacks), and the structure a fused render of the scene
+// traverses before the L1/L2-only refinements (BVH8, compressed BVH4): 0 record loop, 2 BVH2,
+// 4 BVH4.  One place for render_impl and the feature pass (aov_view).
+static size_t fused_lds_slots(uint32_t ft_set, int tr) {
+  return std::min<size_t>(kLdsNodes, (160u * 1024u / (unsigned)fused_waves(ft_set, tr) -
+                                      fused_static_lds(ft_set, tr) - 512u) / 64u);
+}
+static uint32_t scene_ft_set(const Scene* s) {
+  // the feature-set kernels read perlin table 0 from LDS only: scenes whose noise
+  // textures use other tables run the all-features kernel (generic table pointers)
+  const uint32_t feats = s->h.features;
+  return (feats & FT_NOISE) && !s->h.noise_table0 ? FT_ALL : pick_set(feats);
+}
+static int fused_base_tree(const Scene* s, uint32_t ft_set) {
+  const size_t n_refs = s->h.refs.size();
+  const bool small_set = ft_set == kFtSets[0] || ft_set == kFtSets[1];
+  const int env_tree = env_int("RT_TREE", -1);
+  const size_t brute_max = (size_t)env_int("RT_BRUTE_MAX", kBruteMax);  // A/B override
+  const bool fits2 = !s->h.nodes.empty() && s->h.nodes.size() / 4 + n_refs <= fused_lds_slots(ft_set, 2);
+  int tree = 4;
+  // Record loop vs tree, measured on the Cornell box plus 0-12 extra boxes
+  // (tools/brute_sweep.py, profiles/r1_brute_sweep.jsonl): the lockstep loop wins
+  // up to ~56 records (18: +33 %, 48: +16 %), reading the records from the LDS
+  // cache when they fit (C2 +2 % over scalar loads), with scalar loads otherwise.
+  if (small_set && n_refs > 0 && n_refs <= brute_max) tree = 0;
+  else if (small_set && n_refs <= 64 && fits2) tree = 2;
+  if (small_set && (env_tree == 4 || (env_tree == 2 && fits2))) tree = env_tree;  // A/B override
+  return tree;
+}
+// a BVH4 read through L1/L2 with single-prim leaves takes its compressed form (64-B nodes,
+// host_qbvh.cpp) when a kernel of the set exists; RT_QBVH=0: the 128-B nodes (A/B)
+static bool wants_qbvh(uint32_t ft_set) {
+  return env_int("RT_QBVH", 1) != 0 && pick_fused(false, ft_set, 5) != nullptr;
+}
+
+// The feature pass's view of the scene (rt_internal.h AovView, rt_aov.hip): the tree a fused
+// render of it takes (fused_base_tree, then the compressed BVH4 as render_impl), and the
+// DevScene set up for it as render_impl sets up Params::sc.  The BVH8 of RT_BVH8_KERNELS
+// builds is not taken: those scenes' BVH4 (or its compressed form) finds the same hits.
+int aov_view(Scene* s, int device, AovView* out) {
+  DeviceScene* ds = nullptr;
+  int rc = ensure_scene(s, device, &ds);
+  if (rc) return rc;
+  const uint32_t ft_set = scene_ft_set(s);
+  int tree = fused_base_tree(s, ft_set);
+  if (tree == 0 && !ds->brute_pairs) tree = 4;  // (records not uploaded: RT_BRUTE_MAX raised since)
+  if (tree == 2 && !ds->nodes2) tree = 4;
+  const bool f_lds = tree != 4 || 2 * (s->h.nodes4.size() / 8) <= fused_lds_slots(ft_set, 4);
+  if (tree == 4 && !f_lds && wants_qbvh(ft_set)) {
+    if ((rc = ensure_qbvh(s, ds))) return rc;
+    if (ds->qnodes) tree = 5;
+  }
+  out->sc = ds->d;
+  out->tree = tree;
+  if (tree == 2) {
+    out->sc.nodes = ds->nodes2;
+    out->sc.root = ds->root2;
+    out->sc.n_nodes = ds->n_nodes2;
+  } else if (tree == 5) {
+    out->sc.nodes = ds->qnodes;
+    out->sc.root = 0;
+    out->sc.n_nodes = (int32_t)std::min<size_t>(ds->qitems, 0x7FFFFFFF);
+  } else if (tree == 0) {
+    out->sc.n_nodes = 0;
+    out->sc.leafprims = ds->brute_pairs;
+    out->sc.n_refs = (int32_t)ds->brute_slots;
+  }
+  return RT_OK;
+}
+
 static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
                        float* out_host, float* out_dev, rt_stats* stats, int slot_id = 0,
                        const Gather* gather = nullptr) {
@@ -1003,9 +1074,7 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   int fused_blocks = 0;
   const bool lds_nodes = s->h.nodes4.size() / 8 <= (size_t)kLdsNodes / 2;
   const uint32_t feats = s->h.features;
-  // the feature-set kernels read perlin table 0 from LDS only: scenes whose noise
-  // textures use other tables run the all-features kernel (generic table pointers)
-  const uint32_t ft_set = (feats & FT_NOISE) && !s->h.noise_table0 ? FT_ALL : pick_set(feats);
+  const uint32_t ft_set = scene_ft_set(s);
   // The fused kernel's LDS scene cache (stage_nodes): all BVH nodes, then the
   // leaf records when both fit, within the LDS a workgroup may take at the
   // kernel's target waves per SIMD (160 KB per CU, 24 KB of stacks per group).
@@ -1017,27 +1086,10 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   // BVH2 kernels exist only for the two smallest feature sets with the tree and
   // its records in LDS (pick_fused): anything else takes the BVH4.
   const size_t n_refs = s->h.refs.size();
-  auto slots_for = [&](int tr) {
-    return std::min<size_t>(kLdsNodes, (160u * 1024u / (unsigned)fused_waves(ft_set, tr) -
-                                        fused_static_lds(ft_set, tr) - 512u) / 64u);
-  };
-  const bool small_set = ft_set == kFtSets[0] || ft_set == kFtSets[1];
+  auto slots_for = [&](int tr) { return fused_lds_slots(ft_set, tr); };
   // tree: 0 (no tree: every record tested, <= kBruteMax records in LDS), 2 or 4
   const int env_tree = env_int("RT_TREE", -1);
-  int tree = 4;
-  const size_t brute_max = (size_t)env_int("RT_BRUTE_MAX", kBruteMax);  // A/B override
-  // Record loop vs tree, measured on the Cornell box plus 0-12 extra boxes
-  // (tools/brute_sweep.py, profiles/r1_brute_sweep.jsonl): the lockstep loop wins
-  // up to ~56 records (18: +33 %, 48: +16 %), reading the records from the LDS
-  // cache when they fit (C2 +2 % over scalar loads), with scalar loads otherwise.
-  if (mode == RT_MODE_FUSED && small_set && n_refs > 0 && n_refs <= brute_max)
-    tree = 0;
-  else if (mode == RT_MODE_FUSED && small_set && n_refs <= 64 && !s->h.nodes.empty() &&
-           s->h.nodes.size() / 4 + n_refs <= slots_for(2))
-    tree = 2;
-  if (mode == RT_MODE_FUSED && small_set && (env_tree == 2 || env_tree == 4) &&
-      (env_tree == 4 || (!s->h.nodes.empty() && s->h.nodes.size() / 4 + n_refs <= slots_for(2))))
-    tree = env_tree;  // A/B override
+  int tree = mode == RT_MODE_FUSED ? fused_base_tree(s, ft_set) : 4;
   const size_t lds_slots = slots_for(tree);
   const size_t brute_slots = ds->brute_slots;  // record-loop pairs, 2 x 64 B each
   const int smem_env = env_int("RT_BRUTE_SMEM", -1);
@@ -1067,8 +1119,7 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   // Trees read through L1/L2 with single-prim leaves take the compressed BVH4 (64-B nodes,
   // host_qbvh.cpp): the same closest hits, half the bytes per node step.  RT_QBVH=0: the
   // 128-B nodes (A/B)
-  if (mode == RT_MODE_FUSED && tree == 4 && !f_lds && env_int("RT_QBVH", 1) != 0 &&
-      pick_fused(false, ft_set, 5)) {
+  if (mode == RT_MODE_FUSED && tree == 4 && !f_lds && wants_qbvh(ft_set)) {
     if ((rc = ensure_qbvh(s, ds))) return rc;
     if (ds->qnodes) tree = 5;
   }

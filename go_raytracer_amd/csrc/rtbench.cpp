@@ -16,8 +16,12 @@
 // -tree-seed (the scene's rand seed), -mode auto|fused|wavefront, -assets DIR,
 // -progress (a progress line on stderr, the reference's bubbletea bar,
 // camera.go:106-108), -slices N (rt_progress granularity), -stats (one JSON
-// line of rt_stats on stderr).  -cpuprofile has no pprof to drive on the GPU
-// path: the file receives the same JSON statistics instead.
+// line of rt_stats on stderr), -denoise (feature pass at min(spp, 16) samples, then
+// the a-trous denoiser before the PPM is written; prints the statistics line with
+// both times), -aov PREFIX (writes PREFIX_albedo.ppm, PREFIX_normal.ppm as
+// n * 0.5 + 0.5 and PREFIX_depth.ppm normalised to the image maximum, through the
+// same PPM writer).  -cpuprofile has no pprof to drive on the GPU path: the file
+// receives the same JSON statistics instead.
 #include <unistd.h>
 
 #include <atomic>
@@ -29,6 +33,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "rt_abi.h"
@@ -44,10 +49,10 @@ struct Flag {
 };
 
 struct Args {
-  std::string cpuprofile, out = "image.ppm", mode = "auto", assets;
+  std::string cpuprofile, out = "image.ppm", mode = "auto", assets, aov;
   long long N = 1, S = -1, device = 0, width = 0, spp = 0, depth = 0, slices = 0;
   unsigned long long seed = 1, tree_seed = 1;
-  bool progress = false, stats = false;
+  bool progress = false, stats = false, denoise = false;
 };
 
 std::vector<Flag> flags(Args& a) {
@@ -55,10 +60,14 @@ std::vector<Flag> flags(Args& a) {
       {"N", "Set the number of cores to allocate to rendering", Flag::INT, &a.N, "1"},
       {"S", "Set the scene to render, default will render a custom scene function", Flag::INT,
        &a.S, "-1"},
+      {"aov", "write PREFIX_albedo.ppm, PREFIX_normal.ppm and PREFIX_depth.ppm (first-hit feature buffers)",
+       Flag::STR, &a.aov, ""},
       {"assets", "directory holding earthmap.jpg / dragon.obj (default: <exe dir>/../assets)",
        Flag::STR, &a.assets, ""},
       {"cpuprofile", "Write cpu profile to file (here: render statistics as JSON)", Flag::STR,
        &a.cpuprofile, ""},
+      {"denoise", "denoise the image (a-trous filter guided by the feature buffers) before it is written",
+       Flag::BOOL, &a.denoise, ""},
       {"depth", "override Camera.MaxDepth (0 = the scene's)", Flag::INT, &a.depth, "0"},
       {"device", "HIP device ordinal", Flag::INT, &a.device, "0"},
       {"mode", "kernel strategy: auto, fused or wavefront", Flag::STR, &a.mode, "auto"},
@@ -182,17 +191,29 @@ int fail(const char* what, int rc) {
 }
 
 std::string stats_json(const rt_stats& st, const rt_camera_derived& d, const char* scene,
-                       double wall_s) {
+                       double wall_s, int aov_samples, double ms_aov, double ms_denoise) {
   char b[1024];
   snprintf(b, sizeof b,
            "{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"spp\": %d, \"max_depth\": %d, "
            "\"samples\": %" PRIu64 ", \"segments\": %" PRIu64 ", \"ms_render\": %.3f, "
            "\"samples_per_s\": %.6g, \"mode\": %d, \"tree_width\": %d, \"chunk_samples\": %d, "
-           "\"wall_s\": %.3f}",
+           "\"aov_samples\": %d, \"ms_aov\": %.3f, \"ms_denoise\": %.3f, \"wall_s\": %.3f}",
            scene, d.width, d.height, d.spp_sqrt * d.spp_sqrt, d.max_depth, st.samples,
            st.segments, st.ms_total, st.ms_total > 0 ? st.samples / (st.ms_total * 1e-3) : 0.0,
-           st.mode, st.tree_width, st.chunk_samples, wall_s);
+           st.mode, st.tree_width, st.chunk_samples, aov_samples, ms_aov, ms_denoise, wall_s);
   return b;
+}
+
+// one image through the PPM writer (camera.go:160 + PrintColor) into `path`
+int write_ppm(const std::vector<float>& img, int w, int h, FILE* f, const char* path) {
+  int64_t n = rt_format_ppm(img.data(), w, h, nullptr, 0);
+  std::vector<char> text((size_t)(n > 0 ? n : 0));
+  if (n < 0 || rt_format_ppm(img.data(), w, h, text.data(), n) != n) return fail("rt_format_ppm", (int)n);
+  if (!f || fwrite(text.data(), 1, text.size(), f) != text.size() || fclose(f) != 0) {
+    fprintf(stderr, "rtbench: writing %s failed\n", path);
+    return 1;
+  }
+  return 0;
 }
 
 }  // namespace
@@ -272,18 +293,47 @@ int main(int argc, char** argv) {
   if (a.progress) fprintf(stderr, "\rrendering %s: 100.0%%\n", scene);
   if (rc != RT_OK) return fail("rt_render", rc);
 
-  // camera.go:160 header + PrintColor per pixel, then main.go:477's single write
-  int64_t n = rt_format_ppm(rgb.data(), d.width, d.height, nullptr, 0);
-  std::vector<char> text((size_t)(n > 0 ? n : 0));
-  if (n < 0 || rt_format_ppm(rgb.data(), d.width, d.height, text.data(), n) != n)
-    return fail("rt_format_ppm", (int)n);
-  if (fwrite(text.data(), 1, text.size(), out) != text.size() || fclose(out) != 0) {
-    fprintf(stderr, "rtbench: writing %s failed\n", a.out.c_str());
-    return 1;
+  // -denoise / -aov: the feature buffers of the same camera rays, then the filter
+  int aov_samples = 0;
+  double ms_aov = 0.0, ms_denoise = 0.0;
+  if (a.denoise || !a.aov.empty()) {
+    const size_t np = (size_t)d.width * d.height;
+    std::vector<float> albedo(3 * np), normal(3 * np), depth(np);
+    rt_aov f = {albedo.data(), normal.data(), depth.data(), nullptr};
+    aov_samples = d.spp_sqrt * d.spp_sqrt < 16 ? d.spp_sqrt * d.spp_sqrt : 16;
+    rt_stats sa;
+    auto ta = std::chrono::steady_clock::now();
+    if ((rc = rt_render_aov(sc, &cam, &o, aov_samples, &f, &sa)) != RT_OK) return fail("rt_render_aov", rc);
+    ms_aov = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
+    if (a.denoise) {
+      rt_denoise_opts dopt;
+      memset(&dopt, 0, sizeof dopt);  // the library defaults
+      dopt.demodulate = 1;
+      auto td = std::chrono::steady_clock::now();
+      if ((rc = rt_denoise(rgb.data(), &f, d.width, d.height, &dopt, rgb.data())) != RT_OK)
+        return fail("rt_denoise", rc);
+      ms_denoise = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
+    }
+    if (!a.aov.empty()) {
+      float dmax = 0.0f;
+      for (float v : depth) dmax = v > dmax ? v : dmax;
+      std::vector<float> nimg(3 * np), dimg(3 * np);
+      for (size_t i = 0; i < 3 * np; ++i) nimg[i] = normal[i] * 0.5f + 0.5f;
+      for (size_t i = 0; i < np; ++i) dimg[3 * i] = dimg[3 * i + 1] = dimg[3 * i + 2] = dmax > 0 ? depth[i] / dmax : 0.0f;
+      const std::pair<const char*, const std::vector<float>*> outs[] = {
+          {"_albedo.ppm", &albedo}, {"_normal.ppm", &nimg}, {"_depth.ppm", &dimg}};
+      for (const auto& e : outs) {
+        const std::string path = a.aov + e.first;
+        if (write_ppm(*e.second, d.width, d.height, fopen(path.c_str(), "wb"), path.c_str())) return 1;
+      }
+    }
   }
+
+  // camera.go:160 header + PrintColor per pixel, then main.go:477's single write
+  if (write_ppm(rgb, d.width, d.height, out, a.out.c_str())) return 1;
   double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  std::string js = stats_json(st, d, scene, wall);
-  if (a.stats) fprintf(stderr, "%s\n", js.c_str());
+  std::string js = stats_json(st, d, scene, wall, aov_samples, ms_aov, ms_denoise);
+  if (a.stats || a.denoise) fprintf(stderr, "%s\n", js.c_str());
   if (!a.cpuprofile.empty()) {
     FILE* p = fopen(a.cpuprofile.c_str(), "w");
     if (!p) {

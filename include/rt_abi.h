@@ -465,6 +465,65 @@ int rt_quantize_device(const float* rgb_dev, int64_t n_pixels, uint8_t* out_dev,
 int64_t rt_format_ppm_device(const float* rgb_dev, int w, int h, char* out_dev, int64_t cap,
                              int device, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Feature buffers (first hit of the render's own camera rays) and the       */
+/* edge-avoiding a-trous denoiser they guide (DESIGN.md "Feature buffers and */
+/* denoiser").  Added without an ABI version change: detect by the symbols.  */
+/* ------------------------------------------------------------------------ */
+typedef struct {          /* any pointer may be NULL = not wanted */
+  float*   albedo;        /* [rows][W][3] */
+  float*   normal;        /* [rows][W][3] world space, facing the ray; 0 on a miss */
+  float*   depth;         /* [rows][W]    t * |d| from the ray origin; 0 on a miss */
+  int32_t* material;      /* [rows][W]    RT_MAT_* of sample 0's hit, -1 on a miss */
+} rt_aov;
+
+/* The feature ray of sample j of a pixel is exactly the camera ray rt_render gives that
+ * sample (same seed, RT_STREAM_CAMERA draw, stratum, defocus and time); the buffers hold
+ * the mean over samples 0 .. n_samples-1 (0 means 1; more than spp_sqrt^2 is
+ * RT_ERR_INVALID), material is sample 0's.  Rows follow opts->rank / nranks as
+ * rt_render's.  The hit is the closest WORLD surface, evaluated as the render's shading
+ * evaluates it; constant media are transparent to the feature pass (a smoke volume shows
+ * the surface behind it).  Albedo: Lambertian / isotropic = the texture at the hit, metal =
+ * its albedo, dielectric = (1,1,1), diffuse light = its emission when front-facing else 0,
+ * miss = the camera background.  Two calls give identical bits.  stats (may be NULL):
+ * samples and segments count the feature rays, tree_width the structure traversed (the one
+ * rt_render's fused kernel takes for the scene), ms_total the wall time.
+ * rt_render_aov: out_host holds host pointers; rt_render_aov_device: pointers on
+ * opts->device, work enqueued on opts->stream (NULL: a library stream), returns after it
+ * completes. */
+int rt_render_aov(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
+                  int32_t n_samples, const rt_aov* out_host, rt_stats* stats);
+int rt_render_aov_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
+                         int32_t n_samples, const rt_aov* out_device, rt_stats* stats);
+
+typedef struct {
+  int32_t iterations;     /* 0 -> 5; 1..8 */
+  int32_t demodulate;     /* 1: filter rgb / max(albedo, 1e-3), multiply back after */
+  float sigma_color;      /* 0 -> 0.5  (halved every iteration) */
+  float sigma_normal;     /* 0 -> 0.3 */
+  float sigma_depth;      /* 0 -> 0.02 (relative to the pixel's depth) */
+  int32_t _pad;
+} rt_denoise_opts;
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010) of a linear
+ * RGB image [h][w][3], guided by feat (albedo / normal / depth as rt_render_aov writes them
+ * for the same view; material is not read).  A pure image operation: no scene.  Iteration
+ * i = 0 .. iterations-1 takes the 5 x 5 taps (dx, dy) in {-2..2}^2 * 2^i with the B3 kernel
+ * h (x) h, h = [1/16, 1/4, 3/8, 1/4, 1/16], each weighted by
+ *   exp(-|c_p - c_q|^2 / (sigma_color 2^-i)^2) exp(-|n_p - n_q|^2 / sigma_normal^2)
+ *   exp(-(d_p - d_q)^2 / (sigma_depth max(d_p, 1e-6))^2)
+ * (c from the previous iteration), skipping taps outside the image and pixels with a
+ * non-finite colour, renormalised by the weights used; non-finite pixels pass through
+ * unchanged.  feat->normal / feat->depth NULL switches that weight off; feat may be NULL
+ * unless demodulate is set, which needs feat->albedo (else RT_ERR_INVALID).  out may alias
+ * rgb.  opts NULL: the defaults.  rt_denoise: host pointers, staged through the device
+ * (device 0); rt_denoise_device: device pointers on `device`, enqueued on `stream`
+ * (hipStream_t or NULL), returns after the work completes. */
+int rt_denoise(const float* rgb, const rt_aov* feat, int w, int h, const rt_denoise_opts* opts,
+               float* out);
+int rt_denoise_device(const float* rgb_dev, const rt_aov* feat_dev, int w, int h,
+                      const rt_denoise_opts* opts, float* out_dev, int device, void* stream);
+
 /* Demo scenes mirroring main.go (by name or the main.go -S number).
  * names: book1, book2, book3, simple_light, quads, cornell, cornell_smoke, model
  * The camera receives the scene's settings; override fields afterwards. */
