@@ -438,6 +438,18 @@ class Scene:
                                          nodes.ctypes.data or None, C.byref(nn), C.byref(root)))
         return items, nodes, int(root.value)
 
+    def export_records(self, fill=True):
+        """(pairs uint32 [4 * n_slots + shade_n, 4]: the record loop's pair array with the shade
+        table appended, n_slots, the seven layout counts in rt_brute_shape's order, shade_n,
+        n_boxes); n_slots = 0 for a scene too large to have pairs.  fill=False: sizes only."""
+        ns, sn, nb, counts = C.c_int32(), C.c_int32(), C.c_int32(), (C.c_int32 * 7)()
+        check(lib().rt_scene_export_records(self._p, None, C.byref(ns), counts, C.byref(sn), C.byref(nb)))
+        pairs = np.zeros((4 * ns.value + sn.value, 4), np.uint32)
+        if fill:
+            check(lib().rt_scene_export_records(self._p, pairs.ctypes.data or None, C.byref(ns), counts,
+                                                C.byref(sn), C.byref(nb)))
+        return pairs, ns.value, tuple(counts), sn.value, nb.value
+
     MODES = {"auto": 0, "wavefront": 1, "fused": 2}
 
     @staticmethod

@@ -177,6 +177,39 @@ int rt_scene_export_bvh8(const rt_scene* sc, float* nodes, int32_t* n_nodes, uin
   return RT_OK;
 }
 
+int rt_scene_export_qbvh(const rt_scene* sc, float* items, int32_t* n_items, float* nodes4,
+                         int32_t* n_nodes4, uint32_t* root4) {
+  if (!sc) return rt::set_error(RT_ERR_INVALID, "rt_scene_export_qbvh: null");
+  const rt::HostScene& h = sc->s.h;
+  std::vector<rt::F4> recs, qb;
+  rt::build_leaf_records(h, recs);
+  size_t n = 0;
+  const int rc = rt::build_qbvh(h, recs, &qb, &n);
+  if (rc != RT_OK) return rc;
+  if (n_items) *n_items = (int32_t)n;
+  if (n_nodes4) *n_nodes4 = (int32_t)(h.nodes4.size() / 8);
+  if (root4) *root4 = h.root4;
+  if (items && n) memcpy(items, qb.data(), n * 64);
+  if (nodes4 && !h.nodes4.empty()) memcpy(nodes4, h.nodes4.data(), h.nodes4.size() * 16);
+  return RT_OK;
+}
+
+int rt_scene_export_records(const rt_scene* sc, float* pairs, int32_t* n_slots, int32_t counts[7],
+                            int32_t* shade_n, int32_t* n_boxes) {
+  if (!sc) return set_error(RT_ERR_INVALID, "rt_scene_export_records: null");
+  const rt::RecordPack p = rt::pack_records(sc->s.h);
+  if (n_slots) *n_slots = (int32_t)p.n_slots;
+  if (shade_n) *shade_n = p.shade_n;
+  if (n_boxes) *n_boxes = p.n_boxes;
+  if (counts) {
+    const rt::BruteCounts& c = p.counts;
+    const int32_t v[7] = {c.ng, c.vy, c.ax[0], c.ax[1], c.ax[2], c.mx, c.box};
+    memcpy(counts, v, sizeof v);
+  }
+  if (pairs && !p.pairs.empty()) memcpy(pairs, p.pairs.data(), p.pairs.size() * 16);
+  return RT_OK;
+}
+
 int rt_scene_export_prim_bounds(const rt_scene* sc, float* bounds, int32_t* n) {
   if (!sc) return set_error(RT_ERR_INVALID, "rt_scene_export_prim_bounds: null");
   const rt::HostScene& h = sc->s.h;

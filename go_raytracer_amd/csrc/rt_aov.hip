@@ -26,8 +26,6 @@
 
 namespace rt {
 
-FastDiv make_fastdiv(uint32_t d);  // rt_render.hip
-
 #ifdef RT_QTOP
 #error "rt_aov.hip: k_aov<5> stages no top items in LDS; the RT_QTOP experiment build does not cover the feature pass"
 #endif
@@ -221,7 +219,7 @@ int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, 
   std::lock_guard<std::mutex> lk(g_mu);
 
   const uint32_t W = (uint32_t)cd.width, H = (uint32_t)cd.height;
-  const uint32_t rows = H > (uint32_t)o.rank ? (H - (uint32_t)o.rank + o.nranks - 1) / o.nranks : 0;
+  const uint32_t rows = rank_rows(H, o.rank, o.nranks);
   const uint64_t npix64 = (uint64_t)rows * W;
   if (npix64 >= 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_render_aov: image too large");
   const uint32_t npix = (uint32_t)npix64;
@@ -239,28 +237,7 @@ int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, 
   if (npix > 0) {
     Params p{};
     p.sc = view.sc;
-    for (int i = 0; i < 3; ++i) {
-      p.p00r[i] = (float)(cd.pixel00[i] - cd.center[i]);
-      p.du[i] = (float)cd.delta_u[i];
-      p.dv[i] = (float)cd.delta_v[i];
-      p.cc[i] = (float)cd.center[i];
-      p.dku[i] = (float)cd.defocus_u[i];
-      p.dkv[i] = (float)cd.defocus_v[i];
-      p.bg[i] = (float)cd.background[i];
-    }
-    p.recip_s = (float)cd.recip_spp_sqrt;
-    p.maxc = (float)cd.max_contribution;
-    p.s = cd.spp_sqrt;
-    p.defocus = cd.defocus_angle > 0 ? 1 : 0;
-    p.max_depth = cd.max_depth;
-    p.width = (int)W;
-    p.rank = o.rank;
-    p.nranks = o.nranks;
-    p.npix = npix;
-    p.ss = ss;
-    p.seed = o.seed;
-    p.fd_width = make_fastdiv(W);
-    p.fd_s = make_fastdiv((uint32_t)cd.spp_sqrt);
+    set_camera_params(p, cd, o, npix);
     // traversal-stack overflow columns, one per launched thread
     const uint32_t cols = (uint32_t)blocks * 256u;
     void* ost = nullptr;

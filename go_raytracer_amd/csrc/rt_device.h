@@ -204,6 +204,7 @@ struct DevScene {
 };
 
 // ---- record-loop layout ----------------------------------------------------
+constexpr int kBruteMax = 48;      // scenes up to this many leaf entries skip the tree (fused)
 // The seven group counts of a scene's record pairs (DevScene brute_*), fixed at upload.
 struct BruteCounts {
   int32_t ng;     // general pairs

@@ -1,6 +1,6 @@
-// rt_hip_util.h — host-side helpers shared by the HIP translation units of the feature pass
-// and the denoiser (rt_aov.hip, rt_denoise.hip): the error macro, the current-device guard
-// and the grow-only per-device scratch.
+// rt_hip_util.h — host-side helpers shared by the HIP translation units of the render, the
+// feature pass and the denoiser (rt_render.hip, rt_aov.hip, rt_denoise.hip): the error macro,
+// the current-device guard and the grow-only per-device scratch.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,7 +15,8 @@ namespace rt {
       return set_error(RT_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(_e));   \
   } while (0)
 
-// Restores the calling thread's current device on scope exit.
+// Restores the calling thread's current device on scope exit: every ABI entry that
+// switches devices leaves the caller's (e.g. torch's) current device as it found it.
 struct DeviceGuard {
   int prev = -1;
   DeviceGuard() {
@@ -37,6 +38,13 @@ inline int device_ok(const char* who, int device) {
     return set_error(RT_ERR_INVALID, "%s: device %d of %d", who, device, ndev);
   return RT_OK;
 }
+
+// rt_render.hip, shared with the feature pass (rt_aov.hip): the camera part of the launch
+// parameters (rt_path.h Params: image plane, sample grid, rank, seed, the width and
+// spp_sqrt fast divisions), and the rows of an H-row image that `rank` of `nranks` renders
+struct Params;
+void set_camera_params(Params& p, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t npix);
+uint32_t rank_rows(uint32_t H, int rank, int nranks);
 
 // Grow-only device scratch, one buffer per device ordinal (as rt_output.hip's): no allocation
 // per call once warm.  The caller serialises its users, and no work that reads an old buffer

@@ -150,6 +150,27 @@ int build_bvh8(HostScene& s);
 // (rt_device.h "compressed BVH4 node"); *n_items = 0 when the tree is not encodable
 int build_qbvh(const HostScene& s, const std::vector<F4>& recs, std::vector<F4>* out,
                size_t* n_items);
+// host_records.cpp: the traversal's leaf records (rt_device.h "leaf records") in refs order,
+// one record, and the light table's entries
+void make_record(const HostScene& h, uint32_t ref, F4* r);
+void build_leaf_records(const HostScene& h, std::vector<F4>& recs);
+void build_light_records(const HostScene& h, std::vector<F4>& recs);
+// host_records.cpp: s.mats with the per-material "texture reads u,v" flag in the pad
+std::vector<DevMaterial> materials_with_uv_flag(const HostScene& h);
+// host_records.cpp: the scene is small enough for the BVH2 and the record-loop pairs to be
+// uploaded (RT_BRUTE_MAX, at least 64 leaf entries)
+bool tiny_scene(const HostScene& h);
+// host_records.cpp: the record loop's pair array (rt_device.h "record-loop pair layout") of a
+// tiny scene, as upload_scene copies it to the device; empty (n_slots = 0) for any other
+struct RecordPack {
+  std::vector<F4> pairs;  // 4 F4 per slot, then the lean kernel's shade table (shade_n F4)
+  size_t n_slots = 0;     // records in pairs, pads included (even)
+  int32_t shade_n = 0;    // F4s of the shade table after the pairs (0: none)
+  int32_t n_boxes = 0;    // boxes among the records tested as slabs (rt_path.h brute_box)
+  BruteCounts counts{};   // the layout's group counts (DevScene brute_*)
+  int shape = 0;          // brute_shape_of(counts)
+};
+RecordPack pack_records(const HostScene& h);
 // rt_build.hip: the same outputs as build_bvh, built by PLOC on `device` (-1: the calling
 // thread's current device; the current device is restored on return)
 int build_bvh_device(HostScene& s, const std::vector<F4>& lo, const std::vector<F4>& hi,

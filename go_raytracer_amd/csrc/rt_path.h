@@ -14,7 +14,6 @@ constexpr int kLdsWMax = 6;      // clamp-weight stack entries per lane kept in 
 constexpr int kStack = 64;       // traversal stack entries per lane (LDS short stack + HBM overflow)
 constexpr int kShortStack = 12;  // LDS entries per lane (column layout: [entry][thread])
 constexpr int kShortStackMin = 6;  // smallest short stack of any kernel (fused lean set)
-constexpr int kBruteMax = 48;      // scenes up to this many leaf entries skip the tree (fused)
 constexpr int kMaxIt = 1 << 16;  // per-iteration counter slots (no per-iteration memsets)
 constexpr int kXcd = 8;          // queue counters are sharded per XCD (blockIdx % 8)
 constexpr int kMaxParts = 64;    // chunk-range partitions of the fused kernel (one counter each)

@@ -30,7 +30,7 @@
 
 #include <rccl/rccl.h>
 
-#include "rt_internal.h"
+#include "rt_hip_util.h"
 #include "rt_path.h"
 #include "rt_fused.h"
 
@@ -192,13 +192,6 @@ __global__ __launch_bounds__(256) void k_resolve(Params P, float* out, double sc
 }
 
 // ==================================================================== host ==
-#define HIP_OK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess)                                                               \
-      return set_error(RT_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(_e));   \
-  } while (0)
-
 struct DeviceScene {
   int device = -1;
   std::vector<void*> allocs;
@@ -253,18 +246,6 @@ struct RenderState {
     for (auto e : events) (void)hipEventDestroy(e);
     for (auto e : prog_events) (void)hipEventDestroy(e);
     if (own_stream) (void)hipStreamDestroy(own_stream);
-  }
-};
-
-// Restores the calling thread's current device on scope exit: every ABI entry that
-// switches devices leaves the caller's (e.g. torch's) current device as it found it.
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
   }
 };
 
@@ -340,7 +321,7 @@ static int upload(DeviceScene* ds, const std::vector<T>& v, const T** out) {
 static int env_int(const char* name, int dflt) { return tune_int(name, dflt); }
 
 
-FastDiv make_fastdiv(uint32_t d) {  // (also rt_aov.hip)
+FastDiv make_fastdiv(uint32_t d) {
   FastDiv f{1u, 0u, 0u, d};
   if (d <= 1) return f;  // d == 1: t = 0, q = n
   const uint32_t l = 32u - (uint32_t)__builtin_clz(d - 1u);
@@ -348,59 +329,6 @@ FastDiv make_fastdiv(uint32_t d) {  // (also rt_aov.hip)
   f.s1 = 1u;
   f.s2 = l - 1u;
   return f;
-}
-
-// the traversal's leaf records (rt_device.h "leaf records"), in refs order
-static void make_record(const HostScene& h, uint32_t ref, F4* r);
-static void build_leaf_records(const HostScene& h, std::vector<F4>& recs) {
-  recs.assign(4 * h.refs.size(), F4{0, 0, 0, 0});
-  for (size_t i = 0; i < h.refs.size(); ++i) make_record(h, h.refs[i], &recs[4 * i]);
-}
-// light table entries: quad lights as leaf records with the area in [2].w (prim_pdf)
-static void build_light_records(const HostScene& h, std::vector<F4>& recs) {
-  recs.assign(8 * std::max<size_t>(h.lights.size(), 1), F4{0, 0, 0, 0});
-  for (size_t i = 0; i < h.lights.size(); ++i) {
-    const uint32_t ref = h.lights[i].ref;
-    if (ref == PRIM_NONE || (ref >> 30) != PRIM_QUAD) continue;
-    make_record(h, ref, &recs[8 * i]);
-    const F4* q = &h.quad[5 * (size_t)(ref & 0x3FFFFFFFu)];  // Q|D, u|area, v|mat, n, w
-    recs[8 * i + 2].w = q[1].w;                                // area
-    recs[8 * i + 4] = q[0];
-    recs[8 * i + 5] = q[1];
-    recs[8 * i + 6] = q[2];
-  }
-}
-static void make_record(const HostScene& h, uint32_t ref, F4* r) {
-  {
-    const uint32_t type = ref >> 30, idx = ref & 0x3FFFFFFFu;
-    float rb;
-    memcpy(&rb, &ref, 4);
-    if (type == PRIM_SPHERE) {
-      const F4 cr = h.sph_cr[idx], mv = h.sph_mv[idx];
-      r[0] = {cr.x, cr.y, cr.z, rb};
-      r[1] = {mv.x, mv.y, mv.z, cr.w};
-    } else if (type == PRIM_BOX) {  // box leaf (rt_device.h), built by the flattener
-      for (int k = 0; k < 4; ++k) r[k] = h.box_recs[4 * (size_t)idx + k];
-      r[0].w = rb;
-    } else if (type == PRIM_QUAD) {
-      const F4* q = &h.quad[5 * (size_t)idx];  // Q|D, u|area, v|mat, n, w
-      const double u[3] = {q[1].x, q[1].y, q[1].z}, v[3] = {q[2].x, q[2].y, q[2].z},
-                   w[3] = {q[4].x, q[4].y, q[4].z};
-      auto cr = [](const double* a, const double* b, int k) {
-        return k == 0 ? a[1] * b[2] - a[2] * b[1] : k == 1 ? a[2] * b[0] - a[0] * b[2]
-                                                           : a[0] * b[1] - a[1] * b[0];
-      };
-      r[0] = {q[0].x, q[0].y, q[0].z, rb};
-      r[1] = {q[3].x, q[3].y, q[3].z, q[0].w};
-      r[2] = {(float)cr(v, w, 0), (float)cr(v, w, 1), (float)cr(v, w, 2), 0.0f};
-      r[3] = {(float)cr(w, u, 0), (float)cr(w, u, 1), (float)cr(w, u, 2), 0.0f};
-    } else {
-      const F4* t = &h.tri[3 * (size_t)idx];  // v0|mat, e0|area, e1|flags
-      r[0] = {t[0].x, t[0].y, t[0].z, rb};
-      r[1] = {t[1].x, t[1].y, t[1].z, 0.0f};
-      r[2] = {t[2].x, t[2].y, t[2].z, 0.0f};
-    }
-  }
 }
 
 // the scene's device copy on `device` (uploaded on first use, then shared by every
@@ -439,25 +367,7 @@ static int ensure_scene(Scene* s, int device, DeviceScene** out) {
 static int upload_scene(const Scene* s, DeviceScene* ds) {
   const HostScene& h = s->h;
   DevScene& d = ds->d;
-  // per-material "texture reads u,v" flag for sphere UV (stored in the pad)
-  std::vector<DevMaterial> mats = h.mats;
-  for (auto& m : mats) {
-    bool needs = false;
-    std::vector<int> st;
-    if (m.kind != RT_MAT_METAL && m.kind != RT_MAT_DIELECTRIC && m.tex >= 0) st.push_back(m.tex);
-    int guard = 0;
-    while (!st.empty() && guard++ < 4096) {
-      int tx = st.back();
-      st.pop_back();
-      const DevTexture& T = h.texs[tx];
-      if (T.kind == RT_TEX_IMAGE) needs = true;
-      if (T.kind == RT_TEX_CHECKER) {
-        st.push_back(T.a);
-        st.push_back(T.b);
-      }
-    }
-    m._pad = needs ? 1.0f : 0.0f;
-  }
+  const std::vector<DevMaterial> mats = materials_with_uv_flag(h);
   int rc;
 #define UP(vec, field)                                      \
   if ((rc = upload(ds, vec, &d.field)) != RT_OK) return rc;
@@ -484,10 +394,7 @@ static int upload_scene(const Scene* s, DeviceScene* ds) {
     d.leafprims = base ? base + rec0 : nullptr;
   }
   // (the compressed BVH4 is built and uploaded on demand: ensure_qbvh)
-  // the BVH2 and the record-loop pairs serve tiny scenes only (render_impl's tree
-  // choice: <= 64 leaf entries); a 1M-triangle scene would upload 64 MB of BVH2
-  const size_t tiny = (size_t)std::max(64, env_int("RT_BRUTE_MAX", kBruteMax));
-  const bool small = h.refs.size() <= tiny;
+  const bool small = tiny_scene(h);  // the BVH2 and the record-loop pairs: tiny scenes only
   if (small && (rc = upload(ds, h.nodes, &ds->nodes2)) != RT_OK) return rc;
   ds->root2 = h.root;
   ds->n_nodes2 = small ? (int32_t)(h.nodes.size() / 4) : 0;
@@ -502,281 +409,20 @@ static int upload_scene(const Scene* s, DeviceScene* ds) {
     }
     build_light_records(h, lrecs);
     UP(lrecs, light_recs);
-    if (!small) goto records_done;
-    // record-loop order: largest surface first, so the closest hit tends to be found
-    // early and later records fail the interval test before their slower half
-    std::vector<size_t> ord(h.refs.size());
-    for (size_t i = 0; i < ord.size(); ++i) ord[i] = i;
-    auto area = [&](uint32_t ref) -> double {
-      const uint32_t type = ref >> 30, idx = ref & 0x3FFFFFFFu;
-      if (type == PRIM_QUAD) return h.quad[5 * (size_t)idx + 1].w;
-      if (type == PRIM_TRI) return h.tri[3 * (size_t)idx + 1].w;
-      const double r = h.sph_cr[idx].w;
-      return 4.0 * 3.141592653589793 * r * r;
-    };
-    std::stable_sort(ord.begin(), ord.end(),
-                     [&](size_t a, size_t b) { return area(h.refs[a]) > area(h.refs[b]); });
-    // Axis-aligned quads (unit normal +-e_a, A_a = B_a = 0 exactly: Cornell's walls,
-    // floor, ceiling and box tops) go in per-axis pair groups after the general
-    // pairs; the loop tests them with the in-plane terms only, bit-identical to the
-    // general test (rt_path.h brute_axis).  An odd record of a group joins the
-    // general list.  RT_BRUTE_AXIS=0 keeps every record general (A/B).
-    const bool use_axis = env_int("RT_BRUTE_AXIS", 1) != 0;
-    auto axis_of = [&](size_t i) -> int {
-      const F4* r = &recs[4 * i];
-      if (!use_axis || (h.refs[i] >> 30) != PRIM_QUAD) return -1;
-      const float n[3] = {r[1].x, r[1].y, r[1].z}, A[3] = {r[2].x, r[2].y, r[2].z},
-                  B[3] = {r[3].x, r[3].y, r[3].z};
-      for (int a = 0; a < 3; ++a) {
-        const int b = (a + 1) % 3, c = (a + 2) % 3;
-        if ((n[a] == 1.0f || n[a] == -1.0f) && n[b] == 0.0f && n[c] == 0.0f && A[a] == 0.0f &&
-            B[a] == 0.0f)
-          return a;
-      }
-      return -1;
-    };
-    // y-parallel quads (n_y = A_y = 0 and B = (0, B_y, 0) exactly: the sides of Cornell's
-    // boxes rotated about y) go in a pair group between the general and the axis-aligned
-    // ones (rt_path.h brute_vert: the general test without its exact-zero terms, images
-    // bit-identical; C2 -1.6 % against RT_BRUTE_VERT=0, which keeps them general).
-    const bool use_vert = env_int("RT_BRUTE_VERT", 1) != 0;
-    auto vert_of = [&](size_t i) -> int {
-      const F4* r = &recs[4 * i];
-      if (!use_vert || (h.refs[i] >> 30) != PRIM_QUAD || axis_of(i) >= 0) return -1;
-      const float n[3] = {r[1].x, r[1].y, r[1].z}, A[3] = {r[2].x, r[2].y, r[2].z},
-                  B[3] = {r[3].x, r[3].y, r[3].z};
-      // y only (brute_vert<1>): RotateY is the reference's only rotation
-      return n[1] == 0.0f && A[1] == 0.0f && B[0] == 0.0f && B[2] == 0.0f && B[1] != 0.0f ? 1 : -1;
-    };
-    // Boxes rotated about y (NewBox objects.go:208-240 under RotateY / Translate,
-    // transformation.go:13-110; Cornell's two boxes): six quad records whose corners are
-    // the eight corners of one box with a horizontal top and bottom.  The loop tests each
-    // such box once, as three slabs in the box's own frame -- the reference's rotateY.Hit
-    // frame, where each face's quad test is t = (k - o'_a) / d'_a -- instead of its six
-    // records (rt_path.h brute_box).  The face records stay in the array (after the box
-    // descriptors) for the winner's u, v and ref.  RT_BRUTE_BOX=0 keeps them in the groups.
-    struct BoxRec { size_t face[6]; double C[3], ax[3], az[3], H; };
-    std::vector<BoxRec> boxes;
-    std::vector<char> in_box(h.refs.size(), 0);
-    if (env_int("RT_BRUTE_BOX", 1) != 0) {
-      auto qd = [&](size_t i, int k, double* out) {  // k: 0 Q, 1 u, 2 v
-        const F4& f = h.quad[5 * (size_t)(h.refs[i] & 0x3FFFFFFFu) + k];
-        out[0] = f.x, out[1] = f.y, out[2] = f.z;
-      };
-      auto corners = [&](size_t i, double P[4][3]) {
-        double Q[3], u[3], v[3];
-        qd(i, 0, Q), qd(i, 1, u), qd(i, 2, v);
-        for (int c = 0; c < 3; ++c) {
-          P[0][c] = Q[c], P[1][c] = Q[c] + u[c], P[2][c] = Q[c] + v[c];
-          P[3][c] = Q[c] + u[c] + v[c];
-        }
-      };
-      std::vector<size_t> quads;
-      for (size_t i : ord)
-        if ((h.refs[i] >> 30) == PRIM_QUAD) quads.push_back(i);
-      // four corners of quad i == the four points F (as sets, within tol)
-      auto same_face = [&](size_t i, const double F[4][3], double tol) {
-        double P[4][3];
-        corners(i, P);
-        bool used[4] = {false, false, false, false};
-        for (int a = 0; a < 4; ++a) {
-          int m = -1;
-          for (int b = 0; b < 4 && m < 0; ++b)
-            if (!used[b] && fabs(P[a][0] - F[b][0]) <= tol && fabs(P[a][1] - F[b][1]) <= tol &&
-                fabs(P[a][2] - F[b][2]) <= tol)
-              m = b;
-          if (m < 0) return false;
-          used[m] = true;
-        }
-        return true;
-      };
-      for (size_t i : quads) {
-        if (in_box[i]) continue;
-        double C[3], ax[3], az[3];
-        qd(i, 0, C), qd(i, 1, ax), qd(i, 2, az);
-        const double la = sqrt(ax[0] * ax[0] + ax[2] * ax[2]), lb = sqrt(az[0] * az[0] + az[2] * az[2]);
-        // a horizontal rectangle: the bottom (or top) face of a candidate box
-        if (ax[1] != 0.0 || az[1] != 0.0 || la == 0.0 || lb == 0.0 ||
-            fabs(ax[0] * az[0] + ax[2] * az[2]) > 1e-6 * la * lb)
-          continue;
-        const double tol = 1e-5 * (1.0 + fabs(C[0]) + fabs(C[1]) + fabs(C[2]) + la + lb);
-        auto corner = [&](int k, double H, double* out) {  // bit 0: +ax, 1: +az, 2: +H
-          for (int c = 0; c < 3; ++c)
-            out[c] = C[c] + ((k & 1) ? ax[c] : 0.0) + ((k & 2) ? az[c] : 0.0) + (c == 1 && (k & 4) ? H : 0.0);
-        };
-        // faces by (axis, side): x' = bit 0, y = bit 2, z' = bit 1
-        const int fbit[3] = {1, 4, 2};
-        for (size_t j : quads) {
-          if (j == i || in_box[j]) continue;
-          double Qj[3];
-          qd(j, 0, Qj);
-          const double H = Qj[1] - C[1];
-          if (fabs(H) <= tol) continue;
-          BoxRec b{};
-          bool ok = true;
-          for (int f = 0; f < 6 && ok; ++f) {
-            double F[4][3];
-            int n = 0;
-            for (int k = 0; k < 8; ++k)
-              if (((k & fbit[f >> 1]) != 0) == (f & 1)) corner(k, H, F[n++]);
-            size_t hit = (size_t)-1;
-            if (f == 2) hit = i;
-            else if (f == 3) hit = same_face(j, F, tol) ? j : (size_t)-1;
-            else
-              for (size_t m : quads)
-                if (m != i && m != j && !in_box[m] && same_face(m, F, tol)) {
-                  bool dup = false;
-                  for (int g = 0; g < f; ++g) dup |= b.face[g] == m;
-                  if (!dup) { hit = m; break; }
-                }
-            if (hit == (size_t)-1) ok = false;
-            else b.face[f] = hit;
-          }
-          if (!ok) continue;
-          for (int c = 0; c < 3; ++c) b.C[c] = C[c], b.ax[c] = ax[c], b.az[c] = az[c];
-          b.H = H;
-          for (int f = 0; f < 6; ++f) in_box[b.face[f]] = 1;
-          boxes.push_back(b);
-          break;
-        }
-      }
-    }
-    std::vector<size_t> grp[7];  // 0-2: axis-aligned groups, 3: general, 4-6: axis-parallel
-    for (size_t i : ord) {
-      if (in_box[i]) continue;
-      const int a = axis_of(i);
-      const int v = a < 0 ? vert_of(i) : -1;
-      grp[a >= 0 ? a : v >= 0 ? 4 + v : 3].push_back(i);
-    }
-    // The odd records of two axis-aligned groups of different axes form one mixed pair, each
-    // half tested on its own axis (rt_path.h brute_mixed: the axis test, bit for bit, ~35 VALU
-    // where the general pair was ~85; Cornell's light and back wall).  Any other odd record
-    // joins the general list.  (Padding each odd group with a never-hit record instead measured
-    // 2.5 % slower on C2: one more loop and its per-axis setup.)  RT_BRUTE_MIXED=0: no mixed pair.
-    std::vector<std::pair<int, size_t>> odd_ax;  // (axis, record)
-    for (int a : {0, 1, 2, 4, 5, 6})
-      if (grp[a].size() & 1) {
-        if (a < 3 && env_int("RT_BRUTE_MIXED", 1) != 0) odd_ax.push_back({a, grp[a].back()});
-        else grp[3].push_back(grp[a].back());  // the group's smallest record
-        grp[a].pop_back();
-      }
-    if (odd_ax.size() == 3) {  // the third joins the general list
-      grp[3].push_back(odd_ax.back().second);
-      odd_ax.pop_back();
-    }
-    if (odd_ax.size() == 1) {
-      grp[3].push_back(odd_ax.back().second);
-      odd_ax.clear();
-    }
-    std::stable_sort(grp[3].begin(), grp[3].end(),
-                     [&](size_t a, size_t b) { return area(h.refs[a]) > area(h.refs[b]); });
-    std::vector<long> slots;  // record per slot in loop order, -1 = pad
-    for (size_t i : grp[3]) slots.push_back((long)i);
-    if (slots.size() & 1) slots.push_back(-1);
-    d.brute_ng = (int32_t)(slots.size() / 2);
-    for (int a = 0; a < 3; ++a) {
-      for (size_t i : grp[4 + a]) slots.push_back((long)i);
-      d.brute_vt[a] = (int32_t)(grp[4 + a].size() / 2);
-    }
-    const size_t n_general = slots.size();  // general and axis-parallel: the stored D
-    for (int a = 0; a < 3; ++a) {
-      for (size_t i : grp[a]) slots.push_back((long)i);
-      d.brute_ax[a] = (int32_t)(grp[a].size() / 2);
-    }
-    d.brute_mx = 0;  // the mixed pair (axes a0 < a1): (a0 + 1) | (a1 + 1) << 2
-    if (odd_ax.size() == 2) {
-      slots.push_back((long)odd_ax[0].second);  // odd_ax is in axis order (0, 1, 2 above)
-      slots.push_back((long)odd_ax[1].second);
-      d.brute_mx = (odd_ax[0].first + 1) | ((odd_ax[1].first + 1) << 2);
-    }
-    const size_t n_loop = slots.size();  // records the loop tests one by one
-    // box descriptors, two per pair slot (an odd box count repeats the last box: the
-    // same t and faces, so the winner is unchanged), then the six face records per box
-    const size_t nbp = (boxes.size() + 1) / 2;
-    d.brute_box = (int32_t)nbp;
-    ds->brute_boxes = (int32_t)boxes.size();
-    slots.insert(slots.end(), 2 * nbp, -2);
-    const size_t face0 = slots.size();
-    for (const BoxRec& b : boxes)
-      for (int f = 0; f < 6; ++f) slots.push_back((long)b.face[f]);
-    if (slots.empty()) {
-      slots.assign(2, -1);
-      d.brute_ng = 1;
-    }
-    // pair layout (rt_device.h): records 2p, 2p+1 interleaved field by field
-    std::vector<F4> pairs(4 * slots.size(), F4{0, 0, 0, 0});  // pad: n = 0, never hit
-    for (size_t k = 0; k < 2 * nbp; ++k) {
-      // rt_path.h brute_box: C.x, C.z, ax/|ax|^2 (x, z), az/|az|^2 (x, z), y range, faces
-      const BoxRec& b = boxes[std::min(k, boxes.size() - 1)];
-      float* f = (float*)&pairs[4 * (n_loop + k - (k & 1))] + (k & 1);
-      const double a2 = b.ax[0] * b.ax[0] + b.ax[2] * b.ax[2], z2 = b.az[0] * b.az[0] + b.az[2] * b.az[2];
-      const double y0 = b.C[1], y1 = b.C[1] + b.H;
-      const float v[8] = {(float)b.C[0], (float)b.C[2], (float)(b.ax[0] / a2), (float)(b.ax[2] / a2),
-                          (float)(b.az[0] / z2), (float)(b.az[2] / z2), (float)std::min(y0, y1),
-                          (float)std::max(y0, y1)};
-      for (int e = 0; e < 8; ++e) f[2 * e] = v[e];
-      for (int fc = 0; fc < 6; ++fc) {
-        // face slot by (axis x' / y / z', low / high side); y's low side is the lower face
-        const int src = (fc >> 1) == 1 && b.H < 0 ? (fc ^ 1) : fc;
-        const uint32_t slot = (uint32_t)(face0 + 6 * std::min(k, boxes.size() - 1) + src);
-        memcpy(&f[2 * (8 + fc)], &slot, 4);
-      }
-    }
-    for (size_t i = 0; i < slots.size(); ++i) {
-      if (slots[i] < 0) continue;
-      const F4* r = &recs[4 * (size_t)slots[i]];  // Q|ref, n|D, A, B
-      float* f = (float*)&pairs[8 * (i / 2)] + (i & 1);
-      float kb;
-      const uint32_t k = (uint32_t)i;
-      memcpy(&kb, &k, 4);
-      // axis records: D / n_a (= +-D exactly) in the D slot, so t = (D' - o_a) / d_a
-      const int a = i >= n_general && i < n_loop ? axis_of((size_t)slots[i]) : -1;
-      const float na = a == 0 ? r[1].x : a == 1 ? r[1].y : r[1].z;
-      const float Dp = a < 0 ? r[1].w : na * r[1].w;
-      const float v[15] = {r[1].x, r[1].y, r[1].z, Dp,     r[0].x, r[0].y, r[0].z, r[2].x,
-                           r[2].y, r[2].z, r[3].x, r[3].y, r[3].z, kb,     r[0].w};
-      for (int e = 0; e < 15; ++e) f[2 * e] = v[e];
-    }
-    {
-      const BruteCounts bc = {d.brute_ng, d.brute_vt[1], {d.brute_ax[0], d.brute_ax[1], d.brute_ax[2]},
-                              d.brute_mx, d.brute_box};
-      ds->brute_shape = brute_shape_of(bc);
-    }
-    ds->brute_slots = slots.size();
-    // The lean set's shade table, after the pairs: per quad its normal and material kind,
-    // and its texture's solid colour (2 F4), so the record-loop kernel shades from LDS
-    // instead of three dependent global loads (quad, material, texture) per vertex, whose
-    // s_waitcnt vmcnt(0) also waited for the chunk flushes' pixel atomics
-    // (profiles/r4_phases_flush_c2.jsonl).  Only when every quad's material is Lambertian
-    // or a diffuse light with a solid texture (what the lean kernel shades).
-    {
-      const size_t nq = h.quad.size() / 5;
-      std::vector<F4> tab(2 * nq);
-      bool ok = nq > 0;
-      for (size_t qi = 0; qi < nq && ok; ++qi) {
-        const F4* q = &h.quad[5 * qi];
-        uint32_t mb;
-        memcpy(&mb, &q[2].w, 4);
-        ok = mb < mats.size();
-        if (!ok) break;
-        const DevMaterial& m = mats[mb];
-        ok = (m.kind == RT_MAT_LAMBERTIAN || m.kind == RT_MAT_DIFFUSE_LIGHT) && m.tex >= 0 &&
-             (size_t)m.tex < h.texs.size() && h.texs[m.tex].kind == RT_TEX_SOLID;
-        if (!ok) break;
-        float kb;
-        const uint32_t kind = (uint32_t)m.kind;
-        memcpy(&kb, &kind, 4);
-        tab[2 * qi] = {q[3].x, q[3].y, q[3].z, kb};
-        // the colour, and the plane offset D (shade_core puts the hit point on the plane)
-        const F4 col = h.texs[m.tex].color;
-        tab[2 * qi + 1] = {col.x, col.y, col.z, q[0].w};
-      }
-      ds->shade_n = ok && env_int("RT_SHADE_LDS", 1) != 0 ? (int32_t)tab.size() : 0;
-      if (ds->shade_n) pairs.insert(pairs.end(), tab.begin(), tab.end());
-    }
-    if ((rc = upload(ds, pairs, &ds->brute_pairs)) != RT_OK) return rc;
   }
-records_done:
+  if (small) {  // the record loop's pairs (host_records.cpp), packed once per device upload
+    const RecordPack rp = pack_records(h);
+    d.brute_ng = rp.counts.ng;
+    d.brute_vt[1] = rp.counts.vy;
+    for (int a = 0; a < 3; ++a) d.brute_ax[a] = rp.counts.ax[a];
+    d.brute_mx = rp.counts.mx;
+    d.brute_box = rp.counts.box;
+    ds->brute_slots = rp.n_slots;
+    ds->shade_n = rp.shade_n;
+    ds->brute_boxes = rp.n_boxes;
+    ds->brute_shape = rp.shape;
+    if ((rc = upload(ds, rp.pairs, &ds->brute_pairs)) != RT_OK) return rc;
+  }
   UP(h.media, media);
   UP(h.medium_refs, medium_refs);
   {  // spheres tested before the BVH (host_flatten: radius >= kBigSphereR), as leaf records
@@ -857,6 +503,65 @@ static int ensure_state(SlotState* slot, int device, uint32_t P, int depth_cap, 
        (rc = dalloc(st, &st->path, P)) || (rc = dalloc(st, &st->queue[0], (size_t)kXcd * P)) ||
        (rc = dalloc(st, &st->queue[1], (size_t)kXcd * P))))
     return rc;
+  return RT_OK;
+}
+
+// frees one of st's buffers (a grow-on-demand buffer about to be replaced or dropped)
+template <typename T>
+static int dfree(RenderState* st, T** p) {
+  if (!*p) return RT_OK;
+  HIP_OK(hipFree(*p));
+  st->allocs.erase(std::find(st->allocs.begin(), st->allocs.end(), (void*)*p));
+  *p = nullptr;
+  return RT_OK;
+}
+
+// traversal-stack overflow columns: one per launched traversal thread
+static int ensure_ostack(RenderState* st, uint32_t cols) {
+  if (st->ostack_cols >= cols) return RT_OK;
+  int rc;
+  if ((rc = dfree(st, &st->ostack))) return rc;
+  if ((rc = dalloc(st, &st->ostack, (size_t)(kStack - kShortStackMin) * cols))) return rc;
+  st->ostack_cols = cols;
+  return RT_OK;
+}
+
+// *use_csum in: the render wants the chunk sums; out: it has them (st->csum)
+static int ensure_csum(RenderState* st, uint32_t n_chunks, bool* use_csum_io) {
+  int rc;
+  bool use_csum = *use_csum_io;
+  // fused: the per-chunk sums (32 B per chunk, every record stored once per render: no clear).
+  // The buffer grows with the sample count, not the image: above its cap (RT_CSUM_MAX_MB,
+  // default 16 GiB, and at most half of the device's free memory) or when it cannot be
+  // allocated, the render falls back to pixel atomics (P.csum == nullptr: the same integer
+  // sums, so the same image; rt_stats.chunk_records = 0).  A buffer more than 4x larger than
+  // this render needs (and over 256 MiB) is released first.
+  {
+    const size_t need_b = 32 * (size_t)n_chunks;
+    auto drop_csum = [&]() -> int {
+      st->csum_chunks = 0;
+      return dfree(st, &st->csum);
+    };
+    if (st->csum && (!use_csum || (st->csum_chunks > 4 * (size_t)n_chunks &&
+                                   32 * st->csum_chunks > ((size_t)256 << 20))))
+      if ((rc = drop_csum())) return rc;
+    if (use_csum && st->csum_chunks < n_chunks) {
+      if ((rc = drop_csum())) return rc;
+      size_t free_b = 0, total_b = 0;
+      const size_t cap_b = (size_t)std::max(0, env_int("RT_CSUM_MAX_MB", 16384)) << 20;
+      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+      void* q = nullptr;
+      if (need_b <= cap_b && need_b <= free_b / 2 && hipMalloc(&q, std::max<size_t>(need_b, 32)) == hipSuccess) {
+        st->allocs.push_back(q);
+        st->csum = (unsigned long long*)q;
+        st->csum_chunks = n_chunks;
+      } else {
+        (void)hipGetLastError();  // a failed allocation is not sticky: pixel atomics instead
+        use_csum = false;
+      }
+    }
+  }
+  *use_csum_io = use_csum;
   return RT_OK;
 }
 
@@ -995,86 +700,20 @@ static bool wants_qbvh(uint32_t ft_set) {
   return env_int("RT_QBVH", 1) != 0 && pick_fused(false, ft_set, 5) != nullptr;
 }
 
-// The feature pass's view of the scene (rt_internal.h AovView, rt_aov.hip): the tree a fused
-// render of it takes (fused_base_tree, then the compressed BVH4 as render_impl), and the
-// DevScene set up for it as render_impl sets up Params::sc.  The BVH8 of RT_BVH8_KERNELS
-// builds is not taken: those scenes' BVH4 (or its compressed form) finds the same hits.
-int aov_view(Scene* s, int device, AovView* out) {
-  DeviceScene* ds = nullptr;
-  int rc = ensure_scene(s, device, &ds);
-  if (rc) return rc;
-  const uint32_t ft_set = scene_ft_set(s);
-  int tree = fused_base_tree(s, ft_set);
-  if (tree == 0 && !ds->brute_pairs) tree = 4;  // (records not uploaded: RT_BRUTE_MAX raised since)
-  if (tree == 2 && !ds->nodes2) tree = 4;
-  const bool f_lds = tree != 4 || 2 * (s->h.nodes4.size() / 8) <= fused_lds_slots(ft_set, 4);
-  if (tree == 4 && !f_lds && wants_qbvh(ft_set)) {
-    if ((rc = ensure_qbvh(s, ds))) return rc;
-    if (ds->qnodes) tree = 5;
-  }
-  out->sc = ds->d;
-  out->tree = tree;
-  if (tree == 2) {
-    out->sc.nodes = ds->nodes2;
-    out->sc.root = ds->root2;
-    out->sc.n_nodes = ds->n_nodes2;
-  } else if (tree == 5) {
-    out->sc.nodes = ds->qnodes;
-    out->sc.root = 0;
-    out->sc.n_nodes = (int32_t)std::min<size_t>(ds->qitems, 0x7FFFFFFF);
-  } else if (tree == 0) {
-    out->sc.n_nodes = 0;
-    out->sc.leafprims = ds->brute_pairs;
-    out->sc.n_refs = (int32_t)ds->brute_slots;
-  }
-  return RT_OK;
-}
-
-static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
-                       float* out_host, float* out_dev, rt_stats* stats, int slot_id = 0,
-                       const Gather* gather = nullptr) {
-  if (!scene || !cam) return set_error(RT_ERR_INVALID, "rt_render: null scene/camera");
-  rt_render_opts o{};
-  if (opts) o = *opts;
-  if (o.nranks <= 0) o.nranks = 1;
-  if (o.rank < 0 || o.rank >= o.nranks) return set_error(RT_ERR_INVALID, "rt_render: bad rank");
-  rt_camera_derived cd;
-  int rc = rt_camera_derive(cam, &cd);
-  if (rc) return rc;
-  auto t_start = std::chrono::steady_clock::now();
-  const int32_t tuned = tune_count();  // rt_stats.tuned: knobs off their defaults
-
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return set_error(RT_ERR_DEVICE, "rt_render: no HIP device available");
-  if (o.device < 0 || o.device >= ndev)
-    return set_error(RT_ERR_INVALID, "rt_render: device %d of %d", o.device, ndev);
-  DeviceGuard dg;  // the caller's current device is restored on every return
-  HIP_OK(hipSetDevice(o.device));
-  Scene* s = &scene->s;
-  DeviceScene* ds = nullptr;
-  if ((rc = ensure_scene(s, o.device, &ds))) return rc;
-  SlotState* slot = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(s->mu);
-    SlotState*& sl = s->slots[{o.device, slot_id}];
-    if (!sl) sl = new SlotState();
-    slot = sl;
-  }
-  std::lock_guard<std::mutex> inflight(slot->mu);  // one render per (scene, device, slot)
-
-  const uint32_t W = (uint32_t)cd.width, H = (uint32_t)cd.height;
-  const uint32_t rows = H > (uint32_t)o.rank ? (H - (uint32_t)o.rank + o.nranks - 1) / o.nranks : 0;
-  const uint32_t npix = rows * W;
-  const uint32_t ss = (uint32_t)cd.spp_sqrt * (uint32_t)cd.spp_sqrt;
-  int mode = o.mode;
-  if (mode != RT_MODE_WAVEFRONT && mode != RT_MODE_FUSED) mode = RT_MODE_FUSED;
-  const int depth_cap = cd.max_depth + 1;
-  uint32_t P;
-  int fused_blocks = 0;
-  const bool lds_nodes = s->h.nodes4.size() / 8 <= (size_t)kLdsNodes / 2;
-  const uint32_t feats = s->h.features;
-  const uint32_t ft_set = scene_ft_set(s);
+// What a render of the scene traverses and the fused kernel that does it: one decision for
+// render_impl and the feature pass (aov_view), which ignores what it does not need.
+struct StructurePlan {
+  int tree;          // 0 record loop, 2 BVH2, 4 BVH4, 8 BVH8 (5, the compressed BVH4: take_qbvh)
+  bool f_lds;        // the tree's nodes (tree 0: the records) are staged in LDS
+  bool f_recs;       // ... and the leaf records after them
+  bool shade_tab;    // the lean kernel's shade table goes with the record pairs
+  int shape;         // the record layout the kernel is compiled for (rt_device.h brute_shape), 0 = any
+  const void* kernel;
+  size_t lds_bytes;  // dynamic LDS of the kernel
+  bool wants_qbvh;   // a BVH4 read through L1/L2 whose set has a compressed-BVH4 kernel
+};
+static int plan_structure(const Scene* s, const DeviceScene* ds, uint32_t ft_set, int mode,
+                          StructurePlan* out) {
   // The fused kernel's LDS scene cache (stage_nodes): all BVH nodes, then the
   // leaf records when both fit, within the LDS a workgroup may take at the
   // kernel's target waves per SIMD (160 KB per CU, 24 KB of stacks per group).
@@ -1090,6 +729,8 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   // tree: 0 (no tree: every record tested, <= kBruteMax records in LDS), 2 or 4
   const int env_tree = env_int("RT_TREE", -1);
   int tree = mode == RT_MODE_FUSED ? fused_base_tree(s, ft_set) : 4;
+  if (tree == 0 && !ds->brute_pairs) tree = 4;  // (records not uploaded: RT_BRUTE_MAX raised since)
+  if (tree == 2 && !ds->nodes2) tree = 4;
   const size_t lds_slots = slots_for(tree);
   const size_t brute_slots = ds->brute_slots;  // record-loop pairs, 2 x 64 B each
   const int smem_env = env_int("RT_BRUTE_SMEM", -1);
@@ -1113,16 +754,9 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     return set_error(RT_ERR_UNSUPPORTED, "internal: record loop in LDS without its records");
   // Trees read through L1/L2 take the BVH8 (host_bvh8.cpp) when the scene has one (built
   // only with RT_BVH8=1) and a kernel exists for its feature set; RT_TREE=4 keeps the BVH4
-  if (mode == RT_MODE_FUSED && tree == 4 && !f_lds && !s->h.nodes8.empty() && env_tree != 4 &&
-      pick_fused(false, ft_set, 8))
-    tree = 8;
-  // Trees read through L1/L2 with single-prim leaves take the compressed BVH4 (64-B nodes,
-  // host_qbvh.cpp): the same closest hits, half the bytes per node step.  RT_QBVH=0: the
-  // 128-B nodes (A/B)
-  if (mode == RT_MODE_FUSED && tree == 4 && !f_lds && wants_qbvh(ft_set)) {
-    if ((rc = ensure_qbvh(s, ds))) return rc;
-    if (ds->qnodes) tree = 5;
-  }
+  const bool through_l2 = mode == RT_MODE_FUSED && tree == 4 && !f_lds;
+  out->wants_qbvh = through_l2 && wants_qbvh(ft_set);
+  if (through_l2 && !s->h.nodes8.empty() && env_tree != 4 && pick_fused(false, ft_set, 8)) tree = 8;
   // The lean LDS record loop compiled for the scene's record layout, when it is a listed one
   // (fixed at upload: the same for every render of the scene).  RT_BRUTE_SHAPE=0: the generic
   // kernel (A/B; the same hits bit for bit).
@@ -1130,17 +764,116 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
                                  ? ds->brute_shape : 0;
   const void* fused_kernel = pick_fused(f_lds, ft_set, tree, brute_shape_id);
   if (!fused_kernel) return set_error(RT_ERR_UNSUPPORTED, "internal: no fused kernel for this scene");
-#ifdef RT_QTOP
-  const size_t fused_lds = f_lds ? 64 * (node_slots * n_nodes + (f_recs ? rec_slots : 0))
-                           : tree == 5 ? 64 * std::min<size_t>(RT_QTOP, ds->qitems) : 0;
-#else
   const size_t fused_lds = f_lds ? 64 * (node_slots * n_nodes + (f_recs ? rec_slots : 0)) : 0;
+  out->tree = tree;
+  out->f_lds = f_lds;
+  out->f_recs = f_recs;
+  out->shade_tab = shade_tab;
+  out->shape = brute_shape_id;
+  out->kernel = fused_kernel;
+  out->lds_bytes = fused_lds;
+  return RT_OK;
+}
+// Trees read through L1/L2 with single-prim leaves take the compressed BVH4 (64-B nodes,
+// host_qbvh.cpp): the same closest hits, half the bytes per node step.  RT_QBVH=0: the
+// 128-B nodes (A/B)
+// The caller's step from "wants the compressed tree" (plan_structure, the tree still 4) to
+// "has it" (tree 5): nothing the LDS decisions depend on changes across it, f_lds is false
+// either way.
+static int take_qbvh(Scene* s, DeviceScene* ds, uint32_t ft_set, StructurePlan* sp) {
+  const int rc = ensure_qbvh(s, ds);
+  if (rc || !ds->qnodes) return rc;
+  sp->tree = 5;
+  sp->kernel = pick_fused(false, ft_set, 5);
+#ifdef RT_QTOP
+  sp->lds_bytes = 64 * std::min<size_t>(RT_QTOP, ds->qitems);
 #endif
-  if (mode == RT_MODE_FUSED) {
-    if ((rc = occupancy_blocks(fused_kernel, o.device, &fused_blocks, fused_lds))) return rc;
-    if (o.path_slots > 0) fused_blocks = std::max(1, std::min(fused_blocks, (o.path_slots + 255) / 256));
-    P = (uint32_t)fused_blocks * 256u;
+  return RT_OK;
+}
+
+// The DevScene a launch over `tree` reads: the scene's device copy with the tree's nodes and
+// records in place (render_impl adds the shade-table fields).
+static DevScene scene_for_tree(const DeviceScene* ds, int tree) {
+  DevScene sc = ds->d;
+  if (tree == 2) {
+    sc.nodes = ds->nodes2;
+    sc.root = ds->root2;
+    sc.n_nodes = ds->n_nodes2;
+  } else if (tree == 5) {
+    sc.nodes = ds->qnodes;
+    sc.root = 0;  // item 0: the root node (trav_init)
+    sc.n_nodes = (int32_t)std::min<size_t>(ds->qitems, 0x7FFFFFFF);  // 64-B items
+  } else if (tree == 8) {
+    sc.root = 0;  // BVH8 node 0 (trav_init)
+  } else if (tree == 0) {
+    sc.n_nodes = 0;  // records only (stage_nodes puts them at the start of the cache)
+    sc.leafprims = ds->brute_pairs;
+    sc.n_refs = (int32_t)ds->brute_slots;  // even: whole pairs
   }
+  return sc;
+}
+
+// The feature pass's view of the scene (rt_internal.h AovView, rt_aov.hip): the tree a fused
+// render of it takes and the DevScene set up for it as render_impl sets up Params::sc.
+// The BVH8 of RT_BVH8_KERNELS builds is not taken: those scenes' BVH4 (or its compressed
+// form) finds the same hits.
+int aov_view(Scene* s, int device, AovView* out) {
+  DeviceScene* ds = nullptr;
+  int rc = ensure_scene(s, device, &ds);
+  if (rc) return rc;
+  const uint32_t ft_set = scene_ft_set(s);
+  StructurePlan sp;
+  if ((rc = plan_structure(s, ds, ft_set, RT_MODE_FUSED, &sp))) return rc;
+  if (sp.tree == 8) sp.tree = 4;
+  if (sp.tree == 4 && sp.wants_qbvh && (rc = take_qbvh(s, ds, ft_set, &sp))) return rc;
+  out->sc = scene_for_tree(ds, sp.tree);
+  out->tree = sp.tree;
+  return RT_OK;
+}
+
+// The camera part of Params (the render's and the feature pass's): the image plane, the
+// sample grid, the rank's share of the rows and the seed.
+void set_camera_params(Params& p, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t npix) {
+  for (int i = 0; i < 3; ++i) {
+    p.p00r[i] = (float)(cd.pixel00[i] - cd.center[i]);
+    p.du[i] = (float)cd.delta_u[i];
+    p.dv[i] = (float)cd.delta_v[i];
+    p.cc[i] = (float)cd.center[i];
+    p.dku[i] = (float)cd.defocus_u[i];
+    p.dkv[i] = (float)cd.defocus_v[i];
+    p.bg[i] = (float)cd.background[i];
+  }
+  p.recip_s = (float)cd.recip_spp_sqrt;
+  p.maxc = (float)cd.max_contribution;
+  p.s = cd.spp_sqrt;
+  p.defocus = cd.defocus_angle > 0 ? 1 : 0;  // camera.go:262
+  p.max_depth = cd.max_depth;
+  p.width = cd.width;
+  p.rank = o.rank;
+  p.nranks = o.nranks;
+  p.npix = npix;
+  p.ss = (uint32_t)cd.spp_sqrt * (uint32_t)cd.spp_sqrt;
+  p.seed = o.seed;
+  p.fd_width = make_fastdiv((uint32_t)cd.width);
+  p.fd_s = make_fastdiv((uint32_t)cd.spp_sqrt);
+}
+// rows of an H-row image that rank `rank` of `nranks` renders (r % nranks == rank)
+uint32_t rank_rows(uint32_t H, int rank, int nranks) {
+  return H > (uint32_t)rank ? (H - (uint32_t)rank + nranks - 1) / nranks : 0;
+}
+
+// How a render's samples are cut into chunks (rt_path.h chunk_pixel): K samples per chunk, a
+// tail phase of K2-sample chunks after the first S1 samples of every pixel (S1 == ss: none),
+// and the row groups the chunks sweep.  P: the fused kernel's lanes (unused otherwise).
+struct ChunkPlan {
+  uint32_t K, K2, S1;
+  uint32_t cpp1;      // first-phase chunks per pixel
+  uint32_t n_chunks;
+  uint32_t n_groups;  // chunk-order groups of this rank
+  FastDiv fd_gpix, fd_gchunks, fd_gchunks2;
+};
+static int plan_chunks(uint32_t npix, uint32_t rows, uint32_t W, uint32_t ss, uint32_t P, int chunk,
+                       uint32_t ft_set, int tree, bool f_lds, int mode, ChunkPlan* out) {
   // Samples per chunk.  Fused: the largest K in {32, 16, 8} (64 for C2's record loop, below)
   // that still gives
   // every lane >= 12 chunks (tree in LDS) or >= 100 (tree through L1/L2, whose
@@ -1154,8 +887,8 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   // K = 8 (C5 -27 % against 32), whole images at K = 32 (C3 -3 % against 8); at 100
   // C3 takes K = 16 (1.5 % behind 32, which is 14 % behind 8 on C5's 8-GPU share).
   uint32_t K = 32u;
-  if (o.chunk > 0) {
-    K = (uint32_t)o.chunk;
+  if (chunk > 0) {
+    K = (uint32_t)chunk;
   } else if (mode == RT_MODE_FUSED) {
     // (the mesh set asks 200: the 1M-triangle mesh's 2- / 4- / 8-GPU shares -0.6 / -1.6 /
     // -2.3 % with K halved, its whole image unchanged at K = 32; book1 and book2 gained
@@ -1200,7 +933,7 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     // default: with the default chunk size only; an explicit RT_TAIL_FRAC also applies to
     // an explicit chunk size (A/B and tests)
     const int tf_env = env_int("RT_TAIL_FRAC", -1);
-    const int tf = tf_env >= 0 ? tf_env : (few && o.chunk <= 0 ? 4 : 0);
+    const int tf = tf_env >= 0 ? tf_env : (few && chunk <= 0 ? 4 : 0);
     if (mode == RT_MODE_FUSED && !one_phase && tf > 1 && K >= 8u) {
       K2 = std::max<uint32_t>(1u, (uint32_t)env_int("RT_TAIL_K", (int)std::max<uint32_t>(4u, K / 4)));
       const uint32_t s1 = (uint32_t)((uint64_t)ss * (uint32_t)(tf - 1) / (uint32_t)tf) / K * K;
@@ -1214,124 +947,6 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   const uint64_t n_chunks64 = (uint64_t)npix * cpp;
   if (n_chunks64 >= 0xF0000000ull) return set_error(RT_ERR_UNSUPPORTED, "too many work chunks");
   const uint32_t n_chunks = (uint32_t)n_chunks64;
-  if (mode != RT_MODE_FUSED) {
-    P = o.path_slots > 0 ? (uint32_t)o.path_slots : (1u << 20);
-    P = std::max<uint32_t>(256u, std::min<uint32_t>(P, std::max<uint32_t>(n_chunks, 256u)));
-    P = (P + 255u) & ~255u;
-  }
-  if ((rc = ensure_state(slot, o.device, P, depth_cap, std::max<uint32_t>(npix, 1),
-                         mode == RT_MODE_WAVEFRONT)))
-    return rc;
-  RenderState* st = slot->st;
-  const void* extend_kernel =
-      lds_nodes ? (const void*)k_extend<true> : (const void*)k_extend<false>;
-  if (mode == RT_MODE_WAVEFRONT && st->resident_blocks == 0 &&
-      (rc = occupancy_blocks(extend_kernel, o.device, &st->resident_blocks)))
-    return rc;
-  // traversal-stack overflow columns: one per launched traversal thread
-  {
-    const uint32_t cols = mode == RT_MODE_FUSED ? P : (uint32_t)st->resident_blocks * 256u;
-    if (st->ostack_cols < cols) {
-      if (st->ostack) {
-        HIP_OK(hipFree(st->ostack));
-        st->allocs.erase(std::find(st->allocs.begin(), st->allocs.end(), (void*)st->ostack));
-        st->ostack = nullptr;
-      }
-      if ((rc = dalloc(st, &st->ostack, (size_t)(kStack - kShortStackMin) * cols))) return rc;
-      st->ostack_cols = cols;
-    }
-  }
-  // fused: the per-chunk sums (32 B per chunk, every record stored once per render: no clear).
-  // The buffer grows with the sample count, not the image: above its cap (RT_CSUM_MAX_MB,
-  // default 16 GiB, and at most half of the device's free memory) or when it cannot be
-  // allocated, the render falls back to pixel atomics (P.csum == nullptr: the same integer
-  // sums, so the same image; rt_stats.chunk_records = 0).  A buffer more than 4x larger than
-  // this render needs (and over 256 MiB) is released first.
-  bool use_csum = mode == RT_MODE_FUSED && env_int("RT_CSUM", 1) != 0;
-  {
-    const size_t need_b = 32 * (size_t)n_chunks;
-    auto drop_csum = [&]() -> int {
-      if (!st->csum) return RT_OK;
-      HIP_OK(hipFree(st->csum));
-      st->allocs.erase(std::find(st->allocs.begin(), st->allocs.end(), (void*)st->csum));
-      st->csum = nullptr;
-      st->csum_chunks = 0;
-      return RT_OK;
-    };
-    if (st->csum && (!use_csum || (st->csum_chunks > 4 * (size_t)n_chunks &&
-                                   32 * st->csum_chunks > ((size_t)256 << 20))))
-      if ((rc = drop_csum())) return rc;
-    if (use_csum && st->csum_chunks < n_chunks) {
-      if ((rc = drop_csum())) return rc;
-      size_t free_b = 0, total_b = 0;
-      const size_t cap_b = (size_t)std::max(0, env_int("RT_CSUM_MAX_MB", 16384)) << 20;
-      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-      void* q = nullptr;
-      if (need_b <= cap_b && need_b <= free_b / 2 && hipMalloc(&q, std::max<size_t>(need_b, 32)) == hipSuccess) {
-        st->allocs.push_back(q);
-        st->csum = (unsigned long long*)q;
-        st->csum_chunks = n_chunks;
-      } else {
-        (void)hipGetLastError();  // a failed allocation is not sticky: pixel atomics instead
-        use_csum = false;
-      }
-    }
-  }
-
-  hipStream_t stream = (hipStream_t)o.stream;
-  if (!stream) {
-    if (!st->own_stream) HIP_OK(hipStreamCreateWithFlags(&st->own_stream, hipStreamNonBlocking));
-    stream = st->own_stream;
-  }
-
-  Params p{};
-  p.sc = ds->d;
-  if (tree == 2) {
-    p.sc.nodes = ds->nodes2;
-    p.sc.root = ds->root2;
-    p.sc.n_nodes = ds->n_nodes2;
-  } else if (tree == 5) {
-    p.sc.nodes = ds->qnodes;
-    p.sc.root = 0;  // item 0: the root node (trav_init)
-    p.sc.n_nodes = (int32_t)std::min<size_t>(ds->qitems, 0x7FFFFFFF);  // 64-B items
-  } else if (tree == 8) {
-    p.sc.root = 0;  // BVH8 node 0 (trav_init)
-  } else if (tree == 0) {
-    p.sc.n_nodes = 0;  // records only (stage_nodes puts them at the start of the cache)
-    p.sc.leafprims = ds->brute_pairs;
-    p.sc.n_refs = (int32_t)brute_slots;  // even: whole pairs
-    if (shade_tab && f_recs) {  // the shade table follows the pairs, in LDS as in HBM
-      p.sc.shade_lds = (int32_t)(4 * brute_slots);
-      p.sc.shade_n = ds->shade_n;
-    }
-  }
-  for (int i = 0; i < 3; ++i) {
-    p.p00r[i] = (float)(cd.pixel00[i] - cd.center[i]);
-    p.du[i] = (float)cd.delta_u[i];
-    p.dv[i] = (float)cd.delta_v[i];
-    p.cc[i] = (float)cd.center[i];
-    p.dku[i] = (float)cd.defocus_u[i];
-    p.dkv[i] = (float)cd.defocus_v[i];
-    p.bg[i] = (float)cd.background[i];
-  }
-  if (!(p.bg[0] >= 0.0f && p.bg[1] >= 0.0f && p.bg[2] >= 0.0f)) p.sc.merge_ok = 0;
-  p.recip_s = (float)cd.recip_spp_sqrt;
-  p.maxc = (float)cd.max_contribution;
-  p.s = cd.spp_sqrt;
-  p.defocus = cd.defocus_angle > 0 ? 1 : 0;  // camera.go:262
-  p.max_depth = cd.max_depth;
-  p.width = (int)W;
-  p.rank = o.rank;
-  p.nranks = o.nranks;
-  p.npix = npix;
-  p.K = K;
-  p.K2 = K2;
-  p.S1 = S1;
-  p.n1 = npix * cpp1;
-  p.n_chunks = n_chunks;
-  p.P = P;
-  p.ss = ss;
-  uint32_t g_ng = 1u;  // chunk-order groups of this rank
   {
     // chunk order (chunk_pixel): groups of `grows` of this rank's rows, so the paths in
     // flight start from a band of a few rows instead of the whole image (C5 -10 %,
@@ -1342,11 +957,359 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     grows = std::max<uint32_t>(1u, std::min<uint32_t>(grows, std::max<uint32_t>(rows, 1u)));
     while (rows % grows) --grows;  // a divisor of the rank's row count
     const uint32_t gpix = std::max<uint32_t>(1u, grows * W);
-    p.fd_gpix = make_fastdiv(gpix);
-    p.fd_gchunks = make_fastdiv(gpix * cpp1);
-    p.fd_gchunks2 = make_fastdiv(std::max<uint32_t>(1u, gpix * cpp2));
-    g_ng = rows / grows;
+    out->fd_gpix = make_fastdiv(gpix);
+    out->fd_gchunks = make_fastdiv(gpix * cpp1);
+    out->fd_gchunks2 = make_fastdiv(std::max<uint32_t>(1u, gpix * cpp2));
+    out->n_groups = rows / grows;
   }
+  out->K = K;
+  out->K2 = K2;
+  out->S1 = S1;
+  out->cpp1 = cpp1;
+  out->n_chunks = n_chunks;
+  return RT_OK;
+}
+
+// The fused kernel's scheduling knobs and their measured defaults.
+struct SchedPlan {
+  int step_budget;
+  uint32_t shade_min, grab_min, split_min, parts_log2, gran_log2;
+};
+static SchedPlan plan_sched(uint32_t ft_set, int tree, bool f_lds, uint32_t K, size_t n_nodes4) {
+  SchedPlan sd;
+  // Scheduling rounds, measured on the full-size configs (tools/sched_sweep.py,
+  // tools/sched_ab.sh, profiles/r1_sched_sweep*.jsonl, r2_sched_ab*.jsonl): trees read
+  // through L1/L2 gain from bounded rounds so short rays do not idle behind long ones —
+  // 8 steps for large trees (C5 +75 %, C4 +10 % over unbounded), 12 for small ones
+  // (C3's 485 spheres: 7 % faster than 8); LDS-resident trees (C2) lose from any bound.
+  // Kernels with long shading gain from waiting until enough lanes are ready: 32 for
+  // the book2 and all-features sets (C4 -1.2 %), 16 for large trees otherwise (C5 -2 %).
+  // Round 5, on the compressed BVH4 (cheaper node steps, 5 waves per SIMD): the mesh
+  // scene is fastest at 5 steps and 32 ready lanes (C5 +4.6 % over 8 / 16 at 256 spp;
+  // 64 ready lanes halves it), book2 unchanged at 8 / 32 (6 / 32 within 0.1 %), book1 at
+  // 12 / 1 (profiles/r5_sched_sweep_q.jsonl) -- then 10 steps for book1: -0.7 % at full size
+  // (r5_c3_step_ab.jsonl; 9 to 16 swept at 256 spp, r5_knob_sweeps_q.jsonl)
+  const bool big_tree = n_nodes4 >= 1024;
+  const bool long_shade = ft_set == FT_ALL || (ft_set & FT_NOISE);
+  // (book2 at full size: 7 steps and 40 ready lanes -0.7 % against 8 / 32,
+  // profiles/r5_c4_c5_knobs_full.jsonl)
+  // (clamped where read, as every scheduling knob: a round without a traversal step would
+  // never finish a traversal)
+  // (round 6, with the mesh set's 256-chunk batches: 4 steps -0.5 % on C5's whole image, -0.4 /
+  // -0.6 % on its 2- / 8-GPU shares against 5; 3 as 4 except the 8-GPU share, 2 +1.5 %; the
+  // ready-lane bar 24 as 32, 16 +2.5 %, 40 +2 %; profiles/r6_c5_sched_sweep.jsonl)
+  sd.step_budget = std::max(1, env_int("RT_STEP_BUDGET", f_lds ? (1 << 30) : big_tree ? (long_shade ? 7 : 4) : 10));
+  sd.shade_min = (uint32_t)std::max(1, env_int("RT_SHADE_MIN", f_lds ? 1 : long_shade ? 40 : big_tree ? 32 : 1));
+  // chunks per refill of a wave's batch (one returning atomic on the chunk
+  // counter each): C2 grab sweep (profiles/r1_grab_sweep.jsonl) 64 -> 128:
+  // -4 % at 1-2 ranks' shares; 256 for small chunks: -11 % on the 8-GPU share
+  // Round 4, with the 64 partitioned counters below: batches of 32 chunks for the
+  // LDS-resident scenes (C2 -1.7 % on the whole image, its 8-GPU share 5.13 ms against
+  // 5.22 with 128; profiles/r4_share_probe_grab_v1.jsonl, r4_grab_ab.jsonl), while the
+  // scenes that traverse a tree through L1/L2 keep 128 (32 measured C3 +3.7 %, C4 +2.2 %,
+  // C5 +2 %: their waves refill more often and spread over more of the image)
+  // (round 6: 16 for C2's record loop at any K: its whole image at K = 64 -0.4 % against 32
+  // (64 +1 %, 128 +4 %), its 2- / 4-GPU shares -0.9 / -1.3 %, the 8-GPU share ±0;
+  // profiles/r6_chunk_sweep.jsonl, r6_grab_sweep_c2_shares.jsonl)
+  // (round 6: 256 for the mesh set at any K: C5 -1.0 % on the whole image, -0.5 % on its 2-GPU
+  // share; 512 ±0, 1024 +5 %; book2 keeps 128: -0.4 % whole but +0.4 % on its 2-GPU share, and
+  // book1 128: 64 +0.7 %, 256 +2 %; profiles/r6_grab_sweep.jsonl)
+  const bool mesh_set = ft_set == (FT_SPHERE | FT_TRI | FT_METAL);
+  sd.grab_min = (uint32_t)std::max(1, env_int("RT_GRAB_MIN", f_lds ? (tree == 0 && ft_set == 0u ? 16 : 32) : (K <= 8u || mesh_set) ? 256 : 128));
+  {  // drain splitting (k_fused's record-loop kernel): share when >= split_min samples are left
+    const int sm = env_int("RT_SPLIT_MIN", 1);
+    sd.split_min = sm > 0 ? (uint32_t)sm : 0xFFFFFFFFu;  // 0: off (no lane has that many)
+  }
+  // partitioned chunk counters (rt_path.h grab_chunk): 64 partitions interleaved in
+  // granules of 256 chunks; progress slices use one counter (their ranges are contiguous)
+  sd.parts_log2 = (uint32_t)std::min(6, std::max(0, env_int("RT_PARTS_LOG2", 6)));
+  sd.gran_log2 = (uint32_t)std::min(20, std::max(0, env_int("RT_GRAN_LOG2", 8)));
+  return sd;
+}
+
+// rt_progress follows one render per scene: the rt_render call (slot 0) or rt_render_multi
+// call that finds no other render holding the record claims it here, and ProgressDone
+// releases it on every return path of the claimant.
+static bool claim_progress(Progress& pr, uint64_t total, int device) {
+  std::lock_guard<std::mutex> lk(pr.mu);
+  if (pr.busy) return false;
+  pr.busy = 1;
+  pr.total = total;
+  pr.done = 0;
+  pr.device = device;
+  pr.events.clear();  // no slice events unless the claimant adds them
+  pr.cum.clear();
+  return true;
+}
+struct ProgressDone {
+  Progress& p;
+  bool track;
+  bool ok = false;
+  ~ProgressDone() {
+    if (!track) return;
+    std::lock_guard<std::mutex> lk(p.mu);
+    if (ok) p.done = p.total;
+    p.busy = 0;
+  }
+};
+
+// RT_FLAG_PROFILE: events around every kernel, as index pairs into st->events
+struct ProfEvents {
+  RenderState* st;
+  bool on;
+  int used = 0;
+  std::vector<std::pair<int, int>> ext, shade, fused;
+  int next(hipEvent_t* e) {
+    if (used >= (int)st->events.size()) {
+      hipEvent_t ne;
+      HIP_OK(hipEventCreate(&ne));
+      st->events.push_back(ne);
+    }
+    *e = st->events[used++];
+    return RT_OK;
+  }
+  int sum_ms(const std::vector<std::pair<int, int>>& v, double* acc) const {
+    for (auto& pr : v) {
+      float ms = 0;
+      HIP_OK(hipEventElapsedTime(&ms, st->events[pr.first], st->events[pr.second]));
+      *acc += ms;
+    }
+    return RT_OK;
+  }
+};
+
+// The fused strategy: the kernel once, or once per progress slice over consecutive chunk
+// ranges with an event after each (the image does not depend on the split).
+static int launch_fused(Params& p, RenderState* st, hipStream_t stream, const StructurePlan& sp,
+                        int fused_blocks, int slices, ProfEvents& ev) {
+  const uint32_t n_chunks = p.n_chunks;
+  int rc;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (ev.on) {
+    if ((rc = ev.next(&e0)) || (rc = ev.next(&e1))) return rc;
+    HIP_OK(hipEventRecord(e0, stream));
+  }
+  // debug: per-wave start/end clocks (100 MHz), segments and (RT_PHASES builds) phase
+  // cycles -> binary file RT_WAVE_TIMES, kWaveRec u64 per wave
+  std::string wt_file;
+  const char* wt_path = tune_str("RT_WAVE_TIMES", &wt_file) ? wt_file.c_str() : nullptr;
+  unsigned long long* wt = nullptr;
+  const size_t n_waves = (size_t)fused_blocks * 4;
+  if (wt_path && *wt_path) {
+    HIP_OK(hipMalloc(&wt, kWaveRec * n_waves * sizeof(unsigned long long)));
+    p.wave_times = wt;
+  }
+  void* args[] = {&p};
+  for (int sl = 0; sl < slices; ++sl) {
+    if (slices > 1) {  // chunks [n*sl/S, n*(sl+1)/S): the counter starts at the range
+      p.n_chunks = (uint32_t)((uint64_t)n_chunks * (sl + 1) / slices);
+      if (sl > 0)  // one partition (parts_log2 = 0 with slices): its counter is the head
+        HIP_OK(hipMemsetD32Async((hipDeviceptr_t)&st->ctr->part[0],
+                                 (int)((uint64_t)n_chunks * sl / slices), 1, stream));
+    }
+    HIP_OK(hipLaunchKernel(sp.kernel, dim3(fused_blocks), dim3(256), args, sp.lds_bytes, stream));
+    HIP_OK(hipGetLastError());
+    if (slices > 1) HIP_OK(hipEventRecord(st->prog_events[sl], stream));
+  }
+  p.n_chunks = n_chunks;
+  if (wt) {
+    std::vector<unsigned long long> h(kWaveRec * n_waves);
+    HIP_OK(hipMemcpyAsync(h.data(), wt, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    HIP_OK(hipFree(wt));
+    p.wave_times = nullptr;
+    if (FILE* f = fopen(wt_path, "wb")) {
+      fwrite(h.data(), sizeof(h[0]), h.size(), f);
+      fclose(f);
+    }
+  }
+  if (ev.on) {
+    HIP_OK(hipEventRecord(e1, stream));
+    ev.fused.push_back({ev.used - 2, ev.used - 1});
+  }
+  return RT_OK;
+}
+
+// The wavefront strategy: k_init, then extend + shade per iteration in batches, reading the
+// queue lengths back after each batch.  *iterations: extend (= shade) launches.
+static int launch_wavefront(Params& p, RenderState* st, hipStream_t stream, const void* extend_kernel,
+                            ProfEvents& ev, int* iterations_out) {
+  const uint32_t P = p.P, n_chunks = p.n_chunks;
+  int rc, iterations = 0;
+  hipLaunchKernelGGL(k_init, dim3((P + 255) / 256), dim3(256), 0, stream, p);
+  HIP_OK(hipGetLastError());
+  uint32_t n_est = std::min(P, n_chunks);
+  const int kBatch = 4;
+  while (n_est > 0) {
+    for (int b = 0; b < kBatch; ++b) {
+      if (iterations + 1 >= kMaxIt)
+        return set_error(RT_ERR_UNSUPPORTED, "more than %d wavefront iterations", kMaxIt);
+      const uint32_t ext_blocks = std::max<uint32_t>(
+          1u, std::min<uint32_t>((n_est + 255) / 256, (uint32_t)st->resident_blocks));
+      hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+      if (ev.on) {
+        if ((rc = ev.next(&e0)) || (rc = ev.next(&e1)) || (rc = ev.next(&e2))) return rc;
+        HIP_OK(hipEventRecord(e0, stream));
+      }
+      int it_arg = iterations;
+      void* eargs[] = {&p, &it_arg};
+      HIP_OK(hipLaunchKernel(extend_kernel, dim3(ext_blocks), dim3(256), eargs, 0, stream));
+      if (ev.on) HIP_OK(hipEventRecord(e1, stream));
+      hipLaunchKernelGGL(k_shade, dim3((n_est + 255) / 256), dim3(256), 0, stream, p,
+                         iterations);
+      if (ev.on) {
+        HIP_OK(hipEventRecord(e2, stream));
+        ev.ext.push_back({ev.used - 3, ev.used - 2});
+        ev.shade.push_back({ev.used - 2, ev.used - 1});
+      }
+      HIP_OK(hipGetLastError());
+      ++iterations;
+    }
+    uint32_t n_now[kXcd];
+    HIP_OK(hipMemcpyAsync(n_now, &st->ctr->cnt[iterations % kMaxIt][0], sizeof n_now,
+                          hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    n_est = 0;
+    for (int x = 0; x < kXcd; ++x) n_est += n_now[x];
+  }
+  *iterations_out = iterations;
+  return RT_OK;
+}
+
+// the wavefront extend kernel stages the BVH4's nodes in LDS
+static bool extend_in_lds(const Scene* s) { return s->h.nodes4.size() / 8 <= (size_t)kLdsNodes / 2; }
+
+// rt_stats of a finished render, but for ms_total and tuned (the caller's clock and knob count)
+static int fill_stats(rt_stats* stats, const Scene* s, const DeviceScene* ds, const RenderState* st,
+                      const Params& p, const StructurePlan& sp, int mode, uint32_t ft_set,
+                      uint32_t rows, int iterations, const ProfEvents& ev) {
+  const int tree = sp.tree;
+  int rc;
+  memset(stats, 0, sizeof *stats);
+  Counters hc;
+  HIP_OK(hipMemcpy(&hc, st->ctr, offsetof(Counters, cnt), hipMemcpyDeviceToHost));
+  stats->samples = (uint64_t)p.npix * p.ss;
+  stats->segments = hc.segments;
+  stats->stack_pushes = hc.pushes;
+  stats->overflow_samples = hc.overflow;
+  stats->extend_rays = hc.segments;
+  stats->shade_rays = hc.segments;
+  stats->n_extend_launches = mode == RT_MODE_FUSED ? 0 : iterations;
+  stats->n_shade_launches = stats->n_extend_launches;
+  stats->iterations = iterations;
+  stats->rows = (int32_t)rows;
+  stats->mode = mode;
+  stats->path_slots = (int32_t)p.P;
+  stats->kernel_features = mode == RT_MODE_FUSED ? (int32_t)ft_set : (int32_t)FT_ALL;
+  stats->scene_features = (int32_t)s->h.features;
+  stats->tree_width = tree;
+  stats->chunk_samples = (int32_t)p.K;
+  stats->record_boxes = tree == 0 ? ds->brute_boxes : 0;
+  stats->chunk_records = p.csum ? 1 : 0;
+  stats->lds_scene = mode == RT_MODE_FUSED ? (sp.f_lds ? 1 : 0) : (extend_in_lds(s) ? 1 : 0);
+  if (ev.on) {
+    if ((rc = ev.sum_ms(ev.ext, &stats->ms_extend)) || (rc = ev.sum_ms(ev.shade, &stats->ms_shade)) ||
+        (rc = ev.sum_ms(ev.fused, &stats->ms_fused)))
+      return rc;
+  }
+  return RT_OK;
+}
+
+
+static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
+                       float* out_host, float* out_dev, rt_stats* stats, int slot_id = 0,
+                       const Gather* gather = nullptr) {
+  if (!scene || !cam) return set_error(RT_ERR_INVALID, "rt_render: null scene/camera");
+  rt_render_opts o{};
+  if (opts) o = *opts;
+  if (o.nranks <= 0) o.nranks = 1;
+  if (o.rank < 0 || o.rank >= o.nranks) return set_error(RT_ERR_INVALID, "rt_render: bad rank");
+  rt_camera_derived cd;
+  int rc = rt_camera_derive(cam, &cd);
+  if (rc) return rc;
+  auto t_start = std::chrono::steady_clock::now();
+  const int32_t tuned = tune_count();  // rt_stats.tuned: knobs off their defaults
+
+  if ((rc = device_ok("rt_render", o.device))) return rc;
+  DeviceGuard dg;  // the caller's current device is restored on every return
+  HIP_OK(hipSetDevice(o.device));
+  Scene* s = &scene->s;
+  DeviceScene* ds = nullptr;
+  if ((rc = ensure_scene(s, o.device, &ds))) return rc;
+  SlotState* slot = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    SlotState*& sl = s->slots[{o.device, slot_id}];
+    if (!sl) sl = new SlotState();
+    slot = sl;
+  }
+  std::lock_guard<std::mutex> inflight(slot->mu);  // one render per (scene, device, slot)
+
+  const uint32_t W = (uint32_t)cd.width, H = (uint32_t)cd.height;
+  const uint32_t rows = rank_rows(H, o.rank, o.nranks);
+  const uint32_t npix = rows * W;
+  const uint32_t ss = (uint32_t)cd.spp_sqrt * (uint32_t)cd.spp_sqrt;
+  int mode = o.mode;
+  if (mode != RT_MODE_WAVEFRONT && mode != RT_MODE_FUSED) mode = RT_MODE_FUSED;
+  const int depth_cap = cd.max_depth + 1;
+  const uint32_t ft_set = scene_ft_set(s);
+
+  // what to traverse and the kernel for it (the feature pass takes the same: aov_view)
+  StructurePlan sp;
+  if ((rc = plan_structure(s, ds, ft_set, mode, &sp))) return rc;
+  if (sp.tree == 4 && sp.wants_qbvh && (rc = take_qbvh(s, ds, ft_set, &sp))) return rc;
+  // path slots: the fused kernel's resident lanes, or the wavefront queue's length
+  uint32_t P = 0;
+  int fused_blocks = 0;
+  if (mode == RT_MODE_FUSED) {
+    if ((rc = occupancy_blocks(sp.kernel, o.device, &fused_blocks, sp.lds_bytes))) return rc;
+    if (o.path_slots > 0) fused_blocks = std::max(1, std::min(fused_blocks, (o.path_slots + 255) / 256));
+    P = (uint32_t)fused_blocks * 256u;
+  }
+  ChunkPlan cp;
+  if ((rc = plan_chunks(npix, rows, W, ss, P, o.chunk, ft_set, sp.tree, sp.f_lds, mode, &cp))) return rc;
+  const uint32_t n_chunks = cp.n_chunks;
+  if (mode != RT_MODE_FUSED) {
+    P = o.path_slots > 0 ? (uint32_t)o.path_slots : (1u << 20);
+    P = std::max<uint32_t>(256u, std::min<uint32_t>(P, std::max<uint32_t>(n_chunks, 256u)));
+    P = (P + 255u) & ~255u;
+  }
+  if ((rc = ensure_state(slot, o.device, P, depth_cap, std::max<uint32_t>(npix, 1),
+                         mode == RT_MODE_WAVEFRONT)))
+    return rc;
+  RenderState* st = slot->st;
+  const void* extend_kernel =
+      extend_in_lds(s) ? (const void*)k_extend<true> : (const void*)k_extend<false>;
+  if (mode == RT_MODE_WAVEFRONT && st->resident_blocks == 0 &&
+      (rc = occupancy_blocks(extend_kernel, o.device, &st->resident_blocks)))
+    return rc;
+  if ((rc = ensure_ostack(st, mode == RT_MODE_FUSED ? P : (uint32_t)st->resident_blocks * 256u))) return rc;
+  bool use_csum = mode == RT_MODE_FUSED && env_int("RT_CSUM", 1) != 0;
+  if ((rc = ensure_csum(st, n_chunks, &use_csum))) return rc;
+
+  hipStream_t stream = (hipStream_t)o.stream;
+  if (!stream) {
+    if (!st->own_stream) HIP_OK(hipStreamCreateWithFlags(&st->own_stream, hipStreamNonBlocking));
+    stream = st->own_stream;
+  }
+
+  Params p{};
+  p.sc = scene_for_tree(ds, sp.tree);
+  if (sp.tree == 0 && sp.shade_tab && sp.f_recs) {  // the shade table follows the pairs, in LDS as in HBM
+    p.sc.shade_lds = (int32_t)(4 * ds->brute_slots);
+    p.sc.shade_n = ds->shade_n;
+  }
+  set_camera_params(p, cd, o, npix);
+  if (!(p.bg[0] >= 0.0f && p.bg[1] >= 0.0f && p.bg[2] >= 0.0f)) p.sc.merge_ok = 0;
+  p.K = cp.K;
+  p.K2 = cp.K2;
+  p.S1 = cp.S1;
+  p.n1 = npix * cp.cpp1;
+  p.n_chunks = n_chunks;
+  p.P = P;
+  p.fd_gpix = cp.fd_gpix;
+  p.fd_gchunks = cp.fd_gchunks;
+  p.fd_gchunks2 = cp.fd_gchunks2;
   // The order the sweep takes the row groups in (chunk_pixel, k_resolve; images do not
   // depend on it): RT_SWEEP = forward (image order, the default) or reverse.  A render's tail
   // is the paths still in flight when the chunk pool runs dry, so it depends on which rows
@@ -1366,67 +1329,24 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     std::string v;
     if (tune_str("RT_SWEEP", &v) && v == "reverse") {
 #ifdef RT_SWEEP_ORDER
-      if (mode == RT_MODE_FUSED && ft_set != 0u && g_ng > 1 && npix > 0) {
+      if (mode == RT_MODE_FUSED && ft_set != 0u && cp.n_groups > 1 && npix > 0) {
         p.gflip = ~0u;  // (q ^ ~0) + ng = ng - 1 - q
-        p.gbase = g_ng;
+        p.gbase = cp.n_groups;
       }
 #else
       return set_error(RT_ERR_UNSUPPORTED, "RT_SWEEP=reverse needs a library built with -DRT_SWEEP_ORDER");
 #endif
     }
   }
-  p.fd_width = make_fastdiv(W);
-  p.fd_s = make_fastdiv((uint32_t)cd.spp_sqrt);
-  // Scheduling rounds, measured on the full-size configs (tools/sched_sweep.py,
-  // tools/sched_ab.sh, profiles/r1_sched_sweep*.jsonl, r2_sched_ab*.jsonl): trees read
-  // through L1/L2 gain from bounded rounds so short rays do not idle behind long ones —
-  // 8 steps for large trees (C5 +75 %, C4 +10 % over unbounded), 12 for small ones
-  // (C3's 485 spheres: 7 % faster than 8); LDS-resident trees (C2) lose from any bound.
-  // Kernels with long shading gain from waiting until enough lanes are ready: 32 for
-  // the book2 and all-features sets (C4 -1.2 %), 16 for large trees otherwise (C5 -2 %).
-  // Round 5, on the compressed BVH4 (cheaper node steps, 5 waves per SIMD): the mesh
-  // scene is fastest at 5 steps and 32 ready lanes (C5 +4.6 % over 8 / 16 at 256 spp;
-  // 64 ready lanes halves it), book2 unchanged at 8 / 32 (6 / 32 within 0.1 %), book1 at
-  // 12 / 1 (profiles/r5_sched_sweep_q.jsonl) -- then 10 steps for book1: -0.7 % at full size
-  // (r5_c3_step_ab.jsonl; 9 to 16 swept at 256 spp, r5_knob_sweeps_q.jsonl)
-  const bool big_tree = s->h.nodes4.size() / 8 >= 1024;
-  const bool long_shade = ft_set == FT_ALL || (ft_set & FT_NOISE);
-  // (book2 at full size: 7 steps and 40 ready lanes -0.7 % against 8 / 32,
-  // profiles/r5_c4_c5_knobs_full.jsonl)
-  // (clamped where read, as every scheduling knob: a round without a traversal step would
-  // never finish a traversal)
-  // (round 6, with the mesh set's 256-chunk batches: 4 steps -0.5 % on C5's whole image, -0.4 /
-  // -0.6 % on its 2- / 8-GPU shares against 5; 3 as 4 except the 8-GPU share, 2 +1.5 %; the
-  // ready-lane bar 24 as 32, 16 +2.5 %, 40 +2 %; profiles/r6_c5_sched_sweep.jsonl)
-  p.step_budget = std::max(1, env_int("RT_STEP_BUDGET", f_lds ? (1 << 30) : big_tree ? (long_shade ? 7 : 4) : 10));
-  p.shade_min = (uint32_t)std::max(1, env_int("RT_SHADE_MIN", f_lds ? 1 : long_shade ? 40 : big_tree ? 32 : 1));
-  // chunks per refill of a wave's batch (one returning atomic on the chunk
-  // counter each): C2 grab sweep (profiles/r1_grab_sweep.jsonl) 64 -> 128:
-  // -4 % at 1-2 ranks' shares; 256 for small chunks: -11 % on the 8-GPU share
-  // Round 4, with the 64 partitioned counters below: batches of 32 chunks for the
-  // LDS-resident scenes (C2 -1.7 % on the whole image, its 8-GPU share 5.13 ms against
-  // 5.22 with 128; profiles/r4_share_probe_grab_v1.jsonl, r4_grab_ab.jsonl), while the
-  // scenes that traverse a tree through L1/L2 keep 128 (32 measured C3 +3.7 %, C4 +2.2 %,
-  // C5 +2 %: their waves refill more often and spread over more of the image)
-  // (round 6: 16 for C2's record loop at any K: its whole image at K = 64 -0.4 % against 32
-  // (64 +1 %, 128 +4 %), its 2- / 4-GPU shares -0.9 / -1.3 %, the 8-GPU share ±0;
-  // profiles/r6_chunk_sweep.jsonl, r6_grab_sweep_c2_shares.jsonl)
-  // (round 6: 256 for the mesh set at any K: C5 -1.0 % on the whole image, -0.5 % on its 2-GPU
-  // share; 512 ±0, 1024 +5 %; book2 keeps 128: -0.4 % whole but +0.4 % on its 2-GPU share, and
-  // book1 128: 64 +0.7 %, 256 +2 %; profiles/r6_grab_sweep.jsonl)
-  const bool mesh_set = ft_set == (FT_SPHERE | FT_TRI | FT_METAL);
-  p.grab_min = (uint32_t)std::max(1, env_int("RT_GRAB_MIN", f_lds ? (tree == 0 && ft_set == 0u ? 16 : 32) : (K <= 8u || mesh_set) ? 256 : 128));
-  {  // drain splitting (k_fused's record-loop kernel): share when >= split_min samples are left
-    const int sm = env_int("RT_SPLIT_MIN", 1);
-    p.split_min = sm > 0 ? (uint32_t)sm : 0xFFFFFFFFu;  // 0: off (no lane has that many)
-  }
-  // partitioned chunk counters (rt_path.h grab_chunk): 64 partitions interleaved in
-  // granules of 256 chunks; progress slices use one counter (their ranges are contiguous)
-  p.parts_log2 = (uint32_t)std::min(6, std::max(0, env_int("RT_PARTS_LOG2", 6)));
-  p.gran_log2 = (uint32_t)std::min(20, std::max(0, env_int("RT_GRAN_LOG2", 8)));
+  const SchedPlan sd = plan_sched(ft_set, sp.tree, sp.f_lds, cp.K, s->h.nodes4.size() / 8);
+  p.step_budget = sd.step_budget;
+  p.shade_min = sd.shade_min;
+  p.grab_min = sd.grab_min;
+  p.split_min = sd.split_min;
+  p.parts_log2 = sd.parts_log2;
+  p.gran_log2 = sd.gran_log2;
   p.wave_times = nullptr;
-  p.recs_lds = f_recs ? 1u : 0u;
-  p.seed = o.seed;
+  p.recs_lds = sp.f_recs ? 1u : 0u;
   p.ray_o = st->ray_o;
   p.ray_d = st->ray_d;
   p.hit = st->hit;
@@ -1458,18 +1378,7 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     p.trace_sample = (uint32_t)o.trace_sample;
     p.trace_cap = o.trace_cap;
   }
-  const bool prof = (o.flags & RT_FLAG_PROFILE) != 0;
-  std::vector<std::pair<int, int>> ev_ext, ev_shade, ev_fused;  // event index pairs
-  int ev_used = 0;
-  auto next_event = [&](hipEvent_t* e) -> int {
-    if (ev_used >= (int)st->events.size()) {
-      hipEvent_t ne;
-      HIP_OK(hipEventCreate(&ne));
-      st->events.push_back(ne);
-    }
-    *e = st->events[ev_used++];
-    return RT_OK;
-  };
+  ProfEvents ev{st, (o.flags & RT_FLAG_PROFILE) != 0};
 
   HIP_OK(hipMemsetAsync(st->ctr, 0, sizeof(Counters), stream));
   if (npix > 0) {
@@ -1478,7 +1387,6 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     HIP_OK(hipMemsetAsync(st->pflags, 0, (size_t)npix * sizeof(uint32_t), stream));
   }
   int iterations = 0;
-  int n_ext = 0, n_sh = 0;
   // rt_progress: the fused render as `slices` launches over consecutive chunk
   // ranges, an event after each (the image does not depend on the split)
   const int slices = (mode == RT_MODE_FUSED && n_chunks > 0)
@@ -1490,127 +1398,23 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     st->prog_events.push_back(e);
   }
-  // rt_progress follows one render per scene: an rt_render call (slot 0) claims the
-  // record when no other render holds it (rt_render_multi claims it for its shares)
-  bool track = false;
-  if (slot_id == 0) {
+  // rt_progress: an rt_render call (slot 0) claims the record when no other render holds it
+  // (rt_render_multi claims it for its shares); every return path below releases it
+  ProgressDone prog_done{s->prog, slot_id == 0 && claim_progress(s->prog, (uint64_t)npix * ss, o.device)};
+  if (prog_done.track && slices > 1) {
     std::lock_guard<std::mutex> lk(s->prog.mu);
-    if (!s->prog.busy) {  // claimed: no return before prog_done below releases it
-      s->prog.busy = 1;
-      track = true;
-    }
-  }
-  if (track) {
-    std::lock_guard<std::mutex> lk(s->prog.mu);
-    s->prog.total = (uint64_t)npix * ss;
-    s->prog.done = 0;
-    s->prog.device = o.device;
-    s->prog.events.clear();
-    s->prog.cum.clear();
-    if (slices > 1)
-      for (int sl = 0; sl < slices; ++sl) {
-        s->prog.events.push_back((void*)st->prog_events[sl]);
-        s->prog.cum.push_back((uint64_t)((double)s->prog.total *
-                                         (double)((uint64_t)n_chunks * (sl + 1) / slices) /
-                                         (double)n_chunks));
-      }
-    s->prog.busy = 1;
-  }
-  struct ProgressDone {  // every return path below ends the in-flight state
-    Progress& p;
-    bool track;
-    bool ok = false;
-    ~ProgressDone() {
-      if (!track) return;
-      std::lock_guard<std::mutex> lk(p.mu);
-      if (ok) p.done = p.total;
-      p.busy = 0;
-    }
-  } prog_done{s->prog, track};
-  if (n_chunks > 0 && mode == RT_MODE_FUSED) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof) {
-      if ((rc = next_event(&e0)) || (rc = next_event(&e1))) return rc;
-      HIP_OK(hipEventRecord(e0, stream));
-    }
-    // debug: per-wave start/end clocks (100 MHz), segments and (RT_PHASES builds) phase
-    // cycles -> binary file RT_WAVE_TIMES, kWaveRec u64 per wave
-    std::string wt_file;
-    const char* wt_path = tune_str("RT_WAVE_TIMES", &wt_file) ? wt_file.c_str() : nullptr;
-    unsigned long long* wt = nullptr;
-    const size_t n_waves = (size_t)fused_blocks * 4;
-    if (wt_path && *wt_path) {
-      HIP_OK(hipMalloc(&wt, kWaveRec * n_waves * sizeof(unsigned long long)));
-      p.wave_times = wt;
-    }
-    void* args[] = {&p};
     for (int sl = 0; sl < slices; ++sl) {
-      if (slices > 1) {  // chunks [n*sl/S, n*(sl+1)/S): the counter starts at the range
-        p.n_chunks = (uint32_t)((uint64_t)n_chunks * (sl + 1) / slices);
-        if (sl > 0)  // one partition (parts_log2 = 0 with slices): its counter is the head
-          HIP_OK(hipMemsetD32Async((hipDeviceptr_t)&st->ctr->part[0],
-                                   (int)((uint64_t)n_chunks * sl / slices), 1, stream));
-      }
-      HIP_OK(hipLaunchKernel(fused_kernel, dim3(fused_blocks), dim3(256), args, fused_lds, stream));
-      HIP_OK(hipGetLastError());
-      if (slices > 1) HIP_OK(hipEventRecord(st->prog_events[sl], stream));
+      s->prog.events.push_back((void*)st->prog_events[sl]);
+      s->prog.cum.push_back((uint64_t)((double)s->prog.total *
+                                       (double)((uint64_t)n_chunks * (sl + 1) / slices) /
+                                       (double)n_chunks));
     }
-    p.n_chunks = n_chunks;
-    if (wt) {
-      std::vector<unsigned long long> h(kWaveRec * n_waves);
-      HIP_OK(hipMemcpyAsync(h.data(), wt, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, stream));
-      HIP_OK(hipStreamSynchronize(stream));
-      HIP_OK(hipFree(wt));
-      p.wave_times = nullptr;
-      if (FILE* f = fopen(wt_path, "wb")) {
-        fwrite(h.data(), sizeof(h[0]), h.size(), f);
-        fclose(f);
-      }
-    }
-    if (prof) {
-      HIP_OK(hipEventRecord(e1, stream));
-      ev_fused.push_back({ev_used - 2, ev_used - 1});
-    }
+  }
+  if (n_chunks > 0 && mode == RT_MODE_FUSED) {
+    if ((rc = launch_fused(p, st, stream, sp, fused_blocks, slices, ev))) return rc;
     iterations = 1;
   } else if (n_chunks > 0) {
-    hipLaunchKernelGGL(k_init, dim3((P + 255) / 256), dim3(256), 0, stream, p);
-    HIP_OK(hipGetLastError());
-    uint32_t n_est = std::min(P, n_chunks);
-    const int kBatch = 4;
-    while (n_est > 0) {
-      for (int b = 0; b < kBatch; ++b) {
-        if (iterations + 1 >= kMaxIt)
-          return set_error(RT_ERR_UNSUPPORTED, "more than %d wavefront iterations", kMaxIt);
-        const uint32_t ext_blocks = std::max<uint32_t>(
-            1u, std::min<uint32_t>((n_est + 255) / 256, (uint32_t)st->resident_blocks));
-        hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-        if (prof) {
-          if ((rc = next_event(&e0)) || (rc = next_event(&e1)) || (rc = next_event(&e2))) return rc;
-          HIP_OK(hipEventRecord(e0, stream));
-        }
-        int it_arg = iterations;
-        void* eargs[] = {&p, &it_arg};
-        HIP_OK(hipLaunchKernel(extend_kernel, dim3(ext_blocks), dim3(256), eargs, 0, stream));
-        if (prof) HIP_OK(hipEventRecord(e1, stream));
-        hipLaunchKernelGGL(k_shade, dim3((n_est + 255) / 256), dim3(256), 0, stream, p,
-                           iterations);
-        if (prof) {
-          HIP_OK(hipEventRecord(e2, stream));
-          ev_ext.push_back({ev_used - 3, ev_used - 2});
-          ev_shade.push_back({ev_used - 2, ev_used - 1});
-        }
-        HIP_OK(hipGetLastError());
-        ++n_ext;
-        ++n_sh;
-        ++iterations;
-      }
-      uint32_t n_now[kXcd];
-      HIP_OK(hipMemcpyAsync(n_now, &st->ctr->cnt[iterations % kMaxIt][0], sizeof n_now,
-                            hipMemcpyDeviceToHost, stream));
-      HIP_OK(hipStreamSynchronize(stream));
-      n_est = 0;
-      for (int x = 0; x < kXcd; ++x) n_est += n_now[x];
-    }
+    if ((rc = launch_wavefront(p, st, stream, extend_kernel, ev, &iterations))) return rc;
   }
   float* dst = out_dev ? out_dev : st->out;
   if (npix > 0) {
@@ -1633,43 +1437,9 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   }
 
   if (stats) {
-    memset(stats, 0, sizeof *stats);
-    Counters hc;
-    HIP_OK(hipMemcpy(&hc, st->ctr, offsetof(Counters, cnt), hipMemcpyDeviceToHost));
-    stats->samples = (uint64_t)npix * ss;
-    stats->segments = hc.segments;
-    stats->stack_pushes = hc.pushes;
-    stats->overflow_samples = hc.overflow;
-    stats->extend_rays = hc.segments;
-    stats->shade_rays = hc.segments;
+    if ((rc = fill_stats(stats, s, ds, st, p, sp, mode, ft_set, rows, iterations, ev))) return rc;
     stats->ms_total = std::chrono::duration<double, std::milli>(t_end - t_start).count();
-    stats->n_extend_launches = n_ext;
-    stats->n_shade_launches = n_sh;
-    stats->iterations = iterations;
-    stats->rows = (int32_t)rows;
-    stats->mode = mode;
-    stats->path_slots = (int32_t)P;
-    stats->kernel_features = mode == RT_MODE_FUSED ? (int32_t)ft_set : (int32_t)FT_ALL;
-    stats->scene_features = (int32_t)feats;
-    stats->tree_width = tree;
-    stats->chunk_samples = (int32_t)K;
-    stats->record_boxes = tree == 0 ? ds->brute_boxes : 0;
     stats->tuned = tuned;
-    stats->chunk_records = p.csum ? 1 : 0;
-    stats->lds_scene = mode == RT_MODE_FUSED ? (f_lds ? 1 : 0) : (lds_nodes ? 1 : 0);
-    auto sum_ms = [&](const std::vector<std::pair<int, int>>& v, double* acc) -> int {
-      for (auto& pr : v) {
-        float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, st->events[pr.first], st->events[pr.second]));
-        *acc += ms;
-      }
-      return RT_OK;
-    };
-    if (prof) {
-      if ((rc = sum_ms(ev_ext, &stats->ms_extend)) || (rc = sum_ms(ev_shade, &stats->ms_shade)) ||
-          (rc = sum_ms(ev_fused, &stats->ms_fused)))
-        return rc;
-    }
   }
   return RT_OK;
 }
@@ -1698,15 +1468,11 @@ static int render_multi(rt_scene* scene, const rt_camera* cam, const rt_render_o
   if (o.nranks > 1 || o.rank != 0)
     return set_error(RT_ERR_INVALID, "rt_render_multi: shards the image itself (rank/nranks)");
   if (o.stream) return set_error(RT_ERR_INVALID, "rt_render_multi: one stream per share (opts.stream)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return set_error(RT_ERR_DEVICE, "rt_render_multi: no HIP device available");
+  int rc;
   for (int i = 0; i < n; ++i)
-    if (devices[i] < 0 || devices[i] >= ndev)
-      return set_error(RT_ERR_INVALID, "rt_render_multi: device %d of %d", devices[i], ndev);
+    if ((rc = device_ok("rt_render_multi", devices[i]))) return rc;
   rt_camera_derived cd;
-  int rc = rt_camera_derive(cam, &cd);
-  if (rc) return rc;
+  if ((rc = rt_camera_derive(cam, &cd))) return rc;
   Scene* s = &scene->s;
   std::lock_guard<std::mutex> multi(s->multi_mu);
   const auto t0 = std::chrono::steady_clock::now();
@@ -1794,32 +1560,10 @@ static int render_multi(rt_scene* scene, const rt_camera* cam, const rt_render_o
     HIP_OK(hipSetDevice(d0));
   }
   // rt_progress: this call's shares are the tracked render unless another holds it.
-  // Claimed only after every early return of the setup above; the guard is built in
-  // the same statement sequence, so every return below releases it.
-  bool track = false;
-  {
-    std::lock_guard<std::mutex> lk(s->prog.mu);
-    if (!s->prog.busy) {
-      track = true;
-      s->prog.total = (uint64_t)H * W * cd.spp_sqrt * cd.spp_sqrt;
-      s->prog.done = 0;
-      s->prog.device = d0;
-      s->prog.events.clear();  // no slice events: the shares add their samples when done
-      s->prog.cum.clear();
-      s->prog.busy = 1;
-    }
-  }
-  struct ProgressDone {  // every return path below ends the tracked state
-    Progress& p;
-    bool track;
-    bool ok = false;
-    ~ProgressDone() {
-      if (!track) return;
-      std::lock_guard<std::mutex> lk(p.mu);
-      if (ok) p.done = p.total;
-      p.busy = 0;
-    }
-  } prog_done{s->prog, track};
+  // Claimed only after every early return of the setup above, so every return below
+  // releases it.  (No slice events: the shares add their samples when done.)
+  const bool track = claim_progress(s->prog, (uint64_t)H * W * cd.spp_sqrt * cd.spp_sqrt, d0);
+  ProgressDone prog_done{s->prog, track};
   std::vector<rt_stats> st(n);
   std::vector<int> rcs(n, RT_OK);
   std::vector<std::string> errs(n);
@@ -1949,23 +1693,6 @@ int rt_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
   return n;
-}
-
-int rt_scene_export_qbvh(const rt_scene* sc, float* items, int32_t* n_items, float* nodes4,
-                         int32_t* n_nodes4, uint32_t* root4) {
-  if (!sc) return rt::set_error(RT_ERR_INVALID, "rt_scene_export_qbvh: null");
-  const rt::HostScene& h = sc->s.h;
-  std::vector<rt::F4> recs, qb;
-  rt::build_leaf_records(h, recs);
-  size_t n = 0;
-  const int rc = rt::build_qbvh(h, recs, &qb, &n);
-  if (rc != RT_OK) return rc;
-  if (n_items) *n_items = (int32_t)n;
-  if (n_nodes4) *n_nodes4 = (int32_t)(h.nodes4.size() / 8);
-  if (root4) *root4 = h.root4;
-  if (items && n) memcpy(items, qb.data(), n * 64);
-  if (nodes4 && !h.nodes4.empty()) memcpy(nodes4, h.nodes4.data(), h.nodes4.size() * 16);
-  return RT_OK;
 }
 
 }  // extern "C"

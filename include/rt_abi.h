@@ -336,6 +336,13 @@ int rt_scene_export_prim_bounds(const rt_scene* s, float* bounds, int32_t* n);
  * structural tests.  NULL pointers query the counts. */
 int rt_scene_export_qbvh(const rt_scene* s, float* items, int32_t* n_items, float* nodes4,
                          int32_t* n_nodes4, uint32_t* root4);
+/* the record loop's pair array as uploaded for scenes small enough to have one (rt_device.h
+ * "record-loop pair layout"): 4 float4 per slot, then shade_n float4 of the lean kernel's
+ * shade table (0: none), so 16 * n_slots + 4 * shade_n floats; the seven layout counts in
+ * rt_brute_shape's order; the boxes tested as slabs.  n_slots = 0 when the scene is too large
+ * to have pairs.  NULL pointers query the sizes. */
+int rt_scene_export_records(const rt_scene* s, float* pairs, int32_t* n_slots, int32_t counts[7],
+                            int32_t* shade_n, int32_t* n_boxes);
 
 enum {
   RT_FLAG_PROFILE = 1,     /* time every kernel with HIP events */

@@ -23,6 +23,55 @@ def _room(t):
     return world, lights
 
 
+def cornell_room(rt, boxes=2, lights=1):
+    """The Cornell box of the demo scene through the public constructors, with 0-2 boxes
+    and 1-2 quad lights."""
+    t = rt.Tree(1)
+    red, white, green = (t.lambertian(c) for c in ((.65, .05, .05), (.73, .73, .73), (.12, .45, .15)))
+    lm = t.light((15, 15, 15))
+    world = t.list()
+    t.add(world, t.quad((555, 0, 0), (0, 555, 0), (0, 0, 555), green))
+    t.add(world, t.quad((0, 0, 0), (0, 555, 0), (0, 0, 555), red))
+    t.add(world, t.quad((0, 0, 0), (555, 0, 0), (0, 0, 555), white))
+    t.add(world, t.quad((555, 555, 555), (-555, 0, 0), (0, 0, -555), white))
+    t.add(world, t.quad((0, 0, 555), (555, 0, 0), (0, 555, 0), white))
+    ll = t.list()
+    t.add(ll, t.quad((343, 550, 332), (-130, 0, 0), (0, 0, -105), lm))
+    if lights == 2:
+        t.add(ll, t.quad((150, 550, 150), (-60, 0, 0), (0, 0, -60), lm))
+    t.add(world, ll)
+    if boxes >= 1:
+        b1 = t.box((0, 0, 0), (165, 330, 165), white)
+        t.add(world, t.translate(t.rotate_y(b1, 15), (265, 0, 295)))
+    if boxes >= 2:
+        b2 = t.box((0, 0, 0), (165, 165, 165), white)
+        t.add(world, t.translate(t.rotate_y(b2, -18), (130, 0, 65)))
+    _, cam, _, _ = rt.demo_scene("cornell")
+    return t, cam, t.bvh(world), ll
+
+
+def tilted_room(rt, n=20):
+    """The room of test_record_loop_lds_budget_with_shade_table with n tilted quads (20: 23
+    records, a layout outside the list)."""
+    t = rt.Tree(5)
+    world, lights = _room(t)
+    grey = t.lambertian((0.6, 0.5, 0.4))
+    for i in range(n):
+        x, z = -6 + (i % 6) * 2.3, -3 + (i // 6) * 1.7
+        t.add(world, t.quad((x, 0.5 + 0.1 * i, z), (0.9, 0.3, 0.1), (0.1, 1.1, 0.4), grey))
+    return t, _cam(rt, (0, 4, -14), (0, 2, 0)), world, lights
+
+
+def record_scene(rt, name):
+    """The record-loop scenes shared by test_brute_shape_gpu.py and test_records.py."""
+    if name in ("cornell", "quads"):
+        return rt.demo_scene(name)
+    if name == "tilted_room":
+        return tilted_room(rt)
+    boxes, lights = {"no_boxes": (0, 1), "one_box": (1, 1), "two_lights": (2, 2)}[name]
+    return cornell_room(rt, boxes, lights)
+
+
 def fog(rt):
     """camera inside a huge constant medium (book2 fog, main.go:139-140)."""
     t = rt.Tree(1)

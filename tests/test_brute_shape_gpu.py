@@ -46,56 +46,6 @@ def test_unlisted_layouts_are_generic(rt):
     assert _shape(rt, (0, 0, 0, 0, 0, 0, 0)) == 0
 
 
-def _cornell(rt, boxes=2, lights=1):
-    """The Cornell box of the demo scene through the public constructors, with 0-2 boxes
-    and 1-2 quad lights."""
-    t = rt.Tree(1)
-    red, white, green = (t.lambertian(c) for c in ((.65, .05, .05), (.73, .73, .73), (.12, .45, .15)))
-    lm = t.light((15, 15, 15))
-    world = t.list()
-    t.add(world, t.quad((555, 0, 0), (0, 555, 0), (0, 0, 555), green))
-    t.add(world, t.quad((0, 0, 0), (0, 555, 0), (0, 0, 555), red))
-    t.add(world, t.quad((0, 0, 0), (555, 0, 0), (0, 0, 555), white))
-    t.add(world, t.quad((555, 555, 555), (-555, 0, 0), (0, 0, -555), white))
-    t.add(world, t.quad((0, 0, 555), (555, 0, 0), (0, 555, 0), white))
-    ll = t.list()
-    t.add(ll, t.quad((343, 550, 332), (-130, 0, 0), (0, 0, -105), lm))
-    if lights == 2:
-        t.add(ll, t.quad((150, 550, 150), (-60, 0, 0), (0, 0, -60), lm))
-    t.add(world, ll)
-    if boxes >= 1:
-        b1 = t.box((0, 0, 0), (165, 330, 165), white)
-        t.add(world, t.translate(t.rotate_y(b1, 15), (265, 0, 295)))
-    if boxes >= 2:
-        b2 = t.box((0, 0, 0), (165, 165, 165), white)
-        t.add(world, t.translate(t.rotate_y(b2, -18), (130, 0, 65)))
-    _, cam, _, _ = rt.demo_scene("cornell")
-    return t, cam, t.bvh(world), ll
-
-
-def _tilted_room(rt):
-    """The room of test_record_loop_lds_budget_with_shade_table with 20 tilted quads: 23
-    records, a layout outside the list."""
-    t = rt.Tree(5)
-    world, lights = scenes._room(t)
-    grey = t.lambertian((0.6, 0.5, 0.4))
-    for i in range(20):
-        x, z = -6 + (i % 6) * 2.3, -3 + (i // 6) * 1.7
-        t.add(world, t.quad((x, 0.5 + 0.1 * i, z), (0.9, 0.3, 0.1), (0.1, 1.1, 0.4), grey))
-    return t, scenes._cam(rt, (0, 4, -14), (0, 2, 0)), world, lights
-
-
-def _scene(rt, name):
-    if name == "cornell":
-        return rt.demo_scene("cornell")
-    if name == "quads":
-        return rt.demo_scene("quads")
-    if name == "tilted_room":
-        return _tilted_room(rt)
-    boxes, lights = {"no_boxes": (0, 1), "one_box": (1, 1), "two_lights": (2, 2)}[name]
-    return _cornell(rt, boxes, lights)
-
-
 def _both(rt, tune, t, cam, w, l, record_loop=True, **kw):
     out = []
     for flag in ("0", "1"):
@@ -120,7 +70,7 @@ def test_shaped_record_loop_matches_generic(rt, gpu, tune, name):
     boxes and with one box are listed layouts; the quads demo (general pairs, another
     feature set), the 23-record room and a Cornell with two lights are not, so both settings
     run the generic kernel there."""
-    t, cam, w, l = _scene(rt, name)
+    t, cam, w, l = scenes.record_scene(rt, name)
     cam.Width, cam.SamplesPerPixel = 48, 16
     st = _both(rt, tune, t, cam, w, l, record_loop=name != "quads", seed=5)
     if name in ("cornell", "no_boxes", "one_box", "two_lights"):
@@ -139,3 +89,21 @@ def test_shaped_record_loop_with_progress_slices(rt, gpu, tune):
     with rt.Scene(t, w, l) as sc:
         one, st = sc.render(cam, seed=5)
     assert st["segments"] == sliced["segments"]
+
+
+@pytest.mark.gpu
+def test_brute_max_raised_after_upload_takes_the_bvh4(rt, gpu, tune):
+    """A room of 103 leaf entries (over the 64 a device copy carries record pairs and a BVH2
+    for, under 128) renders through the BVH4.  RT_BRUTE_MAX=128 set after the upload asks for
+    the record loop, whose pairs this copy does not have: the render keeps the BVH4, bit for
+    bit, as the feature pass always did."""
+    t, cam, w, l = scenes.tilted_room(rt, 100)
+    cam.Width, cam.SamplesPerPixel = 32, 4
+    with rt.Scene(t, w, l) as sc:
+        assert 64 < len(sc.export_bvh()[1]) < 128
+        a, sa = sc.render(cam, seed=7)
+        tune("RT_BRUTE_MAX", "128")
+        b, sb = sc.render(cam, seed=7)
+    assert sa["tree_width"] == 4 and sb["tree_width"] == 4
+    assert np.isfinite(a).all()
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
