@@ -9,16 +9,17 @@ through the HIP path (camera.go:156).  There is no CPU render path here: the
 HIP library must be built and a GPU present, otherwise calls raise.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 
 from . import _lib
 from ._lib import (RT_FT_ALL, RT_FT_BOX, RT_NOISE_MARBLE, RT_NOISE_PERLIN,  # noqa: F401
-                   RT_NOISE_TURBULENT, RtAov, RtCamera, RtDenoiseOpts,
+                   RT_NOISE_TURBULENT, RtAccumInfo, RtAov, RtCamera, RtDenoiseOpts,
                    RtCameraDerived, RtError, RtRenderOpts, RtSceneInfo, RtStats, RtTreeView,
                    check, lib)
 
-__all__ = ["Tree", "Camera", "Scene", "quantize", "format_ppm", "device_count", "RtError",
+__all__ = ["Tree", "Camera", "Scene", "Accumulator", "quantize", "format_ppm", "device_count", "RtError",
            "tune", "untune", "tuning", "tune_knobs", "tune_from_env",
            "demo_scene", "DEMO_SCENES", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
            "format_ppm_device", "denoise", "denoise_device"]
@@ -378,9 +379,12 @@ class Scene:
         self._p = p
         self._destroy = lib().rt_scene_destroy  # usable at interpreter shutdown
         self.tree = tree
+        self._accums = weakref.WeakSet()
 
     def close(self):
         if getattr(self, "_p", None):
+            for a in list(self._accums):  # rt_scene_destroy frees them: their handles die here
+                a._p = None
             self._destroy(self._p)
             self._p = None
 
@@ -554,6 +558,110 @@ class Scene:
         check(lib().rt_render_aov_device(self._p, C.byref(c), C.byref(o), n_samples, C.byref(a),
                                          C.byref(st)))
         return {f: getattr(st, f) for f, _ in RtStats._fields_}
+
+    def accumulator(self, camera, max_passes=0, device=0, rank=0, nranks=1, path_slots=0, chunk=0,
+                    profile=False, stream=None, mode="auto", progress_slices=0):
+        """A progressive pass accumulator (rt_accum_create) for this rank's rows of `camera`:
+        see Accumulator.  max_passes=0 means 1024."""
+        return Accumulator(self, camera, max_passes, device, rank, nranks, path_slots, chunk,
+                           profile, stream, mode, progress_slices)
+
+
+class Accumulator:
+    """The exact running sum of render passes of one camera, kept on the device (rt_accum).
+
+    ``add(seed)`` renders one pass, exactly the samples ``Scene.render(camera, seed=seed)``
+    computes, and adds it to per-pixel integer sums, so the resolved image is a function of
+    the set of seeds, not of their order, and one pass resolves to ``Scene.render``'s bits.
+    ``resolve()`` returns the running mean image and the per-pixel variance of its luminance,
+    ``info()`` one error figure for the whole image, ``render_until()`` adds passes until that
+    figure is small enough.  A context manager; closing the scene closes its accumulators."""
+
+    def __init__(self, scene, camera, max_passes=0, device=0, rank=0, nranks=1, path_slots=0,
+                 chunk=0, profile=False, stream=None, mode="auto", progress_slices=0):
+        self._p = None
+        d = camera.derived()
+        self.shape = (len(range(rank, d.height, nranks)), d.width)
+        c = camera.to_c()
+        o = Scene._opts(0, device, rank, nranks, path_slots, chunk, profile, stream, mode)
+        o.progress_slices = progress_slices
+        p = C.c_void_p()
+        check(lib().rt_accum_create(scene._p, C.byref(c), C.byref(o), max_passes, C.byref(p)))
+        self._p = p
+        self._destroy = lib().rt_accum_destroy  # usable at interpreter shutdown
+        self.scene = scene
+        scene._accums.add(self)
+
+    def close(self):
+        if getattr(self, "_p", None):
+            self._destroy(self._p)
+            self._p = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _h(self):
+        if not self._p:
+            raise ValueError("Accumulator is closed")
+        return self._p
+
+    def add(self, seed):
+        """One pass with render seed `seed` (rt_accum_add) -> the pass's stats dict."""
+        st = RtStats()
+        check(lib().rt_accum_add(self._h(), seed, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in RtStats._fields_}
+
+    def resolve(self):
+        """(rgb float32 [rows, W, 3]: the mean of all passes, var float32 [rows, W]: the
+        variance of its luminance, 0 before the second pass)."""
+        rgb = np.zeros(self.shape + (3,), np.float32)
+        var = np.zeros(self.shape, np.float32)
+        check(lib().rt_accum_resolve(self._h(), rgb.ctypes.data, var.ctypes.data))
+        return rgb, var
+
+    def resolve_device(self, rgb_tensor, var_tensor=None):
+        """rt_accum_resolve_device into contiguous float32 torch tensors on the accumulator's
+        device: rgb [rows, W, 3] (or None) and var [rows, W] (or None)."""
+        import torch
+        for t, shape in ((rgb_tensor, self.shape + (3,)), (var_tensor, self.shape)):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()
+                                  or tuple(t.shape) != shape or not t.is_cuda):
+                raise ValueError(f"resolve_device: needs a contiguous float32 device tensor of shape {shape}")
+        check(lib().rt_accum_resolve_device(
+            self._h(), None if rgb_tensor is None else rgb_tensor.data_ptr(),
+            None if var_tensor is None else var_tensor.data_ptr()))
+
+    def info(self):
+        """rt_accum_info as a dict: passes, max_passes, samples_per_pixel, nonfinite_pixels,
+        rms_std_error, mean_luminance, rel_error."""
+        i = RtAccumInfo()
+        check(lib().rt_accum_info_get(self._h(), C.byref(i)))
+        return {f: getattr(i, f) for f, _ in RtAccumInfo._fields_}
+
+    def reset(self):
+        check(lib().rt_accum_reset(self._h()))
+
+    @property
+    def passes(self):
+        return self.info()["passes"]
+
+    def render_until(self, rel_error, max_passes, seed=1):
+        """Add passes with seeds seed, seed + 1, ... (pass number p of the accumulator takes
+        seed + p, so a second call goes on where the first stopped) until
+        info()["rel_error"] <= rel_error (checked from the second pass on: one pass has no
+        variance) or the accumulator holds max_passes passes.  Returns the last info()."""
+        i = self.info()
+        while i["passes"] < max_passes:
+            self.add(seed + i["passes"])
+            i = self.info()
+            if i["passes"] >= 2 and i["rel_error"] <= rel_error:
+                break
+        return i
 
 
 def _multi(scene, camera, devices, out_ptr, seed, path_slots, chunk, profile, mode, rccl=False):

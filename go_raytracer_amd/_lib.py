@@ -105,6 +105,13 @@ class RtDenoiseOpts(C.Structure):
                 ("sigma_depth", C.c_float), ("_pad", C.c_int32)]
 
 
+class RtAccumInfo(C.Structure):  # rt_accum_info
+    _fields_ = [("passes", C.c_int32), ("max_passes", C.c_int32),
+                ("samples_per_pixel", C.c_uint64), ("nonfinite_pixels", C.c_uint64),
+                ("rms_std_error", C.c_double), ("mean_luminance", C.c_double),
+                ("rel_error", C.c_double)]
+
+
 class RtTreeView(C.Structure):
     _fields_ = [
         ("nodes", C.c_void_p), ("n_nodes", C.c_int32),
@@ -222,6 +229,14 @@ SIGNATURES = {
                         C.c_void_p]),
     "rt_denoise_device": (_I, [C.c_void_p, C.POINTER(RtAov), _I, _I, C.POINTER(RtDenoiseOpts),
                                C.c_void_p, _I, C.c_void_p]),
+    "rt_accum_create": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
+                             C.POINTER(_P)]),
+    "rt_accum_destroy": (_I, [_P]),
+    "rt_accum_reset": (_I, [_P]),
+    "rt_accum_add": (_I, [_P, C.c_uint64, C.POINTER(RtStats)]),
+    "rt_accum_resolve": (_I, [_P, C.c_void_p, C.c_void_p]),
+    "rt_accum_resolve_device": (_I, [_P, C.c_void_p, C.c_void_p]),
+    "rt_accum_info_get": (_I, [_P, C.POINTER(RtAccumInfo)]),
     "rt_demo_scene": (_I, [_P, C.c_char_p, C.c_char_p, C.POINTER(RtCamera), C.POINTER(_I),
                            C.POINTER(_I)]),
     "rt_demo_scene_name": (_I, [_I, C.POINTER(C.c_char_p)]),

@@ -46,6 +46,21 @@ struct Params;
 void set_camera_params(Params& p, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t npix);
 uint32_t rank_rows(uint32_t H, int rank, int nranks);
 
+// rt_render.hip, for the accumulator (rt_accum.hip): one render pass of rt_render's own
+// path (slot 0, the same plans, launches, buffers and mutex) that hands its sums to a sink
+// instead of resolving them.  fold runs where k_resolve would: the pass's launches are
+// enqueued on `stream`, p holds what k_resolve reads (accum, csum, side, pflags) and scale is
+// pixel_samples_scale; render_pass synchronises the stream after it.  max_passes: a sample
+// stays in the exact fixed-point sum below 2^31 / (spp_sqrt^2 * max_passes), so the sum over
+// that many passes stays inside int64 (Params::vlim; 1 is rt_render's limit).
+struct PassSink {
+  uint32_t max_passes;
+  int (*fold)(void* ctx, const Params& p, double scale, hipStream_t stream);
+  void* ctx;
+};
+int render_pass(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
+                const PassSink* sink);
+
 // Grow-only device scratch, one buffer per device ordinal (as rt_output.hip's): no allocation
 // per call once warm.  The caller serialises its users, and no work that reads an old buffer
 // may be in flight when a larger one is asked for (the old one is freed).

@@ -130,6 +130,7 @@ struct Scene {
   int multi_dev = -1;
   void* rccl = nullptr;                             // RCCL gather state (rt_render.hip RcclGather)
   Progress prog;
+  std::vector<rt_accum*> accums;                    // accumulators alive (rt_accum.hip), under mu
   // the compressed BVH4 (host_qbvh.cpp), built on the host once, at the first render that
   // can traverse it (rt_render.hip ensure_qbvh), then uploaded per device
   std::mutex qb_mu;
@@ -182,6 +183,8 @@ constexpr size_t kBoxLeafMinPrims = 256;
 uint32_t scene_features(const HostScene& h, bool* noise_table0 = nullptr);
 // rt_render.hip
 void release_device(Scene* s);
+// rt_accum.hip: frees the accumulators the scene still owns (release_device calls it first)
+void release_accums(Scene* s);
 // rt_render.hip, for the feature pass (rt_aov.hip): the scene's copy on `device` (the
 // calling thread's current device; uploaded on first use) set up for the structure the fused
 // render of this scene traverses -- tree 0 record loop, 2 BVH2, 4 BVH4, 5 compressed BVH4

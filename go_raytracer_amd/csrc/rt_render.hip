@@ -14,7 +14,8 @@
 //  FUSED — k_fused: persistent threads, one path per lane kept in registers,
 //          trace + shade in a loop, finished lanes refilled from a wave-batched
 //          chunk counter (ballot + one atomic per >=64 chunks).
-// Both end with k_resolve (fixed-point pixel sums -> linear mean RGB).
+// Both end with k_resolve (fixed-point pixel sums -> linear mean RGB), or, for a pass of an
+// accumulator, with rt_accum.hip's fold kernel over the same sums.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
@@ -33,6 +34,7 @@
 #include "rt_hip_util.h"
 #include "rt_path.h"
 #include "rt_fused.h"
+#include "rt_resolve.h"
 
 namespace rt {
 
@@ -149,31 +151,10 @@ __global__ __launch_bounds__(256) void k_resolve(Params P, float* out, double sc
   const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
   if (lp >= P.npix) return;
   const uint32_t f = P.pflags[lp];
-  // the fused kernel's per-chunk sums (SampleAcc::flush): this pixel's chunks are
-  // q * gchunks + sub * gpix + r for its group q, its place r in the group and every
-  // sample block sub (chunk_pixel), summed mod 2^64 like the atomics they replace
+  // the fused kernel's per-chunk sums of this pixel (rt_resolve.h, shared with the
+  // accumulator's fold kernel)
   unsigned long long cs[3] = {0ull, 0ull, 0ull};
-  if (P.csum) {
-    const uint32_t gpix = P.fd_gpix.d, g = fdiv(lp, P.fd_gpix), r = lp - g * gpix;
-#ifdef RT_SWEEP_ORDER
-    const uint32_t q = (g ^ P.gflip) + P.gbase;  // the group's sweep position (an involution)
-#else
-    const uint32_t q = g;
-#endif
-    for (int ph = 0; ph < 2; ++ph) {  // the first phase's chunks, then the tail's (if any)
-      const uint32_t gch = ph ? P.fd_gchunks2.d : P.fd_gchunks.d;
-      const uint32_t cpp = ph && P.S1 >= P.ss ? 0u : gch / gpix;
-      const unsigned long long* rec = P.csum + 4 * ((ph ? (size_t)P.n1 : 0) + (size_t)q * gch + r);
-      // unrolled: eight records' loads in flight per thread before the adds wait (one at a
-      // time, the 655 MB of C2's records were read at ~3.5 TB/s)
-#pragma unroll 8
-      for (uint32_t sb = 0; sb < cpp; ++sb, rec += 4 * (size_t)gpix) {
-        cs[0] += rec[0];
-        cs[1] += rec[1];
-        cs[2] += rec[2];
-      }
-    }
-  }
+  chunk_record_sums(P, lp, cs);
   for (int ch = 0; ch < 3; ++ch) {
     const bool nan = (f & (1u << ch)) != 0, pinf = (f & (8u << ch)) != 0,
                ninf = (f & (64u << ch)) != 0;
@@ -275,6 +256,7 @@ struct RcclGather {
 
 void release_device(Scene* s) {
   DeviceGuard dg;
+  release_accums(s);
   if (s->rccl) {
     static_cast<RcclGather*>(s->rccl)->release();
     delete static_cast<RcclGather*>(s->rccl);
@@ -1218,7 +1200,7 @@ static int fill_stats(rt_stats* stats, const Scene* s, const DeviceScene* ds, co
 
 static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
                        float* out_host, float* out_dev, rt_stats* stats, int slot_id = 0,
-                       const Gather* gather = nullptr) {
+                       const Gather* gather = nullptr, const PassSink* sink = nullptr) {
   if (!scene || !cam) return set_error(RT_ERR_INVALID, "rt_render: null scene/camera");
   rt_render_opts o{};
   if (opts) o = *opts;
@@ -1361,8 +1343,11 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   p.accum = st->accum;
   p.csum = use_csum ? st->csum : nullptr;
   p.side = st->side;
-  // |v| < 2^31 / ss: the ss-sample fixed-point sum of a pixel stays inside int64
-  p.vlim = std::nextafter((float)(2147483648.0 / (double)std::max<uint32_t>(ss, 1u)), 0.0f);
+  // |v| < 2^31 / ss: the ss-sample fixed-point sum of a pixel stays inside int64 (a pass of an
+  // accumulator: the sum of all its max_passes passes, ss * max_passes < 2^31)
+  p.vlim = std::nextafter((float)(2147483648.0 / (double)((uint64_t)std::max<uint32_t>(ss, 1u) *
+                                                          (sink ? std::max<uint32_t>(sink->max_passes, 1u) : 1u))),
+                          0.0f);
   p.pflags = st->pflags;
   p.ostack = st->ostack;
   p.stack_cols = st->ostack_cols;
@@ -1417,7 +1402,9 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     if ((rc = launch_wavefront(p, st, stream, extend_kernel, ev, &iterations))) return rc;
   }
   float* dst = out_dev ? out_dev : st->out;
-  if (npix > 0) {
+  if (npix > 0 && sink) {  // an accumulator's pass: folded into its sums, not resolved
+    if ((rc = sink->fold(sink->ctx, p, cd.pixel_samples_scale, stream))) return rc;
+  } else if (npix > 0) {
     hipLaunchKernelGGL(k_resolve, dim3((npix + 255) / 256), dim3(256), 0, stream, p, dst,
                        cd.pixel_samples_scale);
     HIP_OK(hipGetLastError());
@@ -1442,6 +1429,11 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     stats->tuned = tuned;
   }
   return RT_OK;
+}
+
+int render_pass(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
+                const PassSink* sink) {
+  return render_impl(scene, cam, opts, nullptr, nullptr, stats, 0, nullptr, sink);
 }
 
 // rows of share i ([rows_per][W][3] at gather + i*rows_per*W*3) -> image rows r = i + n*k

@@ -20,7 +20,11 @@
 // the a-trous denoiser before the PPM is written; prints the statistics line with
 // both times), -aov PREFIX (writes PREFIX_albedo.ppm, PREFIX_normal.ppm as
 // n * 0.5 + 0.5 and PREFIX_depth.ppm normalised to the image maximum, through the
-// same PPM writer).  -cpuprofile has no pprof to drive on the GPU path: the file
+// same PPM writer), -passes N (the image as the exact mean of N passes of -spp samples each,
+// seeds seed .. seed + N - 1, through the pass accumulator; -passes 1 writes the plain
+// render's bytes), -until E (stop once the accumulator's rel_error is <= E, checked from the
+// second pass on; at most -passes passes, 1024 without it).  With either, -progress reports
+// passes and the statistics line gains passes, rel_error and ms_accum.  -cpuprofile has no pprof to drive on the GPU path: the file
 // receives the same JSON statistics instead.
 #include <unistd.h>
 
@@ -43,14 +47,15 @@ namespace {
 struct Flag {
   const char* name;
   const char* usage;
-  enum Kind { STR, INT, U64, BOOL } kind;
+  enum Kind { STR, INT, U64, BOOL, F64 } kind;
   void* dst;
   const char* def;  // shown in the usage, Go style
 };
 
 struct Args {
   std::string cpuprofile, out = "image.ppm", mode = "auto", assets, aov;
-  long long N = 1, S = -1, device = 0, width = 0, spp = 0, depth = 0, slices = 0;
+  long long N = 1, S = -1, device = 0, width = 0, spp = 0, depth = 0, slices = 0, passes = 0;
+  double until = 0.0;
   unsigned long long seed = 1, tree_seed = 1;
   bool progress = false, stats = false, denoise = false;
 };
@@ -72,6 +77,8 @@ std::vector<Flag> flags(Args& a) {
       {"device", "HIP device ordinal", Flag::INT, &a.device, "0"},
       {"mode", "kernel strategy: auto, fused or wavefront", Flag::STR, &a.mode, "auto"},
       {"o", "Specify a custom output file", Flag::STR, &a.out, "image.ppm"},
+      {"passes", "render N passes of -spp samples each (seeds seed .. seed+N-1) and write their exact mean",
+       Flag::INT, &a.passes, "0"},
       {"progress", "print render progress on stderr", Flag::BOOL, &a.progress, ""},
       {"seed", "render seed (Philox key)", Flag::U64, &a.seed, "1"},
       {"slices", "progress granularity: launches per render (0 = 20 with -progress)", Flag::INT,
@@ -80,6 +87,8 @@ std::vector<Flag> flags(Args& a) {
       {"stats", "print render statistics (JSON) on stderr", Flag::BOOL, &a.stats, ""},
       {"tree-seed", "seed of the scene builder's rand (main.go's math/rand)", Flag::U64,
        &a.tree_seed, "1"},
+      {"until", "add passes until the image's relative standard error is <= E (at most -passes, default 1024)",
+       Flag::F64, &a.until, "0"},
       {"width", "override Camera.Width (0 = the scene's)", Flag::INT, &a.width, "0"},
   };
 }
@@ -88,9 +97,9 @@ void usage(const char* prog, const std::vector<Flag>& fl) {
   fprintf(stderr, "Usage of %s:\n", prog);
   for (const Flag& f : fl) {
     const char* ty = f.kind == Flag::STR ? " string" : f.kind == Flag::INT ? " int"
-                     : f.kind == Flag::U64 ? " uint" : "";
+                     : f.kind == Flag::U64 ? " uint" : f.kind == Flag::F64 ? " float" : "";
     fprintf(stderr, "  -%s%s\n    \t%s", f.name, ty, f.usage);
-    if (f.def && *f.def && !(f.kind == Flag::INT && !strcmp(f.def, "0")))
+    if (f.def && *f.def && !((f.kind == Flag::INT || f.kind == Flag::F64) && !strcmp(f.def, "0")))
       fprintf(stderr, f.kind == Flag::STR ? " (default \"%s\")" : " (default %s)", f.def);
     fprintf(stderr, "\n");
   }
@@ -113,6 +122,12 @@ bool set_value(const Flag& f, const std::string& v) {
       unsigned long long x = strtoull(v.c_str(), &end, 0);
       if (*end || errno) return false;
       *(unsigned long long*)f.dst = x;
+      return true;
+    }
+    case Flag::F64: {
+      double x = strtod(v.c_str(), &end);
+      if (v.empty() || *end || errno) return false;
+      *(double*)f.dst = x;
       return true;
     }
     case Flag::BOOL: {
@@ -191,16 +206,20 @@ int fail(const char* what, int rc) {
 }
 
 std::string stats_json(const rt_stats& st, const rt_camera_derived& d, const char* scene,
-                       double wall_s, int aov_samples, double ms_aov, double ms_denoise) {
-  char b[1024];
+                       double wall_s, int aov_samples, double ms_aov, double ms_denoise,
+                       const rt_accum_info* acc, double ms_accum) {
+  char b[1024], extra[160] = "";
+  if (acc)  // -passes / -until
+    snprintf(extra, sizeof extra, "\"passes\": %d, \"rel_error\": %.6g, \"ms_accum\": %.3f, ", acc->passes,
+             acc->rel_error, ms_accum);
   snprintf(b, sizeof b,
            "{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"spp\": %d, \"max_depth\": %d, "
            "\"samples\": %" PRIu64 ", \"segments\": %" PRIu64 ", \"ms_render\": %.3f, "
            "\"samples_per_s\": %.6g, \"mode\": %d, \"tree_width\": %d, \"chunk_samples\": %d, "
-           "\"aov_samples\": %d, \"ms_aov\": %.3f, \"ms_denoise\": %.3f, \"wall_s\": %.3f}",
+           "\"aov_samples\": %d, \"ms_aov\": %.3f, \"ms_denoise\": %.3f, %s\"wall_s\": %.3f}",
            scene, d.width, d.height, d.spp_sqrt * d.spp_sqrt, d.max_depth, st.samples,
            st.segments, st.ms_total, st.ms_total > 0 ? st.samples / (st.ms_total * 1e-3) : 0.0,
-           st.mode, st.tree_width, st.chunk_samples, aov_samples, ms_aov, ms_denoise, wall_s);
+           st.mode, st.tree_width, st.chunk_samples, aov_samples, ms_aov, ms_denoise, extra, wall_s);
   return b;
 }
 
@@ -275,23 +294,73 @@ int main(int argc, char** argv) {
   rt_stats st;
   memset(&st, 0, sizeof st);
 
+  // -passes / -until: the image is the accumulator's mean over the passes
+  const bool accumulate = a.passes > 0 || a.until > 0.0;
+  if (a.passes < 0 || a.passes > 0x7FFFFFFF || !(a.until >= 0.0)) {
+    fprintf(stderr, "invalid value for flag -passes / -until\n");
+    fclose(out);
+    return 2;
+  }
+  const int32_t pass_cap = (int32_t)(a.passes > 0 ? a.passes : 1024);
+  rt_accum* acc = nullptr;
+  rt_accum_info ai;
+  memset(&ai, 0, sizeof ai);
+  double ms_accum = 0.0;
+  if (accumulate && (rc = rt_accum_create(sc, &cam, &o, pass_cap, &acc)) != RT_OK)
+    return fail("rt_accum_create", rc);
+
   std::atomic<bool> rendering{true};
+  std::atomic<int> pass_no{0};
   std::thread bar;
   if (a.progress) {
     bar = std::thread([&] {
       uint64_t done = 0, total = 0;
       while (rendering.load()) {
-        if (rt_progress(sc, &done, &total) == RT_OK && total)
-          fprintf(stderr, "\rrendering %s: %5.1f%%", scene, 100.0 * done / total);
+        if (rt_progress(sc, &done, &total) == RT_OK && total) {
+          if (accumulate)
+            fprintf(stderr, "\rrendering %s: pass %d of %d, %5.1f%%", scene, pass_no.load() + 1, pass_cap,
+                    100.0 * done / total);
+          else
+            fprintf(stderr, "\rrendering %s: %5.1f%%", scene, 100.0 * done / total);
+        }
         std::this_thread::sleep_for(std::chrono::milliseconds(100));
       }
     });
   }
-  rc = rt_render(sc, &cam, &o, rgb.data(), &st);
+  const char* what = "rt_render";
+  if (!accumulate) {
+    rc = rt_render(sc, &cam, &o, rgb.data(), &st);
+  } else {
+    auto tp = std::chrono::steady_clock::now();
+    for (int32_t p = 0; p < pass_cap && rc == RT_OK; ++p) {
+      rt_stats sp;
+      pass_no = p;
+      what = "rt_accum_add";
+      if ((rc = rt_accum_add(acc, a.seed + (uint64_t)p, &sp)) != RT_OK) break;
+      const uint64_t samples = st.samples + sp.samples, segments = st.segments + sp.segments;
+      const double ms = st.ms_total + sp.ms_total;
+      st = sp;  // the last pass's, with the totals over the passes
+      st.samples = samples;
+      st.segments = segments;
+      st.ms_total = ms;
+      if (a.until > 0.0 && p >= 1) {
+        what = "rt_accum_info_get";
+        if ((rc = rt_accum_info_get(acc, &ai)) != RT_OK || ai.rel_error <= a.until) break;
+      }
+    }
+    if (rc == RT_OK) {
+      what = "rt_accum_resolve";
+      if ((rc = rt_accum_resolve(acc, rgb.data(), nullptr)) == RT_OK) rc = rt_accum_info_get(acc, &ai);
+    }
+    ms_accum = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
+  }
   rendering = false;
   if (bar.joinable()) bar.join();
-  if (a.progress) fprintf(stderr, "\rrendering %s: 100.0%%\n", scene);
-  if (rc != RT_OK) return fail("rt_render", rc);
+  if (a.progress && accumulate)
+    fprintf(stderr, "\rrendering %s: %d passes, 100.0%%      \n", scene, ai.passes);
+  else if (a.progress)
+    fprintf(stderr, "\rrendering %s: 100.0%%\n", scene);
+  if (rc != RT_OK) return fail(what, rc);
 
   // -denoise / -aov: the feature buffers of the same camera rays, then the filter
   int aov_samples = 0;
@@ -332,7 +401,8 @@ int main(int argc, char** argv) {
   // camera.go:160 header + PrintColor per pixel, then main.go:477's single write
   if (write_ppm(rgb, d.width, d.height, out, a.out.c_str())) return 1;
   double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  std::string js = stats_json(st, d, scene, wall, aov_samples, ms_aov, ms_denoise);
+  std::string js = stats_json(st, d, scene, wall, aov_samples, ms_aov, ms_denoise, accumulate ? &ai : nullptr,
+                              ms_accum);
   if (a.stats || a.denoise) fprintf(stderr, "%s\n", js.c_str());
   if (!a.cpuprofile.empty()) {
     FILE* p = fopen(a.cpuprofile.c_str(), "w");

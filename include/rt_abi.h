@@ -531,6 +531,60 @@ int rt_denoise(const float* rgb, const rt_aov* feat, int w, int h, const rt_deno
 int rt_denoise_device(const float* rgb_dev, const rt_aov* feat_dev, int w, int h,
                       const rt_denoise_opts* opts, float* out_dev, int device, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Progressive pass accumulator (DESIGN.md "Pass accumulator"): the exact    */
+/* sum of any number of render passes of one camera, kept on the device,     */
+/* with a per-pixel variance.  Added without an ABI version change: detect   */
+/* by the symbols.                                                           */
+/* ------------------------------------------------------------------------ */
+typedef struct rt_accum rt_accum;
+
+/* An accumulator for (scene, camera, opts' row share) on opts->device, with no pass yet.
+ * The camera and device, rank / nranks, mode, chunk, path_slots, flags & RT_FLAG_PROFILE,
+ * stream and progress_slices of opts (NULL: the defaults) are fixed here; opts->seed is
+ * ignored (every pass brings its own) and opts->trace_out must be NULL.  max_passes: the most
+ * passes it will take, 0 = 1024; negative, or spp_sqrt^2 * max_passes >= 2^31, is
+ * RT_ERR_INVALID.  Arguments are checked before any device is touched.  About 68 bytes of
+ * device memory per pixel of the share (plus 16 for rt_accum_resolve's staging), allocated
+ * here; no call below allocates.  The scene owns its accumulators: rt_scene_destroy frees
+ * those still alive (their handles are dead after it), rt_accum_destroy frees one early.
+ * Calls on one accumulator serialise; passes and rt_render calls of one scene may interleave
+ * (a pass holds the same per-device lock as rt_render while it runs). */
+int rt_accum_create(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
+                    int32_t max_passes, rt_accum** out);
+int rt_accum_destroy(rt_accum* a);
+/* back to no passes; nothing is reallocated */
+int rt_accum_reset(rt_accum* a);
+/* One pass: exactly the samples rt_render computes for the accumulator's camera and options
+ * with opts->seed = seed, added to the per-pixel sums as 2^-32 fixed-point integers, so the
+ * sums do not depend on the order of the passes.  Samples with |v| >= 2^31 / (spp_sqrt^2 *
+ * max_passes) are summed in fp64 beside them and counted in stats->overflow_samples, as
+ * rt_render does above 2^31 / spp_sqrt^2.  stats (may be NULL) is the pass's own rt_stats.
+ * A pass beyond max_passes returns RT_ERR_INVALID and changes nothing. */
+int rt_accum_add(rt_accum* a, uint64_t seed, rt_stats* stats);
+/* rgb [rows][W][3]: the mean of all samples so far,
+ *   (float)(((double)sum 2^-32 + side) (pixel_samples_scale / passes)),
+ * NaN / +-Inf where a sample was, as rt_render gives them; one pass resolves to rt_render's
+ * image of that seed bit for bit (while no sample overflowed in either), no pass to zeros.
+ * var [rows][W]: the variance of the mean luminance, M2 / ((passes - 1) passes), from
+ * Welford's recurrence over the passes' luminance (0.2126 r + 0.7152 g + 0.0722 b of each
+ * pass's own mean image, in fp64); 0 before the second pass.  Rows as rt_render's.  Either
+ * pointer may be NULL.  _device: pointers on the accumulator's device; both forms return
+ * after the work completes. */
+int rt_accum_resolve(rt_accum* a, float* rgb_host, float* var_host);
+int rt_accum_resolve_device(rt_accum* a, float* rgb_dev, float* var_dev);
+
+typedef struct {
+  int32_t passes, max_passes;
+  uint64_t samples_per_pixel;  /* spp_sqrt^2 * passes */
+  uint64_t nonfinite_pixels;   /* pixels whose variance or mean luminance is not finite */
+  /* over the other pixels: sqrt(mean(var)), mean(luminance), and the first over the second
+   * (+ 1e-6).  A fixed-order fp64 reduction on the device: the same passes in the same order
+   * give the same bits. */
+  double rms_std_error, mean_luminance, rel_error;
+} rt_accum_info;
+int rt_accum_info_get(rt_accum* a, rt_accum_info* out);
+
 /* Demo scenes mirroring main.go (by name or the main.go -S number).
  * names: book1, book2, book3, simple_light, quads, cornell, cornell_smoke, model
  * The camera receives the scene's settings; override fields afterwards. */

@@ -17,7 +17,8 @@ SETS_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 
 
 def main(argv):
-    srcs = [a for a in argv if a.endswith(".hip")] or ["rt_render.hip", "rt_fused_sets.hip"]
+    srcs = [a for a in argv if a.endswith(".hip")] or ["rt_render.hip", "rt_fused_sets.hip", "rt_accum.hip"]
+    srcs = [s for s in srcs if os.path.exists(os.path.join(CSRC, s))]
     extra = [a for a in argv if not a.endswith(".hip")]
     out = ""
     for src in srcs:
@@ -40,7 +41,7 @@ def main(argv):
             cur[key] = val
     for r in rows:
         name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
-        print(f"{name[:60]:60s} vgpr {r.get('VGPRs','?'):>4s} agpr {r.get('AGPRs','?'):>3s} "
+        print(f"{name[:60]:60s} vgpr {r.get('VGPRs','?'):>4s} sgpr {r.get('TotalSGPRs','?'):>4s} agpr {r.get('AGPRs','?'):>3s} "
               f"spill {r.get('VGPRs Spill','?'):>3s} sgpr-spill {r.get('SGPRs Spill','?'):>4s} "
               f"lds {r.get('LDS Size [bytes/block]','?'):>6s} occ {r.get('Occupancy [waves/SIMD]','?')}")
 
