@@ -16,13 +16,14 @@ import numpy as np
 from . import _lib
 from ._lib import (RT_FT_ALL, RT_FT_BOX, RT_NOISE_MARBLE, RT_NOISE_PERLIN,  # noqa: F401
                    RT_NOISE_TURBULENT, RtAccumInfo, RtAov, RtCamera, RtDenoiseOpts,
-                   RtCameraDerived, RtError, RtRenderOpts, RtSceneInfo, RtStats, RtTreeView,
+                   RtDenoiseVarOpts, RtCameraDerived, RtError, RtRenderOpts, RtSceneInfo, RtStats, RtTreeView,
                    check, lib)
 
 __all__ = ["Tree", "Camera", "Scene", "Accumulator", "quantize", "format_ppm", "device_count", "RtError",
            "tune", "untune", "tuning", "tune_knobs", "tune_from_env",
            "demo_scene", "DEMO_SCENES", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
-           "format_ppm_device", "denoise", "denoise_device"]
+           "format_ppm_device", "denoise", "denoise_device", "denoise_var", "denoise_var_device",
+           "RtDenoiseVarOpts"]
 
 DEMO_SCENES = ("book1", "book2", "book3", "simple_light", "quads", "cornell", "cornell_smoke",
                "model")
@@ -580,6 +581,7 @@ class Accumulator:
     def __init__(self, scene, camera, max_passes=0, device=0, rank=0, nranks=1, path_slots=0,
                  chunk=0, profile=False, stream=None, mode="auto", progress_slices=0):
         self._p = None
+        self._device, self._mean, self._var = device, None, None  # denoise_device's tensors
         d = camera.derived()
         self.shape = (len(range(rank, d.height, nranks)), d.width)
         c = camera.to_c()
@@ -635,6 +637,21 @@ class Accumulator:
         check(lib().rt_accum_resolve_device(
             self._h(), None if rgb_tensor is None else rgb_tensor.data_ptr(),
             None if var_tensor is None else var_tensor.data_ptr()))
+
+    def denoise_device(self, aov, out=None, var_out=None, **opts):
+        """The running mean through the variance-guided denoiser, all on the device: resolves
+        into tensors the accumulator owns (allocated on first use, then reused) and runs
+        denoise_var_device(mean, var, aov, out, var_out, **opts).  Returns `out` (a new tensor by
+        default).  Needs two passes: one pass has no variance."""
+        import torch
+        if self.passes < 2:
+            raise ValueError("Accumulator.denoise_device: needs at least 2 passes (no variance yet)")
+        if self._mean is None:
+            dev = torch.device("cuda", self._device)
+            self._mean = torch.empty(self.shape + (3,), dtype=torch.float32, device=dev)
+            self._var = torch.empty(self.shape, dtype=torch.float32, device=dev)
+        self.resolve_device(self._mean, self._var)
+        return denoise_var_device(self._mean, self._var, aov, out=out, var_out=var_out, **opts)
 
     def info(self):
         """rt_accum_info as a dict: passes, max_passes, samples_per_pixel, nonfinite_pixels,
@@ -801,6 +818,76 @@ def denoise_device(rgb, aov=None, out=None, **opts):
         raise ValueError("denoise_device: in place needs a contiguous float32 rgb")
     check(lib().rt_denoise_device(a.data_ptr(), C.byref(f), w, h, C.byref(o), out.data_ptr(),
                                   a.device.index or 0, _stream_of(a)))
+    return out
+
+
+def _denoise_var_opts(iterations=0, demodulate=None, sigma_lum=0.0, sigma_normal=0.0,
+                      sigma_depth=0.0, has_albedo=False):
+    o = RtDenoiseVarOpts()
+    o.iterations = iterations
+    o.demodulate = int(has_albedo if demodulate is None else demodulate)
+    o.sigma_lum, o.sigma_normal, o.sigma_depth = sigma_lum, sigma_normal, sigma_depth
+    return o
+
+
+def denoise_var(rgb, var, aov=None, return_var=False, **opts):
+    """Variance-guided a-trous denoise (rt_denoise_var) of a host float32 [H, W, 3] image and
+    the variance [H, W] of its mean luminance, as Accumulator.resolve returns them, guided by
+    `aov` as denoise is.  opts: iterations (0 = 5), demodulate (default: on when an albedo is
+    given), sigma_lum (0 = 1.0) / sigma_normal / sigma_depth.  Returns a new float32
+    [H, W, 3] array, or with return_var (out, var_out [H, W]: the variance of the filtered
+    image's luminance)."""
+    a = np.ascontiguousarray(rgb, dtype=np.float32)
+    h, w = a.shape[:2]
+    if var is None:
+        raise ValueError("denoise_var: var is required")
+    v = np.ascontiguousarray(var, dtype=np.float32)
+    if v.shape != (h, w):
+        raise ValueError(f"denoise_var: var must have shape {(h, w)}, not {v.shape}")
+    aov = aov or {}
+    keep = [None if aov.get(k) is None else np.ascontiguousarray(aov[k], dtype=np.float32)
+            for k in ("albedo", "normal", "depth")]
+    f = RtAov(*[None if k is None else k.ctypes.data for k in keep], None)
+    o = _denoise_var_opts(has_albedo=keep[0] is not None, **opts)
+    out = np.empty_like(a)
+    vout = np.empty_like(v) if return_var else None
+    check(lib().rt_denoise_var(a.ctypes.data, v.ctypes.data, C.byref(f), w, h, C.byref(o),
+                               out.ctypes.data, None if vout is None else vout.ctypes.data))
+    return (out, vout) if return_var else out
+
+
+def denoise_var_device(rgb, var, aov=None, out=None, var_out=None, **opts):
+    """rt_denoise_var_device on device float32 torch tensors: rgb [H, W, 3], var [H, W]
+    (contiguous float32 on rgb's device), aov as denoise_device's.  `out` may be rgb itself and
+    `var_out` (None: the filtered variance is not written) var itself.  Runs on the tensor's
+    current stream and returns `out` after the work completes."""
+    import torch
+    a = rgb if (rgb.is_contiguous() and rgb.dtype == torch.float32) else \
+        rgb.contiguous().to(torch.float32)
+    h, w = a.shape[:2]
+    for name, t in (("var", var), ("var_out", var_out)):
+        if name == "var_out" and t is None:
+            continue
+        if (t is None or not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous()
+                or tuple(t.shape) != (h, w) or t.device != a.device):
+            raise ValueError(f"denoise_var_device: {name} must be a contiguous float32 tensor of shape "
+                             f"{(h, w)} on rgb's device")
+    aov = aov or {}
+    keep = [None if aov.get(k) is None else aov[k].contiguous().to(torch.float32)
+            for k in ("albedo", "normal", "depth")]
+    f = RtAov(*[None if k is None else k.data_ptr() for k in keep], None)
+    o = _denoise_var_opts(has_albedo=keep[0] is not None, **opts)
+    if out is None:
+        out = torch.empty_like(a)
+    elif (out.dtype != torch.float32 or not out.is_contiguous() or out.shape != a.shape
+          or out.device != a.device):
+        raise ValueError("denoise_var_device: out must be a contiguous float32 tensor of rgb's shape "
+                         "on rgb's device")
+    elif out is rgb and a is not rgb:
+        raise ValueError("denoise_var_device: in place needs a contiguous float32 rgb")
+    check(lib().rt_denoise_var_device(a.data_ptr(), var.data_ptr(), C.byref(f), w, h, C.byref(o),
+                                      out.data_ptr(), None if var_out is None else var_out.data_ptr(),
+                                      a.device.index or 0, _stream_of(a)))
     return out
 
 

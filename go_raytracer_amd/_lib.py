@@ -105,6 +105,12 @@ class RtDenoiseOpts(C.Structure):
                 ("sigma_depth", C.c_float), ("_pad", C.c_int32)]
 
 
+class RtDenoiseVarOpts(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32),
+                ("sigma_lum", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("_pad", C.c_int32)]
+
+
 class RtAccumInfo(C.Structure):  # rt_accum_info
     _fields_ = [("passes", C.c_int32), ("max_passes", C.c_int32),
                 ("samples_per_pixel", C.c_uint64), ("nonfinite_pixels", C.c_uint64),
@@ -229,6 +235,11 @@ SIGNATURES = {
                         C.c_void_p]),
     "rt_denoise_device": (_I, [C.c_void_p, C.POINTER(RtAov), _I, _I, C.POINTER(RtDenoiseOpts),
                                C.c_void_p, _I, C.c_void_p]),
+    "rt_denoise_var": (_I, [C.c_void_p, C.c_void_p, C.POINTER(RtAov), _I, _I,
+                            C.POINTER(RtDenoiseVarOpts), C.c_void_p, C.c_void_p]),
+    "rt_denoise_var_device": (_I, [C.c_void_p, C.c_void_p, C.POINTER(RtAov), _I, _I,
+                                   C.POINTER(RtDenoiseVarOpts), C.c_void_p, C.c_void_p, _I,
+                                   C.c_void_p]),
     "rt_accum_create": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
                              C.POINTER(_P)]),
     "rt_accum_destroy": (_I, [_P]),

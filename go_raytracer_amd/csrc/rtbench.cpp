@@ -18,7 +18,9 @@
 // camera.go:106-108), -slices N (rt_progress granularity), -stats (one JSON
 // line of rt_stats on stderr), -denoise (feature pass at min(spp, 16) samples, then
 // the a-trous denoiser before the PPM is written; prints the statistics line with
-// both times), -aov PREFIX (writes PREFIX_albedo.ppm, PREFIX_normal.ppm as
+// both times), -denoise-var (the same with the variance-guided filter, rt_denoise_var, fed from
+// the pass accumulator's variance: needs -passes N >= 2 or -until; the statistics line gains
+// "denoise_var": 1), -aov PREFIX (writes PREFIX_albedo.ppm, PREFIX_normal.ppm as
 // n * 0.5 + 0.5 and PREFIX_depth.ppm normalised to the image maximum, through the
 // same PPM writer), -passes N (the image as the exact mean of N passes of -spp samples each,
 // seeds seed .. seed + N - 1, through the pass accumulator; -passes 1 writes the plain
@@ -57,7 +59,7 @@ struct Args {
   long long N = 1, S = -1, device = 0, width = 0, spp = 0, depth = 0, slices = 0, passes = 0;
   double until = 0.0;
   unsigned long long seed = 1, tree_seed = 1;
-  bool progress = false, stats = false, denoise = false;
+  bool progress = false, stats = false, denoise = false, denoise_var = false;
 };
 
 std::vector<Flag> flags(Args& a) {
@@ -73,6 +75,8 @@ std::vector<Flag> flags(Args& a) {
        &a.cpuprofile, ""},
       {"denoise", "denoise the image (a-trous filter guided by the feature buffers) before it is written",
        Flag::BOOL, &a.denoise, ""},
+      {"denoise-var", "denoise with the variance-guided filter fed from the accumulator's variance (needs -passes N >= 2 or -until)",
+       Flag::BOOL, &a.denoise_var, ""},
       {"depth", "override Camera.MaxDepth (0 = the scene's)", Flag::INT, &a.depth, "0"},
       {"device", "HIP device ordinal", Flag::INT, &a.device, "0"},
       {"mode", "kernel strategy: auto, fused or wavefront", Flag::STR, &a.mode, "auto"},
@@ -207,11 +211,11 @@ int fail(const char* what, int rc) {
 
 std::string stats_json(const rt_stats& st, const rt_camera_derived& d, const char* scene,
                        double wall_s, int aov_samples, double ms_aov, double ms_denoise,
-                       const rt_accum_info* acc, double ms_accum) {
-  char b[1024], extra[160] = "";
+                       const rt_accum_info* acc, double ms_accum, bool denoise_var) {
+  char b[1024], extra[200] = "";
   if (acc)  // -passes / -until
-    snprintf(extra, sizeof extra, "\"passes\": %d, \"rel_error\": %.6g, \"ms_accum\": %.3f, ", acc->passes,
-             acc->rel_error, ms_accum);
+    snprintf(extra, sizeof extra, "\"passes\": %d, \"rel_error\": %.6g, \"ms_accum\": %.3f, %s", acc->passes,
+             acc->rel_error, ms_accum, denoise_var ? "\"denoise_var\": 1, " : "");
   snprintf(b, sizeof b,
            "{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"spp\": %d, \"max_depth\": %d, "
            "\"samples\": %" PRIu64 ", \"segments\": %" PRIu64 ", \"ms_render\": %.3f, "
@@ -242,6 +246,12 @@ int main(int argc, char** argv) {
   int rc = parse(argc, argv, a);
   if (rc >= 0) return rc;
   auto t0 = std::chrono::steady_clock::now();
+  // the variance comes from the passes: one pass has none (checked before the file is created)
+  if (a.denoise_var && !(a.passes >= 2 || (a.until > 0.0 && a.passes == 0))) {
+    fprintf(stderr, "-denoise-var needs -passes N with N >= 2, or -until\n");
+    usage(argv[0], flags(a));
+    return 2;
+  }
 
   // main.go:434-439: the output file exists before anything renders
   FILE* out = fopen(a.out.c_str(), "wb");
@@ -290,7 +300,7 @@ int main(int argc, char** argv) {
   o.mode = mode;
   o.trace_pixel = -1;
   o.progress_slices = (int32_t)(a.slices > 0 ? a.slices : a.progress ? 20 : 0);
-  std::vector<float> rgb((size_t)d.width * d.height * 3);
+  std::vector<float> rgb((size_t)d.width * d.height * 3), var(a.denoise_var ? (size_t)d.width * d.height : 0);
   rt_stats st;
   memset(&st, 0, sizeof st);
 
@@ -350,7 +360,7 @@ int main(int argc, char** argv) {
     }
     if (rc == RT_OK) {
       what = "rt_accum_resolve";
-      if ((rc = rt_accum_resolve(acc, rgb.data(), nullptr)) == RT_OK) rc = rt_accum_info_get(acc, &ai);
+      if ((rc = rt_accum_resolve(acc, rgb.data(), a.denoise_var ? var.data() : nullptr)) == RT_OK) rc = rt_accum_info_get(acc, &ai);
     }
     ms_accum = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
   }
@@ -365,7 +375,7 @@ int main(int argc, char** argv) {
   // -denoise / -aov: the feature buffers of the same camera rays, then the filter
   int aov_samples = 0;
   double ms_aov = 0.0, ms_denoise = 0.0;
-  if (a.denoise || !a.aov.empty()) {
+  if (a.denoise || a.denoise_var || !a.aov.empty()) {
     const size_t np = (size_t)d.width * d.height;
     std::vector<float> albedo(3 * np), normal(3 * np), depth(np);
     rt_aov f = {albedo.data(), normal.data(), depth.data(), nullptr};
@@ -374,7 +384,15 @@ int main(int argc, char** argv) {
     auto ta = std::chrono::steady_clock::now();
     if ((rc = rt_render_aov(sc, &cam, &o, aov_samples, &f, &sa)) != RT_OK) return fail("rt_render_aov", rc);
     ms_aov = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
-    if (a.denoise) {
+    if (a.denoise_var) {
+      rt_denoise_var_opts vopt;
+      memset(&vopt, 0, sizeof vopt);  // the library defaults
+      vopt.demodulate = 1;
+      auto td = std::chrono::steady_clock::now();
+      if ((rc = rt_denoise_var(rgb.data(), var.data(), &f, d.width, d.height, &vopt, rgb.data(), nullptr)) != RT_OK)
+        return fail("rt_denoise_var", rc);
+      ms_denoise = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
+    } else if (a.denoise) {
       rt_denoise_opts dopt;
       memset(&dopt, 0, sizeof dopt);  // the library defaults
       dopt.demodulate = 1;
@@ -402,8 +420,8 @@ int main(int argc, char** argv) {
   if (write_ppm(rgb, d.width, d.height, out, a.out.c_str())) return 1;
   double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::string js = stats_json(st, d, scene, wall, aov_samples, ms_aov, ms_denoise, accumulate ? &ai : nullptr,
-                              ms_accum);
-  if (a.stats || a.denoise) fprintf(stderr, "%s\n", js.c_str());
+                              ms_accum, a.denoise_var);
+  if (a.stats || a.denoise || a.denoise_var) fprintf(stderr, "%s\n", js.c_str());
   if (!a.cpuprofile.empty()) {
     FILE* p = fopen(a.cpuprofile.c_str(), "w");
     if (!p) {

@@ -531,6 +531,45 @@ int rt_denoise(const float* rgb, const rt_aov* feat, int w, int h, const rt_deno
 int rt_denoise_device(const float* rgb_dev, const rt_aov* feat_dev, int w, int h,
                       const rt_denoise_opts* opts, float* out_dev, int device, void* stream);
 
+typedef struct {
+  int32_t iterations;     /* 0 -> 5; 1..8 */
+  int32_t demodulate;     /* 1: filter rgb / max(albedo, 1e-3), multiply back after */
+  float sigma_lum;        /* 0 -> 1.0  (in standard deviations; the same in every iteration) */
+  float sigma_normal;     /* 0 -> 0.3 */
+  float sigma_depth;      /* 0 -> 0.02 (relative to the pixel's depth) */
+  int32_t _pad;
+} rt_denoise_var_opts;
+
+/* The a-trous filter above with a variance-guided colour weight (the edge-stopping function of
+ * Schied et al., "Spatiotemporal Variance-Guided Filtering", HPG 2017).  var [h][w] is the
+ * variance of the mean luminance of rgb, as rt_accum_resolve writes it.  Added without an ABI
+ * version change: detect by the symbols.  With Y(x) = 0.2126 x.r + 0.7152 x.g + 0.0722 x.b:
+ *   prep: a pixel is valid when its three colour channels and its var are finite.  With
+ *     a = max(albedo, 1e-3) per channel, c = rgb / a and v = var / Y(a)^2 when demodulating
+ *     (exact for a grey albedo, an approximation otherwise: the variance of the luminance of
+ *     rgb / a is not the variance of the luminance of rgb over Y(a)^2 when a's channels
+ *     differ), else c = rgb, v = var; then v = max(v, 0).  Invalid pixels: c = 0, v = 0.
+ *   iteration i = 0 .. iterations-1, step s = 2^i:
+ *     g(p) = sum k3(dx) k3(dy) v(q) / sum k3(dx) k3(dy) over the 3 x 3 adjacent pixels
+ *       q = p + (dx, dy), dx, dy in {-1, 0, 1} whatever s, k3 = [1/4, 1/2, 1/4], both sums over
+ *       the taps inside the image and valid; none: g = 0.
+ *     the 25 taps q = p + (dx, dy) s, dx, dy in {-2..2}, get the weight
+ *       w = h(dx) h(dy) exp(-( |Y(c_p) - Y(c_q)| / (sigma_lum sqrt(g(p)) + 1e-6)
+ *                             + |n_p - n_q|^2 / sigma_normal^2
+ *                             + (d_p - d_q)^2 / (sigma_depth max(d_p, 1e-6))^2 ))
+ *       for valid q inside the image, else 0 (h the B3 kernel above; a NULL normal / depth
+ *       buffer switches its term off).
+ *     c'(p) = sum w c_q / sum w,  v'(p) = sum w^2 v_q / (sum w)^2;  an invalid p keeps c and v.
+ *   output: out = c a and var_out = v Y(a)^2 when demodulating, else c and v; invalid pixels
+ *     pass rgb and var through bit for bit.
+ * out may alias rgb; var_out may be NULL and may alias var.  Argument checks as rt_denoise's
+ * (before any device is touched), and a NULL var is RT_ERR_INVALID. */
+int rt_denoise_var(const float* rgb, const float* var, const rt_aov* feat, int w, int h,
+                   const rt_denoise_var_opts* opts, float* out, float* var_out);
+int rt_denoise_var_device(const float* rgb_dev, const float* var_dev, const rt_aov* feat_dev,
+                          int w, int h, const rt_denoise_var_opts* opts, float* out_dev,
+                          float* var_out_dev, int device, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Progressive pass accumulator (DESIGN.md "Pass accumulator"): the exact    */
 /* sum of any number of render passes of one camera, kept on the device,     */
