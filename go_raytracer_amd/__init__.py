@@ -455,6 +455,23 @@ class Scene:
                                                 C.byref(sn), C.byref(nb)))
         return pairs, ns.value, tuple(counts), sn.value, nb.value
 
+    def lean_light(self):
+        """(kind, block uint32 [n_floats]): the lean light kind the host matcher gives the
+        scene's light list (rt_scene_lean_light; 0 = the general light code) and the light
+        as the kernel of that kind reads it (all zero for kind 0).  No device needed."""
+        k, n = C.c_int32(), C.c_int32()
+        check(lib().rt_scene_lean_light(self._p, C.byref(k), None, C.byref(n)))
+        block = np.zeros(n.value, np.uint32)
+        check(lib().rt_scene_lean_light(self._p, C.byref(k), block.ctypes.data or None, C.byref(n)))
+        return k.value, block
+
+    def plan_light(self, device=0):
+        """The lean light kind a fused render of this scene on `device` launches with now
+        (rt_scene_plan_light; honours RT_LEAN_LIGHT)."""
+        k = C.c_int32()
+        check(lib().rt_scene_plan_light(self._p, device, C.byref(k)))
+        return k.value
+
     MODES = {"auto": 0, "wavefront": 1, "fused": 2}
 
     @staticmethod

@@ -410,4 +410,59 @@ RecordPack pack_records(const HostScene& h) {
   return out;
 }
 
+// the weight merge needs non-negative suffix products: every texture value (solid
+// colours; image and noise values are >= 0 by construction) and metal albedo >= 0
+// (the background is checked per render)
+int32_t scene_merge_ok(const HostScene& h) {
+  for (const auto& t : h.texs)
+    if (t.kind == RT_TEX_SOLID && !(t.color.x >= 0.0f && t.color.y >= 0.0f && t.color.z >= 0.0f))
+      return 0;
+  for (const auto& m : h.mats)
+    if (m.kind == RT_MAT_METAL && !(m.albedo.x >= 0.0f && m.albedo.y >= 0.0f && m.albedo.z >= 0.0f))
+      return 0;
+  return 1;
+}
+// mixture-pdf floor (rt_path.h): only when every light entry is a real prim; an entry of
+// an empty HittableList has pdf 0 by the reference's rules, and its 0/0 NaNs are kept
+float scene_pdf_floor(const HostScene& h) {
+  if (h.lights.empty()) return 0.0f;
+  for (const auto& e : h.lights)
+    if (e.ref == PRIM_NONE) return 0.0f;
+  return 1e-30f;
+}
+
+// The lean kernel's light kind (rt_device.h "lean light kinds"): what the kernel compiled
+// for a kind leaves out must be an exact no-op for this scene -- one entry (no search, no
+// loop), a quad (no dispatch), weight 1.0f (no multiply), the normal on the kind's axis with
+// A_a = B_a = 0 exactly (pack_records' axis test: the dropped terms are exact zeros), merge_ok
+// and the pdf floor at the constants the kernel holds.  The block is copied from the light's
+// record (build_light_records), D' as interleave_pairs stores it for an axis record.
+int lean_light_of(const HostScene& h, LeanLight* block) {
+  if (block) *block = LeanLight{};
+  if (pick_ft_set(h.features) != 0u || h.lights.size() != 1) return 0;
+  const DevLight& e = h.lights[0];
+  if (e.ref == PRIM_NONE || (e.ref >> 30) != PRIM_QUAD || e.weight != 1.0f) return 0;
+  if (scene_merge_ok(h) != 1 || scene_pdf_floor(h) != 1e-30f) return 0;
+  std::vector<F4> lr;
+  build_light_records(h, lr);  // [0..3] Q|ref, n|D, A|area, B ; [4..6] Q, u, v
+  const float n[3] = {lr[1].x, lr[1].y, lr[1].z}, Q[3] = {lr[0].x, lr[0].y, lr[0].z},
+              A[3] = {lr[2].x, lr[2].y, lr[2].z}, B[3] = {lr[3].x, lr[3].y, lr[3].z};
+  for (int kind = 1; kind < kLeanLightCount; ++kind) {
+    const int a = lean_light_axis(kind);
+    if (a < 0) continue;
+    const int b = (a + 1) % 3, c = (a + 2) % 3;
+    if (!((n[a] == 1.0f || n[a] == -1.0f) && n[b] == 0.0f && n[c] == 0.0f && A[a] == 0.0f &&
+          B[a] == 0.0f))
+      continue;
+    if (block) {
+      const float f[kLeanLightFloats] = {
+          Q[0],    Q[1],    Q[2],    n[a] * lr[1].w, A[0],    A[1],    A[2],    lr[2].w, B[0],    B[1],
+          B[2],    0.0f,    lr[5].x, lr[5].y,        lr[5].z, 0.0f,    lr[6].x, lr[6].y, lr[6].z, 0.0f};
+      memcpy(block->f, f, sizeof f);
+    }
+    return kind;
+  }
+  return 0;
+}
+
 }  // namespace rt

@@ -54,7 +54,8 @@ constexpr Knob kKnobs[] = {
     {"RT_TREE", true, 'i', -1, 4},             // 2 / 4: force the BVH2 / BVH4 over the record loop
     {"RT_BRUTE_SMEM", false, 'i', -1, 1},      // 1: record loop through the scalar cache
     {"RT_BRUTE_SHAPE", false, 'i', 0, 1},      // 0: the generic record loop for listed layouts too
-    {"RT_QBVH", false, 'i', 0, 1},            // 0: 128-B BVH4 nodes instead of the compressed 64-B ones
+    {"RT_LEAN_LIGHT", false, 'i', 0, 1},       // 0: the general light code for lean light kinds too
+    {"RT_QBVH", false, 'i', 0, 1},           // 0: 128-B BVH4 nodes instead of the compressed 64-B ones
     {"RT_CHUNK_NEED", false, 'i', 1, 1048576},      // chunks per lane that pick the chunk size
     {"RT_TAIL_FRAC", false, 'i', -1, 1024},       // tail phase: 1 / fraction of the samples
     {"RT_TAIL_K", false, 'i', 1, 4096},          // tail phase chunk size
@@ -159,6 +160,16 @@ int rt_brute_shape(const int32_t counts[7]) {
   if (!counts) return rt::set_error(RT_ERR_INVALID, "rt_brute_shape: counts is NULL");
   const rt::BruteCounts c = {counts[0], counts[1], {counts[2], counts[3], counts[4]}, counts[5], counts[6]};
   return rt::brute_shape_of(c);
+}
+
+int rt_scene_lean_light(const rt_scene* sc, int32_t* kind, float* block, int32_t* n_floats) {
+  if (!sc) return rt::set_error(RT_ERR_INVALID, "rt_scene_lean_light: null");
+  rt::LeanLight b;
+  const int k = rt::lean_light_of(sc->s.h, &b);
+  if (kind) *kind = k;
+  if (n_floats) *n_floats = rt::kLeanLightFloats;
+  if (block) memcpy(block, b.f, sizeof b.f);
+  return RT_OK;
 }
 
 int rt_tune_list(int32_t i, const char** name, int32_t* changes_bits) {

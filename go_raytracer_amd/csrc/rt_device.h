@@ -236,4 +236,23 @@ inline constexpr int brute_shape_of(const BruteCounts& c) {
   return 0;
 }
 
+// ---- lean light kinds --------------------------------------------------------
+// Light lists the lean LDS record-loop kernel's light sampling and light pdf are compiled
+// for (k_fused<true, 0, 0, SHAPE, LIGHT>).  Kind 0 is the general code, which takes any list.
+//   1: one quad light with unit normal +-e_y (A_y = B_y = 0 exactly), weight 1, in a scene
+//      whose weights are all >= 0 (merge_ok) and whose mixture-pdf floor is 1e-30
+// A kind's normal axis, -1 = the general code (a kind for x or z is one more case here, plus
+// its kernels in pick_fused)
+constexpr int kLeanLightCount = 2;
+inline constexpr int lean_light_axis(int kind) { return kind == 1 ? 1 : -1; }
+// The kind's light as plain floats, a member of the launch parameters (no pointer to chase):
+//  f[0..2] Q | f[3] D' = D / n_a   f[4..6] A = v x w | f[7] area   f[8..10] B = w x u | 0
+//  (the pdf's quad test, rt_path.h lean_light_pdf: the light's leaf record with the plane
+//   offset in the record loop's axis form)
+//  f[12..14] u | 0   f[16..18] v | 0                   (quad.Random: Q + u s0 + v s1)
+constexpr int kLeanLightFloats = 20;
+struct alignas(16) LeanLight {
+  float f[kLeanLightFloats];
+};
+
 }  // namespace rt

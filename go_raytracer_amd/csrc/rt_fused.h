@@ -175,10 +175,13 @@ __shared__ unsigned long long g_dinfo[4][3];  // ... and then: samples left, bus
 #endif
 // TREE: 4 = BVH4, 5 = compressed BVH4 (64-B nodes, global only), 2 = BVH2, 0 = no tree
 // (every record tested, tiny scenes).  SHAPE (TREE 0, FT 0, LDS only): the record layout the
-// loop is compiled for (rt_device.h brute_shape), 0 = any
-template <bool LDS, uint32_t FT, int TREE, int SHAPE = 0>
+// loop is compiled for (rt_device.h brute_shape), 0 = any.  LIGHT (the same kernels only): the
+// lean light kind the light sampling and light pdf are compiled for (rt_device.h), 0 = any list
+template <bool LDS, uint32_t FT, int TREE, int SHAPE = 0, int LIGHT = 0>
 __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) {
   static_assert(SHAPE == 0 || (LDS && FT == 0u && TREE == 0), "shapes: the lean LDS record loop only");
+  static_assert(LIGHT == 0 || (LDS && FT == 0u && TREE == 0), "light kinds: the lean LDS record loop only");
+  static_assert(LIGHT >= 0 && LIGHT < kLeanLightCount, "light kinds: unlisted kind");
   extern __shared__ F4 lnodes[];  // LDS scene cache, sized at launch (scene_lds_bytes)
   __shared__ uint32_t lstack[(fused_short(FT, TREE) > 0 ? fused_short(FT, TREE) : 1) * 256];
   __shared__ float lw[3 * fused_wlds(FT, TREE) * 256];
@@ -324,7 +327,7 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
         ++s.segs;
 #endif
         PH_T(t_shade);
-        if (shade_core<false, FT>(P, slot, s, best, ws, sa) == OUT_NEED_CHUNK) has = false;
+        if (shade_core<false, FT, LIGHT>(P, slot, s, best, ws, sa) == OUT_NEED_CHUNK) has = false;
         else {
           trav_init<FT>(P.sc, s.o, s.d, s.time, tr);
 #ifdef RT_QROOT  // (opt-in: +2-4 % on C3-C5)

@@ -172,6 +172,15 @@ struct RecordPack {
   int shape = 0;          // brute_shape_of(counts)
 };
 RecordPack pack_records(const HostScene& h);
+// host_records.cpp: DevScene::merge_ok before the render's background is looked at (every
+// solid colour and metal albedo >= 0) and DevScene::pdf_floor (1e-30 when every light entry
+// is a prim, else 0), fixed at upload
+int32_t scene_merge_ok(const HostScene& h);
+float scene_pdf_floor(const HostScene& h);
+// host_records.cpp: the lean light kind of the scene's light list (rt_device.h "lean light
+// kinds", 0 = the general code) and, for a kind >= 1, its light packed into *block (zeroed
+// otherwise); computed once per upload, next to pack_records
+int lean_light_of(const HostScene& h, LeanLight* block);
 // rt_build.hip: the same outputs as build_bvh, built by PLOC on `device` (-1: the calling
 // thread's current device; the current device is restored on return)
 int build_bvh_device(HostScene& s, const std::vector<F4>& lo, const std::vector<F4>& hi,

@@ -110,6 +110,8 @@ struct Params {
   F4* trace;                  // debug path trace (3 F4 per vertex) or null
   uint32_t trace_gpix, trace_sample;
   int trace_cap;
+  LeanLight ll;               // the light of a lean light kind's kernel (rt_device.h; set only
+                              // for a launch of such a kernel, read by it alone)
 };
 
 RT_D uint32_t pack_path(uint32_t j, uint32_t k, uint32_t nst, uint32_t flags) {
@@ -1758,6 +1760,50 @@ RT_D f3 lights_random(const DevScene& sc, f3 origin, const rt_u32x4& r) {
   return p - origin;
 }
 
+// The light of a lean light kind (rt_device.h; KIND >= 1: one quad light on axis
+// lean_light_axis(KIND), weight 1), read with 16-B scalar loads from the launch parameters --
+// one address, no table entry, no record pointer -- where lights_random and lights_pdf chase
+// kparams -> lights[i] -> light_recs.  The host matcher (host_records.cpp lean_light_of)
+// guarantees what is left out here is an exact no-op.
+// Two loads: the pdf's part (every vertex) first, before the vertex's basis and direction are
+// worked out, and u, v in the half of the vertices that sample the light.
+struct LeanLightRegs {
+  F4 q, a, b;  // f[0..11]: Q | D', A | area, B | 0
+};
+RT_D LeanLightRegs lean_light_load() {
+  const F4* lb = (const F4*)&kparams()->ll;
+  return {ld_cst(lb), ld_cst(lb + 1), ld_cst(lb + 2)};
+}
+// lights_random for the kind: quad.Random objects.go:161-165 (the same expression)
+RT_D f3 lean_light_random(const LeanLightRegs& L, f3 origin, const rt_u32x4& r) {
+  const float s0 = rt_unit_f(r.v[2]), s1 = rt_unit_f(r.v[3]);
+  const F4* lb = (const F4*)&kparams()->ll;
+  const F4 U = ld_cst(lb + 3), V = ld_cst(lb + 4);
+  return (xyz(L.q) + xyz(U) * s0 + xyz(V) * s1) - origin;
+}
+// lights_pdf for the kind: prim_pdf's quad test (hit_quad_rec_m), interval [0.001, +inf).
+// With n = +-e_A the general test's n.d is +-d_A and n.o is +-o_A exactly, so t is the record
+// loop's axis form (brute_half: D' = D / n_A, and |d_A| < 1e-8 makes t NaN, which the alpha /
+// beta test rejects), and dot(dir, n) is +-d_A.  alpha and beta keep hit_quad_rec_m's three
+// terms: the A_A = B_A = 0 term adds an exact zero, but a ray sampled at the light's edge
+// (s0 or s1 = 0, one light sample in 2^23) lands on alpha or beta = +-0, whose sign decides
+// the test (unit_ab_rej), and the zero term takes part in that sign: with the in-plane terms
+// alone the 800 x 800 x 1024 Cornell image was not the general code's.
+// The entry's weight is 1.
+template <int KIND>
+RT_D float lean_light_pdf(const LeanLightRegs& L, f3 o, f3 d) {
+  constexpr int A = lean_light_axis(KIND);
+  static_assert(A >= 0 && A < 3, "lean light: a kind with an axis");
+  const float da = comp<A>(d);
+  const float ia = bitsf(pick_by(fbits(rcp(da)), 0x7FC00000u, neg_mask(fabsf(da) - 1e-8f)));
+  const float t = (L.q.w - comp<A>(o)) * ia;
+  const f3 pp = (o + d * t) - xyz(L.q);
+  const float alpha = dot(pp, xyz(L.a)), beta = dot(pp, xyz(L.b));
+  const uint32_t miss = rec_reject_t(t, 0.001f, kInf, alpha, beta);
+  const float dd = dot(d, d);
+  return bitsf(and_not(fbits((t * t * dd) * fsqrt(dd) * rcp(fabsf(da) * L.a.w)), miss));
+}
+
 // ---------------------------------------------------------- pixel sums -----
 // pixelColor += rayColor(...) (camera.go:97-101) for every sample, in fixed point:
 // each sample's channel becomes floor(v * 2^32) and the pixel sums are int64, so
@@ -2085,7 +2131,9 @@ RT_D void start_sample(const Params& P, uint32_t slot, Path& s, uint32_t chunk, 
 
 // One vertex of rayColor (camera.go:293-331) given its closest hit.
 // Returns OUT_ALIVE (continue with s.o/s.d), or OUT_NEED_CHUNK (chunk flushed).
-template <bool SOA, uint32_t FT>
+// LIGHT: the lean light kind the light sampling and light pdf are compiled for (rt_device.h;
+// the lean LDS record-loop kernel only, k_fused), 0 = any light list
+template <bool SOA, uint32_t FT, int LIGHT = 0>
 RT_D int shade_core(const Params& P, uint32_t slot, Path& s, const Hit& h, const WStack& ws,
                     const SampleAcc& sa) {
   const DevScene& sc = P.sc;
@@ -2268,10 +2316,14 @@ RT_D int shade_core(const Params& P, uint32_t slot, Path& s, const Hit& h, const
         f3 att = ltab ? lcol : tex_value<FT>(sc, M.tex, u, v, p);
         PH_ADD(PH_TEX, t_tex);
         PH_T(t_light);
+        // a lean light kind: the pdf part of the light block is asked for first
+        LeanLightRegs lean;
+        if constexpr (LIGHT != 0) lean = lean_light_load();
         Onb b;
         if (!iso) b = make_onb_unit(n);
         if (rt_unit_f(r.v[0]) < 0.5f) {
-          ndir = lights_random<FT>(sc, p, r);
+          if constexpr (LIGHT != 0) ndir = lean_light_random(lean, p, r);
+          else ndir = lights_random<FT>(sc, p, r);
         } else if (iso) {
           ndir = uniform_sphere(rt_unit_f(r.v[2]), rt_unit_f(r.v[3]));
         } else {
@@ -2290,7 +2342,10 @@ RT_D int shade_core(const Params& P, uint32_t slot, Path& s, const Hit& h, const
 #ifdef ABL_NO_LIGHTPDF
         float pdf = 0.5f * 0.01f + 0.5f * bsdf_pdf;  // ablation build (timing only)
 #else
-        float pdf = 0.5f * lights_pdf<FT>(sc, p, ndir) + 0.5f * bsdf_pdf;
+        float lpdf;
+        if constexpr (LIGHT != 0) lpdf = lean_light_pdf<LIGHT>(lean, p, ndir);
+        else lpdf = lights_pdf<FT>(sc, p, ndir);
+        float pdf = 0.5f * lpdf + 0.5f * bsdf_pdf;
 #endif
         PH_ADD(PH_LIGHT, t_light);
         // pdf >= 1e-30 when every light entry is a prim (sc.pdf_floor): a direction below
@@ -2299,7 +2354,8 @@ RT_D int shade_core(const Params& P, uint32_t slot, Path& s, const Hit& h, const
         // pdf; one sample in ~1e9 of C2 met this).  Any pdf > 1e-30 is untouched.  An empty
         // lights list's pdf is 0 by the reference's rules (hittable.go:89-103): its 0/0 NaNs
         // are the reference's own and stay (floor 0, test_world_without_lights_list).
-        weight = (att * spdf) * rcp(fmaxf(pdf, sc.pdf_floor));
+        // (a lean light kind: the floor is 1e-30 by the host matcher)
+        weight = (att * spdf) * rcp(fmaxf(pdf, LIGHT != 0 ? 1e-30f : sc.pdf_floor));
         clamp_vertex = true;
       }
       // vertex bookkeeping (H1: the clamp is folded backwards at termination)
@@ -2321,7 +2377,8 @@ RT_D int shade_core(const Params& P, uint32_t slot, Path& s, const Hit& h, const
           // for any sign.
           // (the flag is re-read from the kernel-argument segment here, kparams(): held in
           // an SGPR across the loop it added SGPR spills)
-          const bool merge = kparams()->sc.merge_ok && s.nst > 0 && pv.x >= 0.0f && pv.y >= 0.0f &&
+          // (a lean light kind: set by the host matcher and kept by the launch, render_impl)
+          const bool merge = (LIGHT != 0 || kparams()->sc.merge_ok) && s.nst > 0 && pv.x >= 0.0f && pv.y >= 0.0f &&
                              pv.z >= 0.0f && pv.x <= 1.0f && pv.y <= 1.0f && pv.z <= 1.0f;
 #else
           const bool merge = false;

@@ -183,6 +183,8 @@ struct DeviceScene {
   int32_t shade_n = 0;              // F4s of the lean shade table after the pairs (0: none)
   int32_t brute_boxes = 0;          // boxes among them tested as slabs (rt_path.h brute_box)
   int brute_shape = 0;              // the listed layout the pair counts equal (rt_device.h), 0 = none
+  int lean_light = 0;               // the light list's lean kind (rt_device.h), 0 = the general code
+  LeanLight light_block{};          // ... and its light as the kernel of that kind reads it
   uint32_t root2 = PRIM_NONE;
   int32_t n_nodes2 = 0;
   const F4* qnodes = nullptr;       // compressed BVH4 (host_qbvh.cpp): 64-B items, root item 0
@@ -425,25 +427,14 @@ static int upload_scene(const Scene* s, DeviceScene* ds) {
   d.n_media = (int32_t)h.media.size();
   d.medium_draws = h.medium_draws;
   d.n_lights = (int32_t)h.lights.size();
-  // mixture-pdf floor (rt_path.h): only when every light entry is a real prim; an entry of
-  // an empty HittableList has pdf 0 by the reference's rules, and its 0/0 NaNs are kept
-  d.pdf_floor = h.lights.empty() ? 0.0f : 1e-30f;
-  for (const auto& e : h.lights)
-    if (e.ref == PRIM_NONE) d.pdf_floor = 0.0f;
+  d.pdf_floor = scene_pdf_floor(h);  // (host_records.cpp)
   d.n_refs = (int32_t)h.refs.size();
   d.n_perlins = (int32_t)h.perlins.size();
-  // the weight merge needs non-negative suffix products: every texture value (solid
-  // colours; image and noise values are >= 0 by construction) and metal albedo >= 0
-  // (the background is checked per render)
   d.shade_lds = -1;  // set per launch (record-loop kernel with the records in LDS)
   d.shade_n = 0;
-  d.merge_ok = 1;
-  for (const auto& t : h.texs)
-    if (t.kind == RT_TEX_SOLID && !(t.color.x >= 0.0f && t.color.y >= 0.0f && t.color.z >= 0.0f))
-      d.merge_ok = 0;
-  for (const auto& m : mats)
-    if (m.kind == RT_MAT_METAL && !(m.albedo.x >= 0.0f && m.albedo.y >= 0.0f && m.albedo.z >= 0.0f))
-      d.merge_ok = 0;
+  d.merge_ok = scene_merge_ok(h);  // (host_records.cpp; the background is checked per render)
+  // the lean kernel's light kind and its light block (host_records.cpp), fixed at upload
+  ds->lean_light = lean_light_of(h, &ds->light_block);
   return RT_OK;
 }
 
@@ -578,8 +569,17 @@ static const void* fused_for(uint32_t set) {
 static uint32_t pick_set(uint32_t feats) { return pick_ft_set(feats); }
 // BVH2 kernels exist for the two smallest sets with the tree in LDS (tiny scenes)
 // (shape: the lean LDS record loop compiled for a listed record layout, rt_device.h brute_shape)
-static const void* pick_fused(bool lds, uint32_t set, int tree, int shape = 0) {
+// (light: the lean LDS record loop's light code compiled for a lean light kind, rt_device.h; the
+// listed shapes have such kernels, the generic loop does not: nullptr, the caller takes kind 0)
+static const void* pick_fused(bool lds, uint32_t set, int tree, int shape = 0, int light = 0) {
   static_assert(kBruteShapeCount == 3, "pick_fused: one kernel per listed shape");
+  static_assert(kLeanLightCount == 2, "pick_fused: one kernel per listed shape and light kind");
+  if (light != 0) {
+    if (!(tree == 0 && lds && set == kFtSets[0] && light == 1)) return nullptr;
+    if (shape == 1) return (const void*)k_fused<true, kFtSets[0], 0, 1, 1>;
+    if (shape == 2) return (const void*)k_fused<true, kFtSets[0], 0, 2, 1>;
+    return nullptr;
+  }
   if (tree == 0 && lds && set == kFtSets[0] && shape == 1) return (const void*)k_fused<true, kFtSets[0], 0, 1>;
   if (tree == 0 && lds && set == kFtSets[0] && shape == 2) return (const void*)k_fused<true, kFtSets[0], 0, 2>;
   if (tree == 0 && lds && set == kFtSets[0]) return (const void*)k_fused<true, kFtSets[0], 0>;
@@ -690,6 +690,7 @@ struct StructurePlan {
   bool f_recs;       // ... and the leaf records after them
   bool shade_tab;    // the lean kernel's shade table goes with the record pairs
   int shape;         // the record layout the kernel is compiled for (rt_device.h brute_shape), 0 = any
+  int light;         // the lean light kind its light code is compiled for (rt_device.h), 0 = any list
   const void* kernel;
   size_t lds_bytes;  // dynamic LDS of the kernel
   bool wants_qbvh;   // a BVH4 read through L1/L2 whose set has a compressed-BVH4 kernel
@@ -744,7 +745,15 @@ static int plan_structure(const Scene* s, const DeviceScene* ds, uint32_t ft_set
   // kernel (A/B; the same hits bit for bit).
   const int brute_shape_id = tree == 0 && f_lds && ft_set == kFtSets[0] && env_int("RT_BRUTE_SHAPE", 1) != 0
                                  ? ds->brute_shape : 0;
-  const void* fused_kernel = pick_fused(f_lds, ft_set, tree, brute_shape_id);
+  // ... and its light sampling and light pdf compiled for the scene's light list, when that is
+  // a lean light kind (fixed at upload too) and the layout's kernel exists for it.  The block
+  // is a launch parameter: no LDS, nothing to stage.  RT_LEAN_LIGHT=0: the general light code
+  // (A/B; the same image bit for bit).  A render whose background clears merge_ok takes kind 0
+  // at its launch (render_impl).
+  int light = tree == 0 && f_lds && ft_set == kFtSets[0] && env_int("RT_LEAN_LIGHT", 1) != 0
+                  ? ds->lean_light : 0;
+  if (light != 0 && !pick_fused(f_lds, ft_set, tree, brute_shape_id, light)) light = 0;
+  const void* fused_kernel = pick_fused(f_lds, ft_set, tree, brute_shape_id, light);
   if (!fused_kernel) return set_error(RT_ERR_UNSUPPORTED, "internal: no fused kernel for this scene");
   const size_t fused_lds = f_lds ? 64 * (node_slots * n_nodes + (f_recs ? rec_slots : 0)) : 0;
   out->tree = tree;
@@ -752,6 +761,7 @@ static int plan_structure(const Scene* s, const DeviceScene* ds, uint32_t ft_set
   out->f_recs = f_recs;
   out->shade_tab = shade_tab;
   out->shape = brute_shape_id;
+  out->light = light;
   out->kernel = fused_kernel;
   out->lds_bytes = fused_lds;
   return RT_OK;
@@ -1240,6 +1250,13 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   StructurePlan sp;
   if ((rc = plan_structure(s, ds, ft_set, mode, &sp))) return rc;
   if (sp.tree == 4 && sp.wants_qbvh && (rc = take_qbvh(s, ds, ft_set, &sp))) return rc;
+  // A lean light kind's kernel holds merge_ok as the constant true: a render whose background
+  // clears the flag (below) launches the layout's kernel with the general light code instead
+  if (sp.light != 0 && !((float)cd.background[0] >= 0.0f && (float)cd.background[1] >= 0.0f &&
+                         (float)cd.background[2] >= 0.0f)) {
+    sp.light = 0;
+    sp.kernel = pick_fused(sp.f_lds, ft_set, sp.tree, sp.shape, 0);
+  }
   // path slots: the fused kernel's resident lanes, or the wavefront queue's length
   uint32_t P = 0;
   int fused_blocks = 0;
@@ -1283,6 +1300,10 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   }
   set_camera_params(p, cd, o, npix);
   if (!(p.bg[0] >= 0.0f && p.bg[1] >= 0.0f && p.bg[2] >= 0.0f)) p.sc.merge_ok = 0;
+  if (sp.light != 0) {
+    if (!p.sc.merge_ok) return set_error(RT_ERR_UNSUPPORTED, "internal: lean light kernel without merge_ok");
+    p.ll = ds->light_block;
+  }
   p.K = cp.K;
   p.K2 = cp.K2;
   p.S1 = cp.S1;
@@ -1678,6 +1699,20 @@ int rt_progress(const rt_scene* sc, uint64_t* done, uint64_t* total) {
     if (hipEventQuery((hipEvent_t)p.events[i]) != hipSuccess) break;
     *done = p.cum[i];
   }
+  return RT_OK;
+}
+
+int rt_scene_plan_light(rt_scene* sc, int device, int32_t* kind) {
+  if (!sc || !kind) return rt::set_error(RT_ERR_INVALID, "rt_scene_plan_light: null");
+  int rc = rt::device_ok("rt_scene_plan_light", device);
+  if (rc) return rc;
+  rt::DeviceGuard dg;
+  if (hipSetDevice(device) != hipSuccess) return rt::set_error(RT_ERR_DEVICE, "rt_scene_plan_light");
+  rt::DeviceScene* ds = nullptr;
+  if ((rc = rt::ensure_scene(&sc->s, device, &ds))) return rc;
+  rt::StructurePlan sp;
+  if ((rc = rt::plan_structure(&sc->s, ds, rt::scene_ft_set(&sc->s), RT_MODE_FUSED, &sp))) return rc;
+  *kind = sp.light;
   return RT_OK;
 }
 

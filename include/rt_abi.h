@@ -343,6 +343,19 @@ int rt_scene_export_qbvh(const rt_scene* s, float* items, int32_t* n_items, floa
  * to have pairs.  NULL pointers query the sizes. */
 int rt_scene_export_records(const rt_scene* s, float* pairs, int32_t* n_slots, int32_t counts[7],
                             int32_t* shade_n, int32_t* n_boxes);
+/* the lean light kind of the scene's light list as the host matcher decides it at upload (no
+ * device): 0 = any list (the general light code), 1 = one quad light of weight 1 with unit
+ * normal +-e_y in a lean-set scene (RT_FT features 0) of non-negative colours.  For a kind
+ * >= 1, block receives the light as the record-loop kernel of that kind reads it, n_floats
+ * (20) floats: [0..2] Q, [3] D / n_y, [4..6] A = v x w, [7] area, [8..10] B = w x u,
+ * [12..14] u, [16..18] v ([11], [15], [19] are 0); all zero for kind 0.  NULL pointers query
+ * the sizes. */
+int rt_scene_lean_light(const rt_scene* s, int32_t* kind, float* block, int32_t* n_floats);
+/* the lean light kind a fused render of the scene on `device` launches with now (uploads the
+ * scene there on first use): the matcher's kind when the record-loop kernel compiled for it
+ * takes the scene and RT_LEAN_LIGHT is not 0, else 0.  A render whose background has a
+ * negative channel takes kind 0 whatever this returns. */
+int rt_scene_plan_light(rt_scene* s, int device, int32_t* kind);
 
 enum {
   RT_FLAG_PROFILE = 1,     /* time every kernel with HIP events */
