@@ -697,6 +697,69 @@ class Accumulator:
                 break
         return i
 
+    # ---- adaptive passes: resample only the noisy tiles
+    def select(self, rel_error, lum_floor=0, tile=0, min_passes=0):
+        """rt_accum_select: the pixels of the tiles whose error figure e_T exceeds `rel_error`
+        (or that hold a pixel with fewer than `min_passes` passes) become the selection of the
+        next add_active().  0 takes a default: lum_floor 1e-2, tile 8, min_passes 4.  Returns
+        the number of active pixels."""
+        o = _lib.RtAdaptOpts(rel_error, lum_floor, tile, min_passes)
+        n = C.c_uint64()
+        check(lib().rt_accum_select(self._h(), C.byref(o), C.byref(n)))
+        return n.value
+
+    def set_active(self, mask):
+        """rt_accum_set_active: the selection from a [rows, W] mask (nonzero = active).
+        Returns the number of active pixels."""
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.shape != self.shape:
+            raise ValueError(f"set_active: needs a mask of shape {self.shape}")
+        n = C.c_uint64()
+        check(lib().rt_accum_set_active(self._h(), m.ctypes.data, C.byref(n)))
+        return n.value
+
+    def add_active(self, seed):
+        """One pass over the current selection only (rt_accum_add_active): every selected pixel
+        gets exactly the samples add(seed) would give it.  Returns the pass's stats dict."""
+        st = RtStats()
+        check(lib().rt_accum_add_active(self._h(), seed, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in RtStats._fields_}
+
+    def counts(self):
+        """int32 [rows, W]: the passes every pixel has taken (rt_accum_counts)."""
+        c = np.zeros(self.shape, np.int32)
+        check(lib().rt_accum_counts(self._h(), c.ctypes.data))
+        return c
+
+    def tile_error(self, lum_floor=0, tile=0, min_passes=0):
+        """float32 [tiles_y, tiles_x]: e_T of every tile, as select() compares it
+        (rt_accum_tile_error)."""
+        o = _lib.RtAdaptOpts(1.0, lum_floor, tile, min_passes)
+        tx, ty = C.c_int32(), C.c_int32()
+        check(lib().rt_accum_tile_error(self._h(), C.byref(o), None, C.byref(tx), C.byref(ty)))
+        e = np.zeros((ty.value, tx.value), np.float32)
+        check(lib().rt_accum_tile_error(self._h(), C.byref(o), e.ctypes.data, C.byref(tx), C.byref(ty)))
+        return e
+
+    def adapt_info(self):
+        """rt_adapt_info as a dict: active_pixels, total_samples, min_count, max_count, n_tiles,
+        active_tiles."""
+        i = _lib.RtAdaptInfo()
+        check(lib().rt_accum_adapt_info(self._h(), C.byref(i)))
+        return {f: getattr(i, f) for f, _ in _lib.RtAdaptInfo._fields_}
+
+    def render_adaptive(self, rel_error, max_passes, seed=1, **opts):
+        """select() / add_active() until the selection is empty or the accumulator holds
+        max_passes passes.  While some pixel has fewer than min_passes passes every tile is
+        selected, so the first min_passes passes are whole passes (add_active then takes
+        add()'s path).  Pass number p takes seed + p, as render_until.  opts: select()'s
+        lum_floor, tile, min_passes.  Returns adapt_info() with "passes" added."""
+        p = self.info()["passes"]
+        while p < max_passes and self.select(rel_error, **opts) > 0:
+            self.add_active(seed + p)
+            p += 1
+        return dict(self.adapt_info(), passes=p)
+
 
 def _multi(scene, camera, devices, out_ptr, seed, path_slots, chunk, profile, mode, rccl=False):
     devs = (C.c_int32 * len(devices))(*[int(d) for d in devices])

@@ -118,6 +118,17 @@ class RtAccumInfo(C.Structure):  # rt_accum_info
                 ("rel_error", C.c_double)]
 
 
+class RtAdaptOpts(C.Structure):  # rt_adapt_opts
+    _fields_ = [("rel_error", C.c_double), ("lum_floor", C.c_double),
+                ("tile", C.c_int32), ("min_passes", C.c_int32)]
+
+
+class RtAdaptInfo(C.Structure):  # rt_adapt_info
+    _fields_ = [("active_pixels", C.c_uint64), ("total_samples", C.c_uint64),
+                ("min_count", C.c_int32), ("max_count", C.c_int32),
+                ("n_tiles", C.c_int32), ("active_tiles", C.c_int32)]
+
+
 class RtTreeView(C.Structure):
     _fields_ = [
         ("nodes", C.c_void_p), ("n_nodes", C.c_int32),
@@ -250,6 +261,14 @@ SIGNATURES = {
     "rt_accum_resolve": (_I, [_P, C.c_void_p, C.c_void_p]),
     "rt_accum_resolve_device": (_I, [_P, C.c_void_p, C.c_void_p]),
     "rt_accum_info_get": (_I, [_P, C.POINTER(RtAccumInfo)]),
+    "rt_accum_select": (_I, [_P, C.POINTER(RtAdaptOpts), C.POINTER(C.c_uint64)]),
+    "rt_accum_set_active": (_I, [_P, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rt_accum_add_active": (_I, [_P, C.c_uint64, C.POINTER(RtStats)]),
+    "rt_accum_counts": (_I, [_P, C.c_void_p]),
+    "rt_accum_counts_device": (_I, [_P, C.c_void_p]),
+    "rt_accum_tile_error": (_I, [_P, C.POINTER(RtAdaptOpts), C.c_void_p, C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int32)]),
+    "rt_accum_adapt_info": (_I, [_P, C.POINTER(RtAdaptInfo)]),
     "rt_demo_scene": (_I, [_P, C.c_char_p, C.c_char_p, C.POINTER(RtCamera), C.POINTER(_I),
                            C.POINTER(_I)]),
     "rt_demo_scene_name": (_I, [_I, C.POINTER(C.c_char_p)]),

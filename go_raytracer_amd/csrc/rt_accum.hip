@@ -5,22 +5,33 @@
 // pass is an ordinary render (rt_render.hip render_impl: the same plans, launches and buffers,
 // under the same per-(device, slot) mutex) that ends in k_accum_fold instead of k_resolve.
 //
-// State, structure of planes, one entry per pixel of the share (68 B per pixel):
+// State, structure of planes, one entry per pixel of the share (76 B per pixel):
 //   sum[3]   u64  the passes' 2^-32 fixed-point pixel sums, added with plain 64-bit adds
 //                 (a pass's samples are limited to 2^31 / (spp * max_passes), so the total
 //                 stays inside int64; read back as int64)
 //   side[3]  f64  the passes' fp64 side sums (samples above that limit)
 //   mean, m2 f64  Welford's running mean and sum of squared deviations of the pass luminance
 //   flags    u32  the passes' NaN / +Inf / -Inf flag words, OR-ed
+//   count    u32  passes the pixel took; written from the first active-pixel pass on (§14): an
+//                 accumulator that took whole passes only is *uniform* and never touches it
+//   map      u32  the current selection: the active local pixels, ascending
 // k_accum_fold     one pass -> state          (one pixel per lane, 256-thread blocks)
 // k_accum_resolve  state -> mean RGB and the variance of the mean luminance
 // k_accum_info1/2  state -> {sum of variances, sum of means, finite pixels, other pixels}:
 //                  a two-stage block reduction in fp64, fixed tree order, no atomics
+// Per-pixel forms, used once a pass covered a part of the pixels:
+// k_accum_fold_px / k_accum_resolve_px / k_accum_info1_px  the same with count[p] for `passes`,
+//                  the fold through the pass's pixel map
+// k_accum_tiles    state -> per tile: the error figure e_T and the active flag (one tile per lane)
+// k_active_count / k_active_scan / k_active_scatter  active pixels -> the sorted map: ballot
+//                  counts per block, an exclusive scan by one block, a scatter; no atomics
+// k_count_stats    min, max and sum of a u32 array by one block (counts, tile flags)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 
 #include "rt_hip_util.h"
@@ -131,6 +142,217 @@ __global__ __launch_bounds__(256) void k_accum_info2(const double* part, uint32_
     for (int k = 0; k < 4; ++k) out[k] = v[k];
 }
 
+// ------------------------------------------- per-pixel pass counts --
+__global__ __launch_bounds__(256) void k_accum_fill(uint32_t* v, uint32_t n, uint32_t x) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) v[i] = x;
+}
+
+// k_accum_fold for a pass over the pixels map[0 .. P.npix) of the npix-pixel share (map null:
+// a whole pass, the identity): the pass's sums are read at the pass's own pixel v, the state
+// is updated at p = map[v] with the pixel's own pass count
+__global__ __launch_bounds__(256) void k_accum_fold_px(Params P, AccumPlanes A, double scale, uint32_t npix,
+                                                       uint32_t* count, const uint32_t* map) {
+  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= P.npix) return;
+  const uint32_t p = map ? map[v] : v;
+  const uint32_t f = P.pflags[v];
+  unsigned long long cs[3] = {0ull, 0ull, 0ull};
+  chunk_record_sums(P, v, cs);
+  double c[3];
+  for (int ch = 0; ch < 3; ++ch) {
+    const size_t i = (size_t)ch * P.npix + v, k = (size_t)ch * npix + p;
+    const unsigned long long sum = P.accum[i] + cs[ch];
+    const double side = P.side[i];
+    A.sum[k] += sum;
+    A.side[k] += side;
+    c[ch] = flagged_channel(f, ch, (long long)sum, side, scale);
+  }
+  A.flags[p] |= f;
+  const uint32_t n = count[p] + 1u;
+  count[p] = n;
+  const double y = luminance(c[0], c[1], c[2]);
+  double mean = A.mean[p];
+  const double d = y - mean;
+  mean += d / (double)n;
+  A.m2[p] += d * (y - mean);
+  A.mean[p] = mean;
+}
+
+// scale = pixel_samples_scale; a pixel without a pass resolves to zeros
+__global__ __launch_bounds__(256) void k_accum_resolve_px(AccumPlanes A, uint32_t npix, double scale,
+                                                          const uint32_t* count, float* rgb, float* var) {
+  const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
+  if (lp >= npix) return;
+  const uint32_t n = count[lp];
+  if (rgb) {
+    const uint32_t f = A.flags[lp];
+    const double scale_n = n ? scale / (double)n : 0.0;
+    for (int ch = 0; ch < 3; ++ch) {
+      const size_t i = (size_t)ch * npix + lp;
+      rgb[3 * (size_t)lp + ch] = (float)flagged_channel(f, ch, (long long)A.sum[i], A.side[i], scale_n);
+    }
+  }
+  if (var) var[lp] = (float)var_of_mean(A.m2[lp], n);
+}
+
+__global__ __launch_bounds__(256) void k_accum_info1_px(AccumPlanes A, uint32_t npix, const uint32_t* count,
+                                                        double* part) {
+  __shared__ double red[4][256];
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x; lp < npix; lp += stride) {
+    const double var = var_of_mean(A.m2[lp], count[lp]), mean = A.mean[lp];
+    if (isfinite(var) && isfinite(mean)) {
+      v[0] += var;
+      v[1] += mean;
+      v[2] += 1.0;
+    } else {
+      v[3] += 1.0;
+    }
+  }
+  block_sum4(v, red);
+  if (threadIdx.x == 0)
+    for (int k = 0; k < 4; ++k) part[4 * blockIdx.x + k] = v[k];
+}
+
+// {min, max, sum} of v[0 .. n) by one block: thread t takes t, t + 256, ..., then a fixed tree
+__global__ __launch_bounds__(256) void k_count_stats(const uint32_t* v, uint32_t n, unsigned long long* out) {
+  __shared__ unsigned long long red[3][256];
+  unsigned long long lo = ~0ull, hi = 0ull, sum = 0ull;
+  for (uint32_t i = threadIdx.x; i < n; i += 256u) {
+    const unsigned long long x = v[i];
+    lo = x < lo ? x : lo;
+    hi = x > hi ? x : hi;
+    sum += x;
+  }
+  const uint32_t t = threadIdx.x;
+  red[0][t] = lo;
+  red[1][t] = hi;
+  red[2][t] = sum;
+  __syncthreads();
+  for (uint32_t s = 128; s > 0; s >>= 1) {
+    if (t < s) {
+      red[0][t] = red[0][t + s] < red[0][t] ? red[0][t + s] : red[0][t];
+      red[1][t] = red[1][t + s] > red[1][t] ? red[1][t + s] : red[1][t];
+      red[2][t] += red[2][t + s];
+    }
+    __syncthreads();
+  }
+  if (t == 0)
+    for (int k = 0; k < 3; ++k) out[k] = red[k][0];
+}
+
+// ----------------------------------------------------- selection --
+// The share's local image in tiles of tile x tile pixels (edge tiles smaller), tx x ty of them
+struct TileGrid {
+  uint32_t W, rows, tile, tx, ty;
+};
+
+// e_T = sqrt(mean var_p) / (max(mean mean_p, 0) + lum_floor) over the tile's pixels whose
+// variance and Welford mean are finite, summed row by row in fp64 (0 without such a pixel),
+// rounded to fp32: the figure rt_accum_tile_error reports is the one rt_accum_select compares.
+// *young: some pixel of the tile has fewer than min_passes passes.  count null: every pixel
+// has `passes` (a uniform accumulator).
+RT_D float tile_error(const AccumPlanes& A, const uint32_t* count, uint32_t passes, const TileGrid& g,
+                      uint32_t T, double lum_floor, uint32_t min_passes, bool* young) {
+  const uint32_t tr = T / g.tx, tc = T - tr * g.tx;
+  const uint32_t r1 = min((tr + 1u) * g.tile, g.rows), c1 = min((tc + 1u) * g.tile, g.W);
+  double sv = 0.0, sm = 0.0, k = 0.0;
+  bool yg = false;
+  for (uint32_t r = tr * g.tile; r < r1; ++r)
+    for (uint32_t c = tc * g.tile; c < c1; ++c) {
+      const uint32_t lp = r * g.W + c;
+      const uint32_t n = count ? count[lp] : passes;
+      yg |= n < min_passes;
+      const double var = var_of_mean(A.m2[lp], n), mean = A.mean[lp];
+      if (isfinite(var) && isfinite(mean)) {
+        sv += var;
+        sm += mean;
+        k += 1.0;
+      }
+    }
+  *young = yg;
+  return k > 0.0 ? (float)(sqrt(sv / k) / (fmax(sm / k, 0.0) + lum_floor)) : 0.0f;
+}
+
+// one tile per lane -> err[T] (if asked) and flag[T] = young or e_T > rel_error (if asked)
+__global__ __launch_bounds__(256) void k_accum_tiles(AccumPlanes A, const uint32_t* count, uint32_t passes,
+                                                     TileGrid g, double lum_floor, uint32_t min_passes,
+                                                     double rel_error, float* err, uint32_t* flag) {
+  const uint32_t T = blockIdx.x * blockDim.x + threadIdx.x;
+  if (T >= g.tx * g.ty) return;
+  bool young;
+  const float e = tile_error(A, count, passes, g, T, lum_floor, min_passes, &young);
+  if (err) err[T] = e;
+  if (flag) flag[T] = (young || (double)e > rel_error) ? 1u : 0u;
+}
+
+// A pixel is active when its tile is (flag, by rt_accum_select) or its mask byte is set (mask,
+// by rt_accum_set_active)
+struct ActiveSrc {
+  const uint32_t* flag;
+  const uint8_t* mask;
+  TileGrid g;
+};
+RT_D bool pixel_active(const ActiveSrc& a, uint32_t lp) {
+  if (a.mask) return a.mask[lp] != 0;
+  const uint32_t r = lp / a.g.W, c = lp - r * a.g.W;
+  return a.flag[(r / a.g.tile) * a.g.tx + c / a.g.tile] != 0u;
+}
+// The compaction: cnt[b] = active pixels of block b's 256 pixels (four ballots) ...
+__global__ __launch_bounds__(256) void k_active_count(ActiveSrc a, uint32_t npix, uint32_t* cnt) {
+  __shared__ uint32_t wsum[4];
+  const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool act = lp < npix && pixel_active(a, lp);
+  const unsigned long long m = __ballot(act);
+  if (lane_id() == 0u) wsum[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+// ... cnt[0 .. nb) -> its exclusive prefix sums in place, cnt[nb] = the total: one block, 256
+// entries per step, a carry between the steps ...
+__global__ __launch_bounds__(256) void k_active_scan(uint32_t* cnt, uint32_t nb) {
+  __shared__ uint32_t buf[256];
+  __shared__ uint32_t carry;
+  const uint32_t t = threadIdx.x;
+  if (t == 0) carry = 0u;
+  __syncthreads();
+  for (uint32_t base = 0; base < nb; base += 256u) {
+    const uint32_t i = base + t;
+    const uint32_t x = i < nb ? cnt[i] : 0u;
+    buf[t] = x;
+    __syncthreads();
+    for (uint32_t off = 1; off < 256u; off <<= 1) {  // inclusive (Hillis-Steele)
+      const uint32_t y = t >= off ? buf[t - off] : 0u;
+      __syncthreads();
+      buf[t] += y;
+      __syncthreads();
+    }
+    const uint32_t c0 = carry;
+    if (i < nb) cnt[i] = c0 + buf[t] - x;
+    __syncthreads();
+    if (t == 255u) carry = c0 + buf[255];
+    __syncthreads();
+  }
+  if (t == 0) cnt[nb] = carry;
+}
+// ... and block b's active pixels to map[off[b] ..), in ascending order: a lane's place is
+// the active lanes below it in its wave plus the waves below its wave
+__global__ __launch_bounds__(256) void k_active_scatter(ActiveSrc a, uint32_t npix, const uint32_t* off,
+                                                        uint32_t* map) {
+  __shared__ uint32_t wsum[4];
+  const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool act = lp < npix && pixel_active(a, lp);
+  const unsigned long long m = __ballot(act);
+  const uint32_t w = threadIdx.x >> 6;
+  if (lane_id() == 0u) wsum[w] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint32_t base = off[blockIdx.x];
+  for (uint32_t i = 0; i < w; ++i) base += wsum[i];
+  if (act) map[base + prefix_count(m)] = lp;  // base + place < the total <= npix
+}
+
 }  // namespace rt
 
 // ==================================================================== host ==
@@ -148,6 +370,18 @@ struct rt_accum {
   double* part = nullptr;  // [kInfoBlocks][4], then the result [4]
   float *stage_rgb = nullptr, *stage_var = nullptr;
   hipStream_t own_stream = nullptr;
+  // per-pixel pass counts and the selection
+  uint32_t W = 0, rows = 0;
+  uint32_t* count = nullptr;  // [npix], valid while per_pixel
+  uint32_t* map = nullptr;    // [npix], the selection's sel_n active pixels
+  uint32_t* scan = nullptr;   // [ceil(npix / 256) + 1] block counts, then their prefix sums and the total
+  unsigned long long* red = nullptr;  // k_count_stats' results: [0..3) of count, [4..7) of the tile flags
+  bool per_pixel = false;     // a pass covered a part of the pixels: count holds, the _px kernels run
+  bool sel_valid = false;     // a selection was made since the last pass or reset
+  bool sel_tiles = false;     // ... by rt_accum_select (red[4..7) describes its tiles)
+  uint32_t sel_n = 0;         // active pixels of the last selection
+  int32_t n_tiles = 0;
+  const uint32_t* pass_map = nullptr;  // the map of the pass being folded (null: a whole pass)
 };
 
 namespace rt {
@@ -164,10 +398,99 @@ int accum_stream(rt_accum* a, hipStream_t* out) {
 // render_impl's sink: the pass is complete on `stream` up to the resolve
 int fold_pass(void* ctx, const Params& p, double scale, hipStream_t stream) {
   rt_accum* a = (rt_accum*)ctx;
-  if (p.npix != a->npix) return set_error(RT_ERR_INVALID, "rt_accum_add: the pass has %u pixels, the accumulator %u", p.npix, a->npix);
-  hipLaunchKernelGGL(k_accum_fold, dim3((a->npix + 255) / 256), dim3(256), 0, stream, p, a->A, scale,
-                     (uint32_t)a->passes + 1u);
+  const uint32_t want = a->pass_map ? a->sel_n : a->npix;
+  if (p.npix != want) return set_error(RT_ERR_INVALID, "rt_accum_add: the pass has %u pixels, the accumulator expects %u", p.npix, want);
+  if (!a->per_pixel && !a->pass_map) {  // uniform: every pixel has taken every pass
+    hipLaunchKernelGGL(k_accum_fold, dim3((a->npix + 255) / 256), dim3(256), 0, stream, p, a->A, scale,
+                       (uint32_t)a->passes + 1u);
+  } else {
+    if (!a->per_pixel)  // the first active pass: every pixel has `passes` so far
+      hipLaunchKernelGGL(k_accum_fill, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->count, a->npix,
+                         (uint32_t)a->passes);
+    hipLaunchKernelGGL(k_accum_fold_px, dim3((p.npix + 255) / 256), dim3(256), 0, stream, p, a->A, scale,
+                       a->npix, a->count, a->pass_map);
+  }
   HIP_OK(hipGetLastError());
+  return RT_OK;
+}
+
+// rt_adapt_opts with its defaults filled in, or RT_ERR_INVALID: needs no accumulator
+int adapt_opts_ok(const char* who, const rt_adapt_opts* in, rt_adapt_opts* o) {
+  if (!in) return set_error(RT_ERR_INVALID, "%s: null options", who);
+  *o = *in;
+  if (!(o->rel_error > 0.0)) return set_error(RT_ERR_INVALID, "%s: rel_error %g must be > 0", who, o->rel_error);
+  if (!(o->lum_floor >= 0.0) || !std::isfinite(o->lum_floor))
+    return set_error(RT_ERR_INVALID, "%s: lum_floor %g", who, o->lum_floor);
+  if (o->lum_floor == 0.0) o->lum_floor = 1e-2;
+  if (o->tile == 0) o->tile = 8;
+  if (o->tile < 1 || o->tile > 64) return set_error(RT_ERR_INVALID, "%s: tile %d is not in 1..64", who, o->tile);
+  if (o->min_passes == 0) o->min_passes = 4;
+  if (o->min_passes < 2) return set_error(RT_ERR_INVALID, "%s: min_passes %d must be >= 2", who, o->min_passes);
+  return RT_OK;
+}
+
+TileGrid tile_grid(const rt_accum* a, int32_t tile) {
+  TileGrid g;
+  g.W = a->W;
+  g.rows = a->rows;
+  g.tile = (uint32_t)tile;
+  g.tx = (a->W + g.tile - 1u) / g.tile;
+  g.ty = (a->rows + g.tile - 1u) / g.tile;
+  return g;
+}
+
+// the active pixels of `src` -> a->map, ascending; their number -> a->sel_n (one 4-byte read-back)
+int compact_active(rt_accum* a, const ActiveSrc& src, hipStream_t stream) {
+  const uint32_t nb = (a->npix + 255u) / 256u;
+  hipLaunchKernelGGL(k_active_count, dim3(nb), dim3(256), 0, stream, src, a->npix, a->scan);
+  hipLaunchKernelGGL(k_active_scan, dim3(1), dim3(256), 0, stream, a->scan, nb);
+  hipLaunchKernelGGL(k_active_scatter, dim3(nb), dim3(256), 0, stream, src, a->npix, a->scan, a->map);
+  HIP_OK(hipGetLastError());
+  uint32_t n = 0;
+  HIP_OK(hipMemcpyAsync(&n, a->scan + nb, sizeof n, hipMemcpyDeviceToHost, stream));
+  HIP_OK(hipStreamSynchronize(stream));
+  if (n > a->npix) return set_error(RT_ERR_DEVICE, "internal: %u active pixels of %u", n, a->npix);
+  a->sel_n = n;
+  a->sel_valid = true;
+  return RT_OK;
+}
+
+// device and stream of a call on `a` (a->mu held, DeviceGuard in the caller's scope)
+int accum_device(rt_accum* a, hipStream_t* stream) {
+  HIP_OK(hipSetDevice(a->opts.device));
+  return accum_stream(a, stream);
+}
+
+// {min, max, sum} of the per-pixel counts -> h (a->per_pixel)
+int count_stats(rt_accum* a, hipStream_t stream, unsigned long long h[3]) {
+  hipLaunchKernelGGL(k_count_stats, dim3(1), dim3(256), 0, stream, a->count, a->npix, a->red);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(h, a->red, 3 * sizeof h[0], hipMemcpyDeviceToHost, stream));
+  HIP_OK(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+
+int accum_counts(rt_accum* a, int32_t* out, bool host) {
+  if (!a || !out) return set_error(RT_ERR_INVALID, "rt_accum_counts: null");
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (a->npix == 0) return RT_OK;
+  if (host && !a->per_pixel) {
+    std::fill(out, out + a->npix, a->passes);
+    return RT_OK;
+  }
+  DeviceGuard dg;
+  hipStream_t stream;
+  int rc;
+  if ((rc = accum_device(a, &stream))) return rc;
+  if (!a->per_pixel) {
+    hipLaunchKernelGGL(k_accum_fill, dim3((a->npix + 255) / 256), dim3(256), 0, stream, (uint32_t*)out, a->npix,
+                       (uint32_t)a->passes);
+    HIP_OK(hipGetLastError());
+  } else {
+    HIP_OK(hipMemcpyAsync(out, a->count, (size_t)a->npix * sizeof(uint32_t),
+                          host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
+  }
+  HIP_OK(hipStreamSynchronize(stream));
   return RT_OK;
 }
 
@@ -191,8 +514,12 @@ int accum_resolve(rt_accum* a, float* rgb, float* var, bool host) {
   float* drgb = !rgb ? nullptr : host ? a->stage_rgb : rgb;
   float* dvar = !var ? nullptr : host ? a->stage_var : var;
   const double scale_n = a->passes > 0 ? a->cd.pixel_samples_scale / (double)a->passes : 0.0;
-  hipLaunchKernelGGL(k_accum_resolve, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->A, a->npix,
-                     scale_n, (uint32_t)a->passes, drgb, dvar);
+  if (a->per_pixel)
+    hipLaunchKernelGGL(k_accum_resolve_px, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->A, a->npix,
+                       a->cd.pixel_samples_scale, a->count, drgb, dvar);
+  else
+    hipLaunchKernelGGL(k_accum_resolve, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->A, a->npix,
+                       scale_n, (uint32_t)a->passes, drgb, dvar);
   HIP_OK(hipGetLastError());
   if (host && rgb)
     HIP_OK(hipMemcpyAsync(rgb, drgb, 3 * (size_t)a->npix * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -260,11 +587,16 @@ int rt_accum_create(rt_scene* s, const rt_camera* cam, const rt_render_opts* opt
   a->max_passes = max_passes;
   a->npix = (uint32_t)npix64;
   a->ss = (uint32_t)ss;
+  a->W = (uint32_t)cd.width;
+  a->rows = a->W ? a->npix / a->W : 0u;
   const size_t n = std::max<size_t>(a->npix, 1);
-  // sum | side | mean | m2 (f64 / u64), the info partials, then flags and the staging (4 B)
+  // sum | side | mean | m2 (f64 / u64), the info partials and the count statistics, then flags,
+  // the staging (4 B; the selection's tile flags or mask bytes and tile errors pass through it
+  // too), the counts, the pixel map and the scan scratch
   a->state_bytes = n * (3 * 8 + 3 * 8 + 8 + 8);
-  const size_t part_bytes = (size_t)(kInfoBlocks + 1) * 4 * sizeof(double);
-  const size_t total = a->state_bytes + part_bytes + n * 4 + n * 16;
+  const size_t part_bytes = (size_t)(kInfoBlocks + 1) * 4 * sizeof(double) + 8 * sizeof(unsigned long long);
+  const size_t scan_n = (n + 255) / 256 + 1;
+  const size_t total = a->state_bytes + part_bytes + n * 4 + n * 16 + n * 4 + n * 4 + scan_n * 4;
   DeviceGuard dg;
   hipError_t e = hipSetDevice(o.device);
   if (e == hipSuccess) e = hipMalloc(&a->buf, total);
@@ -284,6 +616,10 @@ int rt_accum_create(rt_scene* s, const rt_camera* cam, const rt_render_opts* opt
   a->A.flags = (uint32_t*)(b + a->state_bytes + part_bytes);
   a->stage_rgb = (float*)(b + a->state_bytes + part_bytes + n * 4);
   a->stage_var = a->stage_rgb + 3 * n;
+  a->red = (unsigned long long*)(a->part + (size_t)(kInfoBlocks + 1) * 4);
+  a->count = (uint32_t*)(a->stage_var + n);
+  a->map = a->count + n;
+  a->scan = a->map + n;
   {
     std::lock_guard<std::mutex> lk(s->s.mu);
     s->s.accums.push_back(a);
@@ -320,6 +656,9 @@ int rt_accum_reset(rt_accum* a) {
   HIP_OK(hipMemsetAsync(a->A.flags, 0, std::max<size_t>(a->npix, 1) * sizeof(uint32_t), stream));
   HIP_OK(hipStreamSynchronize(stream));
   a->passes = 0;
+  a->per_pixel = a->sel_valid = a->sel_tiles = false;  // uniform again, no selection
+  a->sel_n = 0;
+  a->n_tiles = 0;
   return RT_OK;
 }
 
@@ -332,9 +671,165 @@ int rt_accum_add(rt_accum* a, uint64_t seed, rt_stats* stats) {
   rt_render_opts o = a->opts;
   o.seed = seed;
   const PassSink sink = {(uint32_t)a->max_passes, fold_pass, a};
+  a->pass_map = nullptr;
   const int rc = render_pass(a->scene, &a->cam, &o, stats, &sink);
-  if (rc == RT_OK) ++a->passes;
+  if (rc == RT_OK) {
+    ++a->passes;
+    a->sel_valid = false;  // a selection describes the state it was made from
+  }
   return rc;
+}
+
+int rt_accum_add_active(rt_accum* a, uint64_t seed, rt_stats* stats) {
+  using namespace rt;
+  if (!a) return set_error(RT_ERR_INVALID, "rt_accum_add_active: null accumulator");
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (!a->sel_valid)
+    return set_error(RT_ERR_INVALID, "rt_accum_add_active: no selection since the last pass or reset");
+  if (a->sel_n == 0) {  // nothing to render: no pass is counted
+    if (stats) memset(stats, 0, sizeof *stats);
+    return RT_OK;
+  }
+  if (a->passes >= a->max_passes)
+    return set_error(RT_ERR_INVALID, "rt_accum_add_active: the accumulator holds its %d passes", a->max_passes);
+  rt_render_opts o = a->opts;
+  o.seed = seed;
+  const PassSink sink = {(uint32_t)a->max_passes, fold_pass, a};
+  // every pixel active: the plain whole pass (the same bits, the grouped chunk order)
+  const bool part = a->sel_n < a->npix;
+  const PixelMap pm = {a->map, a->sel_n};
+  a->pass_map = part ? a->map : nullptr;
+  const int rc = render_pass(a->scene, &a->cam, &o, stats, &sink, part ? &pm : nullptr);
+  a->pass_map = nullptr;
+  if (rc == RT_OK) {
+    ++a->passes;
+    if (part) a->per_pixel = true;
+    a->sel_valid = false;  // consumed
+  }
+  return rc;
+}
+
+int rt_accum_select(rt_accum* a, const rt_adapt_opts* opts, uint64_t* n_active_pixels) {
+  using namespace rt;
+  rt_adapt_opts o;
+  int rc;
+  if ((rc = adapt_opts_ok("rt_accum_select", opts, &o))) return rc;
+  if (!a) return set_error(RT_ERR_INVALID, "rt_accum_select: null accumulator");
+  std::lock_guard<std::mutex> lk(a->mu);
+  const TileGrid g = tile_grid(a, o.tile);
+  if (a->npix == 0) {
+    a->sel_tiles = true;
+    a->n_tiles = 0;
+    a->sel_n = 0;
+    a->sel_valid = true;
+    if (n_active_pixels) *n_active_pixels = 0;
+    return RT_OK;
+  }
+  DeviceGuard dg;
+  hipStream_t stream;
+  if ((rc = accum_device(a, &stream))) return rc;
+  a->sel_valid = a->sel_tiles = false;  // until the new selection stands
+  a->n_tiles = 0;
+  a->sel_n = 0;
+  uint32_t* flag = (uint32_t*)a->stage_rgb;  // tiles <= pixels
+  const uint32_t nt = g.tx * g.ty;
+  hipLaunchKernelGGL(k_accum_tiles, dim3((nt + 255) / 256), dim3(256), 0, stream, a->A,
+                     a->per_pixel ? a->count : nullptr, (uint32_t)a->passes, g, o.lum_floor, (uint32_t)o.min_passes,
+                     o.rel_error, (float*)nullptr, flag);
+  hipLaunchKernelGGL(k_count_stats, dim3(1), dim3(256), 0, stream, flag, nt, a->red + 4);
+  HIP_OK(hipGetLastError());
+  const ActiveSrc src = {flag, nullptr, g};
+  if ((rc = compact_active(a, src, stream))) return rc;
+  a->sel_tiles = true;
+  a->n_tiles = (int32_t)nt;
+  if (n_active_pixels) *n_active_pixels = a->sel_n;
+  return RT_OK;
+}
+
+int rt_accum_set_active(rt_accum* a, const uint8_t* mask_host, uint64_t* n_active_pixels) {
+  using namespace rt;
+  if (!mask_host) return set_error(RT_ERR_INVALID, "rt_accum_set_active: null mask");
+  if (!a) return set_error(RT_ERR_INVALID, "rt_accum_set_active: null accumulator");
+  std::lock_guard<std::mutex> lk(a->mu);
+  a->sel_tiles = false;
+  a->n_tiles = 0;
+  if (a->npix == 0) {
+    a->sel_n = 0;
+    a->sel_valid = true;
+    if (n_active_pixels) *n_active_pixels = 0;
+    return RT_OK;
+  }
+  DeviceGuard dg;
+  hipStream_t stream;
+  int rc;
+  if ((rc = accum_device(a, &stream))) return rc;
+  a->sel_valid = false;
+  a->sel_n = 0;
+  uint8_t* mask = (uint8_t*)a->stage_rgb;
+  HIP_OK(hipMemcpyAsync(mask, mask_host, a->npix, hipMemcpyHostToDevice, stream));
+  const ActiveSrc src = {nullptr, mask, tile_grid(a, 1)};
+  if ((rc = compact_active(a, src, stream))) return rc;
+  if (n_active_pixels) *n_active_pixels = a->sel_n;
+  return RT_OK;
+}
+
+int rt_accum_counts(rt_accum* a, int32_t* counts_host) { return rt::accum_counts(a, counts_host, true); }
+int rt_accum_counts_device(rt_accum* a, int32_t* counts_dev) { return rt::accum_counts(a, counts_dev, false); }
+
+int rt_accum_tile_error(rt_accum* a, const rt_adapt_opts* opts, float* err_host, int32_t* tiles_x,
+                        int32_t* tiles_y) {
+  using namespace rt;
+  rt_adapt_opts o;
+  int rc;
+  if ((rc = adapt_opts_ok("rt_accum_tile_error", opts, &o))) return rc;
+  if (!a) return set_error(RT_ERR_INVALID, "rt_accum_tile_error: null accumulator");
+  std::lock_guard<std::mutex> lk(a->mu);
+  const TileGrid g = tile_grid(a, o.tile);
+  if (tiles_x) *tiles_x = (int32_t)g.tx;
+  if (tiles_y) *tiles_y = (int32_t)g.ty;
+  const uint32_t nt = g.tx * g.ty;
+  if (!err_host || nt == 0) return RT_OK;
+  DeviceGuard dg;
+  hipStream_t stream;
+  if ((rc = accum_device(a, &stream))) return rc;
+  hipLaunchKernelGGL(k_accum_tiles, dim3((nt + 255) / 256), dim3(256), 0, stream, a->A,
+                     a->per_pixel ? a->count : nullptr, (uint32_t)a->passes, g, o.lum_floor, (uint32_t)o.min_passes,
+                     o.rel_error, a->stage_var, (uint32_t*)nullptr);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(err_host, a->stage_var, (size_t)nt * sizeof(float), hipMemcpyDeviceToHost, stream));
+  HIP_OK(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+
+int rt_accum_adapt_info(rt_accum* a, rt_adapt_info* out) {
+  using namespace rt;
+  if (!a || !out) return set_error(RT_ERR_INVALID, "rt_accum_adapt_info: null");
+  std::lock_guard<std::mutex> lk(a->mu);
+  memset(out, 0, sizeof *out);
+  out->active_pixels = a->sel_n;
+  out->n_tiles = a->n_tiles;
+  out->min_count = out->max_count = a->passes;
+  out->total_samples = (uint64_t)a->ss * (uint64_t)a->passes * a->npix;
+  const bool tiles = a->sel_tiles && a->n_tiles > 0 && a->npix > 0;
+  if (a->npix == 0 || (!a->per_pixel && !tiles)) return RT_OK;
+  DeviceGuard dg;
+  hipStream_t stream;
+  int rc;
+  if ((rc = accum_device(a, &stream))) return rc;
+  if (a->per_pixel) {
+    unsigned long long h[3];
+    if ((rc = count_stats(a, stream, h))) return rc;
+    out->min_count = (int32_t)h[0];
+    out->max_count = (int32_t)h[1];
+    out->total_samples = (uint64_t)a->ss * h[2];
+  }
+  if (tiles) {  // the last rt_accum_select's tile flags, summed when it ran
+    unsigned long long h[3];
+    HIP_OK(hipMemcpyAsync(h, a->red + 4, sizeof h, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    out->active_tiles = (int32_t)h[2];
+  }
+  return RT_OK;
 }
 
 int rt_accum_resolve(rt_accum* a, float* rgb_host, float* var_host) {
@@ -361,12 +856,20 @@ int rt_accum_info_get(rt_accum* a, rt_accum_info* out) {
   if ((rc = accum_stream(a, &stream))) return rc;
   const uint32_t nb = std::min<uint32_t>((a->npix + 255u) / 256u, (uint32_t)kInfoBlocks);
   double* res = a->part + 4 * (size_t)kInfoBlocks;
-  hipLaunchKernelGGL(k_accum_info1, dim3(nb), dim3(256), 0, stream, a->A, a->npix, (uint32_t)a->passes, a->part);
+  if (a->per_pixel)
+    hipLaunchKernelGGL(k_accum_info1_px, dim3(nb), dim3(256), 0, stream, a->A, a->npix, a->count, a->part);
+  else
+    hipLaunchKernelGGL(k_accum_info1, dim3(nb), dim3(256), 0, stream, a->A, a->npix, (uint32_t)a->passes, a->part);
   hipLaunchKernelGGL(k_accum_info2, dim3(1), dim3(256), 0, stream, a->part, nb, res);
   HIP_OK(hipGetLastError());
   double h[4];
   HIP_OK(hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
+  if (a->per_pixel) {  // the most any pixel has
+    unsigned long long c[3];
+    if ((rc = count_stats(a, stream, c))) return rc;
+    out->samples_per_pixel = (uint64_t)a->ss * c[1];
+  }
   out->nonfinite_pixels = (uint64_t)h[3];
   if (h[2] > 0.0) {
     out->rms_std_error = sqrt(h[0] / h[2]);

@@ -176,8 +176,9 @@ __shared__ unsigned long long g_dinfo[4][3];  // ... and then: samples left, bus
 // TREE: 4 = BVH4, 5 = compressed BVH4 (64-B nodes, global only), 2 = BVH2, 0 = no tree
 // (every record tested, tiny scenes).  SHAPE (TREE 0, FT 0, LDS only): the record layout the
 // loop is compiled for (rt_device.h brute_shape), 0 = any.  LIGHT (the same kernels only): the
-// lean light kind the light sampling and light pdf are compiled for (rt_device.h), 0 = any list
-template <bool LDS, uint32_t FT, int TREE, int SHAPE = 0, int LIGHT = 0>
+// lean light kind the light sampling and light pdf are compiled for (rt_device.h), 0 = any list.
+// MAP: an active-pixel pass over the pixels listed in P.pixmap (chunk_ids; rt_fused_map.hip)
+template <bool LDS, uint32_t FT, int TREE, int SHAPE = 0, int LIGHT = 0, bool MAP = false>
 __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) {
   static_assert(SHAPE == 0 || (LDS && FT == 0u && TREE == 0), "shapes: the lean LDS record loop only");
   static_assert(LIGHT == 0 || (LDS && FT == 0u && TREE == 0), "light kinds: the lean LDS record loop only");
@@ -248,7 +249,7 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
     if constexpr (kSplit)
       if (b.part >= (uint32_t)kMaxParts) split_samples(P, s, has, c, j0, n0);
     if (c != 0xFFFFFFFFu) {
-      start_sample<false, cam_mode(FT), FT == 0u && TREE == 0>(P, slot, s, c, j0);
+      start_sample<false, cam_mode(FT), FT == 0u && TREE == 0, MAP>(P, slot, s, c, j0);
       if constexpr (kSplit)
         if (j0) s.flags = F_SPLIT | (n0 << kCountShift);
       trav_init<FT>(P.sc, s.o, s.d, s.time, tr);
@@ -386,5 +387,16 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
   X(false, (FT_SPHERE | FT_TRI | FT_METAL), 4)                              \
   X(true, (FT_SPHERE | FT_TRI | FT_METAL | FT_DIEL | FT_CHECKER), 4)        \
   X(false, (FT_SPHERE | FT_TRI | FT_METAL | FT_DIEL | FT_CHECKER), 4)
+
+// The MAP twins (active-pixel passes), compiled in rt_fused_map.hip with the
+// default scheduler: one for every kernel the dispatcher selects with no knob set, but the
+// record loop's SHAPE / LIGHT kernels (the generic record loop renders the same bits).
+// X(LDS, FT, TREE); the sets are rt_device.h kFtSets and FT_ALL.
+#define RT_FUSED_MAP_KERNELS(X)                                                      \
+  X(true, kFtSets[0], 0) X(false, kFtSets[0], 0) X(true, kFtSets[1], 0) X(false, kFtSets[1], 0) \
+  X(true, kFtSets[0], 4) X(false, kFtSets[0], 4) X(true, kFtSets[1], 4) X(false, kFtSets[1], 4) \
+  X(true, kFtSets[2], 4) X(false, kFtSets[2], 4) X(true, kFtSets[3], 4) X(false, kFtSets[3], 4) \
+  X(true, kFtSets[4], 4) X(false, kFtSets[4], 4) X(true, FT_ALL, 4) X(false, FT_ALL, 4)         \
+  X(false, kFtSets[2], 5) X(false, kFtSets[3], 5) X(false, kFtSets[4], 5) X(false, FT_ALL, 5)
 
 }  // namespace rt

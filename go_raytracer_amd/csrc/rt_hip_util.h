@@ -58,8 +58,17 @@ struct PassSink {
   int (*fold)(void* ctx, const Params& p, double scale, hipStream_t stream);
   void* ctx;
 };
+// map (optional): an active-pixel pass over the n sorted local pixels of the
+// share listed in `pixels` (device memory).  The pass is then an image of n pixels of its own:
+// p.npix = n, p's sums are indexed by the place in the list, the chunk plan is the one of an
+// n x 1 image, and the fused kernel's MAP twin runs whatever the mode asks (RT_ERR_UNSUPPORTED
+// before any launch for RT_MODE_WAVEFRONT, and for a structure without a twin).
+struct PixelMap {
+  const uint32_t* pixels;
+  uint32_t n;
+};
 int render_pass(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
-                const PassSink* sink);
+                const PassSink* sink, const PixelMap* map = nullptr);
 
 // Grow-only device scratch, one buffer per device ordinal (as rt_output.hip's): no allocation
 // per call once warm.  The caller serialises its users, and no work that reads an old buffer

@@ -112,6 +112,9 @@ struct Params {
   int trace_cap;
   LeanLight ll;               // the light of a lean light kind's kernel (rt_device.h; set only
                               // for a launch of such a kernel, read by it alone)
+  const uint32_t* pixmap;     // an active-pixel pass (k_fused<.., MAP>): local pixel
+                              // lv of the pass stands for the share's local pixel pixmap[lv]
+                              // (sorted, npix entries); null otherwise, read by MAP kernels alone
 };
 
 RT_D uint32_t pack_path(uint32_t j, uint32_t k, uint32_t nst, uint32_t flags) {
@@ -247,7 +250,17 @@ RT_D uint32_t chunk_pixel(const Params& P, uint32_t chunk, uint32_t& sub) {
 // ONE: a launch without a tail phase (S1 = ss), with the launch parameters held in SGPRs:
 // the record-loop kernel, whose chunk starts lost 3 % to the tail mapping's kernel-argument
 // loads (profiles/r4_tail_code_ab.jsonl); render_impl never gives it a tail
-template <bool ONE = false>
+// MAP: an active-pixel pass.  lpix, the chunk records and the pass's sums stay
+// in the pass's own (virtual) pixels, P.npix of them; row, col and gpix, which key the random
+// stream and aim the camera ray, are those of the share's pixel pixmap[lpix].  The table's
+// address is read from the kernel-argument segment where a chunk starts (kparams), not held
+// in SGPRs across the loop.
+template <bool MAP>
+RT_D uint32_t mapped_pixel(uint32_t lpix) {
+  if constexpr (MAP) return *(const glb_u32*)(kparams()->pixmap + lpix);
+  return lpix;
+}
+template <bool ONE = false, bool MAP = false>
 RT_D Ids chunk_ids(const Params& P, uint32_t chunk) {
   Ids r;
   uint32_t sub;
@@ -256,8 +269,9 @@ RT_D Ids chunk_ids(const Params& P, uint32_t chunk) {
     const uint32_t rr = chunk - q * P.fd_gchunks.d;
     sub = fdiv(rr, P.fd_gpix);
     r.lpix = q * P.fd_gpix.d + (rr - sub * P.fd_gpix.d);
-    const uint32_t row_l = fdiv(r.lpix, P.fd_width);
-    r.col = r.lpix - row_l * (uint32_t)P.width;
+    const uint32_t rp = mapped_pixel<MAP>(r.lpix);
+    const uint32_t row_l = fdiv(rp, P.fd_width);
+    r.col = rp - row_l * (uint32_t)P.width;
     r.row = row_l * (uint32_t)P.nranks + (uint32_t)P.rank;
     r.gpix = r.row * (uint32_t)P.width + r.col;
     r.sample0 = sub * P.K;
@@ -270,8 +284,9 @@ RT_D Ids chunk_ids(const Params& P, uint32_t chunk) {
   uint32_t row_l = fdiv(lrev, P.fd_width);
   r.col = lrev - row_l * (uint32_t)P.width;
 #else
-  uint32_t row_l = fdiv(r.lpix, P.fd_width);
-  r.col = r.lpix - row_l * (uint32_t)P.width;
+  const uint32_t rp = mapped_pixel<MAP>(r.lpix);
+  uint32_t row_l = fdiv(rp, P.fd_width);
+  r.col = rp - row_l * (uint32_t)P.width;
 #endif
   r.row = row_l * (uint32_t)P.nranks + (uint32_t)P.rank;
   r.gpix = r.row * (uint32_t)P.width + r.col;
@@ -2113,9 +2128,9 @@ RT_D void next_sample(const Params& P, uint32_t slot, Path& s, uint32_t j, const
 }
 
 // camera ray for sample j of `chunk` (path state reset)
-template <bool SOA, int CAM = 0, bool ONE = false>
+template <bool SOA, int CAM = 0, bool ONE = false, bool MAP = false>
 RT_D void start_sample(const Params& P, uint32_t slot, Path& s, uint32_t chunk, uint32_t j) {
-  Ids id = chunk_ids<ONE>(P, chunk);
+  Ids id = chunk_ids<ONE, MAP>(P, chunk);
   const rt_u32x4 r = rt_rng_draw(P.seed, id.gpix, id.sample0 + j, RT_STREAM_CAMERA);
   camera_ray_r<CAM>(P, id, id.sample0 + j, r, s.o, s.d, s.time);
   s.spare = rt_spare24(r);

@@ -500,9 +500,16 @@ static int ensure_ostack(RenderState* st, uint32_t cols) {
 }
 
 // *use_csum in: the render wants the chunk sums; out: it has them (st->csum)
-static int ensure_csum(RenderState* st, uint32_t n_chunks, bool* use_csum_io) {
+// keep: an active-pixel pass neither allocates nor frees: it takes the buffer
+// the whole passes left when its chunks fit (a smaller K can give it more chunks than they
+// had), and pixel atomics otherwise
+static int ensure_csum(RenderState* st, uint32_t n_chunks, bool* use_csum_io, bool keep = false) {
   int rc;
   bool use_csum = *use_csum_io;
+  if (keep) {
+    *use_csum_io = use_csum && st->csum && st->csum_chunks >= n_chunks;
+    return RT_OK;
+  }
   // fused: the per-chunk sums (32 B per chunk, every record stored once per render: no clear).
   // The buffer grows with the sample count, not the image: above its cap (RT_CSUM_MAX_MB,
   // default 16 GiB, and at most half of the device's free memory) or when it cannot be
@@ -553,6 +560,9 @@ static_assert(FT_SPHERE == RT_FT_SPHERE && FT_TRI == RT_FT_TRI && FT_METAL == RT
 
 #define RT_FUSED_EXTERN(L, F, T) extern template __global__ void k_fused<L, F, T>(Params);
 RT_FUSED_ILP_KERNELS(RT_FUSED_EXTERN)  // defined in rt_fused_sets.hip
+#undef RT_FUSED_EXTERN
+#define RT_FUSED_EXTERN(L, F, T) extern template __global__ void k_fused<L, F, T, 0, 0, true>(Params);
+RT_FUSED_MAP_KERNELS(RT_FUSED_EXTERN)  // defined in rt_fused_map.hip
 #undef RT_FUSED_EXTERN
 
 template <bool LDS>
@@ -610,6 +620,16 @@ static const void* pick_fused(bool lds, uint32_t set, int tree, int shape = 0, i
   }
   if (tree != 4) return nullptr;  // no such kernel: render_impl never asks (see tree there)
   return lds ? fused_for<true>(set) : fused_for<false>(set);
+}
+
+// The MAP twin (an active-pixel pass, rt_fused.h RT_FUSED_MAP_KERNELS) of the kernel
+// pick_fused(lds, set, tree) returns; nullptr where there is none (the opt-in trees 2 and 8)
+static const void* pick_fused_map(bool lds, uint32_t set, int tree) {
+#define RT_FUSED_PICK(L, F, T) \
+  if (lds == L && set == (F) && tree == T) return (const void*)k_fused<L, F, T, 0, 0, true>;
+  RT_FUSED_MAP_KERNELS(RT_FUSED_PICK)
+#undef RT_FUSED_PICK
+  return nullptr;
 }
 
 // rt_render_multi's share hand-off: after the resolve, the share's image (rows of
@@ -695,8 +715,10 @@ struct StructurePlan {
   size_t lds_bytes;  // dynamic LDS of the kernel
   bool wants_qbvh;   // a BVH4 read through L1/L2 whose set has a compressed-BVH4 kernel
 };
+// no_default_bvh2: an active-pixel pass, whose kernels have no BVH2 twin, takes
+// the BVH4 where the BVH2 is the default choice (49..64 leaf entries); RT_TREE=2 still asks for it
 static int plan_structure(const Scene* s, const DeviceScene* ds, uint32_t ft_set, int mode,
-                          StructurePlan* out) {
+                          StructurePlan* out, bool no_default_bvh2 = false) {
   // The fused kernel's LDS scene cache (stage_nodes): all BVH nodes, then the
   // leaf records when both fit, within the LDS a workgroup may take at the
   // kernel's target waves per SIMD (160 KB per CU, 24 KB of stacks per group).
@@ -714,6 +736,7 @@ static int plan_structure(const Scene* s, const DeviceScene* ds, uint32_t ft_set
   int tree = mode == RT_MODE_FUSED ? fused_base_tree(s, ft_set) : 4;
   if (tree == 0 && !ds->brute_pairs) tree = 4;  // (records not uploaded: RT_BRUTE_MAX raised since)
   if (tree == 2 && !ds->nodes2) tree = 4;
+  if (tree == 2 && no_default_bvh2 && env_tree != 2) tree = 4;
   const size_t lds_slots = slots_for(tree);
   const size_t brute_slots = ds->brute_slots;  // record-loop pairs, 2 x 64 B each
   const int smem_env = env_int("RT_BRUTE_SMEM", -1);
@@ -1210,7 +1233,8 @@ static int fill_stats(rt_stats* stats, const Scene* s, const DeviceScene* ds, co
 
 static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
                        float* out_host, float* out_dev, rt_stats* stats, int slot_id = 0,
-                       const Gather* gather = nullptr, const PassSink* sink = nullptr) {
+                       const Gather* gather = nullptr, const PassSink* sink = nullptr,
+                       const PixelMap* map = nullptr) {
   if (!scene || !cam) return set_error(RT_ERR_INVALID, "rt_render: null scene/camera");
   rt_render_opts o{};
   if (opts) o = *opts;
@@ -1239,16 +1263,22 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
 
   const uint32_t W = (uint32_t)cd.width, H = (uint32_t)cd.height;
   const uint32_t rows = rank_rows(H, o.rank, o.nranks);
-  const uint32_t npix = rows * W;
+  const uint32_t npix_share = rows * W;
+  // an active-pixel pass renders the map's n pixels as an image of its own
+  if (map && (!map->pixels || map->n == 0 || map->n > npix_share))
+    return set_error(RT_ERR_INVALID, "rt_render: a pixel map of %u of %u pixels", map->n, npix_share);
+  const uint32_t npix = map ? map->n : npix_share;
   const uint32_t ss = (uint32_t)cd.spp_sqrt * (uint32_t)cd.spp_sqrt;
   int mode = o.mode;
+  if (map && mode == RT_MODE_WAVEFRONT)
+    return set_error(RT_ERR_UNSUPPORTED, "an active-pixel pass runs the fused kernel only (mode wavefront)");
   if (mode != RT_MODE_WAVEFRONT && mode != RT_MODE_FUSED) mode = RT_MODE_FUSED;
   const int depth_cap = cd.max_depth + 1;
   const uint32_t ft_set = scene_ft_set(s);
 
   // what to traverse and the kernel for it (the feature pass takes the same: aov_view)
   StructurePlan sp;
-  if ((rc = plan_structure(s, ds, ft_set, mode, &sp))) return rc;
+  if ((rc = plan_structure(s, ds, ft_set, mode, &sp, map != nullptr))) return rc;
   if (sp.tree == 4 && sp.wants_qbvh && (rc = take_qbvh(s, ds, ft_set, &sp))) return rc;
   // A lean light kind's kernel holds merge_ok as the constant true: a render whose background
   // clears the flag (below) launches the layout's kernel with the general light code instead
@@ -1256,6 +1286,12 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
                          (float)cd.background[2] >= 0.0f)) {
     sp.light = 0;
     sp.kernel = pick_fused(sp.f_lds, ft_set, sp.tree, sp.shape, 0);
+  }
+  if (map) {  // the structure's MAP twin; the record loop's is the generic one (the same bits)
+    sp.shape = sp.light = 0;
+    sp.kernel = pick_fused_map(sp.f_lds, ft_set, sp.tree);
+    if (!sp.kernel)
+      return set_error(RT_ERR_UNSUPPORTED, "an active-pixel pass has no kernel for tree %d, chosen by RT_TREE / RT_BVH8", sp.tree);
   }
   // path slots: the fused kernel's resident lanes, or the wavefront queue's length
   uint32_t P = 0;
@@ -1266,14 +1302,17 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     P = (uint32_t)fused_blocks * 256u;
   }
   ChunkPlan cp;
-  if ((rc = plan_chunks(npix, rows, W, ss, P, o.chunk, ft_set, sp.tree, sp.f_lds, mode, &cp))) return rc;
+  // (a map: one chunk group, chunk_pixel's "G = npix" order over the sorted list)
+  if ((rc = plan_chunks(npix, map ? 1u : rows, map ? npix : W, ss, P, o.chunk, ft_set, sp.tree, sp.f_lds, mode, &cp)))
+    return rc;
   const uint32_t n_chunks = cp.n_chunks;
   if (mode != RT_MODE_FUSED) {
     P = o.path_slots > 0 ? (uint32_t)o.path_slots : (1u << 20);
     P = std::max<uint32_t>(256u, std::min<uint32_t>(P, std::max<uint32_t>(n_chunks, 256u)));
     P = (P + 255u) & ~255u;
   }
-  if ((rc = ensure_state(slot, o.device, P, depth_cap, std::max<uint32_t>(npix, 1),
+  // (sized for the whole share with a map too: neither pass reallocates the other's buffers)
+  if ((rc = ensure_state(slot, o.device, P, depth_cap, std::max<uint32_t>(npix_share, 1),
                          mode == RT_MODE_WAVEFRONT)))
     return rc;
   RenderState* st = slot->st;
@@ -1284,7 +1323,7 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     return rc;
   if ((rc = ensure_ostack(st, mode == RT_MODE_FUSED ? P : (uint32_t)st->resident_blocks * 256u))) return rc;
   bool use_csum = mode == RT_MODE_FUSED && env_int("RT_CSUM", 1) != 0;
-  if ((rc = ensure_csum(st, n_chunks, &use_csum))) return rc;
+  if ((rc = ensure_csum(st, n_chunks, &use_csum, map != nullptr))) return rc;
 
   hipStream_t stream = (hipStream_t)o.stream;
   if (!stream) {
@@ -1304,6 +1343,7 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
     if (!p.sc.merge_ok) return set_error(RT_ERR_UNSUPPORTED, "internal: lean light kernel without merge_ok");
     p.ll = ds->light_block;
   }
+  p.pixmap = map ? map->pixels : nullptr;
   p.K = cp.K;
   p.K2 = cp.K2;
   p.S1 = cp.S1;
@@ -1453,8 +1493,8 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
 }
 
 int render_pass(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
-                const PassSink* sink) {
-  return render_impl(scene, cam, opts, nullptr, nullptr, stats, 0, nullptr, sink);
+                const PassSink* sink, const PixelMap* map) {
+  return render_impl(scene, cam, opts, nullptr, nullptr, stats, 0, nullptr, sink, map);
 }
 
 // rows of share i ([rows_per][W][3] at gather + i*rows_per*W*3) -> image rows r = i + n*k

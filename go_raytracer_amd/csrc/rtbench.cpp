@@ -26,7 +26,12 @@
 // seeds seed .. seed + N - 1, through the pass accumulator; -passes 1 writes the plain
 // render's bytes), -until E (stop once the accumulator's rel_error is <= E, checked from the
 // second pass on; at most -passes passes, 1024 without it).  With either, -progress reports
-// passes and the statistics line gains passes, rel_error and ms_accum.  -cpuprofile has no pprof to drive on the GPU path: the file
+// passes and the statistics line gains passes, rel_error and ms_accum.  -adaptive E (adaptive
+// passes: every pass is rt_accum_select + rt_accum_add_active, so whole passes while some pixel
+// has fewer than the library's min_passes, then passes over the tiles whose error figure is
+// above E only, until none is left or -passes, default 1024, is reached; composes with
+// -denoise[-var], -aov and -o; the statistics line gains active_last, samples_total and
+// samples_full), -counts FILE (with -adaptive: the passes per pixel as grey, count / max).  -cpuprofile has no pprof to drive on the GPU path: the file
 // receives the same JSON statistics instead.
 #include <unistd.h>
 
@@ -55,9 +60,10 @@ struct Flag {
 };
 
 struct Args {
-  std::string cpuprofile, out = "image.ppm", mode = "auto", assets, aov;
+  std::string cpuprofile, out = "image.ppm", mode = "auto", assets, aov, counts;
   long long N = 1, S = -1, device = 0, width = 0, spp = 0, depth = 0, slices = 0, passes = 0;
-  double until = 0.0;
+  double until = 0.0, adaptive = 0.0;
+  bool adaptive_set = false;
   unsigned long long seed = 1, tree_seed = 1;
   bool progress = false, stats = false, denoise = false, denoise_var = false;
 };
@@ -67,10 +73,14 @@ std::vector<Flag> flags(Args& a) {
       {"N", "Set the number of cores to allocate to rendering", Flag::INT, &a.N, "1"},
       {"S", "Set the scene to render, default will render a custom scene function", Flag::INT,
        &a.S, "-1"},
+      {"adaptive", "adaptive passes: after the first whole passes, resample only the tiles whose relative error is > E (at most -passes, default 1024)",
+       Flag::F64, &a.adaptive, ""},
       {"aov", "write PREFIX_albedo.ppm, PREFIX_normal.ppm and PREFIX_depth.ppm (first-hit feature buffers)",
        Flag::STR, &a.aov, ""},
       {"assets", "directory holding earthmap.jpg / dragon.obj (default: <exe dir>/../assets)",
        Flag::STR, &a.assets, ""},
+      {"counts", "with -adaptive: write the passes per pixel as a grey image (count / largest count)", Flag::STR,
+       &a.counts, ""},
       {"cpuprofile", "Write cpu profile to file (here: render statistics as JSON)", Flag::STR,
        &a.cpuprofile, ""},
       {"denoise", "denoise the image (a-trous filter guided by the feature buffers) before it is written",
@@ -190,6 +200,17 @@ int parse(int argc, char** argv, Args& a) {
       usage(argv[0], fl);
       return 2;
     }
+    if (name == "adaptive") a.adaptive_set = true;
+  }
+  if (a.adaptive_set && !(a.adaptive > 0.0)) {
+    fprintf(stderr, "invalid value for flag -adaptive: the error threshold must be > 0\n");
+    usage(argv[0], fl);
+    return 2;
+  }
+  if (!a.counts.empty() && !a.adaptive_set) {
+    fprintf(stderr, "-counts needs -adaptive\n");
+    usage(argv[0], fl);
+    return 2;
   }
   return -1;
 }
@@ -211,19 +232,24 @@ int fail(const char* what, int rc) {
 
 std::string stats_json(const rt_stats& st, const rt_camera_derived& d, const char* scene,
                        double wall_s, int aov_samples, double ms_aov, double ms_denoise,
-                       const rt_accum_info* acc, double ms_accum, bool denoise_var) {
-  char b[1024], extra[200] = "";
+                       const rt_accum_info* acc, double ms_accum, bool denoise_var,
+                       const rt_adapt_info* ad = nullptr) {
+  char b[1280], extra[200] = "", extra2[200] = "";
   if (acc)  // -passes / -until
     snprintf(extra, sizeof extra, "\"passes\": %d, \"rel_error\": %.6g, \"ms_accum\": %.3f, %s", acc->passes,
              acc->rel_error, ms_accum, denoise_var ? "\"denoise_var\": 1, " : "");
+  if (acc && ad)  // -adaptive
+    snprintf(extra2, sizeof extra2, "\"active_last\": %" PRIu64 ", \"samples_total\": %" PRIu64
+             ", \"samples_full\": %" PRIu64 ", ", ad->active_pixels, ad->total_samples,
+             (uint64_t)acc->passes * (uint64_t)(d.spp_sqrt * d.spp_sqrt) * (uint64_t)d.width * (uint64_t)d.height);
   snprintf(b, sizeof b,
            "{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"spp\": %d, \"max_depth\": %d, "
            "\"samples\": %" PRIu64 ", \"segments\": %" PRIu64 ", \"ms_render\": %.3f, "
            "\"samples_per_s\": %.6g, \"mode\": %d, \"tree_width\": %d, \"chunk_samples\": %d, "
-           "\"aov_samples\": %d, \"ms_aov\": %.3f, \"ms_denoise\": %.3f, %s\"wall_s\": %.3f}",
+           "\"aov_samples\": %d, \"ms_aov\": %.3f, \"ms_denoise\": %.3f, %s%s\"wall_s\": %.3f}",
            scene, d.width, d.height, d.spp_sqrt * d.spp_sqrt, d.max_depth, st.samples,
            st.segments, st.ms_total, st.ms_total > 0 ? st.samples / (st.ms_total * 1e-3) : 0.0,
-           st.mode, st.tree_width, st.chunk_samples, aov_samples, ms_aov, ms_denoise, extra, wall_s);
+           st.mode, st.tree_width, st.chunk_samples, aov_samples, ms_aov, ms_denoise, extra, extra2, wall_s);
   return b;
 }
 
@@ -247,8 +273,8 @@ int main(int argc, char** argv) {
   if (rc >= 0) return rc;
   auto t0 = std::chrono::steady_clock::now();
   // the variance comes from the passes: one pass has none (checked before the file is created)
-  if (a.denoise_var && !(a.passes >= 2 || (a.until > 0.0 && a.passes == 0))) {
-    fprintf(stderr, "-denoise-var needs -passes N with N >= 2, or -until\n");
+  if (a.denoise_var && !(a.passes >= 2 || ((a.until > 0.0 || a.adaptive_set) && a.passes == 0))) {
+    fprintf(stderr, "-denoise-var needs -passes N with N >= 2, or -until / -adaptive\n");
     usage(argv[0], flags(a));
     return 2;
   }
@@ -305,7 +331,7 @@ int main(int argc, char** argv) {
   memset(&st, 0, sizeof st);
 
   // -passes / -until: the image is the accumulator's mean over the passes
-  const bool accumulate = a.passes > 0 || a.until > 0.0;
+  const bool accumulate = a.passes > 0 || a.until > 0.0 || a.adaptive_set;
   if (a.passes < 0 || a.passes > 0x7FFFFFFF || !(a.until >= 0.0)) {
     fprintf(stderr, "invalid value for flag -passes / -until\n");
     fclose(out);
@@ -315,10 +341,16 @@ int main(int argc, char** argv) {
   rt_accum* acc = nullptr;
   rt_accum_info ai;
   memset(&ai, 0, sizeof ai);
+  rt_adapt_info adi;
+  memset(&adi, 0, sizeof adi);
+  rt_adapt_opts ado;
+  memset(&ado, 0, sizeof ado);  // the library defaults: tile 8, min_passes 4, lum_floor 1e-2
+  ado.rel_error = a.adaptive;
   double ms_accum = 0.0;
   if (accumulate && (rc = rt_accum_create(sc, &cam, &o, pass_cap, &acc)) != RT_OK)
     return fail("rt_accum_create", rc);
 
+  bool counts_failed = false;
   std::atomic<bool> rendering{true};
   std::atomic<int> pass_no{0};
   std::thread bar;
@@ -345,8 +377,16 @@ int main(int argc, char** argv) {
     for (int32_t p = 0; p < pass_cap && rc == RT_OK; ++p) {
       rt_stats sp;
       pass_no = p;
-      what = "rt_accum_add";
-      if ((rc = rt_accum_add(acc, a.seed + (uint64_t)p, &sp)) != RT_OK) break;
+      if (a.adaptive_set) {  // the noisy tiles only (Accumulator.render_adaptive); every tile at first
+        uint64_t n_active = 0;
+        what = "rt_accum_select";
+        if ((rc = rt_accum_select(acc, &ado, &n_active)) != RT_OK || n_active == 0) break;
+        what = "rt_accum_add_active";
+        if ((rc = rt_accum_add_active(acc, a.seed + (uint64_t)p, &sp)) != RT_OK) break;
+      } else {
+        what = "rt_accum_add";
+        if ((rc = rt_accum_add(acc, a.seed + (uint64_t)p, &sp)) != RT_OK) break;
+      }
       const uint64_t samples = st.samples + sp.samples, segments = st.segments + sp.segments;
       const double ms = st.ms_total + sp.ms_total;
       st = sp;  // the last pass's, with the totals over the passes
@@ -362,6 +402,21 @@ int main(int argc, char** argv) {
       what = "rt_accum_resolve";
       if ((rc = rt_accum_resolve(acc, rgb.data(), a.denoise_var ? var.data() : nullptr)) == RT_OK) rc = rt_accum_info_get(acc, &ai);
     }
+    if (rc == RT_OK && a.adaptive_set) {
+      what = "rt_accum_adapt_info";
+      rc = rt_accum_adapt_info(acc, &adi);
+      if (rc == RT_OK && !a.counts.empty()) {
+        const size_t np = (size_t)d.width * d.height;
+        std::vector<int32_t> cnt(np);
+        what = "rt_accum_counts";
+        if ((rc = rt_accum_counts(acc, cnt.data())) == RT_OK) {
+          std::vector<float> cimg(3 * np);
+          for (size_t i = 0; i < np; ++i)
+            cimg[3 * i] = cimg[3 * i + 1] = cimg[3 * i + 2] = adi.max_count > 0 ? (float)cnt[i] / (float)adi.max_count : 0.0f;
+          counts_failed = write_ppm(cimg, d.width, d.height, fopen(a.counts.c_str(), "wb"), a.counts.c_str()) != 0;
+        }
+      }
+    }
     ms_accum = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
   }
   rendering = false;
@@ -371,6 +426,11 @@ int main(int argc, char** argv) {
   else if (a.progress)
     fprintf(stderr, "\rrendering %s: 100.0%%\n", scene);
   if (rc != RT_OK) return fail(what, rc);
+  if (counts_failed) {  // (reported by write_ppm; after the progress thread has been joined)
+    rt_scene_destroy(sc);
+    rt_tree_destroy(tree);
+    return 1;
+  }
 
   // -denoise / -aov: the feature buffers of the same camera rays, then the filter
   int aov_samples = 0;
@@ -420,7 +480,7 @@ int main(int argc, char** argv) {
   if (write_ppm(rgb, d.width, d.height, out, a.out.c_str())) return 1;
   double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::string js = stats_json(st, d, scene, wall, aov_samples, ms_aov, ms_denoise, accumulate ? &ai : nullptr,
-                              ms_accum, a.denoise_var);
+                              ms_accum, a.denoise_var, a.adaptive_set ? &adi : nullptr);
   if (a.stats || a.denoise || a.denoise_var) fprintf(stderr, "%s\n", js.c_str());
   if (!a.cpuprofile.empty()) {
     FILE* p = fopen(a.cpuprofile.c_str(), "w");

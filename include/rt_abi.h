@@ -596,7 +596,7 @@ typedef struct rt_accum rt_accum;
  * stream and progress_slices of opts (NULL: the defaults) are fixed here; opts->seed is
  * ignored (every pass brings its own) and opts->trace_out must be NULL.  max_passes: the most
  * passes it will take, 0 = 1024; negative, or spp_sqrt^2 * max_passes >= 2^31, is
- * RT_ERR_INVALID.  Arguments are checked before any device is touched.  About 68 bytes of
+ * RT_ERR_INVALID.  Arguments are checked before any device is touched.  About 76 bytes of
  * device memory per pixel of the share (plus 16 for rt_accum_resolve's staging), allocated
  * here; no call below allocates.  The scene owns its accumulators: rt_scene_destroy frees
  * those still alive (their handles are dead after it), rt_accum_destroy frees one early.
@@ -636,6 +636,65 @@ typedef struct {
   double rms_std_error, mean_luminance, rel_error;
 } rt_accum_info;
 int rt_accum_info_get(rt_accum* a, rt_accum_info* out);
+
+/* Adaptive passes (DESIGN.md "Adaptive passes"): a pass over the noisy tiles only.  Added
+ * without an ABI version change: detect by the symbols.
+ *
+ * A tile is a tile x tile block of the share's local image (local row, column; edge tiles are
+ * smaller).  Over the pixels of tile T whose variance (as rt_accum_resolve's var) and mean
+ * luminance are finite, summed in a fixed order in fp64,
+ *   e_T = sqrt(mean var_p) / (max(mean mean_p, 0) + lum_floor),    0 without such a pixel,
+ * rounded to fp32.  T is active when some pixel of it has taken fewer than min_passes passes or
+ * e_T > rel_error; a pixel is active when its tile is.  lum_floor's default keeps dark tiles
+ * from dominating: a linear luminance of 1e-2 is 25/256 after the image writer's sqrt (a
+ * choice, not a measurement).  Selecting on the samples' own variance biases the estimate, as
+ * in every adaptive sampler; min_passes and tile-level decisions are the mitigation. */
+typedef struct {
+  double rel_error;    /* tile threshold; must be > 0 */
+  double lum_floor;    /* 0 -> 1e-2 */
+  int32_t tile;        /* 0 -> 8; 1..64 */
+  int32_t min_passes;  /* 0 -> 4; >= 2 */
+} rt_adapt_opts;
+
+/* The selection: the active pixels in ascending local index, built on the device by a
+ * deterministic compaction (the same state gives the same selection); their number comes back
+ * in *n_active_pixels (may be NULL).  rt_accum_select chooses by the tile rule above,
+ * rt_accum_set_active takes the caller's mask ([rows][W] bytes, nonzero = active).  The
+ * options and the mask pointer are checked before the accumulator and before any device is
+ * touched (RT_ERR_INVALID). */
+int rt_accum_select(rt_accum* a, const rt_adapt_opts* opts, uint64_t* n_active_pixels);
+int rt_accum_set_active(rt_accum* a, const uint8_t* mask_host, uint64_t* n_active_pixels);
+/* One pass over the current selection: every active pixel gets exactly the samples a whole
+ * pass of `seed` gives it (the random stream is keyed by seed, pixel and sample; the sums are
+ * integers), the others are left alone; stats->samples = active pixels * spp_sqrt^2.  It
+ * counts one pass against max_passes like rt_accum_add.  RT_ERR_INVALID when no selection was
+ * made since the last pass or reset: a selection is consumed by one pass.  An empty selection
+ * is a no-op that counts no pass; a selection of every pixel takes rt_accum_add's path.
+ * RT_ERR_UNSUPPORTED, with the state unchanged, for an accumulator of RT_MODE_WAVEFRONT and
+ * for a scene structure chosen by a tuning knob (RT_TREE=2, RT_BVH8) that has no active-pixel
+ * kernel.  (A scene whose whole passes traverse the BVH2 without RT_TREE asking for
+ * it traverses the BVH4 of the same leaf records in an active pass.)  An active pass never
+ * allocates: it writes chunk records when its chunks fit the buffer the whole passes left, and
+ * adds to the pixels with atomics otherwise (the same integers; stats->chunk_records = 0).  From the first such pass on, rt_accum_resolve divides every pixel's sums by the
+ * pixel's own pass count and var is M2 / ((n - 1) n) with it (a pixel that took every pass
+ * resolves to the same bits as before); rt_accum_info.passes counts the calls that rendered,
+ * samples_per_pixel is the most any pixel has.  rt_accum_reset returns to whole passes. */
+int rt_accum_add_active(rt_accum* a, uint64_t seed, rt_stats* stats);
+/* passes per pixel, [rows][W]; _device: a pointer on the accumulator's device */
+int rt_accum_counts(rt_accum* a, int32_t* counts_host);
+int rt_accum_counts_device(rt_accum* a, int32_t* counts_dev);
+/* e_T of every tile, [tiles_y][tiles_x], as rt_accum_select computes and compares it (opts'
+ * rel_error is checked, not used).  err_host NULL: the sizes only. */
+int rt_accum_tile_error(rt_accum* a, const rt_adapt_opts* opts, float* err_host, int32_t* tiles_x,
+                        int32_t* tiles_y);
+
+typedef struct {
+  uint64_t active_pixels;  /* of the last selection */
+  uint64_t total_samples;  /* spp_sqrt^2 * the sum of the pass counts */
+  int32_t min_count, max_count;
+  int32_t n_tiles, active_tiles;  /* of the last rt_accum_select (0 after rt_accum_set_active) */
+} rt_adapt_info;
+int rt_accum_adapt_info(rt_accum* a, rt_adapt_info* out);
 
 /* Demo scenes mirroring main.go (by name or the main.go -S number).
  * names: book1, book2, book3, simple_light, quads, cornell, cornell_smoke, model
