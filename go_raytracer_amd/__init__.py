@@ -472,6 +472,21 @@ class Scene:
         check(lib().rt_scene_plan_light(self._p, device, C.byref(k)))
         return k.value
 
+    def lean_emitter(self):
+        """The emitter slot of the scene's record layout (rt_scene_lean_emitter): the slot of
+        its one emissive record when the record-loop kernel may draw a vertex's numbers
+        before it resolves the winner, else -1.  No device needed."""
+        k = C.c_int32()
+        check(lib().rt_scene_lean_emitter(self._p, C.byref(k)))
+        return k.value
+
+    def plan_early(self, device=0):
+        """1 when a fused render of this scene on `device` launches the early-draw record-loop
+        kernel now (rt_scene_plan_early; honours RT_LEAN_EARLY_DRAW), else 0."""
+        k = C.c_int32()
+        check(lib().rt_scene_plan_early(self._p, device, C.byref(k)))
+        return k.value
+
     MODES = {"auto": 0, "wavefront": 1, "fused": 2}
 
     @staticmethod

@@ -225,6 +225,8 @@ SIGNATURES = {
     "rt_scene_export_prim_bounds": (_I, [_P, C.c_void_p, C.POINTER(C.c_int32)]),
     "rt_scene_lean_light": (_I, [_P, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32)]),
     "rt_scene_plan_light": (_I, [_P, _I, C.POINTER(C.c_int32)]),
+    "rt_scene_lean_emitter": (_I, [_P, C.POINTER(C.c_int32)]),
+    "rt_scene_plan_early": (_I, [_P, _I, C.POINTER(C.c_int32)]),
     "rt_render": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_void_p,
                        C.POINTER(RtStats)]),
     "rt_render_device": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_void_p,

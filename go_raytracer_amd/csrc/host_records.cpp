@@ -384,6 +384,41 @@ std::vector<F4> shade_table(const HostScene& h) {
   return tab;
 }
 
+// The lean kernel's early draw (rt_path.h shade_core<.., EARLY_SHAPE>) takes "the hit scatters" from
+// the winning slot alone: true for every winner but the emitter slot.  That is the shade
+// table's M.kind != RT_MAT_DIFFUSE_LIGHT exactly when the world has one emissive record, that
+// record is the one quad light of a lean light kind, and it is tested as an ordinary record
+// (a box code resolves to a face only after the draw, so no box face may be emissive).  Only
+// the listed layouts have such a kernel.  -1: the scene is outside this.
+int32_t emitter_slot_of(const HostScene& h, const SlotOrder& so, const std::vector<char>& in_box, int shape) {
+  if (shape == 0 || lean_light_of(h, nullptr) != 1) return -1;
+  auto mat_of = [](const F4* q) {
+    uint32_t mb;
+    memcpy(&mb, &q[2].w, 4);
+    return mb;
+  };
+  long rec = -1;
+  for (size_t i = 0; i < h.refs.size(); ++i) {
+    if ((h.refs[i] >> 30) != PRIM_QUAD) return -1;
+    const uint32_t mb = mat_of(&h.quad[5 * (size_t)(h.refs[i] & 0x3FFFFFFFu)]);
+    if (mb >= h.mats.size()) return -1;
+    if (h.mats[mb].kind != RT_MAT_DIFFUSE_LIGHT) continue;
+    if (rec >= 0) return -1;  // a second emissive record
+    rec = (long)i;
+  }
+  if (rec < 0 || in_box[(size_t)rec]) return -1;
+  // the lights list holds its own copy of the quad (host_flatten.cpp walk_lights): the same
+  // Q, u, v and material
+  const F4* wq = &h.quad[5 * (size_t)(h.refs[(size_t)rec] & 0x3FFFFFFFu)];
+  const F4* lq = &h.quad[5 * (size_t)(h.lights[0].ref & 0x3FFFFFFFu)];
+  for (int k = 0; k < 3; ++k)
+    if (!(wq[k].x == lq[k].x && wq[k].y == lq[k].y && wq[k].z == lq[k].z)) return -1;
+  if (mat_of(wq) != mat_of(lq)) return -1;
+  for (size_t k = 0; k < so.n_loop; ++k)
+    if (so.slots[k] == rec) return (int32_t)k;
+  return -1;
+}
+
 }  // namespace
 
 RecordPack pack_records(const HostScene& h) {
@@ -404,6 +439,7 @@ RecordPack pack_records(const HostScene& h) {
   out.n_slots = so.slots.size();
   out.n_boxes = (int32_t)boxes.size();
   out.shape = brute_shape_of(out.counts);
+  out.emitter_slot = emitter_slot_of(h, so, in_box, out.shape);
   const std::vector<F4> tab = shade_table(h);
   out.shade_n = (int32_t)tab.size();
   out.pairs.insert(out.pairs.end(), tab.begin(), tab.end());

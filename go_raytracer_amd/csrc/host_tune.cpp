@@ -55,6 +55,7 @@ constexpr Knob kKnobs[] = {
     {"RT_BRUTE_SMEM", false, 'i', -1, 1},      // 1: record loop through the scalar cache
     {"RT_BRUTE_SHAPE", false, 'i', 0, 1},      // 0: the generic record loop for listed layouts too
     {"RT_LEAN_LIGHT", false, 'i', 0, 1},       // 0: the general light code for lean light kinds too
+    {"RT_LEAN_EARLY_DRAW", false, 'i', 0, 1},  // 0: the lean light kernel that draws after the winner is resolved
     {"RT_QBVH", false, 'i', 0, 1},           // 0: 128-B BVH4 nodes instead of the compressed 64-B ones
     {"RT_CHUNK_NEED", false, 'i', 1, 1048576},      // chunks per lane that pick the chunk size
     {"RT_TAIL_FRAC", false, 'i', -1, 1024},       // tail phase: 1 / fraction of the samples
@@ -169,6 +170,12 @@ int rt_scene_lean_light(const rt_scene* sc, int32_t* kind, float* block, int32_t
   if (kind) *kind = k;
   if (n_floats) *n_floats = rt::kLeanLightFloats;
   if (block) memcpy(block, b.f, sizeof b.f);
+  return RT_OK;
+}
+
+int rt_scene_lean_emitter(const rt_scene* sc, int32_t* slot) {
+  if (!sc) return rt::set_error(RT_ERR_INVALID, "rt_scene_lean_emitter: null");
+  if (slot) *slot = rt::pack_records(sc->s.h).emitter_slot;
   return RT_OK;
 }
 

@@ -250,6 +250,11 @@ inline constexpr int lean_light_axis(int kind) { return kind == 1 ? 1 : -1; }
 //  (the pdf's quad test, rt_path.h lean_light_pdf: the light's leaf record with the plane
 //   offset in the record loop's axis form)
 //  f[12..14] u | 0   f[16..18] v | 0                   (quad.Random: Q + u s0 + v s1)
+//  f[11], written as 0 above: 0 in the matcher's block (lean_light_of, rt_scene_lean_light);
+//  a launch of the early-draw kernel (k_fused<.., EARLY>) carries the emitter slot's bits
+//  there (a uint32: the record loop's bk of the scene's one emissive record,
+//  host_records.cpp emitter_slot_of), set by render_impl in its copy of the block and read by
+//  shade_core<.., EARLY_SHAPE> alone -- the light code never reads the word
 constexpr int kLeanLightFloats = 20;
 struct alignas(16) LeanLight {
   float f[kLeanLightFloats];

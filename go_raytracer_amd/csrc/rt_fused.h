@@ -22,14 +22,6 @@ RT_D bool stage_nodes(const Params& P, F4* lnodes, int W) {
   return recs;
 }
 
-RT_D void record_trace(const Params& P, const Path& s, const Hit& best) {
-  if (s.gpix == P.trace_gpix && s.s0 + s.j == P.trace_sample && (int)s.k < P.trace_cap) {
-    P.trace[3 * s.k + 0] = {s.o.x, s.o.y, s.o.z, s.time};
-    P.trace[3 * s.k + 1] = {s.d.x, s.d.y, s.d.z, (float)s.k};
-    P.trace[3 * s.k + 2] = {best.t, best.u, best.v, bitsf(best.ref)};
-  }
-}
-
 // media + debug trace on top of the world closest hit, camera.go:300
 template <uint32_t FT>
 RT_D void finish_hit(const Params& P, const Path& s, Hit& best) {
@@ -178,8 +170,12 @@ __shared__ unsigned long long g_dinfo[4][3];  // ... and then: samples left, bus
 // loop is compiled for (rt_device.h brute_shape), 0 = any.  LIGHT (the same kernels only): the
 // lean light kind the light sampling and light pdf are compiled for (rt_device.h), 0 = any list.
 // MAP: an active-pixel pass over the pixels listed in P.pixmap (chunk_ids; rt_fused_map.hip)
-template <bool LDS, uint32_t FT, int TREE, int SHAPE = 0, int LIGHT = 0, bool MAP = false>
+// EARLY (a listed SHAPE with a lean light kind only; pick_fused has it for shape 1): the vertex's
+// Philox draw is issued before the record loop's winner is resolved (rt_path.h shade_core);
+// P.ll.f[11] is the emitter slot (rt_device.h LeanLight)
+template <bool LDS, uint32_t FT, int TREE, int SHAPE = 0, int LIGHT = 0, bool MAP = false, bool EARLY = false>
 __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) {
+  static_assert(!EARLY || (SHAPE != 0 && LIGHT != 0 && !MAP), "early draw: a listed shape with a lean light kind");
   static_assert(SHAPE == 0 || (LDS && FT == 0u && TREE == 0), "shapes: the lean LDS record loop only");
   static_assert(LIGHT == 0 || (LDS && FT == 0u && TREE == 0), "light kinds: the lean LDS record loop only");
   static_assert(LIGHT >= 0 && LIGHT < kLeanLightCount, "light kinds: unlisted kind");
@@ -287,7 +283,7 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
       PH_CNT(PH_TRAV_LANES, __popcll(__ballot(1)));
       PH_CNT(PH_TRAV_ROUNDS, 1);
       if constexpr (TREE == 0)
-        trav_brute<FT, !LDS, SHAPE>(P.sc, lnodes, s.o, s.d, s.time, 0.001f, tr);
+        trav_brute<FT, !LDS, SHAPE, EARLY>(P.sc, lnodes, s.o, s.d, s.time, 0.001f, tr);
       else if constexpr (TREE == 8)
       {
         const int nsteps = trav_steps8<FT>(P.sc, ts, s.o, s.d, s.time, 0.001f, tr, P.step_budget);
@@ -322,13 +318,13 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
         PH_CNT(PH_SHADE_ROUNDS, 1);
         PH_T(t_media);
         Hit best = tr.best;
-        finish_hit<FT>(P, s, best);
+        if constexpr (!EARLY) finish_hit<FT>(P, s, best);  // (EARLY: the trace is shade_core's)
         PH_ADD(PH_MEDIA, t_media);
 #ifndef RT_WAVE_SEGS
         ++s.segs;
 #endif
         PH_T(t_shade);
-        if (shade_core<false, FT, LIGHT>(P, slot, s, best, ws, sa) == OUT_NEED_CHUNK) has = false;
+        if (shade_core<false, FT, LIGHT, EARLY ? SHAPE : 0>(P, slot, s, best, ws, sa, lnodes) == OUT_NEED_CHUNK) has = false;
         else {
           trav_init<FT>(P.sc, s.o, s.d, s.time, tr);
 #ifdef RT_QROOT  // (opt-in: +2-4 % on C3-C5)

@@ -170,6 +170,9 @@ struct RecordPack {
   int32_t n_boxes = 0;    // boxes among the records tested as slabs (rt_path.h brute_box)
   BruteCounts counts{};   // the layout's group counts (DevScene brute_*)
   int shape = 0;          // brute_shape_of(counts)
+  int32_t emitter_slot = -1;  // the slot (the loop's bk) of the scene's one emissive record when
+                              // "winner != this slot" is "the hit scatters" (host_records.cpp
+                              // emitter_slot_of: a listed shape, lean light kind 1), else -1
 };
 RecordPack pack_records(const HostScene& h);
 // host_records.cpp: DevScene::merge_ok before the render's background is looked at (every

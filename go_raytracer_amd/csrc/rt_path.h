@@ -1328,7 +1328,10 @@ RT_D uint32_t box_face(const DevScene& sc, const F4* lrec, uint32_t code, f3 o, 
 // pairs' loads and tests are one straight block that the scheduler interleaves ahead of
 // the ordered best / bk selects.  Same operations on the same operands in the same record
 // order either way: the same hits bit for bit.
-template <uint32_t FT, bool SMEM, int SHAPE = 0>
+// EARLY (a listed SHAPE in LDS only): the loop's winning t and bk are handed back as they are,
+// tr.best = {t, -, -, bk}, and the caller resolves the winner (brute_resolve_early) beside its
+// Philox draw.
+template <uint32_t FT, bool SMEM, int SHAPE = 0, bool EARLY = false>
 RT_D void trav_brute(const DevScene& sc, const F4* lrec, f3 o, f3 d, float time, float tmin,
                      Trav& tr) {
   static_assert(!HAS(FT_SPHERE | FT_TRI), "record loop: quad-only feature sets");
@@ -1386,6 +1389,13 @@ RT_D void trav_brute(const DevScene& sc, const F4* lrec, f3 o, f3 d, float time,
   const int qb = qm + (mx != 0 ? 1 : 0);
   const float iy = rcp(d.y);
   brute_box<SMEM>(sc, lrec, qb, qb + (SHAPE == 0 ? kp->sc.brute_box : bc.box), O, Dv, iy, tmin, best, bk);
+  if constexpr (EARLY) {
+    static_assert(SHAPE != 0 && !SMEM, "early draw: the listed shapes in LDS only");
+    tr.best.t = best;  // (no winner: the t it came with)
+    tr.best.ref = bk;
+    tr.cur = TRAV_DONE;
+    return;
+  }
   if (bk != 0xFFFFFFFFu) {
     if (bk & kBoxCode) bk = box_face<SMEM>(sc, lrec, bk, o, d, iy, best);
     // the winner's fields (pair bk/2, half bk&1): Q at floats 8/10/12, A at
@@ -1411,6 +1421,40 @@ RT_D void trav_brute(const DevScene& sc, const F4* lrec, f3 o, f3 d, float time,
     tr.best.ref = __float_as_uint(f[9]);
   }
   tr.cur = TRAV_DONE;
+}
+// The winner of trav_brute<.., EARLY> resolved to its slot and ref without a branch: every
+// lane reads, so the loads are one straight block that the scheduler can start ahead of the
+// caller's Philox rounds.  A lane whose winner is no box reads the first box pair's half 0 (a
+// valid address) and drops the face by a mask select; a lane without a winner reads slot 0 and
+// the caller drops its ref.  For the lanes that keep them: trav_brute's operations on the same
+// operands.  ref_raw is some quad's ref on every lane (a row of the shade table).
+template <int SHAPE>
+RT_D uint32_t brute_resolve_early(const DevScene& sc, const F4* lrec, uint32_t bk, f3 o, f3 d,
+                                  float best, uint32_t& ref_raw) {
+  constexpr BruteCounts bc = brute_shape(SHAPE);
+  const uint32_t none = (uint32_t)((int32_t)bk >> 31);  // all ones: no winner (slots and box codes: bit 31 clear)
+  uint32_t slot = and_not(bk, none);
+  if constexpr (bc.box > 0) {
+    constexpr uint32_t qb = (uint32_t)(bc.ng + bc.vy + bc.ax[0] + bc.ax[1] + bc.ax[2] + (bc.mx != 0 ? 1 : 0));
+    const uint32_t box = and_not((uint32_t)((int32_t)(bk << 1) >> 31), none);  // all ones: a box code
+    const uint32_t code = pick_by(kBoxCode | (qb << 2), bk, box);
+    slot = pick_by(slot, box_face<false>(sc, lrec, code, o, d, rcp(d.y), best), box);
+  }
+  ref_raw = ((const lds_u32*)lrec)[32u * (slot >> 1) + (slot & 1u) + 28u];
+  return slot;
+}
+// quad.Hit's alpha and beta of the winner in `slot` (trav_brute's resolve): the early-draw
+// kernel needs them for the debug trace only
+RT_D void brute_slot_uv(const F4* lrec, uint32_t slot, f3 o, f3 d, float best, float& u, float& v) {
+  const lds_f32* l = (const lds_f32*)lrec + 32u * (slot >> 1) + (slot & 1u) + 8;
+  float f[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) f[e] = l[2 * e];
+  const float px = fmaf(d.x, best, o.x) - f[0];
+  const float py = fmaf(d.y, best, o.y) - f[1];
+  const float pz = fmaf(d.z, best, o.z) - f[2];
+  u = fmaf(pz, f[5], fmaf(py, f[4], px * f[3]));
+  v = fmaf(pz, f[8], fmaf(py, f[7], px * f[6]));
 }
 
 // the whole traversal at once (wavefront extend kernel)
@@ -2144,17 +2188,55 @@ RT_D void start_sample(const Params& P, uint32_t slot, Path& s, uint32_t chunk, 
   store_ray<SOA>(P, slot, s);
 }
 
+// debug path trace (Params::trace): one world.Hit of the traced sample
+RT_D void record_trace(const Params& P, const Path& s, const Hit& best) {
+  if (s.gpix == P.trace_gpix && s.s0 + s.j == P.trace_sample && (int)s.k < P.trace_cap) {
+    P.trace[3 * s.k + 0] = {s.o.x, s.o.y, s.o.z, s.time};
+    P.trace[3 * s.k + 1] = {s.d.x, s.d.y, s.d.z, (float)s.k};
+    P.trace[3 * s.k + 2] = {best.t, best.u, best.v, bitsf(best.ref)};
+  }
+}
+
 // One vertex of rayColor (camera.go:293-331) given its closest hit.
 // Returns OUT_ALIVE (continue with s.o/s.d), or OUT_NEED_CHUNK (chunk flushed).
 // LIGHT: the lean light kind the light sampling and light pdf are compiled for (rt_device.h;
 // the lean LDS record-loop kernel only, k_fused), 0 = any light list
-template <bool SOA, uint32_t FT, int LIGHT = 0>
+// EARLY_SHAPE (that kernel with a lean light kind only: the listed record layout the
+// early-draw variant is compiled for, k_fused's SHAPE; 0 = no early draw): h is
+// trav_brute<.., EARLY>'s {t, -, -, bk}, the winner still unresolved.  "The hit
+// scatters" is then known from bk alone -- a winner that is not the emitter slot, by the host
+// matcher (host_records.cpp emitter_slot_of) the shade table's M.kind != RT_MAT_DIFFUSE_LIGHT --
+// so the vertex's Philox call is issued first and the winner's dependent LDS reads (box
+// fields, face slot, ref, shade table; all unconditional, lrec = the records in LDS) follow
+// in the same block, for the scheduler to start them ahead of the ten Philox rounds.  The
+// same draws and the same hit as resolving first.
+template <bool SOA, uint32_t FT, int LIGHT = 0, int EARLY_SHAPE = 0>
 RT_D int shade_core(const Params& P, uint32_t slot, Path& s, const Hit& h, const WStack& ws,
-                    const SampleAcc& sa) {
+                    const SampleAcc& sa, const F4* lrec = nullptr) {
+  static_assert(EARLY_SHAPE == 0 || (FT == 0u && LIGHT != 0 && !SOA), "early draw: the lean light kernels only");
   const DevScene& sc = P.sc;
   const f3 o = s.o, d = s.d;
   const float time = s.time;
-  const uint32_t ref = h.ref;
+  rt_u32x4 r;
+  bool scat = false;
+  uint32_t ref = h.ref;
+  F4 etab_a = {0, 0, 0, 0}, etab_b = {0, 0, 0, 0};  // early draw: the winner's shade-table rows
+  if constexpr (EARLY_SHAPE != 0) {
+    const uint32_t bk = h.ref;
+    scat = bk != 0xFFFFFFFFu && bk != fbits(kparams()->ll.f[11]);
+    r = rt_rng_draw(P.seed, s.gpix, s.s0 + s.j + (scat ? 0u : 1u),
+                    scat ? RT_STREAM(s.k, 0) : RT_STREAM_CAMERA);
+    uint32_t ref_raw;
+    const uint32_t wslot = brute_resolve_early<EARLY_SHAPE>(sc, lrec, bk, o, d, h.t, ref_raw);
+    const F4* tab = g_dyn_lds + sc.shade_lds + 2 * (ref_raw & 0x3FFFFFFFu);
+    etab_a = ld_lds(tab), etab_b = ld_lds(tab + 1);
+    ref = bk != 0xFFFFFFFFu ? ref_raw : PRIM_NONE;
+    if (P.trace) {  // debug trace (finish_hit): the hit as trav_brute resolves it
+      Hit th = {h.t, h.u, h.v, ref};
+      if (ref != PRIM_NONE) brute_slot_uv(lrec, wslot, o, d, h.t, th.u, th.v);
+      record_trace(P, s, th);
+    }
+  }
   f3 lterm = mk3(0, 0, 0);
   bool term = false;
   rt_u32x4 rcam;  // camera draw of the next sample, when this vertex made it
@@ -2163,7 +2245,6 @@ RT_D int shade_core(const Params& P, uint32_t slot, Path& s, const Hit& h, const
   float u = h.u, v = h.v;
   bool ff = true;
   DevMaterial M;
-  bool scat = false;
   // lean record-loop kernel: the quad's normal, material kind and solid colour from the
   // shade table in LDS (rt_render.hip), no global loads
   bool ltab = false;
@@ -2219,9 +2300,9 @@ RT_D int shade_core(const Params& P, uint32_t slot, Path& s, const Hit& h, const
         u = phi * (0.5f * kInvPi);
         v = theta * kInvPi;
       }
-    } else if (FT == 0u && sc.shade_lds >= 0) {
+    } else if (FT == 0u && (EARLY_SHAPE != 0 || sc.shade_lds >= 0)) {
       const F4* tab = g_dyn_lds + sc.shade_lds + 2 * idx;
-      const F4 a = ld_lds(tab), b = ld_lds(tab + 1);
+      const F4 a = EARLY_SHAPE != 0 ? etab_a : ld_lds(tab), b = EARLY_SHAPE != 0 ? etab_b : ld_lds(tab + 1);
       lcol = xyz(b);
       nout = xyz(a);
 #ifndef RT_NO_LEAN_SNAP  // (A/B builds: the record-loop kernel without the projection)
@@ -2273,7 +2354,7 @@ RT_D int shade_core(const Params& P, uint32_t slot, Path& s, const Hit& h, const
       M.kind = mat;
     else
       M = sc.mats[mat];
-    scat = M.kind != RT_MAT_DIFFUSE_LIGHT;
+    if constexpr (EARLY_SHAPE == 0) scat = M.kind != RT_MAT_DIFFUSE_LIGHT;  // (early draw: the same, from bk)
   }
   // ONE Philox call per vertex for the whole wave: a scattering vertex draws its
   // own numbers; a path ending here (miss or light) draws the camera numbers of
@@ -2281,8 +2362,8 @@ RT_D int shade_core(const Params& P, uint32_t slot, Path& s, const Hit& h, const
   // C2 +3 %, C3 +2 %.  The all-features kernel (3 waves/SIMD, register-bound)
   // keeps the two draws in their branches (merged there: C4 -3 %).
   constexpr bool kMergeDraws = FT != FT_ALL;
-  rt_u32x4 r;
-  if (kMergeDraws)
+  static_assert(EARLY_SHAPE == 0 || kMergeDraws, "early draw: the vertex's one merged draw");
+  if (kMergeDraws && EARLY_SHAPE == 0)
     r = rt_rng_draw(P.seed, s.gpix, s.s0 + s.j + (scat ? 0u : 1u),
                     scat ? RT_STREAM(s.k, 0) : RT_STREAM_CAMERA);
   if (!scat) {

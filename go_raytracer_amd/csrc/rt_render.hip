@@ -185,6 +185,7 @@ struct DeviceScene {
   int brute_shape = 0;              // the listed layout the pair counts equal (rt_device.h), 0 = none
   int lean_light = 0;               // the light list's lean kind (rt_device.h), 0 = the general code
   LeanLight light_block{};          // ... and its light as the kernel of that kind reads it
+  int32_t emitter_slot = -1;        // the early-draw kernel's emitter slot (host_records.cpp), -1 = none
   uint32_t root2 = PRIM_NONE;
   int32_t n_nodes2 = 0;
   const F4* qnodes = nullptr;       // compressed BVH4 (host_qbvh.cpp): 64-B items, root item 0
@@ -405,6 +406,7 @@ static int upload_scene(const Scene* s, DeviceScene* ds) {
     ds->shade_n = rp.shade_n;
     ds->brute_boxes = rp.n_boxes;
     ds->brute_shape = rp.shape;
+    ds->emitter_slot = rp.emitter_slot;
     if ((rc = upload(ds, rp.pairs, &ds->brute_pairs)) != RT_OK) return rc;
   }
   UP(h.media, media);
@@ -581,15 +583,22 @@ static uint32_t pick_set(uint32_t feats) { return pick_ft_set(feats); }
 // (shape: the lean LDS record loop compiled for a listed record layout, rt_device.h brute_shape)
 // (light: the lean LDS record loop's light code compiled for a lean light kind, rt_device.h; the
 // listed shapes have such kernels, the generic loop does not: nullptr, the caller takes kind 0)
-static const void* pick_fused(bool lds, uint32_t set, int tree, int shape = 0, int light = 0) {
+// (early: the lean light kind's kernel that draws a vertex's numbers before it resolves the
+// winner, rt_path.h shade_core<.., EARLY_SHAPE>; shape 1 with light kind 1 only)
+static const void* pick_fused(bool lds, uint32_t set, int tree, int shape = 0, int light = 0,
+                              bool early = false) {
   static_assert(kBruteShapeCount == 3, "pick_fused: one kernel per listed shape");
   static_assert(kLeanLightCount == 2, "pick_fused: one kernel per listed shape and light kind");
   if (light != 0) {
     if (!(tree == 0 && lds && set == kFtSets[0] && light == 1)) return nullptr;
-    if (shape == 1) return (const void*)k_fused<true, kFtSets[0], 0, 1, 1>;
-    if (shape == 2) return (const void*)k_fused<true, kFtSets[0], 0, 2, 1>;
+    if (shape == 1) return early ? (const void*)k_fused<true, kFtSets[0], 0, 1, 1, false, true>
+                                 : (const void*)k_fused<true, kFtSets[0], 0, 1, 1>;
+    // (shape 2 has no early-draw kernel: it compiled to 9 SGPR spills against the 8 of the
+    // kernel below and was not measured)
+    if (shape == 2) return early ? nullptr : (const void*)k_fused<true, kFtSets[0], 0, 2, 1>;
     return nullptr;
   }
+  if (early) return nullptr;
   if (tree == 0 && lds && set == kFtSets[0] && shape == 1) return (const void*)k_fused<true, kFtSets[0], 0, 1>;
   if (tree == 0 && lds && set == kFtSets[0] && shape == 2) return (const void*)k_fused<true, kFtSets[0], 0, 2>;
   if (tree == 0 && lds && set == kFtSets[0]) return (const void*)k_fused<true, kFtSets[0], 0>;
@@ -711,6 +720,7 @@ struct StructurePlan {
   bool shade_tab;    // the lean kernel's shade table goes with the record pairs
   int shape;         // the record layout the kernel is compiled for (rt_device.h brute_shape), 0 = any
   int light;         // the lean light kind its light code is compiled for (rt_device.h), 0 = any list
+  bool early;        // ... and that kernel's early-draw variant (the scene has an emitter slot)
   const void* kernel;
   size_t lds_bytes;  // dynamic LDS of the kernel
   bool wants_qbvh;   // a BVH4 read through L1/L2 whose set has a compressed-BVH4 kernel
@@ -776,7 +786,13 @@ static int plan_structure(const Scene* s, const DeviceScene* ds, uint32_t ft_set
   int light = tree == 0 && f_lds && ft_set == kFtSets[0] && env_int("RT_LEAN_LIGHT", 1) != 0
                   ? ds->lean_light : 0;
   if (light != 0 && !pick_fused(f_lds, ft_set, tree, brute_shape_id, light)) light = 0;
-  const void* fused_kernel = pick_fused(f_lds, ft_set, tree, brute_shape_id, light);
+  // ... and, for a scene with an emitter slot (fixed at upload) whose shade table is staged, the
+  // variant of that kernel that draws each vertex's numbers before it resolves the winner.
+  // RT_LEAN_EARLY_DRAW=0: the kernel that draws after (A/B; the same image bit for bit).
+  const bool early = light != 0 && ds->emitter_slot >= 0 && shade_tab && f_recs &&
+                     env_int("RT_LEAN_EARLY_DRAW", 1) != 0 &&
+                     pick_fused(f_lds, ft_set, tree, brute_shape_id, light, true) != nullptr;
+  const void* fused_kernel = pick_fused(f_lds, ft_set, tree, brute_shape_id, light, early);
   if (!fused_kernel) return set_error(RT_ERR_UNSUPPORTED, "internal: no fused kernel for this scene");
   const size_t fused_lds = f_lds ? 64 * (node_slots * n_nodes + (f_recs ? rec_slots : 0)) : 0;
   out->tree = tree;
@@ -785,6 +801,7 @@ static int plan_structure(const Scene* s, const DeviceScene* ds, uint32_t ft_set
   out->shade_tab = shade_tab;
   out->shape = brute_shape_id;
   out->light = light;
+  out->early = early;
   out->kernel = fused_kernel;
   out->lds_bytes = fused_lds;
   return RT_OK;
@@ -1285,10 +1302,12 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   if (sp.light != 0 && !((float)cd.background[0] >= 0.0f && (float)cd.background[1] >= 0.0f &&
                          (float)cd.background[2] >= 0.0f)) {
     sp.light = 0;
+    sp.early = false;
     sp.kernel = pick_fused(sp.f_lds, ft_set, sp.tree, sp.shape, 0);
   }
   if (map) {  // the structure's MAP twin; the record loop's is the generic one (the same bits)
     sp.shape = sp.light = 0;
+    sp.early = false;
     sp.kernel = pick_fused_map(sp.f_lds, ft_set, sp.tree);
     if (!sp.kernel)
       return set_error(RT_ERR_UNSUPPORTED, "an active-pixel pass has no kernel for tree %d, chosen by RT_TREE / RT_BVH8", sp.tree);
@@ -1342,6 +1361,10 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   if (sp.light != 0) {
     if (!p.sc.merge_ok) return set_error(RT_ERR_UNSUPPORTED, "internal: lean light kernel without merge_ok");
     p.ll = ds->light_block;
+    if (sp.early) {  // the emitter slot in the block's first spare word (rt_device.h LeanLight)
+      const uint32_t es = (uint32_t)ds->emitter_slot;
+      memcpy(&p.ll.f[11], &es, 4);
+    }
   }
   p.pixmap = map ? map->pixels : nullptr;
   p.K = cp.K;
@@ -1753,6 +1776,20 @@ int rt_scene_plan_light(rt_scene* sc, int device, int32_t* kind) {
   rt::StructurePlan sp;
   if ((rc = rt::plan_structure(&sc->s, ds, rt::scene_ft_set(&sc->s), RT_MODE_FUSED, &sp))) return rc;
   *kind = sp.light;
+  return RT_OK;
+}
+
+int rt_scene_plan_early(rt_scene* sc, int device, int32_t* early) {
+  if (!sc || !early) return rt::set_error(RT_ERR_INVALID, "rt_scene_plan_early: null");
+  int rc = rt::device_ok("rt_scene_plan_early", device);
+  if (rc) return rc;
+  rt::DeviceGuard dg;
+  if (hipSetDevice(device) != hipSuccess) return rt::set_error(RT_ERR_DEVICE, "rt_scene_plan_early");
+  rt::DeviceScene* ds = nullptr;
+  if ((rc = rt::ensure_scene(&sc->s, device, &ds))) return rc;
+  rt::StructurePlan sp;
+  if ((rc = rt::plan_structure(&sc->s, ds, rt::scene_ft_set(&sc->s), RT_MODE_FUSED, &sp))) return rc;
+  *early = sp.early ? 1 : 0;
   return RT_OK;
 }
 

@@ -356,6 +356,19 @@ int rt_scene_lean_light(const rt_scene* s, int32_t* kind, float* block, int32_t*
  * takes the scene and RT_LEAN_LIGHT is not 0, else 0.  A render whose background has a
  * negative channel takes kind 0 whatever this returns. */
 int rt_scene_plan_light(rt_scene* s, int device, int32_t* kind);
+/* the emitter slot of the scene's record layout (host code only, no device): the position, in
+ * the slot order of rt_scene_export_records' pair array (2 * pair + half), of the scene's one
+ * emissive record, when the record-loop kernel may take "the hit scatters" from the winning
+ * slot alone and so draw a vertex's random numbers before the winner is resolved -- a listed
+ * layout (rt_brute_shape 1 or 2), lean light kind 1, exactly one emissive quad in the world,
+ * which is the light list's quad and not a face of a box tested as slabs.  -1 otherwise. */
+int rt_scene_lean_emitter(const rt_scene* s, int32_t* slot);
+/* 1 when a fused render of the scene on `device` launches the early-draw record-loop kernel
+ * now (uploads the scene there on first use): the lean light kind's kernel is taken
+ * (rt_scene_plan_light), the scene has an emitter slot, its layout is rt_brute_shape 1 (the
+ * one layout with such a kernel) and RT_LEAN_EARLY_DRAW is not 0; else 0.  A render whose background has a negative channel takes the general kernel whatever
+ * this returns. */
+int rt_scene_plan_early(rt_scene* s, int device, int32_t* early);
 
 enum {
   RT_FLAG_PROFILE = 1,     /* time every kernel with HIP events */
