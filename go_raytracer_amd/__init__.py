@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (RT_FT_ALL, RT_FT_BOX, RT_NOISE_MARBLE, RT_NOISE_PERLIN,  # noqa: F401
-                   RT_NOISE_TURBULENT, RtAccumInfo, RtAov, RtCamera, RtDenoiseOpts,
+                   RT_NOISE_TURBULENT, RtAccumInfo, RtAov, RtAovEmit, RtCamera, RtDenoiseOpts,
                    RtDenoiseVarOpts, RtCameraDerived, RtError, RtRenderOpts, RtSceneInfo, RtStats, RtTreeView,
                    check, lib)
 
@@ -559,12 +559,16 @@ class Scene:
                                      C.byref(st)))
         return {f: getattr(st, f) for f, _ in RtStats._fields_}
 
-    def render_aov(self, camera, n_samples=1, seed=1, device=0, rank=0, nranks=1):
+    def render_aov(self, camera, n_samples=1, seed=1, device=0, rank=0, nranks=1, emit=False):
         """Feature buffers of this rank's rows (rt_render_aov): the first hit of the camera
         rays render() gives samples 0 .. n_samples-1 of every pixel, averaged.  Returns
         {"albedo": float32 [rows, W, 3], "normal": float32 [rows, W, 3] (world space, facing
         the ray, 0 on a miss), "depth": float32 [rows, W], "material": int32 [rows, W]
-        (RT_MAT_* of sample 0, -1 on a miss), "stats": dict}."""
+        (RT_MAT_* of sample 0, -1 on a miss), "stats": dict}.  emit=True (rt_render_aov_emit)
+        adds the emission split: "emission" float32 [rows, W, 3] (what directly seen lights add
+        to the pixel: their emission, which the render does not clamp), "surface_albedo" float32 [rows, W, 3]
+        (the albedo of the samples that see no light) and "coverage" float32 [rows, W] (the
+        fraction of samples that see a light's front face)."""
         d = camera.derived()
         rows = len(range(rank, d.height, nranks))
         res = {"albedo": np.zeros((rows, d.width, 3), np.float32),
@@ -575,21 +579,37 @@ class Scene:
         st = RtStats()
         c = camera.to_c()
         o = self._opts(seed, device, rank, nranks, 0, 0, False, None)
-        check(lib().rt_render_aov(self._p, C.byref(c), C.byref(o), n_samples, C.byref(a),
-                                  C.byref(st)))
+        if emit:
+            res["emission"] = np.zeros((rows, d.width, 3), np.float32)
+            res["surface_albedo"] = np.zeros((rows, d.width, 3), np.float32)
+            res["coverage"] = np.zeros((rows, d.width), np.float32)
+            e = RtAovEmit(*[res[k].ctypes.data for k in ("emission", "surface_albedo", "coverage")])
+            check(lib().rt_render_aov_emit(self._p, C.byref(c), C.byref(o), n_samples, C.byref(a),
+                                           C.byref(e), C.byref(st)))
+        else:
+            check(lib().rt_render_aov(self._p, C.byref(c), C.byref(o), n_samples, C.byref(a),
+                                      C.byref(st)))
         res["stats"] = {f: getattr(st, f) for f, _ in RtStats._fields_}
         return res
 
     def render_aov_device(self, camera, albedo=None, normal=None, depth=None, material=None,
-                          n_samples=1, seed=1, device=0, rank=0, nranks=1, stream=None):
+                          n_samples=1, seed=1, device=0, rank=0, nranks=1, stream=None,
+                          emission=None, surface_albedo=None, coverage=None):
         """rt_render_aov_device: the same buffers written to device pointers (e.g. torch
-        tensors' .data_ptr(); None = not wanted) on `stream`.  Returns the stats dict."""
+        tensors' .data_ptr(); None = not wanted) on `stream`.  With any of emission /
+        surface_albedo / coverage the call is rt_render_aov_emit_device.  Returns the stats
+        dict."""
         a = RtAov(albedo, normal, depth, material)
         st = RtStats()
         c = camera.to_c()
         o = self._opts(seed, device, rank, nranks, 0, 0, False, stream)
-        check(lib().rt_render_aov_device(self._p, C.byref(c), C.byref(o), n_samples, C.byref(a),
-                                         C.byref(st)))
+        if emission is not None or surface_albedo is not None or coverage is not None:
+            e = RtAovEmit(emission, surface_albedo, coverage)
+            check(lib().rt_render_aov_emit_device(self._p, C.byref(c), C.byref(o), n_samples,
+                                                  C.byref(a), C.byref(e), C.byref(st)))
+        else:
+            check(lib().rt_render_aov_device(self._p, C.byref(c), C.byref(o), n_samples, C.byref(a),
+                                             C.byref(st)))
         return {f: getattr(st, f) for f, _ in RtStats._fields_}
 
     def accumulator(self, camera, max_passes=0, device=0, rank=0, nranks=1, path_slots=0, chunk=0,
@@ -670,11 +690,12 @@ class Accumulator:
             self._h(), None if rgb_tensor is None else rgb_tensor.data_ptr(),
             None if var_tensor is None else var_tensor.data_ptr()))
 
-    def denoise_device(self, aov, out=None, var_out=None, **opts):
+    def denoise_device(self, aov, out=None, var_out=None, split_emitters=False, **opts):
         """The running mean through the variance-guided denoiser, all on the device: resolves
         into tensors the accumulator owns (allocated on first use, then reused) and runs
         denoise_var_device(mean, var, aov, out, var_out, **opts).  Returns `out` (a new tensor by
-        default).  Needs two passes: one pass has no variance."""
+        default).  Needs two passes: one pass has no variance.  split_emitters=True: the
+        emission split (aov from render_aov_device's emission / surface_albedo / coverage)."""
         import torch
         if self.passes < 2:
             raise ValueError("Accumulator.denoise_device: needs at least 2 passes (no variance yet)")
@@ -683,7 +704,8 @@ class Accumulator:
             self._mean = torch.empty(self.shape + (3,), dtype=torch.float32, device=dev)
             self._var = torch.empty(self.shape, dtype=torch.float32, device=dev)
         self.resolve_device(self._mean, self._var)
-        return denoise_var_device(self._mean, self._var, aov, out=out, var_out=var_out, **opts)
+        return denoise_var_device(self._mean, self._var, aov, out=out, var_out=var_out,
+                                  split_emitters=split_emitters, **opts)
 
     def info(self):
         """rt_accum_info as a dict: passes, max_passes, samples_per_pixel, nonfinite_pixels,
@@ -871,38 +893,86 @@ def _denoise_opts(iterations=0, demodulate=None, sigma_color=0.0, sigma_normal=0
     return o
 
 
-def denoise(rgb, aov=None, **opts):
+_EMIT_KEYS = (("emission", 3), ("surface_albedo", 3), ("coverage", 0))
+
+
+def _emit_host(who, aov, h, w):
+    """split_emitters on host arrays: (RtAovEmit, the arrays it points into)"""
+    keep = []
+    for k, ch in _EMIT_KEYS:
+        if (aov or {}).get(k) is None:
+            raise ValueError(f"{who}: split_emitters needs aov[{k!r}] (Scene.render_aov(emit=True))")
+        t = np.ascontiguousarray(aov[k], dtype=np.float32)
+        shape = (h, w, ch) if ch else (h, w)
+        if t.shape != shape:
+            raise ValueError(f"{who}: {k} must have shape {shape}, not {t.shape}")
+        keep.append(t)
+    return RtAovEmit(*[t.ctypes.data for t in keep]), keep
+
+
+def _emit_device(who, aov, a):
+    """split_emitters on device tensors: the checks denoise_var_device applies to var"""
+    import torch
+    h, w = a.shape[:2]
+    keep = []
+    for k, ch in _EMIT_KEYS:
+        t = (aov or {}).get(k)
+        if t is None:
+            raise ValueError(f"{who}: split_emitters needs aov[{k!r}] (render_aov_device's {k})")
+        shape = (h, w, ch) if ch else (h, w)
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous()
+                or tuple(t.shape) != shape or t.device != a.device):
+            raise ValueError(f"{who}: {k} must be a contiguous float32 tensor of shape {shape} "
+                             "on rgb's device")
+        keep.append(t)
+    return RtAovEmit(*[t.data_ptr() for t in keep]), keep
+
+
+def denoise(rgb, aov=None, split_emitters=False, **opts):
     """Edge-avoiding a-trous denoise (rt_denoise) of a host float32 [H, W, 3] image guided by
     `aov`, a dict as Scene.render_aov returns it (any of "albedo", "normal", "depth"; None or
     missing = that guide off).  opts: iterations (0 = 5), demodulate (default: on when an
     albedo is given), sigma_color / sigma_normal / sigma_depth (0 = the library defaults).
-    Returns a new float32 [H, W, 3] array."""
+    split_emitters=True (rt_denoise_emit): aov must also hold "emission", "surface_albedo" and
+    "coverage" (Scene.render_aov(emit=True)); the emission is kept out of the filter, which
+    demodulates by surface_albedo ("albedo" is not read).  Returns a new float32 [H, W, 3]
+    array."""
     a = np.ascontiguousarray(rgb, dtype=np.float32)
     h, w = a.shape[:2]
     aov = aov or {}
+    if split_emitters:
+        e, _keep = _emit_host("denoise", aov, h, w)
     keep = [None if aov.get(k) is None else np.ascontiguousarray(aov[k], dtype=np.float32)
             for k in ("albedo", "normal", "depth")]
     f = RtAov(*[None if k is None else k.ctypes.data for k in keep], None)
-    o = _denoise_opts(has_albedo=keep[0] is not None, **opts)
+    o = _denoise_opts(has_albedo=split_emitters or keep[0] is not None, **opts)
     out = np.empty_like(a)
-    check(lib().rt_denoise(a.ctypes.data, C.byref(f), w, h, C.byref(o), out.ctypes.data))
+    if split_emitters:
+        check(lib().rt_denoise_emit(a.ctypes.data, C.byref(f), C.byref(e), w, h, C.byref(o),
+                                    out.ctypes.data))
+    else:
+        check(lib().rt_denoise(a.ctypes.data, C.byref(f), w, h, C.byref(o), out.ctypes.data))
     return out
 
 
-def denoise_device(rgb, aov=None, out=None, **opts):
+def denoise_device(rgb, aov=None, out=None, split_emitters=False, **opts):
     """rt_denoise_device on device float32 torch tensors: rgb [H, W, 3], aov a dict of
     "albedo" [H, W, 3] / "normal" [H, W, 3] / "depth" [H, W] tensors on the same device.
-    `out` may be rgb itself (in place); by default a new tensor.  Runs on the tensor's
-    current stream and returns after the work completes."""
+    `out` may be rgb itself (in place); by default a new tensor.  split_emitters=True
+    (rt_denoise_emit_device): aov must also hold "emission" [H, W, 3], "surface_albedo"
+    [H, W, 3] and "coverage" [H, W] as contiguous float32 tensors on rgb's device.  Runs on the
+    tensor's current stream and returns after the work completes."""
     import torch
     a = rgb if (rgb.is_contiguous() and rgb.dtype == torch.float32) else \
         rgb.contiguous().to(torch.float32)
     h, w = a.shape[:2]
     aov = aov or {}
+    if split_emitters:
+        e, _keep = _emit_device("denoise_device", aov, a)
     keep = [None if aov.get(k) is None else aov[k].contiguous().to(torch.float32)
             for k in ("albedo", "normal", "depth")]
     f = RtAov(*[None if k is None else k.data_ptr() for k in keep], None)
-    o = _denoise_opts(has_albedo=keep[0] is not None, **opts)
+    o = _denoise_opts(has_albedo=split_emitters or keep[0] is not None, **opts)
     if out is None:
         out = torch.empty_like(a)
     elif (out.dtype != torch.float32 or not out.is_contiguous() or out.shape != a.shape
@@ -911,8 +981,12 @@ def denoise_device(rgb, aov=None, out=None, **opts):
                          "on rgb's device")
     elif out is rgb and a is not rgb:
         raise ValueError("denoise_device: in place needs a contiguous float32 rgb")
-    check(lib().rt_denoise_device(a.data_ptr(), C.byref(f), w, h, C.byref(o), out.data_ptr(),
-                                  a.device.index or 0, _stream_of(a)))
+    if split_emitters:
+        check(lib().rt_denoise_emit_device(a.data_ptr(), C.byref(f), C.byref(e), w, h, C.byref(o),
+                                           out.data_ptr(), a.device.index or 0, _stream_of(a)))
+    else:
+        check(lib().rt_denoise_device(a.data_ptr(), C.byref(f), w, h, C.byref(o), out.data_ptr(),
+                                      a.device.index or 0, _stream_of(a)))
     return out
 
 
@@ -925,13 +999,13 @@ def _denoise_var_opts(iterations=0, demodulate=None, sigma_lum=0.0, sigma_normal
     return o
 
 
-def denoise_var(rgb, var, aov=None, return_var=False, **opts):
+def denoise_var(rgb, var, aov=None, return_var=False, split_emitters=False, **opts):
     """Variance-guided a-trous denoise (rt_denoise_var) of a host float32 [H, W, 3] image and
     the variance [H, W] of its mean luminance, as Accumulator.resolve returns them, guided by
     `aov` as denoise is.  opts: iterations (0 = 5), demodulate (default: on when an albedo is
     given), sigma_lum (0 = 1.0) / sigma_normal / sigma_depth.  Returns a new float32
     [H, W, 3] array, or with return_var (out, var_out [H, W]: the variance of the filtered
-    image's luminance)."""
+    image's luminance).  split_emitters=True (rt_denoise_var_emit): as denoise's."""
     a = np.ascontiguousarray(rgb, dtype=np.float32)
     h, w = a.shape[:2]
     if var is None:
@@ -940,22 +1014,30 @@ def denoise_var(rgb, var, aov=None, return_var=False, **opts):
     if v.shape != (h, w):
         raise ValueError(f"denoise_var: var must have shape {(h, w)}, not {v.shape}")
     aov = aov or {}
+    if split_emitters:
+        e, _keep = _emit_host("denoise_var", aov, h, w)
     keep = [None if aov.get(k) is None else np.ascontiguousarray(aov[k], dtype=np.float32)
             for k in ("albedo", "normal", "depth")]
     f = RtAov(*[None if k is None else k.ctypes.data for k in keep], None)
-    o = _denoise_var_opts(has_albedo=keep[0] is not None, **opts)
+    o = _denoise_var_opts(has_albedo=split_emitters or keep[0] is not None, **opts)
     out = np.empty_like(a)
     vout = np.empty_like(v) if return_var else None
-    check(lib().rt_denoise_var(a.ctypes.data, v.ctypes.data, C.byref(f), w, h, C.byref(o),
-                               out.ctypes.data, None if vout is None else vout.ctypes.data))
+    if split_emitters:
+        check(lib().rt_denoise_var_emit(a.ctypes.data, v.ctypes.data, C.byref(f), C.byref(e), w, h,
+                                        C.byref(o), out.ctypes.data,
+                                        None if vout is None else vout.ctypes.data))
+    else:
+        check(lib().rt_denoise_var(a.ctypes.data, v.ctypes.data, C.byref(f), w, h, C.byref(o),
+                                   out.ctypes.data, None if vout is None else vout.ctypes.data))
     return (out, vout) if return_var else out
 
 
-def denoise_var_device(rgb, var, aov=None, out=None, var_out=None, **opts):
+def denoise_var_device(rgb, var, aov=None, out=None, var_out=None, split_emitters=False, **opts):
     """rt_denoise_var_device on device float32 torch tensors: rgb [H, W, 3], var [H, W]
     (contiguous float32 on rgb's device), aov as denoise_device's.  `out` may be rgb itself and
-    `var_out` (None: the filtered variance is not written) var itself.  Runs on the tensor's
-    current stream and returns `out` after the work completes."""
+    `var_out` (None: the filtered variance is not written) var itself.  split_emitters=True
+    (rt_denoise_var_emit_device): as denoise_device's.  Runs on the tensor's current stream and
+    returns `out` after the work completes."""
     import torch
     a = rgb if (rgb.is_contiguous() and rgb.dtype == torch.float32) else \
         rgb.contiguous().to(torch.float32)
@@ -968,10 +1050,12 @@ def denoise_var_device(rgb, var, aov=None, out=None, var_out=None, **opts):
             raise ValueError(f"denoise_var_device: {name} must be a contiguous float32 tensor of shape "
                              f"{(h, w)} on rgb's device")
     aov = aov or {}
+    if split_emitters:
+        e, _keep = _emit_device("denoise_var_device", aov, a)
     keep = [None if aov.get(k) is None else aov[k].contiguous().to(torch.float32)
             for k in ("albedo", "normal", "depth")]
     f = RtAov(*[None if k is None else k.data_ptr() for k in keep], None)
-    o = _denoise_var_opts(has_albedo=keep[0] is not None, **opts)
+    o = _denoise_var_opts(has_albedo=split_emitters or keep[0] is not None, **opts)
     if out is None:
         out = torch.empty_like(a)
     elif (out.dtype != torch.float32 or not out.is_contiguous() or out.shape != a.shape
@@ -980,9 +1064,14 @@ def denoise_var_device(rgb, var, aov=None, out=None, var_out=None, **opts):
                          "on rgb's device")
     elif out is rgb and a is not rgb:
         raise ValueError("denoise_var_device: in place needs a contiguous float32 rgb")
-    check(lib().rt_denoise_var_device(a.data_ptr(), var.data_ptr(), C.byref(f), w, h, C.byref(o),
-                                      out.data_ptr(), None if var_out is None else var_out.data_ptr(),
-                                      a.device.index or 0, _stream_of(a)))
+    if split_emitters:
+        check(lib().rt_denoise_var_emit_device(
+            a.data_ptr(), var.data_ptr(), C.byref(f), C.byref(e), w, h, C.byref(o), out.data_ptr(),
+            None if var_out is None else var_out.data_ptr(), a.device.index or 0, _stream_of(a)))
+    else:
+        check(lib().rt_denoise_var_device(a.data_ptr(), var.data_ptr(), C.byref(f), w, h, C.byref(o),
+                                          out.data_ptr(), None if var_out is None else var_out.data_ptr(),
+                                          a.device.index or 0, _stream_of(a)))
     return out
 
 

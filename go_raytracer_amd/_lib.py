@@ -99,6 +99,11 @@ class RtAov(C.Structure):  # rt_aov: feature buffers (any pointer may be NULL)
                 ("material", C.c_void_p)]
 
 
+class RtAovEmit(C.Structure):  # rt_aov_emit: the emission split (any pointer may be NULL)
+    _fields_ = [("emission", C.c_void_p), ("surface_albedo", C.c_void_p),
+                ("coverage", C.c_void_p)]
+
+
 class RtDenoiseOpts(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32),
                 ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
@@ -255,6 +260,21 @@ SIGNATURES = {
     "rt_denoise_var_device": (_I, [C.c_void_p, C.c_void_p, C.POINTER(RtAov), _I, _I,
                                    C.POINTER(RtDenoiseVarOpts), C.c_void_p, C.c_void_p, _I,
                                    C.c_void_p]),
+    "rt_render_aov_emit": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
+                                C.POINTER(RtAov), C.POINTER(RtAovEmit), C.POINTER(RtStats)]),
+    "rt_render_aov_emit_device": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
+                                       C.POINTER(RtAov), C.POINTER(RtAovEmit),
+                                       C.POINTER(RtStats)]),
+    "rt_denoise_emit": (_I, [C.c_void_p, C.POINTER(RtAov), C.POINTER(RtAovEmit), _I, _I,
+                             C.POINTER(RtDenoiseOpts), C.c_void_p]),
+    "rt_denoise_emit_device": (_I, [C.c_void_p, C.POINTER(RtAov), C.POINTER(RtAovEmit), _I, _I,
+                                    C.POINTER(RtDenoiseOpts), C.c_void_p, _I, C.c_void_p]),
+    "rt_denoise_var_emit": (_I, [C.c_void_p, C.c_void_p, C.POINTER(RtAov), C.POINTER(RtAovEmit),
+                                 _I, _I, C.POINTER(RtDenoiseVarOpts), C.c_void_p, C.c_void_p]),
+    "rt_denoise_var_emit_device": (_I, [C.c_void_p, C.c_void_p, C.POINTER(RtAov),
+                                        C.POINTER(RtAovEmit), _I, _I,
+                                        C.POINTER(RtDenoiseVarOpts), C.c_void_p, C.c_void_p, _I,
+                                        C.c_void_p]),
     "rt_accum_create": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
                              C.POINTER(_P)]),
     "rt_accum_destroy": (_I, [_P]),

@@ -367,6 +367,96 @@ __global__ __launch_bounds__(256) void k_dnv_atrous(DvParams P, const v4f* __res
   }
 }
 
+// ---- emission split (rt_denoise_emit, rt_denoise_var_emit) ------------------------------------
+//
+// The iteration kernels above run unchanged on records written by a prep of the split inputs:
+// c = (rgb - emission) / max(surface_albedo, 1e-3), and a pixel is also invalid when its
+// emission is not finite or its coverage is not below 1.  The final iteration multiplies the
+// surface albedo back and passes invalid pixels through; k_dn_emit_add then adds the emission
+// to the valid ones.  It takes the validity from the records (the guide record's w, or the
+// sign of the v the last iteration read), not from rgb, which an aliased out has overwritten.
+// One lane per pixel, coalesced: 16 B + 40 B read and 32 B written by the prep, 4 B + 24 B read
+// and 12 B written by the epilogue.
+
+__global__ __launch_bounds__(256) void k_dn_prep_emit(const float* __restrict__ rgb,
+                                                      const float* __restrict__ emission,
+                                                      const float* __restrict__ salbedo,
+                                                      const float* __restrict__ coverage,
+                                                      const float* __restrict__ normal,
+                                                      const float* __restrict__ depth, int64_t n,
+                                                      int demod, v4f* __restrict__ col,
+                                                      v4f* __restrict__ gd) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2];
+  const float e0 = emission[3 * i], e1 = emission[3 * i + 1], e2 = emission[3 * i + 2];
+  const bool valid = isfinite(r) && isfinite(g) && isfinite(b) && isfinite(e0) && isfinite(e1) &&
+                     isfinite(e2) && coverage[i] < 1.0f;
+  r -= e0;
+  g -= e1;
+  b -= e2;
+  if (demod) {
+    r = r / fmaxf(salbedo[3 * i], 1e-3f);
+    g = g / fmaxf(salbedo[3 * i + 1], 1e-3f);
+    b = b / fmaxf(salbedo[3 * i + 2], 1e-3f);
+  }
+  if (!valid) r = g = b = 0.0f;
+  const float d = depth ? depth[i] : 0.0f;
+  v4f nv = {0.0f, 0.0f, 0.0f, valid ? 1.0f : 0.0f};
+  if (normal) nv.x = normal[3 * i], nv.y = normal[3 * i + 1], nv.z = normal[3 * i + 2];
+  *(glb_v4*)(col + i) = v4f{r, g, b, d};
+  *(glb_v4*)(gd + i) = nv;
+}
+
+__global__ __launch_bounds__(256) void k_dnv_prep_emit(const float* __restrict__ rgb,
+                                                       const float* __restrict__ var,
+                                                       const float* __restrict__ emission,
+                                                       const float* __restrict__ salbedo,
+                                                       const float* __restrict__ coverage,
+                                                       const float* __restrict__ normal,
+                                                       const float* __restrict__ depth, int64_t n,
+                                                       int demod, v4f* __restrict__ col,
+                                                       v4f* __restrict__ gd) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2], v = var[i];
+  const float e0 = emission[3 * i], e1 = emission[3 * i + 1], e2 = emission[3 * i + 2];
+  const bool valid = isfinite(r) && isfinite(g) && isfinite(b) && isfinite(v) && isfinite(e0) &&
+                     isfinite(e1) && isfinite(e2) && coverage[i] < 1.0f;
+  r -= e0;
+  g -= e1;
+  b -= e2;
+  if (demod) {
+    const float a0 = fmaxf(salbedo[3 * i], 1e-3f), a1 = fmaxf(salbedo[3 * i + 1], 1e-3f),
+                a2 = fmaxf(salbedo[3 * i + 2], 1e-3f);
+    const float ya = lum(a0, a1, a2);
+    r = r / a0;
+    g = g / a1;
+    b = b / a2;
+    v = v / (ya * ya);
+  }
+  v = fmaxf(v, 0.0f);
+  if (!valid) r = g = b = 0.0f, v = -1.0f;
+  v4f nv = {0.0f, 0.0f, 0.0f, depth ? depth[i] : 0.0f};
+  if (normal) nv.x = normal[3 * i], nv.y = normal[3 * i + 1], nv.z = normal[3 * i + 2];
+  *(glb_v4*)(col + i) = v4f{r, g, b, v};
+  *(glb_v4*)(gd + i) = nv;
+}
+
+// out += emission on the valid pixels.  rec: the guide records (valid: w != 0) or, with var_mode,
+// the colour records the last iteration read (valid: w >= 0).
+__global__ __launch_bounds__(256) void k_dn_emit_add(const v4f* __restrict__ rec, int var_mode,
+                                                     const float* __restrict__ emission, int64_t n,
+                                                     float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float w = ((const float*)(rec + i))[3];
+  if (var_mode ? !(w >= 0.0f) : w == 0.0f) return;
+  out[3 * i] += emission[3 * i];
+  out[3 * i + 1] += emission[3 * i + 1];
+  out[3 * i + 2] += emission[3 * i + 2];
+}
+
 std::mutex g_mu;                 // one denoise at a time: the scratch buffers are shared
 DeviceScratch g_work, g_stage;   // records (48 B per pixel); rt_denoise's staged host buffers
 
@@ -377,8 +467,10 @@ struct Resolved {
 };
 
 // argument checks shared by both entry points (before any device is touched)
+// emit: null for the parents; the split entries pass theirs, which replaces feat->albedo
 int resolve(const char* who, const float* rgb, const rt_aov* feat, int w, int h,
-            const rt_denoise_opts* opts, const float* out, Resolved* r) {
+            const rt_denoise_opts* opts, const float* out, Resolved* r,
+            const rt_aov_emit* const* emit = nullptr) {
   if (w <= 0 || h <= 0) return set_error(RT_ERR_INVALID, "%s: %d x %d image", who, w, h);
   if ((int64_t)w * h >= ((int64_t)1 << 31) / 3)
     return set_error(RT_ERR_INVALID, "%s: %d x %d image", who, w, h);
@@ -389,8 +481,12 @@ int resolve(const char* who, const float* rgb, const rt_aov* feat, int w, int h,
   if (opts) o = *opts;
   if (o.iterations < 0 || o.iterations > 8)
     return set_error(RT_ERR_INVALID, "%s: %d iterations (1..8)", who, o.iterations);
-  if (o.demodulate && (!feat || !feat->albedo))
+  if (emit) {
+    if (!*emit || !(*emit)->emission || !(*emit)->surface_albedo || !(*emit)->coverage)
+      return set_error(RT_ERR_INVALID, "%s: needs the emission, surface_albedo and coverage buffers", who);
+  } else if (o.demodulate && (!feat || !feat->albedo)) {
     return set_error(RT_ERR_INVALID, "%s: demodulate needs the albedo buffer", who);
+  }
   if (!(o.sigma_color >= 0.0f) || !(o.sigma_normal >= 0.0f) || !(o.sigma_depth >= 0.0f))
     return set_error(RT_ERR_INVALID, "%s: negative or NaN sigma", who);
   r->iterations = o.iterations == 0 ? 5 : o.iterations;
@@ -403,7 +499,8 @@ int resolve(const char* who, const float* rgb, const rt_aov* feat, int w, int h,
 
 // rt_denoise_var's checks: rt_denoise's own (sigma_lum in sigma_color's place) and the variance
 int resolve_var(const char* who, const float* rgb, const float* var, const rt_aov* feat, int w, int h,
-                const rt_denoise_var_opts* opts, const float* out, Resolved* r) {
+                const rt_denoise_var_opts* opts, const float* out, Resolved* r,
+                const rt_aov_emit* const* emit = nullptr) {
   rt_denoise_opts o{};
   if (opts) {
     o.iterations = opts->iterations;
@@ -412,7 +509,7 @@ int resolve_var(const char* who, const float* rgb, const float* var, const rt_ao
     o.sigma_normal = opts->sigma_normal;
     o.sigma_depth = opts->sigma_depth;
   }
-  int rc = resolve(who, rgb, feat, w, h, &o, out, r);
+  int rc = resolve(who, rgb, feat, w, h, &o, out, r, emit);
   if (rc) return rc;
   if (!var) return set_error(RT_ERR_INVALID, "%s: null variance", who);
   r->sc = o.sigma_color > 0.0f ? o.sigma_color : 1.0f;  // sigma_lum (the sweep)
@@ -424,20 +521,24 @@ float inv_sq(double sigma) {
   return (float)std::min(v, (double)kMaxInv);
 }
 
-// all pointers on the current device; g_mu held
-int run(const float* rgb, const rt_aov* feat, int w, int h, const Resolved& r, float* out, int device,
-        hipStream_t s) {
+// all pointers on the current device; g_mu held.  emit: the split mode (null: the parent)
+int run(const float* rgb, const rt_aov* feat, const rt_aov_emit* emit, int w, int h, const Resolved& r,
+        float* out, int device, hipStream_t s) {
   const int64_t n = (int64_t)w * h;
   void* wk = nullptr;
   int rc = g_work.get(device, (size_t)n * 48, &wk, "rt_denoise");
   if (rc) return rc;
   v4f* gd = (v4f*)wk;
   v4f* col[2] = {gd + n, gd + 2 * n};
-  const float* albedo = feat ? feat->albedo : nullptr;
+  const float* albedo = emit ? emit->surface_albedo : feat ? feat->albedo : nullptr;
   const float* normal = feat ? feat->normal : nullptr;
   const float* depth = feat ? feat->depth : nullptr;
-  hipLaunchKernelGGL(k_dn_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rgb, albedo, normal,
-                     depth, n, r.demod, col[0], gd);
+  const dim3 lin((unsigned)((n + 255) / 256));
+  if (emit)
+    hipLaunchKernelGGL(k_dn_prep_emit, lin, dim3(256), 0, s, rgb, emit->emission, albedo, emit->coverage,
+                       normal, depth, n, r.demod, col[0], gd);
+  else
+    hipLaunchKernelGGL(k_dn_prep, lin, dim3(256), 0, s, rgb, albedo, normal, depth, n, r.demod, col[0], gd);
   HIP_OK(hipGetLastError());
   const dim3 grid((unsigned)((w + kTW - 1) / kTW), (unsigned)((h + kTH - 1) / kTH));
   for (int i = 0; i < r.iterations; ++i) {
@@ -458,23 +559,32 @@ int run(const float* rgb, const rt_aov* feat, int w, int h, const Resolved& r, f
     else hipLaunchKernelGGL((k_dn_atrous<false, false>), grid, dim3(256), 0, s, p, in, gd, o, rgb, albedo, out);
     HIP_OK(hipGetLastError());
   }
+  if (emit) {  // the guide records keep the validity an aliased out has overwritten in rgb
+    hipLaunchKernelGGL(k_dn_emit_add, lin, dim3(256), 0, s, gd, 0, emit->emission, n, out);
+    HIP_OK(hipGetLastError());
+  }
   return RT_OK;
 }
 
 // the variance-guided filter; all pointers on the current device (var_out may be null); g_mu held
-int run_var(const float* rgb, const float* var, const rt_aov* feat, int w, int h, const Resolved& r,
-            float* out, float* var_out, int device, hipStream_t s) {
+int run_var(const float* rgb, const float* var, const rt_aov* feat, const rt_aov_emit* emit, int w, int h,
+            const Resolved& r, float* out, float* var_out, int device, hipStream_t s) {
   const int64_t n = (int64_t)w * h;
   void* wk = nullptr;
   int rc = g_work.get(device, (size_t)n * 48, &wk, "rt_denoise_var");
   if (rc) return rc;
   v4f* gd = (v4f*)wk;
   v4f* col[2] = {gd + n, gd + 2 * n};
-  const float* albedo = feat ? feat->albedo : nullptr;
+  const float* albedo = emit ? emit->surface_albedo : feat ? feat->albedo : nullptr;
   const float* normal = feat ? feat->normal : nullptr;
   const float* depth = feat ? feat->depth : nullptr;
-  hipLaunchKernelGGL(k_dnv_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rgb, var, albedo,
-                     normal, depth, n, r.demod, col[0], gd);
+  const dim3 lin((unsigned)((n + 255) / 256));
+  if (emit)
+    hipLaunchKernelGGL(k_dnv_prep_emit, lin, dim3(256), 0, s, rgb, var, emit->emission, albedo,
+                       emit->coverage, normal, depth, n, r.demod, col[0], gd);
+  else
+    hipLaunchKernelGGL(k_dnv_prep, lin, dim3(256), 0, s, rgb, var, albedo, normal, depth, n, r.demod,
+                       col[0], gd);
   HIP_OK(hipGetLastError());
   const dim3 grid((unsigned)((w + kTW - 1) / kTW), (unsigned)((h + kTH - 1) / kTH));
   for (int i = 0; i < r.iterations; ++i) {
@@ -493,6 +603,11 @@ int run_var(const float* rgb, const float* var, const rt_aov* feat, int w, int h
     else if (tile) hipLaunchKernelGGL((k_dnv_atrous<true, false>), grid, dim3(256), 0, s, p, in, gd, o, rgb, var, albedo, out, var_out);
     else if (fin) hipLaunchKernelGGL((k_dnv_atrous<false, true>), grid, dim3(256), 0, s, p, in, gd, o, rgb, var, albedo, out, var_out);
     else hipLaunchKernelGGL((k_dnv_atrous<false, false>), grid, dim3(256), 0, s, p, in, gd, o, rgb, var, albedo, out, var_out);
+    HIP_OK(hipGetLastError());
+  }
+  if (emit) {  // the records the last iteration read keep the validity (v >= 0)
+    hipLaunchKernelGGL(k_dn_emit_add, lin, dim3(256), 0, s, col[(r.iterations - 1) & 1], 1, emit->emission, n,
+                       out);
     HIP_OK(hipGetLastError());
   }
   return RT_OK;
@@ -514,7 +629,7 @@ int rt_denoise_device(const float* rgb_dev, const rt_aov* feat_dev, int w, int h
   HIP_OK(hipSetDevice(device));
   std::lock_guard<std::mutex> lk(g_mu);
   hipStream_t s = (hipStream_t)stream;
-  rc = run(rgb_dev, feat_dev, w, h, r, out_dev, device, s);
+  rc = run(rgb_dev, feat_dev, nullptr, w, h, r, out_dev, device, s);
   HIP_OK(hipStreamSynchronize(s));  // also after an error: nothing in flight on the scratch
   if (rc) return rc;
   return RT_OK;
@@ -551,7 +666,7 @@ int rt_denoise(const float* rgb, const rt_aov* feat, int w, int h, const rt_deno
     f.depth = d_rgb + 9 * n;
     HIP_OK(hipMemcpyAsync(f.depth, feat->depth, n * 4, hipMemcpyHostToDevice, s));
   }
-  rc = run(d_rgb, &f, w, h, r, d_rgb, device, s);
+  rc = run(d_rgb, &f, nullptr, w, h, r, d_rgb, device, s);
   if (!rc && hipMemcpyAsync(out, d_rgb, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess)
     rc = set_error(RT_ERR_DEVICE, "rt_denoise: copy to host failed");
   HIP_OK(hipStreamSynchronize(s));  // also after an error: nothing in flight on the scratch
@@ -571,7 +686,7 @@ int rt_denoise_var_device(const float* rgb_dev, const float* var_dev, const rt_a
   HIP_OK(hipSetDevice(device));
   std::lock_guard<std::mutex> lk(g_mu);
   hipStream_t s = (hipStream_t)stream;
-  rc = run_var(rgb_dev, var_dev, feat_dev, w, h, r, out_dev, var_out_dev, device, s);
+  rc = run_var(rgb_dev, var_dev, feat_dev, nullptr, w, h, r, out_dev, var_out_dev, device, s);
   HIP_OK(hipStreamSynchronize(s));  // also after an error: nothing in flight on the scratch
   if (rc) return rc;
   return RT_OK;
@@ -610,13 +725,122 @@ int rt_denoise_var(const float* rgb, const float* var, const rt_aov* feat, int w
     f.depth = d_rgb + 9 * n;
     HIP_OK(hipMemcpyAsync(f.depth, feat->depth, n * 4, hipMemcpyHostToDevice, s));
   }
-  rc = run_var(d_rgb, d_var, &f, w, h, r, d_rgb, var_out ? d_var : nullptr, device, s);
+  rc = run_var(d_rgb, d_var, &f, nullptr, w, h, r, d_rgb, var_out ? d_var : nullptr, device, s);
   if (!rc && (hipMemcpyAsync(out, d_rgb, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess ||
               (var_out && hipMemcpyAsync(var_out, d_var, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)))
     rc = set_error(RT_ERR_DEVICE, "rt_denoise_var: copy to host failed");
   HIP_OK(hipStreamSynchronize(s));  // also after an error: nothing in flight on the scratch
   if (rc) return rc;
   return RT_OK;
+}
+
+// ---- emission split: the parents' entries with an rt_aov_emit after feat ----
+
+int rt_denoise_emit_device(const float* rgb_dev, const rt_aov* feat_dev, const rt_aov_emit* emit_dev,
+                           int w, int h, const rt_denoise_opts* opts, float* out_dev, int device,
+                           void* stream) {
+  using namespace rt;
+  Resolved r;
+  int rc = resolve("rt_denoise_emit_device", rgb_dev, feat_dev, w, h, opts, out_dev, &r, &emit_dev);
+  if (rc) return rc;
+  if ((rc = device_ok("rt_denoise_emit_device", device))) return rc;
+  DeviceGuard dg;
+  HIP_OK(hipSetDevice(device));
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = (hipStream_t)stream;
+  rc = run(rgb_dev, feat_dev, emit_dev, w, h, r, out_dev, device, s);
+  HIP_OK(hipStreamSynchronize(s));  // also after an error: nothing in flight on the scratch
+  if (rc) return rc;
+  return RT_OK;
+}
+
+int rt_denoise_var_emit_device(const float* rgb_dev, const float* var_dev, const rt_aov* feat_dev,
+                               const rt_aov_emit* emit_dev, int w, int h,
+                               const rt_denoise_var_opts* opts, float* out_dev, float* var_out_dev,
+                               int device, void* stream) {
+  using namespace rt;
+  Resolved r;
+  int rc = resolve_var("rt_denoise_var_emit_device", rgb_dev, var_dev, feat_dev, w, h, opts, out_dev, &r,
+                       &emit_dev);
+  if (rc) return rc;
+  if ((rc = device_ok("rt_denoise_var_emit_device", device))) return rc;
+  DeviceGuard dg;
+  HIP_OK(hipSetDevice(device));
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = (hipStream_t)stream;
+  rc = run_var(rgb_dev, var_dev, feat_dev, emit_dev, w, h, r, out_dev, var_out_dev, device, s);
+  HIP_OK(hipStreamSynchronize(s));  // also after an error: nothing in flight on the scratch
+  if (rc) return rc;
+  return RT_OK;
+}
+
+}  // extern "C"
+
+namespace rt {
+namespace {
+
+// the two host entries of the split mode (var null: rt_denoise_emit); arguments already checked.
+// staged: rgb (also the output) | surface_albedo | normal | depth | var (also the output) |
+// emission | coverage
+int host_emit(const char* who, const float* rgb, const float* var, const rt_aov* feat,
+              const rt_aov_emit* emit, int w, int h, const Resolved& r, float* out, float* var_out) {
+  const int device = 0;
+  int rc = device_ok(who, device);
+  if (rc) return rc;
+  DeviceGuard dg;
+  HIP_OK(hipSetDevice(device));
+  std::lock_guard<std::mutex> lk(g_mu);
+  const size_t n = (size_t)w * h;
+  void* stg = nullptr;
+  if ((rc = g_stage.get(device, n * 60, &stg, who))) return rc;
+  float* d_rgb = (float*)stg;
+  float* d_var = d_rgb + 10 * n;
+  rt_aov f{nullptr, nullptr, nullptr, nullptr};
+  rt_aov_emit e{d_rgb + 11 * n, d_rgb + 3 * n, d_rgb + 14 * n};
+  hipStream_t s = nullptr;
+  HIP_OK(hipMemcpyAsync(d_rgb, rgb, n * 12, hipMemcpyHostToDevice, s));
+  if (var) HIP_OK(hipMemcpyAsync(d_var, var, n * 4, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(e.emission, emit->emission, n * 12, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(e.surface_albedo, emit->surface_albedo, n * 12, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(e.coverage, emit->coverage, n * 4, hipMemcpyHostToDevice, s));
+  if (feat && feat->normal) {
+    f.normal = d_rgb + 6 * n;
+    HIP_OK(hipMemcpyAsync(f.normal, feat->normal, n * 12, hipMemcpyHostToDevice, s));
+  }
+  if (feat && feat->depth) {
+    f.depth = d_rgb + 9 * n;
+    HIP_OK(hipMemcpyAsync(f.depth, feat->depth, n * 4, hipMemcpyHostToDevice, s));
+  }
+  rc = var ? run_var(d_rgb, d_var, &f, &e, w, h, r, d_rgb, var_out ? d_var : nullptr, device, s)
+           : run(d_rgb, &f, &e, w, h, r, d_rgb, device, s);
+  if (!rc && (hipMemcpyAsync(out, d_rgb, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess ||
+              (var_out && hipMemcpyAsync(var_out, d_var, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)))
+    rc = set_error(RT_ERR_DEVICE, "%s: copy to host failed", who);
+  HIP_OK(hipStreamSynchronize(s));  // also after an error: nothing in flight on the scratch
+  return rc;
+}
+
+}  // namespace
+}  // namespace rt
+
+extern "C" {
+
+int rt_denoise_emit(const float* rgb, const rt_aov* feat, const rt_aov_emit* emit, int w, int h,
+                    const rt_denoise_opts* opts, float* out) {
+  using namespace rt;
+  Resolved r;
+  int rc = resolve("rt_denoise_emit", rgb, feat, w, h, opts, out, &r, &emit);
+  if (rc) return rc;
+  return host_emit("rt_denoise_emit", rgb, nullptr, feat, emit, w, h, r, out, nullptr);
+}
+
+int rt_denoise_var_emit(const float* rgb, const float* var, const rt_aov* feat, const rt_aov_emit* emit,
+                        int w, int h, const rt_denoise_var_opts* opts, float* out, float* var_out) {
+  using namespace rt;
+  Resolved r;
+  int rc = resolve_var("rt_denoise_var_emit", rgb, var, feat, w, h, opts, out, &r, &emit);
+  if (rc) return rc;
+  return host_emit("rt_denoise_var_emit", rgb, var, feat, emit, w, h, r, out, var_out);
 }
 
 }  // extern "C"

@@ -20,7 +20,10 @@
 // the a-trous denoiser before the PPM is written; prints the statistics line with
 // both times), -denoise-var (the same with the variance-guided filter, rt_denoise_var, fed from
 // the pass accumulator's variance: needs -passes N >= 2 or -until; the statistics line gains
-// "denoise_var": 1), -aov PREFIX (writes PREFIX_albedo.ppm, PREFIX_normal.ppm as
+// "denoise_var": 1), -split-emitters (with either: rt_render_aov_emit and the _emit filter, so
+// directly seen lights stay out of the filter; alone a usage error; -aov then also writes
+// PREFIX_emission.ppm and PREFIX_coverage.ppm; the statistics line gains "split_emitters": 1),
+// -aov PREFIX (writes PREFIX_albedo.ppm, PREFIX_normal.ppm as
 // n * 0.5 + 0.5 and PREFIX_depth.ppm normalised to the image maximum, through the
 // same PPM writer), -passes N (the image as the exact mean of N passes of -spp samples each,
 // seeds seed .. seed + N - 1, through the pass accumulator; -passes 1 writes the plain
@@ -65,7 +68,7 @@ struct Args {
   double until = 0.0, adaptive = 0.0;
   bool adaptive_set = false;
   unsigned long long seed = 1, tree_seed = 1;
-  bool progress = false, stats = false, denoise = false, denoise_var = false;
+  bool progress = false, stats = false, denoise = false, denoise_var = false, split_emitters = false;
 };
 
 std::vector<Flag> flags(Args& a) {
@@ -97,6 +100,8 @@ std::vector<Flag> flags(Args& a) {
       {"seed", "render seed (Philox key)", Flag::U64, &a.seed, "1"},
       {"slices", "progress granularity: launches per render (0 = 20 with -progress)", Flag::INT,
        &a.slices, "0"},
+      {"split-emitters", "with -denoise or -denoise-var: keep directly seen lights out of the filter (emission split); -aov also writes PREFIX_emission.ppm and PREFIX_coverage.ppm",
+       Flag::BOOL, &a.split_emitters, ""},
       {"spp", "override Camera.SamplesPerPixel (0 = the scene's)", Flag::INT, &a.spp, "0"},
       {"stats", "print render statistics (JSON) on stderr", Flag::BOOL, &a.stats, ""},
       {"tree-seed", "seed of the scene builder's rand (main.go's math/rand)", Flag::U64,
@@ -233,8 +238,9 @@ int fail(const char* what, int rc) {
 std::string stats_json(const rt_stats& st, const rt_camera_derived& d, const char* scene,
                        double wall_s, int aov_samples, double ms_aov, double ms_denoise,
                        const rt_accum_info* acc, double ms_accum, bool denoise_var,
-                       const rt_adapt_info* ad = nullptr) {
+                       const rt_adapt_info* ad = nullptr, bool split_emitters = false) {
   char b[1280], extra[200] = "", extra2[200] = "";
+  const char* extra3 = split_emitters ? "\"split_emitters\": 1, " : "";
   if (acc)  // -passes / -until
     snprintf(extra, sizeof extra, "\"passes\": %d, \"rel_error\": %.6g, \"ms_accum\": %.3f, %s", acc->passes,
              acc->rel_error, ms_accum, denoise_var ? "\"denoise_var\": 1, " : "");
@@ -246,10 +252,10 @@ std::string stats_json(const rt_stats& st, const rt_camera_derived& d, const cha
            "{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"spp\": %d, \"max_depth\": %d, "
            "\"samples\": %" PRIu64 ", \"segments\": %" PRIu64 ", \"ms_render\": %.3f, "
            "\"samples_per_s\": %.6g, \"mode\": %d, \"tree_width\": %d, \"chunk_samples\": %d, "
-           "\"aov_samples\": %d, \"ms_aov\": %.3f, \"ms_denoise\": %.3f, %s%s\"wall_s\": %.3f}",
+           "\"aov_samples\": %d, \"ms_aov\": %.3f, \"ms_denoise\": %.3f, %s%s%s\"wall_s\": %.3f}",
            scene, d.width, d.height, d.spp_sqrt * d.spp_sqrt, d.max_depth, st.samples,
            st.segments, st.ms_total, st.ms_total > 0 ? st.samples / (st.ms_total * 1e-3) : 0.0,
-           st.mode, st.tree_width, st.chunk_samples, aov_samples, ms_aov, ms_denoise, extra, extra2, wall_s);
+           st.mode, st.tree_width, st.chunk_samples, aov_samples, ms_aov, ms_denoise, extra, extra2, extra3, wall_s);
   return b;
 }
 
@@ -275,6 +281,11 @@ int main(int argc, char** argv) {
   // the variance comes from the passes: one pass has none (checked before the file is created)
   if (a.denoise_var && !(a.passes >= 2 || ((a.until > 0.0 || a.adaptive_set) && a.passes == 0))) {
     fprintf(stderr, "-denoise-var needs -passes N with N >= 2, or -until / -adaptive\n");
+    usage(argv[0], flags(a));
+    return 2;
+  }
+  if (a.split_emitters && !a.denoise && !a.denoise_var) {  // nothing to split for
+    fprintf(stderr, "-split-emitters needs -denoise or -denoise-var\n");
     usage(argv[0], flags(a));
     return 2;
   }
@@ -442,23 +453,42 @@ int main(int argc, char** argv) {
     aov_samples = d.spp_sqrt * d.spp_sqrt < 16 ? d.spp_sqrt * d.spp_sqrt : 16;
     rt_stats sa;
     auto ta = std::chrono::steady_clock::now();
-    if ((rc = rt_render_aov(sc, &cam, &o, aov_samples, &f, &sa)) != RT_OK) return fail("rt_render_aov", rc);
+    // -split-emitters: the split feature pass and the split filter
+    std::vector<float> emission(a.split_emitters ? 3 * np : 0), salbedo(a.split_emitters ? 3 * np : 0),
+        coverage(a.split_emitters ? np : 0);
+    rt_aov_emit fe = {emission.data(), salbedo.data(), coverage.data()};
+    if (a.split_emitters) {
+      if ((rc = rt_render_aov_emit(sc, &cam, &o, aov_samples, &f, &fe, &sa)) != RT_OK)
+        return fail("rt_render_aov_emit", rc);
+    } else if ((rc = rt_render_aov(sc, &cam, &o, aov_samples, &f, &sa)) != RT_OK) {
+      return fail("rt_render_aov", rc);
+    }
     ms_aov = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
     if (a.denoise_var) {
       rt_denoise_var_opts vopt;
       memset(&vopt, 0, sizeof vopt);  // the library defaults
       vopt.demodulate = 1;
       auto td = std::chrono::steady_clock::now();
-      if ((rc = rt_denoise_var(rgb.data(), var.data(), &f, d.width, d.height, &vopt, rgb.data(), nullptr)) != RT_OK)
+      if (a.split_emitters) {
+        if ((rc = rt_denoise_var_emit(rgb.data(), var.data(), &f, &fe, d.width, d.height, &vopt, rgb.data(),
+                                      nullptr)) != RT_OK)
+          return fail("rt_denoise_var_emit", rc);
+      } else if ((rc = rt_denoise_var(rgb.data(), var.data(), &f, d.width, d.height, &vopt, rgb.data(),
+                                      nullptr)) != RT_OK) {
         return fail("rt_denoise_var", rc);
+      }
       ms_denoise = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
     } else if (a.denoise) {
       rt_denoise_opts dopt;
       memset(&dopt, 0, sizeof dopt);  // the library defaults
       dopt.demodulate = 1;
       auto td = std::chrono::steady_clock::now();
-      if ((rc = rt_denoise(rgb.data(), &f, d.width, d.height, &dopt, rgb.data())) != RT_OK)
+      if (a.split_emitters) {
+        if ((rc = rt_denoise_emit(rgb.data(), &f, &fe, d.width, d.height, &dopt, rgb.data())) != RT_OK)
+          return fail("rt_denoise_emit", rc);
+      } else if ((rc = rt_denoise(rgb.data(), &f, d.width, d.height, &dopt, rgb.data())) != RT_OK) {
         return fail("rt_denoise", rc);
+      }
       ms_denoise = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
     }
     if (!a.aov.empty()) {
@@ -473,6 +503,16 @@ int main(int argc, char** argv) {
         const std::string path = a.aov + e.first;
         if (write_ppm(*e.second, d.width, d.height, fopen(path.c_str(), "wb"), path.c_str())) return 1;
       }
+      if (a.split_emitters) {  // the emission as it is, the coverage as grey
+        std::vector<float> cimg(3 * np);
+        for (size_t i = 0; i < np; ++i) cimg[3 * i] = cimg[3 * i + 1] = cimg[3 * i + 2] = coverage[i];
+        const std::pair<const char*, const std::vector<float>*> eouts[] = {{"_emission.ppm", &emission},
+                                                                            {"_coverage.ppm", &cimg}};
+        for (const auto& e : eouts) {
+          const std::string path = a.aov + e.first;
+          if (write_ppm(*e.second, d.width, d.height, fopen(path.c_str(), "wb"), path.c_str())) return 1;
+        }
+      }
     }
   }
 
@@ -480,7 +520,7 @@ int main(int argc, char** argv) {
   if (write_ppm(rgb, d.width, d.height, out, a.out.c_str())) return 1;
   double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::string js = stats_json(st, d, scene, wall, aov_samples, ms_aov, ms_denoise, accumulate ? &ai : nullptr,
-                              ms_accum, a.denoise_var, a.adaptive_set ? &adi : nullptr);
+                              ms_accum, a.denoise_var, a.adaptive_set ? &adi : nullptr, a.split_emitters);
   if (a.stats || a.denoise || a.denoise_var) fprintf(stderr, "%s\n", js.c_str());
   if (!a.cpuprofile.empty()) {
     FILE* p = fopen(a.cpuprofile.c_str(), "w");

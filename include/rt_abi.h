@@ -597,6 +597,67 @@ int rt_denoise_var_device(const float* rgb_dev, const float* var_dev, const rt_a
                           float* var_out_dev, int device, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Emission split (DESIGN.md "Emission split"): what a directly seen light   */
+/* contributes to a pixel, kept out of the filters.  Added without an ABI    */
+/* version change: detect by the symbols.                                    */
+/* ------------------------------------------------------------------------ */
+typedef struct {            /* any pointer may be NULL = not wanted */
+  float* emission;          /* [rows][W][3] */
+  float* surface_albedo;    /* [rows][W][3] */
+  float* coverage;          /* [rows][W]    */
+} rt_aov_emit;
+
+/* rt_render_aov with three more buffers.  The ray and the hit evaluation of sample j are
+ * rt_render_aov's.  Let L_j be true when the closest world hit of sample j is an
+ * RT_MAT_DIFFUSE_LIGHT seen from its front face.  Over samples 0 .. n-1:
+ *   emission       = mean of E_j, E_j = the light's texture at the hit when L_j, else 0: exactly
+ *                    what such a camera sample adds to the render.  It is NOT clamped: a
+ *                    light does not scatter, so rayColor returns its emission (camera.go:312-314)
+ *                    before the clampContribution of camera.go:330, which only a scattering
+ *                    vertex reaches; MaxContribution does not enter
+ *   surface_albedo = mean of A_j, A_j = rt_render_aov's albedo of the sample when !L_j (a miss
+ *                    = the background, a back-facing light = 0), 0 when L_j
+ *   coverage       = (float)count(L_j) / (float)n, a true division: exactly 1.0f when every
+ *                    sample sees the light
+ * out (may be NULL) takes rt_render_aov's four buffers, bit-identical to that call's.  Two
+ * calls give identical bits.  A NULL emit, or out and emit together without any buffer, is
+ * RT_ERR_INVALID (checked before any device is touched); otherwise the rules, the structures
+ * traversed and the stats are rt_render_aov's. */
+int rt_render_aov_emit(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
+                       int32_t n_samples, const rt_aov* out_host, const rt_aov_emit* emit_host,
+                       rt_stats* stats);
+int rt_render_aov_emit_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
+                              int32_t n_samples, const rt_aov* out_device,
+                              const rt_aov_emit* emit_device, rt_stats* stats);
+
+/* rt_denoise / rt_denoise_var in split mode: the emission is subtracted before the filter and
+ * added back after it, and the filter demodulates by the albedo of the surfaces the pixel
+ * covers.  All three emit buffers are required (else RT_ERR_INVALID); feat->albedo is not read
+ * and feat may be NULL.  The definition is the parent's with exactly these changes:
+ *   valid pixel: the parent's rule, and emission finite, and coverage < 1.
+ *   prep: a = max(surface_albedo, 1e-3) per channel, c = (rgb - emission) / a and
+ *     v = max(var / Y(a)^2, 0) when demodulating; else c = rgb - emission, v = max(var, 0).
+ *   iterations: unchanged (invalid taps are skipped as they are in the parent).
+ *   output, valid pixels: out = c a + emission (c + emission when not demodulating),
+ *     var_out = v Y(a)^2 (v when not demodulating): the emission is deterministic and adds no
+ *     variance.
+ *   output, invalid pixels (those with coverage 1 included): rgb and var pass through bit for
+ *     bit, also when out aliases rgb and var_out aliases var.
+ * With emission = 0, coverage = 0 and surface_albedo = albedo the result is the parent's. */
+int rt_denoise_emit(const float* rgb, const rt_aov* feat, const rt_aov_emit* emit, int w, int h,
+                    const rt_denoise_opts* opts, float* out);
+int rt_denoise_emit_device(const float* rgb_dev, const rt_aov* feat_dev,
+                           const rt_aov_emit* emit_dev, int w, int h,
+                           const rt_denoise_opts* opts, float* out_dev, int device, void* stream);
+int rt_denoise_var_emit(const float* rgb, const float* var, const rt_aov* feat,
+                        const rt_aov_emit* emit, int w, int h, const rt_denoise_var_opts* opts,
+                        float* out, float* var_out);
+int rt_denoise_var_emit_device(const float* rgb_dev, const float* var_dev, const rt_aov* feat_dev,
+                               const rt_aov_emit* emit_dev, int w, int h,
+                               const rt_denoise_var_opts* opts, float* out_dev,
+                               float* var_out_dev, int device, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Progressive pass accumulator (DESIGN.md "Pass accumulator"): the exact    */
 /* sum of any number of render passes of one camera, kept on the device,     */
 /* with a per-pixel variance.  Added without an ABI version change: detect   */
