@@ -884,12 +884,18 @@ def format_ppm_device(rgb, to_host=True):
     return out.cpu().numpy().tobytes() if to_host else out
 
 
-def _denoise_opts(iterations=0, demodulate=None, sigma_color=0.0, sigma_normal=0.0,
-                  sigma_depth=0.0, has_albedo=False):
-    o = RtDenoiseOpts()
+def _denoise_opts(var, iterations=0, demodulate=None, sigma_normal=0.0, sigma_depth=0.0,
+                  has_albedo=False, **sigma):
+    """RtDenoiseVarOpts (its colour sigma: sigma_lum) with a variance, else RtDenoiseOpts
+    (sigma_color)"""
+    o = RtDenoiseVarOpts() if var else RtDenoiseOpts()
     o.iterations = iterations
     o.demodulate = int(has_albedo if demodulate is None else demodulate)
-    o.sigma_color, o.sigma_normal, o.sigma_depth = sigma_color, sigma_normal, sigma_depth
+    o.sigma_normal, o.sigma_depth = sigma_normal, sigma_depth
+    key = "sigma_lum" if var else "sigma_color"
+    setattr(o, key, sigma.pop(key, 0.0))
+    if sigma:
+        raise TypeError(f"_denoise_opts() got an unexpected keyword argument {next(iter(sigma))!r}")
     return o
 
 
@@ -928,6 +934,71 @@ def _emit_device(who, aov, a):
     return RtAovEmit(*[t.data_ptr() for t in keep]), keep
 
 
+def _denoise_host(has_var, rgb, var, aov, return_var, split_emitters, opts):
+    """denoise and denoise_var (has_var): rt_denoise[_var][_emit] on host arrays"""
+    who = "denoise_var" if has_var else "denoise"
+    a = np.ascontiguousarray(rgb, dtype=np.float32)
+    h, w = a.shape[:2]
+    if has_var:
+        if var is None:
+            raise ValueError("denoise_var: var is required")
+        v = np.ascontiguousarray(var, dtype=np.float32)
+        if v.shape != (h, w):
+            raise ValueError(f"denoise_var: var must have shape {(h, w)}, not {v.shape}")
+    aov = aov or {}
+    if split_emitters:
+        e, _keep = _emit_host(who, aov, h, w)
+    keep = [None if aov.get(k) is None else np.ascontiguousarray(aov[k], dtype=np.float32)
+            for k in ("albedo", "normal", "depth")]
+    f = RtAov(*[None if k is None else k.ctypes.data for k in keep], None)
+    o = _denoise_opts(has_var, has_albedo=split_emitters or keep[0] is not None, **opts)
+    out = np.empty_like(a)
+    vout = np.empty_like(v) if return_var else None
+    fn = getattr(lib(), "rt_denoise" + "_var" * has_var + "_emit" * split_emitters)
+    check(fn(a.ctypes.data, *([v.ctypes.data] if has_var else []), C.byref(f),
+             *([C.byref(e)] if split_emitters else []), w, h, C.byref(o), out.ctypes.data,
+             *([None if vout is None else vout.ctypes.data] if has_var else [])))
+    return (out, vout) if return_var else out
+
+
+def _denoise_dev(has_var, rgb, var, aov, out, var_out, split_emitters, opts):
+    """denoise_device and denoise_var_device (has_var): rt_denoise[_var][_emit]_device on torch
+    tensors"""
+    import torch
+    who = "denoise_var_device" if has_var else "denoise_device"
+    a = rgb if (rgb.is_contiguous() and rgb.dtype == torch.float32) else \
+        rgb.contiguous().to(torch.float32)
+    h, w = a.shape[:2]
+    for name, t in (("var", var), ("var_out", var_out)) if has_var else ():
+        if name == "var_out" and t is None:
+            continue
+        if (t is None or not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous()
+                or tuple(t.shape) != (h, w) or t.device != a.device):
+            raise ValueError(f"{who}: {name} must be a contiguous float32 tensor of shape "
+                             f"{(h, w)} on rgb's device")
+    aov = aov or {}
+    if split_emitters:
+        e, _keep = _emit_device(who, aov, a)
+    keep = [None if aov.get(k) is None else aov[k].contiguous().to(torch.float32)
+            for k in ("albedo", "normal", "depth")]
+    f = RtAov(*[None if k is None else k.data_ptr() for k in keep], None)
+    o = _denoise_opts(has_var, has_albedo=split_emitters or keep[0] is not None, **opts)
+    if out is None:
+        out = torch.empty_like(a)
+    elif (out.dtype != torch.float32 or not out.is_contiguous() or out.shape != a.shape
+          or out.device != a.device):
+        raise ValueError(f"{who}: out must be a contiguous float32 tensor of rgb's shape "
+                         "on rgb's device")
+    elif out is rgb and a is not rgb:
+        raise ValueError(f"{who}: in place needs a contiguous float32 rgb")
+    fn = getattr(lib(), "rt_denoise" + "_var" * has_var + "_emit" * split_emitters + "_device")
+    check(fn(a.data_ptr(), *([var.data_ptr()] if has_var else []), C.byref(f),
+             *([C.byref(e)] if split_emitters else []), w, h, C.byref(o), out.data_ptr(),
+             *([None if var_out is None else var_out.data_ptr()] if has_var else []),
+             a.device.index or 0, _stream_of(a)))
+    return out
+
+
 def denoise(rgb, aov=None, split_emitters=False, **opts):
     """Edge-avoiding a-trous denoise (rt_denoise) of a host float32 [H, W, 3] image guided by
     `aov`, a dict as Scene.render_aov returns it (any of "albedo", "normal", "depth"; None or
@@ -937,22 +1008,7 @@ def denoise(rgb, aov=None, split_emitters=False, **opts):
     "coverage" (Scene.render_aov(emit=True)); the emission is kept out of the filter, which
     demodulates by surface_albedo ("albedo" is not read).  Returns a new float32 [H, W, 3]
     array."""
-    a = np.ascontiguousarray(rgb, dtype=np.float32)
-    h, w = a.shape[:2]
-    aov = aov or {}
-    if split_emitters:
-        e, _keep = _emit_host("denoise", aov, h, w)
-    keep = [None if aov.get(k) is None else np.ascontiguousarray(aov[k], dtype=np.float32)
-            for k in ("albedo", "normal", "depth")]
-    f = RtAov(*[None if k is None else k.ctypes.data for k in keep], None)
-    o = _denoise_opts(has_albedo=split_emitters or keep[0] is not None, **opts)
-    out = np.empty_like(a)
-    if split_emitters:
-        check(lib().rt_denoise_emit(a.ctypes.data, C.byref(f), C.byref(e), w, h, C.byref(o),
-                                    out.ctypes.data))
-    else:
-        check(lib().rt_denoise(a.ctypes.data, C.byref(f), w, h, C.byref(o), out.ctypes.data))
-    return out
+    return _denoise_host(False, rgb, None, aov, False, split_emitters, opts)
 
 
 def denoise_device(rgb, aov=None, out=None, split_emitters=False, **opts):
@@ -962,41 +1018,7 @@ def denoise_device(rgb, aov=None, out=None, split_emitters=False, **opts):
     (rt_denoise_emit_device): aov must also hold "emission" [H, W, 3], "surface_albedo"
     [H, W, 3] and "coverage" [H, W] as contiguous float32 tensors on rgb's device.  Runs on the
     tensor's current stream and returns after the work completes."""
-    import torch
-    a = rgb if (rgb.is_contiguous() and rgb.dtype == torch.float32) else \
-        rgb.contiguous().to(torch.float32)
-    h, w = a.shape[:2]
-    aov = aov or {}
-    if split_emitters:
-        e, _keep = _emit_device("denoise_device", aov, a)
-    keep = [None if aov.get(k) is None else aov[k].contiguous().to(torch.float32)
-            for k in ("albedo", "normal", "depth")]
-    f = RtAov(*[None if k is None else k.data_ptr() for k in keep], None)
-    o = _denoise_opts(has_albedo=split_emitters or keep[0] is not None, **opts)
-    if out is None:
-        out = torch.empty_like(a)
-    elif (out.dtype != torch.float32 or not out.is_contiguous() or out.shape != a.shape
-          or out.device != a.device):
-        raise ValueError("denoise_device: out must be a contiguous float32 tensor of rgb's shape "
-                         "on rgb's device")
-    elif out is rgb and a is not rgb:
-        raise ValueError("denoise_device: in place needs a contiguous float32 rgb")
-    if split_emitters:
-        check(lib().rt_denoise_emit_device(a.data_ptr(), C.byref(f), C.byref(e), w, h, C.byref(o),
-                                           out.data_ptr(), a.device.index or 0, _stream_of(a)))
-    else:
-        check(lib().rt_denoise_device(a.data_ptr(), C.byref(f), w, h, C.byref(o), out.data_ptr(),
-                                      a.device.index or 0, _stream_of(a)))
-    return out
-
-
-def _denoise_var_opts(iterations=0, demodulate=None, sigma_lum=0.0, sigma_normal=0.0,
-                      sigma_depth=0.0, has_albedo=False):
-    o = RtDenoiseVarOpts()
-    o.iterations = iterations
-    o.demodulate = int(has_albedo if demodulate is None else demodulate)
-    o.sigma_lum, o.sigma_normal, o.sigma_depth = sigma_lum, sigma_normal, sigma_depth
-    return o
+    return _denoise_dev(False, rgb, None, aov, out, None, split_emitters, opts)
 
 
 def denoise_var(rgb, var, aov=None, return_var=False, split_emitters=False, **opts):
@@ -1006,30 +1028,7 @@ def denoise_var(rgb, var, aov=None, return_var=False, split_emitters=False, **op
     given), sigma_lum (0 = 1.0) / sigma_normal / sigma_depth.  Returns a new float32
     [H, W, 3] array, or with return_var (out, var_out [H, W]: the variance of the filtered
     image's luminance).  split_emitters=True (rt_denoise_var_emit): as denoise's."""
-    a = np.ascontiguousarray(rgb, dtype=np.float32)
-    h, w = a.shape[:2]
-    if var is None:
-        raise ValueError("denoise_var: var is required")
-    v = np.ascontiguousarray(var, dtype=np.float32)
-    if v.shape != (h, w):
-        raise ValueError(f"denoise_var: var must have shape {(h, w)}, not {v.shape}")
-    aov = aov or {}
-    if split_emitters:
-        e, _keep = _emit_host("denoise_var", aov, h, w)
-    keep = [None if aov.get(k) is None else np.ascontiguousarray(aov[k], dtype=np.float32)
-            for k in ("albedo", "normal", "depth")]
-    f = RtAov(*[None if k is None else k.ctypes.data for k in keep], None)
-    o = _denoise_var_opts(has_albedo=split_emitters or keep[0] is not None, **opts)
-    out = np.empty_like(a)
-    vout = np.empty_like(v) if return_var else None
-    if split_emitters:
-        check(lib().rt_denoise_var_emit(a.ctypes.data, v.ctypes.data, C.byref(f), C.byref(e), w, h,
-                                        C.byref(o), out.ctypes.data,
-                                        None if vout is None else vout.ctypes.data))
-    else:
-        check(lib().rt_denoise_var(a.ctypes.data, v.ctypes.data, C.byref(f), w, h, C.byref(o),
-                                   out.ctypes.data, None if vout is None else vout.ctypes.data))
-    return (out, vout) if return_var else out
+    return _denoise_host(True, rgb, var, aov, return_var, split_emitters, opts)
 
 
 def denoise_var_device(rgb, var, aov=None, out=None, var_out=None, split_emitters=False, **opts):
@@ -1038,41 +1037,7 @@ def denoise_var_device(rgb, var, aov=None, out=None, var_out=None, split_emitter
     `var_out` (None: the filtered variance is not written) var itself.  split_emitters=True
     (rt_denoise_var_emit_device): as denoise_device's.  Runs on the tensor's current stream and
     returns `out` after the work completes."""
-    import torch
-    a = rgb if (rgb.is_contiguous() and rgb.dtype == torch.float32) else \
-        rgb.contiguous().to(torch.float32)
-    h, w = a.shape[:2]
-    for name, t in (("var", var), ("var_out", var_out)):
-        if name == "var_out" and t is None:
-            continue
-        if (t is None or not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous()
-                or tuple(t.shape) != (h, w) or t.device != a.device):
-            raise ValueError(f"denoise_var_device: {name} must be a contiguous float32 tensor of shape "
-                             f"{(h, w)} on rgb's device")
-    aov = aov or {}
-    if split_emitters:
-        e, _keep = _emit_device("denoise_var_device", aov, a)
-    keep = [None if aov.get(k) is None else aov[k].contiguous().to(torch.float32)
-            for k in ("albedo", "normal", "depth")]
-    f = RtAov(*[None if k is None else k.data_ptr() for k in keep], None)
-    o = _denoise_var_opts(has_albedo=split_emitters or keep[0] is not None, **opts)
-    if out is None:
-        out = torch.empty_like(a)
-    elif (out.dtype != torch.float32 or not out.is_contiguous() or out.shape != a.shape
-          or out.device != a.device):
-        raise ValueError("denoise_var_device: out must be a contiguous float32 tensor of rgb's shape "
-                         "on rgb's device")
-    elif out is rgb and a is not rgb:
-        raise ValueError("denoise_var_device: in place needs a contiguous float32 rgb")
-    if split_emitters:
-        check(lib().rt_denoise_var_emit_device(
-            a.data_ptr(), var.data_ptr(), C.byref(f), C.byref(e), w, h, C.byref(o), out.data_ptr(),
-            None if var_out is None else var_out.data_ptr(), a.device.index or 0, _stream_of(a)))
-    else:
-        check(lib().rt_denoise_var_device(a.data_ptr(), var.data_ptr(), C.byref(f), w, h, C.byref(o),
-                                          out.data_ptr(), None if var_out is None else var_out.data_ptr(),
-                                          a.device.index or 0, _stream_of(a)))
-    return out
+    return _denoise_dev(True, rgb, var, aov, out, var_out, split_emitters, opts)
 
 
 def device_count():

@@ -1,5 +1,5 @@
 """The denoisers' split mode (rt_denoise_emit_device, rt_denoise_var_emit_device and their host
-entries; rt_denoise.hip k_dn_prep_emit / k_dnv_prep_emit / k_dn_emit_add) against a numpy
+entries; rt_denoise.hip k_dn_prep<VAR, true> / k_dn_emit_add) against a numpy
 restatement of the definition in include/rt_abi.h / DESIGN.md §15.
 
 The restatement is the definition's own reduction to the parents': with x = rgb - emission

@@ -1,4 +1,4 @@
-"""rt_denoise_var_device (rt_denoise.hip, the k_dnv_* kernels) against a numpy restatement of
+"""rt_denoise_var_device (rt_denoise.hip, the Var instances) against a numpy restatement of
 the pinned variance-guided filter.
 
 The checker below is written from the definition in include/rt_abi.h / DESIGN.md §13, not
