@@ -33,6 +33,11 @@ def _d3(v):
     return _lib.D3(*[float(x) for x in v])
 
 
+def _as_dict(s):
+    """A ctypes structure (RtStats, RtAccumInfo, ...) as {field: value}."""
+    return {f: getattr(s, f) for f, _ in s._fields_}
+
+
 class Tree:
     """A scene under construction (rt_tree).  Handles are plain ints."""
 
@@ -407,7 +412,7 @@ class Scene:
     def info(self):
         i = RtSceneInfo()
         check(lib().rt_scene_info_get(self._p, C.byref(i)))
-        return {f: getattr(i, f) for f, _ in RtSceneInfo._fields_}
+        return _as_dict(i)
 
     def export_bvh(self):
         nn, nr, root = C.c_int32(), C.c_int32(), C.c_uint32()
@@ -527,7 +532,7 @@ class Scene:
             o.trace_cap = tbuf.shape[0]
             o.trace_out = tbuf.ctypes.data
         check(lib().rt_render(self._p, C.byref(c), C.byref(o), out.ctypes.data, C.byref(st)))
-        res = {f: getattr(st, f) for f, _ in RtStats._fields_}
+        res = _as_dict(st)
         if tbuf is not None:
             res["trace"] = tbuf[tbuf[:, 7] >= 0]
         return out, res
@@ -557,7 +562,7 @@ class Scene:
         o = self._opts(seed, device, rank, nranks, path_slots, chunk, profile, stream, mode)
         check(lib().rt_render_device(self._p, C.byref(c), C.byref(o), C.c_void_p(out_ptr),
                                      C.byref(st)))
-        return {f: getattr(st, f) for f, _ in RtStats._fields_}
+        return _as_dict(st)
 
     def render_aov(self, camera, n_samples=1, seed=1, device=0, rank=0, nranks=1, emit=False):
         """Feature buffers of this rank's rows (rt_render_aov): the first hit of the camera
@@ -576,21 +581,29 @@ class Scene:
                "depth": np.zeros((rows, d.width), np.float32),
                "material": np.full((rows, d.width), -1, np.int32)}
         a = RtAov(*[res[k].ctypes.data for k in ("albedo", "normal", "depth", "material")])
-        st = RtStats()
-        c = camera.to_c()
-        o = self._opts(seed, device, rank, nranks, 0, 0, False, None)
+        e = None
         if emit:
             res["emission"] = np.zeros((rows, d.width, 3), np.float32)
             res["surface_albedo"] = np.zeros((rows, d.width, 3), np.float32)
             res["coverage"] = np.zeros((rows, d.width), np.float32)
             e = RtAovEmit(*[res[k].ctypes.data for k in ("emission", "surface_albedo", "coverage")])
-            check(lib().rt_render_aov_emit(self._p, C.byref(c), C.byref(o), n_samples, C.byref(a),
-                                           C.byref(e), C.byref(st)))
-        else:
-            check(lib().rt_render_aov(self._p, C.byref(c), C.byref(o), n_samples, C.byref(a),
-                                      C.byref(st)))
-        res["stats"] = {f: getattr(st, f) for f, _ in RtStats._fields_}
+        o = self._opts(seed, device, rank, nranks, 0, 0, False, None)
+        res["stats"] = self._aov(camera, o, n_samples, a, e, False)
         return res
+
+    def _aov(self, camera, o, n_samples, a, e, device):
+        """One of the four rt_render_aov entries: the emit ones with an RtAovEmit `e`, the
+        _device ones with `device` -> the stats dict."""
+        st = RtStats()
+        c = camera.to_c()
+        L = lib()
+        if e is None:
+            fn, args = (L.rt_render_aov_device if device else L.rt_render_aov), (C.byref(a),)
+        else:
+            fn, args = ((L.rt_render_aov_emit_device if device else L.rt_render_aov_emit),
+                        (C.byref(a), C.byref(e)))
+        check(fn(self._p, C.byref(c), C.byref(o), n_samples, *args, C.byref(st)))
+        return _as_dict(st)
 
     def render_aov_device(self, camera, albedo=None, normal=None, depth=None, material=None,
                           n_samples=1, seed=1, device=0, rank=0, nranks=1, stream=None,
@@ -599,18 +612,11 @@ class Scene:
         tensors' .data_ptr(); None = not wanted) on `stream`.  With any of emission /
         surface_albedo / coverage the call is rt_render_aov_emit_device.  Returns the stats
         dict."""
-        a = RtAov(albedo, normal, depth, material)
-        st = RtStats()
-        c = camera.to_c()
-        o = self._opts(seed, device, rank, nranks, 0, 0, False, stream)
+        e = None
         if emission is not None or surface_albedo is not None or coverage is not None:
             e = RtAovEmit(emission, surface_albedo, coverage)
-            check(lib().rt_render_aov_emit_device(self._p, C.byref(c), C.byref(o), n_samples,
-                                                  C.byref(a), C.byref(e), C.byref(st)))
-        else:
-            check(lib().rt_render_aov_device(self._p, C.byref(c), C.byref(o), n_samples, C.byref(a),
-                                             C.byref(st)))
-        return {f: getattr(st, f) for f, _ in RtStats._fields_}
+        o = self._opts(seed, device, rank, nranks, 0, 0, False, stream)
+        return self._aov(camera, o, n_samples, RtAov(albedo, normal, depth, material), e, True)
 
     def accumulator(self, camera, max_passes=0, device=0, rank=0, nranks=1, path_slots=0, chunk=0,
                     profile=False, stream=None, mode="auto", progress_slices=0):
@@ -668,7 +674,7 @@ class Accumulator:
         """One pass with render seed `seed` (rt_accum_add) -> the pass's stats dict."""
         st = RtStats()
         check(lib().rt_accum_add(self._h(), seed, C.byref(st)))
-        return {f: getattr(st, f) for f, _ in RtStats._fields_}
+        return _as_dict(st)
 
     def resolve(self):
         """(rgb float32 [rows, W, 3]: the mean of all passes, var float32 [rows, W]: the
@@ -712,7 +718,7 @@ class Accumulator:
         rms_std_error, mean_luminance, rel_error."""
         i = RtAccumInfo()
         check(lib().rt_accum_info_get(self._h(), C.byref(i)))
-        return {f: getattr(i, f) for f, _ in RtAccumInfo._fields_}
+        return _as_dict(i)
 
     def reset(self):
         check(lib().rt_accum_reset(self._h()))
@@ -760,7 +766,7 @@ class Accumulator:
         gets exactly the samples add(seed) would give it.  Returns the pass's stats dict."""
         st = RtStats()
         check(lib().rt_accum_add_active(self._h(), seed, C.byref(st)))
-        return {f: getattr(st, f) for f, _ in RtStats._fields_}
+        return _as_dict(st)
 
     def counts(self):
         """int32 [rows, W]: the passes every pixel has taken (rt_accum_counts)."""
@@ -783,7 +789,7 @@ class Accumulator:
         active_tiles."""
         i = _lib.RtAdaptInfo()
         check(lib().rt_accum_adapt_info(self._h(), C.byref(i)))
-        return {f: getattr(i, f) for f, _ in _lib.RtAdaptInfo._fields_}
+        return _as_dict(i)
 
     def render_adaptive(self, rel_error, max_passes, seed=1, **opts):
         """select() / add_active() until the selection is empty or the accumulator holds
@@ -809,7 +815,7 @@ def _multi(scene, camera, devices, out_ptr, seed, path_slots, chunk, profile, mo
     fn = lib().rt_render_multi_device if out_ptr[1] else lib().rt_render_multi
     check(fn(scene._p, C.byref(c), C.byref(o), devs, len(devices), C.c_void_p(out_ptr[0]),
              C.byref(st)))
-    return {f: getattr(st, f) for f, _ in RtStats._fields_}
+    return _as_dict(st)
 
 
 def demo_scene(name, seed=1, asset_dir=None):

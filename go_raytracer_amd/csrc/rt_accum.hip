@@ -15,13 +15,14 @@
 //   count    u32  passes the pixel took; written from the first active-pixel pass on (§14): an
 //                 accumulator that took whole passes only is *uniform* and never touches it
 //   map      u32  the current selection: the active local pixels, ascending
-// k_accum_fold     one pass -> state          (one pixel per lane, 256-thread blocks)
-// k_accum_resolve  state -> mean RGB and the variance of the mean luminance
-// k_accum_info1/2  state -> {sum of variances, sum of means, finite pixels, other pixels}:
-//                  a two-stage block reduction in fp64, fixed tree order, no atomics
-// Per-pixel forms, used once a pass covered a part of the pixels:
-// k_accum_fold_px / k_accum_resolve_px / k_accum_info1_px  the same with count[p] for `passes`,
-//                  the fold through the pass's pixel map
+// Each of the next three is one text in two instances.  PX = false, the uniform accumulator:
+// every pixel has the pass count the launch carries, and count and map are not even arguments.
+// PX = true, once a pass covered a part of the pixels: count[p] passes.
+// k_accum_fold<PX>     one pass -> state (one pixel per lane, 256-thread blocks); PX: the
+//                      pass's pixel v updates pixel map[v] of the share
+// k_accum_resolve<PX>  state -> mean RGB and the variance of the mean luminance
+// k_accum_info1<PX>/2  state -> {sum of variances, sum of means, finite pixels, other pixels}:
+//                      a two-stage block reduction in fp64, fixed tree order, no atomics
 // k_accum_tiles    state -> per tile: the error figure e_T and the active flag (one tile per lane)
 // k_active_count / k_active_scan / k_active_scatter  active pixels -> the sorted map: ballot
 //                  counts per block, an exclusive scan by one block, a scatter; no atomics
@@ -33,6 +34,7 @@
 #include <algorithm>
 #include <cmath>
 #include <mutex>
+#include <type_traits>
 
 #include "rt_hip_util.h"
 #include "rt_resolve.h"
@@ -55,39 +57,86 @@ RT_D double var_of_mean(double m2, uint32_t n) {
   return n >= 2u ? m2 / ((double)(n - 1u) * (double)n) : 0.0;
 }
 
-// One finished pass (P's accum / csum records / side / pflags, as k_resolve reads them)
-// into the accumulator; n = passes including this one, scale = pixel_samples_scale.
-__global__ __launch_bounds__(256) void k_accum_fold(Params P, AccumPlanes A, double scale, uint32_t n) {
-  const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
-  if (lp >= P.npix) return;
-  const uint32_t f = P.pflags[lp];
-  unsigned long long cs[3] = {0ull, 0ull, 0ull};
-  chunk_record_sums(P, lp, cs);
-  double c[3];
-  for (int ch = 0; ch < 3; ++ch) {
-    const size_t i = (size_t)ch * P.npix + lp;
-    const unsigned long long sum = P.accum[i] + cs[ch];
-    const double side = P.side[i];
-    A.sum[i] += sum;
-    A.side[i] += side;
-    c[ch] = flagged_channel(f, ch, (long long)sum, side, scale);
-  }
-  A.flags[lp] |= f;
-  const double y = luminance(c[0], c[1], c[2]);
-  double mean = A.mean[lp];
-  const double d = y - mean;
-  mean += d / (double)n;
-  A.m2[lp] += d * (y - mean);
-  A.mean[lp] = mean;
+// Where a kernel's pass counts come from: the launch's n for every pixel, or per pixel
+template <bool PX>
+struct Passes {
+  uint32_t n;  // k_accum_fold: including the pass being folded
+};
+template <>
+struct Passes<true> {
+  uint32_t npix;        // pixels of the share
+  uint32_t* count;      // [npix]
+  const uint32_t* map;  // k_accum_fold: the pass's pixels (null: a whole pass, the identity)
+};
+template <bool PX>
+RT_D uint32_t passes_of(const Passes<PX>& c, uint32_t p) {
+  if constexpr (PX) return c.count[p];
+  else return c.n;
 }
 
-// scale_n = pixel_samples_scale / passes (0 with no pass: the image is zeros)
-__global__ __launch_bounds__(256) void k_accum_resolve(AccumPlanes A, uint32_t npix, double scale_n,
-                                                       uint32_t n, float* rgb, float* var) {
+// Welford's update of pixel p with the luminance y of its n-th pass
+RT_D void welford_add(const AccumPlanes& A, uint32_t p, double y, uint32_t n) {
+  double mean = A.mean[p];
+  const double d = y - mean;
+  mean += d / (double)n;
+  A.m2[p] += d * (y - mean);
+  A.mean[p] = mean;
+}
+
+// Pixel p of n passes into {sum of variances, sum of means, pixels} if its variance of the mean
+// and its Welford mean are finite; else false, and nothing is added
+RT_D bool add_finite(const AccumPlanes& A, uint32_t p, uint32_t n, double& sv, double& sm, double& k) {
+  const double var = var_of_mean(A.m2[p], n), mean = A.mean[p];
+  if (!(isfinite(var) && isfinite(mean))) return false;
+  sv += var;
+  sm += mean;
+  k += 1.0;
+  return true;
+}
+
+// One finished pass (P's accum / csum records / side / pflags, as k_resolve reads them) into the
+// accumulator; scale = pixel_samples_scale.  The pass's sums are read at the pass's own pixel v;
+// PX: the state is updated at p = map[v] with the pixel's own pass count
+template <bool PX>
+__global__ __launch_bounds__(256) void k_accum_fold(Params P, AccumPlanes A, double scale, Passes<PX> c) {
+  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= P.npix) return;
+  uint32_t p = v, npix = P.npix;
+  if constexpr (PX) {
+    p = c.map ? c.map[v] : v;
+    npix = c.npix;
+  }
+  const uint32_t f = P.pflags[v];
+  unsigned long long cs[3] = {0ull, 0ull, 0ull};
+  chunk_record_sums(P, v, cs);
+  double y[3];
+  for (int ch = 0; ch < 3; ++ch) {
+    const size_t i = (size_t)ch * P.npix + v, k = (size_t)ch * npix + p;
+    const unsigned long long sum = P.accum[i] + cs[ch];
+    const double side = P.side[i];
+    A.sum[k] += sum;
+    A.side[k] += side;
+    y[ch] = flagged_channel(f, ch, (long long)sum, side, scale);
+  }
+  A.flags[p] |= f;
+  uint32_t n;
+  if constexpr (PX) c.count[p] = n = c.count[p] + 1u;
+  else n = c.n;
+  welford_add(A, p, luminance(y[0], y[1], y[2]), n);
+}
+
+// PX: scale = pixel_samples_scale, and a pixel without a pass resolves to zeros; else scale is
+// that over the passes, divided on the host (0 with no pass: the image is zeros)
+template <bool PX>
+__global__ __launch_bounds__(256) void k_accum_resolve(AccumPlanes A, uint32_t npix, double scale, Passes<PX> c,
+                                                       float* rgb, float* var) {
   const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
   if (lp >= npix) return;
+  const uint32_t n = passes_of(c, lp);
   if (rgb) {
     const uint32_t f = A.flags[lp];
+    double scale_n = scale;
+    if constexpr (PX) scale_n = n ? scale / (double)n : 0.0;
     for (int ch = 0; ch < 3; ++ch) {
       const size_t i = (size_t)ch * npix + lp;
       rgb[3 * (size_t)lp + ch] = (float)flagged_channel(f, ch, (long long)A.sum[i], A.side[i], scale_n);
@@ -112,20 +161,13 @@ RT_D void block_sum4(double v[4], double (*red)[256]) {
 }
 
 // stage 1: thread t of block b sums pixels b * 256 + t, + gridDim.x * 256, ... in order
-__global__ __launch_bounds__(256) void k_accum_info1(AccumPlanes A, uint32_t npix, uint32_t n, double* part) {
+template <bool PX>
+__global__ __launch_bounds__(256) void k_accum_info1(AccumPlanes A, uint32_t npix, Passes<PX> c, double* part) {
   __shared__ double red[4][256];
   double v[4] = {0.0, 0.0, 0.0, 0.0};
   const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x; lp < npix; lp += stride) {
-    const double var = var_of_mean(A.m2[lp], n), mean = A.mean[lp];
-    if (isfinite(var) && isfinite(mean)) {
-      v[0] += var;
-      v[1] += mean;
-      v[2] += 1.0;
-    } else {
-      v[3] += 1.0;
-    }
-  }
+  for (uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x; lp < npix; lp += stride)
+    if (!add_finite(A, lp, passes_of(c, lp), v[0], v[1], v[2])) v[3] += 1.0;
   block_sum4(v, red);
   if (threadIdx.x == 0)
     for (int k = 0; k < 4; ++k) part[4 * blockIdx.x + k] = v[k];
@@ -148,75 +190,8 @@ __global__ __launch_bounds__(256) void k_accum_fill(uint32_t* v, uint32_t n, uin
   if (i < n) v[i] = x;
 }
 
-// k_accum_fold for a pass over the pixels map[0 .. P.npix) of the npix-pixel share (map null:
-// a whole pass, the identity): the pass's sums are read at the pass's own pixel v, the state
-// is updated at p = map[v] with the pixel's own pass count
-__global__ __launch_bounds__(256) void k_accum_fold_px(Params P, AccumPlanes A, double scale, uint32_t npix,
-                                                       uint32_t* count, const uint32_t* map) {
-  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= P.npix) return;
-  const uint32_t p = map ? map[v] : v;
-  const uint32_t f = P.pflags[v];
-  unsigned long long cs[3] = {0ull, 0ull, 0ull};
-  chunk_record_sums(P, v, cs);
-  double c[3];
-  for (int ch = 0; ch < 3; ++ch) {
-    const size_t i = (size_t)ch * P.npix + v, k = (size_t)ch * npix + p;
-    const unsigned long long sum = P.accum[i] + cs[ch];
-    const double side = P.side[i];
-    A.sum[k] += sum;
-    A.side[k] += side;
-    c[ch] = flagged_channel(f, ch, (long long)sum, side, scale);
-  }
-  A.flags[p] |= f;
-  const uint32_t n = count[p] + 1u;
-  count[p] = n;
-  const double y = luminance(c[0], c[1], c[2]);
-  double mean = A.mean[p];
-  const double d = y - mean;
-  mean += d / (double)n;
-  A.m2[p] += d * (y - mean);
-  A.mean[p] = mean;
-}
-
-// scale = pixel_samples_scale; a pixel without a pass resolves to zeros
-__global__ __launch_bounds__(256) void k_accum_resolve_px(AccumPlanes A, uint32_t npix, double scale,
-                                                          const uint32_t* count, float* rgb, float* var) {
-  const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
-  if (lp >= npix) return;
-  const uint32_t n = count[lp];
-  if (rgb) {
-    const uint32_t f = A.flags[lp];
-    const double scale_n = n ? scale / (double)n : 0.0;
-    for (int ch = 0; ch < 3; ++ch) {
-      const size_t i = (size_t)ch * npix + lp;
-      rgb[3 * (size_t)lp + ch] = (float)flagged_channel(f, ch, (long long)A.sum[i], A.side[i], scale_n);
-    }
-  }
-  if (var) var[lp] = (float)var_of_mean(A.m2[lp], n);
-}
-
-__global__ __launch_bounds__(256) void k_accum_info1_px(AccumPlanes A, uint32_t npix, const uint32_t* count,
-                                                        double* part) {
-  __shared__ double red[4][256];
-  double v[4] = {0.0, 0.0, 0.0, 0.0};
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x; lp < npix; lp += stride) {
-    const double var = var_of_mean(A.m2[lp], count[lp]), mean = A.mean[lp];
-    if (isfinite(var) && isfinite(mean)) {
-      v[0] += var;
-      v[1] += mean;
-      v[2] += 1.0;
-    } else {
-      v[3] += 1.0;
-    }
-  }
-  block_sum4(v, red);
-  if (threadIdx.x == 0)
-    for (int k = 0; k < 4; ++k) part[4 * blockIdx.x + k] = v[k];
-}
-
 // {min, max, sum} of v[0 .. n) by one block: thread t takes t, t + 256, ..., then a fixed tree
+// (block_sum4's tree with one operator per row: a shared form would be longer than the two)
 __global__ __launch_bounds__(256) void k_count_stats(const uint32_t* v, uint32_t n, unsigned long long* out) {
   __shared__ unsigned long long red[3][256];
   unsigned long long lo = ~0ull, hi = 0ull, sum = 0ull;
@@ -265,12 +240,7 @@ RT_D float tile_error(const AccumPlanes& A, const uint32_t* count, uint32_t pass
       const uint32_t lp = r * g.W + c;
       const uint32_t n = count ? count[lp] : passes;
       yg |= n < min_passes;
-      const double var = var_of_mean(A.m2[lp], n), mean = A.mean[lp];
-      if (isfinite(var) && isfinite(mean)) {
-        sv += var;
-        sm += mean;
-        k += 1.0;
-      }
+      add_finite(A, lp, n, sv, sm, k);
     }
   *young = yg;
   return k > 0.0 ? (float)(sqrt(sv / k) / (fmax(sm / k, 0.0) + lum_floor)) : 0.0f;
@@ -376,7 +346,7 @@ struct rt_accum {
   uint32_t* map = nullptr;    // [npix], the selection's sel_n active pixels
   uint32_t* scan = nullptr;   // [ceil(npix / 256) + 1] block counts, then their prefix sums and the total
   unsigned long long* red = nullptr;  // k_count_stats' results: [0..3) of count, [4..7) of the tile flags
-  bool per_pixel = false;     // a pass covered a part of the pixels: count holds, the _px kernels run
+  bool per_pixel = false;     // a pass covered a part of the pixels: count holds, the PX instances run
   bool sel_valid = false;     // a selection was made since the last pass or reset
   bool sel_tiles = false;     // ... by rt_accum_select (red[4..7) describes its tiles)
   uint32_t sel_n = 0;         // active pixels of the last selection
@@ -387,7 +357,10 @@ struct rt_accum {
 namespace rt {
 namespace {
 
-int accum_stream(rt_accum* a, hipStream_t* out) {
+// Every entry's prologue once a->mu is held (DeviceGuard in the caller's scope): makes the
+// accumulator's device current, -> the caller's stream or the accumulator's own
+int accum_device(rt_accum* a, hipStream_t* out) {
+  HIP_OK(hipSetDevice(a->opts.device));
   *out = (hipStream_t)a->opts.stream;
   if (*out) return RT_OK;
   if (!a->own_stream) HIP_OK(hipStreamCreateWithFlags(&a->own_stream, hipStreamNonBlocking));
@@ -395,20 +368,23 @@ int accum_stream(rt_accum* a, hipStream_t* out) {
   return RT_OK;
 }
 
+// the PX instances' counts (a->per_pixel); uniform launches carry Passes<false>{passes}
+Passes<true> px_counts(const rt_accum* a, const uint32_t* map = nullptr) { return {a->npix, a->count, map}; }
+
 // render_impl's sink: the pass is complete on `stream` up to the resolve
 int fold_pass(void* ctx, const Params& p, double scale, hipStream_t stream) {
   rt_accum* a = (rt_accum*)ctx;
   const uint32_t want = a->pass_map ? a->sel_n : a->npix;
   if (p.npix != want) return set_error(RT_ERR_INVALID, "rt_accum_add: the pass has %u pixels, the accumulator expects %u", p.npix, want);
   if (!a->per_pixel && !a->pass_map) {  // uniform: every pixel has taken every pass
-    hipLaunchKernelGGL(k_accum_fold, dim3((a->npix + 255) / 256), dim3(256), 0, stream, p, a->A, scale,
-                       (uint32_t)a->passes + 1u);
+    hipLaunchKernelGGL(k_accum_fold<false>, dim3((a->npix + 255) / 256), dim3(256), 0, stream, p, a->A, scale,
+                       Passes<false>{(uint32_t)a->passes + 1u});
   } else {
     if (!a->per_pixel)  // the first active pass: every pixel has `passes` so far
       hipLaunchKernelGGL(k_accum_fill, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->count, a->npix,
                          (uint32_t)a->passes);
-    hipLaunchKernelGGL(k_accum_fold_px, dim3((p.npix + 255) / 256), dim3(256), 0, stream, p, a->A, scale,
-                       a->npix, a->count, a->pass_map);
+    hipLaunchKernelGGL(k_accum_fold<true>, dim3((p.npix + 255) / 256), dim3(256), 0, stream, p, a->A, scale,
+                       px_counts(a, a->pass_map));
   }
   HIP_OK(hipGetLastError());
   return RT_OK;
@@ -439,8 +415,16 @@ TileGrid tile_grid(const rt_accum* a, int32_t tile) {
   return g;
 }
 
+// a selection of n pixels stands
+int selected(rt_accum* a, uint32_t n, uint64_t* n_active_pixels) {
+  a->sel_n = n;
+  a->sel_valid = true;
+  if (n_active_pixels) *n_active_pixels = n;
+  return RT_OK;
+}
+
 // the active pixels of `src` -> a->map, ascending; their number -> a->sel_n (one 4-byte read-back)
-int compact_active(rt_accum* a, const ActiveSrc& src, hipStream_t stream) {
+int compact_active(rt_accum* a, const ActiveSrc& src, hipStream_t stream, uint64_t* n_active_pixels) {
   const uint32_t nb = (a->npix + 255u) / 256u;
   hipLaunchKernelGGL(k_active_count, dim3(nb), dim3(256), 0, stream, src, a->npix, a->scan);
   hipLaunchKernelGGL(k_active_scan, dim3(1), dim3(256), 0, stream, a->scan, nb);
@@ -450,15 +434,7 @@ int compact_active(rt_accum* a, const ActiveSrc& src, hipStream_t stream) {
   HIP_OK(hipMemcpyAsync(&n, a->scan + nb, sizeof n, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
   if (n > a->npix) return set_error(RT_ERR_DEVICE, "internal: %u active pixels of %u", n, a->npix);
-  a->sel_n = n;
-  a->sel_valid = true;
-  return RT_OK;
-}
-
-// device and stream of a call on `a` (a->mu held, DeviceGuard in the caller's scope)
-int accum_device(rt_accum* a, hipStream_t* stream) {
-  HIP_OK(hipSetDevice(a->opts.device));
-  return accum_stream(a, stream);
+  return selected(a, n, n_active_pixels);
 }
 
 // {min, max, sum} of the per-pixel counts -> h (a->per_pixel)
@@ -494,6 +470,31 @@ int accum_counts(rt_accum* a, int32_t* out, bool host) {
   return RT_OK;
 }
 
+// The accumulator's one allocation, in order: a's pointers into the buffer at `base` and
+// state_bytes -> the buffer's size (base null: only the size is meant)
+size_t carve(rt_accum* a, void* base) {
+  const size_t n = std::max<size_t>(a->npix, 1);
+  size_t off = 0;
+  auto take = [&](auto*& p, size_t count) {  // the next `count` elements of p's type
+    p = (std::remove_reference_t<decltype(p)>)((uintptr_t)base + off);
+    off += count * sizeof *p;
+  };
+  take(a->A.sum, 3 * n);
+  take(a->A.side, 3 * n);
+  take(a->A.mean, n);
+  take(a->A.m2, n);
+  a->state_bytes = off;  // what rt_accum_reset clears, with the flags
+  take(a->part, (size_t)(kInfoBlocks + 1) * 4);
+  take(a->red, 8);
+  take(a->A.flags, n);
+  take(a->stage_rgb, 3 * n);  // the selection's tile flags or mask bytes pass through it too
+  take(a->stage_var, n);      // ... and the tile errors
+  take(a->count, n);
+  take(a->map, n);
+  take(a->scan, (n + 255) / 256 + 1);
+  return off;
+}
+
 void free_accum(rt_accum* a) {
   DeviceGuard dg;
   if (a->buf || a->own_stream) (void)hipSetDevice(a->opts.device);
@@ -507,19 +508,18 @@ int accum_resolve(rt_accum* a, float* rgb, float* var, bool host) {
   std::lock_guard<std::mutex> lk(a->mu);
   if (a->npix == 0 || (!rgb && !var)) return RT_OK;
   DeviceGuard dg;
-  HIP_OK(hipSetDevice(a->opts.device));
   hipStream_t stream;
   int rc;
-  if ((rc = accum_stream(a, &stream))) return rc;
+  if ((rc = accum_device(a, &stream))) return rc;
   float* drgb = !rgb ? nullptr : host ? a->stage_rgb : rgb;
   float* dvar = !var ? nullptr : host ? a->stage_var : var;
   const double scale_n = a->passes > 0 ? a->cd.pixel_samples_scale / (double)a->passes : 0.0;
   if (a->per_pixel)
-    hipLaunchKernelGGL(k_accum_resolve_px, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->A, a->npix,
-                       a->cd.pixel_samples_scale, a->count, drgb, dvar);
+    hipLaunchKernelGGL(k_accum_resolve<true>, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->A, a->npix,
+                       a->cd.pixel_samples_scale, px_counts(a), drgb, dvar);
   else
-    hipLaunchKernelGGL(k_accum_resolve, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->A, a->npix,
-                       scale_n, (uint32_t)a->passes, drgb, dvar);
+    hipLaunchKernelGGL(k_accum_resolve<false>, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->A, a->npix,
+                       scale_n, Passes<false>{(uint32_t)a->passes}, drgb, dvar);
   HIP_OK(hipGetLastError());
   if (host && rgb)
     HIP_OK(hipMemcpyAsync(rgb, drgb, 3 * (size_t)a->npix * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -527,6 +527,35 @@ int accum_resolve(rt_accum* a, float* rgb, float* var, bool host) {
     HIP_OK(hipMemcpyAsync(var, dvar, (size_t)a->npix * sizeof(float), hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
   return RT_OK;
+}
+
+// One pass as `who`: rt_accum_add's whole pass, or (active) rt_accum_add_active's over the selection
+int accum_add(rt_accum* a, const char* who, bool active, uint64_t seed, rt_stats* stats) {
+  if (!a) return set_error(RT_ERR_INVALID, "%s: null accumulator", who);
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (active && !a->sel_valid)
+    return set_error(RT_ERR_INVALID, "%s: no selection since the last pass or reset", who);
+  if (active && a->sel_n == 0) {  // nothing to render: no pass is counted
+    if (stats) memset(stats, 0, sizeof *stats);
+    return RT_OK;
+  }
+  if (a->passes >= a->max_passes)
+    return set_error(RT_ERR_INVALID, "%s: the accumulator holds its %d passes", who, a->max_passes);
+  rt_render_opts o = a->opts;
+  o.seed = seed;
+  const PassSink sink = {(uint32_t)a->max_passes, fold_pass, a};
+  // every pixel active: the plain whole pass (the same bits, the grouped chunk order)
+  const bool part = active && a->sel_n < a->npix;
+  const PixelMap pm = {a->map, a->sel_n};
+  a->pass_map = part ? a->map : nullptr;
+  const int rc = render_pass(a->scene, &a->cam, &o, stats, &sink, part ? &pm : nullptr);
+  a->pass_map = nullptr;
+  if (rc == RT_OK) {
+    ++a->passes;
+    if (part) a->per_pixel = true;
+    a->sel_valid = false;  // a selection describes the state it was made from
+  }
+  return rc;
 }
 
 }  // namespace
@@ -589,14 +618,7 @@ int rt_accum_create(rt_scene* s, const rt_camera* cam, const rt_render_opts* opt
   a->ss = (uint32_t)ss;
   a->W = (uint32_t)cd.width;
   a->rows = a->W ? a->npix / a->W : 0u;
-  const size_t n = std::max<size_t>(a->npix, 1);
-  // sum | side | mean | m2 (f64 / u64), the info partials and the count statistics, then flags,
-  // the staging (4 B; the selection's tile flags or mask bytes and tile errors pass through it
-  // too), the counts, the pixel map and the scan scratch
-  a->state_bytes = n * (3 * 8 + 3 * 8 + 8 + 8);
-  const size_t part_bytes = (size_t)(kInfoBlocks + 1) * 4 * sizeof(double) + 8 * sizeof(unsigned long long);
-  const size_t scan_n = (n + 255) / 256 + 1;
-  const size_t total = a->state_bytes + part_bytes + n * 4 + n * 16 + n * 4 + n * 4 + scan_n * 4;
+  const size_t total = carve(a, nullptr);
   DeviceGuard dg;
   hipError_t e = hipSetDevice(o.device);
   if (e == hipSuccess) e = hipMalloc(&a->buf, total);
@@ -607,19 +629,7 @@ int rt_accum_create(rt_scene* s, const rt_camera* cam, const rt_render_opts* opt
     return set_error(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_DEVICE, "rt_accum_create: %zu bytes: %s", total,
                      hipGetErrorString(e));
   }
-  char* b = (char*)a->buf;
-  a->A.sum = (unsigned long long*)b;
-  a->A.side = (double*)(b + n * 24);
-  a->A.mean = (double*)(b + n * 48);
-  a->A.m2 = (double*)(b + n * 56);
-  a->part = (double*)(b + a->state_bytes);
-  a->A.flags = (uint32_t*)(b + a->state_bytes + part_bytes);
-  a->stage_rgb = (float*)(b + a->state_bytes + part_bytes + n * 4);
-  a->stage_var = a->stage_rgb + 3 * n;
-  a->red = (unsigned long long*)(a->part + (size_t)(kInfoBlocks + 1) * 4);
-  a->count = (uint32_t*)(a->stage_var + n);
-  a->map = a->count + n;
-  a->scan = a->map + n;
+  carve(a, a->buf);
   {
     std::lock_guard<std::mutex> lk(s->s.mu);
     s->s.accums.push_back(a);
@@ -648,10 +658,9 @@ int rt_accum_reset(rt_accum* a) {
   if (!a) return set_error(RT_ERR_INVALID, "rt_accum_reset: null accumulator");
   std::lock_guard<std::mutex> lk(a->mu);
   DeviceGuard dg;
-  HIP_OK(hipSetDevice(a->opts.device));
   hipStream_t stream;
   int rc;
-  if ((rc = accum_stream(a, &stream))) return rc;
+  if ((rc = accum_device(a, &stream))) return rc;
   HIP_OK(hipMemsetAsync(a->buf, 0, a->state_bytes, stream));
   HIP_OK(hipMemsetAsync(a->A.flags, 0, std::max<size_t>(a->npix, 1) * sizeof(uint32_t), stream));
   HIP_OK(hipStreamSynchronize(stream));
@@ -663,50 +672,11 @@ int rt_accum_reset(rt_accum* a) {
 }
 
 int rt_accum_add(rt_accum* a, uint64_t seed, rt_stats* stats) {
-  using namespace rt;
-  if (!a) return set_error(RT_ERR_INVALID, "rt_accum_add: null accumulator");
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (a->passes >= a->max_passes)
-    return set_error(RT_ERR_INVALID, "rt_accum_add: the accumulator holds its %d passes", a->max_passes);
-  rt_render_opts o = a->opts;
-  o.seed = seed;
-  const PassSink sink = {(uint32_t)a->max_passes, fold_pass, a};
-  a->pass_map = nullptr;
-  const int rc = render_pass(a->scene, &a->cam, &o, stats, &sink);
-  if (rc == RT_OK) {
-    ++a->passes;
-    a->sel_valid = false;  // a selection describes the state it was made from
-  }
-  return rc;
+  return rt::accum_add(a, "rt_accum_add", false, seed, stats);
 }
 
 int rt_accum_add_active(rt_accum* a, uint64_t seed, rt_stats* stats) {
-  using namespace rt;
-  if (!a) return set_error(RT_ERR_INVALID, "rt_accum_add_active: null accumulator");
-  std::lock_guard<std::mutex> lk(a->mu);
-  if (!a->sel_valid)
-    return set_error(RT_ERR_INVALID, "rt_accum_add_active: no selection since the last pass or reset");
-  if (a->sel_n == 0) {  // nothing to render: no pass is counted
-    if (stats) memset(stats, 0, sizeof *stats);
-    return RT_OK;
-  }
-  if (a->passes >= a->max_passes)
-    return set_error(RT_ERR_INVALID, "rt_accum_add_active: the accumulator holds its %d passes", a->max_passes);
-  rt_render_opts o = a->opts;
-  o.seed = seed;
-  const PassSink sink = {(uint32_t)a->max_passes, fold_pass, a};
-  // every pixel active: the plain whole pass (the same bits, the grouped chunk order)
-  const bool part = a->sel_n < a->npix;
-  const PixelMap pm = {a->map, a->sel_n};
-  a->pass_map = part ? a->map : nullptr;
-  const int rc = render_pass(a->scene, &a->cam, &o, stats, &sink, part ? &pm : nullptr);
-  a->pass_map = nullptr;
-  if (rc == RT_OK) {
-    ++a->passes;
-    if (part) a->per_pixel = true;
-    a->sel_valid = false;  // consumed
-  }
-  return rc;
+  return rt::accum_add(a, "rt_accum_add_active", true, seed, stats);
 }
 
 int rt_accum_select(rt_accum* a, const rt_adapt_opts* opts, uint64_t* n_active_pixels) {
@@ -720,10 +690,7 @@ int rt_accum_select(rt_accum* a, const rt_adapt_opts* opts, uint64_t* n_active_p
   if (a->npix == 0) {
     a->sel_tiles = true;
     a->n_tiles = 0;
-    a->sel_n = 0;
-    a->sel_valid = true;
-    if (n_active_pixels) *n_active_pixels = 0;
-    return RT_OK;
+    return selected(a, 0, n_active_pixels);
   }
   DeviceGuard dg;
   hipStream_t stream;
@@ -739,10 +706,9 @@ int rt_accum_select(rt_accum* a, const rt_adapt_opts* opts, uint64_t* n_active_p
   hipLaunchKernelGGL(k_count_stats, dim3(1), dim3(256), 0, stream, flag, nt, a->red + 4);
   HIP_OK(hipGetLastError());
   const ActiveSrc src = {flag, nullptr, g};
-  if ((rc = compact_active(a, src, stream))) return rc;
+  if ((rc = compact_active(a, src, stream, n_active_pixels))) return rc;
   a->sel_tiles = true;
   a->n_tiles = (int32_t)nt;
-  if (n_active_pixels) *n_active_pixels = a->sel_n;
   return RT_OK;
 }
 
@@ -753,12 +719,7 @@ int rt_accum_set_active(rt_accum* a, const uint8_t* mask_host, uint64_t* n_activ
   std::lock_guard<std::mutex> lk(a->mu);
   a->sel_tiles = false;
   a->n_tiles = 0;
-  if (a->npix == 0) {
-    a->sel_n = 0;
-    a->sel_valid = true;
-    if (n_active_pixels) *n_active_pixels = 0;
-    return RT_OK;
-  }
+  if (a->npix == 0) return selected(a, 0, n_active_pixels);
   DeviceGuard dg;
   hipStream_t stream;
   int rc;
@@ -768,9 +729,7 @@ int rt_accum_set_active(rt_accum* a, const uint8_t* mask_host, uint64_t* n_activ
   uint8_t* mask = (uint8_t*)a->stage_rgb;
   HIP_OK(hipMemcpyAsync(mask, mask_host, a->npix, hipMemcpyHostToDevice, stream));
   const ActiveSrc src = {nullptr, mask, tile_grid(a, 1)};
-  if ((rc = compact_active(a, src, stream))) return rc;
-  if (n_active_pixels) *n_active_pixels = a->sel_n;
-  return RT_OK;
+  return compact_active(a, src, stream, n_active_pixels);
 }
 
 int rt_accum_counts(rt_accum* a, int32_t* counts_host) { return rt::accum_counts(a, counts_host, true); }
@@ -850,16 +809,16 @@ int rt_accum_info_get(rt_accum* a, rt_accum_info* out) {
   out->samples_per_pixel = (uint64_t)a->ss * (uint64_t)a->passes;
   if (a->npix == 0) return RT_OK;
   DeviceGuard dg;
-  HIP_OK(hipSetDevice(a->opts.device));
   hipStream_t stream;
   int rc;
-  if ((rc = accum_stream(a, &stream))) return rc;
+  if ((rc = accum_device(a, &stream))) return rc;
   const uint32_t nb = std::min<uint32_t>((a->npix + 255u) / 256u, (uint32_t)kInfoBlocks);
   double* res = a->part + 4 * (size_t)kInfoBlocks;
   if (a->per_pixel)
-    hipLaunchKernelGGL(k_accum_info1_px, dim3(nb), dim3(256), 0, stream, a->A, a->npix, a->count, a->part);
+    hipLaunchKernelGGL(k_accum_info1<true>, dim3(nb), dim3(256), 0, stream, a->A, a->npix, px_counts(a), a->part);
   else
-    hipLaunchKernelGGL(k_accum_info1, dim3(nb), dim3(256), 0, stream, a->A, a->npix, (uint32_t)a->passes, a->part);
+    hipLaunchKernelGGL(k_accum_info1<false>, dim3(nb), dim3(256), 0, stream, a->A, a->npix,
+                       Passes<false>{(uint32_t)a->passes}, a->part);
   hipLaunchKernelGGL(k_accum_info2, dim3(1), dim3(256), 0, stream, a->part, nb, res);
   HIP_OK(hipGetLastError());
   double h[4];

@@ -196,6 +196,28 @@ def test_whole_pass_after_active_passes(rt, cornell):
     print("var: largest error / bound", worst)
 
 
+def test_whole_passes_stay_uniform(cornell):
+    """After three whole passes counts() is 3 everywhere and adapt_info() has min = max = 3
+    (the uniform accumulator answers without per-pixel counts); a pass over a selection of
+    every pixel is the whole pass: set_active(all) + add_active(4) resolves to the bits of
+    add(4), and the counts stay uniform."""
+    sc, cam, _ = cornell
+    with sc.accumulator(cam, max_passes=8) as acc, sc.accumulator(cam, max_passes=8) as ref:
+        for a in (acc, ref):
+            for seed in (1, 2, 3):
+                a.add(seed)
+        assert (acc.counts() == 3).all()
+        i = acc.adapt_info()
+        assert (i["min_count"], i["max_count"]) == (3, 3)
+        assert acc.set_active(np.ones(acc.shape, bool)) == acc.shape[0] * acc.shape[1]
+        acc.add_active(4)
+        ref.add(4)
+        assert _same(_state(acc), _state(ref))
+        assert (acc.counts() == 4).all()
+        i = acc.adapt_info()
+        assert (i["min_count"], i["max_count"], i["total_samples"]) == (4, 4, 4 * 16 * acc.counts().size)
+
+
 # ------------------------------------------------------------------------ 3. refusals --
 def _state(acc):
     return acc.resolve() + (acc.counts(), acc.info())

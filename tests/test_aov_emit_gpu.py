@@ -1,4 +1,4 @@
-"""The emission split of the feature pass (rt_render_aov_emit, k_aov_emit in rt_aov.hip).
+"""The emission split of the feature pass (rt_render_aov_emit, k_aov<TREE, true> in rt_aov.hip).
 
 1. rt_render_aov's four buffers are unchanged, and two calls give the same bits.
 2. Self-consistency on Cornell, derived from the definition: the light is solid e = 15 and the
@@ -20,6 +20,7 @@
 4. Row shares and the other structures (BVH2, BVH4, compressed BVH4) agree with the default."""
 import numpy as np
 import pytest
+import torch  # before the library's HIP runtime initialises (one runtime per process)
 
 from tests.test_aov_gpu import _shape
 
@@ -121,6 +122,34 @@ def test_self_consistency_on_cornell(rt, gpu):
     assert ea <= 4 * ulp15
     assert ee <= 4 * ulp15
     assert (g["surface_albedo"][full] == 0).all() and (g["emission"][cov == 0] == 0).all()
+
+
+def test_device_entry_with_one_buffer_wanted(rt, gpu):
+    """render_aov_device asked for exactly one of the seven buffers writes that buffer with the
+    bits of the call that asks for all seven, for each buffer in turn (Cornell 40 x 30, n = 4:
+    covered and rim pixels, 1200 pixels = more than one block and no multiple of 256)."""
+    w, h, n = 40, 30, 4
+    t, cam, wd, l = rt.demo_scene("cornell")
+    shape(cam, w, h, n)
+    dev = torch.device("cuda", 0)
+    planes = {"albedo": 3, "normal": 3, "depth": 0, "material": 0, "emission": 3, "surface_albedo": 3,
+              "coverage": 0}
+
+    def buf(k):
+        dt = torch.int32 if k == "material" else torch.float32
+        return torch.full((h, w, planes[k]) if planes[k] else (h, w), -7, dtype=dt, device=dev)
+
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with rt.Scene(t, wd, l) as sc:
+        every = {k: buf(k) for k in planes}
+        sc.render_aov_device(cam, n_samples=n, seed=3, stream=stream,
+                             **{k: v.data_ptr() for k, v in every.items()})
+        every = {k: v.cpu().numpy() for k, v in every.items()}
+        assert every["coverage"].max() == 1.0 and (every["material"] == LIGHT).any()
+        for k in planes:
+            one = buf(k)
+            sc.render_aov_device(cam, n_samples=n, seed=3, stream=stream, **{k: one.data_ptr()})
+            assert np.array_equal(one.cpu().numpy(), every[k]), k
 
 
 _oracle_cache = {}
