@@ -242,7 +242,7 @@ inline constexpr int brute_shape_of(const BruteCounts& c) {
 //   1: one quad light with unit normal +-e_y (A_y = B_y = 0 exactly), weight 1, in a scene
 //      whose weights are all >= 0 (merge_ok) and whose mixture-pdf floor is 1e-30
 // A kind's normal axis, -1 = the general code (a kind for x or z is one more case here, plus
-// its kernels in pick_fused)
+// its rows in rt_fused.h's table)
 constexpr int kLeanLightCount = 2;
 inline constexpr int lean_light_axis(int kind) { return kind == 1 ? 1 : -1; }
 // The kind's light as plain floats, a member of the launch parameters (no pointer to chase):
@@ -253,7 +253,7 @@ inline constexpr int lean_light_axis(int kind) { return kind == 1 ? 1 : -1; }
 //  f[11], written as 0 above: 0 in the matcher's block (lean_light_of, rt_scene_lean_light);
 //  a launch of the early-draw kernel (k_fused<.., EARLY>) carries the emitter slot's bits
 //  there (a uint32: the record loop's bk of the scene's one emissive record,
-//  host_records.cpp emitter_slot_of), set by render_impl in its copy of the block and read by
+//  host_records.cpp emitter_slot_of), set by fill_params in its copy of the block and read by
 //  shade_core<.., EARLY_SHAPE> alone -- the light code never reads the word
 constexpr int kLeanLightFloats = 20;
 struct alignas(16) LeanLight {

@@ -3,6 +3,10 @@
 // can be compiled in their own translation units with their own code-generation flags
 // (rt_fused_sets.hip: the scheduler strategy per kernel); rt_render.hip holds the rest.
 #pragma once
+#include "rt_device.h"
+// (RT_FUSED_TABLE_ONLY: the kernel table at the end alone, for tools/fused_dispatch.cpp, which
+// runs the dispatcher over stand-in kernels on the host)
+#ifndef RT_FUSED_TABLE_ONLY
 #include "rt_path.h"
 
 namespace rt {
@@ -44,7 +48,7 @@ RT_D void finish_hit(const Params& P, const Path& s, Hit& best) {
 }
 
 // ----------------------------------------------------------------- fused ---
-// FT = compiled-in scene features (rt_device.h), chosen per scene by pick_fused.
+// FT = compiled-in scene features (rt_device.h), chosen per scene by pick_fused (rt_fused_pick.h).
 // Waves per SIMD by feature set: the lean sets fit more waves in the register
 // file (VGPRs <= 512 / waves) and in LDS (24 KB static + the scene cache).
 #ifndef MESH_WAVES
@@ -170,7 +174,7 @@ __shared__ unsigned long long g_dinfo[4][3];  // ... and then: samples left, bus
 // loop is compiled for (rt_device.h brute_shape), 0 = any.  LIGHT (the same kernels only): the
 // lean light kind the light sampling and light pdf are compiled for (rt_device.h), 0 = any list.
 // MAP: an active-pixel pass over the pixels listed in P.pixmap (chunk_ids; rt_fused_map.hip)
-// EARLY (a listed SHAPE with a lean light kind only; pick_fused has it for shape 1): the vertex's
+// EARLY (a listed SHAPE with a lean light kind only; the kernel table has it for shape 1): the vertex's
 // Philox draw is issued before the record loop's winner is resolved (rt_path.h shade_core);
 // P.ll.f[11] is the emitter slot (rt_device.h LeanLight)
 template <bool LDS, uint32_t FT, int TREE, int SHAPE = 0, int LIGHT = 0, bool MAP = false, bool EARLY = false>
@@ -370,29 +374,103 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
   }
 }
 
-// The kernels compiled in rt_fused_sets.hip instead of rt_render.hip, with LLVM's
-// iterative-ILP machine scheduler (Makefile): the C5 mesh set and the C3 sphere set
-// (C5 -0.6 / -1.0 %, C3 -0.8 %, images bit-identical; the same strategy costs the C2 kernel
-// 3.5 %, profiles/r3_sched_strategy_ab.jsonl, r3_split_ilp_ab.jsonl).  X(LDS, FT, TREE).
-// The compressed-BVH kernels (TREE 5) are not in this list: at 5 waves per SIMD the ILP
-// scheduler spilled 6 / 26 VGPRs in them against 1 / 2 with the default one, and the default
-// one renders C3 5.5 % and C5 0.3 % faster (bit-identical, profiles/r5_q_sched_ab.jsonl).
-// (book2's compressed-BVH kernel with the ILP scheduler: C4 +0.7 %, r5_book2_sched_ab.jsonl)
-#define RT_FUSED_ILP_KERNELS(X)                                             \
-  X(true, (FT_SPHERE | FT_TRI | FT_METAL), 4)                               \
-  X(false, (FT_SPHERE | FT_TRI | FT_METAL), 4)                              \
-  X(true, (FT_SPHERE | FT_TRI | FT_METAL | FT_DIEL | FT_CHECKER), 4)        \
-  X(false, (FT_SPHERE | FT_TRI | FT_METAL | FT_DIEL | FT_CHECKER), 4)
-
-// The MAP twins (active-pixel passes), compiled in rt_fused_map.hip with the
-// default scheduler: one for every kernel the dispatcher selects with no knob set, but the
-// record loop's SHAPE / LIGHT kernels (the generic record loop renders the same bits).
-// X(LDS, FT, TREE); the sets are rt_device.h kFtSets and FT_ALL.
-#define RT_FUSED_MAP_KERNELS(X)                                                      \
-  X(true, kFtSets[0], 0) X(false, kFtSets[0], 0) X(true, kFtSets[1], 0) X(false, kFtSets[1], 0) \
-  X(true, kFtSets[0], 4) X(false, kFtSets[0], 4) X(true, kFtSets[1], 4) X(false, kFtSets[1], 4) \
-  X(true, kFtSets[2], 4) X(false, kFtSets[2], 4) X(true, kFtSets[3], 4) X(false, kFtSets[3], 4) \
-  X(true, kFtSets[4], 4) X(false, kFtSets[4], 4) X(true, FT_ALL, 4) X(false, FT_ALL, 4)         \
-  X(false, kFtSets[2], 5) X(false, kFtSets[3], 5) X(false, kFtSets[4], 5) X(false, FT_ALL, 5)
-
 }  // namespace rt
+#endif  // RT_FUSED_TABLE_ONLY
+
+// ------------------------------------------------------------ the kernel table ---
+// Every k_fused instance the library compiles, once: X(LDS, FT, TREE, SHAPE, LIGHT, MAP, EARLY,
+// unit).  `unit` is the translation unit that compiles the row: DEF rt_render.hip (instantiated
+// by the dispatcher), ILP rt_fused_sets.hip (LLVM's iterative-ILP machine scheduler, Makefile),
+// MAP rt_fused_map.hip (the default scheduler; a unit of its own so the build stays parallel).
+// The explicit instantiations of the ILP and MAP units, rt_render.hip's `extern template`
+// declarations of them and the dispatcher (rt_fused_pick.h) all expand from this table, so a
+// row is compiled once, with its unit's flags, and can be chosen.  The sets are rt_device.h
+// kFtSets ([5] is FT_ALL).
+//
+// The record loop (TREE 0) and its lean LDS kernels: per listed layout (SHAPE, rt_device.h
+// brute_shape), per lean light kind (LIGHT), and the early-draw variant (EARLY) for shape 1 with
+// light kind 1 only.  Shape 2 has no early-draw kernel: it compiled to 9 SGPR spills against
+// the 8 of its (2, 1) kernel and was not measured, DESIGN.md §9.  The generic loop has no
+// light-kind kernel: the dispatcher returns nullptr and the planner takes kind 0.
+#define RT_FUSED_ROWS_RECORD_LOOP(X)                           \
+  X(true, kFtSets[0], 0, 1, 1, false, true, DEF)               \
+  X(true, kFtSets[0], 0, 1, 1, false, false, DEF)              \
+  X(true, kFtSets[0], 0, 2, 1, false, false, DEF)              \
+  X(true, kFtSets[0], 0, 1, 0, false, false, DEF)              \
+  X(true, kFtSets[0], 0, 2, 0, false, false, DEF)              \
+  X(true, kFtSets[0], 0, 0, 0, false, false, DEF)              \
+  X(true, kFtSets[1], 0, 0, 0, false, false, DEF)              \
+  X(false, kFtSets[0], 0, 0, 0, false, false, DEF)             \
+  X(false, kFtSets[1], 0, 0, 0, false, false, DEF)
+// BVH2 kernels exist for the two smallest sets with the tree in LDS (tiny scenes)
+#define RT_FUSED_ROWS_BVH2(X)                                  \
+  X(true, kFtSets[0], 2, 0, 0, false, false, DEF)              \
+  X(true, kFtSets[1], 2, 0, 0, false, false, DEF)
+// The BVH4, every set.  The C5 mesh set ([2]) and the C3 sphere set ([3]) take the ILP
+// scheduler: C5 -0.6 / -1.0 %, C3 -0.8 %, images bit-identical; the same strategy costs the C2
+// kernel 3.5 % (profiles/r3_sched_strategy_ab.jsonl, r3_split_ilp_ab.jsonl).
+#define RT_FUSED_ROWS_BVH4(X)                                  \
+  X(true, kFtSets[0], 4, 0, 0, false, false, DEF)              \
+  X(false, kFtSets[0], 4, 0, 0, false, false, DEF)             \
+  X(true, kFtSets[1], 4, 0, 0, false, false, DEF)              \
+  X(false, kFtSets[1], 4, 0, 0, false, false, DEF)             \
+  X(true, kFtSets[2], 4, 0, 0, false, false, ILP)              \
+  X(false, kFtSets[2], 4, 0, 0, false, false, ILP)             \
+  X(true, kFtSets[3], 4, 0, 0, false, false, ILP)              \
+  X(false, kFtSets[3], 4, 0, 0, false, false, ILP)             \
+  X(true, kFtSets[4], 4, 0, 0, false, false, DEF)              \
+  X(false, kFtSets[4], 4, 0, 0, false, false, DEF)             \
+  X(true, FT_ALL, 4, 0, 0, false, false, DEF)                  \
+  X(false, FT_ALL, 4, 0, 0, false, false, DEF)
+// The compressed BVH4 (TREE 5): trees read through L1/L2 only.  Not in the ILP unit: at 5 waves
+// per SIMD the ILP scheduler spilled 6 / 26 VGPRs in the [2] / [3] kernels against 1 / 2 with the
+// default one, and the default one renders C3 5.5 % and C5 0.3 % faster (bit-identical,
+// profiles/r5_q_sched_ab.jsonl).  (book2's kernel with the ILP scheduler: C4 +0.7 %,
+// r5_book2_sched_ab.jsonl)
+#define RT_FUSED_ROWS_QBVH(X)                                  \
+  X(false, kFtSets[2], 5, 0, 0, false, false, DEF)             \
+  X(false, kFtSets[3], 5, 0, 0, false, false, DEF)             \
+  X(false, kFtSets[4], 5, 0, 0, false, false, DEF)             \
+  X(false, FT_ALL, 5, 0, 0, false, false, DEF)
+// The BVH8 (measured slower than the BVH4): A/B builds only.  Large trees read
+// through L1/L2, the three tree sets.
+#ifdef RT_BVH8_KERNELS
+#define RT_FUSED_ROWS_BVH8(X)                                  \
+  X(false, kFtSets[2], 8, 0, 0, false, false, DEF)             \
+  X(false, kFtSets[3], 8, 0, 0, false, false, DEF)             \
+  X(false, kFtSets[4], 8, 0, 0, false, false, DEF)
+#else
+#define RT_FUSED_ROWS_BVH8(X)
+#endif
+// The MAP twins (active-pixel passes): one for every kernel the dispatcher
+// selects with no knob set, but the record loop's SHAPE / LIGHT kernels (the generic record
+// loop renders the same bits).  None for the opt-in trees 2 and 8.
+#define RT_FUSED_ROWS_MAP(X)                                   \
+  X(true, kFtSets[0], 0, 0, 0, true, false, MAP)               \
+  X(false, kFtSets[0], 0, 0, 0, true, false, MAP)              \
+  X(true, kFtSets[1], 0, 0, 0, true, false, MAP)               \
+  X(false, kFtSets[1], 0, 0, 0, true, false, MAP)              \
+  X(true, kFtSets[0], 4, 0, 0, true, false, MAP)               \
+  X(false, kFtSets[0], 4, 0, 0, true, false, MAP)              \
+  X(true, kFtSets[1], 4, 0, 0, true, false, MAP)               \
+  X(false, kFtSets[1], 4, 0, 0, true, false, MAP)              \
+  X(true, kFtSets[2], 4, 0, 0, true, false, MAP)               \
+  X(false, kFtSets[2], 4, 0, 0, true, false, MAP)              \
+  X(true, kFtSets[3], 4, 0, 0, true, false, MAP)               \
+  X(false, kFtSets[3], 4, 0, 0, true, false, MAP)              \
+  X(true, kFtSets[4], 4, 0, 0, true, false, MAP)               \
+  X(false, kFtSets[4], 4, 0, 0, true, false, MAP)              \
+  X(true, FT_ALL, 4, 0, 0, true, false, MAP)                   \
+  X(false, FT_ALL, 4, 0, 0, true, false, MAP)                  \
+  X(false, kFtSets[2], 5, 0, 0, true, false, MAP)              \
+  X(false, kFtSets[3], 5, 0, 0, true, false, MAP)              \
+  X(false, kFtSets[4], 5, 0, 0, true, false, MAP)              \
+  X(false, FT_ALL, 5, 0, 0, true, false, MAP)
+#define RT_FUSED_KERNELS(X)                                                                  \
+  RT_FUSED_ROWS_RECORD_LOOP(X) RT_FUSED_ROWS_BVH2(X) RT_FUSED_ROWS_BVH4(X) RT_FUSED_ROWS_QBVH(X) \
+  RT_FUSED_ROWS_BVH8(X) RT_FUSED_ROWS_MAP(X)
+// A unit picks its rows by defining RT_FUSED_IN_DEF / _ILP / _MAP (L, F, T, S, G, M, E) and
+// expanding RT_FUSED_KERNELS(RT_FUSED_BY_UNIT); the units it leaves out expand to nothing.
+#define RT_FUSED_BY_UNIT(L, F, T, S, G, M, E, U) RT_FUSED_IN_##U(L, F, T, S, G, M, E)
+#define RT_FUSED_SKIP(L, F, T, S, G, M, E)
+#define RT_FUSED_INSTANTIATE(L, F, T, S, G, M, E) template __global__ void k_fused<L, F, T, S, G, M, E>(Params);

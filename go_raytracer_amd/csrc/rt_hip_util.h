@@ -70,6 +70,18 @@ struct PixelMap {
 int render_pass(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
                 const PassSink* sink, const PixelMap* map = nullptr);
 
+// rt_render.hip, for rt_render_multi (rt_multi.hip): share `share` of the image (opts.rank of
+// opts.nranks on opts.device) rendered in the scene's slot 1 + share, resolved into out_dev (or
+// the slot's own buffer when null) and then, with a gather, handed off: the share's image (rows
+// of this rank, [rows][W][3]) is copied to `dst` on device `dst_device` (peer copy over xGMI when
+// the devices differ) on the share's stream, before the render returns.
+struct Gather {
+  float* dst;
+  int dst_device;
+};
+int render_share(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
+                 int share, float* out_dev, const Gather* gather);
+
 // Grow-only device scratch, one buffer per device ordinal (as rt_output.hip's): no allocation
 // per call once warm.  The caller serialises its users, and no work that reads an old buffer
 // may be in flight when a larger one is asked for (the old one is freed).

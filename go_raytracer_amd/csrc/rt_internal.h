@@ -103,6 +103,32 @@ struct Progress {
   std::vector<uint64_t> cum;    // samples complete when event i has fired
 };
 
+// rt_progress follows one render per scene: the rt_render call (slot 0) or rt_render_multi
+// call that finds no other render holding the record claims it here, and ProgressDone
+// releases it on every return path of the claimant.
+inline bool claim_progress(Progress& pr, uint64_t total, int device) {
+  std::lock_guard<std::mutex> lk(pr.mu);
+  if (pr.busy) return false;
+  pr.busy = 1;
+  pr.total = total;
+  pr.done = 0;
+  pr.device = device;
+  pr.events.clear();  // no slice events unless the claimant adds them
+  pr.cum.clear();
+  return true;
+}
+struct ProgressDone {
+  Progress& p;
+  bool track;
+  bool ok = false;
+  ~ProgressDone() {
+    if (!track) return;
+    std::lock_guard<std::mutex> lk(p.mu);
+    if (ok) p.done = p.total;
+    p.busy = 0;
+  }
+};
+
 // Render buffers of one (device, slot): slot 0 serves rt_render / rt_render_device,
 // slots 1..n the shares of rt_render_multi (so {0, 0, 0} gets three of them).  The
 // mutex is held for the whole render: one render in flight per (scene, device, slot).
@@ -128,7 +154,7 @@ struct Scene {
   void* multi_buf = nullptr;                        // gather + image buffer on the first device
   size_t multi_bytes = 0;
   int multi_dev = -1;
-  void* rccl = nullptr;                             // RCCL gather state (rt_render.hip RcclGather)
+  void* rccl = nullptr;                             // RCCL gather state (rt_multi.hip RcclGather)
   Progress prog;
   std::vector<rt_accum*> accums;                    // accumulators alive (rt_accum.hip), under mu
   // the compressed BVH4 (host_qbvh.cpp), built on the host once, at the first render that
@@ -197,10 +223,12 @@ uint32_t scene_features(const HostScene& h, bool* noise_table0 = nullptr);
 void release_device(Scene* s);
 // rt_accum.hip: frees the accumulators the scene still owns (release_device calls it first)
 void release_accums(Scene* s);
+// rt_multi.hip: frees rt_render_multi's RCCL state and gather buffer (release_device calls it next)
+void release_multi(Scene* s);
 // rt_render.hip, for the feature pass (rt_aov.hip): the scene's copy on `device` (the
 // calling thread's current device; uploaded on first use) set up for the structure the fused
 // render of this scene traverses -- tree 0 record loop, 2 BVH2, 4 BVH4, 5 compressed BVH4
-// (built and uploaded on demand), chosen by render_impl's rules
+// (built and uploaded on demand), chosen by the render's rules (plan_kernel)
 struct AovView {
   DevScene sc;
   int tree;

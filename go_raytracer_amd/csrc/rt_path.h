@@ -2473,7 +2473,7 @@ RT_D int shade_core(const Params& P, uint32_t slot, Path& s, const Hit& h, const
           // for any sign.
           // (the flag is re-read from the kernel-argument segment here, kparams(): held in
           // an SGPR across the loop it added SGPR spills)
-          // (a lean light kind: set by the host matcher and kept by the launch, render_impl)
+          // (a lean light kind: set by the host matcher and kept by the launch, plan_kernel)
           const bool merge = (LIGHT != 0 || kparams()->sc.merge_ok) && s.nst > 0 && pv.x >= 0.0f && pv.y >= 0.0f &&
                              pv.z >= 0.0f && pv.x <= 1.0f && pv.y <= 1.0f && pv.z <= 1.0f;
 #else

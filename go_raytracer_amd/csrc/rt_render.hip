@@ -26,10 +26,7 @@
 #include <algorithm>
 #include <chrono>
 #include <string>
-#include <thread>
 #include <vector>
-
-#include <rccl/rccl.h>
 
 #include "rt_hip_util.h"
 #include "rt_path.h"
@@ -221,6 +218,25 @@ struct RenderState {
   std::vector<hipEvent_t> events;
   std::vector<hipEvent_t> prog_events;  // one per progress slice (rt_progress)
   int resident_blocks = 0;
+  // the launch parameters' pointers into these buffers (csum: the render has the chunk sums)
+  void bind(Params& p, bool use_csum) const {
+    p.ray_o = ray_o;
+    p.ray_d = ray_d;
+    p.hit = hit;
+    p.path = path;
+    p.pend = pend;
+    p.pre = pre;
+    p.stack = stack;
+    p.queue[0] = queue[0];
+    p.queue[1] = queue[1];
+    p.ctr = ctr;
+    p.accum = accum;
+    p.csum = use_csum ? csum : nullptr;
+    p.side = side;
+    p.pflags = pflags;
+    p.ostack = ostack;
+    p.stack_cols = ostack_cols;
+  }
   void free_all() {
     for (void* p : allocs) (void)hipFree(p);
     allocs.clear();
@@ -233,38 +249,10 @@ struct RenderState {
   }
 };
 
-// rt_render_multi's RCCL gather (RT_FLAG_GATHER_RCCL): one communicator per device of
-// the list (ncclCommInitAll), a stream and a padded send buffer per share, kept while
-// the device list and the share size stay the same
-struct RcclGather {
-  std::vector<int> devs;
-  std::vector<ncclComm_t> comms;
-  std::vector<hipStream_t> streams;
-  std::vector<float*> send;
-  size_t send_floats = 0;
-  void release() {
-    for (size_t i = 0; i < comms.size(); ++i) {
-      (void)hipSetDevice(devs[i]);
-      if (send.size() > i && send[i]) (void)hipFree(send[i]);
-      if (streams.size() > i && streams[i]) (void)hipStreamDestroy(streams[i]);
-      (void)ncclCommDestroy(comms[i]);
-    }
-    devs.clear();
-    comms.clear();
-    streams.clear();
-    send.clear();
-    send_floats = 0;
-  }
-};
-
 void release_device(Scene* s) {
   DeviceGuard dg;
   release_accums(s);
-  if (s->rccl) {
-    static_cast<RcclGather*>(s->rccl)->release();
-    delete static_cast<RcclGather*>(s->rccl);
-    s->rccl = nullptr;
-  }
+  release_multi(s);
   std::lock_guard<std::mutex> lk(s->mu);
   for (auto& kv : s->slots) {
     if (kv.second->st) {
@@ -282,11 +270,6 @@ void release_device(Scene* s) {
     delete kv.second;
   }
   s->devs.clear();
-  if (s->multi_buf) {
-    (void)hipSetDevice(s->multi_dev);
-    (void)hipFree(s->multi_buf);
-    s->multi_buf = nullptr;
-  }
 }
 
 template <typename T>
@@ -301,11 +284,8 @@ static int upload(DeviceScene* ds, const std::vector<T>& v, const T** out) {
   return RT_OK;
 }
 
-// scheduling knobs of the fused kernel (A/B experiments; defaults measured): rt_tune_set
-// only, never the process environment (host_tune.cpp)
-static int env_int(const char* name, int dflt) { return tune_int(name, dflt); }
-
-
+// (the scheduling knobs below, A/B experiments with measured defaults, are tune_int: rt_tune_set
+// only, never the process environment, host_tune.cpp)
 FastDiv make_fastdiv(uint32_t d) {
   FastDiv f{1u, 0u, 0u, d};
   if (d <= 1) return f;  // d == 1: t = 0, q = n
@@ -530,7 +510,7 @@ static int ensure_csum(RenderState* st, uint32_t n_chunks, bool* use_csum_io, bo
     if (use_csum && st->csum_chunks < n_chunks) {
       if ((rc = drop_csum())) return rc;
       size_t free_b = 0, total_b = 0;
-      const size_t cap_b = (size_t)std::max(0, env_int("RT_CSUM_MAX_MB", 16384)) << 20;
+      const size_t cap_b = (size_t)std::max(0, tune_int("RT_CSUM_MAX_MB", 16384)) << 20;
       if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
       void* q = nullptr;
       if (need_b <= cap_b && need_b <= free_b / 2 && hipMalloc(&q, std::max<size_t>(need_b, 32)) == hipSuccess) {
@@ -560,94 +540,17 @@ static_assert(FT_SPHERE == RT_FT_SPHERE && FT_TRI == RT_FT_TRI && FT_METAL == RT
                   FT_IMAGE == RT_FT_IMAGE && FT_NOISE == RT_FT_NOISE && FT_BOX == RT_FT_BOX,
               "feature bits: rt_device.h and rt_abi.h disagree");
 
-#define RT_FUSED_EXTERN(L, F, T) extern template __global__ void k_fused<L, F, T>(Params);
-RT_FUSED_ILP_KERNELS(RT_FUSED_EXTERN)  // defined in rt_fused_sets.hip
-#undef RT_FUSED_EXTERN
-#define RT_FUSED_EXTERN(L, F, T) extern template __global__ void k_fused<L, F, T, 0, 0, true>(Params);
-RT_FUSED_MAP_KERNELS(RT_FUSED_EXTERN)  // defined in rt_fused_map.hip
-#undef RT_FUSED_EXTERN
+// the table's rows other units compile (rt_fused_sets.hip, rt_fused_map.hip); this unit's are
+// instantiated by the dispatcher
+#define RT_FUSED_EXTERN(L, F, T, S, G, M, E) extern template __global__ void k_fused<L, F, T, S, G, M, E>(Params);
+#define RT_FUSED_IN_DEF RT_FUSED_SKIP
+#define RT_FUSED_IN_ILP RT_FUSED_EXTERN
+#define RT_FUSED_IN_MAP RT_FUSED_EXTERN
+RT_FUSED_KERNELS(RT_FUSED_BY_UNIT)
 
-template <bool LDS>
-static const void* fused_for(uint32_t set) {
-  switch (set) {
-    case kFtSets[0]: return (const void*)k_fused<LDS, kFtSets[0], 4>;
-    case kFtSets[1]: return (const void*)k_fused<LDS, kFtSets[1], 4>;
-    case kFtSets[2]: return (const void*)k_fused<LDS, kFtSets[2], 4>;
-    case kFtSets[3]: return (const void*)k_fused<LDS, kFtSets[3], 4>;
-    case kFtSets[4]: return (const void*)k_fused<LDS, kFtSets[4], 4>;
-    default: return (const void*)k_fused<LDS, FT_ALL, 4>;
-  }
-}
-static uint32_t pick_set(uint32_t feats) { return pick_ft_set(feats); }
-// BVH2 kernels exist for the two smallest sets with the tree in LDS (tiny scenes)
-// (shape: the lean LDS record loop compiled for a listed record layout, rt_device.h brute_shape)
-// (light: the lean LDS record loop's light code compiled for a lean light kind, rt_device.h; the
-// listed shapes have such kernels, the generic loop does not: nullptr, the caller takes kind 0)
-// (early: the lean light kind's kernel that draws a vertex's numbers before it resolves the
-// winner, rt_path.h shade_core<.., EARLY_SHAPE>; shape 1 with light kind 1 only)
-static const void* pick_fused(bool lds, uint32_t set, int tree, int shape = 0, int light = 0,
-                              bool early = false) {
-  static_assert(kBruteShapeCount == 3, "pick_fused: one kernel per listed shape");
-  static_assert(kLeanLightCount == 2, "pick_fused: one kernel per listed shape and light kind");
-  if (light != 0) {
-    if (!(tree == 0 && lds && set == kFtSets[0] && light == 1)) return nullptr;
-    if (shape == 1) return early ? (const void*)k_fused<true, kFtSets[0], 0, 1, 1, false, true>
-                                 : (const void*)k_fused<true, kFtSets[0], 0, 1, 1>;
-    // (shape 2 has no early-draw kernel: it compiled to 9 SGPR spills against the 8 of the
-    // kernel below and was not measured)
-    if (shape == 2) return early ? nullptr : (const void*)k_fused<true, kFtSets[0], 0, 2, 1>;
-    return nullptr;
-  }
-  if (early) return nullptr;
-  if (tree == 0 && lds && set == kFtSets[0] && shape == 1) return (const void*)k_fused<true, kFtSets[0], 0, 1>;
-  if (tree == 0 && lds && set == kFtSets[0] && shape == 2) return (const void*)k_fused<true, kFtSets[0], 0, 2>;
-  if (tree == 0 && lds && set == kFtSets[0]) return (const void*)k_fused<true, kFtSets[0], 0>;
-  if (tree == 0 && lds && set == kFtSets[1]) return (const void*)k_fused<true, kFtSets[1], 0>;
-  if (tree == 0 && !lds && set == kFtSets[0]) return (const void*)k_fused<false, kFtSets[0], 0>;
-  if (tree == 0 && !lds && set == kFtSets[1]) return (const void*)k_fused<false, kFtSets[1], 0>;
-  if (tree == 2 && lds && set == kFtSets[0]) return (const void*)k_fused<true, kFtSets[0], 2>;
-  if (tree == 2 && lds && set == kFtSets[1]) return (const void*)k_fused<true, kFtSets[1], 2>;
-  if (tree == 8) {
-#ifdef RT_BVH8_KERNELS
-    // BVH8 (measured slower than the BVH4): A/B builds only.  Large trees
-    // read through L1/L2, the three tree sets
-    if (!lds && set == kFtSets[2]) return (const void*)k_fused<false, kFtSets[2], 8>;
-    if (!lds && set == kFtSets[3]) return (const void*)k_fused<false, kFtSets[3], 8>;
-    if (!lds && set == kFtSets[4]) return (const void*)k_fused<false, kFtSets[4], 8>;
-#endif
-    return nullptr;
-  }
-  if (tree == 5) {  // the compressed BVH4: trees read through L1/L2
-    if (lds) return nullptr;
-    switch (set) {
-      case kFtSets[2]: return (const void*)k_fused<false, kFtSets[2], 5>;
-      case kFtSets[3]: return (const void*)k_fused<false, kFtSets[3], 5>;
-      case kFtSets[4]: return (const void*)k_fused<false, kFtSets[4], 5>;
-      case FT_ALL: return (const void*)k_fused<false, FT_ALL, 5>;
-      default: return nullptr;
-    }
-  }
-  if (tree != 4) return nullptr;  // no such kernel: render_impl never asks (see tree there)
-  return lds ? fused_for<true>(set) : fused_for<false>(set);
-}
-
-// The MAP twin (an active-pixel pass, rt_fused.h RT_FUSED_MAP_KERNELS) of the kernel
-// pick_fused(lds, set, tree) returns; nullptr where there is none (the opt-in trees 2 and 8)
-static const void* pick_fused_map(bool lds, uint32_t set, int tree) {
-#define RT_FUSED_PICK(L, F, T) \
-  if (lds == L && set == (F) && tree == T) return (const void*)k_fused<L, F, T, 0, 0, true>;
-  RT_FUSED_MAP_KERNELS(RT_FUSED_PICK)
-#undef RT_FUSED_PICK
-  return nullptr;
-}
-
-// rt_render_multi's share hand-off: after the resolve, the share's image (rows of
-// this rank, [rows][W][3]) is copied to `dst` on device `dst_device` (peer copy over
-// xGMI when the devices differ) on the share's stream, before the render returns.
-struct Gather {
-  float* dst;
-  int dst_device;
-};
+}  // namespace rt
+#include "rt_fused_pick.h"
+namespace rt {
 
 // The compressed BVH4 of a tree read through L1/L2 (render_impl's tree 5), on `device`
 // (current): built on the host once per scene and uploaded once per device, by the first
@@ -687,13 +590,13 @@ static uint32_t scene_ft_set(const Scene* s) {
   // the feature-set kernels read perlin table 0 from LDS only: scenes whose noise
   // textures use other tables run the all-features kernel (generic table pointers)
   const uint32_t feats = s->h.features;
-  return (feats & FT_NOISE) && !s->h.noise_table0 ? FT_ALL : pick_set(feats);
+  return (feats & FT_NOISE) && !s->h.noise_table0 ? FT_ALL : pick_ft_set(feats);
 }
 static int fused_base_tree(const Scene* s, uint32_t ft_set) {
   const size_t n_refs = s->h.refs.size();
   const bool small_set = ft_set == kFtSets[0] || ft_set == kFtSets[1];
-  const int env_tree = env_int("RT_TREE", -1);
-  const size_t brute_max = (size_t)env_int("RT_BRUTE_MAX", kBruteMax);  // A/B override
+  const int env_tree = tune_int("RT_TREE", -1);
+  const size_t brute_max = (size_t)tune_int("RT_BRUTE_MAX", kBruteMax);  // A/B override
   const bool fits2 = !s->h.nodes.empty() && s->h.nodes.size() / 4 + n_refs <= fused_lds_slots(ft_set, 2);
   int tree = 4;
   // Record loop vs tree, measured on the Cornell box plus 0-12 extra boxes
@@ -708,7 +611,7 @@ static int fused_base_tree(const Scene* s, uint32_t ft_set) {
 // a BVH4 read through L1/L2 with single-prim leaves takes its compressed form (64-B nodes,
 // host_qbvh.cpp) when a kernel of the set exists; RT_QBVH=0: the 128-B nodes (A/B)
 static bool wants_qbvh(uint32_t ft_set) {
-  return env_int("RT_QBVH", 1) != 0 && pick_fused(false, ft_set, 5) != nullptr;
+  return tune_int("RT_QBVH", 1) != 0 && pick_fused(false, ft_set, 5) != nullptr;
 }
 
 // What a render of the scene traverses and the fused kernel that does it: one decision for
@@ -724,6 +627,7 @@ struct StructurePlan {
   const void* kernel;
   size_t lds_bytes;  // dynamic LDS of the kernel
   bool wants_qbvh;   // a BVH4 read through L1/L2 whose set has a compressed-BVH4 kernel
+  bool merge_bg;     // plan_kernel: the render's background keeps DevScene::merge_ok (no channel < 0)
 };
 // no_default_bvh2: an active-pixel pass, whose kernels have no BVH2 twin, takes
 // the BVH4 where the BVH2 is the default choice (49..64 leaf entries); RT_TREE=2 still asks for it
@@ -742,14 +646,14 @@ static int plan_structure(const Scene* s, const DeviceScene* ds, uint32_t ft_set
   const size_t n_refs = s->h.refs.size();
   auto slots_for = [&](int tr) { return fused_lds_slots(ft_set, tr); };
   // tree: 0 (no tree: every record tested, <= kBruteMax records in LDS), 2 or 4
-  const int env_tree = env_int("RT_TREE", -1);
+  const int env_tree = tune_int("RT_TREE", -1);
   int tree = mode == RT_MODE_FUSED ? fused_base_tree(s, ft_set) : 4;
   if (tree == 0 && !ds->brute_pairs) tree = 4;  // (records not uploaded: RT_BRUTE_MAX raised since)
   if (tree == 2 && !ds->nodes2) tree = 4;
   if (tree == 2 && no_default_bvh2 && env_tree != 2) tree = 4;
   const size_t lds_slots = slots_for(tree);
   const size_t brute_slots = ds->brute_slots;  // record-loop pairs, 2 x 64 B each
-  const int smem_env = env_int("RT_BRUTE_SMEM", -1);
+  const int smem_env = tune_int("RT_BRUTE_SMEM", -1);
   const bool brute_smem =
       tree == 0 && (smem_env >= 0 ? smem_env != 0 : brute_slots > lds_slots);
   const bool w4 = tree == 4;
@@ -776,21 +680,21 @@ static int plan_structure(const Scene* s, const DeviceScene* ds, uint32_t ft_set
   // The lean LDS record loop compiled for the scene's record layout, when it is a listed one
   // (fixed at upload: the same for every render of the scene).  RT_BRUTE_SHAPE=0: the generic
   // kernel (A/B; the same hits bit for bit).
-  const int brute_shape_id = tree == 0 && f_lds && ft_set == kFtSets[0] && env_int("RT_BRUTE_SHAPE", 1) != 0
+  const int brute_shape_id = tree == 0 && f_lds && ft_set == kFtSets[0] && tune_int("RT_BRUTE_SHAPE", 1) != 0
                                  ? ds->brute_shape : 0;
   // ... and its light sampling and light pdf compiled for the scene's light list, when that is
   // a lean light kind (fixed at upload too) and the layout's kernel exists for it.  The block
   // is a launch parameter: no LDS, nothing to stage.  RT_LEAN_LIGHT=0: the general light code
   // (A/B; the same image bit for bit).  A render whose background clears merge_ok takes kind 0
-  // at its launch (render_impl).
-  int light = tree == 0 && f_lds && ft_set == kFtSets[0] && env_int("RT_LEAN_LIGHT", 1) != 0
+  // (plan_kernel).
+  int light = tree == 0 && f_lds && ft_set == kFtSets[0] && tune_int("RT_LEAN_LIGHT", 1) != 0
                   ? ds->lean_light : 0;
   if (light != 0 && !pick_fused(f_lds, ft_set, tree, brute_shape_id, light)) light = 0;
   // ... and, for a scene with an emitter slot (fixed at upload) whose shade table is staged, the
   // variant of that kernel that draws each vertex's numbers before it resolves the winner.
   // RT_LEAN_EARLY_DRAW=0: the kernel that draws after (A/B; the same image bit for bit).
   const bool early = light != 0 && ds->emitter_slot >= 0 && shade_tab && f_recs &&
-                     env_int("RT_LEAN_EARLY_DRAW", 1) != 0 &&
+                     tune_int("RT_LEAN_EARLY_DRAW", 1) != 0 &&
                      pick_fused(f_lds, ft_set, tree, brute_shape_id, light, true) != nullptr;
   const void* fused_kernel = pick_fused(f_lds, ft_set, tree, brute_shape_id, light, early);
   if (!fused_kernel) return set_error(RT_ERR_UNSUPPORTED, "internal: no fused kernel for this scene");
@@ -820,6 +724,34 @@ static int take_qbvh(Scene* s, DeviceScene* ds, uint32_t ft_set, StructurePlan* 
 #ifdef RT_QTOP
   sp->lds_bytes = 64 * std::min<size_t>(RT_QTOP, ds->qitems);
 #endif
+  return RT_OK;
+}
+
+// The kernel a render launches and what it traverses: the scene's structure plan
+// (plan_structure) after the steps that depend on the render.  One decision for render_impl, the
+// feature pass (aov_view) and the rt_scene_plan_* entries, which use what they need of it.
+// background: the camera's (null: non-negative); map: an active-pixel pass.
+static int plan_kernel(Scene* s, DeviceScene* ds, uint32_t ft_set, int mode, const double* background,
+                       bool map, StructurePlan* sp) {
+  int rc;
+  if ((rc = plan_structure(s, ds, ft_set, mode, sp, map))) return rc;
+  if (sp->tree == 4 && sp->wants_qbvh && (rc = take_qbvh(s, ds, ft_set, sp))) return rc;
+  // A lean light kind's kernel holds merge_ok as the constant true: a render whose background
+  // clears the flag (fill_params) launches the layout's kernel with the general light code instead
+  sp->merge_bg = !background || ((float)background[0] >= 0.0f && (float)background[1] >= 0.0f &&
+                                 (float)background[2] >= 0.0f);
+  if (sp->light != 0 && !sp->merge_bg) {
+    sp->light = 0;
+    sp->early = false;
+    sp->kernel = pick_fused(sp->f_lds, ft_set, sp->tree, sp->shape, 0);
+  }
+  if (map) {  // the structure's MAP twin; the record loop's is the generic one (the same bits)
+    sp->shape = sp->light = 0;
+    sp->early = false;
+    sp->kernel = pick_fused_map(sp->f_lds, ft_set, sp->tree);
+    if (!sp->kernel)
+      return set_error(RT_ERR_UNSUPPORTED, "an active-pixel pass has no kernel for tree %d, chosen by RT_TREE / RT_BVH8", sp->tree);
+  }
   return RT_OK;
 }
 
@@ -855,9 +787,11 @@ int aov_view(Scene* s, int device, AovView* out) {
   if (rc) return rc;
   const uint32_t ft_set = scene_ft_set(s);
   StructurePlan sp;
-  if ((rc = plan_structure(s, ds, ft_set, RT_MODE_FUSED, &sp))) return rc;
-  if (sp.tree == 8) sp.tree = 4;
-  if (sp.tree == 4 && sp.wants_qbvh && (rc = take_qbvh(s, ds, ft_set, &sp))) return rc;
+  if ((rc = plan_kernel(s, ds, ft_set, RT_MODE_FUSED, nullptr, false, &sp))) return rc;
+  if (sp.tree == 8) {
+    sp.tree = 4;
+    if (sp.wants_qbvh && (rc = take_qbvh(s, ds, ft_set, &sp))) return rc;
+  }
   out->sc = scene_for_tree(ds, sp.tree);
   out->tree = sp.tree;
   return RT_OK;
@@ -932,7 +866,7 @@ static int plan_chunks(uint32_t npix, uint32_t rows, uint32_t W, uint32_t ss, ui
     const bool book1_set = ft_set == (FT_SPHERE | FT_TRI | FT_METAL | FT_DIEL | FT_CHECKER);
     const int need_dflt = f_lds ? 12 : ft_set == (FT_SPHERE | FT_TRI | FT_METAL) ? 200 : book1_set ? 50 : 100;
     const uint64_t work = (uint64_t)npix * ss,
-                   need = (uint64_t)std::max(1, env_int("RT_CHUNK_NEED", need_dflt)) * P;
+                   need = (uint64_t)std::max(1, tune_int("RT_CHUNK_NEED", need_dflt)) * P;
     K = f_lds ? 8u : 4u;  // the smallest: C3's 8-GPU share 6 % faster at 4 than 8 (C2's ±1 %)
     // Round 6: the lean record-loop kernel (C2) also takes K = 64 at the same bar (half as
     // many chunk starts and records; k_resolve reads half the bytes): C2 28.44 -> 27.81 ms
@@ -964,10 +898,10 @@ static int plan_chunks(uint32_t npix, uint32_t rows, uint32_t W, uint32_t ss, ui
                      (uint64_t)npix * ss / std::max<uint32_t>(K, 1u) < 40ull * P;
     // default: with the default chunk size only; an explicit RT_TAIL_FRAC also applies to
     // an explicit chunk size (A/B and tests)
-    const int tf_env = env_int("RT_TAIL_FRAC", -1);
+    const int tf_env = tune_int("RT_TAIL_FRAC", -1);
     const int tf = tf_env >= 0 ? tf_env : (few && chunk <= 0 ? 4 : 0);
     if (mode == RT_MODE_FUSED && !one_phase && tf > 1 && K >= 8u) {
-      K2 = std::max<uint32_t>(1u, (uint32_t)env_int("RT_TAIL_K", (int)std::max<uint32_t>(4u, K / 4)));
+      K2 = std::max<uint32_t>(1u, (uint32_t)tune_int("RT_TAIL_K", (int)std::max<uint32_t>(4u, K / 4)));
       const uint32_t s1 = (uint32_t)((uint64_t)ss * (uint32_t)(tf - 1) / (uint32_t)tf) / K * K;
       if (s1 > 0 && s1 < ss && K2 < K) S1 = s1;
       else K2 = K;
@@ -984,7 +918,7 @@ static int plan_chunks(uint32_t npix, uint32_t rows, uint32_t W, uint32_t ss, ui
     // flight start from a band of a few rows instead of the whole image (C5 -10 %,
     // C3 -5 %, C4 -3 %, C2 -1 % against image-wide pixel-fastest chunks; 1, 4 and 16
     // rows measured alike, profiles/r2_chunk_order_ab.jsonl)
-    const int env_rows = env_int("RT_CHUNK_ROWS", -1);
+    const int env_rows = tune_int("RT_CHUNK_ROWS", -1);
     uint32_t grows = env_rows > 0 ? (uint32_t)env_rows : 4u;
     grows = std::max<uint32_t>(1u, std::min<uint32_t>(grows, std::max<uint32_t>(rows, 1u)));
     while (rows % grows) --grows;  // a divisor of the rank's row count
@@ -1030,8 +964,8 @@ static SchedPlan plan_sched(uint32_t ft_set, int tree, bool f_lds, uint32_t K, s
   // (round 6, with the mesh set's 256-chunk batches: 4 steps -0.5 % on C5's whole image, -0.4 /
   // -0.6 % on its 2- / 8-GPU shares against 5; 3 as 4 except the 8-GPU share, 2 +1.5 %; the
   // ready-lane bar 24 as 32, 16 +2.5 %, 40 +2 %; profiles/r6_c5_sched_sweep.jsonl)
-  sd.step_budget = std::max(1, env_int("RT_STEP_BUDGET", f_lds ? (1 << 30) : big_tree ? (long_shade ? 7 : 4) : 10));
-  sd.shade_min = (uint32_t)std::max(1, env_int("RT_SHADE_MIN", f_lds ? 1 : long_shade ? 40 : big_tree ? 32 : 1));
+  sd.step_budget = std::max(1, tune_int("RT_STEP_BUDGET", f_lds ? (1 << 30) : big_tree ? (long_shade ? 7 : 4) : 10));
+  sd.shade_min = (uint32_t)std::max(1, tune_int("RT_SHADE_MIN", f_lds ? 1 : long_shade ? 40 : big_tree ? 32 : 1));
   // chunks per refill of a wave's batch (one returning atomic on the chunk
   // counter each): C2 grab sweep (profiles/r1_grab_sweep.jsonl) 64 -> 128:
   // -4 % at 1-2 ranks' shares; 256 for small chunks: -11 % on the 8-GPU share
@@ -1047,41 +981,26 @@ static SchedPlan plan_sched(uint32_t ft_set, int tree, bool f_lds, uint32_t K, s
   // share; 512 ±0, 1024 +5 %; book2 keeps 128: -0.4 % whole but +0.4 % on its 2-GPU share, and
   // book1 128: 64 +0.7 %, 256 +2 %; profiles/r6_grab_sweep.jsonl)
   const bool mesh_set = ft_set == (FT_SPHERE | FT_TRI | FT_METAL);
-  sd.grab_min = (uint32_t)std::max(1, env_int("RT_GRAB_MIN", f_lds ? (tree == 0 && ft_set == 0u ? 16 : 32) : (K <= 8u || mesh_set) ? 256 : 128));
+  sd.grab_min = (uint32_t)std::max(1, tune_int("RT_GRAB_MIN", f_lds ? (tree == 0 && ft_set == 0u ? 16 : 32) : (K <= 8u || mesh_set) ? 256 : 128));
   {  // drain splitting (k_fused's record-loop kernel): share when >= split_min samples are left
-    const int sm = env_int("RT_SPLIT_MIN", 1);
+    const int sm = tune_int("RT_SPLIT_MIN", 1);
     sd.split_min = sm > 0 ? (uint32_t)sm : 0xFFFFFFFFu;  // 0: off (no lane has that many)
   }
   // partitioned chunk counters (rt_path.h grab_chunk): 64 partitions interleaved in
   // granules of 256 chunks; progress slices use one counter (their ranges are contiguous)
-  sd.parts_log2 = (uint32_t)std::min(6, std::max(0, env_int("RT_PARTS_LOG2", 6)));
-  sd.gran_log2 = (uint32_t)std::min(20, std::max(0, env_int("RT_GRAN_LOG2", 8)));
+  sd.parts_log2 = (uint32_t)std::min(6, std::max(0, tune_int("RT_PARTS_LOG2", 6)));
+  sd.gran_log2 = (uint32_t)std::min(20, std::max(0, tune_int("RT_GRAN_LOG2", 8)));
   return sd;
 }
 
-// rt_progress follows one render per scene: the rt_render call (slot 0) or rt_render_multi
-// call that finds no other render holding the record claims it here, and ProgressDone
-// releases it on every return path of the claimant.
-static bool claim_progress(Progress& pr, uint64_t total, int device) {
-  std::lock_guard<std::mutex> lk(pr.mu);
-  if (pr.busy) return false;
-  pr.busy = 1;
-  pr.total = total;
-  pr.done = 0;
-  pr.device = device;
-  pr.events.clear();  // no slice events unless the claimant adds them
-  pr.cum.clear();
-  return true;
-}
-struct ProgressDone {
-  Progress& p;
-  bool track;
-  bool ok = false;
-  ~ProgressDone() {
-    if (!track) return;
-    std::lock_guard<std::mutex> lk(p.mu);
-    if (ok) p.done = p.total;
-    p.busy = 0;
+// A device allocation of one call: whatever `p` still points at when the scope ends is freed, so
+// every error exit between the hipMalloc and the success path's own hipFree (which then clears
+// `p`) releases it.
+template <typename T>
+struct FreeOnExit {
+  T*& p;
+  ~FreeOnExit() {
+    if (p) (void)hipFree(p);
   }
 };
 
@@ -1126,6 +1045,7 @@ static int launch_fused(Params& p, RenderState* st, hipStream_t stream, const St
   std::string wt_file;
   const char* wt_path = tune_str("RT_WAVE_TIMES", &wt_file) ? wt_file.c_str() : nullptr;
   unsigned long long* wt = nullptr;
+  FreeOnExit<unsigned long long> wt_guard{wt};
   const size_t n_waves = (size_t)fused_blocks * 4;
   if (wt_path && *wt_path) {
     HIP_OK(hipMalloc(&wt, kWaveRec * n_waves * sizeof(unsigned long long)));
@@ -1149,6 +1069,7 @@ static int launch_fused(Params& p, RenderState* st, hipStream_t stream, const St
     HIP_OK(hipMemcpyAsync(h.data(), wt, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
     HIP_OK(hipFree(wt));
+    wt = nullptr;
     p.wave_times = nullptr;
     if (FILE* f = fopen(wt_path, "wb")) {
       fwrite(h.data(), sizeof(h[0]), h.size(), f);
@@ -1248,10 +1169,217 @@ static int fill_stats(rt_stats* stats, const Scene* s, const DeviceScene* ds, co
 }
 
 
+// the scene's render slot `slot_id` on `device`, created on first use
+static SlotState* slot_of(Scene* s, int device, int slot_id) {
+  std::lock_guard<std::mutex> lk(s->mu);
+  SlotState*& sl = s->slots[{device, slot_id}];
+  if (!sl) sl = new SlotState();
+  return sl;
+}
+
+// Where a render's image goes and which of the scene's render slots it runs in.  A caller
+// names what it sets.
+struct RenderTarget {
+  float* host = nullptr;           // the image, copied to host memory
+  float* dev = nullptr;            // resolved into this device buffer instead of the slot's own
+  int slot_id = 0;                 // 0: rt_render[_device] and passes; 1 + i: share i of rt_render_multi
+  const Gather* gather = nullptr;  // the share's hand-off (rt_hip_util.h)
+  const PassSink* sink = nullptr;  // an accumulator's pass: folded into its sums, not resolved
+  const PixelMap* map = nullptr;   // an active-pixel pass
+};
+
+// Path slots: the fused kernel's resident lanes, at most opts.path_slots (the chunk plan cuts
+// the work by them) ...
+static int fused_slots(const StructurePlan& sp, const rt_render_opts& o, int* blocks, uint32_t* P) {
+  int rc;
+  if ((rc = occupancy_blocks(sp.kernel, o.device, blocks, sp.lds_bytes))) return rc;
+  if (o.path_slots > 0) *blocks = std::max(1, std::min(*blocks, (o.path_slots + 255) / 256));
+  *P = (uint32_t)*blocks * 256u;
+  return RT_OK;
+}
+// ... or the wavefront queue's length, at most the chunks there are
+static uint32_t wavefront_slots(const rt_render_opts& o, uint32_t n_chunks) {
+  uint32_t P = o.path_slots > 0 ? (uint32_t)o.path_slots : (1u << 20);
+  P = std::max<uint32_t>(256u, std::min<uint32_t>(P, std::max<uint32_t>(n_chunks, 256u)));
+  return (P + 255u) & ~255u;
+}
+
+// What the plans decide of the launch parameters: the scene as the plan's tree reads it, the
+// chunk cut and the scheduling knobs.  After set_camera_params (p.npix).
+static int fill_params(Params& p, const DeviceScene* ds, const StructurePlan& sp, const ChunkPlan& cp,
+                       const SchedPlan& sd, uint32_t P) {
+  p.sc = scene_for_tree(ds, sp.tree);
+  if (sp.tree == 0 && sp.shade_tab && sp.f_recs) {  // the shade table follows the pairs, in LDS as in HBM
+    p.sc.shade_lds = (int32_t)(4 * ds->brute_slots);
+    p.sc.shade_n = ds->shade_n;
+  }
+  if (!sp.merge_bg) p.sc.merge_ok = 0;
+  if (sp.light != 0) {
+    if (!p.sc.merge_ok) return set_error(RT_ERR_UNSUPPORTED, "internal: lean light kernel without merge_ok");
+    p.ll = ds->light_block;
+    if (sp.early) {  // the emitter slot in the block's first spare word (rt_device.h LeanLight)
+      const uint32_t es = (uint32_t)ds->emitter_slot;
+      memcpy(&p.ll.f[11], &es, 4);
+    }
+  }
+  p.K = cp.K;
+  p.K2 = cp.K2;
+  p.S1 = cp.S1;
+  p.n1 = p.npix * cp.cpp1;
+  p.n_chunks = cp.n_chunks;
+  p.P = P;
+  p.fd_gpix = cp.fd_gpix;
+  p.fd_gchunks = cp.fd_gchunks;
+  p.fd_gchunks2 = cp.fd_gchunks2;
+  p.step_budget = sd.step_budget;
+  p.shade_min = sd.shade_min;
+  p.grab_min = sd.grab_min;
+  p.split_min = sd.split_min;
+  p.parts_log2 = sd.parts_log2;
+  p.gran_log2 = sd.gran_log2;
+  p.wave_times = nullptr;
+  p.recs_lds = sp.f_recs ? 1u : 0u;
+  return RT_OK;
+}
+
+// The order the sweep takes the row groups in (chunk_pixel, k_resolve; images do not
+// depend on it): RT_SWEEP = forward (image order, the default) or reverse.  A render's tail
+// is the paths still in flight when the chunk pool runs dry, so it depends on which rows
+// the sweep ends on: book2's costly bottom rows (fog, the box ground) end its forward sweep,
+// and its 2- / 8-GPU shares are 2.3 / 3.2 % faster reversed, while C5 and book1 are 1-6 %
+// slower (the sky ends their reverse sweep right after the metal dragon / the sphere field,
+// whose long specular paths are then still in flight); no probe of the rows' costs chose
+// between them reliably, DESIGN.md §8.  Feature-set kernels only (the record loop maps
+// chunks in one phase).  The group of sweep position q is (q ^ gflip) + gbase, compiled in
+// only with -DRT_SWEEP_ORDER: even that form, two kernel-argument words and two VALU ops
+// per chunk start, measured C4 +0.3 % and C5 +0.5 % in the default order at full size
+// (profiles/r6_sweep_table_cost_ab.jsonl; a table lookup the same).
+static int sweep_order(Params& p, int mode, uint32_t ft_set, const ChunkPlan& cp) {
+#ifdef RT_SWEEP_ORDER
+  p.gflip = p.gbase = 0u;
+#endif
+  std::string v;
+  if (tune_str("RT_SWEEP", &v) && v == "reverse") {
+#ifdef RT_SWEEP_ORDER
+    if (mode == RT_MODE_FUSED && ft_set != 0u && cp.n_groups > 1 && p.npix > 0) {
+      p.gflip = ~0u;  // (q ^ ~0) + ng = ng - 1 - q
+      p.gbase = cp.n_groups;
+    }
+#else
+    return set_error(RT_ERR_UNSUPPORTED, "RT_SWEEP=reverse needs a library built with -DRT_SWEEP_ORDER");
+#endif
+  }
+  return RT_OK;
+}
+
+// opts.trace_out: the device buffer the traced sample's vertices are recorded in (t = -1: a
+// vertex the path did not reach); the caller's guard frees it
+static int start_trace(Params& p, const rt_render_opts& o, F4*& dtrace) {
+  if (!(o.trace_out && o.trace_cap > 0)) return RT_OK;
+  HIP_OK(hipMalloc(&dtrace, (size_t)o.trace_cap * 3 * sizeof(F4)));
+  std::vector<float> init((size_t)o.trace_cap * 12, 0.0f);
+  for (int v = 0; v < o.trace_cap; ++v) init[12 * v + 7] = -1.0f;
+  HIP_OK(hipMemcpy(dtrace, init.data(), init.size() * 4, hipMemcpyHostToDevice));
+  p.trace = dtrace;
+  p.trace_gpix = (uint32_t)o.trace_pixel;
+  p.trace_sample = (uint32_t)o.trace_sample;
+  p.trace_cap = o.trace_cap;
+  return RT_OK;
+}
+
+// ... copied to opts.trace_out after the render, and freed
+static int read_trace(const rt_render_opts& o, F4*& dtrace) {
+  if (!dtrace) return RT_OK;
+  HIP_OK(hipMemcpy(o.trace_out, dtrace, (size_t)o.trace_cap * 3 * sizeof(F4), hipMemcpyDeviceToHost));
+  HIP_OK(hipFree(dtrace));
+  dtrace = nullptr;
+  return RT_OK;
+}
+
+// the overflow columns of the traversal stacks, one per traversal thread: the fused kernel's
+// lanes, or the wavefront extend kernel's resident blocks (asked once per state)
+static int ensure_trav_stacks(RenderState* st, int device, int mode, uint32_t P, const void* extend_kernel) {
+  int rc;
+  if (mode == RT_MODE_WAVEFRONT && st->resident_blocks == 0 &&
+      (rc = occupancy_blocks(extend_kernel, device, &st->resident_blocks)))
+    return rc;
+  return ensure_ostack(st, mode == RT_MODE_FUSED ? P : (uint32_t)st->resident_blocks * 256u);
+}
+
+// the caller's stream, or the slot's own (created on first use)
+static int render_stream(RenderState* st, const rt_render_opts& o, hipStream_t* stream) {
+  if (!o.stream && !st->own_stream) HIP_OK(hipStreamCreateWithFlags(&st->own_stream, hipStreamNonBlocking));
+  *stream = o.stream ? (hipStream_t)o.stream : st->own_stream;
+  return RT_OK;
+}
+
+// |v| < 2^31 / ss: the ss-sample fixed-point sum of a pixel stays inside int64 (a pass of an
+// accumulator: the sum of all its max_passes passes, ss * max_passes < 2^31)
+static float sample_limit(uint32_t ss, const PassSink* sink) {
+  return std::nextafter((float)(2147483648.0 / (double)((uint64_t)std::max<uint32_t>(ss, 1u) *
+                                                        (sink ? std::max<uint32_t>(sink->max_passes, 1u) : 1u))),
+                        0.0f);
+}
+
+// the counters and the npix pixels' sums and flags, cleared on the render's stream
+static int clear_sums(const RenderState* st, uint32_t npix, hipStream_t stream) {
+  HIP_OK(hipMemsetAsync(st->ctr, 0, sizeof(Counters), stream));
+  if (npix > 0) {
+    HIP_OK(hipMemsetAsync(st->accum, 0, 3 * (size_t)npix * sizeof(unsigned long long), stream));
+    HIP_OK(hipMemsetAsync(st->side, 0, 3 * (size_t)npix * sizeof(double), stream));
+    HIP_OK(hipMemsetAsync(st->pflags, 0, (size_t)npix * sizeof(uint32_t), stream));
+  }
+  return RT_OK;
+}
+
+// rt_progress of a render in `slices` launches: the slot's event per slice, created on first
+// use, ...
+static int slice_events(RenderState* st, int slices) {
+  while ((int)st->prog_events.size() < slices) {
+    hipEvent_t e;
+    HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    st->prog_events.push_back(e);
+  }
+  return RT_OK;
+}
+// ... and, in the record of the render that claimed it, those events with the samples complete
+// when each has fired
+static void track_slices(Progress& pr, const RenderState* st, int slices, uint32_t n_chunks) {
+  std::lock_guard<std::mutex> lk(pr.mu);
+  for (int sl = 0; sl < slices; ++sl) {
+    pr.events.push_back((void*)st->prog_events[sl]);
+    pr.cum.push_back((uint64_t)((double)pr.total * (double)((uint64_t)n_chunks * (sl + 1) / slices) /
+                                (double)n_chunks));
+  }
+}
+
+// After the launches: the sums resolved to the image (or folded into an accumulator's), the
+// image copied where the target wants it, and the stream synchronised.
+static int finish_render(const Params& p, const RenderState* st, hipStream_t stream, double scale,
+                         int device, const RenderTarget& tg) {
+  const uint32_t npix = p.npix;
+  int rc;
+  float* dst = tg.dev ? tg.dev : st->out;
+  if (npix > 0 && tg.sink) {  // an accumulator's pass: folded into its sums, not resolved
+    if ((rc = tg.sink->fold(tg.sink->ctx, p, scale, stream))) return rc;
+  } else if (npix > 0) {
+    hipLaunchKernelGGL(k_resolve, dim3((npix + 255) / 256), dim3(256), 0, stream, p, dst, scale);
+    HIP_OK(hipGetLastError());
+  }
+  if (tg.host && npix > 0)
+    HIP_OK(hipMemcpyAsync(tg.host, dst, 3 * (size_t)npix * sizeof(float), hipMemcpyDeviceToHost,
+                          stream));
+  if (tg.gather && npix > 0)
+    HIP_OK(hipMemcpyPeerAsync(tg.gather->dst, tg.gather->dst_device, dst, device,
+                              3 * (size_t)npix * sizeof(float), stream));
+  HIP_OK(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+
+// One render on one device: plan (kernel, slots, chunks, scheduling), the slot's buffers, the
+// launch parameters, the launches, the image.
 static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
-                       float* out_host, float* out_dev, rt_stats* stats, int slot_id = 0,
-                       const Gather* gather = nullptr, const PassSink* sink = nullptr,
-                       const PixelMap* map = nullptr) {
+                       rt_stats* stats, const RenderTarget& tg) {
   if (!scene || !cam) return set_error(RT_ERR_INVALID, "rt_render: null scene/camera");
   rt_render_opts o{};
   if (opts) o = *opts;
@@ -1269,15 +1397,10 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   Scene* s = &scene->s;
   DeviceScene* ds = nullptr;
   if ((rc = ensure_scene(s, o.device, &ds))) return rc;
-  SlotState* slot = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(s->mu);
-    SlotState*& sl = s->slots[{o.device, slot_id}];
-    if (!sl) sl = new SlotState();
-    slot = sl;
-  }
+  SlotState* slot = slot_of(s, o.device, tg.slot_id);
   std::lock_guard<std::mutex> inflight(slot->mu);  // one render per (scene, device, slot)
 
+  const PixelMap* map = tg.map;
   const uint32_t W = (uint32_t)cd.width, H = (uint32_t)cd.height;
   const uint32_t rows = rank_rows(H, o.rank, o.nranks);
   const uint32_t npix_share = rows * W;
@@ -1290,223 +1413,71 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   if (map && mode == RT_MODE_WAVEFRONT)
     return set_error(RT_ERR_UNSUPPORTED, "an active-pixel pass runs the fused kernel only (mode wavefront)");
   if (mode != RT_MODE_WAVEFRONT && mode != RT_MODE_FUSED) mode = RT_MODE_FUSED;
-  const int depth_cap = cd.max_depth + 1;
   const uint32_t ft_set = scene_ft_set(s);
 
-  // what to traverse and the kernel for it (the feature pass takes the same: aov_view)
+  // the plans: kernel and structure (the feature pass takes the same: aov_view), path slots (the
+  // fused kernel's lanes before the chunk cut, the wavefront queue after it), scheduling
   StructurePlan sp;
-  if ((rc = plan_structure(s, ds, ft_set, mode, &sp, map != nullptr))) return rc;
-  if (sp.tree == 4 && sp.wants_qbvh && (rc = take_qbvh(s, ds, ft_set, &sp))) return rc;
-  // A lean light kind's kernel holds merge_ok as the constant true: a render whose background
-  // clears the flag (below) launches the layout's kernel with the general light code instead
-  if (sp.light != 0 && !((float)cd.background[0] >= 0.0f && (float)cd.background[1] >= 0.0f &&
-                         (float)cd.background[2] >= 0.0f)) {
-    sp.light = 0;
-    sp.early = false;
-    sp.kernel = pick_fused(sp.f_lds, ft_set, sp.tree, sp.shape, 0);
-  }
-  if (map) {  // the structure's MAP twin; the record loop's is the generic one (the same bits)
-    sp.shape = sp.light = 0;
-    sp.early = false;
-    sp.kernel = pick_fused_map(sp.f_lds, ft_set, sp.tree);
-    if (!sp.kernel)
-      return set_error(RT_ERR_UNSUPPORTED, "an active-pixel pass has no kernel for tree %d, chosen by RT_TREE / RT_BVH8", sp.tree);
-  }
-  // path slots: the fused kernel's resident lanes, or the wavefront queue's length
+  if ((rc = plan_kernel(s, ds, ft_set, mode, cd.background, map != nullptr, &sp))) return rc;
   uint32_t P = 0;
   int fused_blocks = 0;
-  if (mode == RT_MODE_FUSED) {
-    if ((rc = occupancy_blocks(sp.kernel, o.device, &fused_blocks, sp.lds_bytes))) return rc;
-    if (o.path_slots > 0) fused_blocks = std::max(1, std::min(fused_blocks, (o.path_slots + 255) / 256));
-    P = (uint32_t)fused_blocks * 256u;
-  }
+  if (mode == RT_MODE_FUSED && (rc = fused_slots(sp, o, &fused_blocks, &P))) return rc;
   ChunkPlan cp;
   // (a map: one chunk group, chunk_pixel's "G = npix" order over the sorted list)
   if ((rc = plan_chunks(npix, map ? 1u : rows, map ? npix : W, ss, P, o.chunk, ft_set, sp.tree, sp.f_lds, mode, &cp)))
     return rc;
   const uint32_t n_chunks = cp.n_chunks;
-  if (mode != RT_MODE_FUSED) {
-    P = o.path_slots > 0 ? (uint32_t)o.path_slots : (1u << 20);
-    P = std::max<uint32_t>(256u, std::min<uint32_t>(P, std::max<uint32_t>(n_chunks, 256u)));
-    P = (P + 255u) & ~255u;
-  }
-  // (sized for the whole share with a map too: neither pass reallocates the other's buffers)
-  if ((rc = ensure_state(slot, o.device, P, depth_cap, std::max<uint32_t>(npix_share, 1),
+  if (mode != RT_MODE_FUSED) P = wavefront_slots(o, n_chunks);
+  const SchedPlan sd = plan_sched(ft_set, sp.tree, sp.f_lds, cp.K, s->h.nodes4.size() / 8);
+
+  // the slot's buffers (sized for the whole share with a map too: neither pass reallocates the
+  // other's) and the stream
+  if ((rc = ensure_state(slot, o.device, P, cd.max_depth + 1, std::max<uint32_t>(npix_share, 1),
                          mode == RT_MODE_WAVEFRONT)))
     return rc;
   RenderState* st = slot->st;
   const void* extend_kernel =
       extend_in_lds(s) ? (const void*)k_extend<true> : (const void*)k_extend<false>;
-  if (mode == RT_MODE_WAVEFRONT && st->resident_blocks == 0 &&
-      (rc = occupancy_blocks(extend_kernel, o.device, &st->resident_blocks)))
-    return rc;
-  if ((rc = ensure_ostack(st, mode == RT_MODE_FUSED ? P : (uint32_t)st->resident_blocks * 256u))) return rc;
-  bool use_csum = mode == RT_MODE_FUSED && env_int("RT_CSUM", 1) != 0;
+  if ((rc = ensure_trav_stacks(st, o.device, mode, P, extend_kernel))) return rc;
+  bool use_csum = mode == RT_MODE_FUSED && tune_int("RT_CSUM", 1) != 0;
   if ((rc = ensure_csum(st, n_chunks, &use_csum, map != nullptr))) return rc;
-
-  hipStream_t stream = (hipStream_t)o.stream;
-  if (!stream) {
-    if (!st->own_stream) HIP_OK(hipStreamCreateWithFlags(&st->own_stream, hipStreamNonBlocking));
-    stream = st->own_stream;
-  }
+  hipStream_t stream = nullptr;
+  if ((rc = render_stream(st, o, &stream))) return rc;
 
   Params p{};
-  p.sc = scene_for_tree(ds, sp.tree);
-  if (sp.tree == 0 && sp.shade_tab && sp.f_recs) {  // the shade table follows the pairs, in LDS as in HBM
-    p.sc.shade_lds = (int32_t)(4 * ds->brute_slots);
-    p.sc.shade_n = ds->shade_n;
-  }
   set_camera_params(p, cd, o, npix);
-  if (!(p.bg[0] >= 0.0f && p.bg[1] >= 0.0f && p.bg[2] >= 0.0f)) p.sc.merge_ok = 0;
-  if (sp.light != 0) {
-    if (!p.sc.merge_ok) return set_error(RT_ERR_UNSUPPORTED, "internal: lean light kernel without merge_ok");
-    p.ll = ds->light_block;
-    if (sp.early) {  // the emitter slot in the block's first spare word (rt_device.h LeanLight)
-      const uint32_t es = (uint32_t)ds->emitter_slot;
-      memcpy(&p.ll.f[11], &es, 4);
-    }
-  }
+  if ((rc = fill_params(p, ds, sp, cp, sd, P)) || (rc = sweep_order(p, mode, ft_set, cp))) return rc;
+  st->bind(p, use_csum);
   p.pixmap = map ? map->pixels : nullptr;
-  p.K = cp.K;
-  p.K2 = cp.K2;
-  p.S1 = cp.S1;
-  p.n1 = npix * cp.cpp1;
-  p.n_chunks = n_chunks;
-  p.P = P;
-  p.fd_gpix = cp.fd_gpix;
-  p.fd_gchunks = cp.fd_gchunks;
-  p.fd_gchunks2 = cp.fd_gchunks2;
-  // The order the sweep takes the row groups in (chunk_pixel, k_resolve; images do not
-  // depend on it): RT_SWEEP = forward (image order, the default) or reverse.  A render's tail
-  // is the paths still in flight when the chunk pool runs dry, so it depends on which rows
-  // the sweep ends on: book2's costly bottom rows (fog, the box ground) end its forward sweep,
-  // and its 2- / 8-GPU shares are 2.3 / 3.2 % faster reversed, while C5 and book1 are 1-6 %
-  // slower (the sky ends their reverse sweep right after the metal dragon / the sphere field,
-  // whose long specular paths are then still in flight); no probe of the rows' costs chose
-  // between them reliably, DESIGN.md §8.  Feature-set kernels only (the record loop maps
-  // chunks in one phase).  The group of sweep position q is (q ^ gflip) + gbase, compiled in
-  // only with -DRT_SWEEP_ORDER: even that form, two kernel-argument words and two VALU ops
-  // per chunk start, measured C4 +0.3 % and C5 +0.5 % in the default order at full size
-  // (profiles/r6_sweep_table_cost_ab.jsonl; a table lookup the same).
-#ifdef RT_SWEEP_ORDER
-  p.gflip = p.gbase = 0u;
-#endif
-  {
-    std::string v;
-    if (tune_str("RT_SWEEP", &v) && v == "reverse") {
-#ifdef RT_SWEEP_ORDER
-      if (mode == RT_MODE_FUSED && ft_set != 0u && cp.n_groups > 1 && npix > 0) {
-        p.gflip = ~0u;  // (q ^ ~0) + ng = ng - 1 - q
-        p.gbase = cp.n_groups;
-      }
-#else
-      return set_error(RT_ERR_UNSUPPORTED, "RT_SWEEP=reverse needs a library built with -DRT_SWEEP_ORDER");
-#endif
-    }
-  }
-  const SchedPlan sd = plan_sched(ft_set, sp.tree, sp.f_lds, cp.K, s->h.nodes4.size() / 8);
-  p.step_budget = sd.step_budget;
-  p.shade_min = sd.shade_min;
-  p.grab_min = sd.grab_min;
-  p.split_min = sd.split_min;
-  p.parts_log2 = sd.parts_log2;
-  p.gran_log2 = sd.gran_log2;
-  p.wave_times = nullptr;
-  p.recs_lds = sp.f_recs ? 1u : 0u;
-  p.ray_o = st->ray_o;
-  p.ray_d = st->ray_d;
-  p.hit = st->hit;
-  p.path = st->path;
-  p.pend = st->pend;
-  p.pre = st->pre;
-
-  p.stack = st->stack;
-  p.queue[0] = st->queue[0];
-  p.queue[1] = st->queue[1];
-  p.ctr = st->ctr;
-  p.accum = st->accum;
-  p.csum = use_csum ? st->csum : nullptr;
-  p.side = st->side;
-  // |v| < 2^31 / ss: the ss-sample fixed-point sum of a pixel stays inside int64 (a pass of an
-  // accumulator: the sum of all its max_passes passes, ss * max_passes < 2^31)
-  p.vlim = std::nextafter((float)(2147483648.0 / (double)((uint64_t)std::max<uint32_t>(ss, 1u) *
-                                                          (sink ? std::max<uint32_t>(sink->max_passes, 1u) : 1u))),
-                          0.0f);
-  p.pflags = st->pflags;
-  p.ostack = st->ostack;
-  p.stack_cols = st->ostack_cols;
-
+  p.vlim = sample_limit(ss, tg.sink);
   F4* dtrace = nullptr;
-  if (o.trace_out && o.trace_cap > 0) {
-    HIP_OK(hipMalloc(&dtrace, (size_t)o.trace_cap * 3 * sizeof(F4)));
-    std::vector<float> init((size_t)o.trace_cap * 12, 0.0f);
-    for (int v = 0; v < o.trace_cap; ++v) init[12 * v + 7] = -1.0f;
-    HIP_OK(hipMemcpy(dtrace, init.data(), init.size() * 4, hipMemcpyHostToDevice));
-    p.trace = dtrace;
-    p.trace_gpix = (uint32_t)o.trace_pixel;
-    p.trace_sample = (uint32_t)o.trace_sample;
-    p.trace_cap = o.trace_cap;
-  }
+  FreeOnExit<F4> trace_guard{dtrace};
+  if ((rc = start_trace(p, o, dtrace))) return rc;
   ProfEvents ev{st, (o.flags & RT_FLAG_PROFILE) != 0};
 
-  HIP_OK(hipMemsetAsync(st->ctr, 0, sizeof(Counters), stream));
-  if (npix > 0) {
-    HIP_OK(hipMemsetAsync(st->accum, 0, 3 * (size_t)npix * sizeof(unsigned long long), stream));
-    HIP_OK(hipMemsetAsync(st->side, 0, 3 * (size_t)npix * sizeof(double), stream));
-    HIP_OK(hipMemsetAsync(st->pflags, 0, (size_t)npix * sizeof(uint32_t), stream));
-  }
-  int iterations = 0;
+  if ((rc = clear_sums(st, npix, stream))) return rc;
   // rt_progress: the fused render as `slices` launches over consecutive chunk
   // ranges, an event after each (the image does not depend on the split)
   const int slices = (mode == RT_MODE_FUSED && n_chunks > 0)
                          ? std::max(1, std::min(o.progress_slices, 1024))
                          : 1;
   if (slices > 1) p.parts_log2 = 0;
-  while ((int)st->prog_events.size() < slices) {
-    hipEvent_t e;
-    HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    st->prog_events.push_back(e);
-  }
+  if ((rc = slice_events(st, slices))) return rc;
   // rt_progress: an rt_render call (slot 0) claims the record when no other render holds it
   // (rt_render_multi claims it for its shares); every return path below releases it
-  ProgressDone prog_done{s->prog, slot_id == 0 && claim_progress(s->prog, (uint64_t)npix * ss, o.device)};
-  if (prog_done.track && slices > 1) {
-    std::lock_guard<std::mutex> lk(s->prog.mu);
-    for (int sl = 0; sl < slices; ++sl) {
-      s->prog.events.push_back((void*)st->prog_events[sl]);
-      s->prog.cum.push_back((uint64_t)((double)s->prog.total *
-                                       (double)((uint64_t)n_chunks * (sl + 1) / slices) /
-                                       (double)n_chunks));
-    }
-  }
+  ProgressDone prog_done{s->prog, tg.slot_id == 0 && claim_progress(s->prog, (uint64_t)npix * ss, o.device)};
+  if (prog_done.track && slices > 1) track_slices(s->prog, st, slices, n_chunks);
+  int iterations = 0;
   if (n_chunks > 0 && mode == RT_MODE_FUSED) {
     if ((rc = launch_fused(p, st, stream, sp, fused_blocks, slices, ev))) return rc;
     iterations = 1;
   } else if (n_chunks > 0) {
     if ((rc = launch_wavefront(p, st, stream, extend_kernel, ev, &iterations))) return rc;
   }
-  float* dst = out_dev ? out_dev : st->out;
-  if (npix > 0 && sink) {  // an accumulator's pass: folded into its sums, not resolved
-    if ((rc = sink->fold(sink->ctx, p, cd.pixel_samples_scale, stream))) return rc;
-  } else if (npix > 0) {
-    hipLaunchKernelGGL(k_resolve, dim3((npix + 255) / 256), dim3(256), 0, stream, p, dst,
-                       cd.pixel_samples_scale);
-    HIP_OK(hipGetLastError());
-  }
-  if (out_host && npix > 0)
-    HIP_OK(hipMemcpyAsync(out_host, dst, 3 * (size_t)npix * sizeof(float), hipMemcpyDeviceToHost,
-                          stream));
-  if (gather && npix > 0)
-    HIP_OK(hipMemcpyPeerAsync(gather->dst, gather->dst_device, dst, o.device,
-                              3 * (size_t)npix * sizeof(float), stream));
-  HIP_OK(hipStreamSynchronize(stream));
+  if ((rc = finish_render(p, st, stream, cd.pixel_samples_scale, o.device, tg))) return rc;
   prog_done.ok = true;
   auto t_end = std::chrono::steady_clock::now();
-  if (dtrace) {
-    HIP_OK(hipMemcpy(o.trace_out, dtrace, (size_t)o.trace_cap * 3 * sizeof(F4), hipMemcpyDeviceToHost));
-    HIP_OK(hipFree(dtrace));
-  }
-
+  if ((rc = read_trace(o, dtrace))) return rc;
   if (stats) {
     if ((rc = fill_stats(stats, s, ds, st, p, sp, mode, ft_set, rows, iterations, ev))) return rc;
     stats->ms_total = std::chrono::duration<double, std::milli>(t_end - t_start).count();
@@ -1517,237 +1488,52 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
 
 int render_pass(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
                 const PassSink* sink, const PixelMap* map) {
-  return render_impl(scene, cam, opts, nullptr, nullptr, stats, 0, nullptr, sink, map);
+  RenderTarget tg;
+  tg.sink = sink;
+  tg.map = map;
+  return render_impl(scene, cam, opts, stats, tg);
 }
 
-// rows of share i ([rows_per][W][3] at gather + i*rows_per*W*3) -> image rows r = i + n*k
-__global__ __launch_bounds__(256) void k_deinterleave(const float* gather, float* out, uint32_t H,
-                                                      uint32_t W, uint32_t n, uint32_t rows_per) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t row_floats = 3ull * W;
-  if (i >= (uint64_t)H * row_floats) return;
-  const uint32_t r = (uint32_t)(i / row_floats);
-  const uint64_t x = i - (uint64_t)r * row_floats;
-  out[i] = gather[((uint64_t)(r % n) * rows_per + r / n) * row_floats + x];
+int render_share(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
+                 int share, float* out_dev, const Gather* gather) {
+  RenderTarget tg;
+  tg.slot_id = 1 + share;
+  tg.dev = out_dev;
+  tg.gather = gather;
+  return render_impl(scene, cam, opts, stats, tg);
 }
 
-// rt_render_multi: share i (rows r % n == i, camera.go:119-122) on devices[i], one
-// host thread and stream per share, each with its own render slot; the shares are
-// peer-copied to devices[0] and de-interleaved there.
-static int render_multi(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts,
-                        const int32_t* devices, int32_t n, float* out_host, float* out_dev,
-                        rt_stats* stats) {
-  if (!scene || !cam || !devices || n <= 0)
-    return set_error(RT_ERR_INVALID, "rt_render_multi: null argument or n <= 0");
-  rt_render_opts o{};
-  if (opts) o = *opts;
-  if (o.nranks > 1 || o.rank != 0)
-    return set_error(RT_ERR_INVALID, "rt_render_multi: shards the image itself (rank/nranks)");
-  if (o.stream) return set_error(RT_ERR_INVALID, "rt_render_multi: one stream per share (opts.stream)");
-  int rc;
-  for (int i = 0; i < n; ++i)
-    if ((rc = device_ok("rt_render_multi", devices[i]))) return rc;
-  rt_camera_derived cd;
-  if ((rc = rt_camera_derive(cam, &cd))) return rc;
-  Scene* s = &scene->s;
-  std::lock_guard<std::mutex> multi(s->multi_mu);
-  const auto t0 = std::chrono::steady_clock::now();
-  const uint32_t H = (uint32_t)cd.height, W = (uint32_t)cd.width, N = (uint32_t)n;
-  const uint32_t rows_per = (H + N - 1) / N;
-  const size_t gather_floats = (size_t)N * rows_per * W * 3, img_floats = (size_t)H * W * 3;
-  const int d0 = devices[0];
-  DeviceGuard dg;  // the caller's current device is restored on every return
-  HIP_OK(hipSetDevice(d0));
-  const size_t need = (gather_floats + img_floats) * sizeof(float);
-  if (!s->multi_buf || s->multi_dev != d0 || s->multi_bytes < need) {
-    if (s->multi_buf) {
-      (void)hipSetDevice(s->multi_dev);
-      (void)hipFree(s->multi_buf);
-      s->multi_buf = nullptr;
-      HIP_OK(hipSetDevice(d0));
-    }
-    HIP_OK(hipMalloc(&s->multi_buf, std::max<size_t>(need, 4)));
-    s->multi_bytes = need;
-    s->multi_dev = d0;
-  }
-  float* gbuf = (float*)s->multi_buf;
-  float* img = out_dev ? out_dev : gbuf + gather_floats;
-  // xGMI peer access both ways.  "Already enabled" is success; any other failure is
-  // an error (the copies would silently fall back to staging through host memory).
-  // Devices that report no peer path copy through the runtime's staged path.
-  auto enable_peer = [](int from, int to) -> int {
-    HIP_OK(hipSetDevice(from));
-    const hipError_t e = hipDeviceEnablePeerAccess(to, 0);
-    if (e == hipErrorPeerAccessAlreadyEnabled) {
-      (void)hipGetLastError();  // clear the sticky "already enabled" status
-      return RT_OK;
-    }
-    if (e != hipSuccess)
-      return set_error(RT_ERR_DEVICE, "rt_render_multi: peer access %d -> %d: %s", from, to,
-                       hipGetErrorString(e));
-    return RT_OK;
-  };
-  for (int i = 1; i < n; ++i)
-    if (devices[i] != d0) {
-      int can_a = 0, can_b = 0;
-      HIP_OK(hipDeviceCanAccessPeer(&can_a, devices[i], d0));
-      HIP_OK(hipDeviceCanAccessPeer(&can_b, d0, devices[i]));
-      if (can_a && (rc = enable_peer(devices[i], d0))) return rc;
-      if (can_b && (rc = enable_peer(d0, devices[i]))) return rc;
-    }
-  HIP_OK(hipSetDevice(d0));
-  // RCCL gather (RT_FLAG_GATHER_RCCL): communicators over the device list, cached
-  const bool use_rccl = (o.flags & RT_FLAG_GATHER_RCCL) != 0;
-  RcclGather* rg = nullptr;
-  const size_t share_floats = (size_t)rows_per * W * 3;
-  if (use_rccl) {
-    for (int i = 0; i < n; ++i)
-      for (int j = 0; j < i; ++j)
-        if (devices[i] == devices[j])
-          return set_error(RT_ERR_INVALID, "rt_render_multi: RCCL gather needs distinct devices");
-    if (!s->rccl) s->rccl = new RcclGather();
-    rg = static_cast<RcclGather*>(s->rccl);
-    if (rg->devs != std::vector<int>(devices, devices + n)) {
-      rg->release();
-      rg->devs.assign(devices, devices + n);
-      rg->comms.assign(n, nullptr);
-      const ncclResult_t r = ncclCommInitAll(rg->comms.data(), n, devices);
-      if (r != ncclSuccess) {
-        rg->comms.clear();
-        rg->devs.clear();
-        return set_error(RT_ERR_DEVICE, "rt_render_multi: ncclCommInitAll: %s", ncclGetErrorString(r));
-      }
-      rg->streams.assign(n, nullptr);
-      rg->send.assign(n, nullptr);
-      for (int i = 0; i < n; ++i) {
-        HIP_OK(hipSetDevice(devices[i]));
-        HIP_OK(hipStreamCreateWithFlags(&rg->streams[i], hipStreamNonBlocking));
-      }
-    }
-    if (rg->send_floats < share_floats) {
-      for (int i = 0; i < n; ++i) {
-        HIP_OK(hipSetDevice(devices[i]));
-        if (rg->send[i]) HIP_OK(hipFree(rg->send[i]));
-        rg->send[i] = nullptr;
-        HIP_OK(hipMalloc(&rg->send[i], std::max<size_t>(share_floats, 1) * sizeof(float)));
-      }
-      rg->send_floats = share_floats;
-    }
-    HIP_OK(hipSetDevice(d0));
-  }
-  // rt_progress: this call's shares are the tracked render unless another holds it.
-  // Claimed only after every early return of the setup above, so every return below
-  // releases it.  (No slice events: the shares add their samples when done.)
-  const bool track = claim_progress(s->prog, (uint64_t)H * W * cd.spp_sqrt * cd.spp_sqrt, d0);
-  ProgressDone prog_done{s->prog, track};
-  std::vector<rt_stats> st(n);
-  std::vector<int> rcs(n, RT_OK);
-  std::vector<std::string> errs(n);
-  std::vector<std::thread> th;
-  for (int i = 0; i < n; ++i)
-    th.emplace_back([&, i] {
-      rt_render_opts oi = o;
-      oi.device = devices[i];
-      oi.rank = i;
-      oi.nranks = n;
-      oi.progress_slices = 0;
-      const Gather g = {gbuf + (size_t)i * rows_per * W * 3, d0};
-      if (rg)  // the share's rows into its padded send buffer; the gather follows
-        rcs[i] = render_impl(scene, cam, &oi, nullptr, rg->send[i], &st[i], 1 + i, nullptr);
-      else
-        rcs[i] = render_impl(scene, cam, &oi, nullptr, nullptr, &st[i], 1 + i, &g);
-      if (rcs[i] != RT_OK) {
-        errs[i] = rt_last_error();
-      } else if (track) {  // rt_progress advances share by share
-        std::lock_guard<std::mutex> lk(s->prog.mu);
-        s->prog.done = std::min(s->prog.total, s->prog.done + st[i].samples);
-      }
-    });
-  for (auto& t : th) t.join();
-  for (int i = 0; i < n; ++i)
-    if (rcs[i] != RT_OK) return set_error(rcs[i], "rt_render_multi share %d: %s", i, errs[i].c_str());
-  if (rg && share_floats > 0) {
-    // one collective: every share's [rows_per][W][3] tile to devices[0]'s gather buffer
-    // (rank-major, the layout k_deinterleave reads); rows past a short share are padding
-    ncclResult_t r = ncclGroupStart();
-    for (int i = 0; r == ncclSuccess && i < n; ++i) {
-      HIP_OK(hipSetDevice(devices[i]));
-      r = ncclGather(rg->send[i], i == 0 ? (void*)gbuf : nullptr, share_floats, ncclFloat32, 0,
-                     rg->comms[i], rg->streams[i]);
-    }
-    const ncclResult_t r2 = ncclGroupEnd();
-    if (r == ncclSuccess) r = r2;
-    if (r != ncclSuccess)
-      return set_error(RT_ERR_DEVICE, "rt_render_multi: ncclGather: %s", ncclGetErrorString(r));
-    for (int i = 0; i < n; ++i) {
-      HIP_OK(hipSetDevice(devices[i]));
-      HIP_OK(hipStreamSynchronize(rg->streams[i]));
-    }
-  }
-  HIP_OK(hipSetDevice(d0));
-  if (img_floats > 0) {
-    hipLaunchKernelGGL(k_deinterleave, dim3((unsigned)((img_floats + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)0, gbuf, img, H, W, N, rows_per);
-    HIP_OK(hipGetLastError());
-    if (out_host)
-      HIP_OK(hipMemcpy(out_host, img, img_floats * sizeof(float), hipMemcpyDeviceToHost));
-  }
-  HIP_OK(hipStreamSynchronize((hipStream_t)0));
-  prog_done.ok = true;
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    *stats = st[0];
-    stats->samples = stats->segments = stats->stack_pushes = stats->overflow_samples = 0;
-    stats->extend_rays = stats->shade_rays = 0;
-    stats->rows = 0;
-    stats->ms_fused = stats->ms_extend = stats->ms_shade = 0;
-    for (int i = 0; i < n; ++i) {
-      stats->samples += st[i].samples;
-      stats->segments += st[i].segments;
-      stats->stack_pushes += st[i].stack_pushes;
-      stats->overflow_samples += st[i].overflow_samples;
-      stats->extend_rays += st[i].extend_rays;
-      stats->shade_rays += st[i].shade_rays;
-      stats->rows += st[i].rows;
-      // the slowest share bounds the render
-      stats->ms_fused = std::max(stats->ms_fused, st[i].ms_fused);
-      stats->ms_extend = std::max(stats->ms_extend, st[i].ms_extend);
-      stats->ms_shade = std::max(stats->ms_shade, st[i].ms_shade);
-    }
-    stats->ms_total =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return RT_OK;
+// the device, the scene's copy on it and the scene's structure plan, for the rt_scene_plan_*
+// entries: what plan_structure fixes per scene, before a render's background or pixel map
+static int scene_plan(const char* who, rt_scene* sc, int device, const void* out, StructurePlan* sp) {
+  if (!sc || !out) return set_error(RT_ERR_INVALID, "%s: null", who);
+  int rc = device_ok(who, device);
+  if (rc) return rc;
+  DeviceGuard dg;
+  if (hipSetDevice(device) != hipSuccess) return set_error(RT_ERR_DEVICE, "%s", who);
+  DeviceScene* ds = nullptr;
+  if ((rc = ensure_scene(&sc->s, device, &ds))) return rc;
+  return plan_structure(&sc->s, ds, scene_ft_set(&sc->s), RT_MODE_FUSED, sp);
 }
 
 }  // namespace rt
 
 extern "C" {
 
-int rt_render_multi(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
-                    const int32_t* devices, int32_t n, float* out_rgb, rt_stats* stats) {
-  if (!out_rgb) return rt::set_error(RT_ERR_INVALID, "rt_render_multi: null output");
-  return rt::render_multi(s, cam, opts, devices, n, out_rgb, nullptr, stats);
-}
-
-int rt_render_multi_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
-                           const int32_t* devices, int32_t n, float* out_rgb_device,
-                           rt_stats* stats) {
-  if (!out_rgb_device) return rt::set_error(RT_ERR_INVALID, "rt_render_multi_device: null output");
-  return rt::render_multi(s, cam, opts, devices, n, nullptr, out_rgb_device, stats);
-}
-
-
 int rt_render(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts, float* out_rgb,
               rt_stats* stats) {
   if (!out_rgb) return rt::set_error(RT_ERR_INVALID, "rt_render: null output");
-  return rt::render_impl(s, cam, opts, out_rgb, nullptr, stats);
+  rt::RenderTarget tg;
+  tg.host = out_rgb;
+  return rt::render_impl(s, cam, opts, stats, tg);
 }
 
 int rt_render_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
                      float* out_rgb_device, rt_stats* stats) {
   if (!out_rgb_device) return rt::set_error(RT_ERR_INVALID, "rt_render_device: null output");
-  return rt::render_impl(s, cam, opts, nullptr, out_rgb_device, stats);
+  rt::RenderTarget tg;
+  tg.dev = out_rgb_device;
+  return rt::render_impl(s, cam, opts, stats, tg);
 }
 
 int rt_progress(const rt_scene* sc, uint64_t* done, uint64_t* total) {
@@ -1766,31 +1552,17 @@ int rt_progress(const rt_scene* sc, uint64_t* done, uint64_t* total) {
 }
 
 int rt_scene_plan_light(rt_scene* sc, int device, int32_t* kind) {
-  if (!sc || !kind) return rt::set_error(RT_ERR_INVALID, "rt_scene_plan_light: null");
-  int rc = rt::device_ok("rt_scene_plan_light", device);
-  if (rc) return rc;
-  rt::DeviceGuard dg;
-  if (hipSetDevice(device) != hipSuccess) return rt::set_error(RT_ERR_DEVICE, "rt_scene_plan_light");
-  rt::DeviceScene* ds = nullptr;
-  if ((rc = rt::ensure_scene(&sc->s, device, &ds))) return rc;
   rt::StructurePlan sp;
-  if ((rc = rt::plan_structure(&sc->s, ds, rt::scene_ft_set(&sc->s), RT_MODE_FUSED, &sp))) return rc;
-  *kind = sp.light;
-  return RT_OK;
+  const int rc = rt::scene_plan("rt_scene_plan_light", sc, device, kind, &sp);
+  if (rc == RT_OK) *kind = sp.light;
+  return rc;
 }
 
 int rt_scene_plan_early(rt_scene* sc, int device, int32_t* early) {
-  if (!sc || !early) return rt::set_error(RT_ERR_INVALID, "rt_scene_plan_early: null");
-  int rc = rt::device_ok("rt_scene_plan_early", device);
-  if (rc) return rc;
-  rt::DeviceGuard dg;
-  if (hipSetDevice(device) != hipSuccess) return rt::set_error(RT_ERR_DEVICE, "rt_scene_plan_early");
-  rt::DeviceScene* ds = nullptr;
-  if ((rc = rt::ensure_scene(&sc->s, device, &ds))) return rc;
   rt::StructurePlan sp;
-  if ((rc = rt::plan_structure(&sc->s, ds, rt::scene_ft_set(&sc->s), RT_MODE_FUSED, &sp))) return rc;
-  *early = sp.early ? 1 : 0;
-  return RT_OK;
+  const int rc = rt::scene_plan("rt_scene_plan_early", sc, device, early, &sp);
+  if (rc == RT_OK) *early = sp.early ? 1 : 0;
+  return rc;
 }
 
 int rt_device_count(void) {

@@ -17,7 +17,7 @@ SETS_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 
 
 def main(argv):
-    srcs = [a for a in argv if a.endswith(".hip")] or ["rt_render.hip", "rt_fused_sets.hip", "rt_accum.hip", "rt_fused_map.hip"]
+    srcs = [a for a in argv if a.endswith(".hip")] or ["rt_render.hip", "rt_fused_sets.hip", "rt_accum.hip", "rt_fused_map.hip", "rt_multi.hip"]
     srcs = [s for s in srcs if os.path.exists(os.path.join(CSRC, s))]
     extra = [a for a in argv if not a.endswith(".hip")]
     out = ""
