@@ -619,11 +619,13 @@ class Scene:
         return self._aov(camera, o, n_samples, RtAov(albedo, normal, depth, material), e, True)
 
     def accumulator(self, camera, max_passes=0, device=0, rank=0, nranks=1, path_slots=0, chunk=0,
-                    profile=False, stream=None, mode="auto", progress_slices=0):
+                    profile=False, stream=None, mode="auto", progress_slices=0, features=None):
         """A progressive pass accumulator (rt_accum_create) for this rank's rows of `camera`:
-        see Accumulator.  max_passes=0 means 1024."""
+        see Accumulator.  max_passes=0 means 1024.  features="guides" keeps the albedo, normal
+        and depth of the passes' own camera samples next to the image sums, "emit" also the
+        emission split (rt_accum_set_features): see Accumulator.resolve_aov."""
         return Accumulator(self, camera, max_passes, device, rank, nranks, path_slots, chunk,
-                           profile, stream, mode, progress_slices)
+                           profile, stream, mode, progress_slices, features)
 
 
 class Accumulator:
@@ -634,12 +636,23 @@ class Accumulator:
     the set of seeds, not of their order, and one pass resolves to ``Scene.render``'s bits.
     ``resolve()`` returns the running mean image and the per-pixel variance of its luminance,
     ``info()`` one error figure for the whole image, ``render_until()`` adds passes until that
-    figure is small enough.  A context manager; closing the scene closes its accumulators."""
+    figure is small enough.  A context manager; closing the scene closes its accumulators.
+
+    ``features="guides"`` or ``"emit"`` makes every pass also sum the first-hit features of its
+    own camera samples (all of them, for whole and for active-pixel passes): ``resolve_aov()``
+    returns their means, the guides of exactly the samples in the image, and
+    ``denoise_device()`` then needs no ``aov``."""
+
+    FEATURES = {None: 0, "guides": _lib.RT_ACCUM_FEAT_GUIDES,
+                "emit": _lib.RT_ACCUM_FEAT_GUIDES | _lib.RT_ACCUM_FEAT_EMIT}
 
     def __init__(self, scene, camera, max_passes=0, device=0, rank=0, nranks=1, path_slots=0,
-                 chunk=0, profile=False, stream=None, mode="auto", progress_slices=0):
+                 chunk=0, profile=False, stream=None, mode="auto", progress_slices=0, features=None):
         self._p = None
         self._device, self._mean, self._var = device, None, None  # denoise_device's tensors
+        self._aov = None  # resolve_aov_device's
+        if features not in self.FEATURES:
+            raise ValueError(f"Accumulator: features must be None, 'guides' or 'emit', not {features!r}")
         d = camera.derived()
         self.shape = (len(range(rank, d.height, nranks)), d.width)
         c = camera.to_c()
@@ -651,11 +664,58 @@ class Accumulator:
         self._destroy = lib().rt_accum_destroy  # usable at interpreter shutdown
         self.scene = scene
         scene._accums.add(self)
+        if features is not None:
+            try:
+                check(lib().rt_accum_set_features(self._p, self.FEATURES[features]))
+            except BaseException:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_p", None):
             self._destroy(self._p)
             self._p = None
+
+    @property
+    def features(self):
+        """None, "guides" or "emit": the feature planes the passes keep (rt_accum_get_features)."""
+        m = C.c_uint32()
+        check(lib().rt_accum_get_features(self._h(), C.byref(m)))
+        return {v: k for k, v in self.FEATURES.items()}.get(m.value, m.value)
+
+    def _aov_keys(self):
+        f = self.features
+        if f is None:
+            raise ValueError("Accumulator: no feature planes (Scene.accumulator(features=...))")
+        return ("albedo", "normal", "depth") + (("emission", "surface_albedo", "coverage") if f == "emit" else ())
+
+    def resolve_aov(self):
+        """The feature buffers of exactly the camera samples the passes rendered
+        (rt_accum_resolve_aov): {"albedo", "normal", "depth"} and, with features="emit",
+        {"emission", "surface_albedo", "coverage"}, float32 arrays shaped as
+        Scene.render_aov's: per pixel the mean over its passes' samples, zeros without a pass."""
+        keys = self._aov_keys()
+        res = {k: np.zeros(self.shape + ((3,) if k not in ("depth", "coverage") else ()), np.float32)
+               for k in keys}
+        a = RtAov(*[res[k].ctypes.data for k in keys[:3]], None)
+        e = RtAovEmit(*[res[k].ctypes.data for k in keys[3:]]) if len(keys) > 3 else None
+        check(lib().rt_accum_resolve_aov(self._h(), C.byref(a), None if e is None else C.byref(e)))
+        return res
+
+    def resolve_aov_device(self):
+        """resolve_aov() into torch tensors on the accumulator's device, which the accumulator
+        owns (allocated on first use, overwritten by the next call)."""
+        import torch
+        keys = self._aov_keys()
+        if self._aov is None or tuple(self._aov) != keys:
+            dev = torch.device("cuda", self._device)
+            self._aov = {k: torch.empty(self.shape + ((3,) if k not in ("depth", "coverage") else ()),
+                                        dtype=torch.float32, device=dev) for k in keys}
+        t = self._aov
+        a = RtAov(*[t[k].data_ptr() for k in keys[:3]], None)
+        e = RtAovEmit(*[t[k].data_ptr() for k in keys[3:]]) if len(keys) > 3 else None
+        check(lib().rt_accum_resolve_aov_device(self._h(), C.byref(a), None if e is None else C.byref(e)))
+        return t
 
     __del__ = close
 
@@ -696,15 +756,31 @@ class Accumulator:
             self._h(), None if rgb_tensor is None else rgb_tensor.data_ptr(),
             None if var_tensor is None else var_tensor.data_ptr()))
 
-    def denoise_device(self, aov, out=None, var_out=None, split_emitters=False, **opts):
+    _OWN_GUIDES = object()  # denoise_device's default aov
+
+    def denoise_device(self, aov=_OWN_GUIDES, out=None, var_out=None, split_emitters=None, **opts):
         """The running mean through the variance-guided denoiser, all on the device: resolves
         into tensors the accumulator owns (allocated on first use, then reused) and runs
         denoise_var_device(mean, var, aov, out, var_out, **opts).  Returns `out` (a new tensor by
         default).  Needs two passes: one pass has no variance.  split_emitters=True: the
-        emission split (aov from render_aov_device's emission / surface_albedo / coverage)."""
+        emission split (aov from render_aov_device's emission / surface_albedo / coverage).
+        Without an aov, an accumulator with features uses its own guides
+        (resolve_aov_device()), and split_emitters then defaults to on with features="emit";
+        without features that is a ValueError.  An explicit aov=None on an accumulator without
+        features still means the unguided filter."""
         import torch
+        own = aov is None or aov is self._OWN_GUIDES
+        if own and self.features is None:
+            if aov is not None:
+                raise ValueError("Accumulator.denoise_device: needs aov, or an accumulator with features")
+            own = False
+        if own and split_emitters is None:
+            split_emitters = self.features == "emit"
+        split_emitters = bool(split_emitters)
         if self.passes < 2:
             raise ValueError("Accumulator.denoise_device: needs at least 2 passes (no variance yet)")
+        if own:
+            aov = self.resolve_aov_device()
         if self._mean is None:
             dev = torch.device("cuda", self._device)
             self._mean = torch.empty(self.shape + (3,), dtype=torch.float32, device=dev)

@@ -30,6 +30,7 @@ RT_FT_MEDIA, RT_FT_CHECKER, RT_FT_IMAGE, RT_FT_NOISE = 16, 32, 64, 128
 RT_FT_BOX = 256
 RT_FT_ALL = 511
 RT_MODE_AUTO, RT_MODE_WAVEFRONT, RT_MODE_FUSED = 0, 1, 2
+RT_ACCUM_FEAT_GUIDES, RT_ACCUM_FEAT_EMIT = 1, 2  # rt_accum_set_features' plane groups
 
 D3 = C.c_double * 3
 
@@ -291,6 +292,10 @@ SIGNATURES = {
     "rt_accum_tile_error": (_I, [_P, C.POINTER(RtAdaptOpts), C.c_void_p, C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int32)]),
     "rt_accum_adapt_info": (_I, [_P, C.POINTER(RtAdaptInfo)]),
+    "rt_accum_set_features": (_I, [_P, C.c_uint32]),
+    "rt_accum_get_features": (_I, [_P, C.POINTER(C.c_uint32)]),
+    "rt_accum_resolve_aov": (_I, [_P, C.POINTER(RtAov), C.POINTER(RtAovEmit)]),
+    "rt_accum_resolve_aov_device": (_I, [_P, C.POINTER(RtAov), C.POINTER(RtAovEmit)]),
     "rt_demo_scene": (_I, [_P, C.c_char_p, C.c_char_p, C.POINTER(RtCamera), C.POINTER(_I),
                            C.POINTER(_I)]),
     "rt_demo_scene_name": (_I, [_I, C.POINTER(C.c_char_p)]),

@@ -27,6 +27,12 @@
 // k_active_count / k_active_scan / k_active_scatter  active pixels -> the sorted map: ballot
 //                  counts per block, an exclusive scan by one block, a scatter; no atomics
 // k_count_stats    min, max and sum of a u32 array by one block (counts, tile flags)
+//
+// Feature buffers (rt_accum_set_features): a second allocation, alive only while
+// features are on, of the FeatPlanes sums (rt_hip_util.h; 56 B per pixel for the guides group,
+// 52 B for the emit group) and 56 B per pixel of staging for rt_accum_resolve_aov.  A pass then
+// also runs rt_aov.hip's k_aov_fold for the same seed and pixels on the same stream;
+// k_feat_resolve<PX> maps the sums to the rt_aov / rt_aov_emit planes.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -143,6 +149,31 @@ __global__ __launch_bounds__(256) void k_accum_resolve(AccumPlanes A, uint32_t n
     }
   }
   if (var) var[lp] = (float)var_of_mean(A.m2[lp], n);
+}
+
+// The float planes of rt_accum_resolve_aov (rt_aov's without the material, rt_aov_emit's), any null
+struct FeatOut {
+  float *albedo, *normal, *depth, *emission, *surface_albedo, *coverage;
+};
+
+// Feature sums -> their means over the n_p * ss camera samples of pixel lp: each fp64 sum
+// divided in fp64 and rounded once to fp32; a pixel without a pass resolves to zeros.  An
+// output whose group is not enabled is null (checked on the host).
+template <bool PX>
+__global__ __launch_bounds__(256) void k_feat_resolve(FeatPlanes F, uint32_t ss, Passes<PX> c, FeatOut out) {
+  const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
+  if (lp >= F.npix) return;
+  const double den = (double)passes_of(c, lp) * (double)ss;
+  const size_t n = F.npix;
+  auto mean3 = [&](const double* sum, float* o) {
+    for (int ch = 0; ch < 3; ++ch) o[3 * (size_t)lp + ch] = den > 0.0 ? (float)(sum[ch * n + lp] / den) : 0.0f;
+  };
+  if (out.albedo) mean3(F.albedo, out.albedo);
+  if (out.normal) mean3(F.normal, out.normal);
+  if (out.depth) out.depth[lp] = den > 0.0 ? (float)(F.depth[lp] / den) : 0.0f;
+  if (out.emission) mean3(F.emission, out.emission);
+  if (out.surface_albedo) mean3(F.surface_albedo, out.surface_albedo);
+  if (out.coverage) out.coverage[lp] = den > 0.0 ? (float)((double)F.nlight[lp] / den) : 0.0f;
 }
 
 constexpr int kInfoBlocks = 256;  // at most: stage 2 is one block over the partials
@@ -352,6 +383,12 @@ struct rt_accum {
   uint32_t sel_n = 0;         // active pixels of the last selection
   int32_t n_tiles = 0;
   const uint32_t* pass_map = nullptr;  // the map of the pass being folded (null: a whole pass)
+  // feature buffers: off until rt_accum_set_features
+  uint32_t features = 0;     // RT_ACCUM_FEAT_* enabled
+  void* feat_buf = nullptr;  // the enabled groups' planes | resolve staging
+  size_t feat_state_bytes = 0;
+  rt::FeatPlanes F{};
+  float* feat_stage = nullptr;  // [14][npix] floats: rt_accum_resolve_aov's planes in FeatOut's order
 };
 
 namespace rt {
@@ -387,6 +424,7 @@ int fold_pass(void* ctx, const Params& p, double scale, hipStream_t stream) {
                        px_counts(a, a->pass_map));
   }
   HIP_OK(hipGetLastError());
+  if (a->features) return aov_fold_enqueue(a->F, a->per_pixel || a->pass_map, a->pass_map, stream);
   return RT_OK;
 }
 
@@ -495,9 +533,45 @@ size_t carve(rt_accum* a, void* base) {
   return off;
 }
 
+// The feature allocation, in order: the enabled groups of a->F and the staging at `base`
+// (null: only the size is meant), feat_state_bytes -> what rt_accum_reset clears
+size_t carve_features(rt_accum* a, uint32_t planes, void* base) {
+  const size_t n = std::max<size_t>(a->npix, 1);
+  size_t off = 0;
+  auto take = [&](auto*& p, size_t count) {
+    p = (std::remove_reference_t<decltype(p)>)((uintptr_t)base + off);
+    off += count * sizeof *p;
+  };
+  a->F = FeatPlanes{};
+  a->F.npix = a->npix;
+  if (planes & RT_ACCUM_FEAT_GUIDES) {
+    take(a->F.albedo, 3 * n);
+    take(a->F.normal, 3 * n);
+    take(a->F.depth, n);
+  }
+  if (planes & RT_ACCUM_FEAT_EMIT) {
+    take(a->F.emission, 3 * n);
+    take(a->F.surface_albedo, 3 * n);
+    take(a->F.nlight, n);
+  }
+  a->feat_state_bytes = off;
+  take(a->feat_stage, 14 * n);
+  return off;
+}
+
+// features off: the feature allocation freed (the accumulator's device is current)
+void drop_features(rt_accum* a) {
+  if (a->feat_buf) (void)hipFree(a->feat_buf);
+  a->feat_buf = nullptr;
+  a->features = 0;
+  a->F = FeatPlanes{};
+  a->feat_stage = nullptr;
+}
+
 void free_accum(rt_accum* a) {
   DeviceGuard dg;
-  if (a->buf || a->own_stream) (void)hipSetDevice(a->opts.device);
+  if (a->buf || a->feat_buf || a->own_stream) (void)hipSetDevice(a->opts.device);
+  drop_features(a);
   if (a->buf) (void)hipFree(a->buf);
   if (a->own_stream) (void)hipStreamDestroy(a->own_stream);
   delete a;
@@ -529,6 +603,45 @@ int accum_resolve(rt_accum* a, float* rgb, float* var, bool host) {
   return RT_OK;
 }
 
+int accum_resolve_aov(rt_accum* a, const rt_aov* outp, const rt_aov_emit* emitp, bool host) {
+  const char* who = host ? "rt_accum_resolve_aov" : "rt_accum_resolve_aov_device";
+  if (!a) return set_error(RT_ERR_INVALID, "%s: null accumulator", who);
+  const rt_aov no_out{nullptr, nullptr, nullptr, nullptr};
+  const rt_aov_emit no_emit{nullptr, nullptr, nullptr};
+  const rt_aov& o = outp ? *outp : no_out;
+  const rt_aov_emit& e = emitp ? *emitp : no_emit;
+  if (o.material) return set_error(RT_ERR_INVALID, "%s: the accumulator keeps no material plane", who);
+  void* const user[6] = {o.albedo, o.normal, o.depth, e.emission, e.surface_albedo, e.coverage};
+  const bool guides = user[0] || user[1] || user[2], emit = user[3] || user[4] || user[5];
+  if (!guides && !emit) return set_error(RT_ERR_INVALID, "%s: no buffer wanted", who);
+  std::lock_guard<std::mutex> lk(a->mu);
+  if ((guides && !(a->features & RT_ACCUM_FEAT_GUIDES)) || (emit && !(a->features & RT_ACCUM_FEAT_EMIT)))
+    return set_error(RT_ERR_INVALID, "%s: the %s planes are not enabled (rt_accum_set_features)", who,
+                     guides && !(a->features & RT_ACCUM_FEAT_GUIDES) ? "guide" : "emit");
+  if (a->npix == 0) return RT_OK;
+  DeviceGuard dg;
+  hipStream_t stream;
+  int rc;
+  if ((rc = accum_device(a, &stream))) return rc;
+  const size_t n = a->npix;
+  const size_t floats[6] = {3 * n, 3 * n, n, 3 * n, 3 * n, n};
+  float* dev[6];  // where the kernel writes: the caller's device buffer or the plane's staging slot
+  size_t off = 0;
+  for (int i = 0; i < 6; off += floats[i++]) dev[i] = !user[i] ? nullptr : host ? a->feat_stage + off : (float*)user[i];
+  const FeatOut fo{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5]};
+  if (a->per_pixel)
+    hipLaunchKernelGGL(k_feat_resolve<true>, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->F, a->ss,
+                       px_counts(a), fo);
+  else
+    hipLaunchKernelGGL(k_feat_resolve<false>, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->F, a->ss,
+                       Passes<false>{(uint32_t)a->passes}, fo);
+  HIP_OK(hipGetLastError());
+  for (int i = 0; host && i < 6; ++i)
+    if (user[i]) HIP_OK(hipMemcpyAsync(user[i], dev[i], floats[i] * sizeof(float), hipMemcpyDeviceToHost, stream));
+  HIP_OK(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+
 // One pass as `who`: rt_accum_add's whole pass, or (active) rt_accum_add_active's over the selection
 int accum_add(rt_accum* a, const char* who, bool active, uint64_t seed, rt_stats* stats) {
   if (!a) return set_error(RT_ERR_INVALID, "%s: null accumulator", who);
@@ -547,9 +660,14 @@ int accum_add(rt_accum* a, const char* who, bool active, uint64_t seed, rt_stats
   // every pixel active: the plain whole pass (the same bits, the grouped chunk order)
   const bool part = active && a->sel_n < a->npix;
   const PixelMap pm = {a->map, a->sel_n};
+  // the feature fold's view and scratch before the render starts; its mutex until the pass ends
+  const bool fold = a->features && a->npix > 0;
+  int rc = fold ? aov_fold_begin(a->scene, a->cd, o, part ? a->sel_n : a->npix) : RT_OK;
+  if (rc) return rc;
   a->pass_map = part ? a->map : nullptr;
-  const int rc = render_pass(a->scene, &a->cam, &o, stats, &sink, part ? &pm : nullptr);
+  rc = render_pass(a->scene, &a->cam, &o, stats, &sink, part ? &pm : nullptr);
   a->pass_map = nullptr;
+  if (fold) aov_fold_end();
   if (rc == RT_OK) {
     ++a->passes;
     if (part) a->per_pixel = true;
@@ -663,12 +781,56 @@ int rt_accum_reset(rt_accum* a) {
   if ((rc = accum_device(a, &stream))) return rc;
   HIP_OK(hipMemsetAsync(a->buf, 0, a->state_bytes, stream));
   HIP_OK(hipMemsetAsync(a->A.flags, 0, std::max<size_t>(a->npix, 1) * sizeof(uint32_t), stream));
+  if (a->feat_buf) HIP_OK(hipMemsetAsync(a->feat_buf, 0, a->feat_state_bytes, stream));
   HIP_OK(hipStreamSynchronize(stream));
   a->passes = 0;
   a->per_pixel = a->sel_valid = a->sel_tiles = false;  // uniform again, no selection
   a->sel_n = 0;
   a->n_tiles = 0;
   return RT_OK;
+}
+
+int rt_accum_set_features(rt_accum* a, uint32_t planes) {
+  using namespace rt;
+  if (!a) return set_error(RT_ERR_INVALID, "rt_accum_set_features: null accumulator");
+  if (planes & ~(RT_ACCUM_FEAT_GUIDES | RT_ACCUM_FEAT_EMIT))
+    return set_error(RT_ERR_INVALID, "rt_accum_set_features: unknown planes 0x%x", planes);
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (a->passes > 0)
+    return set_error(RT_ERR_INVALID, "rt_accum_set_features: the accumulator holds %d passes (rt_accum_reset first)",
+                     a->passes);
+  if (planes == a->features) return RT_OK;
+  DeviceGuard dg;
+  HIP_OK(hipSetDevice(a->opts.device));
+  drop_features(a);
+  if (planes == 0) return RT_OK;
+  const size_t total = carve_features(a, planes, nullptr);
+  hipError_t e = hipMalloc(&a->feat_buf, total);
+  if (e == hipSuccess) e = hipMemset(a->feat_buf, 0, total);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    drop_features(a);
+    return set_error(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_DEVICE, "rt_accum_set_features: %zu bytes: %s", total,
+                     hipGetErrorString(e));
+  }
+  carve_features(a, planes, a->feat_buf);
+  a->features = planes;
+  return RT_OK;
+}
+
+int rt_accum_get_features(rt_accum* a, uint32_t* planes) {
+  if (!a || !planes) return rt::set_error(RT_ERR_INVALID, "rt_accum_get_features: null");
+  std::lock_guard<std::mutex> lk(a->mu);
+  *planes = a->features;
+  return RT_OK;
+}
+
+int rt_accum_resolve_aov(rt_accum* a, const rt_aov* out_host, const rt_aov_emit* emit_host) {
+  return rt::accum_resolve_aov(a, out_host, emit_host, true);
+}
+
+int rt_accum_resolve_aov_device(rt_accum* a, const rt_aov* out_dev, const rt_aov_emit* emit_dev) {
+  return rt::accum_resolve_aov(a, out_dev, emit_dev, false);
 }
 
 int rt_accum_add(rt_accum* a, uint64_t seed, rt_stats* stats) {

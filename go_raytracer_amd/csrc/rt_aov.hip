@@ -17,6 +17,10 @@
 // apart and sums the albedo of the other samples as surface_albedo.  One template: the EMIT
 // instances are the instructions a separate kernel compiled to, the others differ from a
 // kernel without the AovEmit argument in kernel-argument offsets only.
+//
+// k_aov_fold<TREE, EMIT, PX>: the pass accumulator's feature fold (rt_accum.hip),
+// the same samples (aov_sample is the one text of both kernels) summed into the accumulator's
+// fp64 planes for all spp_sqrt^2 samples of a pass's seed, over a whole pass or its active pixels.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -55,176 +59,240 @@ struct AovEmit {
   float* coverage;
 };
 
+// A pixel's sums over its samples, in fp32 registers in sample order
+struct AovSums {
+  f3 asum, nsum;
+  float dsum;
+  int32_t kind0;  // the material kind of sample 0's hit, -1 on a miss
+  f3 esum, ssum;  // EMIT only, as nlight
+  uint32_t nlight;
+};
+RT_D AovSums aov_sums_zero() {
+  return {mk3(0, 0, 0), mk3(0, 0, 0), 0.0f, -1, mk3(0, 0, 0), mk3(0, 0, 0), 0u};
+}
+
+// The camera ids of local pixel lp of the share, for `count` samples from sample 0
+RT_D Ids aov_ids(const Params& P, uint32_t lp, uint32_t count) {
+  Ids id;
+  const uint32_t row_l = fdiv(lp, P.fd_width);
+  id.lpix = lp;
+  id.col = lp - row_l * (uint32_t)P.width;
+  id.row = row_l * (uint32_t)P.nranks + (uint32_t)P.rank;
+  id.gpix = id.row * (uint32_t)P.width + id.col;
+  id.sample0 = 0;
+  id.count = count;
+  return id;
+}
+
+// Sample j of pixel id, added to s: the one text of the feature pass (k_aov) and of the
+// accumulator's feature fold (k_aov_fold).
 // TREE: 0 record loop (quad-only scenes: the media set's code, which covers the lean one),
 // 2 BVH2, 4 BVH4, 5 compressed BVH4 (any feature)
+template <int TREE, bool EMIT>
+RT_D void aov_sample(const Params& P, const Ids& id, uint32_t j, const TravStack& ts, AovSums& s) {
+  constexpr uint32_t FT = TREE == 0 ? (uint32_t)FT_MEDIA : (uint32_t)FT_ALL;
+  const DevScene& sc = P.sc;
+  (void)ts;
+  const rt_u32x4 r = rt_rng_draw(P.seed, id.gpix, j, RT_STREAM_CAMERA);
+  f3 o, d;
+  float time;
+  camera_ray_r<0>(P, id, j, r, o, d, time);
+  Trav tr;
+  trav_init<FT>(sc, o, d, time, tr);
+  if constexpr (TREE == 0) {
+    trav_brute<FT, true>(sc, nullptr, o, d, time, 0.001f, tr);
+  } else {
+    do {  // a near-edge rejection ends a round early (retest_near), as trace_world
+      trav_steps<false, FT, TREE != 2, TREE == 5>(sc, nullptr, false, ts, o, d, time, 0.001f, tr,
+                                                  0x7FFFFFFF);
+      retest_near<FT>(sc, o, d, 0.001f, tr);
+    } while (tr.cur != TRAV_DONE);
+  }
+  Hit h = tr.best;
+  const uint32_t ref = h.ref;
+  f3 alb = mk3(P.bg[0], P.bg[1], P.bg[2]), n = mk3(0, 0, 0);  // a miss: camera.go:300-302
+  float depth = 0.0f;
+  int32_t kind = -1;
+  bool lit = false;  // L_j
+  if (ref != PRIM_NONE) {
+    // finish_hit's refinements of the winning hit (no media, no trace)
+#ifndef RT_NO_TRI_REFINE
+    if (HAS(FT_TRI) && (ref >> 30) == PRIM_TRI)
+      refine_tri_hit(sc, ref & 0x3FFFFFFFu, o, d, h.t, h.u, h.v);
+#endif
+#ifdef RT_SPHERE32_LEAVES
+    if (HAS(FT_SPHERE) && (ref >> 30) == PRIM_SPHERE && h.v >= 0.0f)
+      refine_sphere_hit(sc, ref & 0x3FFFFFFFu, o, d, time, h.t);
+#endif
+    // shade_core's hit record: r.At(t) snapped onto the surface, the outward normal,
+    // setFaceNormal (hittable.go:27-34), and the texture coordinates
+    const float t = h.t;
+    float u = h.u, v = h.v;
+    f3 p = o + d * t;
+    const uint32_t type = ref >> 30, idx = ref & 0x3FFFFFFFu;
+    f3 nout;
+    int mat;
+    if (HAS(FT_SPHERE) && type == PRIM_SPHERE) {
+      const F4 cr = sc.sph_cr[idx], mv = sc.sph_mv[idx];
+      const f3 cc = xyz(cr) + xyz(mv) * time;
+      const double cx = (double)cr.x + (double)time * (double)mv.x;
+      const double cy = (double)cr.y + (double)time * (double)mv.y;
+      const double cz = (double)cr.z + (double)time * (double)mv.z;
+      const double ex = (double)p.x - cx, ey = (double)p.y - cy, ez = (double)p.z - cz;
+      const double rr = (double)cr.w;
+      const float dn = (float)(rr * rr - (ex * ex + ey * ey + ez * ez));
+      const f3 e = p - cc;
+      const float le = length(e);
+      const f3 nu = e * rcp(le);
+      p = p + nu * (dn * rcp(fabsf(cr.w) + le));
+      nout = cr.w < 0.0f ? -nu : nu;  // (p - c) / r objects.go:102
+      mat = (int)fbits(mv.w);
+      if (sc.mats[mat]._pad != 0.0f) {  // calculateSphereUV objects.go:44-50
+        const F2 rs = sc.sph_uv[idx];
+        const f3 no = mk3(rs.x * nout.x - rs.y * nout.z, nout.y, rs.y * nout.x + rs.x * nout.z);
+        const float theta = acosf(-no.y);
+        const float phi = atan2f(-no.z, no.x) + kPi;
+        u = phi * (0.5f * kInvPi);
+        v = theta * kInvPi;
+      }
+    } else if (!HAS(FT_TRI) || type == PRIM_QUAD) {
+      const F4* q = sc.quad + 5 * (size_t)idx;
+      nout = xyz(q[3]);
+      p = p - nout * (dot(nout, p) - q[0].w);  // onto the plane n.p = D
+      mat = (int)fbits(q[2].w);
+      if (HAS(FT_BOX) && u < 0.0f) {  // a box leaf's face: alpha, beta at this p
+        if (sc.mats[mat]._pad != 0.0f) {
+          const f3 pp = p - xyz(q[0]), w = xyz(q[4]);
+          u = dot(w, cross(pp, xyz(q[2])));
+          v = dot(w, cross(xyz(q[1]), pp));
+        } else {
+          u = v = 0.0f;
+        }
+      }
+    } else {
+      nout = tri_normal(sc, idx, u, v);
+      mat = (int)fbits(sc.tri[3 * (size_t)idx].w);
+      const uint32_t tf = fbits(sc.tri[3 * (size_t)idx + 2].w);
+      if (tf & TRI_HAS_UV) {  // objects.go:437-446
+        const F4* at = sc.tri_attr + 6 * (size_t)idx;
+        const float w = 1.0f - u - v;
+        const float tu = w * at[4].x + u * at[4].z + v * at[5].x;
+        const float tv = w * at[4].y + u * at[4].w + v * at[5].y;
+        u = tu;
+        v = tv;
+      }
+    }
+    const bool ff = dot(d, nout) < 0;
+    n = ff ? nout : -nout;
+    const DevMaterial M = sc.mats[mat];
+    kind = M.kind;
+    if (M.kind == RT_MAT_METAL) alb = xyz(M.albedo);
+    else if (M.kind == RT_MAT_DIELECTRIC) alb = mk3(1, 1, 1);
+    else if (M.kind == RT_MAT_DIFFUSE_LIGHT && !ff) alb = mk3(0, 0, 0);  // materials.go:150-155
+    else alb = tex_value<FT>(sc, M.tex, u, v, p);
+    depth = t * length(d);
+    if constexpr (EMIT) lit = M.kind == RT_MAT_DIFFUSE_LIGHT && ff;
+  }
+  if constexpr (EMIT) {
+    if (lit) {
+      // what the render adds for this sample: a light does not scatter, so rayColor returns
+      // its emission (camera.go:312-314) before the clampContribution of camera.go:330
+      s.esum = s.esum + alb;
+      ++s.nlight;
+    } else {
+      s.ssum = s.ssum + alb;
+    }
+  }
+  s.asum = s.asum + alb;
+  s.nsum = s.nsum + n;
+  s.dsum += depth;
+  if (j == 0) s.kind0 = kind;
+}
+
 template <int TREE, bool EMIT>
 __global__ __launch_bounds__(256) void k_aov(Params P, AovOut out, AovEmit em) {
   constexpr uint32_t FT = TREE == 0 ? (uint32_t)FT_MEDIA : (uint32_t)FT_ALL;
   __shared__ uint32_t lstack[kShortStack * 256];
   if constexpr (HAS(FT_NOISE)) stage_perlin(P.sc);
   __syncthreads();
-  const DevScene& sc = P.sc;
   const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
   const TravStack ts = {&lstack[threadIdx.x], P.ostack + gtid, P.stack_cols, kShortStack};
-  (void)ts;
   const uint32_t stride = gridDim.x * blockDim.x;
   for (uint32_t lp = gtid; lp < P.npix; lp += stride) {
-    Ids id;
-    const uint32_t row_l = fdiv(lp, P.fd_width);
-    id.lpix = lp;
-    id.col = lp - row_l * (uint32_t)P.width;
-    id.row = row_l * (uint32_t)P.nranks + (uint32_t)P.rank;
-    id.gpix = id.row * (uint32_t)P.width + id.col;
-    id.sample0 = 0;
-    id.count = out.n;
-    f3 asum = mk3(0, 0, 0), nsum = mk3(0, 0, 0);
-    float dsum = 0.0f;
-    int32_t kind0 = -1;
-    f3 esum = mk3(0, 0, 0), ssum = mk3(0, 0, 0);  // EMIT only, as nlight and lit
-    uint32_t nlight = 0;
-    for (uint32_t j = 0; j < out.n; ++j) {
-      const rt_u32x4 r = rt_rng_draw(P.seed, id.gpix, j, RT_STREAM_CAMERA);
-      f3 o, d;
-      float time;
-      camera_ray_r<0>(P, id, j, r, o, d, time);
-      Trav tr;
-      trav_init<FT>(sc, o, d, time, tr);
-      if constexpr (TREE == 0) {
-        trav_brute<FT, true>(sc, nullptr, o, d, time, 0.001f, tr);
-      } else {
-        do {  // a near-edge rejection ends a round early (retest_near), as trace_world
-          trav_steps<false, FT, TREE != 2, TREE == 5>(sc, nullptr, false, ts, o, d, time, 0.001f, tr,
-                                                      0x7FFFFFFF);
-          retest_near<FT>(sc, o, d, 0.001f, tr);
-        } while (tr.cur != TRAV_DONE);
-      }
-      Hit h = tr.best;
-      const uint32_t ref = h.ref;
-      f3 alb = mk3(P.bg[0], P.bg[1], P.bg[2]), n = mk3(0, 0, 0);  // a miss: camera.go:300-302
-      float depth = 0.0f;
-      int32_t kind = -1;
-      bool lit = false;  // L_j
-      if (ref != PRIM_NONE) {
-        // finish_hit's refinements of the winning hit (no media, no trace)
-#ifndef RT_NO_TRI_REFINE
-        if (HAS(FT_TRI) && (ref >> 30) == PRIM_TRI)
-          refine_tri_hit(sc, ref & 0x3FFFFFFFu, o, d, h.t, h.u, h.v);
-#endif
-#ifdef RT_SPHERE32_LEAVES
-        if (HAS(FT_SPHERE) && (ref >> 30) == PRIM_SPHERE && h.v >= 0.0f)
-          refine_sphere_hit(sc, ref & 0x3FFFFFFFu, o, d, time, h.t);
-#endif
-        // shade_core's hit record: r.At(t) snapped onto the surface, the outward normal,
-        // setFaceNormal (hittable.go:27-34), and the texture coordinates
-        const float t = h.t;
-        float u = h.u, v = h.v;
-        f3 p = o + d * t;
-        const uint32_t type = ref >> 30, idx = ref & 0x3FFFFFFFu;
-        f3 nout;
-        int mat;
-        if (HAS(FT_SPHERE) && type == PRIM_SPHERE) {
-          const F4 cr = sc.sph_cr[idx], mv = sc.sph_mv[idx];
-          const f3 cc = xyz(cr) + xyz(mv) * time;
-          const double cx = (double)cr.x + (double)time * (double)mv.x;
-          const double cy = (double)cr.y + (double)time * (double)mv.y;
-          const double cz = (double)cr.z + (double)time * (double)mv.z;
-          const double ex = (double)p.x - cx, ey = (double)p.y - cy, ez = (double)p.z - cz;
-          const double rr = (double)cr.w;
-          const float dn = (float)(rr * rr - (ex * ex + ey * ey + ez * ez));
-          const f3 e = p - cc;
-          const float le = length(e);
-          const f3 nu = e * rcp(le);
-          p = p + nu * (dn * rcp(fabsf(cr.w) + le));
-          nout = cr.w < 0.0f ? -nu : nu;  // (p - c) / r objects.go:102
-          mat = (int)fbits(mv.w);
-          if (sc.mats[mat]._pad != 0.0f) {  // calculateSphereUV objects.go:44-50
-            const F2 rs = sc.sph_uv[idx];
-            const f3 no = mk3(rs.x * nout.x - rs.y * nout.z, nout.y, rs.y * nout.x + rs.x * nout.z);
-            const float theta = acosf(-no.y);
-            const float phi = atan2f(-no.z, no.x) + kPi;
-            u = phi * (0.5f * kInvPi);
-            v = theta * kInvPi;
-          }
-        } else if (!HAS(FT_TRI) || type == PRIM_QUAD) {
-          const F4* q = sc.quad + 5 * (size_t)idx;
-          nout = xyz(q[3]);
-          p = p - nout * (dot(nout, p) - q[0].w);  // onto the plane n.p = D
-          mat = (int)fbits(q[2].w);
-          if (HAS(FT_BOX) && u < 0.0f) {  // a box leaf's face: alpha, beta at this p
-            if (sc.mats[mat]._pad != 0.0f) {
-              const f3 pp = p - xyz(q[0]), w = xyz(q[4]);
-              u = dot(w, cross(pp, xyz(q[2])));
-              v = dot(w, cross(xyz(q[1]), pp));
-            } else {
-              u = v = 0.0f;
-            }
-          }
-        } else {
-          nout = tri_normal(sc, idx, u, v);
-          mat = (int)fbits(sc.tri[3 * (size_t)idx].w);
-          const uint32_t tf = fbits(sc.tri[3 * (size_t)idx + 2].w);
-          if (tf & TRI_HAS_UV) {  // objects.go:437-446
-            const F4* at = sc.tri_attr + 6 * (size_t)idx;
-            const float w = 1.0f - u - v;
-            const float tu = w * at[4].x + u * at[4].z + v * at[5].x;
-            const float tv = w * at[4].y + u * at[4].w + v * at[5].y;
-            u = tu;
-            v = tv;
-          }
-        }
-        const bool ff = dot(d, nout) < 0;
-        n = ff ? nout : -nout;
-        const DevMaterial M = sc.mats[mat];
-        kind = M.kind;
-        if (M.kind == RT_MAT_METAL) alb = xyz(M.albedo);
-        else if (M.kind == RT_MAT_DIELECTRIC) alb = mk3(1, 1, 1);
-        else if (M.kind == RT_MAT_DIFFUSE_LIGHT && !ff) alb = mk3(0, 0, 0);  // materials.go:150-155
-        else alb = tex_value<FT>(sc, M.tex, u, v, p);
-        depth = t * length(d);
-        if constexpr (EMIT) lit = M.kind == RT_MAT_DIFFUSE_LIGHT && ff;
-      }
-      if constexpr (EMIT) {
-        if (lit) {
-          // what the render adds for this sample: a light does not scatter, so rayColor returns
-          // its emission (camera.go:312-314) before the clampContribution of camera.go:330
-          esum = esum + alb;
-          ++nlight;
-        } else {
-          ssum = ssum + alb;
-        }
-      }
-      asum = asum + alb;
-      nsum = nsum + n;
-      dsum += depth;
-      if (j == 0) kind0 = kind;
-    }
+    const Ids id = aov_ids(P, lp, out.n);
+    AovSums s = aov_sums_zero();
+    for (uint32_t j = 0; j < out.n; ++j) aov_sample<TREE, EMIT>(P, id, j, ts, s);
     const float inv = 1.0f / (float)out.n;
     if (out.albedo) {
-      out.albedo[3 * (size_t)lp + 0] = asum.x * inv;
-      out.albedo[3 * (size_t)lp + 1] = asum.y * inv;
-      out.albedo[3 * (size_t)lp + 2] = asum.z * inv;
+      out.albedo[3 * (size_t)lp + 0] = s.asum.x * inv;
+      out.albedo[3 * (size_t)lp + 1] = s.asum.y * inv;
+      out.albedo[3 * (size_t)lp + 2] = s.asum.z * inv;
     }
     if (out.normal) {
-      out.normal[3 * (size_t)lp + 0] = nsum.x * inv;
-      out.normal[3 * (size_t)lp + 1] = nsum.y * inv;
-      out.normal[3 * (size_t)lp + 2] = nsum.z * inv;
+      out.normal[3 * (size_t)lp + 0] = s.nsum.x * inv;
+      out.normal[3 * (size_t)lp + 1] = s.nsum.y * inv;
+      out.normal[3 * (size_t)lp + 2] = s.nsum.z * inv;
     }
-    if (out.depth) out.depth[lp] = dsum * inv;
-    if (out.material) out.material[lp] = kind0;
+    if (out.depth) out.depth[lp] = s.dsum * inv;
+    if (out.material) out.material[lp] = s.kind0;
     if constexpr (EMIT) {
       if (em.emission) {
-        em.emission[3 * (size_t)lp + 0] = esum.x * inv;
-        em.emission[3 * (size_t)lp + 1] = esum.y * inv;
-        em.emission[3 * (size_t)lp + 2] = esum.z * inv;
+        em.emission[3 * (size_t)lp + 0] = s.esum.x * inv;
+        em.emission[3 * (size_t)lp + 1] = s.esum.y * inv;
+        em.emission[3 * (size_t)lp + 2] = s.esum.z * inv;
       }
       if (em.surface_albedo) {
-        em.surface_albedo[3 * (size_t)lp + 0] = ssum.x * inv;
-        em.surface_albedo[3 * (size_t)lp + 1] = ssum.y * inv;
-        em.surface_albedo[3 * (size_t)lp + 2] = ssum.z * inv;
+        em.surface_albedo[3 * (size_t)lp + 0] = s.ssum.x * inv;
+        em.surface_albedo[3 * (size_t)lp + 1] = s.ssum.y * inv;
+        em.surface_albedo[3 * (size_t)lp + 2] = s.ssum.z * inv;
       }
       // a true division (the build's fp32 divide is not correctly rounded): through fp64, whose
       // 53 bits >= 2 * 24 + 2 make the second rounding innocuous, so nlight == n gives 1.0f
-      if (em.coverage) em.coverage[lp] = (float)((double)nlight / (double)out.n);
+      if (em.coverage) em.coverage[lp] = (float)((double)s.nlight / (double)out.n);
+    }
+  }
+}
+
+// The accumulator's feature fold: k_aov's loop over the P.npix pixels of one
+// pass, all P.ss samples of P.seed each, the per-pass fp32 sums added to the fp64 planes F
+// instead of being averaged.  PX, as k_accum_fold's: the pass's pixel v is local pixel
+// p = map[v] of the share (map null: p = v), and every camera id comes from p, so an active
+// pass casts the rays rt_accum_add(seed) casts for that pixel.  One writer per pixel, no
+// atomics; count[] is k_accum_fold's.  v < P.npix <= F.npix and map[v] < F.npix (the
+// compaction's sorted list of local pixels), so every store is inside its plane.
+template <int TREE, bool EMIT, bool PX>
+__global__ __launch_bounds__(256) void k_aov_fold(Params P, FeatPlanes F, const uint32_t* map) {
+  constexpr uint32_t FT = TREE == 0 ? (uint32_t)FT_MEDIA : (uint32_t)FT_ALL;
+  __shared__ uint32_t lstack[kShortStack * 256];
+  if constexpr (HAS(FT_NOISE)) stage_perlin(P.sc);
+  __syncthreads();
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const TravStack ts = {&lstack[threadIdx.x], P.ostack + gtid, P.stack_cols, kShortStack};
+  const uint32_t stride = gridDim.x * blockDim.x;
+  const size_t n = F.npix;
+  for (uint32_t v = gtid; v < P.npix; v += stride) {
+    uint32_t p = v;
+    if constexpr (PX) p = map ? map[v] : v;
+    const Ids id = aov_ids(P, p, P.ss);
+    AovSums s = aov_sums_zero();
+    for (uint32_t j = 0; j < P.ss; ++j) aov_sample<TREE, EMIT>(P, id, j, ts, s);
+    if (F.albedo) {  // the guides group
+      F.albedo[p] += (double)s.asum.x;
+      F.albedo[n + p] += (double)s.asum.y;
+      F.albedo[2 * n + p] += (double)s.asum.z;
+      F.normal[p] += (double)s.nsum.x;
+      F.normal[n + p] += (double)s.nsum.y;
+      F.normal[2 * n + p] += (double)s.nsum.z;
+      F.depth[p] += (double)s.dsum;
+    }
+    if constexpr (EMIT) {
+      F.emission[p] += (double)s.esum.x;
+      F.emission[n + p] += (double)s.esum.y;
+      F.emission[2 * n + p] += (double)s.esum.z;
+      F.surface_albedo[p] += (double)s.ssum.x;
+      F.surface_albedo[n + p] += (double)s.ssum.y;
+      F.surface_albedo[2 * n + p] += (double)s.ssum.z;
+      F.nlight[p] += s.nlight;
     }
   }
 }
@@ -361,7 +429,63 @@ int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, 
   return RT_OK;
 }
 
+// the pass aov_fold_begin prepared, valid while it holds g_mu
+struct {
+  Params p;
+  int tree, blocks;
+} g_fold;
+
+template <int TREE>
+void launch_fold(bool emit, bool px, hipStream_t stream, const FeatPlanes& F, const uint32_t* map) {
+  const dim3 g((unsigned)g_fold.blocks), b(256);
+  if (emit && px) hipLaunchKernelGGL((k_aov_fold<TREE, true, true>), g, b, 0, stream, g_fold.p, F, map);
+  else if (emit) hipLaunchKernelGGL((k_aov_fold<TREE, true, false>), g, b, 0, stream, g_fold.p, F, map);
+  else if (px) hipLaunchKernelGGL((k_aov_fold<TREE, false, true>), g, b, 0, stream, g_fold.p, F, map);
+  else hipLaunchKernelGGL((k_aov_fold<TREE, false, false>), g, b, 0, stream, g_fold.p, F, map);
+}
+
 }  // namespace
+
+int aov_fold_begin(rt_scene* scene, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t n_pass) {
+  int rc;
+  if ((rc = device_ok("rt_accum_add", o.device))) return rc;
+  DeviceGuard dg;
+  HIP_OK(hipSetDevice(o.device));
+  AovView view;
+  if ((rc = aov_view(&scene->s, o.device, &view))) return rc;
+  std::unique_lock<std::mutex> lk(g_mu);
+  const int blocks = (int)std::min<uint32_t>((n_pass + 255u) / 256u,
+                                             (uint32_t)(view.tree == 0 ? kAovMaxBlocks : kAovMaxTreeBlocks));
+  const uint32_t cols = (uint32_t)blocks * 256u;  // an overflow-stack column per launched thread
+  void* ost = nullptr;
+  if ((rc = g_stacks.get(o.device, (size_t)(view.tree == 0 ? 1 : kStack - kShortStack) * cols * sizeof(uint32_t), &ost,
+                         "rt_accum_add")))
+    return rc;
+  g_fold.p = Params{};
+  g_fold.p.sc = view.sc;
+  set_camera_params(g_fold.p, cd, o, n_pass);
+  g_fold.p.ostack = (uint32_t*)ost;
+  g_fold.p.stack_cols = cols;
+  g_fold.tree = view.tree;
+  g_fold.blocks = blocks;
+  lk.release();  // held until aov_fold_end
+  return RT_OK;
+}
+
+int aov_fold_enqueue(const FeatPlanes& F, bool px, const uint32_t* map, hipStream_t stream) {
+  const bool emit = F.emission != nullptr;
+  switch (g_fold.tree) {
+    case 0: launch_fold<0>(emit, px, stream, F, map); break;
+    case 2: launch_fold<2>(emit, px, stream, F, map); break;
+    case 5: launch_fold<5>(emit, px, stream, F, map); break;
+    default: launch_fold<4>(emit, px, stream, F, map); break;
+  }
+  HIP_OK(hipGetLastError());
+  return RT_OK;
+}
+
+void aov_fold_end() { g_mu.unlock(); }
+
 }  // namespace rt
 
 extern "C" {

@@ -82,6 +82,28 @@ struct Gather {
 int render_share(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
                  int share, float* out_dev, const Gather* gather);
 
+// The accumulator's feature sums, a structure of planes over the npix pixels of
+// the share: the per-pass fp32 sums of the feature rays (rt_aov.hip k_aov_fold), added in fp64.
+// A group that is not enabled has null pointers.
+struct FeatPlanes {
+  double* albedo;          // [3][npix]  the RT_ACCUM_FEAT_GUIDES group
+  double* normal;          // [3][npix]
+  double* depth;           // [npix]
+  double* emission;        // [3][npix]  the RT_ACCUM_FEAT_EMIT group
+  double* surface_albedo;  // [3][npix]
+  uint32_t* nlight;        // [npix]     samples whose first hit is a light's front face (exact)
+  uint32_t npix;
+};
+// rt_aov.hip, for the accumulator (rt_accum.hip): the feature fold of one pass.  aov_fold_begin
+// does what can fail without a launch, before the render starts: the scene's aov_view on
+// o.device and the overflow-stack scratch for a pass of n_pass pixels; on RT_OK it holds the
+// feature pass's mutex until aov_fold_end (after the pass's stream is synchronised).  Between
+// the two, aov_fold_enqueue launches k_aov_fold on `stream` for o.seed: the pass's pixel v is
+// pixel map[v] of the share (px), or v when map is null.
+int aov_fold_begin(rt_scene* scene, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t n_pass);
+int aov_fold_enqueue(const FeatPlanes& F, bool px, const uint32_t* map, hipStream_t stream);
+void aov_fold_end();
+
 // Grow-only device scratch, one buffer per device ordinal (as rt_output.hip's): no allocation
 // per call once warm.  The caller serialises its users, and no work that reads an old buffer
 // may be in flight when a larger one is asked for (the old one is freed).

@@ -34,7 +34,10 @@
 // has fewer than the library's min_passes, then passes over the tiles whose error figure is
 // above E only, until none is left or -passes, default 1024, is reached; composes with
 // -denoise[-var], -aov and -o; the statistics line gains active_last, samples_total and
-// samples_full), -counts FILE (with -adaptive: the passes per pixel as grey, count / max).  -cpuprofile has no pprof to drive on the GPU path: the file
+// samples_full), -accum-features (with -passes / -until / -adaptive: the accumulator keeps the
+// feature sums of its passes' own camera samples, rt_accum_set_features, and the denoisers and
+// -aov take those guides instead of a separate feature pass; without an accumulating flag a
+// usage error; the statistics line gains "accum_features": 1), -counts FILE (with -adaptive: the passes per pixel as grey, count / max).  -cpuprofile has no pprof to drive on the GPU path: the file
 // receives the same JSON statistics instead.
 #include <unistd.h>
 
@@ -69,6 +72,7 @@ struct Args {
   bool adaptive_set = false;
   unsigned long long seed = 1, tree_seed = 1;
   bool progress = false, stats = false, denoise = false, denoise_var = false, split_emitters = false;
+  bool accum_features = false;
 };
 
 std::vector<Flag> flags(Args& a) {
@@ -76,6 +80,8 @@ std::vector<Flag> flags(Args& a) {
       {"N", "Set the number of cores to allocate to rendering", Flag::INT, &a.N, "1"},
       {"S", "Set the scene to render, default will render a custom scene function", Flag::INT,
        &a.S, "-1"},
+      {"accum-features", "with -passes, -until or -adaptive: the denoiser's and -aov's feature buffers come from the accumulator (the passes' own camera samples), not from a separate feature pass",
+       Flag::BOOL, &a.accum_features, ""},
       {"adaptive", "adaptive passes: after the first whole passes, resample only the tiles whose relative error is > E (at most -passes, default 1024)",
        Flag::F64, &a.adaptive, ""},
       {"aov", "write PREFIX_albedo.ppm, PREFIX_normal.ppm and PREFIX_depth.ppm (first-hit feature buffers)",
@@ -238,9 +244,12 @@ int fail(const char* what, int rc) {
 std::string stats_json(const rt_stats& st, const rt_camera_derived& d, const char* scene,
                        double wall_s, int aov_samples, double ms_aov, double ms_denoise,
                        const rt_accum_info* acc, double ms_accum, bool denoise_var,
-                       const rt_adapt_info* ad = nullptr, bool split_emitters = false) {
+                       const rt_adapt_info* ad = nullptr, bool split_emitters = false,
+                       bool accum_features = false) {
   char b[1280], extra[200] = "", extra2[200] = "";
-  const char* extra3 = split_emitters ? "\"split_emitters\": 1, " : "";
+  const std::string extra3s = std::string(split_emitters ? "\"split_emitters\": 1, " : "") +
+                              (accum_features ? "\"accum_features\": 1, " : "");
+  const char* extra3 = extra3s.c_str();
   if (acc)  // -passes / -until
     snprintf(extra, sizeof extra, "\"passes\": %d, \"rel_error\": %.6g, \"ms_accum\": %.3f, %s", acc->passes,
              acc->rel_error, ms_accum, denoise_var ? "\"denoise_var\": 1, " : "");
@@ -286,6 +295,11 @@ int main(int argc, char** argv) {
   }
   if (a.split_emitters && !a.denoise && !a.denoise_var) {  // nothing to split for
     fprintf(stderr, "-split-emitters needs -denoise or -denoise-var\n");
+    usage(argv[0], flags(a));
+    return 2;
+  }
+  if (a.accum_features && !(a.passes > 0 || a.until > 0.0 || a.adaptive_set)) {  // no accumulator to keep them
+    fprintf(stderr, "-accum-features needs -passes, -until or -adaptive\n");
     usage(argv[0], flags(a));
     return 2;
   }
@@ -360,6 +374,9 @@ int main(int argc, char** argv) {
   double ms_accum = 0.0;
   if (accumulate && (rc = rt_accum_create(sc, &cam, &o, pass_cap, &acc)) != RT_OK)
     return fail("rt_accum_create", rc);
+  if (a.accum_features &&
+      (rc = rt_accum_set_features(acc, RT_ACCUM_FEAT_GUIDES | (a.split_emitters ? RT_ACCUM_FEAT_EMIT : 0u))) != RT_OK)
+    return fail("rt_accum_set_features", rc);
 
   bool counts_failed = false;
   std::atomic<bool> rendering{true};
@@ -451,13 +468,17 @@ int main(int argc, char** argv) {
     std::vector<float> albedo(3 * np), normal(3 * np), depth(np);
     rt_aov f = {albedo.data(), normal.data(), depth.data(), nullptr};
     aov_samples = d.spp_sqrt * d.spp_sqrt < 16 ? d.spp_sqrt * d.spp_sqrt : 16;
+    if (a.accum_features) aov_samples = d.spp_sqrt * d.spp_sqrt;  // of every pass the pixel took
     rt_stats sa;
     auto ta = std::chrono::steady_clock::now();
     // -split-emitters: the split feature pass and the split filter
     std::vector<float> emission(a.split_emitters ? 3 * np : 0), salbedo(a.split_emitters ? 3 * np : 0),
         coverage(a.split_emitters ? np : 0);
     rt_aov_emit fe = {emission.data(), salbedo.data(), coverage.data()};
-    if (a.split_emitters) {
+    if (a.accum_features) {  // the guides of the passes' own samples: no feature pass
+      if ((rc = rt_accum_resolve_aov(acc, &f, a.split_emitters ? &fe : nullptr)) != RT_OK)
+        return fail("rt_accum_resolve_aov", rc);
+    } else if (a.split_emitters) {
       if ((rc = rt_render_aov_emit(sc, &cam, &o, aov_samples, &f, &fe, &sa)) != RT_OK)
         return fail("rt_render_aov_emit", rc);
     } else if ((rc = rt_render_aov(sc, &cam, &o, aov_samples, &f, &sa)) != RT_OK) {
@@ -520,7 +541,8 @@ int main(int argc, char** argv) {
   if (write_ppm(rgb, d.width, d.height, out, a.out.c_str())) return 1;
   double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::string js = stats_json(st, d, scene, wall, aov_samples, ms_aov, ms_denoise, accumulate ? &ai : nullptr,
-                              ms_accum, a.denoise_var, a.adaptive_set ? &adi : nullptr, a.split_emitters);
+                              ms_accum, a.denoise_var, a.adaptive_set ? &adi : nullptr, a.split_emitters,
+                              a.accum_features);
   if (a.stats || a.denoise || a.denoise_var) fprintf(stderr, "%s\n", js.c_str());
   if (!a.cpuprofile.empty()) {
     FILE* p = fopen(a.cpuprofile.c_str(), "w");

@@ -672,7 +672,7 @@ typedef struct rt_accum rt_accum;
  * passes it will take, 0 = 1024; negative, or spp_sqrt^2 * max_passes >= 2^31, is
  * RT_ERR_INVALID.  Arguments are checked before any device is touched.  About 76 bytes of
  * device memory per pixel of the share (plus 16 for rt_accum_resolve's staging), allocated
- * here; no call below allocates.  The scene owns its accumulators: rt_scene_destroy frees
+ * here; no call below allocates but rt_accum_set_features.  The scene owns its accumulators: rt_scene_destroy frees
  * those still alive (their handles are dead after it), rt_accum_destroy frees one early.
  * Calls on one accumulator serialise; passes and rt_render calls of one scene may interleave
  * (a pass holds the same per-device lock as rt_render while it runs). */
@@ -769,6 +769,37 @@ typedef struct {
   int32_t n_tiles, active_tiles;  /* of the last rt_accum_select (0 after rt_accum_set_active) */
 } rt_adapt_info;
 int rt_accum_adapt_info(rt_accum* a, rt_adapt_info* out);
+
+/* Accumulator-owned feature buffers (DESIGN.md "Accumulator-owned feature buffers"): the
+ * feature sums of exactly the camera samples the accumulator's passes rendered, kept per pixel
+ * on the device next to the image sums.  Added without an ABI version change: detect by the
+ * symbols.
+ *
+ * rt_accum_set_features chooses the plane groups (a mask of RT_ACCUM_FEAT_*; 0 frees them): only
+ * while the accumulator holds no pass (else RT_ERR_INVALID, as for unknown bits).  The planes
+ * are a second allocation of 56 (guides) + 52 (emit) bytes per pixel of the share plus 56 of
+ * staging; RT_ERR_OOM leaves the features off.  With features on, every rt_accum_add /
+ * rt_accum_add_active also casts, for the same seed and the same pixels and on the same stream,
+ * the feature rays of ALL spp_sqrt^2 samples (the rays, the hit evaluation and L_j of
+ * rt_render_aov_emit), sums them per pass in fp32 in sample order as rt_render_aov does and adds
+ * the pass's sums to fp64 sums (the light-sample count to an exact integer).  The image sums,
+ * the variance and the pass's rt_stats are not affected; the pass is counted only when both were
+ * enqueued.  rt_accum_reset clears the feature sums and keeps the setting.
+ *
+ * rt_accum_resolve_aov writes, for a pixel that took n passes (N = n spp_sqrt^2 samples), every
+ * plane as (float)(sum / N) with the division in fp64, coverage = (float)(light samples / N), and
+ * zeros where n = 0: one pass of seed s gives rt_render_aov_emit(n_samples = spp_sqrt^2, seed s)
+ * to within the rounding of that call's reciprocal (bit-equal when spp_sqrt^2 is a power of two;
+ * coverage always).  Any pointer may be NULL, emit may be NULL; RT_ERR_INVALID when a group is
+ * asked for that is not enabled, when out->material is not NULL (no material plane is kept:
+ * "the kind of sample 0" has no meaning over several passes) or when no buffer is wanted.
+ * _device: pointers on the accumulator's device; both forms return after the work completes. */
+#define RT_ACCUM_FEAT_GUIDES 1u   /* albedo, normal, depth */
+#define RT_ACCUM_FEAT_EMIT   2u   /* emission, surface_albedo, coverage */
+int rt_accum_set_features(rt_accum* a, uint32_t planes);
+int rt_accum_get_features(rt_accum* a, uint32_t* planes);
+int rt_accum_resolve_aov(rt_accum* a, const rt_aov* out_host, const rt_aov_emit* emit_host);
+int rt_accum_resolve_aov_device(rt_accum* a, const rt_aov* out_dev, const rt_aov_emit* emit_dev);
 
 /* Demo scenes mirroring main.go (by name or the main.go -S number).
  * names: book1, book2, book3, simple_light, quads, cornell, cornell_smoke, model
