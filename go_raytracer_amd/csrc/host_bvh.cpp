@@ -436,7 +436,7 @@ int build_bvh(HostScene& s, const std::vector<F4>& lo, const std::vector<F4>& hi
     for (int k = 0; k < 4; ++k) {
       uint32_t code = CHILD_EMPTY;
       // empty slot: an inverted infinite box (lo = +inf, hi = -inf), which the
-      // sign-selected slab test (rt_path.h trav_steps) never hits; the min/max slab
+      // sign-selected slab test (rt_trav.h trav_steps) never hits; the min/max slab
       // tests (LDS trees) skip it by its code
       Box b;
       for (int a = 0; a < 3; ++a) b.mn[a] = INFINITY, b.mx[a] = -INFINITY;

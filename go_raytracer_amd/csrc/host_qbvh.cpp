@@ -138,7 +138,7 @@ int build_qbvh(const HostScene& h, const std::vector<F4>& recs, std::vector<F4>*
     uint32_t leafmask = 0;
     for (int k = 0; k < 4; ++k) {
       for (int a = 0; a < 3; ++a) {
-        if (empty[k]) {  // an inverted infinite box: never hit (rt_path.h trav_steps)
+        if (empty[k]) {  // an inverted infinite box: never hit (rt_trav.h trav_steps)
           planes[a][0][k] = 0x7C00;
           planes[a][1][k] = 0xFC00;
         } else {

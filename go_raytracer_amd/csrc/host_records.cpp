@@ -108,7 +108,7 @@ struct Records {
   // Axis-aligned quads (unit normal +-e_a, A_a = B_a = 0 exactly: Cornell's walls,
   // floor, ceiling and box tops) go in per-axis pair groups after the general
   // pairs; the loop tests them with the in-plane terms only, bit-identical to the
-  // general test (rt_path.h brute_axis).  An odd record of a group joins the
+  // general test (rt_records.h brute_axis).  An odd record of a group joins the
   // general list.  RT_BRUTE_AXIS=0 keeps every record general (A/B).
   int axis_of(size_t i) const {
     const F4* r = &recs[4 * i];
@@ -125,7 +125,7 @@ struct Records {
   }
   // y-parallel quads (n_y = A_y = 0 and B = (0, B_y, 0) exactly: the sides of Cornell's
   // boxes rotated about y) go in a pair group between the general and the axis-aligned
-  // ones (rt_path.h brute_vert: the general test without its exact-zero terms, images
+  // ones (rt_records.h brute_vert: the general test without its exact-zero terms, images
   // bit-identical; C2 -1.6 % against RT_BRUTE_VERT=0, which keeps them general).
   int vert_of(size_t i) const {
     const F4* r = &recs[4 * i];
@@ -142,7 +142,7 @@ struct Records {
 // the eight corners of one box with a horizontal top and bottom.  The loop tests each
 // such box once, as three slabs in the box's own frame -- the reference's rotateY.Hit
 // frame, where each face's quad test is t = (k - o'_a) / d'_a -- instead of its six
-// records (rt_path.h brute_box).  The face records stay in the array (after the box
+// records (rt_records.h brute_box).  The face records stay in the array (after the box
 // descriptors) for the winner's u, v and ref.  RT_BRUTE_BOX=0 keeps them in the groups.
 struct BoxRec { size_t face[6]; double C[3], ax[3], az[3], H; };
 std::vector<BoxRec> find_boxes(const HostScene& h, const std::vector<size_t>& ord,
@@ -248,7 +248,7 @@ Groups group_records(const Records& R, const std::vector<size_t>& ord, const std
     grp[a >= 0 ? a : v >= 0 ? 4 + v : 3].push_back(i);
   }
   // The odd records of two axis-aligned groups of different axes form one mixed pair, each
-  // half tested on its own axis (rt_path.h brute_mixed: the axis test, bit for bit, ~35 VALU
+  // half tested on its own axis (rt_records.h brute_mixed: the axis test, bit for bit, ~35 VALU
   // where the general pair was ~85; Cornell's light and back wall).  Any other odd record
   // joins the general list.  (Padding each odd group with a never-hit record instead measured
   // 2.5 % slower on C2: one more loop and its per-axis setup.)  RT_BRUTE_MIXED=0: no mixed pair.
@@ -318,7 +318,7 @@ std::vector<F4> interleave_pairs(const Records& R, const SlotOrder& so, const st
   const auto& slots = so.slots;
   std::vector<F4> pairs(4 * slots.size(), F4{0, 0, 0, 0});  // pad: n = 0, never hit
   for (size_t k = 0; k < 2 * so.nbp; ++k) {
-    // rt_path.h brute_box: C.x, C.z, ax/|ax|^2 (x, z), az/|az|^2 (x, z), y range, faces
+    // rt_records.h brute_box: C.x, C.z, ax/|ax|^2 (x, z), az/|az|^2 (x, z), y range, faces
     const BoxRec& b = boxes[std::min(k, boxes.size() - 1)];
     float* f = (float*)&pairs[4 * (so.n_loop + k - (k & 1))] + (k & 1);
     const double a2 = b.ax[0] * b.ax[0] + b.ax[2] * b.ax[2], z2 = b.az[0] * b.az[0] + b.az[2] * b.az[2];

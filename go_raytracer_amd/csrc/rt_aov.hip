@@ -32,13 +32,14 @@
 #include <vector>
 
 #include "rt_hip_util.h"
-#include "rt_path.h"
+// the render's camera rays, traversal, record loop and textures: not its path state or
+// shading core (rt_path.h)
+#include "rt_camera.h"
+#include "rt_trav.h"
+#include "rt_records.h"
+#include "rt_shade.h"
 
 namespace rt {
-
-#ifdef RT_QTOP
-#error "rt_aov.hip: k_aov<5> stages no top items in LDS; the RT_QTOP experiment build does not cover the feature pass"
-#endif
 
 struct AovOut {
   float* albedo;
@@ -116,14 +117,8 @@ RT_D void aov_sample(const Params& P, const Ids& id, uint32_t j, const TravStack
   bool lit = false;  // L_j
   if (ref != PRIM_NONE) {
     // finish_hit's refinements of the winning hit (no media, no trace)
-#ifndef RT_NO_TRI_REFINE
     if (HAS(FT_TRI) && (ref >> 30) == PRIM_TRI)
       refine_tri_hit(sc, ref & 0x3FFFFFFFu, o, d, h.t, h.u, h.v);
-#endif
-#ifdef RT_SPHERE32_LEAVES
-    if (HAS(FT_SPHERE) && (ref >> 30) == PRIM_SPHERE && h.v >= 0.0f)
-      refine_sphere_hit(sc, ref & 0x3FFFFFFFu, o, d, time, h.t);
-#endif
     // shade_core's hit record: r.At(t) snapped onto the surface, the outward normal,
     // setFaceNormal (hittable.go:27-34), and the texture coordinates
     const float t = h.t;

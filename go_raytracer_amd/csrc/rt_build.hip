@@ -416,7 +416,7 @@ static int finalize_tree(HostScene& s, const std::vector<F4>& nlo, const std::ve
       const int c = kids[o][k];
       uint32_t code = CHILD_EMPTY;
       // an empty slot's box is inverted and infinite (lo = +inf, hi = -inf): the
-      // sign-selected slab test (rt_path.h trav_steps) never hits it
+      // sign-selected slab test (rt_trav.h trav_steps) never hits it
       float b[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
       if (c >= 0) {
         code = code_of(c, idx4);

@@ -41,7 +41,7 @@ inline constexpr uint32_t leaf_code(uint32_t first, uint32_t count) {
 //  f4[0] = child codes (bits) of children 0..3   f4[1] = lo.x   f4[2] = hi.x
 //  f4[3] = lo.y   f4[4] = hi.y   f4[5] = lo.z   f4[6] = hi.z   f4[7] = 0
 //  (codes first: they are fetched with the leaf-record-sized part of a traversal step's
-//  loads, so they arrive with the first planes, rt_path.h trav_steps)
+//  loads, so they arrive with the first planes, rt_trav.h trav_steps)
 // child code: inner BVH4 node index, leaf code (LEAF_BIT, as BVH2), or CHILD_EMPTY
 constexpr uint32_t CHILD_EMPTY = 0xFFFFFFFEu;
 
@@ -180,17 +180,17 @@ struct DevScene {
   const DevImage* images;
   const DevPerlin* perlins;
   int32_t brute_ax[3];  // record loop (TREE 0): axis-aligned pairs per normal axis, after
-                        // the general pairs (host-grouped; rt_path.h brute_axis)
+                        // the general pairs (host-grouped; rt_records.h brute_axis)
   int32_t brute_vt[3];  // record loop: pairs parallel to an axis (n_a = A_a = 0, B along a:
                         // the sides of boxes rotated about a), between the general and the
-                        // axis-aligned pairs (rt_path.h brute_vert; only y is grouped: RotateY
+                        // axis-aligned pairs (rt_records.h brute_vert; only y is grouped: RotateY
                         // is the reference's only rotation, transformation.go:48)
   int32_t brute_box;    // record loop: pairs of box descriptors after the axis-aligned pairs
-                        // (boxes rotated about y, tested as slabs: rt_path.h brute_box),
+                        // (boxes rotated about y, tested as slabs: rt_records.h brute_box),
                         // then the boxes' face records (not looped over)
   int32_t brute_ng;     // record loop: general pairs (the first ones)
   int32_t brute_mx;     // record loop: a mixed pair after the axis-aligned ones, two axis-aligned
-                        // records of axes a0 < a1 (rt_path.h brute_mixed): (a0+1) | (a1+1) << 2,
+                        // records of axes a0 < a1 (rt_records.h brute_mixed): (a0+1) | (a1+1) << 2,
                         // 0 when there is none
   float pdf_floor;      // 1e-30 when every light entry is a prim, else 0 (rt_path.h shade)
   int32_t n_perlins;    // perlin 0's tables are staged in LDS by the noise kernels
@@ -247,7 +247,7 @@ constexpr int kLeanLightCount = 2;
 inline constexpr int lean_light_axis(int kind) { return kind == 1 ? 1 : -1; }
 // The kind's light as plain floats, a member of the launch parameters (no pointer to chase):
 //  f[0..2] Q | f[3] D' = D / n_a   f[4..6] A = v x w | f[7] area   f[8..10] B = w x u | 0
-//  (the pdf's quad test, rt_path.h lean_light_pdf: the light's leaf record with the plane
+//  (the pdf's quad test, rt_shade.h lean_light_pdf: the light's leaf record with the plane
 //   offset in the record loop's axis form)
 //  f[12..14] u | 0   f[16..18] v | 0                   (quad.Random: Q + u s0 + v s1)
 //  f[11], written as 0 above: 0 in the matcher's block (lean_light_of, rt_scene_lean_light);

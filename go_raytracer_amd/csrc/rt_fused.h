@@ -29,20 +29,9 @@ RT_D bool stage_nodes(const Params& P, F4* lnodes, int W) {
 // media + debug trace on top of the world closest hit, camera.go:300
 template <uint32_t FT>
 RT_D void finish_hit(const Params& P, const Path& s, Hit& best) {
-#ifndef RT_NO_TRI_REFINE
   if (HAS(FT_TRI) && best.ref != PRIM_NONE && (best.ref >> 30) == PRIM_TRI)
     refine_tri_hit(P.sc, best.ref & 0x3FFFFFFFu, s.o, s.d, best.t, best.u, best.v);
-#endif
-#ifdef RT_SPHERE32_LEAVES
-  // a BVH sphere leaf won (fp32 test): its t in fp64 (v = -1: a big sphere, fp64 already)
-  if (HAS(FT_SPHERE) && best.ref != PRIM_NONE && (best.ref >> 30) == PRIM_SPHERE && best.v >= 0.0f)
-    refine_sphere_hit(P.sc, best.ref & 0x3FFFFFFFu, s.o, s.d, s.time, best.t);
-#endif
-#ifdef ABL_NO_MEDIA
-  if (false)
-#else
   if (HAS(FT_MEDIA) && P.sc.n_media > 0)
-#endif
     trace_media(P, s.o, s.d, s.time, 0.001f, s.gpix, s.s0 + s.j, s.k, s.spare, best);
   if (P.trace) record_trace(P, s, best);
 }
@@ -64,18 +53,6 @@ RT_D void finish_hit(const Params& P, const Path& s, Hit& best) {
 // (profiles/r5_c4_c5_isolation_ab.jsonl); round 2's 5-wave try of the 128-B-node kernel
 // spilled 32 VGPRs in the traversal loop and lost 24 %
 #define TRI_QWAVES 5
-#endif
-// RT_QTOP=N (experiment): the compressed BVH4's first N items (BFS order: the root and its
-// top levels, which nearly every ray visits) staged in dynamic LDS at kernel start and read
-// from there, off the vector-memory return path that bounds C5; one LDS stack entry fewer
-// so five blocks still fit
-#ifdef RT_QTOP
-#ifndef TRI_QSHORT
-#define TRI_QSHORT 12
-#endif
-#ifndef MESH_QSHORT
-#define MESH_QSHORT 12
-#endif
 #endif
 #ifndef TRI_QSHORT
 // 13 LDS traversal-stack entries fill five blocks' LDS (5 x 31,776 B of 160 KiB): C5 -1.5 %,
@@ -191,32 +168,16 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
   if constexpr (HAS(FT_NOISE)) stage_perlin(P.sc);  // before stage_nodes' barrier
   if constexpr (cam_mode(FT) == 1) stage_camera(P);
   const bool recs_lds = LDS && TREE != 8 && stage_nodes(P, lnodes, TREE == 4 ? 8 : 4);
-#ifdef RT_QTOP
-  if constexpr (TREE == 5) {  // the top items into the dynamic LDS (sized at launch)
-    const uint32_t nq = 4u * (uint32_t)min(RT_QTOP, P.sc.n_nodes);
-    for (uint32_t i = threadIdx.x; i < nq; i += blockDim.x) st_lds(&lnodes[i], ld_glb(P.sc.nodes + i));
-  }
-#endif
   if (!LDS) __syncthreads();  // staged tables visible to every wave (stage_nodes ends with one)
   const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;  // weight-stack column
-  const TravStack ts = {&lstack[threadIdx.x], P.ostack + slot, P.stack_cols, fused_short(FT, TREE)
-#ifdef RT_COUNT_TRAV_OVF
-                        , &P.ctr->pushes
-#endif
-  };
+  const TravStack ts = {&lstack[threadIdx.x], P.ostack + slot, P.stack_cols, fused_short(FT, TREE)};
   const WStack ws = {&lw[threadIdx.x], fused_wlds(FT, TREE)};
   const SampleAcc sa = {&lacc[threadIdx.x]};
   Path s;
   s.pushes = 0;
-  if constexpr ((FT == 0u && TREE == 0) || kSplitTrees) {  // read by split_samples before a lane's first chunk
-    s.chunk = s.j = 0u;
-    s.flags = 0u;
-  }
-#ifdef RT_WAVE_SEGS
-  uint32_t wave_segs = 0;  // segments shaded by this wave (wave-uniform: no VGPR)
-#else
+  s.chunk = s.j = 0u;  // read by split_samples before a lane's first chunk
+  s.flags = 0u;
   s.segs = 0;
-#endif
   Trav tr;
   tr.cur = TRAV_DONE;
   bool has = false;
@@ -243,30 +204,20 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
   for (;;) {
     PH_T(t_grab);
     uint32_t c = grab_chunk(P, b, !has), j0 = 0u, n0 = 0u;
-    // lanes share samples in the drain (split_samples; RT_NO_SPLIT_TREES: the record-loop
-    // kernel only)
-    constexpr bool kSplit = (FT == 0u && TREE == 0) || kSplitTrees;
-    if constexpr (kSplit)
-      if (b.part >= (uint32_t)kMaxParts) split_samples(P, s, has, c, j0, n0);
+    // lanes share samples in the drain (split_samples), in every kernel: measured against
+    // the record-loop kernel alone, profiles/r4_split_trees_ab.jsonl
+    if (b.part >= (uint32_t)kMaxParts) split_samples(P, s, has, c, j0, n0);
     if (c != 0xFFFFFFFFu) {
       start_sample<false, cam_mode(FT), FT == 0u && TREE == 0, MAP>(P, slot, s, c, j0);
-      if constexpr (kSplit)
-        if (j0) s.flags = F_SPLIT | (n0 << kCountShift);
+      if (j0) s.flags = F_SPLIT | (n0 << kCountShift);
       trav_init<FT>(P.sc, s.o, s.d, s.time, tr);
-#ifdef RT_QROOT  // (opt-in: +2-4 % on C3-C5)
-      if constexpr (TREE == 5) trav_root_q(ts, s.o, 0.001f, tr);
-#endif
       has = true;
     }
     PH_ADD(PH_GRAB, t_grab);
 #ifdef RT_DRAIN_TIMES
     if (b.part >= (uint32_t)kMaxParts && __builtin_amdgcn_readfirstlane((uint32_t)(g_tdrain[wave_in_group] != 0ull)) == 0u) {
       uint32_t rem = has ? (s.flags >> kCountShift) - s.j : 0u, act = has ? 1u : 0u;
-#ifndef RT_WAVE_SEGS
       uint32_t sg = s.segs;
-#else
-      uint32_t sg = 0u;
-#endif
       for (int off = 32; off > 0; off >>= 1) {
         rem += __shfl_xor(rem, off);
         act += __shfl_xor(act, off);
@@ -313,10 +264,6 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
     const uint32_t n_ready = (uint32_t)__popcll(__ballot(ready));
     const bool busy = __any(has && !ready);
     if (n_ready >= P.shade_min || !busy) {
-#ifdef RT_WAVE_SEGS
-      wave_segs += n_ready;
-#endif
-
       if (ready) {
         PH_CNT(PH_SHADE_LANES, n_ready);
         PH_CNT(PH_SHADE_ROUNDS, 1);
@@ -324,28 +271,17 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
         Hit best = tr.best;
         if constexpr (!EARLY) finish_hit<FT>(P, s, best);  // (EARLY: the trace is shade_core's)
         PH_ADD(PH_MEDIA, t_media);
-#ifndef RT_WAVE_SEGS
         ++s.segs;
-#endif
         PH_T(t_shade);
         if (shade_core<false, FT, LIGHT, EARLY ? SHAPE : 0>(P, slot, s, best, ws, sa, lnodes) == OUT_NEED_CHUNK) has = false;
-        else {
-          trav_init<FT>(P.sc, s.o, s.d, s.time, tr);
-#ifdef RT_QROOT  // (opt-in: +2-4 % on C3-C5)
-          if constexpr (TREE == 5) trav_root_q(ts, s.o, 0.001f, tr);
-#endif
-        }
+        else trav_init<FT>(P.sc, s.o, s.d, s.time, tr);
         PH_ADD(PH_SHADE, t_shade);
       }
     }
   }
   PH_ADD(PH_LOOP, t_loop);
-#ifdef RT_WAVE_SEGS
-  const uint32_t segs = wave_segs;
-#else
   uint32_t segs = s.segs;
   for (int off = 32; off > 0; off >>= 1) segs += __shfl_xor(segs, off);
-#endif
   uint32_t pushes = s.pushes;
   for (int off = 32; off > 0; off >>= 1) pushes += __shfl_xor(pushes, off);
   if (lane_id() == 0) {

@@ -40,7 +40,7 @@ inline int device_ok(const char* who, int device) {
 }
 
 // rt_render.hip, shared with the feature pass (rt_aov.hip): the camera part of the launch
-// parameters (rt_path.h Params: image plane, sample grid, rank, seed, the width and
+// parameters (rt_params.h Params: image plane, sample grid, rank, seed, the width and
 // spp_sqrt fast divisions), and the rows of an H-row image that `rank` of `nranks` renders
 struct Params;
 void set_camera_params(Params& p, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t npix);

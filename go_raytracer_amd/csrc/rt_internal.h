@@ -193,7 +193,7 @@ struct RecordPack {
   std::vector<F4> pairs;  // 4 F4 per slot, then the lean kernel's shade table (shade_n F4)
   size_t n_slots = 0;     // records in pairs, pads included (even)
   int32_t shade_n = 0;    // F4s of the shade table after the pairs (0: none)
-  int32_t n_boxes = 0;    // boxes among the records tested as slabs (rt_path.h brute_box)
+  int32_t n_boxes = 0;    // boxes among the records tested as slabs (rt_records.h brute_box)
   BruteCounts counts{};   // the layout's group counts (DevScene brute_*)
   int shape = 0;          // brute_shape_of(counts)
   int32_t emitter_slot = -1;  // the slot (the loop's bk) of the scene's one emissive record when

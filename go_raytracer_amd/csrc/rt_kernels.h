@@ -105,13 +105,6 @@ RT_D f3 refract(f3 v, f3 n, float eta) {
   return perp + par;
 }
 
-// clampContribution camera.go:334-341
-RT_D f3 clamp_contribution(f3 c, float maxv) {
-  float intensity = c.x + c.y + c.z;
-  if (intensity > maxv) return c * (maxv * rcp(intensity));
-  return c;
-}
-
 // --------------------------------------------------------- intersection ----
 // sphere.Hit objects.go:83-115 — evaluated in fp64 (fp32 cancels in
 // |oc|^2 - r^2 for the R=1000 ground and R=5000 fog spheres).  Open interval.
@@ -145,13 +138,8 @@ RT_D bool hit_sphere_d(const DevScene& sc, uint32_t i, f3 o, f3 d, float time, d
   return true;
 }
 // Both roots of the sphere quadratic, as hit_sphere_d computes them (same
-// arithmetic, so identical doubles): r0 <= r1.  False when the ray misses.
-RT_D bool sphere_roots_cm(F4 cr, F4 mv, f3 o, f3 d, float time, double& r0, double& r1);
-RT_D bool sphere_roots_d(const DevScene& sc, uint32_t i, f3 o, f3 d, float time, double& r0,
-                         double& r1) {
-  return sphere_roots_cm(sc.sph_cr[i], sc.sph_mv[i], o, d, time, r0, r1);
-}
-// the same from the sphere's center | radius and motion records
+// arithmetic, so identical doubles): r0 <= r1.  False when the ray misses.  From the
+// sphere's center | radius and motion records.
 RT_D bool sphere_roots_cm(F4 cr, F4 mv, f3 o, f3 d, float time, double& r0, double& r1) {
   double cx = (double)cr.x + (double)time * (double)mv.x;
   double cy = (double)cr.y + (double)time * (double)mv.y;
@@ -291,56 +279,12 @@ RT_D bool hit_sphere_rec64(const F4 r[4], f3 o, f3 d, float time, float tmin, fl
   t_out = (float)(q * __builtin_amdgcn_rcp(a));  // fp32-level result from fp64 q: float t
   return true;
 }
-// Measured slower, kept opt-in (-DRT_SPHERE32_LEAVES; C3 +3.6 %, C4 +5.4 %, C5 +3.8 % against
-// the fp64 leaves, profiles/r4_sphere_leaves_ab.jsonl): the BVH's sphere leaves (radius
-// < kBigSphereR) in fp32 with the numerically robust discriminant r^2 - |oc - (h/a) d|^2
-// (no cancellation of |oc|^2 against r^2), falling back to the fp64 test where the fp32
-// result is uncertain: the discriminant within its rounding bound (a grazing ray) or a
-// root next to tmin or tmax (a self-hit or a near-tie with the closest hit so far).  The
-// winner's t is re-solved in fp64 once per segment (refine_sphere_hit).
-RT_D bool hit_sphere_rec32(const F4 r[4], f3 o, f3 d, float time, float tmin, float tmax,
-                           float& t_out) {
-  const F4 c0 = r[0], mv = r[1];
-  const f3 oc = mk3(fmaf(time, mv.x, c0.x), fmaf(time, mv.y, c0.y), fmaf(time, mv.z, c0.z)) - o;
-  const float a = dot(d, d), ia = rcp(a), h = dot(d, oc);
-  const float s = h * ia;  // the ray's closest approach to the center
-  const f3 f = mk3(fmaf(-s, d.x, oc.x), fmaf(-s, d.y, oc.y), fmaf(-s, d.z, oc.z));
-  const float ff = dot(f, f), rr = mv.w * mv.w, q = rr - ff;  // disc / a
-  // rounding of f ~ eps |oc| per component: |ff| off by ~4 eps |f| |oc|
-  const float err = 6.0e-7f * (rr + fsqrt(ff * dot(oc, oc)));
-  if (fabsf(q) <= err) return hit_sphere_rec64(r, o, d, time, tmin, tmax, t_out);
-  if (q < 0.0f) return false;
-  const float sq = fsqrt(q * ia);  // sqrt(disc) / a
-  float root = s - sq;
-  const float tol = 1.0e-5f * (fabsf(root) + tmin);
-  if (fabsf(root - tmin) <= tol || fabsf(root - tmax) <= 1.0e-5f * fabsf(root))
-    return hit_sphere_rec64(r, o, d, time, tmin, tmax, t_out);
-  if (!(tmin < root && root < tmax)) {
-    root = s + sq;
-    if (fabsf(root - tmin) <= 1.0e-5f * (fabsf(root) + tmin) ||
-        fabsf(root - tmax) <= 1.0e-5f * fabsf(root))
-      return hit_sphere_rec64(r, o, d, time, tmin, tmax, t_out);
-    if (!(tmin < root && root < tmax)) return false;
-  }
-  t_out = root;
-  return true;
-}
+// The BVH's sphere leaves are tested in fp64 like the big spheres.  (An fp32 test with an
+// fp64 fallback and a per-segment fp64 refinement of the winner measured C3 +3.6 %, C4 +5.4 %,
+// C5 +3.8 % against this, profiles/r4_sphere_leaves_ab.jsonl; removed)
 RT_D bool hit_sphere_rec(const F4 r[4], f3 o, f3 d, float time, float tmin, float tmax,
                          float& t_out) {
-#ifdef RT_SPHERE32_LEAVES
-  return hit_sphere_rec32(r, o, d, time, tmin, tmax, t_out);
-#else
   return hit_sphere_rec64(r, o, d, time, tmin, tmax, t_out);
-#endif
-}
-// The winning sphere's t re-solved in fp64 (hit_sphere_d's quadratic on the same fp32
-// ray): the root nearest to the fp32 test's, so the refinement never changes which root
-// (entering or leaving) the traversal chose
-RT_D void refine_sphere_hit(const DevScene& sc, uint32_t idx, f3 o, f3 d, float time, float& t_io) {
-  double r0, r1;
-  if (!sphere_roots_d(sc, idx, o, d, time, r0, r1)) return;  // fp32 hit, fp64 grazing miss
-  const double t = (double)t_io;
-  t_io = (float)(fabs(r0 - t) <= fabs(r1 - t) ? r0 : r1);
 }
 RT_D bool hit_quad_rec(const F4 r[4], f3 o, f3 d, float tmin, float tmax, float& t_out,
                        float& a_out, float& b_out) {

@@ -178,7 +178,7 @@ struct DeviceScene {
   const F4* brute_pairs = nullptr;  // quad records in pairs, largest first (record loop)
   size_t brute_slots = 0;           // records in brute_pairs, pads included (even)
   int32_t shade_n = 0;              // F4s of the lean shade table after the pairs (0: none)
-  int32_t brute_boxes = 0;          // boxes among them tested as slabs (rt_path.h brute_box)
+  int32_t brute_boxes = 0;          // boxes among them tested as slabs (rt_records.h brute_box)
   int brute_shape = 0;              // the listed layout the pair counts equal (rt_device.h), 0 = none
   int lean_light = 0;               // the light list's lean kind (rt_device.h), 0 = the general code
   LeanLight light_block{};          // ... and its light as the kernel of that kind reads it
@@ -343,7 +343,7 @@ static int upload_scene(const Scene* s, DeviceScene* ds) {
   UP(h.tri, tri);
   UP(h.tri_attr, tri_attr);
   // the BVH4 nodes and the leaf records in ONE allocation (nodes first): the traversal
-  // addresses both as 32-bit byte offsets from the node base (rt_path.h trav_steps)
+  // addresses both as 32-bit byte offsets from the node base (rt_trav.h trav_steps)
   std::vector<F4> recs;
   build_leaf_records(h, recs);
   {
@@ -721,9 +721,6 @@ static int take_qbvh(Scene* s, DeviceScene* ds, uint32_t ft_set, StructurePlan* 
   if (rc || !ds->qnodes) return rc;
   sp->tree = 5;
   sp->kernel = pick_fused(false, ft_set, 5);
-#ifdef RT_QTOP
-  sp->lds_bytes = 64 * std::min<size_t>(RT_QTOP, ds->qitems);
-#endif
   return RT_OK;
 }
 
@@ -828,7 +825,7 @@ uint32_t rank_rows(uint32_t H, int rank, int nranks) {
   return H > (uint32_t)rank ? (H - (uint32_t)rank + nranks - 1) / nranks : 0;
 }
 
-// How a render's samples are cut into chunks (rt_path.h chunk_pixel): K samples per chunk, a
+// How a render's samples are cut into chunks (rt_camera.h chunk_pixel): K samples per chunk, a
 // tail phase of K2-sample chunks after the first S1 samples of every pixel (S1 == ss: none),
 // and the row groups the chunks sweep.  P: the fused kernel's lanes (unused otherwise).
 struct ChunkPlan {
@@ -886,7 +883,7 @@ static int plan_chunks(uint32_t npix, uint32_t rows, uint32_t W, uint32_t ss, ui
   }
   K = std::max<uint32_t>(1u, std::min<uint32_t>(std::min(K, ss), 4096u));
   // Tail phase (fused, default chunk sizes): the last ~1/RT_TAIL_FRAC of every pixel's
-  // samples in chunks of K / 4 (min 4), after all first-phase chunks (rt_path.h chunk_pixel),
+  // samples in chunks of K / 4 (min 4), after all first-phase chunks (rt_camera.h chunk_pixel),
   // by default (1/4) when a lane gets fewer than 40 chunks: the multi-GPU shares.  C2's 2-,
   // 4- and 8-GPU shares -1.0 / -4.0 / -2.3 %, the whole image (52 chunks per lane, no tail)
   // +0.5 % with it (profiles/r4_tail_ab.jsonl)

@@ -39,7 +39,7 @@ def test_feature_parity(rt, oracle, gpu, name, mode):
 
 @pytest.mark.parametrize("tables", [1, 3])
 def test_noise_tables_kernel_choice(rt, oracle, gpu, tables):
-    """Feature-set kernels read perlin table 0 from LDS only (rt_path.h LdsPerlin); a
+    """Feature-set kernels read perlin table 0 from LDS only (rt_shade.h LdsPerlin); a
     scene whose reachable noise textures use other tables runs the all-features kernel
     (generic table pointers).  Both match the oracle."""
     t = rt.Tree(9)

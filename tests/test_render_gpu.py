@@ -50,7 +50,7 @@ def test_bitwise_invariances(rt, gpu, name):
 
 @pytest.mark.parametrize("name", ["book1", "book2", "cornell"])
 def test_tail_phase_is_bitwise(rt, gpu, name, tune):
-    """The two-phase chunk plan (rt_path.h chunk_pixel: the last samples of every pixel in
+    """The two-phase chunk plan (rt_camera.h chunk_pixel: the last samples of every pixel in
     shorter chunks after all first-phase chunks) regroups samples only; with exact
     fixed-point pixel sums the image is the same bits for any tail fraction and tail chunk
     size, and for the one-phase plan (the record-loop kernel ignores the request)."""
@@ -87,7 +87,7 @@ def test_drain_split_is_bitwise(rt, gpu, name, nranks, tune):
 @pytest.mark.parametrize("name,width,nranks", [("book1", 96, 1), ("book2", 128, 2),
                                                 ("cornell_smoke", 96, 3), ("cornell", 64, 1)])
 def test_sweep_order_reverse(rt, gpu, name, width, nranks, tune):
-    """The reverse chunk sweep (RT_SWEEP=reverse; rt_path.h chunk_pixel's (q ^ gflip) + gbase,
+    """The reverse chunk sweep (RT_SWEEP=reverse; rt_camera.h chunk_pixel's (q ^ gflip) + gbase,
     k_resolve's inverse) is an opt-in build, -DRT_SWEEP_ORDER (DESIGN.md §8 "Sweep order": it
     cost C4/C5 0.3-0.5 % compiled in).  The default library refuses the knob at render time
     with RT_ERR_UNSUPPORTED instead of ignoring it; a -DRT_SWEEP_ORDER library
@@ -233,7 +233,7 @@ def test_kernel_selection(rt, gpu, name, width, lean, width_tree, lds):
 @pytest.mark.parametrize("var", ["RT_BRUTE_AXIS", "RT_BRUTE_VERT", "RT_BRUTE_MIXED"])
 @pytest.mark.parametrize("name", ["cornell", "cornell_smoke"])
 def test_axis_record_groups_match_general_test(rt, gpu, tune, var, name):
-    """The record loop's axis-aligned groups (rt_path.h brute_axis), its y-parallel
+    """The record loop's axis-aligned groups (rt_records.h brute_axis), its y-parallel
     group (brute_vert: the rotated boxes' sides) and the mixed pair of two groups' odd
     records (brute_mixed: the light on y and the back wall on z in Cornell) compute the
     general quad test's t, alpha and beta bit for bit: the Cornell boxes render the same
@@ -256,7 +256,7 @@ def test_axis_record_groups_match_general_test(rt, gpu, tune, var, name):
 @pytest.mark.parametrize("name", ["cornell", "cornell_smoke"])
 def test_record_loop_boxes(rt, oracle, gpu, tune, name):
     """Boxes rotated about y are tested as one slab test each in the record loop
-    (rt_path.h brute_box, the reference's rotateY frame): Cornell's two boxes are found,
+    (rt_records.h brute_box, the reference's rotateY frame): Cornell's two boxes are found,
     the smoke scene's boxes are media boundaries (not records), and the image agrees
     with the oracle as closely as the six-records path does (RT_BRUTE_BOX=0)."""
     t, cam, w, l = rt.demo_scene(name)
