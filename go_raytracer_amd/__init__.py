@@ -21,7 +21,7 @@ from ._lib import (RT_FT_ALL, RT_FT_BOX, RT_NOISE_MARBLE, RT_NOISE_PERLIN,  # no
 
 __all__ = ["Tree", "Camera", "Scene", "Accumulator", "quantize", "format_ppm", "device_count", "RtError",
            "tune", "untune", "tuning", "tune_knobs", "tune_from_env",
-           "demo_scene", "DEMO_SCENES", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
+           "demo_scene", "DEMO_SCENES", "build_bvh_boxes", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
            "format_ppm_device", "denoise", "denoise_device", "denoise_var", "denoise_var_device",
            "RtDenoiseVarOpts"]
 
@@ -906,6 +906,31 @@ def demo_scene(name, seed=1, asset_dir=None):
     check(lib().rt_demo_scene(t.ptr, name.encode(), asset_dir.encode(), C.byref(cam), C.byref(w),
                               C.byref(l)))
     return t, Camera.from_c(cam), w.value, l.value
+
+
+def build_bvh_boxes(boxes, builder=0):
+    """A tree over caller-supplied boxes (rt_bvh_build_boxes, a structural test export):
+    `boxes` float32 [n, 6] (lo xyz, hi xyz), builder 0 = host binned SAH, 1 = device PLOC.
+    Returns {"nodes": float32 [N, 16], "refs": uint32 [n] (leaf position -> box index), "root",
+    "nodes4": uint32 [M, 32], "root4", "bvh_depth", "max_leaf"}, the arrays as
+    Scene.export_bvh / export_qbvh give them."""
+    b = np.ascontiguousarray(boxes, dtype=np.float32)
+    if b.ndim != 2 or b.shape[1] != 6:
+        raise ValueError(f"build_bvh_boxes: boxes must have shape [n, 6], not {b.shape}")
+    n = b.shape[0]
+    cap = max(n - 1, 0)  # no tree over n boxes has more inner nodes
+    nodes, nodes4 = np.zeros((cap, 16), np.float32), np.zeros((cap, 32), np.uint32)
+    refs = np.zeros(n, np.uint32)
+    nn, nr, n4, depth, leaf = (C.c_int32() for _ in range(5))
+    root, root4 = C.c_uint32(), C.c_uint32()
+    check(lib().rt_bvh_build_boxes(b.ctypes.data or None, n, int(builder), nodes.ctypes.data or None,
+                                   C.byref(nn), refs.ctypes.data or None, C.byref(nr), C.byref(root),
+                                   nodes4.ctypes.data or None, C.byref(n4), C.byref(root4),
+                                   C.byref(depth), C.byref(leaf)))
+    assert nn.value <= cap and n4.value <= cap and nr.value == n
+    return {"nodes": nodes[:nn.value], "refs": refs, "root": int(root.value),
+            "nodes4": nodes4[:n4.value], "root4": int(root4.value),
+            "bvh_depth": depth.value, "max_leaf": leaf.value}
 
 
 def substitute_mesh_obj(nu=0, nv=0):

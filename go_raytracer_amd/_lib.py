@@ -229,6 +229,10 @@ SIGNATURES = {
     "rt_scene_export_records": (_I, [_P, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rt_scene_export_prim_bounds": (_I, [_P, C.c_void_p, C.POINTER(C.c_int32)]),
+    "rt_bvh_build_boxes": (_I, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32),
+                                C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
+                                C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
+                                C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rt_scene_lean_light": (_I, [_P, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32)]),
     "rt_scene_plan_light": (_I, [_P, _I, C.POINTER(C.c_int32)]),
     "rt_scene_lean_emitter": (_I, [_P, C.POINTER(C.c_int32)]),

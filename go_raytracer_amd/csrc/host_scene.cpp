@@ -219,4 +219,37 @@ int rt_scene_export_prim_bounds(const rt_scene* sc, float* bounds, int32_t* n) {
   return RT_OK;
 }
 
+int rt_bvh_build_boxes(const float* boxes, int32_t n, int32_t builder, float* nodes,
+                       int32_t* n_nodes, uint32_t* refs, int32_t* n_refs, uint32_t* root,
+                       float* nodes4, int32_t* n_nodes4, uint32_t* root4, int32_t* bvh_depth,
+                       int32_t* max_leaf) {
+  if (n < 0 || (n > 0 && !boxes)) return set_error(RT_ERR_INVALID, "rt_bvh_build_boxes: no boxes");
+  if (builder != 0 && builder != 1)
+    return set_error(RT_ERR_INVALID, "rt_bvh_build_boxes: builder %d is not 0 (host) or 1 (device)", builder);
+  if (builder == 1 && !rt::bvh_device_available())
+    return set_error(RT_ERR_DEVICE, "rt_bvh_build_boxes: no HIP device is available");
+  std::vector<rt::F4> lo(n), hi(n);
+  std::vector<uint32_t> prims(n);
+  for (int32_t i = 0; i < n; ++i) {
+    const float* b = boxes + 6 * (size_t)i;
+    lo[i] = {b[0], b[1], b[2], 0};
+    hi[i] = {b[3], b[4], b[5], 0};
+    prims[i] = (uint32_t)i;
+  }
+  rt::HostScene h;  // only the builders' outputs are read
+  const int rc = builder ? rt::build_bvh_device(h, lo, hi, prims, -1) : rt::build_bvh(h, lo, hi, prims);
+  if (rc != RT_OK) return rc;
+  if (n_nodes) *n_nodes = (int32_t)(h.nodes.size() / 4);
+  if (n_refs) *n_refs = (int32_t)h.refs.size();
+  if (root) *root = h.root;
+  if (n_nodes4) *n_nodes4 = (int32_t)(h.nodes4.size() / 8);
+  if (root4) *root4 = h.root4;
+  if (bvh_depth) *bvh_depth = h.bvh_depth;
+  if (max_leaf) *max_leaf = h.max_leaf;
+  if (nodes && !h.nodes.empty()) memcpy(nodes, h.nodes.data(), h.nodes.size() * 16);
+  if (refs && !h.refs.empty()) memcpy(refs, h.refs.data(), h.refs.size() * 4);
+  if (nodes4 && !h.nodes4.empty()) memcpy(nodes4, h.nodes4.data(), h.nodes4.size() * 16);
+  return RT_OK;
+}
+
 }  // extern "C"

@@ -179,8 +179,9 @@ __global__ __launch_bounds__(kBlock) void k_nn(const float4* clo, const float4* 
 
 // create: the lower of a mutual pair makes the new node; valid: survives into the
 // next cluster list (everything but the upper of a mutual pair).  `force` (no
-// mutual pair found last time: never observed, kept as a guarantee of progress)
-// pairs clusters 2k, 2k+1.
+// mutual pair found last time: boxes whose merged half-area overflows to +inf, so
+// that k_nn finds no neighbour; test_device_tree_equals_replay_when_areas_overflow
+// in tests/test_bvh_ploc_gpu.py reaches it) pairs clusters 2k, 2k+1.
 __global__ __launch_bounds__(kBlock) void k_flags(const int* nn, int m, int force, int* create,
                                                  int* valid) {
   const int i = blockIdx.x * kBlock + threadIdx.x;

@@ -343,6 +343,19 @@ int rt_scene_export_qbvh(const rt_scene* s, float* items, int32_t* n_items, floa
  * to have pairs.  NULL pointers query the sizes. */
 int rt_scene_export_records(const rt_scene* s, float* pairs, int32_t* n_slots, int32_t counts[7],
                             int32_t* shade_n, int32_t* n_boxes);
+/* structural test export: a tree over caller-supplied boxes (n x 6 floats: lo xyz, hi xyz),
+ * built by the unchanged builder of rt_scene_create -- builder 0: the host binned SAH, 1: the
+ * device PLOC on the calling thread's current device (RT_ERR_DEVICE without one) -- with prim i
+ * = box i and no padding, so a test can put boxes on an exact lattice.  Outputs as
+ * rt_scene_export_bvh (nodes, refs: leaf position -> box index, root), rt_scene_export_qbvh's
+ * BVH4 (nodes4, root4) and rt_scene_info's bvh_depth and max_leaf.  n_nodes and n_nodes4 are
+ * at most max(n - 1, 0) and n_refs is n; NULL pointers query the counts (the tree is built
+ * either way).  n = 0 and n = 1 follow the builder: the host one gives an empty tree
+ * (root PRIM_NONE) and a single leaf, the device one RT_ERR_INVALID below two boxes. */
+int rt_bvh_build_boxes(const float* boxes, int32_t n, int32_t builder, float* nodes,
+                       int32_t* n_nodes, uint32_t* refs, int32_t* n_refs, uint32_t* root,
+                       float* nodes4, int32_t* n_nodes4, uint32_t* root4, int32_t* bvh_depth,
+                       int32_t* max_leaf);
 /* the lean light kind of the scene's light list as the host matcher decides it at upload (no
  * device): 0 = any list (the general light code), 1 = one quad light of weight 1 with unit
  * normal +-e_y in a lean-set scene (RT_FT features 0) of non-negative colours.  For a kind

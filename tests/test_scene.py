@@ -59,8 +59,16 @@ def bvh_invariants(sc):
     it (the exported BVH2; the BVH4 shares its leaves and boxes)."""
     nodes, refs, root, bounds = sc.export_bvh()
     i = sc.info()
+    bvh_tree_invariants(nodes, refs, root, bounds, i["n_world_prims"], i["max_leaf"])
+    return nodes, refs, bounds
+
+
+def bvh_tree_invariants(nodes, refs, root, bounds, n_prims, max_leaf, boxes=True):
+    """bvh_invariants on the arrays themselves (rt.build_bvh_boxes gives them without a
+    scene): `bounds` are the prim boxes in ref order.  boxes=False walks the leaves only
+    (inputs whose boxes are NaN have no containment to check)."""
     n = len(refs)
-    assert n == i["n_world_prims"]
+    assert n == n_prims
     seen = np.zeros(n, np.int32)
     stack = [(root, np.full(3, -np.inf, np.float32), np.full(3, np.inf, np.float32))]
     while stack:  # iterative: device-built trees of big meshes are deep
@@ -69,17 +77,18 @@ def bvh_invariants(sc):
             first, cnt = (code >> 4) & 0x7FFFFFF, (code & 15) + 1
             seen[first:first + cnt] += 1
             b = bounds[first:first + cnt]
-            assert (b[:, :3] >= lo - 1e-6).all() and (b[:, 3:] <= hi + 1e-6).all()
+            if boxes:
+                assert (b[:, :3] >= lo - 1e-6).all() and (b[:, 3:] <= hi + 1e-6).all()
             continue
         nd = nodes[code]
         c0 = int(nd[3:4].view(np.uint32)[0])
         c1 = int(nd[7:8].view(np.uint32)[0])
         for c, (blo, bhi) in ((c0, (nd[0:3], nd[4:7])), (c1, (nd[8:11], nd[12:15]))):
-            assert (blo >= lo - 1e-6).all() and (bhi <= hi + 1e-6).all()
+            if boxes:
+                assert (blo >= lo - 1e-6).all() and (bhi <= hi + 1e-6).all()
             stack.append((c, blo, bhi))
     assert (seen == 1).all(), "every world prim is referenced by exactly one leaf"
-    assert i["max_leaf"] <= 16
-    return nodes, refs, bounds
+    assert max_leaf <= 16
 
 
 @pytest.mark.parametrize("name", ["cornell", "book1", "book2", "quads", "model:96x24"])
@@ -242,6 +251,46 @@ def test_box_leaves_kept_only_where_they_pay(rt, tune):
         assert not sc.info()["features"] & rt.RT_FT_BOX
 
 
+def bvh4_children(nodes4, node):
+    """(code, lo, hi) of the four child slots of one BVH4 node (rt_device.h "BVH4 node":
+    [field][child], codes first), boxes in float64."""
+    nd = nodes4[node].view(np.float32).reshape(8, 4)
+    codes = nodes4[node][0:4]
+    return [(int(codes[k]), np.array([nd[1 + 2 * a, k] for a in range(3)], np.float64),
+             np.array([nd[2 + 2 * a, k] for a in range(3)], np.float64)) for k in range(4)]
+
+
+def bvh4_tree_invariants(nodes4, root4, bounds, boxes=True):
+    """The BVH4 on its own arrays: every node is reached once, every prim is in exactly one
+    leaf, every child box lies in its parent's and contains the prims below it, and an empty
+    slot holds the inverted infinite box.  boxes=False walks the leaves only."""
+    LEAF, EMPTY = 0x80000000, 0xFFFFFFFE
+    seen_nodes = np.zeros(len(nodes4), np.int32)
+    seen = np.zeros(len(bounds), np.int32)
+    stack = [(root4, np.full(3, -np.inf), np.full(3, np.inf))]
+    while stack:
+        code, lo, hi = stack.pop()
+        if code & LEAF:
+            first, cnt = (code >> 4) & 0x7FFFFFF, (code & 15) + 1
+            seen[first:first + cnt] += 1
+            b = bounds[first:first + cnt]
+            if boxes:
+                assert (b[:, :3] >= lo).all() and (b[:, 3:] <= hi).all()
+            continue
+        seen_nodes[code] += 1
+        kids = bvh4_children(nodes4, code)
+        assert sum(c != EMPTY for c, _, _ in kids) >= 2
+        for c, blo, bhi in kids:
+            if c == EMPTY:
+                assert (blo == np.inf).all() and (bhi == -np.inf).all()
+                continue
+            if boxes:
+                assert (blo >= lo).all() and (bhi <= hi).all()
+            stack.append((c, blo, bhi))
+    assert (seen_nodes == 1).all(), "every BVH4 node is reached exactly once"
+    assert (seen == 1).all(), "every prim is referenced by exactly one BVH4 leaf"
+
+
 def qbvh_invariants(sc):
     """host_qbvh.cpp: the compressed BVH4 mirrors the BVH4 item by item -- every BVH4 node
     is one 64-B node item, every single-prim leaf one leaf record (its bit set in the node's
@@ -272,13 +321,8 @@ def qbvh_invariants(sc):
         corner, lo, hi, base, lmask = planes(item)
         if kind == "node":
             seen_nodes[what] += 1
-            nd = nodes4[what].view(np.float32).reshape(8, 4)  # [field][child]
-            codes = nodes4[what][0:4]
             kids = []
-            for k in range(4):
-                c = int(codes[k])
-                blo = np.array([nd[1 + 2 * a, k] for a in range(3)], np.float64)
-                bhi = np.array([nd[2 + 2 * a, k] for a in range(3)], np.float64)
+            for c, blo, bhi in bvh4_children(nodes4, what):
                 if c == EMPTY or not (blo <= bhi).all():
                     kids.append(None)
                 elif c & LEAF:
