@@ -29,7 +29,7 @@
 // k_count_stats    min, max and sum of a u32 array by one block (counts, tile flags)
 //
 // Feature buffers (rt_accum_set_features): a second allocation, alive only while
-// features are on, of the FeatPlanes sums (rt_hip_util.h; 56 B per pixel for the guides group,
+// features are on, of the FeatPlanes sums (rt_host_units.h; 56 B per pixel for the guides group,
 // 52 B for the emit group) and 56 B per pixel of staging for rt_accum_resolve_aov.  A pass then
 // also runs rt_aov.hip's k_aov_fold for the same seed and pixels on the same stream;
 // k_feat_resolve<PX> maps the sums to the rt_aov / rt_aov_emit planes.
@@ -43,6 +43,7 @@
 #include <type_traits>
 
 #include "rt_hip_util.h"
+#include "rt_host_units.h"
 #include "rt_resolve.h"
 
 namespace rt {
@@ -365,12 +366,12 @@ struct rt_accum {
   int32_t max_passes = 0, passes = 0;
   uint32_t npix = 0, ss = 0;
   std::mutex mu;  // one call per accumulator at a time
-  void* buf = nullptr;  // planes | info partials and result | resolve staging
+  rt::DeviceBuffer buf;  // planes | info partials and result | resolve staging
   size_t state_bytes = 0;
   rt::AccumPlanes A{};
   double* part = nullptr;  // [kInfoBlocks][4], then the result [4]
   float *stage_rgb = nullptr, *stage_var = nullptr;
-  hipStream_t own_stream = nullptr;
+  rt::Stream own_stream;  // for an accumulator without opts.stream
   // per-pixel pass counts and the selection
   uint32_t W = 0, rows = 0;
   uint32_t* count = nullptr;  // [npix], valid while per_pixel
@@ -385,7 +386,7 @@ struct rt_accum {
   const uint32_t* pass_map = nullptr;  // the map of the pass being folded (null: a whole pass)
   // feature buffers: off until rt_accum_set_features
   uint32_t features = 0;     // RT_ACCUM_FEAT_* enabled
-  void* feat_buf = nullptr;  // the enabled groups' planes | resolve staging
+  rt::DeviceBuffer feat_buf;  // the enabled groups' planes | resolve staging
   size_t feat_state_bytes = 0;
   rt::FeatPlanes F{};
   float* feat_stage = nullptr;  // [14][npix] floats: rt_accum_resolve_aov's planes in FeatOut's order
@@ -398,11 +399,7 @@ namespace {
 // accumulator's device current, -> the caller's stream or the accumulator's own
 int accum_device(rt_accum* a, hipStream_t* out) {
   HIP_OK(hipSetDevice(a->opts.device));
-  *out = (hipStream_t)a->opts.stream;
-  if (*out) return RT_OK;
-  if (!a->own_stream) HIP_OK(hipStreamCreateWithFlags(&a->own_stream, hipStreamNonBlocking));
-  *out = a->own_stream;
-  return RT_OK;
+  return a->own_stream.pick(a->opts.stream, out);
 }
 
 // the PX instances' counts (a->per_pixel); uniform launches carry Passes<false>{passes}
@@ -561,8 +558,7 @@ size_t carve_features(rt_accum* a, uint32_t planes, void* base) {
 
 // features off: the feature allocation freed (the accumulator's device is current)
 void drop_features(rt_accum* a) {
-  if (a->feat_buf) (void)hipFree(a->feat_buf);
-  a->feat_buf = nullptr;
+  a->feat_buf.reset();
   a->features = 0;
   a->F = FeatPlanes{};
   a->feat_stage = nullptr;
@@ -570,10 +566,7 @@ void drop_features(rt_accum* a) {
 
 void free_accum(rt_accum* a) {
   DeviceGuard dg;
-  if (a->buf || a->feat_buf || a->own_stream) (void)hipSetDevice(a->opts.device);
-  drop_features(a);
-  if (a->buf) (void)hipFree(a->buf);
-  if (a->own_stream) (void)hipStreamDestroy(a->own_stream);
+  if (a->buf.p || a->feat_buf.p || a->own_stream.s) (void)hipSetDevice(a->opts.device);
   delete a;
 }
 
@@ -738,16 +731,17 @@ int rt_accum_create(rt_scene* s, const rt_camera* cam, const rt_render_opts* opt
   a->rows = a->W ? a->npix / a->W : 0u;
   const size_t total = carve(a, nullptr);
   DeviceGuard dg;
-  hipError_t e = hipSetDevice(o.device);
-  if (e == hipSuccess) e = hipMalloc(&a->buf, total);
-  if (e == hipSuccess) e = hipMemset(a->buf, 0, total);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
+  auto zeroed = [&]() -> int {  // the one allocation, on the accumulator's device
+    HIP_OK(hipSetDevice(o.device));
+    if ((rc = a->buf.grow(total, "rt_accum_create"))) return rc;
+    HIP_OK(hipMemset(a->buf.p, 0, total));
+    return RT_OK;
+  };
+  if ((rc = zeroed())) {
     free_accum(a);
-    return set_error(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_DEVICE, "rt_accum_create: %zu bytes: %s", total,
-                     hipGetErrorString(e));
+    return rc;
   }
-  carve(a, a->buf);
+  carve(a, a->buf.p);
   {
     std::lock_guard<std::mutex> lk(s->s.mu);
     s->s.accums.push_back(a);
@@ -779,9 +773,9 @@ int rt_accum_reset(rt_accum* a) {
   hipStream_t stream;
   int rc;
   if ((rc = accum_device(a, &stream))) return rc;
-  HIP_OK(hipMemsetAsync(a->buf, 0, a->state_bytes, stream));
+  HIP_OK(hipMemsetAsync(a->buf.p, 0, a->state_bytes, stream));
   HIP_OK(hipMemsetAsync(a->A.flags, 0, std::max<size_t>(a->npix, 1) * sizeof(uint32_t), stream));
-  if (a->feat_buf) HIP_OK(hipMemsetAsync(a->feat_buf, 0, a->feat_state_bytes, stream));
+  if (a->feat_buf.p) HIP_OK(hipMemsetAsync(a->feat_buf.p, 0, a->feat_state_bytes, stream));
   HIP_OK(hipStreamSynchronize(stream));
   a->passes = 0;
   a->per_pixel = a->sel_valid = a->sel_tiles = false;  // uniform again, no selection
@@ -805,15 +799,14 @@ int rt_accum_set_features(rt_accum* a, uint32_t planes) {
   drop_features(a);
   if (planes == 0) return RT_OK;
   const size_t total = carve_features(a, planes, nullptr);
-  hipError_t e = hipMalloc(&a->feat_buf, total);
-  if (e == hipSuccess) e = hipMemset(a->feat_buf, 0, total);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
+  int rc = a->feat_buf.grow(total, "rt_accum_set_features");
+  if (rc == RT_OK && hipMemset(a->feat_buf.p, 0, total) != hipSuccess)
+    rc = set_error(RT_ERR_DEVICE, "rt_accum_set_features: clearing %zu bytes", total);
+  if (rc) {
     drop_features(a);
-    return set_error(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_DEVICE, "rt_accum_set_features: %zu bytes: %s", total,
-                     hipGetErrorString(e));
+    return rc;
   }
-  carve_features(a, planes, a->feat_buf);
+  carve_features(a, planes, a->feat_buf.p);
   a->features = planes;
   return RT_OK;
 }

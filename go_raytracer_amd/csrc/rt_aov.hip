@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "rt_hip_util.h"
+#include "rt_host_units.h"
 // the render's camera rays, traversal, record loop and textures: not its path state or
 // shading core (rt_path.h)
 #include "rt_camera.h"
@@ -298,7 +299,9 @@ namespace {
 // library stream are shared
 std::mutex g_mu;
 DeviceScratch g_stacks, g_stage;
-std::vector<hipStream_t> g_streams;
+// the library stream of each device ordinal.  Process lifetime: the list is never destroyed, so
+// no stream is released while the runtime unloads.
+std::vector<Stream>& g_streams = *new std::vector<Stream>();
 
 template <int TREE>
 void launch_aov(bool split, dim3 grid, hipStream_t stream, const Params& p, const AovOut& ao, const AovEmit& ae) {
@@ -344,13 +347,9 @@ int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, 
   if (npix64 >= 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_render_aov: image too large");
   const uint32_t npix = (uint32_t)npix64;
 
-  hipStream_t stream = (hipStream_t)o.stream;
-  if (!stream) {
-    if ((int)g_streams.size() <= o.device) g_streams.resize(o.device + 1, nullptr);
-    if (!g_streams[o.device])
-      HIP_OK(hipStreamCreateWithFlags(&g_streams[o.device], hipStreamNonBlocking));
-    stream = g_streams[o.device];
-  }
+  hipStream_t stream;
+  if ((int)g_streams.size() <= o.device) g_streams.resize(o.device + 1);
+  if ((rc = g_streams[o.device].pick(o.stream, &stream))) return rc;
 
   const int blocks = (int)std::min<uint32_t>((npix + 255u) / 256u,
                                              (uint32_t)(view.tree == 0 ? kAovMaxBlocks : kAovMaxTreeBlocks));

@@ -29,7 +29,7 @@
 #include <chrono>
 #include <vector>
 
-#include "rt_internal.h"
+#include "rt_hip_util.h"
 
 namespace rt {
 namespace {
@@ -42,13 +42,6 @@ constexpr int kR = PLOC_R;  // PLOC search radius (clusters on each side)
 #define PLOC_TOP 16384  // clusters left to the host full SAH sweep: C5 render +2.5 % vs the host tree (1: +6 %)
 #endif
 constexpr int kBlock = 256;
-
-#define B_OK(expr)                                                                       \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess)                                                                \
-      return set_error(RT_ERR_DEVICE, "bvh build: %s: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
 
 __device__ __forceinline__ float4 fmin4(float4 a, float4 b) {
   return make_float4(fminf(a.x, b.x), fminf(a.y, b.y), fminf(a.z, b.z), 0.0f);
@@ -223,21 +216,6 @@ __global__ __launch_bounds__(kBlock) void k_emit(const int* nn, int m, int force
     chi2[o] = chi[i];
   }
 }
-
-struct DevBuf {
-  std::vector<void*> p;
-  ~DevBuf() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  template <typename T>
-  int alloc(T** out, size_t n) {
-    void* q = nullptr;
-    B_OK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-    p.push_back(q);
-    *out = (T*)q;
-    return RT_OK;
-  }
-};
 
 double area_of(const F4& lo, const F4& hi) {
   const double dx = (double)hi.x - lo.x, dy = (double)hi.y - lo.y, dz = (double)hi.z - lo.z;
@@ -446,57 +424,50 @@ int build_bvh_device(HostScene& s, const std::vector<F4>& lo, const std::vector<
   auto t0 = std::chrono::steady_clock::now();
   // device < 0: the calling thread's current device (one process per GPU builds on its
   // own GPU); the caller's current device is restored on return
-  int prev = 0;
-  B_OK(hipGetDevice(&prev));
-  if (device < 0) device = prev;
-  struct DeviceGuard {
-    int d;
-    ~DeviceGuard() { (void)hipSetDevice(d); }
-  } dg{prev};
-  B_OK(hipSetDevice(device));
+  DeviceGuard dg;
+  if (device < 0) device = dg.prev;
+  HIP_OK(hipSetDevice(device));
+  int rc;
+  Stream own;  // the build's stream and buffers, released when it returns
   hipStream_t st;
-  B_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  struct StreamGuard {
-    hipStream_t s;
-    ~StreamGuard() { (void)hipStreamDestroy(s); }
-  } sg{st};
-  DevBuf B;
+  if ((rc = own.pick(nullptr, &st))) return rc;
+  DevicePool pool;
+  auto alloc = [&pool](auto** out, size_t count) { return pool.alloc(out, count, "bvh build"); };
   float4 *dlo, *dhi, *part, *nlo, *nhi, *clo[2], *chi[2];
   uint64_t *key, *key2;
   uint32_t *val, *val2;
   int *cl[2], *nn, *create, *valid, *sc, *sv, *counts;
   const int nodes = 2 * n - 1;
   const int nb = (n + kBlock - 1) / kBlock, nparts = std::min(nb, 1024);
-  int rc;
-  if ((rc = B.alloc(&dlo, n)) || (rc = B.alloc(&dhi, n)) || (rc = B.alloc(&part, 2 * nparts)) ||
-      (rc = B.alloc(&nlo, nodes)) || (rc = B.alloc(&nhi, nodes)) || (rc = B.alloc(&clo[0], n)) ||
-      (rc = B.alloc(&chi[0], n)) || (rc = B.alloc(&clo[1], n)) || (rc = B.alloc(&chi[1], n)) ||
-      (rc = B.alloc(&key, n)) || (rc = B.alloc(&key2, n)) || (rc = B.alloc(&val, n)) ||
-      (rc = B.alloc(&val2, n)) || (rc = B.alloc(&cl[0], n)) || (rc = B.alloc(&cl[1], n)) ||
-      (rc = B.alloc(&nn, n)) || (rc = B.alloc(&create, n)) || (rc = B.alloc(&valid, n)) ||
-      (rc = B.alloc(&sc, n)) || (rc = B.alloc(&sv, n)) || (rc = B.alloc(&counts, 2)))
+  if ((rc = alloc(&dlo, n)) || (rc = alloc(&dhi, n)) || (rc = alloc(&part, 2 * nparts)) ||
+      (rc = alloc(&nlo, nodes)) || (rc = alloc(&nhi, nodes)) || (rc = alloc(&clo[0], n)) ||
+      (rc = alloc(&chi[0], n)) || (rc = alloc(&clo[1], n)) || (rc = alloc(&chi[1], n)) ||
+      (rc = alloc(&key, n)) || (rc = alloc(&key2, n)) || (rc = alloc(&val, n)) ||
+      (rc = alloc(&val2, n)) || (rc = alloc(&cl[0], n)) || (rc = alloc(&cl[1], n)) ||
+      (rc = alloc(&nn, n)) || (rc = alloc(&create, n)) || (rc = alloc(&valid, n)) ||
+      (rc = alloc(&sc, n)) || (rc = alloc(&sv, n)) || (rc = alloc(&counts, 2)))
     return rc;
   static_assert(sizeof(F4) == sizeof(float4), "F4 layout");
-  B_OK(hipMemcpyAsync(dlo, lo.data(), n * sizeof(float4), hipMemcpyHostToDevice, st));
-  B_OK(hipMemcpyAsync(dhi, hi.data(), n * sizeof(float4), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(dlo, lo.data(), n * sizeof(float4), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(dhi, hi.data(), n * sizeof(float4), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_bounds, dim3(nparts), dim3(kBlock), 0, st, dlo, dhi, n, part);
   hipLaunchKernelGGL(k_morton, dim3(nb), dim3(kBlock), 0, st, dlo, dhi, n, part, nparts, key, val);
-  B_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
   // stable radix sort of (code, index) pairs
   size_t tmp_sort = 0, tmp_scan = 0;
-  B_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, key, key2, val, val2, n, 0, 63, st));
-  B_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, create, sc, n, st));
+  HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, key, key2, val, val2, n, 0, 63, st));
+  HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, create, sc, n, st));
   void* tmp = nullptr;
   {
     char* t8;
-    if ((rc = B.alloc(&t8, std::max(tmp_sort, tmp_scan)))) return rc;
+    if ((rc = alloc(&t8, std::max(tmp_sort, tmp_scan)))) return rc;
     tmp = t8;
   }
   size_t tb = tmp_sort;
-  B_OK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key2, val, val2, n, 0, 63, st));
+  HIP_OK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key2, val, val2, n, 0, 63, st));
   hipLaunchKernelGGL(k_leaves, dim3(nb), dim3(kBlock), 0, st, dlo, dhi, n, val2, nlo, nhi, cl[0],
                      clo[0], chi[0]);
-  B_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
   // PLOC iterations down to `top` clusters; the top of the tree is then built on
   // the host by a full SAH sweep over those clusters (PLOC's radius-limited merges
   // are weakest where few large clusters remain)
@@ -508,16 +479,16 @@ int build_bvh_device(HostScene& s, const std::vector<F4>& lo, const std::vector<
     if (!force) hipLaunchKernelGGL(k_nn, dim3(g), dim3(kBlock), 0, st, clo[cur], chi[cur], m, nn);
     hipLaunchKernelGGL(k_flags, dim3(g), dim3(kBlock), 0, st, nn, m, force, create, valid);
     tb = tmp_scan;
-    B_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, create, sc, m, st));
+    HIP_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, create, sc, m, st));
     tb = tmp_scan;
-    B_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, valid, sv, m, st));
+    HIP_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, valid, sv, m, st));
     hipLaunchKernelGGL(k_emit, dim3(g), dim3(kBlock), 0, st, nn, m, force, create, valid, sc, sv,
                        node_base, cl[cur], clo[cur], chi[cur], nlo, nhi, cl[cur ^ 1], clo[cur ^ 1],
                        chi[cur ^ 1], counts);
-    B_OK(hipGetLastError());
+    HIP_OK(hipGetLastError());
     int hc[2];
-    B_OK(hipMemcpyAsync(hc, counts, sizeof hc, hipMemcpyDeviceToHost, st));
-    B_OK(hipStreamSynchronize(st));
+    HIP_OK(hipMemcpyAsync(hc, counts, sizeof hc, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
     force = hc[1] == 0;  // no mutual pair: pair neighbours next time (guaranteed progress)
     node_base += hc[1];
     m = hc[0];
@@ -527,13 +498,13 @@ int build_bvh_device(HostScene& s, const std::vector<F4>& lo, const std::vector<
   std::vector<uint32_t> order(n);
   std::vector<int> top_ids(m);
   std::vector<F4> top_lo(m), top_hi(m);
-  B_OK(hipMemcpyAsync(hlo.data(), nlo, node_base * sizeof(F4), hipMemcpyDeviceToHost, st));
-  B_OK(hipMemcpyAsync(hhi.data(), nhi, node_base * sizeof(F4), hipMemcpyDeviceToHost, st));
-  B_OK(hipMemcpyAsync(order.data(), val2, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  B_OK(hipMemcpyAsync(top_ids.data(), cl[cur], m * sizeof(int), hipMemcpyDeviceToHost, st));
-  B_OK(hipMemcpyAsync(top_lo.data(), clo[cur], m * sizeof(F4), hipMemcpyDeviceToHost, st));
-  B_OK(hipMemcpyAsync(top_hi.data(), chi[cur], m * sizeof(F4), hipMemcpyDeviceToHost, st));
-  B_OK(hipStreamSynchronize(st));
+  HIP_OK(hipMemcpyAsync(hlo.data(), nlo, node_base * sizeof(F4), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(hhi.data(), nhi, node_base * sizeof(F4), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(order.data(), val2, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(top_ids.data(), cl[cur], m * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(top_lo.data(), clo[cur], m * sizeof(F4), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(top_hi.data(), chi[cur], m * sizeof(F4), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
   if (m > 1) build_top_sah(top_ids, top_lo, top_hi, hlo, hhi, node_base);
   if (node_base != nodes) return set_error(RT_ERR_DEVICE, "bvh build: %d of %d nodes", node_base, nodes);
   auto t1 = std::chrono::steady_clock::now();

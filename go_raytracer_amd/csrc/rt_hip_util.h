@@ -1,8 +1,12 @@
-// rt_hip_util.h — host-side helpers shared by the HIP translation units of the render, the
-// feature pass and the denoiser (rt_render.hip, rt_aov.hip, rt_denoise.hip): the error macro,
-// the current-device guard and the grow-only per-device scratch.
+// rt_hip_util.h — the generic host-side HIP helpers of every HIP translation unit: the error
+// macro, the current-device guard, and the owners of device memory, streams and events.  No
+// other unit calls hipMalloc, hipFree, hipStreamCreate*, hipStreamDestroy, hipEventCreate* or
+// hipEventDestroy (DESIGN.md "Device resources"; tests/test_hip_resources.py).  What the render,
+// the accumulator and the feature pass declare for one another is rt_host_units.h.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "rt_internal.h"
 
@@ -39,94 +43,152 @@ inline int device_ok(const char* who, int device) {
   return RT_OK;
 }
 
-// rt_render.hip, shared with the feature pass (rt_aov.hip): the camera part of the launch
-// parameters (rt_params.h Params: image plane, sample grid, rank, seed, the width and
-// spp_sqrt fast divisions), and the rows of an H-row image that `rank` of `nranks` renders
-struct Params;
-void set_camera_params(Params& p, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t npix);
-uint32_t rank_rows(uint32_t H, int rank, int nranks);
+// ------------------------------------------------------------------- owners ---
+// Device memory, streams and events belong to one of the types below, and each frees what it
+// holds when it is destroyed.  None of them records or switches the device: whoever allocates
+// from, resets or destroys an owner has the owner's device current, as the entries have after
+// their hipSetDevice and as release_device, free_accum and RcclGather::release make it before
+// they delete.  `who` names the ABI entry in the error message.
 
-// rt_render.hip, for the accumulator (rt_accum.hip): one render pass of rt_render's own
-// path (slot 0, the same plans, launches, buffers and mutex) that hands its sums to a sink
-// instead of resolving them.  fold runs where k_resolve would: the pass's launches are
-// enqueued on `stream`, p holds what k_resolve reads (accum, csum, side, pflags) and scale is
-// pixel_samples_scale; render_pass synchronises the stream after it.  max_passes: a sample
-// stays in the exact fixed-point sum below 2^31 / (spp_sqrt^2 * max_passes), so the sum over
-// that many passes stays inside int64 (Params::vlim; 1 is rt_render's limit).
-struct PassSink {
-  uint32_t max_passes;
-  int (*fold)(void* ctx, const Params& p, double scale, hipStream_t stream);
-  void* ctx;
-};
-// map (optional): an active-pixel pass over the n sorted local pixels of the
-// share listed in `pixels` (device memory).  The pass is then an image of n pixels of its own:
-// p.npix = n, p's sums are indexed by the place in the list, the chunk plan is the one of an
-// n x 1 image, and the fused kernel's MAP twin runs whatever the mode asks (RT_ERR_UNSUPPORTED
-// before any launch for RT_MODE_WAVEFRONT, and for a structure without a twin).
-struct PixelMap {
-  const uint32_t* pixels;
-  uint32_t n;
-};
-int render_pass(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
-                const PassSink* sink, const PixelMap* map = nullptr);
+// A failed allocation, reported the same way by every owner: out of memory is RT_ERR_OOM,
+// anything else RT_ERR_DEVICE, and HIP's last error is cleared (a failed hipMalloc is not
+// sticky: the next hipGetLastError of the thread would report it as a launch failure).
+inline int alloc_failed(const char* who, size_t bytes, hipError_t e) {
+  (void)hipGetLastError();
+  return set_error(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_DEVICE, "%s: device allocation of %zu bytes: %s",
+                   who, bytes, hipGetErrorString(e));
+}
 
-// rt_render.hip, for rt_render_multi (rt_multi.hip): share `share` of the image (opts.rank of
-// opts.nranks on opts.device) rendered in the scene's slot 1 + share, resolved into out_dev (or
-// the slot's own buffer when null) and then, with a gather, handed off: the share's image (rows
-// of this rank, [rows][W][3]) is copied to `dst` on device `dst_device` (peer copy over xGMI when
-// the devices differ) on the share's stream, before the render returns.
-struct Gather {
-  float* dst;
-  int dst_device;
-};
-int render_share(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
-                 int share, float* out_dev, const Gather* gather);
-
-// The accumulator's feature sums, a structure of planes over the npix pixels of
-// the share: the per-pass fp32 sums of the feature rays (rt_aov.hip k_aov_fold), added in fp64.
-// A group that is not enabled has null pointers.
-struct FeatPlanes {
-  double* albedo;          // [3][npix]  the RT_ACCUM_FEAT_GUIDES group
-  double* normal;          // [3][npix]
-  double* depth;           // [npix]
-  double* emission;        // [3][npix]  the RT_ACCUM_FEAT_EMIT group
-  double* surface_albedo;  // [3][npix]
-  uint32_t* nlight;        // [npix]     samples whose first hit is a light's front face (exact)
-  uint32_t npix;
-};
-// rt_aov.hip, for the accumulator (rt_accum.hip): the feature fold of one pass.  aov_fold_begin
-// does what can fail without a launch, before the render starts: the scene's aov_view on
-// o.device and the overflow-stack scratch for a pass of n_pass pixels; on RT_OK it holds the
-// feature pass's mutex until aov_fold_end (after the pass's stream is synchronised).  Between
-// the two, aov_fold_enqueue launches k_aov_fold on `stream` for o.seed: the pass's pixel v is
-// pixel map[v] of the share (px), or v when map is null.
-int aov_fold_begin(rt_scene* scene, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t n_pass);
-int aov_fold_enqueue(const FeatPlanes& F, bool px, const uint32_t* map, hipStream_t stream);
-void aov_fold_end();
-
-// Grow-only device scratch, one buffer per device ordinal (as rt_output.hip's): no allocation
-// per call once warm.  The caller serialises its users, and no work that reads an old buffer
-// may be in flight when a larger one is asked for (the old one is freed).
-struct DeviceScratch {
-  std::vector<void*> buf;
-  std::vector<size_t> cap;
-  int get(int device, size_t bytes, void** out, const char* who) {
-    if ((int)buf.size() <= device) {
-      buf.resize(device + 1, nullptr);
-      cap.resize(device + 1, 0);
+// Allocations that die together: a scene's device copy, a render slot's buffers, one build.
+struct DevicePool {
+  std::vector<void*> allocs;
+  DevicePool() = default;
+  DevicePool(const DevicePool&) = delete;
+  DevicePool& operator=(const DevicePool&) = delete;
+  ~DevicePool() {
+    for (void* p : allocs) (void)hipFree(p);
+  }
+  // `bytes` (> 0) or nothing: false without a word in rt_last_error, for a caller with a fallback
+  bool try_alloc(void** out, size_t bytes, hipError_t* err = nullptr) {
+    const hipError_t e = hipMalloc(out, bytes);
+    if (err) *err = e;
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      *out = nullptr;
+      return false;
     }
-    if (cap[device] < bytes) {
-      if (buf[device]) (void)hipFree(buf[device]);
-      buf[device] = nullptr;
-      cap[device] = 0;
-      if (hipMalloc(&buf[device], bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return set_error(RT_ERR_OOM, "%s: scratch of %zu bytes", who, bytes);
-      }
-      cap[device] = bytes;
-    }
-    *out = buf[device];
+    allocs.push_back(*out);
+    return true;
+  }
+  // count elements, a zero count rounded up to one
+  template <typename T>
+  int alloc(T** out, size_t count, const char* who) {
+    const size_t bytes = (count ? count : 1) * sizeof(T);
+    hipError_t e;
+    return try_alloc((void**)out, bytes, &e) ? RT_OK : alloc_failed(who, bytes, e);
+  }
+  // v's copy on the device; an empty v is a null pointer and no allocation
+  template <typename T>
+  int upload(const std::vector<T>& v, const T** out, const char* who) {
+    *out = nullptr;
+    if (v.empty()) return RT_OK;
+    T* p = nullptr;
+    const int rc = alloc(&p, v.size(), who);
+    if (rc) return rc;
+    HIP_OK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    *out = p;
     return RT_OK;
+  }
+  // one buffer ahead of the rest (a grow-on-demand member about to be replaced or dropped)
+  template <typename T>
+  int free(T** p) {
+    if (!*p) return RT_OK;
+    HIP_OK(hipFree(*p));
+    allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)*p));
+    *p = nullptr;
+    return RT_OK;
+  }
+};
+
+// One allocation and its size; move-only.
+struct DeviceBuffer {
+  void* p = nullptr;
+  size_t bytes = 0;
+  DeviceBuffer() = default;
+  DeviceBuffer(DeviceBuffer&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+  ~DeviceBuffer() { reset(); }
+  void reset() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  // at least `need` bytes (zero rounded up to one); the contents do not survive growing, and a
+  // failure leaves the buffer empty: the old allocation is freed before the new one is made
+  int grow(size_t need, const char* who) {
+    if (p && bytes >= need) return RT_OK;
+    reset();
+    const size_t n = need ? need : 1;
+    const hipError_t e = hipMalloc(&p, n);
+    if (e != hipSuccess) {
+      p = nullptr;
+      return alloc_failed(who, n, e);
+    }
+    bytes = n;
+    return RT_OK;
+  }
+};
+
+// A non-blocking stream, created on first use; move-only.
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+  ~Stream() { reset(); }
+  void reset() {
+    if (s) (void)hipStreamDestroy(s);
+    s = nullptr;
+  }
+  // the caller's stream when it gave one, else this one
+  int pick(void* callers, hipStream_t* out) {
+    if (!callers && !s) HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    *out = callers ? (hipStream_t)callers : s;
+    return RT_OK;
+  }
+  int ensure() { hipStream_t made; return pick(nullptr, &made); }
+};
+
+// Events created as they are first needed and kept for reuse.
+struct Events {
+  std::vector<hipEvent_t> ev;
+  Events() = default;
+  Events(const Events&) = delete;
+  Events& operator=(const Events&) = delete;
+  ~Events() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+  // at least n events, the new ones with `flags` (hipEventDefault, hipEventDisableTiming)
+  int ensure(size_t n, unsigned flags) {
+    while (ev.size() < n) {
+      hipEvent_t e;
+      HIP_OK(hipEventCreateWithFlags(&e, flags));
+      ev.push_back(e);
+    }
+    return RT_OK;
+  }
+};
+
+// Grow-only device scratch, one buffer per device ordinal (`device` is current), for a file-scope
+// instance: no allocation per call once warm.  The buffers are never deleted: they live as long
+// as the process, so nothing is freed while the runtime unloads.  The caller serialises its
+// users, and no work that reads an old buffer may be in flight when a larger one is asked for.
+struct DeviceScratch {
+  std::vector<DeviceBuffer*> buf;
+  int get(int device, size_t bytes, void** out, const char* who) {
+    if ((int)buf.size() <= device) buf.resize(device + 1, nullptr);
+    if (!buf[device]) buf[device] = new DeviceBuffer();
+    const int rc = bytes ? buf[device]->grow(bytes, who) : RT_OK;
+    *out = buf[device]->p;
+    return rc;
   }
 };
 

@@ -1,0 +1,76 @@
+// rt_host_units.h — what the host sides of the render (rt_render.hip), the feature pass
+// (rt_aov.hip), the accumulator (rt_accum.hip) and rt_render_multi (rt_multi.hip) declare for
+// one another.  The generic HIP helpers and the resource owners are rt_hip_util.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "rt_internal.h"
+
+namespace rt {
+
+// rt_render.hip, shared with the feature pass (rt_aov.hip): the camera part of the launch
+// parameters (rt_params.h Params: image plane, sample grid, rank, seed, the width and
+// spp_sqrt fast divisions), and the rows of an H-row image that `rank` of `nranks` renders
+struct Params;
+void set_camera_params(Params& p, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t npix);
+uint32_t rank_rows(uint32_t H, int rank, int nranks);
+
+// rt_render.hip, for the accumulator (rt_accum.hip): one render pass of rt_render's own
+// path (slot 0, the same plans, launches, buffers and mutex) that hands its sums to a sink
+// instead of resolving them.  fold runs where k_resolve would: the pass's launches are
+// enqueued on `stream`, p holds what k_resolve reads (accum, csum, side, pflags) and scale is
+// pixel_samples_scale; render_pass synchronises the stream after it.  max_passes: a sample
+// stays in the exact fixed-point sum below 2^31 / (spp_sqrt^2 * max_passes), so the sum over
+// that many passes stays inside int64 (Params::vlim; 1 is rt_render's limit).
+struct PassSink {
+  uint32_t max_passes;
+  int (*fold)(void* ctx, const Params& p, double scale, hipStream_t stream);
+  void* ctx;
+};
+// map (optional): an active-pixel pass over the n sorted local pixels of the
+// share listed in `pixels` (device memory).  The pass is then an image of n pixels of its own:
+// p.npix = n, p's sums are indexed by the place in the list, the chunk plan is the one of an
+// n x 1 image, and the fused kernel's MAP twin runs whatever the mode asks (RT_ERR_UNSUPPORTED
+// before any launch for RT_MODE_WAVEFRONT, and for a structure without a twin).
+struct PixelMap {
+  const uint32_t* pixels;
+  uint32_t n;
+};
+int render_pass(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
+                const PassSink* sink, const PixelMap* map = nullptr);
+
+// rt_render.hip, for rt_render_multi (rt_multi.hip): share `share` of the image (opts.rank of
+// opts.nranks on opts.device) rendered in the scene's slot 1 + share, resolved into out_dev (or
+// the slot's own buffer when null) and then, with a gather, handed off: the share's image (rows
+// of this rank, [rows][W][3]) is copied to `dst` on device `dst_device` (peer copy over xGMI when
+// the devices differ) on the share's stream, before the render returns.
+struct Gather {
+  float* dst;
+  int dst_device;
+};
+int render_share(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, rt_stats* stats,
+                 int share, float* out_dev, const Gather* gather);
+
+// The accumulator's feature sums, a structure of planes over the npix pixels of
+// the share: the per-pass fp32 sums of the feature rays (rt_aov.hip k_aov_fold), added in fp64.
+// A group that is not enabled has null pointers.
+struct FeatPlanes {
+  double* albedo;          // [3][npix]  the RT_ACCUM_FEAT_GUIDES group
+  double* normal;          // [3][npix]
+  double* depth;           // [npix]
+  double* emission;        // [3][npix]  the RT_ACCUM_FEAT_EMIT group
+  double* surface_albedo;  // [3][npix]
+  uint32_t* nlight;        // [npix]     samples whose first hit is a light's front face (exact)
+  uint32_t npix;
+};
+// rt_aov.hip, for the accumulator (rt_accum.hip): the feature fold of one pass.  aov_fold_begin
+// does what can fail without a launch, before the render starts: the scene's aov_view on
+// o.device and the overflow-stack scratch for a pass of n_pass pixels; on RT_OK it holds the
+// feature pass's mutex until aov_fold_end (after the pass's stream is synchronised).  Between
+// the two, aov_fold_enqueue launches k_aov_fold on `stream` for o.seed: the pass's pixel v is
+// pixel map[v] of the share (px), or v when map is null.
+int aov_fold_begin(rt_scene* scene, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t n_pass);
+int aov_fold_enqueue(const FeatPlanes& F, bool px, const uint32_t* map, hipStream_t stream);
+void aov_fold_end();
+
+}  // namespace rt

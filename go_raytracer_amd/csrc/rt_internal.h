@@ -85,8 +85,9 @@ struct HostScene {
   int32_t tuned = 0;        // tuning knobs set when the scene was created (rt_scene_info.tuned)
 };
 
-struct DeviceScene;  // defined in the HIP translation unit
+struct DeviceScene;  // defined in the HIP translation units
 struct RenderState;
+struct MultiState;
 
 // Progress of the tracked render (rt_progress): written by the rendering thread,
 // read by any polling thread under `mu`.  One render is tracked at a time: the
@@ -151,10 +152,7 @@ struct Scene {
   std::map<int, DeviceSlot*> devs;                  // per device ordinal, uploaded lazily
   std::map<std::pair<int, int>, SlotState*> slots;  // per (device, slot)
   std::mutex multi_mu;                              // one rt_render_multi at a time
-  void* multi_buf = nullptr;                        // gather + image buffer on the first device
-  size_t multi_bytes = 0;
-  int multi_dev = -1;
-  void* rccl = nullptr;                             // RCCL gather state (rt_multi.hip RcclGather)
+  MultiState* multi = nullptr;                      // its gather buffer and RCCL state (rt_multi.hip)
   Progress prog;
   std::vector<rt_accum*> accums;                    // accumulators alive (rt_accum.hip), under mu
   // the compressed BVH4 (host_qbvh.cpp), built on the host once, at the first render that

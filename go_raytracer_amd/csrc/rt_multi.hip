@@ -14,6 +14,7 @@
 #include <rccl/rccl.h>
 
 #include "rt_hip_util.h"
+#include "rt_host_units.h"
 
 namespace rt {
 
@@ -22,14 +23,14 @@ namespace rt {
 struct RcclGather {
   std::vector<int> devs;
   std::vector<ncclComm_t> comms;
-  std::vector<hipStream_t> streams;
-  std::vector<float*> send;
-  size_t send_floats = 0;
+  std::vector<Stream> streams;
+  std::vector<DeviceBuffer> send;
+  size_t send_floats = 0;  // what every send buffer holds (0: grow them first)
   void release() {
     for (size_t i = 0; i < comms.size(); ++i) {
       (void)hipSetDevice(devs[i]);
-      if (send.size() > i && send[i]) (void)hipFree(send[i]);
-      if (streams.size() > i && streams[i]) (void)hipStreamDestroy(streams[i]);
+      if (send.size() > i) send[i].reset();
+      if (streams.size() > i) streams[i].reset();
       (void)ncclCommDestroy(comms[i]);
     }
     devs.clear();
@@ -40,17 +41,19 @@ struct RcclGather {
   }
 };
 
+// rt_render_multi's device state (Scene::multi, created by the first call, under multi_mu)
+struct MultiState {
+  DeviceBuffer gather;  // gather + image buffer on gather_dev, the device list's first
+  int gather_dev = -1;
+  RcclGather rccl;      // empty until a call asks for RT_FLAG_GATHER_RCCL
+};
+
 void release_multi(Scene* s) {
-  if (s->rccl) {
-    static_cast<RcclGather*>(s->rccl)->release();
-    delete static_cast<RcclGather*>(s->rccl);
-    s->rccl = nullptr;
-  }
-  if (s->multi_buf) {
-    (void)hipSetDevice(s->multi_dev);
-    (void)hipFree(s->multi_buf);
-    s->multi_buf = nullptr;
-  }
+  if (!s->multi) return;
+  s->multi->rccl.release();
+  if (s->multi->gather.p) (void)hipSetDevice(s->multi->gather_dev);
+  delete s->multi;
+  s->multi = nullptr;
 }
 
 // rows of share i ([rows_per][W][3] at gather + i*rows_per*W*3) -> image rows r = i + n*k
@@ -65,18 +68,14 @@ __global__ __launch_bounds__(256) void k_deinterleave(const float* gather, float
 }
 
 // the scene's gather + image buffer on device d0 (current), at least `need` bytes
-static int ensure_gather_buffer(Scene* s, int d0, size_t need) {
-  if (s->multi_buf && s->multi_dev == d0 && s->multi_bytes >= need) return RT_OK;
-  if (s->multi_buf) {
-    (void)hipSetDevice(s->multi_dev);
-    (void)hipFree(s->multi_buf);
-    s->multi_buf = nullptr;
+static int ensure_gather_buffer(MultiState* ms, int d0, size_t need) {
+  if (ms->gather.p && ms->gather_dev != d0) {  // another list's first device: freed there
+    (void)hipSetDevice(ms->gather_dev);
+    ms->gather.reset();
     HIP_OK(hipSetDevice(d0));
   }
-  HIP_OK(hipMalloc(&s->multi_buf, std::max<size_t>(need, 4)));
-  s->multi_bytes = need;
-  s->multi_dev = d0;
-  return RT_OK;
+  ms->gather_dev = d0;
+  return ms->gather.grow(need, "rt_render_multi");
 }
 
 // xGMI peer access both ways.  "Already enabled" is success; any other failure is
@@ -112,13 +111,12 @@ static int enable_peers(const int32_t* devices, int n) {
 
 // The scene's RCCL state for this device list and share size: communicators over the list,
 // cached, and a send buffer of share_floats per share.  Leaves devices[0] current.
-static int setup_rccl(Scene* s, const int32_t* devices, int n, size_t share_floats, RcclGather** out) {
+static int setup_rccl(RcclGather* rg, const int32_t* devices, int n, size_t share_floats) {
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < i; ++j)
       if (devices[i] == devices[j])
         return set_error(RT_ERR_INVALID, "rt_render_multi: RCCL gather needs distinct devices");
-  if (!s->rccl) s->rccl = new RcclGather();
-  RcclGather* rg = static_cast<RcclGather*>(s->rccl);
+  int rc;
   if (rg->devs != std::vector<int>(devices, devices + n)) {
     rg->release();
     rg->devs.assign(devices, devices + n);
@@ -129,25 +127,22 @@ static int setup_rccl(Scene* s, const int32_t* devices, int n, size_t share_floa
       rg->devs.clear();
       return set_error(RT_ERR_DEVICE, "rt_render_multi: ncclCommInitAll: %s", ncclGetErrorString(r));
     }
-    rg->streams.assign(n, nullptr);
-    rg->send.assign(n, nullptr);
+    rg->streams.resize(n);
+    rg->send.resize(n);
     for (int i = 0; i < n; ++i) {
       HIP_OK(hipSetDevice(devices[i]));
-      HIP_OK(hipStreamCreateWithFlags(&rg->streams[i], hipStreamNonBlocking));
+      if ((rc = rg->streams[i].ensure())) return rc;
     }
   }
   if (rg->send_floats < share_floats) {
+    rg->send_floats = 0;  // until every buffer has grown: after a failure the next call grows again
     for (int i = 0; i < n; ++i) {
       HIP_OK(hipSetDevice(devices[i]));
-      if (rg->send[i]) HIP_OK(hipFree(rg->send[i]));
-      rg->send[i] = nullptr;
-      HIP_OK(hipMalloc(&rg->send[i], std::max<size_t>(share_floats, 1) * sizeof(float)));
+      if ((rc = rg->send[i].grow(share_floats * sizeof(float), "rt_render_multi"))) return rc;
     }
     rg->send_floats = share_floats;
   }
-  const int d0 = devices[0];
-  HIP_OK(hipSetDevice(d0));
-  *out = rg;
+  HIP_OK(hipSetDevice(devices[0]));
   return RT_OK;
 }
 
@@ -157,8 +152,8 @@ static int gather_rccl(RcclGather* rg, const int32_t* devices, int n, size_t sha
   ncclResult_t r = ncclGroupStart();
   for (int i = 0; r == ncclSuccess && i < n; ++i) {
     HIP_OK(hipSetDevice(devices[i]));
-    r = ncclGather(rg->send[i], i == 0 ? (void*)gbuf : nullptr, share_floats, ncclFloat32, 0,
-                   rg->comms[i], rg->streams[i]);
+    r = ncclGather(rg->send[i].p, i == 0 ? (void*)gbuf : nullptr, share_floats, ncclFloat32, 0,
+                   rg->comms[i], rg->streams[i].s);
   }
   const ncclResult_t r2 = ncclGroupEnd();
   if (r == ncclSuccess) r = r2;
@@ -166,7 +161,7 @@ static int gather_rccl(RcclGather* rg, const int32_t* devices, int n, size_t sha
     return set_error(RT_ERR_DEVICE, "rt_render_multi: ncclGather: %s", ncclGetErrorString(r));
   for (int i = 0; i < n; ++i) {
     HIP_OK(hipSetDevice(devices[i]));
-    HIP_OK(hipStreamSynchronize(rg->streams[i]));
+    HIP_OK(hipStreamSynchronize(rg->streams[i].s));
   }
   return RT_OK;
 }
@@ -219,12 +214,14 @@ static int render_multi(rt_scene* scene, const rt_camera* cam, const rt_render_o
   const int d0 = devices[0];
   DeviceGuard dg;  // the caller's current device is restored on every return
   HIP_OK(hipSetDevice(d0));
-  if ((rc = ensure_gather_buffer(s, d0, (gather_floats + img_floats) * sizeof(float)))) return rc;
-  float* gbuf = (float*)s->multi_buf;
+  if (!s->multi) s->multi = new MultiState();
+  if ((rc = ensure_gather_buffer(s->multi, d0, (gather_floats + img_floats) * sizeof(float)))) return rc;
+  float* gbuf = (float*)s->multi->gather.p;
   float* img = out_dev ? out_dev : gbuf + gather_floats;
   if ((rc = enable_peers(devices, n))) return rc;
-  RcclGather* rg = nullptr;  // RT_FLAG_GATHER_RCCL: the shares gathered by one collective
-  if ((o.flags & RT_FLAG_GATHER_RCCL) && (rc = setup_rccl(s, devices, n, share_floats, &rg))) return rc;
+  // RT_FLAG_GATHER_RCCL: the shares gathered by one collective
+  RcclGather* rg = (o.flags & RT_FLAG_GATHER_RCCL) ? &s->multi->rccl : nullptr;
+  if (rg && (rc = setup_rccl(rg, devices, n, share_floats))) return rc;
   // rt_progress: this call's shares are the tracked render unless another holds it.
   // Claimed only after every early return of the setup above, so every return below
   // releases it.  (No slice events: the shares add their samples when done.)
@@ -243,7 +240,7 @@ static int render_multi(rt_scene* scene, const rt_camera* cam, const rt_render_o
       oi.progress_slices = 0;
       const Gather g = {gbuf + (size_t)i * share_floats, d0};
       // (RCCL: the share's rows into its padded send buffer; the gather follows)
-      rcs[i] = render_share(scene, cam, &oi, &st[i], i, rg ? rg->send[i] : nullptr, rg ? nullptr : &g);
+      rcs[i] = render_share(scene, cam, &oi, &st[i], i, rg ? (float*)rg->send[i].p : nullptr, rg ? nullptr : &g);
       if (rcs[i] != RT_OK) {
         errs[i] = rt_last_error();
       } else if (track) {  // rt_progress advances share by share

@@ -20,13 +20,9 @@
 #include <string.h>
 
 #include <mutex>
-#include <vector>
 
-#include "rt_abi.h"
+#include "rt_hip_util.h"
 
-namespace rt {
-int set_error(int code, const char* fmt, ...);
-}
 using rt::set_error;
 
 namespace {
@@ -179,38 +175,9 @@ __global__ __launch_bounds__(kThreads) void k_quantize(const float* __restrict__
     out[i] = (uint8_t)quant(rgb[i]);
 }
 
-// grow-only per-device scratch for tile sums (+1 slot for the grand total)
-struct Scratch {
-  std::mutex mu;
-  std::vector<void*> buf;
-  std::vector<size_t> cap;
-};
-Scratch g_scratch;
-
-int scratch(int device, size_t bytes, void** out) {
-  std::lock_guard<std::mutex> lk(g_scratch.mu);
-  if ((int)g_scratch.buf.size() <= device) {
-    g_scratch.buf.resize(device + 1, nullptr);
-    g_scratch.cap.resize(device + 1, 0);
-  }
-  if (g_scratch.cap[device] < bytes) {
-    if (g_scratch.buf[device]) (void)hipFree(g_scratch.buf[device]);
-    g_scratch.buf[device] = nullptr;
-    g_scratch.cap[device] = 0;
-    if (hipMalloc(&g_scratch.buf[device], bytes) != hipSuccess)
-      return set_error(RT_ERR_OOM, "rt_format_ppm_device: scratch of %zu bytes", bytes);
-    g_scratch.cap[device] = bytes;
-  }
-  *out = g_scratch.buf[device];
-  return RT_OK;
-}
-
-#define HIP_OK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess)                                                               \
-      return set_error(RT_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(_e));   \
-  } while (0)
+// the tile sums (+1 slot for the grand total), per device
+std::mutex g_scratch_mu;
+rt::DeviceScratch g_scratch;
 
 }  // namespace
 
@@ -221,6 +188,7 @@ int rt_quantize_device(const float* rgb_dev, int64_t n_pixels, uint8_t* out_dev,
   if (n_pixels < 0 || (n_pixels > 0 && (!rgb_dev || !out_dev)))
     return set_error(RT_ERR_INVALID, "rt_quantize_device: bad args");
   if (n_pixels == 0) return RT_OK;
+  rt::DeviceGuard dg;  // the caller's current device is restored on every return
   HIP_OK(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const int64_t n3 = 3 * n_pixels;
@@ -241,12 +209,17 @@ int64_t rt_format_ppm_device(const float* rgb_dev, int w, int h, char* out_dev, 
   const int64_t ntiles = (n + kTile - 1) / kTile;
   if (ntiles > (int64_t)1024 * 65536)
     return set_error(RT_ERR_INVALID, "rt_format_ppm_device: %lld pixels", (long long)n);
+  rt::DeviceGuard dg;  // the caller's current device is restored on every return
   HIP_OK(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   int64_t body = 0;
   if (n > 0) {
     void* scr = nullptr;
-    int rc = scratch(device, (size_t)(ntiles + 1) * sizeof(int64_t), &scr);
+    int rc;
+    {
+      std::lock_guard<std::mutex> lk(g_scratch_mu);
+      rc = g_scratch.get(device, (size_t)(ntiles + 1) * sizeof(int64_t), &scr, "rt_format_ppm_device");
+    }
     if (rc) return rc;
     int64_t* tiles = (int64_t*)scr;
     int64_t* grand = tiles + ntiles;

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "rt_hip_util.h"
+#include "rt_host_units.h"
 #include "rt_path.h"
 #include "rt_fused.h"
 #include "rt_resolve.h"
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(256) void k_resolve(Params P, float* out, double sc
 // ==================================================================== host ==
 struct DeviceScene {
   int device = -1;
-  std::vector<void*> allocs;
+  DevicePool pool;              // every array below, freed with the copy
   DevScene d{};                 // nodes = BVH4
   const F4* nodes2 = nullptr;   // BVH2 of the same leaves (tiny scenes)
   const F4* brute_pairs = nullptr;  // quad records in pairs, largest first (record loop)
@@ -189,9 +190,6 @@ struct DeviceScene {
   size_t qitems = 0;
   std::mutex qmu;                   // ensure_qbvh: the first render that needs it uploads it
   bool q_done = false;
-  ~DeviceScene() {
-    for (void* p : allocs) (void)hipFree(p);
-  }
 };
 
 struct RenderState {
@@ -199,8 +197,8 @@ struct RenderState {
   uint32_t P = 0;
   int depth_cap = 0;
   uint32_t npix = 0;
-  hipStream_t own_stream = nullptr;
-  std::vector<void*> allocs;
+  Stream own_stream;  // for renders without opts.stream
+  DevicePool pool;    // every buffer below
   F4 *ray_o = nullptr, *ray_d = nullptr, *hit = nullptr, *pend = nullptr, *pre = nullptr,
      *stack = nullptr;
   uint2* path = nullptr;
@@ -215,8 +213,8 @@ struct RenderState {
   uint32_t ostack_cols = 0;
   float* out = nullptr;
   uint32_t out_cap = 0;
-  std::vector<hipEvent_t> events;
-  std::vector<hipEvent_t> prog_events;  // one per progress slice (rt_progress)
+  Events events;       // RT_FLAG_PROFILE (ProfEvents)
+  Events prog_events;  // one per progress slice (rt_progress)
   int resident_blocks = 0;
   // the launch parameters' pointers into these buffers (csum: the render has the chunk sums)
   void bind(Params& p, bool use_csum) const {
@@ -236,16 +234,6 @@ struct RenderState {
     p.pflags = pflags;
     p.ostack = ostack;
     p.stack_cols = ostack_cols;
-  }
-  void free_all() {
-    for (void* p : allocs) (void)hipFree(p);
-    allocs.clear();
-  }
-  ~RenderState() {
-    free_all();
-    for (auto e : events) (void)hipEventDestroy(e);
-    for (auto e : prog_events) (void)hipEventDestroy(e);
-    if (own_stream) (void)hipStreamDestroy(own_stream);
   }
 };
 
@@ -270,18 +258,6 @@ void release_device(Scene* s) {
     delete kv.second;
   }
   s->devs.clear();
-}
-
-template <typename T>
-static int upload(DeviceScene* ds, const std::vector<T>& v, const T** out) {
-  *out = nullptr;
-  if (v.empty()) return RT_OK;
-  void* p = nullptr;
-  HIP_OK(hipMalloc(&p, v.size() * sizeof(T)));
-  ds->allocs.push_back(p);
-  HIP_OK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = (const T*)p;
-  return RT_OK;
 }
 
 // (the scheduling knobs below, A/B experiments with measured defaults, are tune_int: rt_tune_set
@@ -334,8 +310,9 @@ static int upload_scene(const Scene* s, DeviceScene* ds) {
   DevScene& d = ds->d;
   const std::vector<DevMaterial> mats = materials_with_uv_flag(h);
   int rc;
-#define UP(vec, field)                                      \
-  if ((rc = upload(ds, vec, &d.field)) != RT_OK) return rc;
+  auto upload = [ds](const auto& vec, auto* out) { return ds->pool.upload(vec, out, "scene upload"); };
+#define UP(vec, field)                                  \
+  if ((rc = upload(vec, &d.field)) != RT_OK) return rc;
   UP(h.sph_cr, sph_cr);
   UP(h.sph_mv, sph_mv);
   UP(h.sph_uv, sph_uv);
@@ -354,13 +331,13 @@ static int upload_scene(const Scene* s, DeviceScene* ds) {
       return set_error(RT_ERR_UNSUPPORTED, "scene: BVH nodes + leaf records exceed 4 GiB");
     tree_buf.insert(tree_buf.end(), recs.begin(), recs.end());
     const F4* base = nullptr;
-    if ((rc = upload(ds, tree_buf, &base)) != RT_OK) return rc;
+    if ((rc = upload(tree_buf, &base)) != RT_OK) return rc;
     d.nodes = base;
     d.leafprims = base ? base + rec0 : nullptr;
   }
   // (the compressed BVH4 is built and uploaded on demand: ensure_qbvh)
   const bool small = tiny_scene(h);  // the BVH2 and the record-loop pairs: tiny scenes only
-  if (small && (rc = upload(ds, h.nodes, &ds->nodes2)) != RT_OK) return rc;
+  if (small && (rc = upload(h.nodes, &ds->nodes2)) != RT_OK) return rc;
   ds->root2 = h.root;
   ds->n_nodes2 = small ? (int32_t)(h.nodes.size() / 4) : 0;
   UP(h.refs, refs);
@@ -387,7 +364,7 @@ static int upload_scene(const Scene* s, DeviceScene* ds) {
     ds->brute_boxes = rp.n_boxes;
     ds->brute_shape = rp.shape;
     ds->emitter_slot = rp.emitter_slot;
-    if ((rc = upload(ds, rp.pairs, &ds->brute_pairs)) != RT_OK) return rc;
+    if ((rc = upload(rp.pairs, &ds->brute_pairs)) != RT_OK) return rc;
   }
   UP(h.media, media);
   UP(h.medium_refs, medium_refs);
@@ -420,15 +397,6 @@ static int upload_scene(const Scene* s, DeviceScene* ds) {
   return RT_OK;
 }
 
-template <typename T>
-static int dalloc(RenderState* st, T** p, size_t count) {
-  void* q = nullptr;
-  HIP_OK(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-  st->allocs.push_back(q);
-  *p = (T*)q;
-  return RT_OK;
-}
-
 // slot-indexed wavefront buffers (only for WAVEFRONT) + the weight stack,
 // counters and pixel accumulators (both modes)
 static int ensure_state(SlotState* slot, int device, uint32_t P, int depth_cap, uint32_t npix,
@@ -446,28 +414,19 @@ static int ensure_state(SlotState* slot, int device, uint32_t P, int depth_cap, 
   st->depth_cap = depth_cap;
   st->npix = npix;
   int rc;
-  if ((rc = dalloc(st, &st->stack, (size_t)P * depth_cap)) || (rc = dalloc(st, &st->ctr, 1)) ||
-      (rc = dalloc(st, &st->accum, 3 * (size_t)npix)) || (rc = dalloc(st, &st->side, 3 * (size_t)npix)) ||
-      (rc = dalloc(st, &st->pflags, npix)) ||
-      (rc = dalloc(st, &st->out, 3 * (size_t)npix)))
+  auto alloc = [st](auto** out, size_t count) { return st->pool.alloc(out, count, "rt_render"); };
+  if ((rc = alloc(&st->stack, (size_t)P * depth_cap)) || (rc = alloc(&st->ctr, 1)) ||
+      (rc = alloc(&st->accum, 3 * (size_t)npix)) || (rc = alloc(&st->side, 3 * (size_t)npix)) ||
+      (rc = alloc(&st->pflags, npix)) ||
+      (rc = alloc(&st->out, 3 * (size_t)npix)))
     return rc;
   if (soa &&
-      ((rc = dalloc(st, &st->ray_o, P)) || (rc = dalloc(st, &st->ray_d, P)) ||
-       (rc = dalloc(st, &st->hit, P)) || (rc = dalloc(st, &st->pend, P)) ||
-       (rc = dalloc(st, &st->pre, P)) ||
-       (rc = dalloc(st, &st->path, P)) || (rc = dalloc(st, &st->queue[0], (size_t)kXcd * P)) ||
-       (rc = dalloc(st, &st->queue[1], (size_t)kXcd * P))))
+      ((rc = alloc(&st->ray_o, P)) || (rc = alloc(&st->ray_d, P)) ||
+       (rc = alloc(&st->hit, P)) || (rc = alloc(&st->pend, P)) ||
+       (rc = alloc(&st->pre, P)) ||
+       (rc = alloc(&st->path, P)) || (rc = alloc(&st->queue[0], (size_t)kXcd * P)) ||
+       (rc = alloc(&st->queue[1], (size_t)kXcd * P))))
     return rc;
-  return RT_OK;
-}
-
-// frees one of st's buffers (a grow-on-demand buffer about to be replaced or dropped)
-template <typename T>
-static int dfree(RenderState* st, T** p) {
-  if (!*p) return RT_OK;
-  HIP_OK(hipFree(*p));
-  st->allocs.erase(std::find(st->allocs.begin(), st->allocs.end(), (void*)*p));
-  *p = nullptr;
   return RT_OK;
 }
 
@@ -475,8 +434,9 @@ static int dfree(RenderState* st, T** p) {
 static int ensure_ostack(RenderState* st, uint32_t cols) {
   if (st->ostack_cols >= cols) return RT_OK;
   int rc;
-  if ((rc = dfree(st, &st->ostack))) return rc;
-  if ((rc = dalloc(st, &st->ostack, (size_t)(kStack - kShortStackMin) * cols))) return rc;
+  if ((rc = st->pool.free(&st->ostack))) return rc;
+  st->ostack_cols = 0;  // (a failed allocation below leaves no columns, not the old count)
+  if ((rc = st->pool.alloc(&st->ostack, (size_t)(kStack - kShortStackMin) * cols, "rt_render"))) return rc;
   st->ostack_cols = cols;
   return RT_OK;
 }
@@ -502,7 +462,7 @@ static int ensure_csum(RenderState* st, uint32_t n_chunks, bool* use_csum_io, bo
     const size_t need_b = 32 * (size_t)n_chunks;
     auto drop_csum = [&]() -> int {
       st->csum_chunks = 0;
-      return dfree(st, &st->csum);
+      return st->pool.free(&st->csum);
     };
     if (st->csum && (!use_csum || (st->csum_chunks > 4 * (size_t)n_chunks &&
                                    32 * st->csum_chunks > ((size_t)256 << 20))))
@@ -512,15 +472,12 @@ static int ensure_csum(RenderState* st, uint32_t n_chunks, bool* use_csum_io, bo
       size_t free_b = 0, total_b = 0;
       const size_t cap_b = (size_t)std::max(0, tune_int("RT_CSUM_MAX_MB", 16384)) << 20;
       if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-      void* q = nullptr;
-      if (need_b <= cap_b && need_b <= free_b / 2 && hipMalloc(&q, std::max<size_t>(need_b, 32)) == hipSuccess) {
-        st->allocs.push_back(q);
-        st->csum = (unsigned long long*)q;
+      // (a failed allocation is not an error: pixel atomics instead)
+      if (need_b <= cap_b && need_b <= free_b / 2 &&
+          st->pool.try_alloc((void**)&st->csum, std::max<size_t>(need_b, 32)))
         st->csum_chunks = n_chunks;
-      } else {
-        (void)hipGetLastError();  // a failed allocation is not sticky: pixel atomics instead
+      else
         use_csum = false;
-      }
     }
   }
   *use_csum_io = use_csum;
@@ -570,7 +527,7 @@ static int ensure_qbvh(Scene* s, DeviceScene* ds) {
     }
   }
   if (s->qb_items) {
-    const int rc = upload(ds, s->qb, &ds->qnodes);
+    const int rc = ds->pool.upload(s->qb, &ds->qnodes, "scene upload");
     if (rc != RT_OK) return rc;
     ds->qitems = s->qb_items;
   }
@@ -990,17 +947,6 @@ static SchedPlan plan_sched(uint32_t ft_set, int tree, bool f_lds, uint32_t K, s
   return sd;
 }
 
-// A device allocation of one call: whatever `p` still points at when the scope ends is freed, so
-// every error exit between the hipMalloc and the success path's own hipFree (which then clears
-// `p`) releases it.
-template <typename T>
-struct FreeOnExit {
-  T*& p;
-  ~FreeOnExit() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // RT_FLAG_PROFILE: events around every kernel, as index pairs into st->events
 struct ProfEvents {
   RenderState* st;
@@ -1008,18 +954,15 @@ struct ProfEvents {
   int used = 0;
   std::vector<std::pair<int, int>> ext, shade, fused;
   int next(hipEvent_t* e) {
-    if (used >= (int)st->events.size()) {
-      hipEvent_t ne;
-      HIP_OK(hipEventCreate(&ne));
-      st->events.push_back(ne);
-    }
-    *e = st->events[used++];
+    const int rc = st->events.ensure((size_t)used + 1, hipEventDefault);
+    if (rc) return rc;
+    *e = st->events.ev[used++];
     return RT_OK;
   }
   int sum_ms(const std::vector<std::pair<int, int>>& v, double* acc) const {
     for (auto& pr : v) {
       float ms = 0;
-      HIP_OK(hipEventElapsedTime(&ms, st->events[pr.first], st->events[pr.second]));
+      HIP_OK(hipEventElapsedTime(&ms, st->events.ev[pr.first], st->events.ev[pr.second]));
       *acc += ms;
     }
     return RT_OK;
@@ -1041,12 +984,11 @@ static int launch_fused(Params& p, RenderState* st, hipStream_t stream, const St
   // cycles -> binary file RT_WAVE_TIMES, kWaveRec u64 per wave
   std::string wt_file;
   const char* wt_path = tune_str("RT_WAVE_TIMES", &wt_file) ? wt_file.c_str() : nullptr;
-  unsigned long long* wt = nullptr;
-  FreeOnExit<unsigned long long> wt_guard{wt};
+  DeviceBuffer wt;
   const size_t n_waves = (size_t)fused_blocks * 4;
   if (wt_path && *wt_path) {
-    HIP_OK(hipMalloc(&wt, kWaveRec * n_waves * sizeof(unsigned long long)));
-    p.wave_times = wt;
+    if ((rc = wt.grow(kWaveRec * n_waves * sizeof(unsigned long long), "rt_render"))) return rc;
+    p.wave_times = (unsigned long long*)wt.p;
   }
   void* args[] = {&p};
   for (int sl = 0; sl < slices; ++sl) {
@@ -1058,15 +1000,13 @@ static int launch_fused(Params& p, RenderState* st, hipStream_t stream, const St
     }
     HIP_OK(hipLaunchKernel(sp.kernel, dim3(fused_blocks), dim3(256), args, sp.lds_bytes, stream));
     HIP_OK(hipGetLastError());
-    if (slices > 1) HIP_OK(hipEventRecord(st->prog_events[sl], stream));
+    if (slices > 1) HIP_OK(hipEventRecord(st->prog_events.ev[sl], stream));
   }
   p.n_chunks = n_chunks;
-  if (wt) {
+  if (wt.p) {
     std::vector<unsigned long long> h(kWaveRec * n_waves);
-    HIP_OK(hipMemcpyAsync(h.data(), wt, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(h.data(), wt.p, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
-    HIP_OK(hipFree(wt));
-    wt = nullptr;
     p.wave_times = nullptr;
     if (FILE* f = fopen(wt_path, "wb")) {
       fwrite(h.data(), sizeof(h[0]), h.size(), f);
@@ -1180,7 +1120,7 @@ struct RenderTarget {
   float* host = nullptr;           // the image, copied to host memory
   float* dev = nullptr;            // resolved into this device buffer instead of the slot's own
   int slot_id = 0;                 // 0: rt_render[_device] and passes; 1 + i: share i of rt_render_multi
-  const Gather* gather = nullptr;  // the share's hand-off (rt_hip_util.h)
+  const Gather* gather = nullptr;  // the share's hand-off (rt_host_units.h)
   const PassSink* sink = nullptr;  // an accumulator's pass: folded into its sums, not resolved
   const PixelMap* map = nullptr;   // an active-pixel pass
 };
@@ -1270,26 +1210,25 @@ static int sweep_order(Params& p, int mode, uint32_t ft_set, const ChunkPlan& cp
 }
 
 // opts.trace_out: the device buffer the traced sample's vertices are recorded in (t = -1: a
-// vertex the path did not reach); the caller's guard frees it
-static int start_trace(Params& p, const rt_render_opts& o, F4*& dtrace) {
+// vertex the path did not reach); the caller's buffer, freed when the render returns
+static int start_trace(Params& p, const rt_render_opts& o, DeviceBuffer* dtrace) {
   if (!(o.trace_out && o.trace_cap > 0)) return RT_OK;
-  HIP_OK(hipMalloc(&dtrace, (size_t)o.trace_cap * 3 * sizeof(F4)));
+  const int rc = dtrace->grow((size_t)o.trace_cap * 3 * sizeof(F4), "rt_render");
+  if (rc) return rc;
   std::vector<float> init((size_t)o.trace_cap * 12, 0.0f);
   for (int v = 0; v < o.trace_cap; ++v) init[12 * v + 7] = -1.0f;
-  HIP_OK(hipMemcpy(dtrace, init.data(), init.size() * 4, hipMemcpyHostToDevice));
-  p.trace = dtrace;
+  HIP_OK(hipMemcpy(dtrace->p, init.data(), init.size() * 4, hipMemcpyHostToDevice));
+  p.trace = (F4*)dtrace->p;
   p.trace_gpix = (uint32_t)o.trace_pixel;
   p.trace_sample = (uint32_t)o.trace_sample;
   p.trace_cap = o.trace_cap;
   return RT_OK;
 }
 
-// ... copied to opts.trace_out after the render, and freed
-static int read_trace(const rt_render_opts& o, F4*& dtrace) {
-  if (!dtrace) return RT_OK;
-  HIP_OK(hipMemcpy(o.trace_out, dtrace, (size_t)o.trace_cap * 3 * sizeof(F4), hipMemcpyDeviceToHost));
-  HIP_OK(hipFree(dtrace));
-  dtrace = nullptr;
+// ... copied to opts.trace_out after the render
+static int read_trace(const rt_render_opts& o, const DeviceBuffer& dtrace) {
+  if (!dtrace.p) return RT_OK;
+  HIP_OK(hipMemcpy(o.trace_out, dtrace.p, (size_t)o.trace_cap * 3 * sizeof(F4), hipMemcpyDeviceToHost));
   return RT_OK;
 }
 
@@ -1301,13 +1240,6 @@ static int ensure_trav_stacks(RenderState* st, int device, int mode, uint32_t P,
       (rc = occupancy_blocks(extend_kernel, device, &st->resident_blocks)))
     return rc;
   return ensure_ostack(st, mode == RT_MODE_FUSED ? P : (uint32_t)st->resident_blocks * 256u);
-}
-
-// the caller's stream, or the slot's own (created on first use)
-static int render_stream(RenderState* st, const rt_render_opts& o, hipStream_t* stream) {
-  if (!o.stream && !st->own_stream) HIP_OK(hipStreamCreateWithFlags(&st->own_stream, hipStreamNonBlocking));
-  *stream = o.stream ? (hipStream_t)o.stream : st->own_stream;
-  return RT_OK;
 }
 
 // |v| < 2^31 / ss: the ss-sample fixed-point sum of a pixel stays inside int64 (a pass of an
@@ -1329,22 +1261,12 @@ static int clear_sums(const RenderState* st, uint32_t npix, hipStream_t stream) 
   return RT_OK;
 }
 
-// rt_progress of a render in `slices` launches: the slot's event per slice, created on first
-// use, ...
-static int slice_events(RenderState* st, int slices) {
-  while ((int)st->prog_events.size() < slices) {
-    hipEvent_t e;
-    HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    st->prog_events.push_back(e);
-  }
-  return RT_OK;
-}
-// ... and, in the record of the render that claimed it, those events with the samples complete
-// when each has fired
+// rt_progress of a render in `slices` launches: in the record of the render that claimed it, the
+// slot's event per slice with the samples complete when each has fired
 static void track_slices(Progress& pr, const RenderState* st, int slices, uint32_t n_chunks) {
   std::lock_guard<std::mutex> lk(pr.mu);
   for (int sl = 0; sl < slices; ++sl) {
-    pr.events.push_back((void*)st->prog_events[sl]);
+    pr.events.push_back((void*)st->prog_events.ev[sl]);
     pr.cum.push_back((uint64_t)((double)pr.total * (double)((uint64_t)n_chunks * (sl + 1) / slices) /
                                 (double)n_chunks));
   }
@@ -1439,7 +1361,7 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   bool use_csum = mode == RT_MODE_FUSED && tune_int("RT_CSUM", 1) != 0;
   if ((rc = ensure_csum(st, n_chunks, &use_csum, map != nullptr))) return rc;
   hipStream_t stream = nullptr;
-  if ((rc = render_stream(st, o, &stream))) return rc;
+  if ((rc = st->own_stream.pick(o.stream, &stream))) return rc;  // the caller's, or the slot's own
 
   Params p{};
   set_camera_params(p, cd, o, npix);
@@ -1447,9 +1369,8 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
   st->bind(p, use_csum);
   p.pixmap = map ? map->pixels : nullptr;
   p.vlim = sample_limit(ss, tg.sink);
-  F4* dtrace = nullptr;
-  FreeOnExit<F4> trace_guard{dtrace};
-  if ((rc = start_trace(p, o, dtrace))) return rc;
+  DeviceBuffer dtrace;
+  if ((rc = start_trace(p, o, &dtrace))) return rc;
   ProfEvents ev{st, (o.flags & RT_FLAG_PROFILE) != 0};
 
   if ((rc = clear_sums(st, npix, stream))) return rc;
@@ -1459,7 +1380,7 @@ static int render_impl(rt_scene* scene, const rt_camera* cam, const rt_render_op
                          ? std::max(1, std::min(o.progress_slices, 1024))
                          : 1;
   if (slices > 1) p.parts_log2 = 0;
-  if ((rc = slice_events(st, slices))) return rc;
+  if ((rc = st->prog_events.ensure((size_t)slices, hipEventDisableTiming))) return rc;
   // rt_progress: an rt_render call (slot 0) claims the record when no other render holds it
   // (rt_render_multi claims it for its shares); every return path below releases it
   ProgressDone prog_done{s->prog, tg.slot_id == 0 && claim_progress(s->prog, (uint64_t)npix * ss, o.device)};

@@ -32,7 +32,9 @@ enum {
   RT_ERR_INVALID = -1,     /* bad argument / handle */
   RT_ERR_UNSUPPORTED = -2, /* e.g. a BVH or transform used as a light (hittable.go:69-72) */
   RT_ERR_DEVICE = -3,      /* HIP runtime failure or no GPU */
-  RT_ERR_OOM = -4,
+  RT_ERR_OOM = -4,         /* out of memory; a device allocation that hipMalloc refuses with
+                              hipErrorOutOfMemory, in every entry (the render, the BVH build and
+                              rt_render_multi reported RT_ERR_DEVICE for it before) */
   RT_ERR_IO = -5
 };
 

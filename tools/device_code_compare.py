@@ -17,7 +17,11 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-UNITS = ["rt_render", "rt_fused_sets", "rt_fused_map", "rt_aov", "rt_accum", "rt_multi"]
+UNITS = ["rt_render", "rt_fused_sets", "rt_fused_map", "rt_aov", "rt_accum", "rt_multi", "rt_output", "rt_build",
+         "rt_denoise"]
+# units without the kernel headers: no build switch reaches them, the default build is all there is
+PLAIN_UNITS = ["rt_output", "rt_build", "rt_denoise"]
+NAME_MAX = 160  # a printed kernel name is cut here (hipCUB's run to kilobytes)
 BUILDS = {"default": [], "bvh8": ["-DRT_BVH8_KERNELS"], "sweep": ["-DRT_SWEEP_ORDER"]}
 # rt_fused_sets.hip's own flags (Makefile FUSED_SETS_FLAGS)
 SETS_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
@@ -40,7 +44,8 @@ def emit_one(csrc, out, build, unit):
 def emit(csrc, out):
     os.makedirs(out, exist_ok=True)
     out = os.path.abspath(out)
-    jobs = [(b, u) for b in BUILDS for u in UNITS if os.path.exists(os.path.join(csrc, u + ".hip"))]
+    jobs = [(b, u) for b in BUILDS for u in UNITS
+            if os.path.exists(os.path.join(csrc, u + ".hip")) and (b == "default" or u not in PLAIN_UNITS)]
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
         res = list(ex.map(lambda j: emit_one(csrc, out, *j), jobs))
     bad = [f"{b}.{u}" for b, u, rc in res if rc]
@@ -82,7 +87,7 @@ def streams(path):
 
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return dict(zip(names, out))
+    return {k: v if len(v) <= NAME_MAX else v[:NAME_MAX] + "..." for k, v in zip(names, out)}
 
 
 def diff(pdir, ndir):
