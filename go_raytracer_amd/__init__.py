@@ -23,7 +23,7 @@ __all__ = ["Tree", "Camera", "Scene", "Accumulator", "quantize", "format_ppm", "
            "tune", "untune", "tuning", "tune_knobs", "tune_from_env",
            "demo_scene", "DEMO_SCENES", "build_bvh_boxes", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
            "format_ppm_device", "denoise", "denoise_device", "denoise_var", "denoise_var_device",
-           "RtDenoiseVarOpts"]
+           "RtDenoiseVarOpts", "reproject", "reproject_device", "Temporal"]
 
 DEMO_SCENES = ("book1", "book2", "book3", "simple_light", "quads", "cornell", "cornell_smoke",
                "model")
@@ -656,6 +656,7 @@ class Accumulator:
         d = camera.derived()
         self.shape = (len(range(rank, d.height, nranks)), d.width)
         c = camera.to_c()
+        self.camera, self.nranks = Camera.from_c(c), nranks  # the camera as it is now: a copy
         o = Scene._opts(0, device, rank, nranks, path_slots, chunk, profile, stream, mode)
         o.progress_slices = progress_slices
         p = C.c_void_p()
@@ -1145,6 +1146,153 @@ def denoise_var_device(rgb, var, aov=None, out=None, var_out=None, split_emitter
     (rt_denoise_var_emit_device): as denoise_device's.  Runs on the tensor's current stream and
     returns `out` after the work completes."""
     return _denoise_dev(True, rgb, var, aov, out, var_out, split_emitters, opts)
+
+
+_FRAME_KEYS = (("rgb", 3), ("var", 0), ("count", 0), ("normal", 3), ("depth", 0))
+
+
+def _reproject_opts(max_history=0.0, depth_tol=0.0, normal_tol=0.0, min_weight=0.0):
+    return _lib.RtReprojectOpts(max_history, depth_tol, normal_tol, min_weight)
+
+
+def _frame(who, name, f, h, w, conv, ptr):
+    """An RtFrame over the dict `f` ("rgb", "normal", "depth"; optional "var" and "count", the
+    count an array or one number for every pixel) -> (RtFrame, the arrays it points into).
+    conv(key, value, shape) checks or converts one buffer, ptr(buffer) is its address."""
+    if not isinstance(f, dict):
+        raise ValueError(f"{who}: {name} must be a dict of rgb, normal, depth (and var, count)")
+    keep, ptrs, scalar = [], [], 0.0
+    for k, ch in _FRAME_KEYS:
+        t = f.get(k)
+        if k == "count" and isinstance(t, (int, float)):
+            t, scalar = None, float(t)
+        if t is None:
+            if k in ("rgb", "normal", "depth"):
+                raise ValueError(f"{who}: {name}[{k!r}] is required")
+            ptrs.append(None)
+            continue
+        t = conv(f"{name}[{k!r}]", t, (h, w, ch) if ch else (h, w))
+        keep.append(t)
+        ptrs.append(ptr(t))
+    return _lib.RtFrame(*ptrs, scalar, 0), keep
+
+
+def reproject(cam_prev, prev, cam_cur, cur, **opts):
+    """Temporal reprojection (rt_reproject) on host arrays: the frame `cur` seen by `cam_cur`
+    blended with the history `prev` seen by `cam_prev` that lies behind each of its pixels.  A
+    frame is a dict of float32 arrays "rgb" [H, W, 3], "normal" [H, W, 3] and "depth" [H, W] (as
+    Accumulator.resolve / resolve_aov give them) with an optional "var" [H, W] (missing: 0) and
+    "count" ([H, W], or one number for every pixel; missing: 0, which marks every pixel
+    invalid).  opts: max_history, depth_tol, normal_tol, min_weight (0 = the library defaults).
+    Returns new arrays (rgb, var, count)."""
+    who = "reproject"
+    if not isinstance(cur, dict) or cur.get("rgb") is None:
+        raise ValueError(f"{who}: cur['rgb'] is required")
+    h, w = np.shape(cur["rgb"])[:2]
+
+    def conv(name, t, shape):
+        a = np.ascontiguousarray(t, dtype=np.float32)
+        if a.shape != shape:
+            raise ValueError(f"{who}: {name} must have shape {shape}, not {a.shape}")
+        return a
+    fp, keep_p = _frame(who, "prev", prev, h, w, conv, lambda a: a.ctypes.data)
+    fc, keep_c = _frame(who, "cur", cur, h, w, conv, lambda a: a.ctypes.data)
+    rgb, var, cnt = (np.empty((h, w, 3), np.float32), np.empty((h, w), np.float32),
+                     np.empty((h, w), np.float32))
+    fo = _lib.RtFrame(rgb.ctypes.data, var.ctypes.data, cnt.ctypes.data, None, None, 0.0, 0)
+    o = _reproject_opts(**opts)
+    cp, cc = cam_prev.to_c(), cam_cur.to_c()
+    check(lib().rt_reproject(C.byref(cp), C.byref(fp), C.byref(cc), C.byref(fc), w, h, C.byref(o),
+                             C.byref(fo)))
+    return rgb, var, cnt
+
+
+def reproject_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
+    """rt_reproject_device on torch tensors: frames as reproject's, every buffer a contiguous
+    float32 tensor on cur["rgb"]'s device.  `out`: a dict of the "rgb" / "var" / "count" tensors
+    to write (missing or None: a new tensor); they may be cur's own (in place), never prev's.
+    Runs on the tensors' current stream and returns (rgb, var, count) after the work completes."""
+    import torch
+    who = "reproject_device"
+    if not isinstance(cur, dict) or not torch.is_tensor(cur.get("rgb")) or cur["rgb"].dim() != 3:
+        raise ValueError(f"{who}: cur['rgb'] must be a [H, W, 3] tensor")
+    a = cur["rgb"]
+    h, w = a.shape[:2]
+
+    def conv(name, t, shape):
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous()
+                or tuple(t.shape) != shape or t.device != a.device):
+            raise ValueError(f"{who}: {name} must be a contiguous float32 tensor of shape {shape} "
+                             "on cur['rgb']'s device")
+        return t
+    fp, keep_p = _frame(who, "prev", prev, h, w, conv, lambda t: t.data_ptr())
+    fc, keep_c = _frame(who, "cur", cur, h, w, conv, lambda t: t.data_ptr())
+    res = []
+    for k, ch in _FRAME_KEYS[:3]:
+        shape = (h, w, ch) if ch else (h, w)
+        t = (out or {}).get(k)
+        t = torch.empty(shape, dtype=torch.float32, device=a.device) if t is None else conv(f"out[{k!r}]", t, shape)
+        if any(t.data_ptr() == p.data_ptr() for p in keep_p):
+            raise ValueError(f"{who}: out[{k!r}] is a buffer of prev (the taps gather from prev)")
+        res.append(t)
+    fo = _lib.RtFrame(*[t.data_ptr() for t in res], None, None, 0.0, 0)
+    o = _reproject_opts(**opts)
+    cp, cc = cam_prev.to_c(), cam_cur.to_c()
+    check(lib().rt_reproject_device(C.byref(cp), C.byref(fp), C.byref(cc), C.byref(fc), w, h,
+                                    C.byref(o), C.byref(fo), a.device.index or 0, _stream_of(a)))
+    return tuple(res)
+
+
+class Temporal:
+    """The history of a moving camera (DESIGN.md "Temporal reprojection"): ``push(acc)`` takes the
+    accumulator of the next frame, reprojects the stored history into its camera
+    (reproject_device) and keeps the result as the new history.  Two sets of device tensors are
+    owned and used in turn, so a push allocates nothing once warm.  opts: reproject's
+    (max_history, depth_tol, normal_tol, min_weight).  The scene is static and the cameras have
+    no defocus; ``reset()`` drops the history (a cut, a changed scene)."""
+
+    def __init__(self, **opts):
+        _reproject_opts(**opts)  # a wrong name fails here, not at the second push
+        self._opts = opts
+        self._sets = [None, None]
+        self.reset()
+
+    def reset(self):
+        """Drop the history: the next push returns its frame unchanged."""
+        self._prev, self._cam = None, None
+
+    def push(self, acc):
+        """`acc`: an Accumulator with features ("guides" or "emit") of the whole image
+        (nranks == 1) holding at least one pass.  Resolves its mean, variance, normal and depth on
+        the device, every pixel weighing acc.passes, and blends the history into them.  Returns
+        the tensors (rgb [H, W, 3], var [H, W], count [H, W]) ready for denoise_var_device; they
+        belong to this object and are overwritten by the push after the next.  The first push
+        (and the first after reset()) returns the current frame unchanged."""
+        import torch
+        if acc.features is None:
+            raise ValueError("Temporal.push: needs an accumulator with features (the normal and depth guides)")
+        if acc.nranks != 1:
+            raise ValueError("Temporal.push: needs the whole image (nranks == 1)")
+        passes = acc.passes
+        if passes < 1:
+            raise ValueError("Temporal.push: the accumulator holds no pass")
+        k = 0 if self._prev != 0 else 1  # the set the history is not in
+        h, w = acc.shape
+        dev = torch.device("cuda", acc._device)
+        s = self._sets[k]
+        if s is None or s["depth"].shape != (h, w) or s["depth"].device != dev:
+            s = self._sets[k] = {key: torch.empty((h, w, ch) if ch else (h, w), dtype=torch.float32, device=dev)
+                                 for key, ch in _FRAME_KEYS}
+        acc.resolve_device(s["rgb"], s["var"])
+        guides = RtAov(None, s["normal"].data_ptr(), s["depth"].data_ptr(), None)
+        check(lib().rt_accum_resolve_aov_device(acc._h(), C.byref(guides), None))
+        p = None if self._prev is None else self._sets[self._prev]
+        if p is None or p["depth"].shape != (h, w) or p["depth"].device != dev:
+            s["count"].fill_(float(passes))
+        else:
+            reproject_device(self._cam, p, acc.camera, dict(s, count=float(passes)), out=s, **self._opts)
+        self._prev, self._cam = k, acc.camera
+        return s["rgb"], s["var"], s["count"]
 
 
 def device_count():

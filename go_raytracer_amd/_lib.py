@@ -117,6 +117,17 @@ class RtDenoiseVarOpts(C.Structure):
                 ("sigma_depth", C.c_float), ("_pad", C.c_int32)]
 
 
+class RtFrame(C.Structure):  # rt_frame: one frame of rt_reproject (var and count may be NULL)
+    _fields_ = [("rgb", C.c_void_p), ("var", C.c_void_p), ("count", C.c_void_p),
+                ("normal", C.c_void_p), ("depth", C.c_void_p),
+                ("count_scalar", C.c_float), ("_pad", C.c_int32)]
+
+
+class RtReprojectOpts(C.Structure):  # rt_reproject_opts (0 = the library default)
+    _fields_ = [("max_history", C.c_float), ("depth_tol", C.c_float),
+                ("normal_tol", C.c_float), ("min_weight", C.c_float)]
+
+
 class RtAccumInfo(C.Structure):  # rt_accum_info
     _fields_ = [("passes", C.c_int32), ("max_passes", C.c_int32),
                 ("samples_per_pixel", C.c_uint64), ("nonfinite_pixels", C.c_uint64),
@@ -300,6 +311,12 @@ SIGNATURES = {
     "rt_accum_get_features": (_I, [_P, C.POINTER(C.c_uint32)]),
     "rt_accum_resolve_aov": (_I, [_P, C.POINTER(RtAov), C.POINTER(RtAovEmit)]),
     "rt_accum_resolve_aov_device": (_I, [_P, C.POINTER(RtAov), C.POINTER(RtAovEmit)]),
+    "rt_reproject": (_I, [C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtCamera),
+                          C.POINTER(RtFrame), _I, _I, C.POINTER(RtReprojectOpts),
+                          C.POINTER(RtFrame)]),
+    "rt_reproject_device": (_I, [C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtCamera),
+                                 C.POINTER(RtFrame), _I, _I, C.POINTER(RtReprojectOpts),
+                                 C.POINTER(RtFrame), _I, C.c_void_p]),
     "rt_demo_scene": (_I, [_P, C.c_char_p, C.c_char_p, C.POINTER(RtCamera), C.POINTER(_I),
                            C.POINTER(_I)]),
     "rt_demo_scene_name": (_I, [_I, C.POINTER(C.c_char_p)]),

@@ -1,0 +1,271 @@
+// rt_temporal.hip — temporal reprojection (rt_reproject, include/rt_abi.h): the previous frame's
+// colour, variance and history length carried into the current camera through the depth and
+// normal buffers, the stage Schied et al., "Spatiotemporal Variance-Guided Filtering", HPG 2017,
+// put in front of the spatial filter (rt_denoise.hip's Var mode).  A pure image operation beside
+// the denoiser: accumulate -> resolve -> reproject -> denoise -> quantize -> PPM in HBM.
+//
+//   k_reproject : one lane per pixel of the current frame, a wave = one 64-pixel row segment of a
+//                 64 x 4 tile (every read and write of the current frame is a coalesced row
+//                 segment).  The lane rebuilds the hit point from its depth, projects it into the
+//                 previous camera and gathers the four bilinear taps of the previous frame, each
+//                 tested against the reprojected depth and the current normal.  Both cameras
+//                 travel as kernel arguments: they are wave-uniform, so they live in SGPRs and
+//                 cost no memory traffic.  No LDS, no atomics: neighbouring lanes reproject to
+//                 neighbouring pixels, so the taps are near-coherent gathers served by L1/L2, and
+//                 the 12-byte pixels are read as three dword loads.  The tap loop is branch-free:
+//                 coordinates clamped, an invalid tap's weight and values zeroed by selects (so a
+//                 NaN in the previous frame never meets a multiply).
+//
+// Bytes per pixel: 36 read of the current frame (28 without var and count planes), up to 4 x 36
+// gathered from the previous one (L1/L2-resident: adjacent lanes share three of four taps), 20
+// written.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include <mutex>
+
+#include "rt_hip_util.h"
+
+namespace rt {
+namespace {
+
+constexpr int kTW = 64, kTH = 4;  // tile: one wave per row of 64 pixels
+
+struct V3 {
+  float x, y, z;
+};
+
+// everything wave-uniform: the two cameras relative to their centres (rt_abi.h's D, Ac, Uc, Vc,
+// Ap, Up, Vp) and the resolved options
+struct TpParams {
+  int w, h, tiles_x;
+  V3 d, ac, uc, vc, ap, up, vp;
+  float max_history;  // 0: 8 x the current pixel's count
+  float depth_tol, normal_tol, min_weight;
+  float prev_count, cur_count;  // the frames' count_scalar
+};
+
+struct Planes {  // an rt_frame's buffers
+  float* rgb;
+  float* var;
+  float* count;
+  float* normal;
+  float* depth;
+};
+
+__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ V3 load3(const float* p, size_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
+__device__ __forceinline__ bool finite3(V3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
+
+__global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Planes cur, Planes out) {
+  const int tile_y = blockIdx.x / P.tiles_x, tile_x = blockIdx.x - tile_y * P.tiles_x;
+  const int x = tile_x * kTW + (threadIdx.x & (kTW - 1)), y = tile_y * kTH + (threadIdx.x >> 6);
+  if (x >= P.w || y >= P.h) return;
+  const size_t pi = (size_t)y * P.w + x;
+  // the current pixel, read whole before any write: out may alias cur
+  const V3 c = load3(cur.rgb, pi), np = load3(cur.normal, pi);
+  const float v = cur.var ? cur.var[pi] : 0.0f;
+  const float nc = cur.count ? cur.count[pi] : P.cur_count;
+  const float dp = cur.depth[pi];
+  const bool valid = finite3(c) && isfinite(v) && isfinite(nc) && nc > 0.0f;
+  bool hist = valid && isfinite(dp) && dp > 0.0f && finite3(np);
+
+  // the hit point relative to the previous centre, and its pixel in the previous camera
+  const float fx = (float)x, fy = (float)y;
+  const V3 dir = {P.ac.x + fx * P.uc.x + fy * P.vc.x, P.ac.y + fx * P.uc.y + fy * P.vc.y,
+                  P.ac.z + fx * P.uc.z + fy * P.vc.z};
+  const float t = dp / sqrtf(dot(dir, dir));
+  const V3 r = {P.d.x + t * dir.x, P.d.y + t * dir.y, P.d.z + t * dir.z};
+  const float d1 = sqrtf(dot(r, r));
+  const V3 wp = {P.up.y * P.vp.z - P.up.z * P.vp.y, P.up.z * P.vp.x - P.up.x * P.vp.z,
+                 P.up.x * P.vp.y - P.up.y * P.vp.x};
+  const float s = dot(P.ap, wp) / dot(r, wp);
+  hist = hist && isfinite(s) && s > 0.0f;
+  const V3 q = {s * r.x - P.ap.x, s * r.y - P.ap.y, s * r.z - P.ap.z};
+  float u = dot(q, P.up) / dot(P.up, P.up), vv = dot(q, P.vp) / dot(P.vp, P.vp);
+  // beyond [-1, w) x [-1, h) no tap is inside: clamped there (NaN included) so that the
+  // conversion to int is defined; such a pixel ends with S = 0
+  u = hist ? fminf(fmaxf(u, -2.0f), (float)P.w + 1.0f) : -2.0f;
+  vv = hist ? fminf(fmaxf(vv, -2.0f), (float)P.h + 1.0f) : -2.0f;
+  const float u0 = floorf(u), v0 = floorf(vv);
+  const int x0 = (int)u0, y0 = (int)v0;
+  const float bu[2] = {1.0f - (u - u0), u - u0}, bv[2] = {1.0f - (vv - v0), vv - v0};
+  const float tol_d = P.depth_tol * d1;
+
+  float S = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f, sn = 0.0f;
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const int qx = x0 + a, qy = y0 + b;
+      const int cx = min(max(qx, 0), P.w - 1), cy = min(max(qy, 0), P.h - 1);
+      const size_t qi = (size_t)cy * P.w + cx;
+      const V3 cq = load3(prev.rgb, qi), nq = load3(prev.normal, qi);
+      const float vq = prev.var ? prev.var[qi] : 0.0f;
+      const float cntq = prev.count ? prev.count[qi] : P.prev_count;
+      const float dq = prev.depth[qi];
+      const float nx = np.x - nq.x, ny = np.y - nq.y, nz = np.z - nq.z;
+      const bool ok = hist && cx == qx && cy == qy && finite3(cq) && isfinite(vq) && isfinite(cntq) &&
+                      cntq > 0.0f && dq > 0.0f && fabsf(dq - d1) <= tol_d &&
+                      nx * nx + ny * ny + nz * nz <= P.normal_tol;
+      const float beta = ok ? bu[a] * bv[b] : 0.0f;
+      S += beta;
+      sr += beta * (ok ? cq.x : 0.0f);
+      sg += beta * (ok ? cq.y : 0.0f);
+      sb += beta * (ok ? cq.z : 0.0f);
+      sv += beta * beta * (ok ? vq : 0.0f);
+      sn += beta * (ok ? cntq : 0.0f);
+    }
+  }
+  hist = hist && S >= P.min_weight;
+
+  V3 o = c;
+  float ov = v, on = nc;
+  if (hist) {
+    const float inv = 1.0f / S;
+    const float cap = P.max_history > 0.0f ? P.max_history : 8.0f * nc;
+    const float nh = fminf(sn * inv, cap), vh = sv * (inv * inv);
+    const float n = nh + nc, in = 1.0f / n;
+    o.x = (nh * (sr * inv) + nc * c.x) * in;
+    o.y = (nh * (sg * inv) + nc * c.y) * in;
+    o.z = (nh * (sb * inv) + nc * c.z) * in;
+    ov = (nh * nh * vh + nc * nc * v) * (in * in);
+    on = n;
+  }
+  if (out.rgb) out.rgb[3 * pi] = o.x, out.rgb[3 * pi + 1] = o.y, out.rgb[3 * pi + 2] = o.z;
+  if (out.var) out.var[pi] = ov;
+  if (out.count) out.count[pi] = on;
+}
+
+// ---- host -------------------------------------------------------------------------------------
+
+std::mutex g_mu;        // one host-staged call at a time: the staging buffer is shared
+DeviceScratch g_stage;  // rt_reproject's staged frames (72 B per pixel)
+
+V3 v3(const double* a) { return {(float)a[0], (float)a[1], (float)a[2]}; }
+V3 v3_diff(const double* a, const double* b) {  // the difference in fp64, then rounded
+  return {(float)(a[0] - b[0]), (float)(a[1] - b[1]), (float)(a[2] - b[2])};
+}
+
+Planes planes_of(const rt_frame* f) { return {f->rgb, f->var, f->count, f->normal, f->depth}; }
+
+// argument checks of both entry points (before any device is touched) -> the kernel's parameters
+int resolve(const char* who, const rt_camera* cam_prev, const rt_frame* prev, const rt_camera* cam_cur,
+            const rt_frame* cur, int w, int h, const rt_reproject_opts* opts, const rt_frame* out,
+            TpParams* P) {
+  if (!cam_prev || !cam_cur) return set_error(RT_ERR_INVALID, "%s: null camera", who);
+  if (!prev || !cur || !out) return set_error(RT_ERR_INVALID, "%s: null frame", who);
+  if (!prev->rgb || !prev->normal || !prev->depth || !cur->rgb || !cur->normal || !cur->depth)
+    return set_error(RT_ERR_INVALID, "%s: prev and cur need rgb, normal and depth", who);
+  if (!out->rgb && !out->var && !out->count) return set_error(RT_ERR_INVALID, "%s: out has no buffer", who);
+  if (w <= 0 || h <= 0 || (int64_t)w * h >= ((int64_t)1 << 31) / 3)
+    return set_error(RT_ERR_INVALID, "%s: %d x %d image", who, w, h);
+  const rt_reproject_opts o = opts ? *opts : rt_reproject_opts{};
+  for (float f : {o.max_history, o.depth_tol, o.normal_tol, o.min_weight})
+    if (!(f >= 0.0f) || !isfinite(f)) return set_error(RT_ERR_INVALID, "%s: negative or non-finite option", who);
+  const float* const prev_bufs[5] = {prev->rgb, prev->var, prev->count, prev->normal, prev->depth};
+  for (const float* ob : {out->rgb, out->var, out->count})
+    for (const float* pb : prev_bufs)
+      if (ob && ob == pb)
+        return set_error(RT_ERR_INVALID, "%s: out aliases a buffer of prev (the taps gather from prev)", who);
+  rt_camera_derived dp, dc;
+  int rc = rt_camera_derive(cam_prev, &dp);
+  if (rc == RT_OK) rc = rt_camera_derive(cam_cur, &dc);
+  if (rc != RT_OK) return rc;
+  if (dp.width != w || dp.height != h || dc.width != w || dc.height != h)
+    return set_error(RT_ERR_INVALID, "%s: cameras of %d x %d and %d x %d for a %d x %d image", who, dp.width,
+                     dp.height, dc.width, dc.height, w, h);
+  if (dp.defocus_angle > 0.0 || dc.defocus_angle > 0.0)
+    return set_error(RT_ERR_UNSUPPORTED, "%s: a defocus camera measures depth from the lens sample", who);
+  P->w = w;
+  P->h = h;
+  P->tiles_x = (w + kTW - 1) / kTW;
+  P->d = v3_diff(dc.center, dp.center);
+  P->ac = v3_diff(dc.pixel00, dc.center);
+  P->uc = v3(dc.delta_u);
+  P->vc = v3(dc.delta_v);
+  P->ap = v3_diff(dp.pixel00, dp.center);
+  P->up = v3(dp.delta_u);
+  P->vp = v3(dp.delta_v);
+  P->max_history = o.max_history;
+  P->depth_tol = o.depth_tol > 0.0f ? o.depth_tol : 0.05f;
+  P->normal_tol = o.normal_tol > 0.0f ? o.normal_tol : 0.1f;
+  P->min_weight = o.min_weight > 0.0f ? o.min_weight : 0.01f;
+  P->prev_count = prev->count_scalar;
+  P->cur_count = cur->count_scalar;
+  return RT_OK;
+}
+
+int launch(const TpParams& P, const Planes& prev, const Planes& cur, const Planes& out, hipStream_t s) {
+  const int64_t tiles = (int64_t)P.tiles_x * ((P.h + kTH - 1) / kTH);  // < 2^31 / 3: w h is
+  hipLaunchKernelGGL(k_reproject, dim3((unsigned)tiles), dim3(256), 0, s, P, prev, cur, out);
+  HIP_OK(hipGetLastError());
+  return RT_OK;
+}
+
+}  // namespace
+}  // namespace rt
+
+using namespace rt;
+
+extern "C" {
+
+int rt_reproject_device(const rt_camera* cam_prev, const rt_frame* prev_dev, const rt_camera* cam_cur,
+                        const rt_frame* cur_dev, int w, int h, const rt_reproject_opts* opts,
+                        const rt_frame* out_dev, int device, void* stream) {
+  const char* who = "rt_reproject_device";
+  TpParams P;
+  int rc = resolve(who, cam_prev, prev_dev, cam_cur, cur_dev, w, h, opts, out_dev, &P);
+  if (rc) return rc;
+  if ((rc = device_ok(who, device))) return rc;
+  DeviceGuard dg;
+  HIP_OK(hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  rc = launch(P, planes_of(prev_dev), planes_of(cur_dev), planes_of(out_dev), s);
+  HIP_OK(hipStreamSynchronize(s));
+  return rc;
+}
+
+int rt_reproject(const rt_camera* cam_prev, const rt_frame* prev, const rt_camera* cam_cur,
+                 const rt_frame* cur, int w, int h, const rt_reproject_opts* opts, const rt_frame* out) {
+  const char* who = "rt_reproject";
+  TpParams P;
+  int rc = resolve(who, cam_prev, prev, cam_cur, cur, w, h, opts, out, &P);
+  if (rc) return rc;
+  if ((rc = device_ok(who, 0))) return rc;
+  DeviceGuard dg;
+  HIP_OK(hipSetDevice(0));
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = nullptr;
+  // both frames as 9 planes-floats per pixel each: rgb, var, count, normal, depth.  out is written
+  // over cur's copy (out may alias cur), into the var and count slots also when cur has neither
+  const size_t n = (size_t)w * h;
+  constexpr int kOff[6] = {0, 3, 4, 5, 8, 9};
+  void* stg = nullptr;
+  if ((rc = g_stage.get(0, n * 4 * 18, &stg, who))) return rc;
+  Planes d[2];
+  const rt_frame* src[2] = {prev, cur};
+  for (int f = 0; f < 2; ++f) {
+    float* base = (float*)stg + (size_t)f * 9 * n;
+    const float* host[5] = {src[f]->rgb, src[f]->var, src[f]->count, src[f]->normal, src[f]->depth};
+    float* dev[5];
+    for (int k = 0; k < 5; ++k) {
+      dev[k] = host[k] ? base + kOff[k] * n : nullptr;
+      if (host[k])
+        HIP_OK(hipMemcpyAsync(dev[k], host[k], n * 4 * (kOff[k + 1] - kOff[k]), hipMemcpyHostToDevice, s));
+    }
+    d[f] = {dev[0], dev[1], dev[2], dev[3], dev[4]};
+  }
+  float* cbase = (float*)stg + 9 * n;
+  const Planes o = {out->rgb ? cbase : nullptr, out->var ? cbase + kOff[1] * n : nullptr,
+                    out->count ? cbase + kOff[2] * n : nullptr, nullptr, nullptr};
+  rc = launch(P, d[0], d[1], o, s);
+  if (!rc && ((o.rgb && hipMemcpyAsync(out->rgb, o.rgb, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+              (o.var && hipMemcpyAsync(out->var, o.var, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+              (o.count && hipMemcpyAsync(out->count, o.count, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)))
+    rc = set_error(RT_ERR_DEVICE, "%s: copy to host failed", who);
+  HIP_OK(hipStreamSynchronize(s));  // also after an error: nothing in flight on the staging buffer
+  return rc;
+}
+
+}  // extern "C"

@@ -37,7 +37,16 @@
 // samples_full), -accum-features (with -passes / -until / -adaptive: the accumulator keeps the
 // feature sums of its passes' own camera samples, rt_accum_set_features, and the denoisers and
 // -aov take those guides instead of a separate feature pass; without an accumulating flag a
-// usage error; the statistics line gains "accum_features": 1), -counts FILE (with -adaptive: the passes per pixel as grey, count / max).  -cpuprofile has no pprof to drive on the GPU path: the file
+// usage error; the statistics line gains "accum_features": 1), -frames N -orbit DEG (N frames, frame k
+// with the camera's look_from turned about the vup axis through look_at by k * DEG degrees and written
+// to the -o name with _%03d before the extension, -aov's prefix with the same suffix; one statistics
+// line per frame, with "frame": k; without -temporal the frames are independent), -temporal (with
+// -accum-features and an accumulating flag, else a usage error: each frame's accumulator mean, variance
+// and guides go through rt_reproject against the history of the frames before it, every pixel of a frame
+// weighing its passes, before -denoise-var and the writer, and the result is the next frame's history;
+// the host entry, which stages through the device and gives rt_reproject_device's bits: this client
+// links no HIP runtime to own device buffers with; the statistics line gains "temporal": 1 and
+// ms_reproject), -counts FILE (with -adaptive: the passes per pixel as grey, count / max).  -cpuprofile has no pprof to drive on the GPU path: the file
 // receives the same JSON statistics instead.
 #include <unistd.h>
 
@@ -45,6 +54,7 @@
 #include <cerrno>
 #include <chrono>
 #include <cinttypes>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -72,7 +82,9 @@ struct Args {
   bool adaptive_set = false;
   unsigned long long seed = 1, tree_seed = 1;
   bool progress = false, stats = false, denoise = false, denoise_var = false, split_emitters = false;
-  bool accum_features = false;
+  bool accum_features = false, temporal = false;
+  long long frames = 0;
+  double orbit = 0.0;
 };
 
 std::vector<Flag> flags(Args& a) {
@@ -98,8 +110,12 @@ std::vector<Flag> flags(Args& a) {
        Flag::BOOL, &a.denoise_var, ""},
       {"depth", "override Camera.MaxDepth (0 = the scene's)", Flag::INT, &a.depth, "0"},
       {"device", "HIP device ordinal", Flag::INT, &a.device, "0"},
+      {"frames", "render N frames, frame k to the -o name with _00k before the extension (see -orbit)", Flag::INT,
+       &a.frames, "0"},
       {"mode", "kernel strategy: auto, fused or wavefront", Flag::STR, &a.mode, "auto"},
       {"o", "Specify a custom output file", Flag::STR, &a.out, "image.ppm"},
+      {"orbit", "with -frames: turn the camera's look_from about the vup axis through look_at by DEG degrees per frame",
+       Flag::F64, &a.orbit, "0"},
       {"passes", "render N passes of -spp samples each (seeds seed .. seed+N-1) and write their exact mean",
        Flag::INT, &a.passes, "0"},
       {"progress", "print render progress on stderr", Flag::BOOL, &a.progress, ""},
@@ -110,6 +126,8 @@ std::vector<Flag> flags(Args& a) {
        Flag::BOOL, &a.split_emitters, ""},
       {"spp", "override Camera.SamplesPerPixel (0 = the scene's)", Flag::INT, &a.spp, "0"},
       {"stats", "print render statistics (JSON) on stderr", Flag::BOOL, &a.stats, ""},
+      {"temporal", "with -accum-features and -passes / -until / -adaptive: blend each frame with the reprojected history of the frames before it (rt_reproject)",
+       Flag::BOOL, &a.temporal, ""},
       {"tree-seed", "seed of the scene builder's rand (main.go's math/rand)", Flag::U64,
        &a.tree_seed, "1"},
       {"until", "add passes until the image's relative standard error is <= E (at most -passes, default 1024)",
@@ -245,10 +263,13 @@ std::string stats_json(const rt_stats& st, const rt_camera_derived& d, const cha
                        double wall_s, int aov_samples, double ms_aov, double ms_denoise,
                        const rt_accum_info* acc, double ms_accum, bool denoise_var,
                        const rt_adapt_info* ad = nullptr, bool split_emitters = false,
-                       bool accum_features = false) {
-  char b[1280], extra[200] = "", extra2[200] = "";
+                       bool accum_features = false, int frame = -1, bool temporal = false,
+                       double ms_reproject = 0.0) {
+  char b[1280], extra[200] = "", extra2[200] = "", extra4[120] = "";
+  if (frame >= 0) snprintf(extra4, sizeof extra4, "\"frame\": %d, ", frame);
+  if (temporal) snprintf(extra4 + strlen(extra4), sizeof extra4 - strlen(extra4), "\"temporal\": 1, \"ms_reproject\": %.3f, ", ms_reproject);
   const std::string extra3s = std::string(split_emitters ? "\"split_emitters\": 1, " : "") +
-                              (accum_features ? "\"accum_features\": 1, " : "");
+                              (accum_features ? "\"accum_features\": 1, " : "") + extra4;
   const char* extra3 = extra3s.c_str();
   if (acc)  // -passes / -until
     snprintf(extra, sizeof extra, "\"passes\": %d, \"rel_error\": %.6g, \"ms_accum\": %.3f, %s", acc->passes,
@@ -303,9 +324,29 @@ int main(int argc, char** argv) {
     usage(argv[0], flags(a));
     return 2;
   }
+  if (a.temporal && !(a.accum_features && (a.passes > 0 || a.until > 0.0 || a.adaptive_set))) {  // no guides, no history
+    fprintf(stderr, "-temporal needs -accum-features and -passes, -until or -adaptive\n");
+    usage(argv[0], flags(a));
+    return 2;
+  }
+  if (a.frames < 0 || a.frames > 999 || !(a.orbit == a.orbit)) {
+    fprintf(stderr, "invalid value for flag -frames (0..999) / -orbit\n");
+    usage(argv[0], flags(a));
+    return 2;
+  }
+  const bool numbered = a.frames > 0;  // -frames: frame k goes to the -o name with _00k before the extension
+  const int n_frames = numbered ? (int)a.frames : 1;
+  auto frame_name = [&](const std::string& name, int k, bool before_ext) {
+    char tag[8];
+    snprintf(tag, sizeof tag, "_%03d", k);
+    const size_t slash = name.rfind('/'), dot = name.rfind('.');
+    const bool ext = before_ext && dot != std::string::npos && (slash == std::string::npos || dot > slash);
+    return ext ? name.substr(0, dot) + tag + name.substr(dot) : name + tag;
+  };
 
   // main.go:434-439: the output file exists before anything renders
-  FILE* out = fopen(a.out.c_str(), "wb");
+  const std::string out_first = numbered ? frame_name(a.out, 0, true) : a.out;
+  FILE* out = fopen(out_first.c_str(), "wb");
   if (!out) {
     fprintf(stderr, "Error creating output file\n");
     return 1;
@@ -343,6 +384,42 @@ int main(int argc, char** argv) {
   if ((rc = rt_scene_create(tree, world, lights, &sc)) != RT_OK)
     return fail("rt_scene_create", rc);
 
+  // -temporal: the history (the frames before this one, reprojected and blended) and its camera
+  const size_t n_px = (size_t)d.width * d.height;
+  std::vector<float> h_rgb, h_var, h_count, h_normal, h_depth, count;
+  rt_camera h_cam;
+  bool have_history = false;
+  const rt_camera cam0 = cam;
+  const std::string aov0 = a.aov;
+
+  for (int frame = 0; frame < n_frames; ++frame) {
+  double ms_reproject = 0.0;
+  std::string out_name = a.out;
+  if (numbered) {
+    out_name = frame_name(a.out, frame, true);
+    if (!aov0.empty()) a.aov = frame_name(aov0, frame, false);
+    if (frame > 0 && !(out = fopen(out_name.c_str(), "wb"))) {
+      fprintf(stderr, "Error creating output file\n");
+      return 1;
+    }
+    // -orbit: look_from turned about the vup axis through look_at (Rodrigues' formula)
+    double from[3] = {0, 0, 0}, at[3] = {0, 0, -1}, up[3] = {0, 1, 0};
+    if (cam0.positioned)
+      for (int i = 0; i < 3; ++i) from[i] = cam0.look_from[i], at[i] = cam0.look_at[i], up[i] = cam0.vup[i];
+    const double th = a.orbit * (double)frame * M_PI / 180.0, co = cos(th), si = sin(th);
+    const double ul = sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
+    const double k[3] = {up[0] / ul, up[1] / ul, up[2] / ul};
+    const double v[3] = {from[0] - at[0], from[1] - at[1], from[2] - at[2]};
+    const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2];
+    const double kxv[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
+    for (int i = 0; i < 3; ++i) {
+      cam.look_from[i] = at[i] + (v[i] * co + kxv[i] * si + k[i] * kv * (1.0 - co));
+      cam.look_at[i] = at[i];
+      cam.vup[i] = up[i];
+    }
+    cam.positioned = 1;
+  }
+
   rt_render_opts o;
   memset(&o, 0, sizeof o);
   o.seed = a.seed;
@@ -351,7 +428,7 @@ int main(int argc, char** argv) {
   o.mode = mode;
   o.trace_pixel = -1;
   o.progress_slices = (int32_t)(a.slices > 0 ? a.slices : a.progress ? 20 : 0);
-  std::vector<float> rgb((size_t)d.width * d.height * 3), var(a.denoise_var ? (size_t)d.width * d.height : 0);
+  std::vector<float> rgb((size_t)d.width * d.height * 3), var(a.denoise_var || a.temporal ? (size_t)d.width * d.height : 0);
   rt_stats st;
   memset(&st, 0, sizeof st);
 
@@ -428,7 +505,7 @@ int main(int argc, char** argv) {
     }
     if (rc == RT_OK) {
       what = "rt_accum_resolve";
-      if ((rc = rt_accum_resolve(acc, rgb.data(), a.denoise_var ? var.data() : nullptr)) == RT_OK) rc = rt_accum_info_get(acc, &ai);
+      if ((rc = rt_accum_resolve(acc, rgb.data(), a.denoise_var || a.temporal ? var.data() : nullptr)) == RT_OK) rc = rt_accum_info_get(acc, &ai);
     }
     if (rc == RT_OK && a.adaptive_set) {
       what = "rt_accum_adapt_info";
@@ -463,7 +540,7 @@ int main(int argc, char** argv) {
   // -denoise / -aov: the feature buffers of the same camera rays, then the filter
   int aov_samples = 0;
   double ms_aov = 0.0, ms_denoise = 0.0;
-  if (a.denoise || a.denoise_var || !a.aov.empty()) {
+  if (a.denoise || a.denoise_var || !a.aov.empty() || a.temporal) {
     const size_t np = (size_t)d.width * d.height;
     std::vector<float> albedo(3 * np), normal(3 * np), depth(np);
     rt_aov f = {albedo.data(), normal.data(), depth.data(), nullptr};
@@ -485,6 +562,21 @@ int main(int argc, char** argv) {
       return fail("rt_render_aov", rc);
     }
     ms_aov = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
+    if (a.temporal) {  // the history into this frame's camera, then this frame as the new history
+      auto tr = std::chrono::steady_clock::now();
+      count.assign(n_px, (float)ai.passes);
+      if (have_history) {
+        const rt_frame prev = {h_rgb.data(), h_var.data(), h_count.data(), h_normal.data(), h_depth.data(), 0.0f, 0};
+        const rt_frame cur = {rgb.data(), var.data(), nullptr, normal.data(), depth.data(), (float)ai.passes, 0};
+        const rt_frame res = {rgb.data(), var.data(), count.data(), nullptr, nullptr, 0.0f, 0};
+        if ((rc = rt_reproject(&h_cam, &prev, &cam, &cur, d.width, d.height, nullptr, &res)) != RT_OK)
+          return fail("rt_reproject", rc);
+      }
+      h_rgb = rgb, h_var = var, h_count = count, h_normal = normal, h_depth = depth;
+      h_cam = cam;
+      have_history = true;
+      ms_reproject = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
+    }
     if (a.denoise_var) {
       rt_denoise_var_opts vopt;
       memset(&vopt, 0, sizeof vopt);  // the library defaults
@@ -538,12 +630,12 @@ int main(int argc, char** argv) {
   }
 
   // camera.go:160 header + PrintColor per pixel, then main.go:477's single write
-  if (write_ppm(rgb, d.width, d.height, out, a.out.c_str())) return 1;
+  if (write_ppm(rgb, d.width, d.height, out, out_name.c_str())) return 1;
   double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::string js = stats_json(st, d, scene, wall, aov_samples, ms_aov, ms_denoise, accumulate ? &ai : nullptr,
                               ms_accum, a.denoise_var, a.adaptive_set ? &adi : nullptr, a.split_emitters,
-                              a.accum_features);
-  if (a.stats || a.denoise || a.denoise_var) fprintf(stderr, "%s\n", js.c_str());
+                              a.accum_features, numbered ? frame : -1, a.temporal, ms_reproject);
+  if (a.stats || a.denoise || a.denoise_var || a.temporal) fprintf(stderr, "%s\n", js.c_str());
   if (!a.cpuprofile.empty()) {
     FILE* p = fopen(a.cpuprofile.c_str(), "w");
     if (!p) {
@@ -553,6 +645,8 @@ int main(int argc, char** argv) {
     fprintf(p, "%s\n", js.c_str());
     fclose(p);
   }
+  if (acc && (rc = rt_accum_destroy(acc)) != RT_OK) return fail("rt_accum_destroy", rc);
+  }  // frames
   rt_scene_destroy(sc);
   rt_tree_destroy(tree);
   return 0;

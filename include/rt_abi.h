@@ -816,6 +816,80 @@ int rt_accum_get_features(rt_accum* a, uint32_t* planes);
 int rt_accum_resolve_aov(rt_accum* a, const rt_aov* out_host, const rt_aov_emit* emit_host);
 int rt_accum_resolve_aov_device(rt_accum* a, const rt_aov* out_dev, const rt_aov_emit* emit_dev);
 
+/* ------------------------------------------------------------------------ */
+/* Temporal reprojection (DESIGN.md "Temporal reprojection"): the previous   */
+/* frame's colour, variance and history length carried into a new camera     */
+/* through the depth and normal buffers, the stage Schied et al.,            */
+/* "Spatiotemporal Variance-Guided Filtering", HPG 2017, put in front of the */
+/* spatial filter.  A pure image operation: no scene (which is static: there */
+/* are no motion vectors).  Added without an ABI version change: detect by   */
+/* the symbols.                                                              */
+/* ------------------------------------------------------------------------ */
+typedef struct {            /* one frame on one device (or host), whole image, row-major */
+  float* rgb;               /* [h][w][3] linear mean colour */
+  float* var;               /* [h][w]    variance of the mean luminance (rt_accum_resolve's); NULL = 0 */
+  float* count;             /* [h][w]    history weight n of the pixel; NULL = count_scalar everywhere */
+  float* normal;            /* [h][w][3] rt_aov's normal */
+  float* depth;             /* [h][w]    rt_aov's depth */
+  float  count_scalar;      /* used when count is NULL (e.g. the accumulator's passes) */
+  int32_t _pad;
+} rt_frame;
+
+typedef struct {
+  float max_history;        /* 0 -> 8 x the current pixel's count; cap on the reprojected weight */
+  float depth_tol;          /* 0 -> 0.05 (relative) */
+  float normal_tol;         /* 0 -> 0.1  (|n_p - n_q|^2) */
+  float min_weight;         /* 0 -> 0.01 (sum of the valid bilinear weights) */
+} rt_reproject_opts;
+
+/* out = the frame `cur` (seen by cam_cur) blended with the history `prev` (seen by cam_prev)
+ * found behind each of its pixels.  out uses rgb, var and count; each may be NULL = not wanted,
+ * but at least one is required; its normal and depth are not written (the current frame's are
+ * the new history's).  opts NULL: the defaults.
+ *
+ * Per pixel p = (x, y) of the current frame.  The host derives both cameras in fp64
+ * (rt_camera_derive) and hands the kernel fp32 vectors relative to a camera's centre, every
+ * difference of positions taken in fp64 before the rounding: with C, P00, U, V a camera's
+ * center, pixel00, delta_u, delta_v (suffix c: cam_cur, p: cam_prev) these are D = Cc - Cp,
+ * Ac = P00c - Cc, Uc, Vc, Ap = P00p - Cp, Up, Vp.  The kernel works in fp32.
+ *   current pixel valid: the three colour channels and var are finite, and n_c = count is
+ *     finite and > 0.  If not, out takes the current pixel's rgb, var and count bit for bit.
+ *   history lookup: there is NO HISTORY when depth_cur(p) is not finite or <= 0 (a miss), or
+ *     when normal_cur(p) is not finite.  Otherwise
+ *       dir = Ac + x Uc + y Vc,   r = D + depth_cur(p) dir / |dir|   (the hit point relative to
+ *       the previous centre),   d' = |r|,
+ *       Wp = Up x Vp,  num = Ap . Wp,  den = r . Wp,  s = num / den;
+ *     no history unless s is finite and > 0 (the point lies in front of the previous camera);
+ *       q = s r - Ap,   u = q . Up / Up . Up,   v = q . Vp / Vp . Vp
+ *     (integer (u, v) are pixel centres), x0 = floor(u), y0 = floor(v), and the four taps
+ *     (x0 + a, y0 + b), a, b in {0, 1}, have the bilinear weights
+ *     beta = (a ? u - x0 : 1 - (u - x0)) (b ? v - y0 : 1 - (v - y0)).
+ *   tap valid: it is inside the image; the previous rgb and var are finite; n_q is finite and
+ *     > 0; depth_q > 0; |depth_q - d'| <= depth_tol d'; |n_p - n_q|^2 <= normal_tol.
+ *     S = sum of beta over the valid taps.  If S < min_weight there is no history.
+ *   reprojected history: c_h = sum beta c_q / S,  v_h = sum beta^2 v_q / S^2 (the taps as
+ *     independent estimators, the rule rt_denoise_var applies to its taps),
+ *     n_h = min(sum beta n_q / S, max_history).
+ *   blend: out.rgb = (n_h c_h + n_c c) / (n_h + n_c),
+ *     out.var = (n_h^2 v_h + n_c^2 v) / (n_h + n_c)^2,  out.count = n_h + n_c.
+ *     With no history n_h = 0 and out is the current pixel's bits.
+ * Argument checks, before any device is touched.  RT_ERR_INVALID: a NULL camera, frame or out;
+ * a missing rgb, normal or depth in prev or cur; out without any buffer; w or h <= 0 (or
+ * w h >= 2^31 / 3), or a camera whose derived width / height is not w x h; negative or
+ * non-finite options; any out buffer that is also a prev buffer (the taps gather from prev, so
+ * prev cannot be written; out may alias cur).  RT_ERR_UNSUPPORTED: either camera has
+ * defocus_angle > 0 (depth is then measured from the lens sample, not from the centre).
+ * rt_reproject: host pointers, staged through the device (device 0); rt_reproject_device: device
+ * pointers on `device`, enqueued on `stream` (hipStream_t or NULL), returns after the work
+ * completes.  Two calls give identical bits. */
+int rt_reproject(const rt_camera* cam_prev, const rt_frame* prev, const rt_camera* cam_cur,
+                 const rt_frame* cur, int w, int h, const rt_reproject_opts* opts,
+                 const rt_frame* out);
+int rt_reproject_device(const rt_camera* cam_prev, const rt_frame* prev_dev,
+                        const rt_camera* cam_cur, const rt_frame* cur_dev, int w, int h,
+                        const rt_reproject_opts* opts, const rt_frame* out_dev, int device,
+                        void* stream);
+
 /* Demo scenes mirroring main.go (by name or the main.go -S number).
  * names: book1, book2, book3, simple_light, quads, cornell, cornell_smoke, model
  * The camera receives the scene's settings; override fields afterwards. */

@@ -1,0 +1,158 @@
+"""Temporal reprojection's measurements on Cornell.
+
+time: Cornell 800 x 800, two cameras 1 degree apart on the orbit, 2 passes x 4 spp each, resolved
+on the device; rt_reproject_device (in place, all three outputs) against the guided filter
+rt_denoise_var_device (5 iterations, all guides) on the same frame and against a device-to-device
+copy of the bytes the reprojection moves (about 100 per pixel, read and written: 50 copied),
+alternated call by call: HIP events around each blocking call, 5 warm-up rounds, then the median
+(min, max) of 25.
+
+quality: Cornell 128 x 128, an 8-frame orbit of 1 degree per frame, 2 passes x 4 spp per frame
+(features="emit"), against a 1024-spp render of the last camera: mean squared error of the last
+frame's own mean, of the temporal result, of the guided filter on the frame's mean, and of the
+guided filter on the temporal result, over every pixel, over the rim pixels of directly seen
+lights (0 < coverage < 1), over the pixels that found history, and split into the pixels within
+2 of a directly seen light (the bilinear taps mix the emitter into its coplanar surroundings:
+depth and normal cannot tell them apart) and the pixels elsewhere.
+
+Prints one JSON object; -o FILE also writes it.
+"""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch  # before the library's HIP runtime initialises
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import go_raytracer_amd as rt  # noqa: E402
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def stat(v):
+    return [float(np.median(v)), float(min(v)), float(max(v))]
+
+
+def orbit(cam, degrees):
+    """look_from turned about the vup axis through look_at (rtbench's -orbit)"""
+    frm, at, up = (np.array(x, np.float64) for x in cam._pos)
+    k = up / np.linalg.norm(up)
+    v, th = frm - at, math.radians(degrees)
+    out = type(cam).from_c(cam.to_c())
+    out.PositionCamera(at + v * math.cos(th) + np.cross(k, v) * math.sin(th) + k * (k @ v) * (1 - math.cos(th)), at, up)
+    return out
+
+
+def frame_tensors(sc, cam, seeds, dev):
+    h = w = cam.Width
+    f = {k: torch.empty((h, w, 3) if k in ("rgb", "normal") else (h, w), dtype=torch.float32, device=dev)
+         for k in ("rgb", "var", "normal", "depth")}
+    with sc.accumulator(cam, max_passes=len(seeds), features="guides") as acc:
+        for s in seeds:
+            acc.add(s)
+        acc.resolve_device(f["rgb"], f["var"])
+        aov = {k: v.clone() for k, v in acc.resolve_aov_device().items()}
+    f["normal"], f["depth"] = aov["normal"], aov["depth"]
+    return f, aov
+
+
+def bench_time(width, rounds, warm):
+    dev = torch.device("cuda", 0)
+    t, cam, w, l = rt.demo_scene("cornell")
+    cam.Width, cam.SamplesPerPixel = width, 4
+    cams = (cam, orbit(cam, 1.0))
+    with rt.Scene(t, w, l) as sc:
+        (prev, _), (cur, aov) = (frame_tensors(sc, c, s, dev) for c, s in zip(cams, ((1, 2), (3, 4))))
+    prev["count"] = torch.full((width, width), 2.0, device=dev)
+    out = {k: torch.empty_like(cur[k]) for k in ("rgb", "var")}
+    out["count"] = torch.empty((width, width), device=dev)
+    n = width * width
+    src = torch.empty(n * 50 // 4, dtype=torch.float32, device=dev).normal_()
+    dst = torch.empty_like(src)
+    den, vout = torch.empty_like(cur["rgb"]), torch.empty_like(cur["var"])
+    calls = {
+        "reproject": lambda: rt.reproject_device(cams[0], prev, cams[1], dict(cur, count=2.0), out=out),
+        "denoise_var": lambda: rt.denoise_var_device(cur["rgb"], cur["var"], aov, out=den, var_out=vout),
+        "copy_50_bytes_per_pixel": lambda: (dst.copy_(src), torch.cuda.synchronize()),
+    }
+    ms = {k: [] for k in calls}
+    for r in range(warm + rounds):
+        for k, fn in calls.items():
+            v = timed(fn)
+            if r >= warm:
+                ms[k].append(v)
+    found = float((out["count"] > 2.0).float().mean().item())
+    return {"image": f"cornell {width}x{width}", "rounds": rounds, "warmup_rounds": warm,
+            "ms_median_min_max": {k: stat(v) for k, v in ms.items()},
+            "bytes_per_pixel_nominal": 100, "history_found_share": found,
+            "note": "HIP events around each blocking call (launch, kernel and the stream synchronise)"}
+
+
+def bench_quality(width, frames, degrees, ref_spp):
+    t, cam, w, l = rt.demo_scene("cornell")
+    cam.Width, cam.SamplesPerPixel = width, 4
+    temporal = rt.Temporal()
+    with rt.Scene(t, w, l) as sc:
+        for k in range(frames):
+            camk = orbit(cam, degrees * k)
+            with sc.accumulator(camk, max_passes=2, features="emit") as acc:
+                acc.add(10 * k + 1)
+                acc.add(10 * k + 2)
+                rgb, var, count = temporal.push(acc)
+                if k == frames - 1:
+                    mean, _ = acc.resolve()
+                    aov = acc.resolve_aov_device()
+                    cover = aov["coverage"].cpu().numpy()
+                    both = rt.denoise_var_device(rgb, var, aov, split_emitters=True).cpu().numpy()
+                    only = acc.denoise_device().cpu().numpy()
+                    temp, cnt = rgb.cpu().numpy(), count.cpu().numpy()
+        camk.SamplesPerPixel = ref_spp
+        ref, _ = sc.render(camk, seed=977)
+    fin = np.isfinite(mean).all(-1) & np.isfinite(ref).all(-1)
+    near = cover > 0  # the directly seen lights and the pixels within 2 of them
+    for _ in range(2):
+        pad = np.pad(near, 1)
+        near = np.logical_or.reduce([pad[dy:dy + width, dx:dx + width] for dy in range(3) for dx in range(3)])
+    sets = {"all": fin, "rim": fin & (cover > 0) & (cover < 1), "with_history": fin & (cnt > 2.0),
+            "within_2_of_a_light": fin & near, "elsewhere": fin & ~near}
+    cols = {"per_frame_mean": mean, "temporal": temp, "guided_filter": only, "temporal_guided_filter": both}
+    return {"image": f"cornell {width}x{width}", "frames": frames, "degrees_per_frame": degrees,
+            "passes_per_frame": 2, "spp_per_pass": 4, "reference_spp": ref_spp,
+            "pixels": {k: int(m.sum()) for k, m in sets.items()},
+            "history_found_share": float((cnt > 2.0).mean()), "mean_count": float(cnt.mean()),
+            "mse": {s: {c: float(((x[m].astype(np.float64) - ref[m]) ** 2).mean()) if m.any() else None
+                        for c, x in cols.items()} for s, m in sets.items()}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("-o", default=None)
+    ap.add_argument("--width", type=int, default=800)
+    ap.add_argument("--rounds", type=int, default=25)
+    ap.add_argument("--quality-width", type=int, default=128)
+    ap.add_argument("--frames", type=int, default=8)
+    ap.add_argument("--ref-spp", type=int, default=1024)
+    a = ap.parse_args()
+    if rt.device_count() <= 0:
+        raise SystemExit("temporal_bench: no HIP device visible")
+    res = {"device": torch.cuda.get_device_name(0), "time": bench_time(a.width, a.rounds, 5),
+           "quality": bench_quality(a.quality_width, a.frames, 1.0, a.ref_spp)}
+    text = json.dumps(res, indent=1)
+    print(text)
+    if a.o:
+        with open(a.o, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
