@@ -23,7 +23,8 @@ __all__ = ["Tree", "Camera", "Scene", "Accumulator", "quantize", "format_ppm", "
            "tune", "untune", "tuning", "tune_knobs", "tune_from_env",
            "demo_scene", "DEMO_SCENES", "build_bvh_boxes", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
            "format_ppm_device", "denoise", "denoise_device", "denoise_var", "denoise_var_device",
-           "RtDenoiseVarOpts", "reproject", "reproject_device", "Temporal"]
+           "RtDenoiseVarOpts", "reproject", "reproject_device", "reproject_emit", "reproject_emit_device",
+           "Temporal"]
 
 DEMO_SCENES = ("book1", "book2", "book3", "simple_light", "quads", "cornell", "cornell_smoke",
                "model")
@@ -1177,15 +1178,21 @@ def _frame(who, name, f, h, w, conv, ptr):
     return _lib.RtFrame(*ptrs, scalar, 0), keep
 
 
-def reproject(cam_prev, prev, cam_cur, cur, **opts):
-    """Temporal reprojection (rt_reproject) on host arrays: the frame `cur` seen by `cam_cur`
-    blended with the history `prev` seen by `cam_prev` that lies behind each of its pixels.  A
-    frame is a dict of float32 arrays "rgb" [H, W, 3], "normal" [H, W, 3] and "depth" [H, W] (as
-    Accumulator.resolve / resolve_aov give them) with an optional "var" [H, W] (missing: 0) and
-    "count" ([H, W], or one number for every pixel; missing: 0, which marks every pixel
-    invalid).  opts: max_history, depth_tol, normal_tol, min_weight (0 = the library defaults).
-    Returns new arrays (rgb, var, count)."""
-    who = "reproject"
+def _frame_emit(who, name, f, h, w, conv, ptr):
+    """The RtAovEmit of a frame dict for the _emit entries: "emission" [H, W, 3] and "coverage"
+    [H, W] are required (surface_albedo is not read: NULL) -> (RtAovEmit, the buffers)"""
+    keep = []
+    for k, ch in (("emission", 3), ("coverage", 0)):
+        if f.get(k) is None:
+            raise ValueError(f"{who}: {name}[{k!r}] is required (an accumulator with features='emit', "
+                             "resolve_aov / resolve_aov_device)")
+        keep.append(conv(f"{name}[{k!r}]", f[k], (h, w, ch) if ch else (h, w)))
+    return RtAovEmit(ptr(keep[0]), None, ptr(keep[1])), keep
+
+
+def _reproject_host(emit, cam_prev, prev, cam_cur, cur, opts):
+    """reproject and reproject_emit (emit): rt_reproject[_emit] on host arrays"""
+    who = "reproject_emit" if emit else "reproject"
     if not isinstance(cur, dict) or cur.get("rgb") is None:
         raise ValueError(f"{who}: cur['rgb'] is required")
     h, w = np.shape(cur["rgb"])[:2]
@@ -1195,25 +1202,33 @@ def reproject(cam_prev, prev, cam_cur, cur, **opts):
         if a.shape != shape:
             raise ValueError(f"{who}: {name} must have shape {shape}, not {a.shape}")
         return a
-    fp, keep_p = _frame(who, "prev", prev, h, w, conv, lambda a: a.ctypes.data)
-    fc, keep_c = _frame(who, "cur", cur, h, w, conv, lambda a: a.ctypes.data)
+
+    def ptr(a):
+        return a.ctypes.data
+    fp, keep_p = _frame(who, "prev", prev, h, w, conv, ptr)
+    fc, keep_c = _frame(who, "cur", cur, h, w, conv, ptr)
+    if emit:
+        ep, keep_ep = _frame_emit(who, "prev", prev, h, w, conv, ptr)
+        ec, keep_ec = _frame_emit(who, "cur", cur, h, w, conv, ptr)
     rgb, var, cnt = (np.empty((h, w, 3), np.float32), np.empty((h, w), np.float32),
                      np.empty((h, w), np.float32))
     fo = _lib.RtFrame(rgb.ctypes.data, var.ctypes.data, cnt.ctypes.data, None, None, 0.0, 0)
     o = _reproject_opts(**opts)
     cp, cc = cam_prev.to_c(), cam_cur.to_c()
-    check(lib().rt_reproject(C.byref(cp), C.byref(fp), C.byref(cc), C.byref(fc), w, h, C.byref(o),
-                             C.byref(fo)))
+    if emit:
+        check(lib().rt_reproject_emit(C.byref(cp), C.byref(fp), C.byref(ep), C.byref(cc), C.byref(fc), C.byref(ec),
+                                      w, h, C.byref(o), C.byref(fo)))
+    else:
+        check(lib().rt_reproject(C.byref(cp), C.byref(fp), C.byref(cc), C.byref(fc), w, h, C.byref(o),
+                                 C.byref(fo)))
     return rgb, var, cnt
 
 
-def reproject_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
-    """rt_reproject_device on torch tensors: frames as reproject's, every buffer a contiguous
-    float32 tensor on cur["rgb"]'s device.  `out`: a dict of the "rgb" / "var" / "count" tensors
-    to write (missing or None: a new tensor); they may be cur's own (in place), never prev's.
-    Runs on the tensors' current stream and returns (rgb, var, count) after the work completes."""
+def _reproject_dev(emit, cam_prev, prev, cam_cur, cur, out, opts):
+    """reproject_device and reproject_emit_device (emit): rt_reproject[_emit]_device on torch
+    tensors"""
     import torch
-    who = "reproject_device"
+    who = "reproject_emit_device" if emit else "reproject_device"
     if not isinstance(cur, dict) or not torch.is_tensor(cur.get("rgb")) or cur["rgb"].dim() != 3:
         raise ValueError(f"{who}: cur['rgb'] must be a [H, W, 3] tensor")
     a = cur["rgb"]
@@ -1225,8 +1240,15 @@ def reproject_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
             raise ValueError(f"{who}: {name} must be a contiguous float32 tensor of shape {shape} "
                              "on cur['rgb']'s device")
         return t
-    fp, keep_p = _frame(who, "prev", prev, h, w, conv, lambda t: t.data_ptr())
-    fc, keep_c = _frame(who, "cur", cur, h, w, conv, lambda t: t.data_ptr())
+
+    def ptr(t):
+        return t.data_ptr()
+    fp, keep_p = _frame(who, "prev", prev, h, w, conv, ptr)
+    fc, keep_c = _frame(who, "cur", cur, h, w, conv, ptr)
+    if emit:
+        ep, keep_ep = _frame_emit(who, "prev", prev, h, w, conv, ptr)
+        ec, keep_ec = _frame_emit(who, "cur", cur, h, w, conv, ptr)
+        keep_p = keep_p + keep_ep
     res = []
     for k, ch in _FRAME_KEYS[:3]:
         shape = (h, w, ch) if ch else (h, w)
@@ -1238,9 +1260,49 @@ def reproject_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
     fo = _lib.RtFrame(*[t.data_ptr() for t in res], None, None, 0.0, 0)
     o = _reproject_opts(**opts)
     cp, cc = cam_prev.to_c(), cam_cur.to_c()
-    check(lib().rt_reproject_device(C.byref(cp), C.byref(fp), C.byref(cc), C.byref(fc), w, h,
-                                    C.byref(o), C.byref(fo), a.device.index or 0, _stream_of(a)))
+    if emit:
+        check(lib().rt_reproject_emit_device(C.byref(cp), C.byref(fp), C.byref(ep), C.byref(cc), C.byref(fc),
+                                             C.byref(ec), w, h, C.byref(o), C.byref(fo), a.device.index or 0,
+                                             _stream_of(a)))
+    else:
+        check(lib().rt_reproject_device(C.byref(cp), C.byref(fp), C.byref(cc), C.byref(fc), w, h,
+                                        C.byref(o), C.byref(fo), a.device.index or 0, _stream_of(a)))
     return tuple(res)
+
+
+def reproject(cam_prev, prev, cam_cur, cur, **opts):
+    """Temporal reprojection (rt_reproject) on host arrays: the frame `cur` seen by `cam_cur`
+    blended with the history `prev` seen by `cam_prev` that lies behind each of its pixels.  A
+    frame is a dict of float32 arrays "rgb" [H, W, 3], "normal" [H, W, 3] and "depth" [H, W] (as
+    Accumulator.resolve / resolve_aov give them) with an optional "var" [H, W] (missing: 0) and
+    "count" ([H, W], or one number for every pixel; missing: 0, which marks every pixel
+    invalid).  opts: max_history, depth_tol, normal_tol, min_weight (0 = the library defaults).
+    Returns new arrays (rgb, var, count)."""
+    return _reproject_host(False, cam_prev, prev, cam_cur, cur, opts)
+
+
+def reproject_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
+    """rt_reproject_device on torch tensors: frames as reproject's, every buffer a contiguous
+    float32 tensor on cur["rgb"]'s device.  `out`: a dict of the "rgb" / "var" / "count" tensors
+    to write (missing or None: a new tensor); they may be cur's own (in place), never prev's.
+    Runs on the tensors' current stream and returns (rgb, var, count) after the work completes."""
+    return _reproject_dev(False, cam_prev, prev, cam_cur, cur, out, opts)
+
+
+def reproject_emit(cam_prev, prev, cam_cur, cur, **opts):
+    """reproject with the directly seen emission kept out of the history (rt_reproject_emit): both
+    frames must also hold "emission" [H, W, 3] and "coverage" [H, W] (resolve_aov of an
+    accumulator with features="emit").  The history carries (rgb - emission) / (1 - coverage),
+    the current frame's own emission is added back, and a fully covered pixel neither gives nor
+    takes history.  Returns new arrays (rgb, var, count)."""
+    return _reproject_host(True, cam_prev, prev, cam_cur, cur, opts)
+
+
+def reproject_emit_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
+    """rt_reproject_emit_device on torch tensors: frames as reproject_emit's, every buffer a
+    contiguous float32 tensor on cur["rgb"]'s device; `out` as reproject_device's (never a buffer
+    of prev, its emission and coverage included)."""
+    return _reproject_dev(True, cam_prev, prev, cam_cur, cur, out, opts)
 
 
 class Temporal:
@@ -1249,11 +1311,14 @@ class Temporal:
     (reproject_device) and keeps the result as the new history.  Two sets of device tensors are
     owned and used in turn, so a push allocates nothing once warm.  opts: reproject's
     (max_history, depth_tol, normal_tol, min_weight).  The scene is static and the cameras have
-    no defocus; ``reset()`` drops the history (a cut, a changed scene)."""
+    no defocus; ``reset()`` drops the history (a cut, a changed scene).  split_emitters=True
+    (reproject_emit_device) keeps directly seen lights out of the history: the accumulators must
+    then have features="emit", whose emission and coverage are kept with the history."""
 
-    def __init__(self, **opts):
+    def __init__(self, split_emitters=False, **opts):
         _reproject_opts(**opts)  # a wrong name fails here, not at the second push
         self._opts = opts
+        self._split = bool(split_emitters)
         self._sets = [None, None]
         self.reset()
 
@@ -1271,6 +1336,9 @@ class Temporal:
         import torch
         if acc.features is None:
             raise ValueError("Temporal.push: needs an accumulator with features (the normal and depth guides)")
+        if self._split and acc.features != "emit":
+            raise ValueError("Temporal.push: split_emitters needs an accumulator with features='emit' "
+                             f"(Scene.accumulator(..., features='emit')), not features={acc.features!r}")
         if acc.nranks != 1:
             raise ValueError("Temporal.push: needs the whole image (nranks == 1)")
         passes = acc.passes
@@ -1280,17 +1348,20 @@ class Temporal:
         h, w = acc.shape
         dev = torch.device("cuda", acc._device)
         s = self._sets[k]
+        keys = _FRAME_KEYS + ((("emission", 3), ("coverage", 0)) if self._split else ())
         if s is None or s["depth"].shape != (h, w) or s["depth"].device != dev:
             s = self._sets[k] = {key: torch.empty((h, w, ch) if ch else (h, w), dtype=torch.float32, device=dev)
-                                 for key, ch in _FRAME_KEYS}
+                                 for key, ch in keys}
         acc.resolve_device(s["rgb"], s["var"])
         guides = RtAov(None, s["normal"].data_ptr(), s["depth"].data_ptr(), None)
-        check(lib().rt_accum_resolve_aov_device(acc._h(), C.byref(guides), None))
+        emit = RtAovEmit(s["emission"].data_ptr(), None, s["coverage"].data_ptr()) if self._split else None
+        check(lib().rt_accum_resolve_aov_device(acc._h(), C.byref(guides), emit and C.byref(emit)))
         p = None if self._prev is None else self._sets[self._prev]
         if p is None or p["depth"].shape != (h, w) or p["depth"].device != dev:
             s["count"].fill_(float(passes))
         else:
-            reproject_device(self._cam, p, acc.camera, dict(s, count=float(passes)), out=s, **self._opts)
+            fn = reproject_emit_device if self._split else reproject_device
+            fn(self._cam, p, acc.camera, dict(s, count=float(passes)), out=s, **self._opts)
         self._prev, self._cam = k, acc.camera
         return s["rgb"], s["var"], s["count"]
 

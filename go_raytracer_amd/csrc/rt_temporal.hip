@@ -16,9 +16,18 @@
 //                 coordinates clamped, an invalid tap's weight and values zeroed by selects (so a
 //                 NaN in the previous frame never meets a multiply).
 //
+//   k_reproject<Emit> : the template twin of rt_reproject_emit.  Emit = true keeps the directly
+//                 seen emission out of the history: every frame's pixel enters as z = (rgb -
+//                 emission) / (1 - coverage), the surface radiance of the samples that saw no light,
+//                 and the current frame's own emission is added back to the blend.  A tap whose
+//                 emission is not finite or whose coverage is not in [0, 1) is invalid like any
+//                 other: its values are selected to 0 and its divisor to 1 before the subtraction
+//                 and the division.  Emit = false is rt_reproject's kernel, instruction for
+//                 instruction (profiles/temporal_emit_device_code.txt).
+//
 // Bytes per pixel: 36 read of the current frame (28 without var and count planes), up to 4 x 36
 // gathered from the previous one (L1/L2-resident: adjacent lanes share three of four taps), 20
-// written.
+// written.  Emit: 16 more of the current pixel, 4 x 16 more gathered.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -53,11 +62,25 @@ struct Planes {  // an rt_frame's buffers
   float* depth;
 };
 
+// the emission split's planes of both frames (rt_aov_emit's emission and coverage); no member
+// without it, so that k_reproject<false> takes rt_reproject's arguments
+template <bool Emit>
+struct EmitPlanes {};
+template <>
+struct EmitPlanes<true> {
+  const float* prev_emission;
+  const float* prev_coverage;
+  const float* cur_emission;
+  const float* cur_coverage;
+};
+
 __device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 __device__ __forceinline__ V3 load3(const float* p, size_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
 __device__ __forceinline__ bool finite3(V3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
 
-__global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Planes cur, Planes out) {
+template <bool Emit>
+__global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Planes cur, Planes out,
+                                                   EmitPlanes<Emit> em) {
   const int tile_y = blockIdx.x / P.tiles_x, tile_x = blockIdx.x - tile_y * P.tiles_x;
   const int x = tile_x * kTW + (threadIdx.x & (kTW - 1)), y = tile_y * kTH + (threadIdx.x >> 6);
   if (x >= P.w || y >= P.h) return;
@@ -67,7 +90,19 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
   const float v = cur.var ? cur.var[pi] : 0.0f;
   const float nc = cur.count ? cur.count[pi] : P.cur_count;
   const float dp = cur.depth[pi];
-  const bool valid = finite3(c) && isfinite(v) && isfinite(nc) && nc > 0.0f;
+  bool valid = finite3(c) && isfinite(v) && isfinite(nc) && nc > 0.0f;
+  // Emit: z = (c - e) / k and v_z = v / k^2 stand in for c and v up to the blend; a pixel whose
+  // samples all saw the light (k = 0) carries no surface radiance and is not valid
+  V3 e = {0.0f, 0.0f, 0.0f}, z = c;
+  float kc = 1.0f, vz = v;
+  if constexpr (Emit) {
+    e = load3(em.cur_emission, pi);
+    const float cov = em.cur_coverage[pi];
+    valid = valid && finite3(e) && cov >= 0.0f && cov < 1.0f;
+    kc = valid ? 1.0f - cov : 1.0f;
+    z = {(c.x - e.x) / kc, (c.y - e.y) / kc, (c.z - e.z) / kc};
+    vz = v / (kc * kc);
+  }
   bool hist = valid && isfinite(dp) && dp > 0.0f && finite3(np);
 
   // the hit point relative to the previous centre, and its pixel in the previous camera
@@ -105,15 +140,30 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
       const float cntq = prev.count ? prev.count[qi] : P.prev_count;
       const float dq = prev.depth[qi];
       const float nx = np.x - nq.x, ny = np.y - nq.y, nz = np.z - nq.z;
-      const bool ok = hist && cx == qx && cy == qy && finite3(cq) && isfinite(vq) && isfinite(cntq) &&
-                      cntq > 0.0f && dq > 0.0f && fabsf(dq - d1) <= tol_d &&
-                      nx * nx + ny * ny + nz * nz <= P.normal_tol;
+      bool ok = hist && cx == qx && cy == qy && finite3(cq) && isfinite(vq) && isfinite(cntq) &&
+                cntq > 0.0f && dq > 0.0f && fabsf(dq - d1) <= tol_d &&
+                nx * nx + ny * ny + nz * nz <= P.normal_tol;
+      V3 eq = {0.0f, 0.0f, 0.0f};
+      float covq = 0.0f;
+      if constexpr (Emit) {
+        eq = load3(em.prev_emission, qi);
+        covq = em.prev_coverage[qi];
+        ok = ok && finite3(eq) && covq >= 0.0f && covq < 1.0f;  // a NaN coverage fails both
+      }
       const float beta = ok ? bu[a] * bv[b] : 0.0f;
+      V3 tq = {ok ? cq.x : 0.0f, ok ? cq.y : 0.0f, ok ? cq.z : 0.0f};
+      float tv = ok ? vq : 0.0f;
+      if constexpr (Emit) {  // the tap's z and v_z, from selected values only
+        const float kq = ok ? 1.0f - covq : 1.0f;
+        tq = {(tq.x - (ok ? eq.x : 0.0f)) / kq, (tq.y - (ok ? eq.y : 0.0f)) / kq,
+              (tq.z - (ok ? eq.z : 0.0f)) / kq};
+        tv = tv / (kq * kq);
+      }
       S += beta;
-      sr += beta * (ok ? cq.x : 0.0f);
-      sg += beta * (ok ? cq.y : 0.0f);
-      sb += beta * (ok ? cq.z : 0.0f);
-      sv += beta * beta * (ok ? vq : 0.0f);
+      sr += beta * tq.x;
+      sg += beta * tq.y;
+      sb += beta * tq.z;
+      sv += beta * beta * tv;
       sn += beta * (ok ? cntq : 0.0f);
     }
   }
@@ -126,11 +176,15 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
     const float cap = P.max_history > 0.0f ? P.max_history : 8.0f * nc;
     const float nh = fminf(sn * inv, cap), vh = sv * (inv * inv);
     const float n = nh + nc, in = 1.0f / n;
-    o.x = (nh * (sr * inv) + nc * c.x) * in;
-    o.y = (nh * (sg * inv) + nc * c.y) * in;
-    o.z = (nh * (sb * inv) + nc * c.z) * in;
-    ov = (nh * nh * vh + nc * nc * v) * (in * in);
+    o.x = (nh * (sr * inv) + nc * z.x) * in;
+    o.y = (nh * (sg * inv) + nc * z.y) * in;
+    o.z = (nh * (sb * inv) + nc * z.z) * in;
+    ov = (nh * nh * vh + nc * nc * vz) * (in * in);
     on = n;
+    if constexpr (Emit) {  // re-lit by the current frame's own emission, which adds no variance
+      o = {kc * o.x + e.x, kc * o.y + e.y, kc * o.z + e.z};
+      ov = kc * kc * ov;
+    }
   }
   if (out.rgb) out.rgb[3 * pi] = o.x, out.rgb[3 * pi + 1] = o.y, out.rgb[3 * pi + 2] = o.z;
   if (out.var) out.var[pi] = ov;
@@ -140,7 +194,7 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
 // ---- host -------------------------------------------------------------------------------------
 
 std::mutex g_mu;        // one host-staged call at a time: the staging buffer is shared
-DeviceScratch g_stage;  // rt_reproject's staged frames (72 B per pixel)
+DeviceScratch g_stage;  // the host entries' staged frames (72 B per pixel, 104 with the emit planes)
 
 V3 v3(const double* a) { return {(float)a[0], (float)a[1], (float)a[2]}; }
 V3 v3_diff(const double* a, const double* b) {  // the difference in fp64, then rounded
@@ -149,14 +203,19 @@ V3 v3_diff(const double* a, const double* b) {  // the difference in fp64, then 
 
 Planes planes_of(const rt_frame* f) { return {f->rgb, f->var, f->count, f->normal, f->depth}; }
 
-// argument checks of both entry points (before any device is touched) -> the kernel's parameters
-int resolve(const char* who, const rt_camera* cam_prev, const rt_frame* prev, const rt_camera* cam_cur,
-            const rt_frame* cur, int w, int h, const rt_reproject_opts* opts, const rt_frame* out,
+// argument checks of every entry point (before any device is touched) -> the kernel's parameters;
+// emit: the _emit entries, which need both rt_aov_emit with emission and coverage
+int resolve(const char* who, bool emit, const rt_camera* cam_prev, const rt_frame* prev,
+            const rt_aov_emit* prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
+            const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts, const rt_frame* out,
             TpParams* P) {
   if (!cam_prev || !cam_cur) return set_error(RT_ERR_INVALID, "%s: null camera", who);
   if (!prev || !cur || !out) return set_error(RT_ERR_INVALID, "%s: null frame", who);
+  if (emit && (!prev_emit || !cur_emit)) return set_error(RT_ERR_INVALID, "%s: null emit", who);
   if (!prev->rgb || !prev->normal || !prev->depth || !cur->rgb || !cur->normal || !cur->depth)
     return set_error(RT_ERR_INVALID, "%s: prev and cur need rgb, normal and depth", who);
+  if (emit && (!prev_emit->emission || !prev_emit->coverage || !cur_emit->emission || !cur_emit->coverage))
+    return set_error(RT_ERR_INVALID, "%s: prev_emit and cur_emit need emission and coverage", who);
   if (!out->rgb && !out->var && !out->count) return set_error(RT_ERR_INVALID, "%s: out has no buffer", who);
   if (w <= 0 || h <= 0 || (int64_t)w * h >= ((int64_t)1 << 31) / 3)
     return set_error(RT_ERR_INVALID, "%s: %d x %d image", who, w, h);
@@ -168,6 +227,11 @@ int resolve(const char* who, const rt_camera* cam_prev, const rt_frame* prev, co
     for (const float* pb : prev_bufs)
       if (ob && ob == pb)
         return set_error(RT_ERR_INVALID, "%s: out aliases a buffer of prev (the taps gather from prev)", who);
+  if (emit)
+    for (const float* ob : {out->rgb, out->var, out->count})
+      for (const float* pb : {prev_emit->emission, prev_emit->surface_albedo, prev_emit->coverage})
+        if (ob && ob == pb)
+          return set_error(RT_ERR_INVALID, "%s: out aliases a buffer of prev_emit (the taps gather from prev)", who);
   rt_camera_derived dp, dc;
   int rc = rt_camera_derive(cam_prev, &dp);
   if (rc == RT_OK) rc = rt_camera_derive(cam_cur, &dc);
@@ -196,11 +260,87 @@ int resolve(const char* who, const rt_camera* cam_prev, const rt_frame* prev, co
   return RT_OK;
 }
 
-int launch(const TpParams& P, const Planes& prev, const Planes& cur, const Planes& out, hipStream_t s) {
+// emit: the frames' rt_aov_emit (both NULL for rt_reproject's kernel, both checked by resolve)
+int launch(const TpParams& P, const Planes& prev, const Planes& cur, const Planes& out,
+           const rt_aov_emit* prev_emit, const rt_aov_emit* cur_emit, hipStream_t s) {
   const int64_t tiles = (int64_t)P.tiles_x * ((P.h + kTH - 1) / kTH);  // < 2^31 / 3: w h is
-  hipLaunchKernelGGL(k_reproject, dim3((unsigned)tiles), dim3(256), 0, s, P, prev, cur, out);
+  if (prev_emit) {
+    const EmitPlanes<true> em = {prev_emit->emission, prev_emit->coverage, cur_emit->emission, cur_emit->coverage};
+    hipLaunchKernelGGL(k_reproject<true>, dim3((unsigned)tiles), dim3(256), 0, s, P, prev, cur, out, em);
+  } else {
+    hipLaunchKernelGGL(k_reproject<false>, dim3((unsigned)tiles), dim3(256), 0, s, P, prev, cur, out,
+                       EmitPlanes<false>{});
+  }
   HIP_OK(hipGetLastError());
   return RT_OK;
+}
+
+// rt_reproject_device and rt_reproject_emit_device (emit)
+int reproject_device(const char* who, bool emit, const rt_camera* cam_prev, const rt_frame* prev,
+                     const rt_aov_emit* prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
+                     const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
+                     const rt_frame* out, int device, void* stream) {
+  TpParams P;
+  int rc = resolve(who, emit, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out, &P);
+  if (rc) return rc;
+  if ((rc = device_ok(who, device))) return rc;
+  DeviceGuard dg;
+  HIP_OK(hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  rc = launch(P, planes_of(prev), planes_of(cur), planes_of(out), prev_emit, cur_emit, s);
+  HIP_OK(hipStreamSynchronize(s));
+  return rc;
+}
+
+// rt_reproject and rt_reproject_emit (emit): host pointers, staged through device 0
+int reproject_host(const char* who, bool emit, const rt_camera* cam_prev, const rt_frame* prev,
+                   const rt_aov_emit* prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
+                   const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
+                   const rt_frame* out) {
+  TpParams P;
+  int rc = resolve(who, emit, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out, &P);
+  if (rc) return rc;
+  if ((rc = device_ok(who, 0))) return rc;
+  DeviceGuard dg;
+  HIP_OK(hipSetDevice(0));
+  std::lock_guard<std::mutex> lk(g_mu);
+  hipStream_t s = nullptr;
+  // both frames as 9 planes-floats per pixel each: rgb, var, count, normal, depth, and with emit 4
+  // more: emission, coverage.  out is written over cur's copy (out may alias cur), into the var
+  // and count slots also when cur has neither
+  const size_t n = (size_t)w * h;
+  constexpr int kOff[8] = {0, 3, 4, 5, 8, 9, 12, 13};
+  const int nbuf = emit ? 7 : 5, per = kOff[nbuf];
+  void* stg = nullptr;
+  if ((rc = g_stage.get(0, n * 4 * 2 * per, &stg, who))) return rc;
+  Planes d[2];
+  rt_aov_emit de[2];
+  const rt_frame* src[2] = {prev, cur};
+  const rt_aov_emit* esrc[2] = {prev_emit, cur_emit};
+  for (int f = 0; f < 2; ++f) {
+    float* base = (float*)stg + (size_t)f * per * n;
+    const float* host[7] = {src[f]->rgb,    src[f]->var,   src[f]->count,
+                            src[f]->normal, src[f]->depth, emit ? esrc[f]->emission : nullptr,
+                            emit ? esrc[f]->coverage : nullptr};
+    float* dev[7] = {};
+    for (int k = 0; k < nbuf; ++k) {
+      dev[k] = host[k] ? base + kOff[k] * n : nullptr;
+      if (host[k])
+        HIP_OK(hipMemcpyAsync(dev[k], host[k], n * 4 * (kOff[k + 1] - kOff[k]), hipMemcpyHostToDevice, s));
+    }
+    d[f] = {dev[0], dev[1], dev[2], dev[3], dev[4]};
+    de[f] = {dev[5], nullptr, dev[6]};
+  }
+  float* cbase = (float*)stg + (size_t)per * n;
+  const Planes o = {out->rgb ? cbase : nullptr, out->var ? cbase + kOff[1] * n : nullptr,
+                    out->count ? cbase + kOff[2] * n : nullptr, nullptr, nullptr};
+  rc = launch(P, d[0], d[1], o, emit ? &de[0] : nullptr, emit ? &de[1] : nullptr, s);
+  if (!rc && ((o.rgb && hipMemcpyAsync(out->rgb, o.rgb, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+              (o.var && hipMemcpyAsync(out->var, o.var, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+              (o.count && hipMemcpyAsync(out->count, o.count, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)))
+    rc = set_error(RT_ERR_DEVICE, "%s: copy to host failed", who);
+  HIP_OK(hipStreamSynchronize(s));  // also after an error: nothing in flight on the staging buffer
+  return rc;
 }
 
 }  // namespace
@@ -213,59 +353,28 @@ extern "C" {
 int rt_reproject_device(const rt_camera* cam_prev, const rt_frame* prev_dev, const rt_camera* cam_cur,
                         const rt_frame* cur_dev, int w, int h, const rt_reproject_opts* opts,
                         const rt_frame* out_dev, int device, void* stream) {
-  const char* who = "rt_reproject_device";
-  TpParams P;
-  int rc = resolve(who, cam_prev, prev_dev, cam_cur, cur_dev, w, h, opts, out_dev, &P);
-  if (rc) return rc;
-  if ((rc = device_ok(who, device))) return rc;
-  DeviceGuard dg;
-  HIP_OK(hipSetDevice(device));
-  hipStream_t s = (hipStream_t)stream;
-  rc = launch(P, planes_of(prev_dev), planes_of(cur_dev), planes_of(out_dev), s);
-  HIP_OK(hipStreamSynchronize(s));
-  return rc;
+  return reproject_device("rt_reproject_device", false, cam_prev, prev_dev, nullptr, cam_cur, cur_dev, nullptr, w, h,
+                          opts, out_dev, device, stream);
 }
 
 int rt_reproject(const rt_camera* cam_prev, const rt_frame* prev, const rt_camera* cam_cur,
                  const rt_frame* cur, int w, int h, const rt_reproject_opts* opts, const rt_frame* out) {
-  const char* who = "rt_reproject";
-  TpParams P;
-  int rc = resolve(who, cam_prev, prev, cam_cur, cur, w, h, opts, out, &P);
-  if (rc) return rc;
-  if ((rc = device_ok(who, 0))) return rc;
-  DeviceGuard dg;
-  HIP_OK(hipSetDevice(0));
-  std::lock_guard<std::mutex> lk(g_mu);
-  hipStream_t s = nullptr;
-  // both frames as 9 planes-floats per pixel each: rgb, var, count, normal, depth.  out is written
-  // over cur's copy (out may alias cur), into the var and count slots also when cur has neither
-  const size_t n = (size_t)w * h;
-  constexpr int kOff[6] = {0, 3, 4, 5, 8, 9};
-  void* stg = nullptr;
-  if ((rc = g_stage.get(0, n * 4 * 18, &stg, who))) return rc;
-  Planes d[2];
-  const rt_frame* src[2] = {prev, cur};
-  for (int f = 0; f < 2; ++f) {
-    float* base = (float*)stg + (size_t)f * 9 * n;
-    const float* host[5] = {src[f]->rgb, src[f]->var, src[f]->count, src[f]->normal, src[f]->depth};
-    float* dev[5];
-    for (int k = 0; k < 5; ++k) {
-      dev[k] = host[k] ? base + kOff[k] * n : nullptr;
-      if (host[k])
-        HIP_OK(hipMemcpyAsync(dev[k], host[k], n * 4 * (kOff[k + 1] - kOff[k]), hipMemcpyHostToDevice, s));
-    }
-    d[f] = {dev[0], dev[1], dev[2], dev[3], dev[4]};
-  }
-  float* cbase = (float*)stg + 9 * n;
-  const Planes o = {out->rgb ? cbase : nullptr, out->var ? cbase + kOff[1] * n : nullptr,
-                    out->count ? cbase + kOff[2] * n : nullptr, nullptr, nullptr};
-  rc = launch(P, d[0], d[1], o, s);
-  if (!rc && ((o.rgb && hipMemcpyAsync(out->rgb, o.rgb, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-              (o.var && hipMemcpyAsync(out->var, o.var, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-              (o.count && hipMemcpyAsync(out->count, o.count, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)))
-    rc = set_error(RT_ERR_DEVICE, "%s: copy to host failed", who);
-  HIP_OK(hipStreamSynchronize(s));  // also after an error: nothing in flight on the staging buffer
-  return rc;
+  return reproject_host("rt_reproject", false, cam_prev, prev, nullptr, cam_cur, cur, nullptr, w, h, opts, out);
+}
+
+int rt_reproject_emit_device(const rt_camera* cam_prev, const rt_frame* prev_dev, const rt_aov_emit* prev_emit_dev,
+                             const rt_camera* cam_cur, const rt_frame* cur_dev, const rt_aov_emit* cur_emit_dev,
+                             int w, int h, const rt_reproject_opts* opts, const rt_frame* out_dev, int device,
+                             void* stream) {
+  return reproject_device("rt_reproject_emit_device", true, cam_prev, prev_dev, prev_emit_dev, cam_cur, cur_dev,
+                          cur_emit_dev, w, h, opts, out_dev, device, stream);
+}
+
+int rt_reproject_emit(const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
+                      const rt_camera* cam_cur, const rt_frame* cur, const rt_aov_emit* cur_emit, int w, int h,
+                      const rt_reproject_opts* opts, const rt_frame* out) {
+  return reproject_host("rt_reproject_emit", true, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts,
+                        out);
 }
 
 }  // extern "C"

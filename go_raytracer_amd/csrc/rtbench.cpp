@@ -46,7 +46,9 @@
 // weighing its passes, before -denoise-var and the writer, and the result is the next frame's history;
 // the host entry, which stages through the device and gives rt_reproject_device's bits: this client
 // links no HIP runtime to own device buffers with; the statistics line gains "temporal": 1 and
-// ms_reproject), -counts FILE (with -adaptive: the passes per pixel as grey, count / max).  -cpuprofile has no pprof to drive on the GPU path: the file
+// ms_reproject), -temporal-emit (as -temporal, and needs -split-emitters too, else a usage error: the
+// stage runs through rt_reproject_emit with the accumulator's emission and coverage, which are kept
+// with the history; the statistics line also gains "temporal_emit": 1), -counts FILE (with -adaptive: the passes per pixel as grey, count / max).  -cpuprofile has no pprof to drive on the GPU path: the file
 // receives the same JSON statistics instead.
 #include <unistd.h>
 
@@ -82,7 +84,7 @@ struct Args {
   bool adaptive_set = false;
   unsigned long long seed = 1, tree_seed = 1;
   bool progress = false, stats = false, denoise = false, denoise_var = false, split_emitters = false;
-  bool accum_features = false, temporal = false;
+  bool accum_features = false, temporal = false, temporal_emit = false;
   long long frames = 0;
   double orbit = 0.0;
 };
@@ -128,6 +130,8 @@ std::vector<Flag> flags(Args& a) {
       {"stats", "print render statistics (JSON) on stderr", Flag::BOOL, &a.stats, ""},
       {"temporal", "with -accum-features and -passes / -until / -adaptive: blend each frame with the reprojected history of the frames before it (rt_reproject)",
        Flag::BOOL, &a.temporal, ""},
+      {"temporal-emit", "as -temporal, with directly seen lights kept out of the history (rt_reproject_emit); needs -split-emitters too",
+       Flag::BOOL, &a.temporal_emit, ""},
       {"tree-seed", "seed of the scene builder's rand (main.go's math/rand)", Flag::U64,
        &a.tree_seed, "1"},
       {"until", "add passes until the image's relative standard error is <= E (at most -passes, default 1024)",
@@ -264,10 +268,11 @@ std::string stats_json(const rt_stats& st, const rt_camera_derived& d, const cha
                        const rt_accum_info* acc, double ms_accum, bool denoise_var,
                        const rt_adapt_info* ad = nullptr, bool split_emitters = false,
                        bool accum_features = false, int frame = -1, bool temporal = false,
-                       double ms_reproject = 0.0) {
-  char b[1280], extra[200] = "", extra2[200] = "", extra4[120] = "";
+                       double ms_reproject = 0.0, bool temporal_emit = false) {
+  char b[1280], extra[200] = "", extra2[200] = "", extra4[160] = "";
   if (frame >= 0) snprintf(extra4, sizeof extra4, "\"frame\": %d, ", frame);
   if (temporal) snprintf(extra4 + strlen(extra4), sizeof extra4 - strlen(extra4), "\"temporal\": 1, \"ms_reproject\": %.3f, ", ms_reproject);
+  if (temporal_emit) snprintf(extra4 + strlen(extra4), sizeof extra4 - strlen(extra4), "\"temporal_emit\": 1, ");
   const std::string extra3s = std::string(split_emitters ? "\"split_emitters\": 1, " : "") +
                               (accum_features ? "\"accum_features\": 1, " : "") + extra4;
   const char* extra3 = extra3s.c_str();
@@ -329,6 +334,12 @@ int main(int argc, char** argv) {
     usage(argv[0], flags(a));
     return 2;
   }
+  if (a.temporal_emit && !(a.split_emitters && a.accum_features && (a.passes > 0 || a.until > 0.0 || a.adaptive_set))) {
+    fprintf(stderr, "-temporal-emit needs -split-emitters, -accum-features and -passes, -until or -adaptive\n");  // no emit planes
+    usage(argv[0], flags(a));
+    return 2;
+  }
+  if (a.temporal_emit) a.temporal = true;  // the same stage, through rt_reproject_emit
   if (a.frames < 0 || a.frames > 999 || !(a.orbit == a.orbit)) {
     fprintf(stderr, "invalid value for flag -frames (0..999) / -orbit\n");
     usage(argv[0], flags(a));
@@ -386,7 +397,7 @@ int main(int argc, char** argv) {
 
   // -temporal: the history (the frames before this one, reprojected and blended) and its camera
   const size_t n_px = (size_t)d.width * d.height;
-  std::vector<float> h_rgb, h_var, h_count, h_normal, h_depth, count;
+  std::vector<float> h_rgb, h_var, h_count, h_normal, h_depth, h_emission, h_coverage, count;
   rt_camera h_cam;
   bool have_history = false;
   const rt_camera cam0 = cam;
@@ -569,10 +580,18 @@ int main(int argc, char** argv) {
         const rt_frame prev = {h_rgb.data(), h_var.data(), h_count.data(), h_normal.data(), h_depth.data(), 0.0f, 0};
         const rt_frame cur = {rgb.data(), var.data(), nullptr, normal.data(), depth.data(), (float)ai.passes, 0};
         const rt_frame res = {rgb.data(), var.data(), count.data(), nullptr, nullptr, 0.0f, 0};
-        if ((rc = rt_reproject(&h_cam, &prev, &cam, &cur, d.width, d.height, nullptr, &res)) != RT_OK)
+        const rt_aov_emit prev_emit = {h_emission.data(), nullptr, h_coverage.data()};
+        const rt_aov_emit cur_emit = {emission.data(), nullptr, coverage.data()};
+        if (a.temporal_emit) {
+          if ((rc = rt_reproject_emit(&h_cam, &prev, &prev_emit, &cam, &cur, &cur_emit, d.width, d.height, nullptr,
+                                      &res)) != RT_OK)
+            return fail("rt_reproject_emit", rc);
+        } else if ((rc = rt_reproject(&h_cam, &prev, &cam, &cur, d.width, d.height, nullptr, &res)) != RT_OK) {
           return fail("rt_reproject", rc);
+        }
       }
       h_rgb = rgb, h_var = var, h_count = count, h_normal = normal, h_depth = depth;
+      if (a.temporal_emit) h_emission = emission, h_coverage = coverage;
       h_cam = cam;
       have_history = true;
       ms_reproject = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
@@ -634,7 +653,7 @@ int main(int argc, char** argv) {
   double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::string js = stats_json(st, d, scene, wall, aov_samples, ms_aov, ms_denoise, accumulate ? &ai : nullptr,
                               ms_accum, a.denoise_var, a.adaptive_set ? &adi : nullptr, a.split_emitters,
-                              a.accum_features, numbered ? frame : -1, a.temporal, ms_reproject);
+                              a.accum_features, numbered ? frame : -1, a.temporal, ms_reproject, a.temporal_emit);
   if (a.stats || a.denoise || a.denoise_var || a.temporal) fprintf(stderr, "%s\n", js.c_str());
   if (!a.cpuprofile.empty()) {
     FILE* p = fopen(a.cpuprofile.c_str(), "w");

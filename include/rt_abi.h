@@ -890,6 +890,42 @@ int rt_reproject_device(const rt_camera* cam_prev, const rt_frame* prev_dev,
                         const rt_reproject_opts* opts, const rt_frame* out_dev, int device,
                         void* stream);
 
+/* rt_reproject with the directly seen emission kept out of the history (DESIGN.md "Temporal
+ * reprojection"; the emission split of rt_denoise_emit applied to the temporal stage): a light
+ * that lies in a surface's plane passes the depth and normal tests, and without the split the
+ * bilinear taps bleed it into the pixels beside it, frame after frame.  Added without an ABI
+ * version change (rt_frame and rt_reproject_opts are unchanged): detect by the symbols.
+ * prev_emit / cur_emit: the frames' rt_aov_emit (rt_accum_resolve_aov's of an accumulator with
+ * RT_ACCUM_FEAT_EMIT); emission and coverage are required, surface_albedo is not read and may be
+ * NULL.  The definition is rt_reproject's with exactly these changes.  Per frame and pixel let
+ *   k = 1 - coverage,   z = (rgb - emission) / k   (the surface radiance per sample that saw no
+ *   light),   v_z = var / k^2;   the history weight n stays in pixel units.
+ *   current pixel valid: the parent's rule, and emission finite, and coverage finite with
+ *     0 <= coverage < 1.
+ *   tap valid: the parent's rule, and the tap's emission finite and 0 <= coverage_q < 1.  A fully
+ *     covered pixel carries no surface information: it is never a tap and never takes history.
+ *   reprojected history and blend: the parent's formulas for c_h, v_h, n_h, the cap and the
+ *     blend, applied to z, v_z and n (z_q, v_z_q of the taps; z_c, v_z_c of the current pixel).
+ *   output, pixels that found history: out.rgb = k_c z_blend + emission_c, out.var = k_c^2
+ *     v_blend, out.count = n_h + n_c: the emission is deterministic and adds no variance.
+ *   output, every other pixel (invalid, a miss, coverage 1, S < min_weight): rgb, var and count
+ *     pass through bit for bit, also when out aliases cur.
+ * The operations run in this order: subtract, divide, then multiply-add; so with emission = 0 and
+ * coverage = 0 in both frames the result is rt_reproject's bit for bit.
+ * Argument checks, before any device is touched: the parent's, and RT_ERR_INVALID for a NULL
+ * prev_emit or cur_emit, for a missing emission or coverage in either, and for an out buffer that
+ * is also a buffer of prev_emit.  out may alias cur's and cur_emit's buffers (the current pixel
+ * is read whole before any write).  Host and device forms as rt_reproject's; rt_reproject_emit
+ * stages 104 bytes per pixel.  Two calls give identical bits. */
+int rt_reproject_emit(const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
+                      const rt_camera* cam_cur, const rt_frame* cur, const rt_aov_emit* cur_emit,
+                      int w, int h, const rt_reproject_opts* opts, const rt_frame* out);
+int rt_reproject_emit_device(const rt_camera* cam_prev, const rt_frame* prev_dev,
+                             const rt_aov_emit* prev_emit_dev, const rt_camera* cam_cur,
+                             const rt_frame* cur_dev, const rt_aov_emit* cur_emit_dev, int w, int h,
+                             const rt_reproject_opts* opts, const rt_frame* out_dev, int device,
+                             void* stream);
+
 /* Demo scenes mirroring main.go (by name or the main.go -S number).
  * names: book1, book2, book3, simple_light, quads, cornell, cornell_smoke, model
  * The camera receives the scene's settings; override fields afterwards. */

@@ -1,6 +1,7 @@
 """Is a tree's device code another tree's?  Per kernel: resources and instruction stream.
 
-  python tools/device_code_compare.py emit CSRC OUTDIR    # compile CSRC's device side into OUTDIR
+  python tools/device_code_compare.py emit CSRC OUTDIR [UNIT ...]   # compile CSRC's device side (or the named
+                                                                    # units only) into OUTDIR
   python tools/device_code_compare.py diff PARENT_OUT NEW_OUT
 
 `emit` compiles every device translation unit of a csrc directory with the Makefile's
@@ -9,7 +10,9 @@ and in the opt-in builds a test or tool uses.  `diff` prints one line per kernel
 form of profiles/render_host_stages_device_code.txt and ends with a RESULT line; the exit
 status is 0 only if every kernel's resources and instructions are equal and the kernel
 sets match.  Block labels are compared without their function number, which depends only
-on a function's position in the module.
+on a function's position in the module.  A kernel that became a template twin is compared with
+its parent under the parent's name: `k<false>(args, Twin<false>)` in the new tree pairs with a
+plain `k(args)` that only the parent has.
 """
 import os
 import re
@@ -18,9 +21,9 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 UNITS = ["rt_render", "rt_fused_sets", "rt_fused_map", "rt_aov", "rt_accum", "rt_multi", "rt_output", "rt_build",
-         "rt_denoise"]
+         "rt_denoise", "rt_temporal"]
 # units without the kernel headers: no build switch reaches them, the default build is all there is
-PLAIN_UNITS = ["rt_output", "rt_build", "rt_denoise"]
+PLAIN_UNITS = ["rt_output", "rt_build", "rt_denoise", "rt_temporal"]
 NAME_MAX = 160  # a printed kernel name is cut here (hipCUB's run to kilobytes)
 BUILDS = {"default": [], "bvh8": ["-DRT_BVH8_KERNELS"], "sweep": ["-DRT_SWEEP_ORDER"]}
 # rt_fused_sets.hip's own flags (Makefile FUSED_SETS_FLAGS)
@@ -41,10 +44,10 @@ def emit_one(csrc, out, build, unit):
     return build, unit, r.returncode
 
 
-def emit(csrc, out):
+def emit(csrc, out, units=()):
     os.makedirs(out, exist_ok=True)
     out = os.path.abspath(out)
-    jobs = [(b, u) for b in BUILDS for u in UNITS
+    jobs = [(b, u) for b in BUILDS for u in (units or UNITS)
             if os.path.exists(os.path.join(csrc, u + ".hip")) and (b == "default" or u not in PLAIN_UNITS)]
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
         res = list(ex.map(lambda j: emit_one(csrc, out, *j), jobs))
@@ -85,9 +88,40 @@ def streams(path):
     return funcs
 
 
-def demangle(names):
+def demangle(names, cut=True):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return {k: v if len(v) <= NAME_MAX else v[:NAME_MAX] + "..." for k, v in zip(names, out)}
+    return {k: v if len(v) <= NAME_MAX or not cut else v[:NAME_MAX] + "..." for k, v in zip(names, out)}
+
+
+def base_name(name):
+    """(the demangled kernel name without `void`, template arguments and argument list, its
+    template arguments or None)"""
+    depth, i = 0, len(name)
+    while i > 0:  # the argument list: back from the end to its opening parenthesis
+        i -= 1
+        depth += (name[i] == ")") - (name[i] == "(")
+        if depth == 0:
+            break
+    head = re.sub(r"^void ", "", name[:i])
+    m = re.match(r"^(.*?)(<[^()]*>)$", head)
+    return (m.group(1), m.group(2)) if m else (head, None)
+
+
+def pair_twins(pres, nres, pins, nins, names):
+    """rename the parent's plain kernel k to the new tree's k<false> where only the trees' own
+    side has each"""
+    full = demangle(list(dict.fromkeys(list(pres) + list(nres))), cut=False)
+    for nk in [k for k in nres if k not in pres]:
+        nb, nt = base_name(full[nk])
+        if nt != "<false>":
+            continue
+        for pk in [k for k in pres if k not in nres]:
+            if base_name(full[pk]) == (nb, None):
+                print(f"   twin: {names[nk]} against the parent's {names[pk]}")
+                pres[nk] = pres.pop(pk)
+                if pk in pins:  # under the new name, so that only the code can differ
+                    pins[nk] = [line.replace(pk, nk) for line in pins.pop(pk)]
+                break
 
 
 def diff(pdir, ndir):
@@ -102,6 +136,7 @@ def diff(pdir, ndir):
             pins, nins = (streams(p[:-8] + ".s") if os.path.exists(p[:-8] + ".s") else {} for p in (pr, nr))
             names = demangle(list(dict.fromkeys(list(pres) + list(nres))))
             print(f"-- {unit}: parent {len(pres)} kernels, new {len(nres)} kernels")
+            pair_twins(pres, nres, pins, nins, names)
             for k in pres:
                 if k not in nres:
                     same = False
@@ -122,13 +157,16 @@ def diff(pdir, ndir):
                 same = same and req and ieq
                 print(f"   {names[k]:{width}s} {cols}  resources {'equal' if req else 'DIFFER'}"
                       f"  instructions {n} {'equal' if ieq else 'DIFFER'}")
+                if not ieq and k in pins and k in nins and len(pins[k]) == len(nins[k]):
+                    for a, b in [(a, b) for a, b in zip(pins[k], nins[k]) if a != b][:8]:
+                        print(f"      parent: {a}\n      new:    {b}")
     print("RESULT: device code is the parent's" if same else "RESULT: device code DIFFERS from the parent's")
     return 0 if same else 1
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 4 and sys.argv[1] == "emit":
-        sys.exit(emit(sys.argv[2], sys.argv[3]))
+    if len(sys.argv) >= 4 and sys.argv[1] == "emit":
+        sys.exit(emit(sys.argv[2], sys.argv[3], sys.argv[4:]))
     if len(sys.argv) == 4 and sys.argv[1] == "diff":
         sys.exit(diff(sys.argv[2], sys.argv[3]))
     sys.exit(__doc__)
