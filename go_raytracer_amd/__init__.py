@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (RT_FT_ALL, RT_FT_BOX, RT_NOISE_MARBLE, RT_NOISE_PERLIN,  # noqa: F401
-                   RT_NOISE_TURBULENT, RtAccumInfo, RtAov, RtAovEmit, RtCamera, RtDenoiseOpts,
+                   RT_NOISE_TURBULENT, RtAccumInfo, RtAov, RtAovEmit, RtAovMedia, RtCamera, RtDenoiseOpts,
                    RtDenoiseVarOpts, RtCameraDerived, RtError, RtRenderOpts, RtSceneInfo, RtStats, RtTreeView,
                    check, lib)
 
@@ -565,7 +565,7 @@ class Scene:
                                      C.byref(st)))
         return _as_dict(st)
 
-    def render_aov(self, camera, n_samples=1, seed=1, device=0, rank=0, nranks=1, emit=False):
+    def render_aov(self, camera, n_samples=1, seed=1, device=0, rank=0, nranks=1, emit=False, media=False):
         """Feature buffers of this rank's rows (rt_render_aov): the first hit of the camera
         rays render() gives samples 0 .. n_samples-1 of every pixel, averaged.  Returns
         {"albedo": float32 [rows, W, 3], "normal": float32 [rows, W, 3] (world space, facing
@@ -574,7 +574,11 @@ class Scene:
         adds the emission split: "emission" float32 [rows, W, 3] (what directly seen lights add
         to the pixel: their emission, which the render does not clamp), "surface_albedo" float32 [rows, W, 3]
         (the albedo of the samples that see no light) and "coverage" float32 [rows, W] (the
-        fraction of samples that see a light's front face)."""
+        fraction of samples that see a light's front face).  media=True (rt_render_aov_media)
+        traces the constant media as the render's camera vertex does: every buffer is then of the
+        sample's first event, a scatter inside a volume included (the phase material's albedo,
+        no normal, the scatter's depth), and "scatter" float32 [rows, W] is the fraction of
+        samples whose first event is a scatter.  With emit=True it returns both sets."""
         d = camera.derived()
         rows = len(range(rank, d.height, nranks))
         res = {"albedo": np.zeros((rows, d.width, 3), np.float32),
@@ -588,17 +592,25 @@ class Scene:
             res["surface_albedo"] = np.zeros((rows, d.width, 3), np.float32)
             res["coverage"] = np.zeros((rows, d.width), np.float32)
             e = RtAovEmit(*[res[k].ctypes.data for k in ("emission", "surface_albedo", "coverage")])
+        m = None
+        if media:
+            res["scatter"] = np.zeros((rows, d.width), np.float32)
+            m = RtAovMedia(res["scatter"].ctypes.data)
         o = self._opts(seed, device, rank, nranks, 0, 0, False, None)
-        res["stats"] = self._aov(camera, o, n_samples, a, e, False)
+        res["stats"] = self._aov(camera, o, n_samples, a, e, False, m)
         return res
 
-    def _aov(self, camera, o, n_samples, a, e, device):
-        """One of the four rt_render_aov entries: the emit ones with an RtAovEmit `e`, the
-        _device ones with `device` -> the stats dict."""
+    def _aov(self, camera, o, n_samples, a, e, device, m=None):
+        """One of the six rt_render_aov entries: the emit ones with an RtAovEmit `e`, the media
+        ones with an RtAovMedia `m` (e may then be None), the _device ones with `device` -> the
+        stats dict."""
         st = RtStats()
         c = camera.to_c()
         L = lib()
-        if e is None:
+        if m is not None:
+            fn, args = ((L.rt_render_aov_media_device if device else L.rt_render_aov_media),
+                        (C.byref(a), None if e is None else C.byref(e), C.byref(m)))
+        elif e is None:
             fn, args = (L.rt_render_aov_device if device else L.rt_render_aov), (C.byref(a),)
         else:
             fn, args = ((L.rt_render_aov_emit_device if device else L.rt_render_aov_emit),
@@ -608,23 +620,26 @@ class Scene:
 
     def render_aov_device(self, camera, albedo=None, normal=None, depth=None, material=None,
                           n_samples=1, seed=1, device=0, rank=0, nranks=1, stream=None,
-                          emission=None, surface_albedo=None, coverage=None):
+                          emission=None, surface_albedo=None, coverage=None, media=False, scatter=None):
         """rt_render_aov_device: the same buffers written to device pointers (e.g. torch
         tensors' .data_ptr(); None = not wanted) on `stream`.  With any of emission /
-        surface_albedo / coverage the call is rt_render_aov_emit_device.  Returns the stats
-        dict."""
+        surface_albedo / coverage the call is rt_render_aov_emit_device; with media=True or a
+        `scatter` pointer it is rt_render_aov_media_device.  Returns the stats dict."""
         e = None
         if emission is not None or surface_albedo is not None or coverage is not None:
             e = RtAovEmit(emission, surface_albedo, coverage)
+        m = RtAovMedia(scatter) if media or scatter is not None else None
         o = self._opts(seed, device, rank, nranks, 0, 0, False, stream)
-        return self._aov(camera, o, n_samples, RtAov(albedo, normal, depth, material), e, True)
+        return self._aov(camera, o, n_samples, RtAov(albedo, normal, depth, material), e, True, m)
 
     def accumulator(self, camera, max_passes=0, device=0, rank=0, nranks=1, path_slots=0, chunk=0,
                     profile=False, stream=None, mode="auto", progress_slices=0, features=None):
         """A progressive pass accumulator (rt_accum_create) for this rank's rows of `camera`:
         see Accumulator.  max_passes=0 means 1024.  features="guides" keeps the albedo, normal
         and depth of the passes' own camera samples next to the image sums, "emit" also the
-        emission split (rt_accum_set_features): see Accumulator.resolve_aov."""
+        emission split (rt_accum_set_features): see Accumulator.resolve_aov.  "guides+media" and
+        "emit+media" keep the same planes of the samples' first events, constant media traced
+        (Scene.render_aov(media=True)), and a scatter plane."""
         return Accumulator(self, camera, max_passes, device, rank, nranks, path_slots, chunk,
                            profile, stream, mode, progress_slices, features)
 
@@ -642,10 +657,14 @@ class Accumulator:
     ``features="guides"`` or ``"emit"`` makes every pass also sum the first-hit features of its
     own camera samples (all of them, for whole and for active-pixel passes): ``resolve_aov()``
     returns their means, the guides of exactly the samples in the image, and
-    ``denoise_device()`` then needs no ``aov``."""
+    ``denoise_device()`` then needs no ``aov``.  ``"guides+media"`` / ``"emit+media"`` trace the
+    constant media in those feature rays (``Scene.render_aov(media=True)``): the planes are of the
+    samples' first events and ``resolve_aov()`` adds ``"scatter"``."""
 
     FEATURES = {None: 0, "guides": _lib.RT_ACCUM_FEAT_GUIDES,
-                "emit": _lib.RT_ACCUM_FEAT_GUIDES | _lib.RT_ACCUM_FEAT_EMIT}
+                "emit": _lib.RT_ACCUM_FEAT_GUIDES | _lib.RT_ACCUM_FEAT_EMIT,
+                "guides+media": _lib.RT_ACCUM_FEAT_GUIDES | _lib.RT_ACCUM_FEAT_MEDIA,
+                "emit+media": _lib.RT_ACCUM_FEAT_GUIDES | _lib.RT_ACCUM_FEAT_EMIT | _lib.RT_ACCUM_FEAT_MEDIA}
 
     def __init__(self, scene, camera, max_passes=0, device=0, rank=0, nranks=1, path_slots=0,
                  chunk=0, profile=False, stream=None, mode="auto", progress_slices=0, features=None):
@@ -653,7 +672,8 @@ class Accumulator:
         self._device, self._mean, self._var = device, None, None  # denoise_device's tensors
         self._aov = None  # resolve_aov_device's
         if features not in self.FEATURES:
-            raise ValueError(f"Accumulator: features must be None, 'guides' or 'emit', not {features!r}")
+            raise ValueError("Accumulator: features must be None, 'guides', 'emit', 'guides+media' or "
+                             f"'emit+media', not {features!r}")
         d = camera.derived()
         self.shape = (len(range(rank, d.height, nranks)), d.width)
         c = camera.to_c()
@@ -680,7 +700,8 @@ class Accumulator:
 
     @property
     def features(self):
-        """None, "guides" or "emit": the feature planes the passes keep (rt_accum_get_features)."""
+        """None, "guides", "emit", "guides+media" or "emit+media": the feature planes the passes
+        keep (rt_accum_get_features)."""
         m = C.c_uint32()
         check(lib().rt_accum_get_features(self._h(), C.byref(m)))
         return {v: k for k, v in self.FEATURES.items()}.get(m.value, m.value)
@@ -689,19 +710,34 @@ class Accumulator:
         f = self.features
         if f is None:
             raise ValueError("Accumulator: no feature planes (Scene.accumulator(features=...))")
-        return ("albedo", "normal", "depth") + (("emission", "surface_albedo", "coverage") if f == "emit" else ())
+        f = str(f)
+        return (("albedo", "normal", "depth")
+                + (("emission", "surface_albedo", "coverage") if f.startswith("emit") else ())
+                + (("scatter",) if f.endswith("+media") else ()))
+
+    @staticmethod
+    def _aov_args(keys, ptr):
+        """rt_accum_resolve_aov's or, with a scatter plane, rt_accum_resolve_aov_media's arguments
+        for the planes `keys`, ptr(key) -> the plane's address; (the _media entry?, the arguments)"""
+        a = RtAov(*[ptr(k) for k in keys[:3]], None)
+        e = RtAovEmit(*[ptr(k) for k in keys[3:6]]) if "coverage" in keys else None
+        args = (C.byref(a), None if e is None else C.byref(e))
+        if "scatter" not in keys:
+            return False, args, (a, e)
+        m = RtAovMedia(ptr("scatter"))
+        return True, args + (C.byref(m),), (a, e, m)
 
     def resolve_aov(self):
         """The feature buffers of exactly the camera samples the passes rendered
-        (rt_accum_resolve_aov): {"albedo", "normal", "depth"} and, with features="emit",
-        {"emission", "surface_albedo", "coverage"}, float32 arrays shaped as
+        (rt_accum_resolve_aov): {"albedo", "normal", "depth"}, with features="emit" also
+        {"emission", "surface_albedo", "coverage"} and with "+media" also {"scatter"}
+        (rt_accum_resolve_aov_media), float32 arrays shaped as
         Scene.render_aov's: per pixel the mean over its passes' samples, zeros without a pass."""
         keys = self._aov_keys()
-        res = {k: np.zeros(self.shape + ((3,) if k not in ("depth", "coverage") else ()), np.float32)
+        res = {k: np.zeros(self.shape + ((3,) if k not in ("depth", "coverage", "scatter") else ()), np.float32)
                for k in keys}
-        a = RtAov(*[res[k].ctypes.data for k in keys[:3]], None)
-        e = RtAovEmit(*[res[k].ctypes.data for k in keys[3:]]) if len(keys) > 3 else None
-        check(lib().rt_accum_resolve_aov(self._h(), C.byref(a), None if e is None else C.byref(e)))
+        media, args, _keep = self._aov_args(keys, lambda k: res[k].ctypes.data)
+        check((lib().rt_accum_resolve_aov_media if media else lib().rt_accum_resolve_aov)(self._h(), *args))
         return res
 
     def resolve_aov_device(self):
@@ -711,12 +747,12 @@ class Accumulator:
         keys = self._aov_keys()
         if self._aov is None or tuple(self._aov) != keys:
             dev = torch.device("cuda", self._device)
-            self._aov = {k: torch.empty(self.shape + ((3,) if k not in ("depth", "coverage") else ()),
+            self._aov = {k: torch.empty(self.shape + ((3,) if k not in ("depth", "coverage", "scatter") else ()),
                                         dtype=torch.float32, device=dev) for k in keys}
         t = self._aov
-        a = RtAov(*[t[k].data_ptr() for k in keys[:3]], None)
-        e = RtAovEmit(*[t[k].data_ptr() for k in keys[3:]]) if len(keys) > 3 else None
-        check(lib().rt_accum_resolve_aov_device(self._h(), C.byref(a), None if e is None else C.byref(e)))
+        media, args, _keep = self._aov_args(keys, lambda k: t[k].data_ptr())
+        check((lib().rt_accum_resolve_aov_media_device if media else lib().rt_accum_resolve_aov_device)(
+            self._h(), *args))
         return t
 
     __del__ = close
@@ -777,7 +813,7 @@ class Accumulator:
                 raise ValueError("Accumulator.denoise_device: needs aov, or an accumulator with features")
             own = False
         if own and split_emitters is None:
-            split_emitters = self.features == "emit"
+            split_emitters = str(self.features).startswith("emit")
         split_emitters = bool(split_emitters)
         if self.passes < 2:
             raise ValueError("Accumulator.denoise_device: needs at least 2 passes (no variance yet)")
@@ -1336,7 +1372,7 @@ class Temporal:
         import torch
         if acc.features is None:
             raise ValueError("Temporal.push: needs an accumulator with features (the normal and depth guides)")
-        if self._split and acc.features != "emit":
+        if self._split and not str(acc.features).startswith("emit"):
             raise ValueError("Temporal.push: split_emitters needs an accumulator with features='emit' "
                              f"(Scene.accumulator(..., features='emit')), not features={acc.features!r}")
         if acc.nranks != 1:

@@ -31,6 +31,7 @@ RT_FT_BOX = 256
 RT_FT_ALL = 511
 RT_MODE_AUTO, RT_MODE_WAVEFRONT, RT_MODE_FUSED = 0, 1, 2
 RT_ACCUM_FEAT_GUIDES, RT_ACCUM_FEAT_EMIT = 1, 2  # rt_accum_set_features' plane groups
+RT_ACCUM_FEAT_MEDIA = 4  # ... and the modifier that makes them first-event sums (with a scatter count)
 
 D3 = C.c_double * 3
 
@@ -103,6 +104,10 @@ class RtAov(C.Structure):  # rt_aov: feature buffers (any pointer may be NULL)
 class RtAovEmit(C.Structure):  # rt_aov_emit: the emission split (any pointer may be NULL)
     _fields_ = [("emission", C.c_void_p), ("surface_albedo", C.c_void_p),
                 ("coverage", C.c_void_p)]
+
+
+class RtAovMedia(C.Structure):  # rt_aov_media: the media mode's plane (may be NULL)
+    _fields_ = [("scatter", C.c_void_p)]
 
 
 class RtDenoiseOpts(C.Structure):
@@ -281,6 +286,12 @@ SIGNATURES = {
     "rt_render_aov_emit_device": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
                                        C.POINTER(RtAov), C.POINTER(RtAovEmit),
                                        C.POINTER(RtStats)]),
+    "rt_render_aov_media": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
+                                 C.POINTER(RtAov), C.POINTER(RtAovEmit), C.POINTER(RtAovMedia),
+                                 C.POINTER(RtStats)]),
+    "rt_render_aov_media_device": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
+                                        C.POINTER(RtAov), C.POINTER(RtAovEmit), C.POINTER(RtAovMedia),
+                                        C.POINTER(RtStats)]),
     "rt_denoise_emit": (_I, [C.c_void_p, C.POINTER(RtAov), C.POINTER(RtAovEmit), _I, _I,
                              C.POINTER(RtDenoiseOpts), C.c_void_p]),
     "rt_denoise_emit_device": (_I, [C.c_void_p, C.POINTER(RtAov), C.POINTER(RtAovEmit), _I, _I,
@@ -311,6 +322,9 @@ SIGNATURES = {
     "rt_accum_get_features": (_I, [_P, C.POINTER(C.c_uint32)]),
     "rt_accum_resolve_aov": (_I, [_P, C.POINTER(RtAov), C.POINTER(RtAovEmit)]),
     "rt_accum_resolve_aov_device": (_I, [_P, C.POINTER(RtAov), C.POINTER(RtAovEmit)]),
+    "rt_accum_resolve_aov_media": (_I, [_P, C.POINTER(RtAov), C.POINTER(RtAovEmit), C.POINTER(RtAovMedia)]),
+    "rt_accum_resolve_aov_media_device": (_I, [_P, C.POINTER(RtAov), C.POINTER(RtAovEmit),
+                                               C.POINTER(RtAovMedia)]),
     "rt_reproject": (_I, [C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtCamera),
                           C.POINTER(RtFrame), _I, _I, C.POINTER(RtReprojectOpts),
                           C.POINTER(RtFrame)]),

@@ -30,7 +30,8 @@
 //
 // Feature buffers (rt_accum_set_features): a second allocation, alive only while
 // features are on, of the FeatPlanes sums (rt_host_units.h; 56 B per pixel for the guides group,
-// 52 B for the emit group) and 56 B per pixel of staging for rt_accum_resolve_aov.  A pass then
+// 52 B for the emit group, 4 B of scatter counts for RT_ACCUM_FEAT_MEDIA) and 56 B per pixel (60 B
+// with the scatter plane) of staging for rt_accum_resolve_aov.  A pass then
 // also runs rt_aov.hip's k_aov_fold for the same seed and pixels on the same stream;
 // k_feat_resolve<PX> maps the sums to the rt_aov / rt_aov_emit planes.
 #include <hip/hip_runtime.h>
@@ -175,6 +176,18 @@ __global__ __launch_bounds__(256) void k_feat_resolve(FeatPlanes F, uint32_t ss,
   if (out.emission) mean3(F.emission, out.emission);
   if (out.surface_albedo) mean3(F.surface_albedo, out.surface_albedo);
   if (out.coverage) out.coverage[lp] = den > 0.0 ? (float)((double)F.nlight[lp] / den) : 0.0f;
+}
+
+// The media mode's plane (RT_ACCUM_FEAT_MEDIA), a kernel of its own so that k_feat_resolve stays
+// the code it was: scatter = the pixel's scatter samples over its n_p * ss camera samples, as
+// coverage above; 0 without a pass.
+template <bool PX>
+__global__ __launch_bounds__(256) void k_scatter_resolve(const uint32_t* nscatter, uint32_t npix, uint32_t ss,
+                                                         Passes<PX> c, float* scatter) {
+  const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
+  if (lp >= npix) return;
+  const double den = (double)passes_of(c, lp) * (double)ss;
+  scatter[lp] = den > 0.0 ? (float)((double)nscatter[lp] / den) : 0.0f;
 }
 
 constexpr int kInfoBlocks = 256;  // at most: stage 2 is one block over the partials
@@ -389,7 +402,8 @@ struct rt_accum {
   rt::DeviceBuffer feat_buf;  // the enabled groups' planes | resolve staging
   size_t feat_state_bytes = 0;
   rt::FeatPlanes F{};
-  float* feat_stage = nullptr;  // [14][npix] floats: rt_accum_resolve_aov's planes in FeatOut's order
+  uint32_t* nscatter = nullptr;  // [npix] RT_ACCUM_FEAT_MEDIA: samples whose first event is a scatter (exact)
+  float* feat_stage = nullptr;  // [14][npix] floats: rt_accum_resolve_aov's planes in FeatOut's order, then scatter's
 };
 
 namespace rt {
@@ -421,7 +435,7 @@ int fold_pass(void* ctx, const Params& p, double scale, hipStream_t stream) {
                        px_counts(a, a->pass_map));
   }
   HIP_OK(hipGetLastError());
-  if (a->features) return aov_fold_enqueue(a->F, a->per_pixel || a->pass_map, a->pass_map, stream);
+  if (a->features) return aov_fold_enqueue(a->F, a->nscatter, a->per_pixel || a->pass_map, a->pass_map, stream);
   return RT_OK;
 }
 
@@ -551,8 +565,10 @@ size_t carve_features(rt_accum* a, uint32_t planes, void* base) {
     take(a->F.surface_albedo, 3 * n);
     take(a->F.nlight, n);
   }
+  a->nscatter = nullptr;
+  if (planes & RT_ACCUM_FEAT_MEDIA) take(a->nscatter, n);
   a->feat_state_bytes = off;
-  take(a->feat_stage, 14 * n);
+  take(a->feat_stage, (planes & RT_ACCUM_FEAT_MEDIA ? 15 : 14) * n);
   return off;
 }
 
@@ -561,6 +577,7 @@ void drop_features(rt_accum* a) {
   a->feat_buf.reset();
   a->features = 0;
   a->F = FeatPlanes{};
+  a->nscatter = nullptr;
   a->feat_stage = nullptr;
 }
 
@@ -596,9 +613,14 @@ int accum_resolve(rt_accum* a, float* rgb, float* var, bool host) {
   return RT_OK;
 }
 
-int accum_resolve_aov(rt_accum* a, const rt_aov* outp, const rt_aov_emit* emitp, bool host) {
-  const char* who = host ? "rt_accum_resolve_aov" : "rt_accum_resolve_aov_device";
+// media: the rt_accum_resolve_aov_media entries (mediap is required there)
+int accum_resolve_aov(rt_accum* a, const rt_aov* outp, const rt_aov_emit* emitp, const rt_aov_media* mediap,
+                      bool media, bool host) {
+  const char* who = media ? (host ? "rt_accum_resolve_aov_media" : "rt_accum_resolve_aov_media_device")
+                          : (host ? "rt_accum_resolve_aov" : "rt_accum_resolve_aov_device");
   if (!a) return set_error(RT_ERR_INVALID, "%s: null accumulator", who);
+  if (media && !mediap) return set_error(RT_ERR_INVALID, "%s: null media", who);
+  float* const uscat = media ? mediap->scatter : nullptr;
   const rt_aov no_out{nullptr, nullptr, nullptr, nullptr};
   const rt_aov_emit no_emit{nullptr, nullptr, nullptr};
   const rt_aov& o = outp ? *outp : no_out;
@@ -606,8 +628,10 @@ int accum_resolve_aov(rt_accum* a, const rt_aov* outp, const rt_aov_emit* emitp,
   if (o.material) return set_error(RT_ERR_INVALID, "%s: the accumulator keeps no material plane", who);
   void* const user[6] = {o.albedo, o.normal, o.depth, e.emission, e.surface_albedo, e.coverage};
   const bool guides = user[0] || user[1] || user[2], emit = user[3] || user[4] || user[5];
-  if (!guides && !emit) return set_error(RT_ERR_INVALID, "%s: no buffer wanted", who);
+  if (!guides && !emit && !uscat) return set_error(RT_ERR_INVALID, "%s: no buffer wanted", who);
   std::lock_guard<std::mutex> lk(a->mu);
+  if (uscat && !(a->features & RT_ACCUM_FEAT_MEDIA))
+    return set_error(RT_ERR_INVALID, "%s: the scatter plane is not enabled (rt_accum_set_features)", who);
   if ((guides && !(a->features & RT_ACCUM_FEAT_GUIDES)) || (emit && !(a->features & RT_ACCUM_FEAT_EMIT)))
     return set_error(RT_ERR_INVALID, "%s: the %s planes are not enabled (rt_accum_set_features)", who,
                      guides && !(a->features & RT_ACCUM_FEAT_GUIDES) ? "guide" : "emit");
@@ -622,13 +646,22 @@ int accum_resolve_aov(rt_accum* a, const rt_aov* outp, const rt_aov_emit* emitp,
   size_t off = 0;
   for (int i = 0; i < 6; off += floats[i++]) dev[i] = !user[i] ? nullptr : host ? a->feat_stage + off : (float*)user[i];
   const FeatOut fo{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5]};
-  if (a->per_pixel)
+  const bool planes = guides || emit;  // else: the scatter plane alone
+  if (planes && a->per_pixel)
     hipLaunchKernelGGL(k_feat_resolve<true>, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->F, a->ss,
                        px_counts(a), fo);
-  else
+  else if (planes)
     hipLaunchKernelGGL(k_feat_resolve<false>, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->F, a->ss,
                        Passes<false>{(uint32_t)a->passes}, fo);
+  float* const dscat = !uscat ? nullptr : host ? a->feat_stage + 14 * n : uscat;
+  if (dscat && a->per_pixel)
+    hipLaunchKernelGGL(k_scatter_resolve<true>, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->nscatter,
+                       a->npix, a->ss, px_counts(a), dscat);
+  else if (dscat)
+    hipLaunchKernelGGL(k_scatter_resolve<false>, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->nscatter,
+                       a->npix, a->ss, Passes<false>{(uint32_t)a->passes}, dscat);
   HIP_OK(hipGetLastError());
+  if (host && uscat) HIP_OK(hipMemcpyAsync(uscat, dscat, n * sizeof(float), hipMemcpyDeviceToHost, stream));
   for (int i = 0; host && i < 6; ++i)
     if (user[i]) HIP_OK(hipMemcpyAsync(user[i], dev[i], floats[i] * sizeof(float), hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
@@ -787,8 +820,10 @@ int rt_accum_reset(rt_accum* a) {
 int rt_accum_set_features(rt_accum* a, uint32_t planes) {
   using namespace rt;
   if (!a) return set_error(RT_ERR_INVALID, "rt_accum_set_features: null accumulator");
-  if (planes & ~(RT_ACCUM_FEAT_GUIDES | RT_ACCUM_FEAT_EMIT))
+  if (planes & ~(RT_ACCUM_FEAT_GUIDES | RT_ACCUM_FEAT_EMIT | RT_ACCUM_FEAT_MEDIA))
     return set_error(RT_ERR_INVALID, "rt_accum_set_features: unknown planes 0x%x", planes);
+  if (planes == RT_ACCUM_FEAT_MEDIA)
+    return set_error(RT_ERR_INVALID, "rt_accum_set_features: RT_ACCUM_FEAT_MEDIA modifies GUIDES / EMIT, it needs one");
   std::lock_guard<std::mutex> lk(a->mu);
   if (a->passes > 0)
     return set_error(RT_ERR_INVALID, "rt_accum_set_features: the accumulator holds %d passes (rt_accum_reset first)",
@@ -819,11 +854,21 @@ int rt_accum_get_features(rt_accum* a, uint32_t* planes) {
 }
 
 int rt_accum_resolve_aov(rt_accum* a, const rt_aov* out_host, const rt_aov_emit* emit_host) {
-  return rt::accum_resolve_aov(a, out_host, emit_host, true);
+  return rt::accum_resolve_aov(a, out_host, emit_host, nullptr, false, true);
 }
 
 int rt_accum_resolve_aov_device(rt_accum* a, const rt_aov* out_dev, const rt_aov_emit* emit_dev) {
-  return rt::accum_resolve_aov(a, out_dev, emit_dev, false);
+  return rt::accum_resolve_aov(a, out_dev, emit_dev, nullptr, false, false);
+}
+
+int rt_accum_resolve_aov_media(rt_accum* a, const rt_aov* out_host, const rt_aov_emit* emit_host,
+                               const rt_aov_media* media_host) {
+  return rt::accum_resolve_aov(a, out_host, emit_host, media_host, true, true);
+}
+
+int rt_accum_resolve_aov_media_device(rt_accum* a, const rt_aov* out_dev, const rt_aov_emit* emit_dev,
+                                      const rt_aov_media* media_dev) {
+  return rt::accum_resolve_aov(a, out_dev, emit_dev, media_dev, true, false);
 }
 
 int rt_accum_add(rt_accum* a, uint64_t seed, rt_stats* stats) {

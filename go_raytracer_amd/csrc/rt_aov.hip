@@ -10,7 +10,8 @@
 // BVH4, all read through L1/L2 here (a feature ray per sample is ~1/10 of a path: no LDS
 // scene cache).  The hit -> (p, n, material, u, v) evaluation restates shade_core's
 // (rt_path.h) without touching it: the fused kernels are sensitive to code generation
-// (DESIGN.md §9).  Constant media are not traced: they are transparent to this pass.
+// (DESIGN.md §9).  Constant media are not traced: they are transparent to this pass, unless the
+// media mode is asked for (below).
 //
 // k_aov<TREE, true> (rt_render_aov_emit): the emission split of DESIGN.md §15.  It also counts
 // the samples whose first hit is a front-facing light (L_j of rt_abi.h), sums their emission
@@ -18,7 +19,15 @@
 // instances are the instructions a separate kernel compiled to, the others differ from a
 // kernel without the AovEmit argument in kernel-argument offsets only.
 //
-// k_aov_fold<TREE, EMIT, PX>: the pass accumulator's feature fold (rt_accum.hip),
+// k_aov<TREE, EMIT, true> (rt_render_aov_media): the first EVENT of the sample.  The
+// media are laid over the closest world hit exactly as the render's vertex 0 lays them
+// (trace_media with the camera draw's spare word: the render's own free-flight draws); a sample
+// whose winner is a medium takes the phase material's albedo at the scatter point, no normal and
+// the scatter's depth, and is counted into the `scatter` plane.  The MEDIA = false instances are
+// the instructions they were (profiles/aov_media_device_code.txt); the dispatcher takes a MEDIA
+// instance only for a scene that has media.
+//
+// k_aov_fold<TREE, EMIT, PX, MEDIA>: the pass accumulator's feature fold (rt_accum.hip),
 // the same samples (aov_sample is the one text of both kernels) summed into the accumulator's
 // fp64 planes for all spp_sqrt^2 samples of a pass's seed, over a whole pass or its active pixels.
 #include <hip/hip_runtime.h>
@@ -29,6 +38,7 @@
 #include <algorithm>
 #include <chrono>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "rt_hip_util.h"
@@ -61,6 +71,22 @@ struct AovEmit {
   float* coverage;
 };
 
+// The media mode's buffer (rt_abi.h rt_aov_media), a device pointer, and the accumulator's scatter
+// counts (rt_accum.hip keeps them beside FeatPlanes).  They ride behind an argument the kernels
+// already take, so that the MEDIA = false kernels take exactly the arguments they took: a
+// trailing argument of an empty struct still occupies 8 bytes of the kernel-argument segment
+// and moves the hidden arguments (blockDim, which these kernels read) behind it.
+struct AovEmitMedia : AovEmit {
+  float* scatter;
+};
+struct FeatPlanesMedia : FeatPlanes {
+  uint32_t* nscatter;  // [npix], as nlight
+};
+template <bool MEDIA>
+using AovEmitArg = std::conditional_t<MEDIA, AovEmitMedia, AovEmit>;
+template <bool MEDIA>
+using FeatPlanesArg = std::conditional_t<MEDIA, FeatPlanesMedia, FeatPlanes>;
+
 // A pixel's sums over its samples, in fp32 registers in sample order
 struct AovSums {
   f3 asum, nsum;
@@ -68,9 +94,10 @@ struct AovSums {
   int32_t kind0;  // the material kind of sample 0's hit, -1 on a miss
   f3 esum, ssum;  // EMIT only, as nlight
   uint32_t nlight;
+  uint32_t nscatter;  // MEDIA only: the samples whose first event is a scatter in a medium
 };
 RT_D AovSums aov_sums_zero() {
-  return {mk3(0, 0, 0), mk3(0, 0, 0), 0.0f, -1, mk3(0, 0, 0), mk3(0, 0, 0), 0u};
+  return {mk3(0, 0, 0), mk3(0, 0, 0), 0.0f, -1, mk3(0, 0, 0), mk3(0, 0, 0), 0u, 0u};
 }
 
 // The camera ids of local pixel lp of the share, for `count` samples from sample 0
@@ -90,7 +117,9 @@ RT_D Ids aov_ids(const Params& P, uint32_t lp, uint32_t count) {
 // accumulator's feature fold (k_aov_fold).
 // TREE: 0 record loop (quad-only scenes: the media set's code, which covers the lean one),
 // 2 BVH2, 4 BVH4, 5 compressed BVH4 (any feature)
-template <int TREE, bool EMIT>
+// MEDIA: the first event, not the first surface: the render's vertex-0 trace_media on top of
+// the world hit (finish_hit's order: the triangle refinement, then the media)
+template <int TREE, bool EMIT, bool MEDIA>
 RT_D void aov_sample(const Params& P, const Ids& id, uint32_t j, const TravStack& ts, AovSums& s) {
   constexpr uint32_t FT = TREE == 0 ? (uint32_t)FT_MEDIA : (uint32_t)FT_ALL;
   const DevScene& sc = P.sc;
@@ -111,6 +140,11 @@ RT_D void aov_sample(const Params& P, const Ids& id, uint32_t j, const TravStack
     } while (tr.cur != TRAV_DONE);
   }
   Hit h = tr.best;
+  if constexpr (MEDIA) {
+    if (HAS(FT_TRI) && h.ref != PRIM_NONE && (h.ref >> 30) == PRIM_TRI)
+      refine_tri_hit(sc, h.ref & 0x3FFFFFFFu, o, d, h.t, h.u, h.v);
+    trace_media(P, o, d, time, 0.001f, id.gpix, j, 0u, rt_spare24(r), h);
+  }
   const uint32_t ref = h.ref;
   f3 alb = mk3(P.bg[0], P.bg[1], P.bg[2]), n = mk3(0, 0, 0);  // a miss: camera.go:300-302
   float depth = 0.0f;
@@ -118,8 +152,9 @@ RT_D void aov_sample(const Params& P, const Ids& id, uint32_t j, const TravStack
   bool lit = false;  // L_j
   if (ref != PRIM_NONE) {
     // finish_hit's refinements of the winning hit (no media, no trace)
-    if (HAS(FT_TRI) && (ref >> 30) == PRIM_TRI)
-      refine_tri_hit(sc, ref & 0x3FFFFFFFu, o, d, h.t, h.u, h.v);
+    if constexpr (!MEDIA)
+      if (HAS(FT_TRI) && (ref >> 30) == PRIM_TRI)
+        refine_tri_hit(sc, ref & 0x3FFFFFFFu, o, d, h.t, h.u, h.v);
     // shade_core's hit record: r.At(t) snapped onto the surface, the outward normal,
     // setFaceNormal (hittable.go:27-34), and the texture coordinates
     const float t = h.t;
@@ -128,7 +163,15 @@ RT_D void aov_sample(const Params& P, const Ids& id, uint32_t j, const TravStack
     const uint32_t type = ref >> 30, idx = ref & 0x3FFFFFFFu;
     f3 nout;
     int mat;
-    if (HAS(FT_SPHERE) && type == PRIM_SPHERE) {
+    const bool medium = MEDIA && type == PRIM_MEDIUM;
+    if (medium) {
+      // a scatter inside a volume, as shade_core takes a medium hit: p = r.At(t) as it is, the
+      // phase material at u = v = 0.  The reference's (1,0,0) normal (medium.go:162-166) is a
+      // placeholder: a volume has no shading normal, the guide gets none
+      nout = mk3(0, 0, 0);
+      mat = sc.media[idx].phase_mat;
+      u = v = 0.0f;
+    } else if (HAS(FT_SPHERE) && type == PRIM_SPHERE) {
       const F4 cr = sc.sph_cr[idx], mv = sc.sph_mv[idx];
       const f3 cc = xyz(cr) + xyz(mv) * time;
       const double cx = (double)cr.x + (double)time * (double)mv.x;
@@ -180,6 +223,7 @@ RT_D void aov_sample(const Params& P, const Ids& id, uint32_t j, const TravStack
     }
     const bool ff = dot(d, nout) < 0;
     n = ff ? nout : -nout;
+    if (medium) n = mk3(0, 0, 0);
     const DevMaterial M = sc.mats[mat];
     kind = M.kind;
     if (M.kind == RT_MAT_METAL) alb = xyz(M.albedo);
@@ -188,6 +232,7 @@ RT_D void aov_sample(const Params& P, const Ids& id, uint32_t j, const TravStack
     else alb = tex_value<FT>(sc, M.tex, u, v, p);
     depth = t * length(d);
     if constexpr (EMIT) lit = M.kind == RT_MAT_DIFFUSE_LIGHT && ff;
+    if constexpr (MEDIA) s.nscatter += medium ? 1u : 0u;
   }
   if constexpr (EMIT) {
     if (lit) {
@@ -205,8 +250,8 @@ RT_D void aov_sample(const Params& P, const Ids& id, uint32_t j, const TravStack
   if (j == 0) s.kind0 = kind;
 }
 
-template <int TREE, bool EMIT>
-__global__ __launch_bounds__(256) void k_aov(Params P, AovOut out, AovEmit em) {
+template <int TREE, bool EMIT, bool MEDIA>
+__global__ __launch_bounds__(256) void k_aov(Params P, AovOut out, AovEmitArg<MEDIA> em) {
   constexpr uint32_t FT = TREE == 0 ? (uint32_t)FT_MEDIA : (uint32_t)FT_ALL;
   __shared__ uint32_t lstack[kShortStack * 256];
   if constexpr (HAS(FT_NOISE)) stage_perlin(P.sc);
@@ -217,7 +262,7 @@ __global__ __launch_bounds__(256) void k_aov(Params P, AovOut out, AovEmit em) {
   for (uint32_t lp = gtid; lp < P.npix; lp += stride) {
     const Ids id = aov_ids(P, lp, out.n);
     AovSums s = aov_sums_zero();
-    for (uint32_t j = 0; j < out.n; ++j) aov_sample<TREE, EMIT>(P, id, j, ts, s);
+    for (uint32_t j = 0; j < out.n; ++j) aov_sample<TREE, EMIT, MEDIA>(P, id, j, ts, s);
     const float inv = 1.0f / (float)out.n;
     if (out.albedo) {
       out.albedo[3 * (size_t)lp + 0] = s.asum.x * inv;
@@ -246,6 +291,9 @@ __global__ __launch_bounds__(256) void k_aov(Params P, AovOut out, AovEmit em) {
       // 53 bits >= 2 * 24 + 2 make the second rounding innocuous, so nlight == n gives 1.0f
       if (em.coverage) em.coverage[lp] = (float)((double)s.nlight / (double)out.n);
     }
+    if constexpr (MEDIA) {  // as coverage: exactly 0 and exactly 1 at the ends
+      if (em.scatter) em.scatter[lp] = (float)((double)s.nscatter / (double)out.n);
+    }
   }
 }
 
@@ -256,8 +304,8 @@ __global__ __launch_bounds__(256) void k_aov(Params P, AovOut out, AovEmit em) {
 // pass casts the rays rt_accum_add(seed) casts for that pixel.  One writer per pixel, no
 // atomics; count[] is k_accum_fold's.  v < P.npix <= F.npix and map[v] < F.npix (the
 // compaction's sorted list of local pixels), so every store is inside its plane.
-template <int TREE, bool EMIT, bool PX>
-__global__ __launch_bounds__(256) void k_aov_fold(Params P, FeatPlanes F, const uint32_t* map) {
+template <int TREE, bool EMIT, bool PX, bool MEDIA>
+__global__ __launch_bounds__(256) void k_aov_fold(Params P, FeatPlanesArg<MEDIA> F, const uint32_t* map) {
   constexpr uint32_t FT = TREE == 0 ? (uint32_t)FT_MEDIA : (uint32_t)FT_ALL;
   __shared__ uint32_t lstack[kShortStack * 256];
   if constexpr (HAS(FT_NOISE)) stage_perlin(P.sc);
@@ -271,7 +319,7 @@ __global__ __launch_bounds__(256) void k_aov_fold(Params P, FeatPlanes F, const 
     if constexpr (PX) p = map ? map[v] : v;
     const Ids id = aov_ids(P, p, P.ss);
     AovSums s = aov_sums_zero();
-    for (uint32_t j = 0; j < P.ss; ++j) aov_sample<TREE, EMIT>(P, id, j, ts, s);
+    for (uint32_t j = 0; j < P.ss; ++j) aov_sample<TREE, EMIT, MEDIA>(P, id, j, ts, s);
     if (F.albedo) {  // the guides group
       F.albedo[p] += (double)s.asum.x;
       F.albedo[n + p] += (double)s.asum.y;
@@ -290,6 +338,7 @@ __global__ __launch_bounds__(256) void k_aov_fold(Params P, FeatPlanes F, const 
       F.surface_albedo[2 * n + p] += (double)s.ssum.z;
       F.nlight[p] += s.nlight;
     }
+    if constexpr (MEDIA) F.nscatter[p] += s.nscatter;
   }
 }
 
@@ -303,18 +352,36 @@ DeviceScratch g_stacks, g_stage;
 // no stream is released while the runtime unloads.
 std::vector<Stream>& g_streams = *new std::vector<Stream>();
 
+// scatter: the media mode's plane, null for the kernels without it
 template <int TREE>
-void launch_aov(bool split, dim3 grid, hipStream_t stream, const Params& p, const AovOut& ao, const AovEmit& ae) {
-  if (split) hipLaunchKernelGGL((k_aov<TREE, true>), grid, dim3(256), 0, stream, p, ao, ae);
-  else hipLaunchKernelGGL((k_aov<TREE, false>), grid, dim3(256), 0, stream, p, ao, ae);
+void launch_aov(bool split, dim3 grid, hipStream_t stream, const Params& p, const AovOut& ao, const AovEmit& ae,
+                bool media, float* scatter) {
+  const dim3 b(256);
+  AovEmitMedia md;
+  (AovEmit&)md = ae;
+  md.scatter = scatter;
+  if (media && split) hipLaunchKernelGGL((k_aov<TREE, true, true>), grid, b, 0, stream, p, ao, md);
+  else if (media) hipLaunchKernelGGL((k_aov<TREE, false, true>), grid, b, 0, stream, p, ao, md);
+  else if (split) hipLaunchKernelGGL((k_aov<TREE, true, false>), grid, b, 0, stream, p, ao, ae);
+  else hipLaunchKernelGGL((k_aov<TREE, false, false>), grid, b, 0, stream, p, ao, ae);
 }
 
-// split: the rt_render_aov_emit entries (outp may be null, emitp is required); else emitp is null
+// split: the rt_render_aov_emit entries (outp may be null, emitp is required); else emitp is null.
+// mediap: the rt_render_aov_media entries (required there; outp and emitp may be null), which
+// are the split ones when emitp is given
 int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
-             const rt_aov* outp, const rt_aov_emit* emitp, bool split, bool host, rt_stats* stats) {
+             const rt_aov* outp, const rt_aov_emit* emitp, const rt_aov_media* mediap, bool split, bool media,
+             bool host, rt_stats* stats) {
   if (!scene || !cam) return set_error(RT_ERR_INVALID, "rt_render_aov: null scene/camera");
   const rt_aov no_out{nullptr, nullptr, nullptr, nullptr};
-  if (split) {
+  if (media) {
+    if (!mediap) return set_error(RT_ERR_INVALID, "rt_render_aov_media: null media");
+    if (!outp) outp = &no_out;
+    split = emitp != nullptr;
+    if (!outp->albedo && !outp->normal && !outp->depth && !outp->material && !mediap->scatter &&
+        !(emitp && (emitp->emission || emitp->surface_albedo || emitp->coverage)))
+      return set_error(RT_ERR_INVALID, "rt_render_aov_media: no buffer wanted");
+  } else if (split) {
     if (!emitp) return set_error(RT_ERR_INVALID, "rt_render_aov_emit: null emit");
     if (!outp) outp = &no_out;
     if (!outp->albedo && !outp->normal && !outp->depth && !outp->material && !emitp->emission &&
@@ -374,13 +441,13 @@ int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, 
     const struct {
       void* user;
       size_t bytes;
-    } planes[7] = {{outp->albedo, 3 * (size_t)npix * 4},     {outp->normal, 3 * (size_t)npix * 4},
+    } planes[8] = {{outp->albedo, 3 * (size_t)npix * 4},     {outp->normal, 3 * (size_t)npix * 4},
                    {outp->depth, (size_t)npix * 4},          {outp->material, (size_t)npix * 4},
                    {em.emission, 3 * (size_t)npix * 4},      {em.surface_albedo, 3 * (size_t)npix * 4},
-                   {em.coverage, (size_t)npix * 4}};
-    const int n_planes = split ? 7 : 4;
-    void* dev[7];  // where the kernel writes: the caller's device buffer or the plane's staging slot
-    for (int i = 0; i < 7; ++i) dev[i] = host ? nullptr : planes[i].user;
+                   {em.coverage, (size_t)npix * 4},          {media ? mediap->scatter : nullptr, (size_t)npix * 4}};
+    const int n_planes = media ? 8 : split ? 7 : 4;
+    void* dev[8];  // where the kernel writes: the caller's device buffer or the plane's staging slot
+    for (int i = 0; i < 8; ++i) dev[i] = host ? nullptr : planes[i].user;
     if (host) {  // one scratch buffer; an absent plane keeps its slot
       size_t total = 0;
       for (int i = 0; i < n_planes; ++i) total += planes[i].bytes;
@@ -393,11 +460,15 @@ int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, 
     const AovOut ao{(float*)dev[0], (float*)dev[1], (float*)dev[2], (int32_t*)dev[3], n};
     const AovEmit ae{(float*)dev[4], (float*)dev[5], (float*)dev[6]};
     const dim3 g((unsigned)blocks);
+    // a scene without media: the kernels without the mode (rt_render_aov_emit's bits), scatter = 0
+    const bool mk = media && view.sc.n_media > 0;
+    float* const scat = (float*)dev[7];
+    if (media && !mk && scat) HIP_OK(hipMemsetAsync(scat, 0, planes[7].bytes, stream));
     switch (view.tree) {
-      case 0: launch_aov<0>(split, g, stream, p, ao, ae); break;
-      case 2: launch_aov<2>(split, g, stream, p, ao, ae); break;
-      case 5: launch_aov<5>(split, g, stream, p, ao, ae); break;
-      default: launch_aov<4>(split, g, stream, p, ao, ae); break;
+      case 0: launch_aov<0>(split, g, stream, p, ao, ae, mk, scat); break;
+      case 2: launch_aov<2>(split, g, stream, p, ao, ae, mk, scat); break;
+      case 5: launch_aov<5>(split, g, stream, p, ao, ae, mk, scat); break;
+      default: launch_aov<4>(split, g, stream, p, ao, ae, mk, scat); break;
     }
     HIP_OK(hipGetLastError());
     for (int k = 0; host && k < n_planes; ++k) {
@@ -427,15 +498,28 @@ int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, 
 struct {
   Params p;
   int tree, blocks;
+  bool has_media;
 } g_fold;
 
-template <int TREE>
-void launch_fold(bool emit, bool px, hipStream_t stream, const FeatPlanes& F, const uint32_t* map) {
+template <int TREE, bool MEDIA>
+void launch_fold(bool emit, bool px, hipStream_t stream, const FeatPlanesArg<MEDIA>& F, const uint32_t* map) {
   const dim3 g((unsigned)g_fold.blocks), b(256);
-  if (emit && px) hipLaunchKernelGGL((k_aov_fold<TREE, true, true>), g, b, 0, stream, g_fold.p, F, map);
-  else if (emit) hipLaunchKernelGGL((k_aov_fold<TREE, true, false>), g, b, 0, stream, g_fold.p, F, map);
-  else if (px) hipLaunchKernelGGL((k_aov_fold<TREE, false, true>), g, b, 0, stream, g_fold.p, F, map);
-  else hipLaunchKernelGGL((k_aov_fold<TREE, false, false>), g, b, 0, stream, g_fold.p, F, map);
+  if (emit && px) hipLaunchKernelGGL((k_aov_fold<TREE, true, true, MEDIA>), g, b, 0, stream, g_fold.p, F, map);
+  else if (emit) hipLaunchKernelGGL((k_aov_fold<TREE, true, false, MEDIA>), g, b, 0, stream, g_fold.p, F, map);
+  else if (px) hipLaunchKernelGGL((k_aov_fold<TREE, false, true, MEDIA>), g, b, 0, stream, g_fold.p, F, map);
+  else hipLaunchKernelGGL((k_aov_fold<TREE, false, false, MEDIA>), g, b, 0, stream, g_fold.p, F, map);
+}
+
+template <int TREE>
+void launch_fold(bool emit, bool px, hipStream_t stream, const FeatPlanes& F, const uint32_t* map, uint32_t* nscatter) {
+  if (nscatter) {
+    FeatPlanesMedia fm;
+    (FeatPlanes&)fm = F;
+    fm.nscatter = nscatter;
+    launch_fold<TREE, true>(emit, px, stream, fm, map);
+  } else {
+    launch_fold<TREE, false>(emit, px, stream, F, map);
+  }
 }
 
 }  // namespace
@@ -462,17 +546,20 @@ int aov_fold_begin(rt_scene* scene, const rt_camera_derived& cd, const rt_render
   g_fold.p.stack_cols = cols;
   g_fold.tree = view.tree;
   g_fold.blocks = blocks;
+  g_fold.has_media = view.sc.n_media > 0;
   lk.release();  // held until aov_fold_end
   return RT_OK;
 }
 
-int aov_fold_enqueue(const FeatPlanes& F, bool px, const uint32_t* map, hipStream_t stream) {
+int aov_fold_enqueue(const FeatPlanes& F, uint32_t* nscatter, bool px, const uint32_t* map, hipStream_t stream) {
   const bool emit = F.emission != nullptr;
+  // a scene without media: the kernels without the mode, the counts stay 0
+  uint32_t* const ns = g_fold.has_media ? nscatter : nullptr;
   switch (g_fold.tree) {
-    case 0: launch_fold<0>(emit, px, stream, F, map); break;
-    case 2: launch_fold<2>(emit, px, stream, F, map); break;
-    case 5: launch_fold<5>(emit, px, stream, F, map); break;
-    default: launch_fold<4>(emit, px, stream, F, map); break;
+    case 0: launch_fold<0>(emit, px, stream, F, map, ns); break;
+    case 2: launch_fold<2>(emit, px, stream, F, map, ns); break;
+    case 5: launch_fold<5>(emit, px, stream, F, map, ns); break;
+    default: launch_fold<4>(emit, px, stream, F, map, ns); break;
   }
   HIP_OK(hipGetLastError());
   return RT_OK;
@@ -486,23 +573,35 @@ extern "C" {
 
 int rt_render_aov(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
                   const rt_aov* out_host, rt_stats* stats) {
-  return rt::aov_impl(s, cam, opts, n_samples, out_host, nullptr, false, true, stats);
+  return rt::aov_impl(s, cam, opts, n_samples, out_host, nullptr, nullptr, false, false, true, stats);
 }
 
 int rt_render_aov_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
                          int32_t n_samples, const rt_aov* out_device, rt_stats* stats) {
-  return rt::aov_impl(s, cam, opts, n_samples, out_device, nullptr, false, false, stats);
+  return rt::aov_impl(s, cam, opts, n_samples, out_device, nullptr, nullptr, false, false, false, stats);
 }
 
 int rt_render_aov_emit(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
                        const rt_aov* out_host, const rt_aov_emit* emit_host, rt_stats* stats) {
-  return rt::aov_impl(s, cam, opts, n_samples, out_host, emit_host, true, true, stats);
+  return rt::aov_impl(s, cam, opts, n_samples, out_host, emit_host, nullptr, true, false, true, stats);
 }
 
 int rt_render_aov_emit_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
                               int32_t n_samples, const rt_aov* out_device,
                               const rt_aov_emit* emit_device, rt_stats* stats) {
-  return rt::aov_impl(s, cam, opts, n_samples, out_device, emit_device, true, false, stats);
+  return rt::aov_impl(s, cam, opts, n_samples, out_device, emit_device, nullptr, true, false, false, stats);
+}
+
+int rt_render_aov_media(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
+                        const rt_aov* out_host, const rt_aov_emit* emit_host, const rt_aov_media* media_host,
+                        rt_stats* stats) {
+  return rt::aov_impl(s, cam, opts, n_samples, out_host, emit_host, media_host, false, true, true, stats);
+}
+
+int rt_render_aov_media_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
+                               int32_t n_samples, const rt_aov* out_device, const rt_aov_emit* emit_device,
+                               const rt_aov_media* media_device, rt_stats* stats) {
+  return rt::aov_impl(s, cam, opts, n_samples, out_device, emit_device, media_device, false, true, false, stats);
 }
 
 }  // extern "C"

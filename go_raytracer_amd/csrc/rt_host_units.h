@@ -68,9 +68,11 @@ struct FeatPlanes {
 // o.device and the overflow-stack scratch for a pass of n_pass pixels; on RT_OK it holds the
 // feature pass's mutex until aov_fold_end (after the pass's stream is synchronised).  Between
 // the two, aov_fold_enqueue launches k_aov_fold on `stream` for o.seed: the pass's pixel v is
-// pixel map[v] of the share (px), or v when map is null.
+// pixel map[v] of the share (px), or v when map is null.  nscatter (null: off): the media mode
+// (RT_ACCUM_FEAT_MEDIA), the sums become first-event sums and the pass's scatter samples are
+// counted into nscatter[F.npix]; for a scene without media the plain kernels run.
 int aov_fold_begin(rt_scene* scene, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t n_pass);
-int aov_fold_enqueue(const FeatPlanes& F, bool px, const uint32_t* map, hipStream_t stream);
+int aov_fold_enqueue(const FeatPlanes& F, uint32_t* nscatter, bool px, const uint32_t* map, hipStream_t stream);
 void aov_fold_end();
 
 }  // namespace rt

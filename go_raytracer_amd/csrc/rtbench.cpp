@@ -48,7 +48,12 @@
 // links no HIP runtime to own device buffers with; the statistics line gains "temporal": 1 and
 // ms_reproject), -temporal-emit (as -temporal, and needs -split-emitters too, else a usage error: the
 // stage runs through rt_reproject_emit with the accumulator's emission and coverage, which are kept
-// with the history; the statistics line also gains "temporal_emit": 1), -counts FILE (with -adaptive: the passes per pixel as grey, count / max).  -cpuprofile has no pprof to drive on the GPU path: the file
+// with the history; the statistics line also gains "temporal_emit": 1), -aov-media (with -aov, -denoise[-var] or
+// -accum-features, else a usage error: the feature buffers are of the samples' first EVENTS, constant
+// media traced as the render's camera vertex traces them, through rt_render_aov_media or an accumulator
+// with RT_ACCUM_FEAT_MEDIA; -aov also writes PREFIX_scatter.ppm, the scatter fraction as grey; the
+// statistics line gains "aov_media": 1; without the flag every byte written is what it was),
+// -counts FILE (with -adaptive: the passes per pixel as grey, count / max).  -cpuprofile has no pprof to drive on the GPU path: the file
 // receives the same JSON statistics instead.
 #include <unistd.h>
 
@@ -84,7 +89,7 @@ struct Args {
   bool adaptive_set = false;
   unsigned long long seed = 1, tree_seed = 1;
   bool progress = false, stats = false, denoise = false, denoise_var = false, split_emitters = false;
-  bool accum_features = false, temporal = false, temporal_emit = false;
+  bool accum_features = false, temporal = false, temporal_emit = false, aov_media = false;
   long long frames = 0;
   double orbit = 0.0;
 };
@@ -98,6 +103,8 @@ std::vector<Flag> flags(Args& a) {
        Flag::BOOL, &a.accum_features, ""},
       {"adaptive", "adaptive passes: after the first whole passes, resample only the tiles whose relative error is > E (at most -passes, default 1024)",
        Flag::F64, &a.adaptive, ""},
+      {"aov-media", "with -aov, -denoise[-var] or -accum-features: trace constant media in the feature buffers (first-event guides); -aov also writes PREFIX_scatter.ppm",
+       Flag::BOOL, &a.aov_media, ""},
       {"aov", "write PREFIX_albedo.ppm, PREFIX_normal.ppm and PREFIX_depth.ppm (first-hit feature buffers)",
        Flag::STR, &a.aov, ""},
       {"assets", "directory holding earthmap.jpg / dragon.obj (default: <exe dir>/../assets)",
@@ -268,11 +275,12 @@ std::string stats_json(const rt_stats& st, const rt_camera_derived& d, const cha
                        const rt_accum_info* acc, double ms_accum, bool denoise_var,
                        const rt_adapt_info* ad = nullptr, bool split_emitters = false,
                        bool accum_features = false, int frame = -1, bool temporal = false,
-                       double ms_reproject = 0.0, bool temporal_emit = false) {
+                       double ms_reproject = 0.0, bool temporal_emit = false, bool aov_media = false) {
   char b[1280], extra[200] = "", extra2[200] = "", extra4[160] = "";
   if (frame >= 0) snprintf(extra4, sizeof extra4, "\"frame\": %d, ", frame);
   if (temporal) snprintf(extra4 + strlen(extra4), sizeof extra4 - strlen(extra4), "\"temporal\": 1, \"ms_reproject\": %.3f, ", ms_reproject);
   if (temporal_emit) snprintf(extra4 + strlen(extra4), sizeof extra4 - strlen(extra4), "\"temporal_emit\": 1, ");
+  if (aov_media) snprintf(extra4 + strlen(extra4), sizeof extra4 - strlen(extra4), "\"aov_media\": 1, ");
   const std::string extra3s = std::string(split_emitters ? "\"split_emitters\": 1, " : "") +
                               (accum_features ? "\"accum_features\": 1, " : "") + extra4;
   const char* extra3 = extra3s.c_str();
@@ -336,6 +344,11 @@ int main(int argc, char** argv) {
   }
   if (a.temporal_emit && !(a.split_emitters && a.accum_features && (a.passes > 0 || a.until > 0.0 || a.adaptive_set))) {
     fprintf(stderr, "-temporal-emit needs -split-emitters, -accum-features and -passes, -until or -adaptive\n");  // no emit planes
+    usage(argv[0], flags(a));
+    return 2;
+  }
+  if (a.aov_media && !(a.denoise || a.denoise_var || !a.aov.empty() || a.accum_features)) {  // no feature buffers
+    fprintf(stderr, "-aov-media needs -aov, -denoise, -denoise-var or -accum-features\n");
     usage(argv[0], flags(a));
     return 2;
   }
@@ -463,7 +476,8 @@ int main(int argc, char** argv) {
   if (accumulate && (rc = rt_accum_create(sc, &cam, &o, pass_cap, &acc)) != RT_OK)
     return fail("rt_accum_create", rc);
   if (a.accum_features &&
-      (rc = rt_accum_set_features(acc, RT_ACCUM_FEAT_GUIDES | (a.split_emitters ? RT_ACCUM_FEAT_EMIT : 0u))) != RT_OK)
+      (rc = rt_accum_set_features(acc, RT_ACCUM_FEAT_GUIDES | (a.split_emitters ? RT_ACCUM_FEAT_EMIT : 0u) |
+                                          (a.aov_media ? RT_ACCUM_FEAT_MEDIA : 0u))) != RT_OK)
     return fail("rt_accum_set_features", rc);
 
   bool counts_failed = false;
@@ -563,7 +577,16 @@ int main(int argc, char** argv) {
     std::vector<float> emission(a.split_emitters ? 3 * np : 0), salbedo(a.split_emitters ? 3 * np : 0),
         coverage(a.split_emitters ? np : 0);
     rt_aov_emit fe = {emission.data(), salbedo.data(), coverage.data()};
-    if (a.accum_features) {  // the guides of the passes' own samples: no feature pass
+    // -aov-media: the first-event buffers and the scatter plane
+    std::vector<float> scatter(a.aov_media ? np : 0);
+    const rt_aov_media fm = {scatter.data()};
+    if (a.aov_media && a.accum_features) {
+      if ((rc = rt_accum_resolve_aov_media(acc, &f, a.split_emitters ? &fe : nullptr, &fm)) != RT_OK)
+        return fail("rt_accum_resolve_aov_media", rc);
+    } else if (a.aov_media) {
+      if ((rc = rt_render_aov_media(sc, &cam, &o, aov_samples, &f, a.split_emitters ? &fe : nullptr, &fm, &sa)) != RT_OK)
+        return fail("rt_render_aov_media", rc);
+    } else if (a.accum_features) {  // the guides of the passes' own samples: no feature pass
       if ((rc = rt_accum_resolve_aov(acc, &f, a.split_emitters ? &fe : nullptr)) != RT_OK)
         return fail("rt_accum_resolve_aov", rc);
     } else if (a.split_emitters) {
@@ -645,6 +668,12 @@ int main(int argc, char** argv) {
           if (write_ppm(*e.second, d.width, d.height, fopen(path.c_str(), "wb"), path.c_str())) return 1;
         }
       }
+      if (a.aov_media) {  // the scatter fraction as grey
+        std::vector<float> simg(3 * np);
+        for (size_t i = 0; i < np; ++i) simg[3 * i] = simg[3 * i + 1] = simg[3 * i + 2] = scatter[i];
+        const std::string path = a.aov + "_scatter.ppm";
+        if (write_ppm(simg, d.width, d.height, fopen(path.c_str(), "wb"), path.c_str())) return 1;
+      }
     }
   }
 
@@ -653,7 +682,8 @@ int main(int argc, char** argv) {
   double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::string js = stats_json(st, d, scene, wall, aov_samples, ms_aov, ms_denoise, accumulate ? &ai : nullptr,
                               ms_accum, a.denoise_var, a.adaptive_set ? &adi : nullptr, a.split_emitters,
-                              a.accum_features, numbered ? frame : -1, a.temporal, ms_reproject, a.temporal_emit);
+                              a.accum_features, numbered ? frame : -1, a.temporal, ms_reproject, a.temporal_emit,
+                              a.aov_media);
   if (a.stats || a.denoise || a.denoise_var || a.temporal) fprintf(stderr, "%s\n", js.c_str());
   if (!a.cpuprofile.empty()) {
     FILE* p = fopen(a.cpuprofile.c_str(), "w");

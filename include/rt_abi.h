@@ -531,7 +531,7 @@ typedef struct {          /* any pointer may be NULL = not wanted */
  * RT_ERR_INVALID), material is sample 0's.  Rows follow opts->rank / nranks as
  * rt_render's.  The hit is the closest WORLD surface, evaluated as the render's shading
  * evaluates it; constant media are transparent to the feature pass (a smoke volume shows
- * the surface behind it).  Albedo: Lambertian / isotropic = the texture at the hit, metal =
+ * the surface behind it; rt_render_aov_media below traces them).  Albedo: Lambertian / isotropic = the texture at the hit, metal =
  * its albedo, dielectric = (1,1,1), diffuse light = its emission when front-facing else 0,
  * miss = the camera background.  Two calls give identical bits.  stats (may be NULL):
  * samples and segments count the feature rays, tree_width the structure traversed (the one
@@ -644,6 +644,46 @@ int rt_render_aov_emit(rt_scene* s, const rt_camera* cam, const rt_render_opts* 
 int rt_render_aov_emit_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
                               int32_t n_samples, const rt_aov* out_device,
                               const rt_aov_emit* emit_device, rt_stats* stats);
+
+/* ------------------------------------------------------------------------ */
+/* Media in the feature pass (DESIGN.md "Media in the feature pass"): the    */
+/* first EVENT of a camera sample, which in a constant medium is a scatter,  */
+/* not the surface behind it.  Opt-in and added without an ABI version       */
+/* change: detect by the symbols.                                            */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  float* scatter;           /* [rows][W]; may be NULL */
+} rt_aov_media;
+
+/* rt_render_aov_emit with the constant media traced.  The ray of sample j is rt_render_aov's and
+ * its closest world hit is found as there (triangle refinement included).  Then the media are
+ * laid over that hit exactly as the render's vertex 0 lays them: the free-flight draws are the
+ * render's own, a pure function of (seed, pixel, sample j, vertex 0, the spare word of the
+ * sample's camera draw), so the feature ray scatters exactly where the render's sample does.
+ * The first event of sample j is whichever is closer; let M_j be true when it is a medium.
+ *   M_j false: everything is as in rt_render_aov / rt_render_aov_emit for that sample.
+ *   M_j true:  material kind = the kind of the medium's phase material (RT_MAT_ISOTROPIC);
+ *              albedo = that material's texture at p = o + t d with u = v = 0, as the render's
+ *              shading evaluates a medium hit; normal = (0, 0, 0), a volume has no shading
+ *              normal; depth = t |d|; L_j = false, E_j = 0, A_j = the albedo.
+ *   scatter  = (float)count(M_j) / (float)n, a true division as coverage's: exactly 0 where no
+ *              sample scattered, exactly 1 where all did.
+ * The buffers are means over samples 0 .. n-1 summed in fp32 in sample order, material is
+ * sample 0's.  A miss behind a scatter is a medium event (depth > 0, the albedo is not the
+ * background).  A pixel none of whose samples scattered has rt_render_aov's bits.  Two calls give
+ * identical bits.  For a scene without media the call runs rt_render_aov_emit's kernels: every
+ * plane has that call's bits and scatter is 0.
+ * media must not be NULL (it selects the mode); out and emit may be NULL; RT_ERR_INVALID when no
+ * buffer at all is wanted (every argument check comes before any device is touched).  Otherwise
+ * the rules, the structures traversed and the stats are rt_render_aov's: segments count the
+ * feature rays, not the media tests. */
+int rt_render_aov_media(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
+                        int32_t n_samples, const rt_aov* out_host, const rt_aov_emit* emit_host,
+                        const rt_aov_media* media_host, rt_stats* stats);
+int rt_render_aov_media_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
+                               int32_t n_samples, const rt_aov* out_device,
+                               const rt_aov_emit* emit_device, const rt_aov_media* media_device,
+                               rt_stats* stats);
 
 /* rt_denoise / rt_denoise_var in split mode: the emission is subtracted before the filter and
  * added back after it, and the filter demodulates by the albedo of the surfaces the pixel
@@ -808,13 +848,29 @@ int rt_accum_adapt_info(rt_accum* a, rt_adapt_info* out);
  * coverage always).  Any pointer may be NULL, emit may be NULL; RT_ERR_INVALID when a group is
  * asked for that is not enabled, when out->material is not NULL (no material plane is kept:
  * "the kind of sample 0" has no meaning over several passes) or when no buffer is wanted.
- * _device: pointers on the accumulator's device; both forms return after the work completes. */
+ * _device: pointers on the accumulator's device; both forms return after the work completes.
+ *
+ * RT_ACCUM_FEAT_MEDIA modifies GUIDES / EMIT (alone it is RT_ERR_INVALID): the feature rays are
+ * rt_render_aov_media's, so the groups' sums become first-event sums, and the scatter samples of
+ * every pixel are counted into an exact integer, 4 more bytes per pixel and 4 of staging.
+ * rt_accum_resolve_aov on such an accumulator returns the first-event planes.
+ * rt_accum_resolve_aov_media is rt_accum_resolve_aov with the scatter plane,
+ * scatter = (float)(scatter samples / N) as coverage; media must not be NULL, media->scatter may
+ * be; asking for scatter on an accumulator without the bit is RT_ERR_INVALID, and so is a call
+ * that wants no buffer.  One pass of seed s gives rt_render_aov_media(n_samples = spp_sqrt^2,
+ * seed s) as above; scatter always exactly. */
 #define RT_ACCUM_FEAT_GUIDES 1u   /* albedo, normal, depth */
 #define RT_ACCUM_FEAT_EMIT   2u   /* emission, surface_albedo, coverage */
+#define RT_ACCUM_FEAT_MEDIA  4u   /* modifies GUIDES / EMIT: their sums become first-event sums, and a
+                                     scatter count (an exact integer) is kept per pixel */
 int rt_accum_set_features(rt_accum* a, uint32_t planes);
 int rt_accum_get_features(rt_accum* a, uint32_t* planes);
 int rt_accum_resolve_aov(rt_accum* a, const rt_aov* out_host, const rt_aov_emit* emit_host);
 int rt_accum_resolve_aov_device(rt_accum* a, const rt_aov* out_dev, const rt_aov_emit* emit_dev);
+int rt_accum_resolve_aov_media(rt_accum* a, const rt_aov* out_host, const rt_aov_emit* emit_host,
+                               const rt_aov_media* media_host);
+int rt_accum_resolve_aov_media_device(rt_accum* a, const rt_aov* out_dev, const rt_aov_emit* emit_dev,
+                                      const rt_aov_media* media_dev);
 
 /* ------------------------------------------------------------------------ */
 /* Temporal reprojection (DESIGN.md "Temporal reprojection"): the previous   */

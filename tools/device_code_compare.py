@@ -12,7 +12,7 @@ status is 0 only if every kernel's resources and instructions are equal and the 
 sets match.  Block labels are compared without their function number, which depends only
 on a function's position in the module.  A kernel that became a template twin is compared with
 its parent under the parent's name: `k<false>(args, Twin<false>)` in the new tree pairs with a
-plain `k(args)` that only the parent has.
+plain `k(args)` that only the parent has, and `k<A, B, false>` with the parent's `k<A, B>`.
 """
 import os
 import re
@@ -113,10 +113,16 @@ def pair_twins(pres, nres, pins, nins, names):
     full = demangle(list(dict.fromkeys(list(pres) + list(nres))), cut=False)
     for nk in [k for k in nres if k not in pres]:
         nb, nt = base_name(full[nk])
-        if nt != "<false>":
+        # k<false> pairs with a plain k, k<A, B, false> with the parent's k<A, B>: a template that
+        # gained a last parameter, switched off
+        if nt == "<false>":
+            want = (nb, None)
+        elif nt and nt.endswith(", false>"):
+            want = (nb, nt[:-len(", false>")] + ">")
+        else:
             continue
         for pk in [k for k in pres if k not in nres]:
-            if base_name(full[pk]) == (nb, None):
+            if base_name(full[pk]) == want:
                 print(f"   twin: {names[nk]} against the parent's {names[pk]}")
                 pres[nk] = pres.pop(pk)
                 if pk in pins:  # under the new name, so that only the code can differ
