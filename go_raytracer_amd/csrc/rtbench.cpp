@@ -1,60 +1,23 @@
-// rtbench: the reference's command line (main.go:414-478) over the C ABI.
+// rtbench: the reference's command line (main.go:414-478) over the C ABI, and the ABI's one C client.
 //
 //   rtbench [-o image.ppm] [-N cores] [-S scene] [-cpuprofile file] [extensions]
 //
-// Same flags, defaults and effects as main.go: -S picks the scene function
-// (1 book1 .. 8 model, main.go:447-472; anything else is defaultScene, which
-// renders nothing, so the output file is created and left empty), -o names the
-// output file (created before the render, main.go:434-439), -N is
-// Camera.MaxThreads (the GPU path ignores it; kept in rt_camera.max_threads).
-// Flag syntax follows Go's flag package: -name value, -name=value, --name;
-// bool flags take no value; parsing stops at "--" or the first non-flag;
-// an unknown flag or a bad value prints the usage and exits 2, -h exits 0.
+// main.go's flags with Go's flag-package syntax and exits (usage + 2, -h 0); the output file is
+// created before anything renders and the default scene leaves it empty.  -h lists every flag
+// and README.md describes the extensions.  main() parses, validates (make_job), opens the output
+// and builds the scene (rt_tree_*, rt_demo_scene, rt_camera_derive, rt_scene_create); then every
+// frame goes through the stages:
 //
-// Extensions beyond main.go (defaults leave the reference scene unchanged):
-// -device, -width, -spp, -depth (camera overrides), -seed (render seed),
-// -tree-seed (the scene's rand seed), -mode auto|fused|wavefront, -assets DIR,
-// -progress (a progress line on stderr, the reference's bubbletea bar,
-// camera.go:106-108), -slices N (rt_progress granularity), -stats (one JSON
-// line of rt_stats on stderr), -denoise (feature pass at min(spp, 16) samples, then
-// the a-trous denoiser before the PPM is written; prints the statistics line with
-// both times), -denoise-var (the same with the variance-guided filter, rt_denoise_var, fed from
-// the pass accumulator's variance: needs -passes N >= 2 or -until; the statistics line gains
-// "denoise_var": 1), -split-emitters (with either: rt_render_aov_emit and the _emit filter, so
-// directly seen lights stay out of the filter; alone a usage error; -aov then also writes
-// PREFIX_emission.ppm and PREFIX_coverage.ppm; the statistics line gains "split_emitters": 1),
-// -aov PREFIX (writes PREFIX_albedo.ppm, PREFIX_normal.ppm as
-// n * 0.5 + 0.5 and PREFIX_depth.ppm normalised to the image maximum, through the
-// same PPM writer), -passes N (the image as the exact mean of N passes of -spp samples each,
-// seeds seed .. seed + N - 1, through the pass accumulator; -passes 1 writes the plain
-// render's bytes), -until E (stop once the accumulator's rel_error is <= E, checked from the
-// second pass on; at most -passes passes, 1024 without it).  With either, -progress reports
-// passes and the statistics line gains passes, rel_error and ms_accum.  -adaptive E (adaptive
-// passes: every pass is rt_accum_select + rt_accum_add_active, so whole passes while some pixel
-// has fewer than the library's min_passes, then passes over the tiles whose error figure is
-// above E only, until none is left or -passes, default 1024, is reached; composes with
-// -denoise[-var], -aov and -o; the statistics line gains active_last, samples_total and
-// samples_full), -accum-features (with -passes / -until / -adaptive: the accumulator keeps the
-// feature sums of its passes' own camera samples, rt_accum_set_features, and the denoisers and
-// -aov take those guides instead of a separate feature pass; without an accumulating flag a
-// usage error; the statistics line gains "accum_features": 1), -frames N -orbit DEG (N frames, frame k
-// with the camera's look_from turned about the vup axis through look_at by k * DEG degrees and written
-// to the -o name with _%03d before the extension, -aov's prefix with the same suffix; one statistics
-// line per frame, with "frame": k; without -temporal the frames are independent), -temporal (with
-// -accum-features and an accumulating flag, else a usage error: each frame's accumulator mean, variance
-// and guides go through rt_reproject against the history of the frames before it, every pixel of a frame
-// weighing its passes, before -denoise-var and the writer, and the result is the next frame's history;
-// the host entry, which stages through the device and gives rt_reproject_device's bits: this client
-// links no HIP runtime to own device buffers with; the statistics line gains "temporal": 1 and
-// ms_reproject), -temporal-emit (as -temporal, and needs -split-emitters too, else a usage error: the
-// stage runs through rt_reproject_emit with the accumulator's emission and coverage, which are kept
-// with the history; the statistics line also gains "temporal_emit": 1), -aov-media (with -aov, -denoise[-var] or
-// -accum-features, else a usage error: the feature buffers are of the samples' first EVENTS, constant
-// media traced as the render's camera vertex traces them, through rt_render_aov_media or an accumulator
-// with RT_ACCUM_FEAT_MEDIA; -aov also writes PREFIX_scatter.ppm, the scatter fraction as grey; the
-// statistics line gains "aov_media": 1; without the flag every byte written is what it was),
-// -counts FILE (with -adaptive: the passes per pixel as grey, count / max).  -cpuprofile has no pprof to drive on the GPU path: the file
-// receives the same JSON statistics instead.
+//   begin_frame     the frame's file names, its output file, the -orbit camera (no ABI call)
+//   render          rt_render, or an accumulator: rt_accum_create, rt_accum_set_features, per pass
+//                   rt_accum_add or rt_accum_select + rt_accum_add_active, rt_accum_info_get,
+//                   rt_accum_resolve, rt_accum_adapt_info, rt_accum_counts; rt_progress on a thread
+//   feature_planes  rt_render_aov[_emit|_media] or rt_accum_resolve_aov[_media]
+//   temporal_step   rt_reproject[_emit] (the host entries: this client links no HIP runtime)
+//   filter          rt_denoise[_var][_emit]
+//   write_aovs      rt_format_ppm per plane
+//   finish_frame    rt_format_ppm, the statistics line (-cpuprofile has no pprof to drive on the
+//                   GPU path: the file receives the same line), rt_accum_destroy
 #include <unistd.h>
 
 #include <atomic>
@@ -62,9 +25,11 @@
 #include <chrono>
 #include <cinttypes>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <utility>
@@ -147,9 +112,10 @@ std::vector<Flag> flags(Args& a) {
   };
 }
 
-void usage(const char* prog, const std::vector<Flag>& fl) {
+void usage(const char* prog) {
+  Args defaults;
   fprintf(stderr, "Usage of %s:\n", prog);
-  for (const Flag& f : fl) {
+  for (const Flag& f : flags(defaults)) {
     const char* ty = f.kind == Flag::STR ? " string" : f.kind == Flag::INT ? " int"
                      : f.kind == Flag::U64 ? " uint" : f.kind == Flag::F64 ? " float" : "";
     fprintf(stderr, "  -%s%s\n    \t%s", f.name, ty, f.usage);
@@ -195,6 +161,17 @@ bool set_value(const Flag& f, const std::string& v) {
   return false;
 }
 
+// every usage error: the message, the usage, exit code 2
+int usage_error(const char* prog, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vfprintf(stderr, fmt, ap);
+  va_end(ap);
+  fprintf(stderr, "\n");
+  usage(prog);
+  return 2;
+}
+
 // flag.FlagSet.Parse with ExitOnError: returns the exit code, or -1 to go on
 int parse(int argc, char** argv, Args& a) {
   std::vector<Flag> fl = flags(a);
@@ -205,52 +182,26 @@ int parse(int argc, char** argv, Args& a) {
     if (dashes == 2 && s.size() == 2) break;  // "--" terminates
     std::string name = s.substr(dashes), val;
     bool has_val = false;
-    if (name.empty() || name[0] == '-' || name[0] == '=') {
-      fprintf(stderr, "bad flag syntax: %s\n", s.c_str());
-      usage(argv[0], fl);
-      return 2;
-    }
+    if (name.empty() || name[0] == '-' || name[0] == '=') return usage_error(argv[0], "bad flag syntax: %s", s.c_str());
     size_t eq = name.find('=');
     if (eq != std::string::npos) val = name.substr(eq + 1), name = name.substr(0, eq), has_val = true;
     if (name == "h" || name == "help") {
-      usage(argv[0], fl);
+      usage(argv[0]);
       return 0;
     }
     const Flag* f = nullptr;
     for (const Flag& c : fl)
       if (name == c.name) f = &c;
-    if (!f) {
-      fprintf(stderr, "flag provided but not defined: -%s\n", name.c_str());
-      usage(argv[0], fl);
-      return 2;
-    }
+    if (!f) return usage_error(argv[0], "flag provided but not defined: -%s", name.c_str());
     if (f->kind == Flag::BOOL && !has_val) {
       val = "true";
     } else if (!has_val) {
-      if (i + 1 >= argc) {
-        fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
-        usage(argv[0], fl);
-        return 2;
-      }
+      if (i + 1 >= argc) return usage_error(argv[0], "flag needs an argument: -%s", name.c_str());
       val = argv[++i];
     }
-    if (!set_value(*f, val)) {
-      fprintf(stderr, "invalid value \"%s\" for flag -%s: parse error\n", val.c_str(),
-              name.c_str());
-      usage(argv[0], fl);
-      return 2;
-    }
+    if (!set_value(*f, val))
+      return usage_error(argv[0], "invalid value \"%s\" for flag -%s: parse error", val.c_str(), name.c_str());
     if (name == "adaptive") a.adaptive_set = true;
-  }
-  if (a.adaptive_set && !(a.adaptive > 0.0)) {
-    fprintf(stderr, "invalid value for flag -adaptive: the error threshold must be > 0\n");
-    usage(argv[0], fl);
-    return 2;
-  }
-  if (!a.counts.empty() && !a.adaptive_set) {
-    fprintf(stderr, "-counts needs -adaptive\n");
-    usage(argv[0], fl);
-    return 2;
   }
   return -1;
 }
@@ -265,52 +216,502 @@ std::string exe_dir() {
   return k == std::string::npos ? "." : p.substr(0, k);
 }
 
+// ---------------------------------------------------------------- the validated job ---
+enum class Features { NONE, PASS, ACCUM };  // where the feature planes come from
+enum class Filter { NONE, PLAIN, VAR };
+
+// What the run does, fixed before the output file exists; the stages read this, not the flags.
+struct Job {
+  Args a;  // the plain values: names, seeds, sizes
+  bool accumulate = false, adaptive = false, passes_ok = true;  // -passes / -until / -adaptive
+  int32_t pass_cap = 0;
+  Features source = Features::NONE;
+  bool accum_features = false, emit = false, media = false;  // the planes beyond the guides
+  Filter filter = Filter::NONE;
+  bool temporal = false, temporal_emit = false, want_var = false;
+  bool counts = false, aov = false, print_stats = false;
+  bool numbered = false;  // -frames: frame k goes to the -o name with _00k before the extension
+  int n_frames = 1;
+};
+
+// the "flag X needs flag Y" checks in their precedence: the first that fails is reported.
+// Returns the exit code, or -1 with `j` filled.
+int make_job(const Args& a, const char* prog, Job& j) {
+  const bool acc = a.passes > 0 || a.until > 0.0 || a.adaptive_set, filtered = a.denoise || a.denoise_var;
+  const struct { bool bad; const char* msg; } checks[] = {
+      {a.adaptive_set && !(a.adaptive > 0.0), "invalid value for flag -adaptive: the error threshold must be > 0"},
+      {!a.counts.empty() && !a.adaptive_set, "-counts needs -adaptive"},
+      // the variance comes from the passes: one pass has none
+      {a.denoise_var && !(a.passes >= 2 || ((a.until > 0.0 || a.adaptive_set) && a.passes == 0)),
+       "-denoise-var needs -passes N with N >= 2, or -until / -adaptive"},
+      {a.split_emitters && !filtered, "-split-emitters needs -denoise or -denoise-var"},  // nothing to split for
+      {a.accum_features && !acc, "-accum-features needs -passes, -until or -adaptive"},  // no accumulator to keep them
+      {a.temporal && !(a.accum_features && acc),  // no guides, no history
+       "-temporal needs -accum-features and -passes, -until or -adaptive"},
+      {a.temporal_emit && !(a.split_emitters && a.accum_features && acc),  // no emit planes
+       "-temporal-emit needs -split-emitters, -accum-features and -passes, -until or -adaptive"},
+      {a.aov_media && !(filtered || !a.aov.empty() || a.accum_features),  // no feature buffers
+       "-aov-media needs -aov, -denoise, -denoise-var or -accum-features"},
+      {a.frames < 0 || a.frames > 999 || !(a.orbit == a.orbit), "invalid value for flag -frames (0..999) / -orbit"},
+  };
+  for (const auto& c : checks)
+    if (c.bad) return usage_error(prog, "%s", c.msg);
+  j.a = a;
+  j.accumulate = acc;
+  j.adaptive = a.adaptive_set;
+  j.passes_ok = !(a.passes < 0 || a.passes > 0x7FFFFFFF || !(a.until >= 0.0));  // reported once the scene is built
+  j.pass_cap = (int32_t)(a.passes > 0 ? a.passes : 1024);
+  j.temporal_emit = a.temporal_emit;
+  j.temporal = a.temporal || a.temporal_emit;  // the same stage, through rt_reproject_emit
+  j.aov = !a.aov.empty();
+  if (filtered || j.aov || j.temporal) j.source = a.accum_features ? Features::ACCUM : Features::PASS;
+  j.accum_features = a.accum_features;
+  j.emit = a.split_emitters;
+  j.media = a.aov_media;
+  j.filter = a.denoise_var ? Filter::VAR : a.denoise ? Filter::PLAIN : Filter::NONE;
+  j.want_var = a.denoise_var || j.temporal;
+  j.counts = !a.counts.empty();
+  j.print_stats = a.stats || filtered || j.temporal;
+  j.numbered = a.frames > 0;
+  j.n_frames = j.numbered ? (int)a.frames : 1;
+  return -1;
+}
+
+std::string frame_name(const std::string& name, int k, bool before_ext) {
+  char tag[16];
+  snprintf(tag, sizeof tag, "_%03d", k);
+  const size_t slash = name.rfind('/'), dot = name.rfind('.');
+  const bool ext = before_ext && dot != std::string::npos && (slash == std::string::npos || dot > slash);
+  return ext ? name.substr(0, dot) + tag + name.substr(dot) : name + tag;
+}
+
+// ------------------------------------------------------------------- owned handles ---
+struct Release {
+  void operator()(rt_tree* p) const { rt_tree_destroy(p); }
+  void operator()(rt_scene* p) const { rt_scene_destroy(p); }
+  void operator()(rt_accum* p) const { rt_accum_destroy(p); }
+  void operator()(FILE* p) const { fclose(p); }
+};
+template <class T>
+using Owned = std::unique_ptr<T, Release>;
+
+// the last ABI call's name and code, for the one failure report
+struct Call {
+  const char* what = "";
+  int rc = RT_OK;
+  bool ok(const char* name, int code) {
+    what = name, rc = code;
+    return code == RT_OK;
+  }
+};
+
 int fail(const char* what, int rc) {
   fprintf(stderr, "rtbench: %s failed (%d): %s\n", what, rc, rt_last_error());
   return 1;
 }
 
-std::string stats_json(const rt_stats& st, const rt_camera_derived& d, const char* scene,
-                       double wall_s, int aov_samples, double ms_aov, double ms_denoise,
-                       const rt_accum_info* acc, double ms_accum, bool denoise_var,
-                       const rt_adapt_info* ad = nullptr, bool split_emitters = false,
-                       bool accum_features = false, int frame = -1, bool temporal = false,
-                       double ms_reproject = 0.0, bool temporal_emit = false, bool aov_media = false) {
-  char b[1280], extra[200] = "", extra2[200] = "", extra4[160] = "";
-  if (frame >= 0) snprintf(extra4, sizeof extra4, "\"frame\": %d, ", frame);
-  if (temporal) snprintf(extra4 + strlen(extra4), sizeof extra4 - strlen(extra4), "\"temporal\": 1, \"ms_reproject\": %.3f, ", ms_reproject);
-  if (temporal_emit) snprintf(extra4 + strlen(extra4), sizeof extra4 - strlen(extra4), "\"temporal_emit\": 1, ");
-  if (aov_media) snprintf(extra4 + strlen(extra4), sizeof extra4 - strlen(extra4), "\"aov_media\": 1, ");
-  const std::string extra3s = std::string(split_emitters ? "\"split_emitters\": 1, " : "") +
-                              (accum_features ? "\"accum_features\": 1, " : "") + extra4;
-  const char* extra3 = extra3s.c_str();
-  if (acc)  // -passes / -until
-    snprintf(extra, sizeof extra, "\"passes\": %d, \"rel_error\": %.6g, \"ms_accum\": %.3f, %s", acc->passes,
-             acc->rel_error, ms_accum, denoise_var ? "\"denoise_var\": 1, " : "");
-  if (acc && ad)  // -adaptive
-    snprintf(extra2, sizeof extra2, "\"active_last\": %" PRIu64 ", \"samples_total\": %" PRIu64
-             ", \"samples_full\": %" PRIu64 ", ", ad->active_pixels, ad->total_samples,
-             (uint64_t)acc->passes * (uint64_t)(d.spp_sqrt * d.spp_sqrt) * (uint64_t)d.width * (uint64_t)d.height);
-  snprintf(b, sizeof b,
-           "{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"spp\": %d, \"max_depth\": %d, "
-           "\"samples\": %" PRIu64 ", \"segments\": %" PRIu64 ", \"ms_render\": %.3f, "
-           "\"samples_per_s\": %.6g, \"mode\": %d, \"tree_width\": %d, \"chunk_samples\": %d, "
-           "\"aov_samples\": %d, \"ms_aov\": %.3f, \"ms_denoise\": %.3f, %s%s%s\"wall_s\": %.3f}",
-           scene, d.width, d.height, d.spp_sqrt * d.spp_sqrt, d.max_depth, st.samples,
-           st.segments, st.ms_total, st.ms_total > 0 ? st.samples / (st.ms_total * 1e-3) : 0.0,
-           st.mode, st.tree_width, st.chunk_samples, aov_samples, ms_aov, ms_denoise, extra, extra2, extra3, wall_s);
+double ms_since(std::chrono::steady_clock::time_point t) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+// The run and its current frame: what the stages work on.
+struct Ctx {
+  const char* scene = nullptr;
+  rt_scene* sc = nullptr;
+  rt_camera cam0, cam;  // the scene's camera, the frame's
+  rt_camera_derived d;
+  rt_render_opts o;
+  std::chrono::steady_clock::time_point t0;
+  int frame = 0;
+  std::string out_name, aov;  // the frame's image and -aov prefix
+  Owned<FILE> out;
+  Owned<rt_accum> acc;
+  std::vector<float> rgb, var, albedo, normal, depth, emission, salbedo, coverage, scatter;
+  rt_stats st;
+  rt_accum_info ai;
+  rt_adapt_info adi;
+  int aov_samples = 0;
+  double ms_accum = 0.0, ms_aov = 0.0, ms_denoise = 0.0, ms_reproject = 0.0;
+  // -temporal: the history (the frames before this one, reprojected and blended) and its camera
+  std::vector<float> h_rgb, h_var, h_count, h_normal, h_depth, h_emission, h_coverage, count;
+  rt_camera h_cam;
+  bool have_history = false;
+
+  size_t n_px() const { return (size_t)d.width * d.height; }
+  int spp() const { return d.spp_sqrt * d.spp_sqrt; }
+  rt_aov guides() { return {albedo.data(), normal.data(), depth.data(), nullptr}; }
+  rt_aov_emit emit_planes() { return {emission.data(), salbedo.data(), coverage.data()}; }
+};
+
+// -progress: a line on stderr while the frame renders; joined when the scope ends
+struct Progress {
+  std::atomic<bool> rendering{true};
+  std::atomic<int> pass_no{0};
+  std::thread bar;
+  Progress(const Job& j, const Ctx& c) {
+    if (!j.a.progress) return;
+    bar = std::thread([this, &j, &c] {
+      uint64_t done = 0, total = 0;
+      while (rendering.load()) {
+        if (rt_progress(c.sc, &done, &total) == RT_OK && total) {
+          if (j.accumulate)
+            fprintf(stderr, "\rrendering %s: pass %d of %d, %5.1f%%", c.scene, pass_no.load() + 1, j.pass_cap,
+                    100.0 * done / total);
+          else
+            fprintf(stderr, "\rrendering %s: %5.1f%%", c.scene, 100.0 * done / total);
+        }
+        std::this_thread::sleep_for(std::chrono::milliseconds(100));
+      }
+    });
+  }
+  void stop() {
+    rendering = false;
+    if (bar.joinable()) bar.join();
+  }
+  ~Progress() { stop(); }
+};
+
+// ---------------------------------------------------------------------- statistics ---
+struct Stats {
+  const rt_stats* st;
+  const rt_camera_derived* d;
+  const char* scene;
+  double wall_s, ms_aov, ms_denoise, ms_accum, ms_reproject;
+  int aov_samples;
+  const rt_accum_info* acc;    // -passes / -until / -adaptive, else null
+  const rt_adapt_info* adapt;  // -adaptive, else null
+  bool denoise_var, split_emitters, accum_features, temporal, temporal_emit, aov_media;
+  int frame;  // -frames, else -1
+};
+
+void appendf(std::string& s, const char* fmt, ...) {
+  va_list ap, ap2;
+  va_start(ap, fmt);
+  va_copy(ap2, ap);
+  const int n = vsnprintf(nullptr, 0, fmt, ap);
+  va_end(ap);
+  const size_t at = s.size();
+  s.resize(at + (size_t)n + 1);
+  vsnprintf(&s[at], (size_t)n + 1, fmt, ap2);
+  va_end(ap2);
+  s.resize(at + (size_t)n);
+}
+
+std::string stats_json(const Stats& s) {
+  const rt_stats& st = *s.st;
+  const rt_camera_derived& d = *s.d;
+  const int spp = d.spp_sqrt * d.spp_sqrt;
+  std::string b;
+  appendf(b, "{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"spp\": %d, \"max_depth\": %d, ", s.scene, d.width,
+          d.height, spp, d.max_depth);
+  appendf(b, "\"samples\": %" PRIu64 ", \"segments\": %" PRIu64 ", \"ms_render\": %.3f, \"samples_per_s\": %.6g, ",
+          st.samples, st.segments, st.ms_total, st.ms_total > 0 ? st.samples / (st.ms_total * 1e-3) : 0.0);
+  appendf(b, "\"mode\": %d, \"tree_width\": %d, \"chunk_samples\": %d, ", st.mode, st.tree_width, st.chunk_samples);
+  appendf(b, "\"aov_samples\": %d, \"ms_aov\": %.3f, \"ms_denoise\": %.3f, ", s.aov_samples, s.ms_aov, s.ms_denoise);
+  if (s.acc)
+    appendf(b, "\"passes\": %d, \"rel_error\": %.6g, \"ms_accum\": %.3f, ", s.acc->passes, s.acc->rel_error, s.ms_accum);
+  if (s.acc && s.denoise_var) b += "\"denoise_var\": 1, ";
+  if (s.acc && s.adapt)
+    appendf(b, "\"active_last\": %" PRIu64 ", \"samples_total\": %" PRIu64 ", \"samples_full\": %" PRIu64 ", ",
+            s.adapt->active_pixels, s.adapt->total_samples,
+            (uint64_t)s.acc->passes * (uint64_t)spp * (uint64_t)d.width * (uint64_t)d.height);
+  if (s.split_emitters) b += "\"split_emitters\": 1, ";
+  if (s.accum_features) b += "\"accum_features\": 1, ";
+  if (s.frame >= 0) appendf(b, "\"frame\": %d, ", s.frame);
+  if (s.temporal) appendf(b, "\"temporal\": 1, \"ms_reproject\": %.3f, ", s.ms_reproject);
+  if (s.temporal_emit) b += "\"temporal_emit\": 1, ";
+  if (s.aov_media) b += "\"aov_media\": 1, ";
+  appendf(b, "\"wall_s\": %.3f}", s.wall_s);
   return b;
 }
 
-// one image through the PPM writer (camera.go:160 + PrintColor) into `path`
-int write_ppm(const std::vector<float>& img, int w, int h, FILE* f, const char* path) {
+// ------------------------------------------------------------------------- writers ---
+// one image through the PPM writer (camera.go:160 + PrintColor) into `path`; `f` is closed
+int write_ppm(const std::vector<float>& img, int w, int h, Owned<FILE> f, const char* path) {
   int64_t n = rt_format_ppm(img.data(), w, h, nullptr, 0);
   std::vector<char> text((size_t)(n > 0 ? n : 0));
   if (n < 0 || rt_format_ppm(img.data(), w, h, text.data(), n) != n) return fail("rt_format_ppm", (int)n);
-  if (!f || fwrite(text.data(), 1, text.size(), f) != text.size() || fclose(f) != 0) {
+  if (!f || fwrite(text.data(), 1, text.size(), f.get()) != text.size() || fclose(f.release()) != 0) {
     fprintf(stderr, "rtbench: writing %s failed\n", path);
     return 1;
   }
+  return 0;
+}
+
+int write_ppm(const std::vector<float>& img, const Ctx& c, const std::string& path) {
+  return write_ppm(img, c.d.width, c.d.height, Owned<FILE>(fopen(path.c_str(), "wb")), path.c_str());
+}
+
+// a plane as a grey image, plane / scale (0 where the scale is not positive)
+std::vector<float> grey(const std::vector<float>& plane, float scale) {
+  std::vector<float> img(3 * plane.size());
+  for (size_t i = 0; i < plane.size(); ++i) img[3 * i] = img[3 * i + 1] = img[3 * i + 2] = scale > 0 ? plane[i] / scale : 0.0f;
+  return img;
+}
+
+// -------------------------------------------------------------------------- stages ---
+// Every stage returns the exit code that ends the run, or 0 to go on.
+
+// -orbit: look_from turned about the vup axis through look_at (Rodrigues' formula)
+rt_camera orbit_camera(const rt_camera& cam0, double degrees) {
+  rt_camera cam = cam0;
+  double from[3] = {0, 0, 0}, at[3] = {0, 0, -1}, up[3] = {0, 1, 0};
+  if (cam0.positioned)
+    for (int i = 0; i < 3; ++i) from[i] = cam0.look_from[i], at[i] = cam0.look_at[i], up[i] = cam0.vup[i];
+  const double th = degrees * M_PI / 180.0, co = cos(th), si = sin(th);
+  const double ul = sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
+  const double k[3] = {up[0] / ul, up[1] / ul, up[2] / ul};
+  const double v[3] = {from[0] - at[0], from[1] - at[1], from[2] - at[2]};
+  const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2];
+  const double kxv[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
+  for (int i = 0; i < 3; ++i) {
+    cam.look_from[i] = at[i] + (v[i] * co + kxv[i] * si + k[i] * kv * (1.0 - co));
+    cam.look_at[i] = at[i];
+    cam.vup[i] = up[i];
+  }
+  cam.positioned = 1;
+  return cam;
+}
+
+// the frame's names, its output file (frame 0's exists already) and its camera
+int begin_frame(const Job& j, Ctx& c, int frame) {
+  c.frame = frame;
+  c.aov_samples = 0;
+  c.ms_accum = c.ms_aov = c.ms_denoise = c.ms_reproject = 0.0;
+  c.out_name = j.numbered ? frame_name(j.a.out, frame, true) : j.a.out;
+  c.aov = j.numbered && j.aov ? frame_name(j.a.aov, frame, false) : j.a.aov;
+  if (frame > 0) c.out.reset(fopen(c.out_name.c_str(), "wb"));
+  if (!c.out) {
+    fprintf(stderr, "Error creating output file\n");
+    return 1;
+  }
+  c.cam = j.numbered ? orbit_camera(c.cam0, j.a.orbit * (double)frame) : c.cam0;
+  return 0;
+}
+
+// -passes / -until / -adaptive: passes into the accumulator until the cap, the target or no tile is left
+void add_passes(const Job& j, Ctx& c, std::atomic<int>& pass_no, Call& s) {
+  rt_adapt_opts ado;
+  memset(&ado, 0, sizeof ado);  // the library defaults: tile 8, min_passes 4, lum_floor 1e-2
+  ado.rel_error = j.a.adaptive;
+  for (int32_t p = 0; p < j.pass_cap; ++p) {
+    rt_stats sp;
+    pass_no = p;
+    if (j.adaptive) {  // the noisy tiles only (Accumulator.render_adaptive); every tile at first
+      uint64_t n_active = 0;
+      if (!s.ok("rt_accum_select", rt_accum_select(c.acc.get(), &ado, &n_active)) || n_active == 0) break;
+      if (!s.ok("rt_accum_add_active", rt_accum_add_active(c.acc.get(), j.a.seed + (uint64_t)p, &sp))) break;
+    } else if (!s.ok("rt_accum_add", rt_accum_add(c.acc.get(), j.a.seed + (uint64_t)p, &sp))) {
+      break;
+    }
+    const uint64_t samples = c.st.samples + sp.samples, segments = c.st.segments + sp.segments;
+    const double ms = c.st.ms_total + sp.ms_total;
+    c.st = sp;  // the last pass's, with the totals over the passes
+    c.st.samples = samples;
+    c.st.segments = segments;
+    c.st.ms_total = ms;
+    if (j.a.until > 0.0 && p >= 1 &&
+        (!s.ok("rt_accum_info_get", rt_accum_info_get(c.acc.get(), &c.ai)) || c.ai.rel_error <= j.a.until))
+      break;
+  }
+}
+
+// the accumulator's mean (and variance), its figures, and -counts: the passes per pixel as grey, count / max
+void resolve_passes(const Job& j, Ctx& c, Call& s, bool& counts_failed) {
+  if (s.ok("rt_accum_resolve", rt_accum_resolve(c.acc.get(), c.rgb.data(), j.want_var ? c.var.data() : nullptr)))
+    s.ok("rt_accum_resolve", rt_accum_info_get(c.acc.get(), &c.ai));
+  if (s.rc != RT_OK || !j.adaptive) return;
+  if (!s.ok("rt_accum_adapt_info", rt_accum_adapt_info(c.acc.get(), &c.adi)) || !j.counts) return;
+  std::vector<int32_t> cnt(c.n_px());
+  if (!s.ok("rt_accum_counts", rt_accum_counts(c.acc.get(), cnt.data()))) return;
+  counts_failed = write_ppm(grey(std::vector<float>(cnt.begin(), cnt.end()), (float)c.adi.max_count), c, j.a.counts) != 0;
+}
+
+// the frame's image: one render, or the accumulator's mean over the passes
+int render(const Job& j, Ctx& c) {
+  c.rgb.assign(3 * c.n_px(), 0.0f);
+  c.var.assign(j.want_var ? c.n_px() : 0, 0.0f);
+  memset(&c.st, 0, sizeof c.st);
+  memset(&c.ai, 0, sizeof c.ai);
+  memset(&c.adi, 0, sizeof c.adi);
+  Call s;
+  if (j.accumulate) {
+    rt_accum* acc = nullptr;
+    if (!s.ok("rt_accum_create", rt_accum_create(c.sc, &c.cam, &c.o, j.pass_cap, &acc))) return fail(s.what, s.rc);
+    c.acc.reset(acc);
+  }
+  const uint32_t planes = RT_ACCUM_FEAT_GUIDES | (j.emit ? RT_ACCUM_FEAT_EMIT : 0u) | (j.media ? RT_ACCUM_FEAT_MEDIA : 0u);
+  if (j.accum_features && !s.ok("rt_accum_set_features", rt_accum_set_features(c.acc.get(), planes)))
+    return fail(s.what, s.rc);
+
+  bool counts_failed = false;
+  Progress bar(j, c);
+  if (!j.accumulate) {
+    s.ok("rt_render", rt_render(c.sc, &c.cam, &c.o, c.rgb.data(), &c.st));
+  } else {
+    const auto tp = std::chrono::steady_clock::now();
+    add_passes(j, c, bar.pass_no, s);
+    if (s.rc == RT_OK) resolve_passes(j, c, s, counts_failed);
+    c.ms_accum = ms_since(tp);
+  }
+  bar.stop();
+  if (j.a.progress && j.accumulate)
+    fprintf(stderr, "\rrendering %s: %d passes, 100.0%%      \n", c.scene, c.ai.passes);
+  else if (j.a.progress)
+    fprintf(stderr, "\rrendering %s: 100.0%%\n", c.scene);
+  if (s.rc != RT_OK) return fail(s.what, s.rc);
+  return counts_failed ? 1 : 0;  // (reported by write_ppm)
+}
+
+// -denoise / -aov / -temporal: the feature planes of the same camera rays, from a feature pass at
+// min(spp, 16) samples or from the accumulator (the guides of every pass the pixel took)
+int feature_planes(const Job& j, Ctx& c) {
+  if (j.source == Features::NONE) return 0;
+  const size_t np = c.n_px();
+  c.albedo.assign(3 * np, 0.0f), c.normal.assign(3 * np, 0.0f), c.depth.assign(np, 0.0f);
+  c.emission.assign(j.emit ? 3 * np : 0, 0.0f), c.salbedo.assign(j.emit ? 3 * np : 0, 0.0f);
+  c.coverage.assign(j.emit ? np : 0, 0.0f), c.scatter.assign(j.media ? np : 0, 0.0f);
+  const bool pass = j.source == Features::PASS;
+  const int n = c.aov_samples = pass && c.spp() >= 16 ? 16 : c.spp();
+  const rt_aov f = c.guides();
+  const rt_aov_emit fe = c.emit_planes(), *split = j.emit ? &fe : nullptr;
+  const rt_aov_media fm = {c.scatter.data()};
+  rt_stats sa;
+  Call s;
+  const auto ta = std::chrono::steady_clock::now();
+  if (!pass && j.media)
+    s.ok("rt_accum_resolve_aov_media", rt_accum_resolve_aov_media(c.acc.get(), &f, split, &fm));
+  else if (!pass)
+    s.ok("rt_accum_resolve_aov", rt_accum_resolve_aov(c.acc.get(), &f, split));
+  else if (j.media)
+    s.ok("rt_render_aov_media", rt_render_aov_media(c.sc, &c.cam, &c.o, n, &f, split, &fm, &sa));
+  else if (j.emit)
+    s.ok("rt_render_aov_emit", rt_render_aov_emit(c.sc, &c.cam, &c.o, n, &f, &fe, &sa));
+  else
+    s.ok("rt_render_aov", rt_render_aov(c.sc, &c.cam, &c.o, n, &f, &sa));
+  c.ms_aov = ms_since(ta);
+  return s.rc == RT_OK ? 0 : fail(s.what, s.rc);
+}
+
+// -temporal: the history into this frame's camera, then this frame as the new history
+int temporal_step(const Job& j, Ctx& c) {
+  if (!j.temporal) return 0;
+  const auto tr = std::chrono::steady_clock::now();
+  const int w = c.d.width, h = c.d.height;
+  c.count.assign(c.n_px(), (float)c.ai.passes);
+  if (c.have_history) {
+    const rt_frame prev = {c.h_rgb.data(), c.h_var.data(), c.h_count.data(), c.h_normal.data(), c.h_depth.data(), 0.0f, 0};
+    const rt_frame cur = {c.rgb.data(), c.var.data(), nullptr, c.normal.data(), c.depth.data(), (float)c.ai.passes, 0};
+    const rt_frame res = {c.rgb.data(), c.var.data(), c.count.data(), nullptr, nullptr, 0.0f, 0};
+    const rt_aov_emit prev_emit = {c.h_emission.data(), nullptr, c.h_coverage.data()};
+    const rt_aov_emit cur_emit = {c.emission.data(), nullptr, c.coverage.data()};
+    Call s;
+    if (j.temporal_emit)
+      s.ok("rt_reproject_emit",
+           rt_reproject_emit(&c.h_cam, &prev, &prev_emit, &c.cam, &cur, &cur_emit, w, h, nullptr, &res));
+    else
+      s.ok("rt_reproject", rt_reproject(&c.h_cam, &prev, &c.cam, &cur, w, h, nullptr, &res));
+    if (s.rc != RT_OK) return fail(s.what, s.rc);
+  }
+  c.h_rgb = c.rgb, c.h_var = c.var, c.h_count = c.count, c.h_normal = c.normal, c.h_depth = c.depth;
+  if (j.temporal_emit) c.h_emission = c.emission, c.h_coverage = c.coverage;
+  c.h_cam = c.cam;
+  c.have_history = true;
+  c.ms_reproject = ms_since(tr);
+  return 0;
+}
+
+// -denoise / -denoise-var, with -split-emitters their _emit entries; in place, the library's defaults
+int filter(const Job& j, Ctx& c) {
+  if (j.filter == Filter::NONE) return 0;
+  const int w = c.d.width, h = c.d.height;
+  const rt_aov f = c.guides();
+  const rt_aov_emit fe = c.emit_planes();
+  float* rgb = c.rgb.data();
+  rt_denoise_var_opts vopt;
+  rt_denoise_opts dopt;
+  memset(&vopt, 0, sizeof vopt);
+  memset(&dopt, 0, sizeof dopt);
+  vopt.demodulate = dopt.demodulate = 1;
+  Call s;
+  const auto td = std::chrono::steady_clock::now();
+  if (j.filter == Filter::VAR && j.emit)
+    s.ok("rt_denoise_var_emit", rt_denoise_var_emit(rgb, c.var.data(), &f, &fe, w, h, &vopt, rgb, nullptr));
+  else if (j.filter == Filter::VAR)
+    s.ok("rt_denoise_var", rt_denoise_var(rgb, c.var.data(), &f, w, h, &vopt, rgb, nullptr));
+  else if (j.emit)
+    s.ok("rt_denoise_emit", rt_denoise_emit(rgb, &f, &fe, w, h, &dopt, rgb));
+  else
+    s.ok("rt_denoise", rt_denoise(rgb, &f, w, h, &dopt, rgb));
+  c.ms_denoise = ms_since(td);
+  return s.rc == RT_OK ? 0 : fail(s.what, s.rc);
+}
+
+// -aov: PREFIX_albedo, _normal as n * 0.5 + 0.5, _depth over the image maximum; the emission as it
+// is; coverage and scatter as grey
+int write_aovs(const Job& j, const Ctx& c) {
+  if (!j.aov) return 0;
+  float dmax = 0.0f;
+  for (float v : c.depth) dmax = v > dmax ? v : dmax;
+  std::vector<float> nimg(c.normal.size());
+  for (size_t i = 0; i < nimg.size(); ++i) nimg[i] = c.normal[i] * 0.5f + 0.5f;
+  const auto put = [&](const char* suffix, const std::vector<float>& img) { return write_ppm(img, c, c.aov + suffix); };
+  if (put("_albedo.ppm", c.albedo) || put("_normal.ppm", nimg) || put("_depth.ppm", grey(c.depth, dmax))) return 1;
+  if (j.emit && (put("_emission.ppm", c.emission) || put("_coverage.ppm", grey(c.coverage, 1.0f)))) return 1;
+  if (j.media && put("_scatter.ppm", grey(c.scatter, 1.0f))) return 1;
+  return 0;
+}
+
+// camera.go:160 header + PrintColor per pixel, then main.go:477's single write; the statistics
+int finish_frame(const Job& j, Ctx& c) {
+  if (write_ppm(c.rgb, c.d.width, c.d.height, std::move(c.out), c.out_name.c_str())) return 1;
+  const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - c.t0).count();
+  Stats s;
+  s.st = &c.st, s.d = &c.d, s.scene = c.scene, s.wall_s = wall;
+  s.ms_aov = c.ms_aov, s.ms_denoise = c.ms_denoise, s.ms_accum = c.ms_accum, s.ms_reproject = c.ms_reproject;
+  s.aov_samples = c.aov_samples;
+  s.acc = j.accumulate ? &c.ai : nullptr;
+  s.adapt = j.adaptive ? &c.adi : nullptr;
+  s.denoise_var = j.filter == Filter::VAR, s.split_emitters = j.emit, s.accum_features = j.accum_features;
+  s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.aov_media = j.media;
+  s.frame = j.numbered ? c.frame : -1;
+  const std::string js = stats_json(s);
+  if (j.print_stats) fprintf(stderr, "%s\n", js.c_str());
+  if (!j.a.cpuprofile.empty()) {
+    Owned<FILE> p(fopen(j.a.cpuprofile.c_str(), "w"));
+    if (!p) {
+      fprintf(stderr, "rtbench: cannot create %s\n", j.a.cpuprofile.c_str());
+      return 1;
+    }
+    fprintf(p.get(), "%s\n", js.c_str());
+  }
+  const int rc = c.acc ? rt_accum_destroy(c.acc.release()) : RT_OK;
+  return rc == RT_OK ? 0 : fail("rt_accum_destroy", rc);
+}
+
+// the scene function's tree, the camera with the overrides, the device scene
+int build_scene(const Job& j, Ctx& c, Owned<rt_tree>& tree, Owned<rt_scene>& sc) {
+  const Args& a = j.a;
+  std::string assets = a.assets.empty() ? exe_dir() + "/../assets" : a.assets;
+  if (a.assets.empty() && getenv("RT_ASSET_DIR")) assets = getenv("RT_ASSET_DIR");
+  rt_tree* t = nullptr;
+  Call s;
+  if (!s.ok("rt_tree_create", rt_tree_create(&t))) return fail(s.what, s.rc);
+  tree.reset(t);
+  rt_tree_seed(t, a.tree_seed);
+  rt_camera& cam = c.cam0;
+  memset(&cam, 0, sizeof cam);
+  int world = -1, lights = -1;
+  if (!s.ok("rt_demo_scene", rt_demo_scene(t, c.scene, assets.c_str(), &cam, &world, &lights))) return fail(s.what, s.rc);
+  cam.max_threads = (int32_t)a.N;
+  if (a.width > 0) cam.width = (int32_t)a.width;
+  if (a.spp > 0) cam.samples_per_pixel = (int32_t)a.spp;
+  if (a.depth > 0) cam.max_depth = (int32_t)a.depth;
+  if (!s.ok("rt_camera_derive", rt_camera_derive(&cam, &c.d))) return fail(s.what, s.rc);
+  rt_scene* scene = nullptr;
+  if (!s.ok("rt_scene_create", rt_scene_create(t, world, lights, &scene))) return fail(s.what, s.rc);
+  sc.reset(scene);
+  c.sc = scene;
   return 0;
 }
 
@@ -318,385 +719,55 @@ int write_ppm(const std::vector<float>& img, int w, int h, FILE* f, const char* 
 
 int main(int argc, char** argv) {
   Args a;
+  Job j;
   int rc = parse(argc, argv, a);
   if (rc >= 0) return rc;
-  auto t0 = std::chrono::steady_clock::now();
-  // the variance comes from the passes: one pass has none (checked before the file is created)
-  if (a.denoise_var && !(a.passes >= 2 || ((a.until > 0.0 || a.adaptive_set) && a.passes == 0))) {
-    fprintf(stderr, "-denoise-var needs -passes N with N >= 2, or -until / -adaptive\n");
-    usage(argv[0], flags(a));
-    return 2;
-  }
-  if (a.split_emitters && !a.denoise && !a.denoise_var) {  // nothing to split for
-    fprintf(stderr, "-split-emitters needs -denoise or -denoise-var\n");
-    usage(argv[0], flags(a));
-    return 2;
-  }
-  if (a.accum_features && !(a.passes > 0 || a.until > 0.0 || a.adaptive_set)) {  // no accumulator to keep them
-    fprintf(stderr, "-accum-features needs -passes, -until or -adaptive\n");
-    usage(argv[0], flags(a));
-    return 2;
-  }
-  if (a.temporal && !(a.accum_features && (a.passes > 0 || a.until > 0.0 || a.adaptive_set))) {  // no guides, no history
-    fprintf(stderr, "-temporal needs -accum-features and -passes, -until or -adaptive\n");
-    usage(argv[0], flags(a));
-    return 2;
-  }
-  if (a.temporal_emit && !(a.split_emitters && a.accum_features && (a.passes > 0 || a.until > 0.0 || a.adaptive_set))) {
-    fprintf(stderr, "-temporal-emit needs -split-emitters, -accum-features and -passes, -until or -adaptive\n");  // no emit planes
-    usage(argv[0], flags(a));
-    return 2;
-  }
-  if (a.aov_media && !(a.denoise || a.denoise_var || !a.aov.empty() || a.accum_features)) {  // no feature buffers
-    fprintf(stderr, "-aov-media needs -aov, -denoise, -denoise-var or -accum-features\n");
-    usage(argv[0], flags(a));
-    return 2;
-  }
-  if (a.temporal_emit) a.temporal = true;  // the same stage, through rt_reproject_emit
-  if (a.frames < 0 || a.frames > 999 || !(a.orbit == a.orbit)) {
-    fprintf(stderr, "invalid value for flag -frames (0..999) / -orbit\n");
-    usage(argv[0], flags(a));
-    return 2;
-  }
-  const bool numbered = a.frames > 0;  // -frames: frame k goes to the -o name with _00k before the extension
-  const int n_frames = numbered ? (int)a.frames : 1;
-  auto frame_name = [&](const std::string& name, int k, bool before_ext) {
-    char tag[8];
-    snprintf(tag, sizeof tag, "_%03d", k);
-    const size_t slash = name.rfind('/'), dot = name.rfind('.');
-    const bool ext = before_ext && dot != std::string::npos && (slash == std::string::npos || dot > slash);
-    return ext ? name.substr(0, dot) + tag + name.substr(dot) : name + tag;
-  };
+  const auto t0 = std::chrono::steady_clock::now();
+  if ((rc = make_job(a, argv[0], j)) >= 0) return rc;
 
   // main.go:434-439: the output file exists before anything renders
-  const std::string out_first = numbered ? frame_name(a.out, 0, true) : a.out;
-  FILE* out = fopen(out_first.c_str(), "wb");
+  Owned<FILE> out(fopen((j.numbered ? frame_name(a.out, 0, true) : a.out).c_str(), "wb"));
   if (!out) {
     fprintf(stderr, "Error creating output file\n");
     return 1;
   }
   const char* scene = nullptr;
-  if (a.S < 1 || a.S > 8 || rt_demo_scene_name((int)a.S, &scene) != RT_OK || !scene) {
-    fclose(out);  // defaultScene (main.go:412-414): nothing rendered, empty file
-    return 0;
-  }
-  int mode = a.mode == "auto" ? RT_MODE_AUTO : a.mode == "fused" ? RT_MODE_FUSED
-             : a.mode == "wavefront" ? RT_MODE_WAVEFRONT : -1;
+  if (a.S < 1 || a.S > 8 || rt_demo_scene_name((int)a.S, &scene) != RT_OK || !scene)
+    return 0;  // defaultScene (main.go:412-414): nothing rendered, empty file
+  const int mode = a.mode == "auto" ? RT_MODE_AUTO : a.mode == "fused" ? RT_MODE_FUSED
+                   : a.mode == "wavefront" ? RT_MODE_WAVEFRONT : -1;
   if (mode < 0) {
     fprintf(stderr, "invalid value \"%s\" for flag -mode\n", a.mode.c_str());
-    fclose(out);
     return 2;
   }
-  std::string assets = a.assets.empty() ? exe_dir() + "/../assets" : a.assets;
-  if (a.assets.empty() && getenv("RT_ASSET_DIR")) assets = getenv("RT_ASSET_DIR");
 
-  rt_tree* tree = nullptr;
-  rt_scene* sc = nullptr;
-  if ((rc = rt_tree_create(&tree)) != RT_OK) return fail("rt_tree_create", rc);
-  rt_tree_seed(tree, a.tree_seed);
-  rt_camera cam;
-  memset(&cam, 0, sizeof cam);
-  int world = -1, lights = -1;
-  if ((rc = rt_demo_scene(tree, scene, assets.c_str(), &cam, &world, &lights)) != RT_OK)
-    return fail("rt_demo_scene", rc);
-  cam.max_threads = (int32_t)a.N;
-  if (a.width > 0) cam.width = (int32_t)a.width;
-  if (a.spp > 0) cam.samples_per_pixel = (int32_t)a.spp;
-  if (a.depth > 0) cam.max_depth = (int32_t)a.depth;
-  rt_camera_derived d;
-  if ((rc = rt_camera_derive(&cam, &d)) != RT_OK) return fail("rt_camera_derive", rc);
-  if ((rc = rt_scene_create(tree, world, lights, &sc)) != RT_OK)
-    return fail("rt_scene_create", rc);
-
-  // -temporal: the history (the frames before this one, reprojected and blended) and its camera
-  const size_t n_px = (size_t)d.width * d.height;
-  std::vector<float> h_rgb, h_var, h_count, h_normal, h_depth, h_emission, h_coverage, count;
-  rt_camera h_cam;
-  bool have_history = false;
-  const rt_camera cam0 = cam;
-  const std::string aov0 = a.aov;
-
-  for (int frame = 0; frame < n_frames; ++frame) {
-  double ms_reproject = 0.0;
-  std::string out_name = a.out;
-  if (numbered) {
-    out_name = frame_name(a.out, frame, true);
-    if (!aov0.empty()) a.aov = frame_name(aov0, frame, false);
-    if (frame > 0 && !(out = fopen(out_name.c_str(), "wb"))) {
-      fprintf(stderr, "Error creating output file\n");
-      return 1;
-    }
-    // -orbit: look_from turned about the vup axis through look_at (Rodrigues' formula)
-    double from[3] = {0, 0, 0}, at[3] = {0, 0, -1}, up[3] = {0, 1, 0};
-    if (cam0.positioned)
-      for (int i = 0; i < 3; ++i) from[i] = cam0.look_from[i], at[i] = cam0.look_at[i], up[i] = cam0.vup[i];
-    const double th = a.orbit * (double)frame * M_PI / 180.0, co = cos(th), si = sin(th);
-    const double ul = sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
-    const double k[3] = {up[0] / ul, up[1] / ul, up[2] / ul};
-    const double v[3] = {from[0] - at[0], from[1] - at[1], from[2] - at[2]};
-    const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2];
-    const double kxv[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
-    for (int i = 0; i < 3; ++i) {
-      cam.look_from[i] = at[i] + (v[i] * co + kxv[i] * si + k[i] * kv * (1.0 - co));
-      cam.look_at[i] = at[i];
-      cam.vup[i] = up[i];
-    }
-    cam.positioned = 1;
-  }
-
-  rt_render_opts o;
-  memset(&o, 0, sizeof o);
-  o.seed = a.seed;
-  o.device = (int32_t)a.device;
-  o.nranks = 1;
-  o.mode = mode;
-  o.trace_pixel = -1;
-  o.progress_slices = (int32_t)(a.slices > 0 ? a.slices : a.progress ? 20 : 0);
-  std::vector<float> rgb((size_t)d.width * d.height * 3), var(a.denoise_var || a.temporal ? (size_t)d.width * d.height : 0);
-  rt_stats st;
-  memset(&st, 0, sizeof st);
-
-  // -passes / -until: the image is the accumulator's mean over the passes
-  const bool accumulate = a.passes > 0 || a.until > 0.0 || a.adaptive_set;
-  if (a.passes < 0 || a.passes > 0x7FFFFFFF || !(a.until >= 0.0)) {
+  Owned<rt_tree> tree;
+  Owned<rt_scene> sc;  // after the tree and before the context: the accumulator goes first, then the scene
+  Ctx c;
+  c.scene = scene;
+  c.t0 = t0;
+  c.out = std::move(out);
+  if ((rc = build_scene(j, c, tree, sc)) != 0) return rc;
+  if (!j.passes_ok) {
     fprintf(stderr, "invalid value for flag -passes / -until\n");
-    fclose(out);
     return 2;
   }
-  const int32_t pass_cap = (int32_t)(a.passes > 0 ? a.passes : 1024);
-  rt_accum* acc = nullptr;
-  rt_accum_info ai;
-  memset(&ai, 0, sizeof ai);
-  rt_adapt_info adi;
-  memset(&adi, 0, sizeof adi);
-  rt_adapt_opts ado;
-  memset(&ado, 0, sizeof ado);  // the library defaults: tile 8, min_passes 4, lum_floor 1e-2
-  ado.rel_error = a.adaptive;
-  double ms_accum = 0.0;
-  if (accumulate && (rc = rt_accum_create(sc, &cam, &o, pass_cap, &acc)) != RT_OK)
-    return fail("rt_accum_create", rc);
-  if (a.accum_features &&
-      (rc = rt_accum_set_features(acc, RT_ACCUM_FEAT_GUIDES | (a.split_emitters ? RT_ACCUM_FEAT_EMIT : 0u) |
-                                          (a.aov_media ? RT_ACCUM_FEAT_MEDIA : 0u))) != RT_OK)
-    return fail("rt_accum_set_features", rc);
+  memset(&c.o, 0, sizeof c.o);
+  c.o.seed = a.seed;
+  c.o.device = (int32_t)a.device;
+  c.o.nranks = 1;
+  c.o.mode = mode;
+  c.o.trace_pixel = -1;
+  c.o.progress_slices = (int32_t)(a.slices > 0 ? a.slices : a.progress ? 20 : 0);
 
-  bool counts_failed = false;
-  std::atomic<bool> rendering{true};
-  std::atomic<int> pass_no{0};
-  std::thread bar;
-  if (a.progress) {
-    bar = std::thread([&] {
-      uint64_t done = 0, total = 0;
-      while (rendering.load()) {
-        if (rt_progress(sc, &done, &total) == RT_OK && total) {
-          if (accumulate)
-            fprintf(stderr, "\rrendering %s: pass %d of %d, %5.1f%%", scene, pass_no.load() + 1, pass_cap,
-                    100.0 * done / total);
-          else
-            fprintf(stderr, "\rrendering %s: %5.1f%%", scene, 100.0 * done / total);
-        }
-        std::this_thread::sleep_for(std::chrono::milliseconds(100));
-      }
-    });
+  for (int frame = 0; frame < j.n_frames; ++frame) {
+    if ((rc = begin_frame(j, c, frame)) != 0) return rc;
+    if ((rc = render(j, c)) != 0) return rc;
+    if ((rc = feature_planes(j, c)) != 0) return rc;
+    if ((rc = temporal_step(j, c)) != 0) return rc;
+    if ((rc = filter(j, c)) != 0) return rc;
+    if ((rc = write_aovs(j, c)) != 0) return rc;
+    if ((rc = finish_frame(j, c)) != 0) return rc;
   }
-  const char* what = "rt_render";
-  if (!accumulate) {
-    rc = rt_render(sc, &cam, &o, rgb.data(), &st);
-  } else {
-    auto tp = std::chrono::steady_clock::now();
-    for (int32_t p = 0; p < pass_cap && rc == RT_OK; ++p) {
-      rt_stats sp;
-      pass_no = p;
-      if (a.adaptive_set) {  // the noisy tiles only (Accumulator.render_adaptive); every tile at first
-        uint64_t n_active = 0;
-        what = "rt_accum_select";
-        if ((rc = rt_accum_select(acc, &ado, &n_active)) != RT_OK || n_active == 0) break;
-        what = "rt_accum_add_active";
-        if ((rc = rt_accum_add_active(acc, a.seed + (uint64_t)p, &sp)) != RT_OK) break;
-      } else {
-        what = "rt_accum_add";
-        if ((rc = rt_accum_add(acc, a.seed + (uint64_t)p, &sp)) != RT_OK) break;
-      }
-      const uint64_t samples = st.samples + sp.samples, segments = st.segments + sp.segments;
-      const double ms = st.ms_total + sp.ms_total;
-      st = sp;  // the last pass's, with the totals over the passes
-      st.samples = samples;
-      st.segments = segments;
-      st.ms_total = ms;
-      if (a.until > 0.0 && p >= 1) {
-        what = "rt_accum_info_get";
-        if ((rc = rt_accum_info_get(acc, &ai)) != RT_OK || ai.rel_error <= a.until) break;
-      }
-    }
-    if (rc == RT_OK) {
-      what = "rt_accum_resolve";
-      if ((rc = rt_accum_resolve(acc, rgb.data(), a.denoise_var || a.temporal ? var.data() : nullptr)) == RT_OK) rc = rt_accum_info_get(acc, &ai);
-    }
-    if (rc == RT_OK && a.adaptive_set) {
-      what = "rt_accum_adapt_info";
-      rc = rt_accum_adapt_info(acc, &adi);
-      if (rc == RT_OK && !a.counts.empty()) {
-        const size_t np = (size_t)d.width * d.height;
-        std::vector<int32_t> cnt(np);
-        what = "rt_accum_counts";
-        if ((rc = rt_accum_counts(acc, cnt.data())) == RT_OK) {
-          std::vector<float> cimg(3 * np);
-          for (size_t i = 0; i < np; ++i)
-            cimg[3 * i] = cimg[3 * i + 1] = cimg[3 * i + 2] = adi.max_count > 0 ? (float)cnt[i] / (float)adi.max_count : 0.0f;
-          counts_failed = write_ppm(cimg, d.width, d.height, fopen(a.counts.c_str(), "wb"), a.counts.c_str()) != 0;
-        }
-      }
-    }
-    ms_accum = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
-  }
-  rendering = false;
-  if (bar.joinable()) bar.join();
-  if (a.progress && accumulate)
-    fprintf(stderr, "\rrendering %s: %d passes, 100.0%%      \n", scene, ai.passes);
-  else if (a.progress)
-    fprintf(stderr, "\rrendering %s: 100.0%%\n", scene);
-  if (rc != RT_OK) return fail(what, rc);
-  if (counts_failed) {  // (reported by write_ppm; after the progress thread has been joined)
-    rt_scene_destroy(sc);
-    rt_tree_destroy(tree);
-    return 1;
-  }
-
-  // -denoise / -aov: the feature buffers of the same camera rays, then the filter
-  int aov_samples = 0;
-  double ms_aov = 0.0, ms_denoise = 0.0;
-  if (a.denoise || a.denoise_var || !a.aov.empty() || a.temporal) {
-    const size_t np = (size_t)d.width * d.height;
-    std::vector<float> albedo(3 * np), normal(3 * np), depth(np);
-    rt_aov f = {albedo.data(), normal.data(), depth.data(), nullptr};
-    aov_samples = d.spp_sqrt * d.spp_sqrt < 16 ? d.spp_sqrt * d.spp_sqrt : 16;
-    if (a.accum_features) aov_samples = d.spp_sqrt * d.spp_sqrt;  // of every pass the pixel took
-    rt_stats sa;
-    auto ta = std::chrono::steady_clock::now();
-    // -split-emitters: the split feature pass and the split filter
-    std::vector<float> emission(a.split_emitters ? 3 * np : 0), salbedo(a.split_emitters ? 3 * np : 0),
-        coverage(a.split_emitters ? np : 0);
-    rt_aov_emit fe = {emission.data(), salbedo.data(), coverage.data()};
-    // -aov-media: the first-event buffers and the scatter plane
-    std::vector<float> scatter(a.aov_media ? np : 0);
-    const rt_aov_media fm = {scatter.data()};
-    if (a.aov_media && a.accum_features) {
-      if ((rc = rt_accum_resolve_aov_media(acc, &f, a.split_emitters ? &fe : nullptr, &fm)) != RT_OK)
-        return fail("rt_accum_resolve_aov_media", rc);
-    } else if (a.aov_media) {
-      if ((rc = rt_render_aov_media(sc, &cam, &o, aov_samples, &f, a.split_emitters ? &fe : nullptr, &fm, &sa)) != RT_OK)
-        return fail("rt_render_aov_media", rc);
-    } else if (a.accum_features) {  // the guides of the passes' own samples: no feature pass
-      if ((rc = rt_accum_resolve_aov(acc, &f, a.split_emitters ? &fe : nullptr)) != RT_OK)
-        return fail("rt_accum_resolve_aov", rc);
-    } else if (a.split_emitters) {
-      if ((rc = rt_render_aov_emit(sc, &cam, &o, aov_samples, &f, &fe, &sa)) != RT_OK)
-        return fail("rt_render_aov_emit", rc);
-    } else if ((rc = rt_render_aov(sc, &cam, &o, aov_samples, &f, &sa)) != RT_OK) {
-      return fail("rt_render_aov", rc);
-    }
-    ms_aov = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
-    if (a.temporal) {  // the history into this frame's camera, then this frame as the new history
-      auto tr = std::chrono::steady_clock::now();
-      count.assign(n_px, (float)ai.passes);
-      if (have_history) {
-        const rt_frame prev = {h_rgb.data(), h_var.data(), h_count.data(), h_normal.data(), h_depth.data(), 0.0f, 0};
-        const rt_frame cur = {rgb.data(), var.data(), nullptr, normal.data(), depth.data(), (float)ai.passes, 0};
-        const rt_frame res = {rgb.data(), var.data(), count.data(), nullptr, nullptr, 0.0f, 0};
-        const rt_aov_emit prev_emit = {h_emission.data(), nullptr, h_coverage.data()};
-        const rt_aov_emit cur_emit = {emission.data(), nullptr, coverage.data()};
-        if (a.temporal_emit) {
-          if ((rc = rt_reproject_emit(&h_cam, &prev, &prev_emit, &cam, &cur, &cur_emit, d.width, d.height, nullptr,
-                                      &res)) != RT_OK)
-            return fail("rt_reproject_emit", rc);
-        } else if ((rc = rt_reproject(&h_cam, &prev, &cam, &cur, d.width, d.height, nullptr, &res)) != RT_OK) {
-          return fail("rt_reproject", rc);
-        }
-      }
-      h_rgb = rgb, h_var = var, h_count = count, h_normal = normal, h_depth = depth;
-      if (a.temporal_emit) h_emission = emission, h_coverage = coverage;
-      h_cam = cam;
-      have_history = true;
-      ms_reproject = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
-    }
-    if (a.denoise_var) {
-      rt_denoise_var_opts vopt;
-      memset(&vopt, 0, sizeof vopt);  // the library defaults
-      vopt.demodulate = 1;
-      auto td = std::chrono::steady_clock::now();
-      if (a.split_emitters) {
-        if ((rc = rt_denoise_var_emit(rgb.data(), var.data(), &f, &fe, d.width, d.height, &vopt, rgb.data(),
-                                      nullptr)) != RT_OK)
-          return fail("rt_denoise_var_emit", rc);
-      } else if ((rc = rt_denoise_var(rgb.data(), var.data(), &f, d.width, d.height, &vopt, rgb.data(),
-                                      nullptr)) != RT_OK) {
-        return fail("rt_denoise_var", rc);
-      }
-      ms_denoise = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
-    } else if (a.denoise) {
-      rt_denoise_opts dopt;
-      memset(&dopt, 0, sizeof dopt);  // the library defaults
-      dopt.demodulate = 1;
-      auto td = std::chrono::steady_clock::now();
-      if (a.split_emitters) {
-        if ((rc = rt_denoise_emit(rgb.data(), &f, &fe, d.width, d.height, &dopt, rgb.data())) != RT_OK)
-          return fail("rt_denoise_emit", rc);
-      } else if ((rc = rt_denoise(rgb.data(), &f, d.width, d.height, &dopt, rgb.data())) != RT_OK) {
-        return fail("rt_denoise", rc);
-      }
-      ms_denoise = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
-    }
-    if (!a.aov.empty()) {
-      float dmax = 0.0f;
-      for (float v : depth) dmax = v > dmax ? v : dmax;
-      std::vector<float> nimg(3 * np), dimg(3 * np);
-      for (size_t i = 0; i < 3 * np; ++i) nimg[i] = normal[i] * 0.5f + 0.5f;
-      for (size_t i = 0; i < np; ++i) dimg[3 * i] = dimg[3 * i + 1] = dimg[3 * i + 2] = dmax > 0 ? depth[i] / dmax : 0.0f;
-      const std::pair<const char*, const std::vector<float>*> outs[] = {
-          {"_albedo.ppm", &albedo}, {"_normal.ppm", &nimg}, {"_depth.ppm", &dimg}};
-      for (const auto& e : outs) {
-        const std::string path = a.aov + e.first;
-        if (write_ppm(*e.second, d.width, d.height, fopen(path.c_str(), "wb"), path.c_str())) return 1;
-      }
-      if (a.split_emitters) {  // the emission as it is, the coverage as grey
-        std::vector<float> cimg(3 * np);
-        for (size_t i = 0; i < np; ++i) cimg[3 * i] = cimg[3 * i + 1] = cimg[3 * i + 2] = coverage[i];
-        const std::pair<const char*, const std::vector<float>*> eouts[] = {{"_emission.ppm", &emission},
-                                                                            {"_coverage.ppm", &cimg}};
-        for (const auto& e : eouts) {
-          const std::string path = a.aov + e.first;
-          if (write_ppm(*e.second, d.width, d.height, fopen(path.c_str(), "wb"), path.c_str())) return 1;
-        }
-      }
-      if (a.aov_media) {  // the scatter fraction as grey
-        std::vector<float> simg(3 * np);
-        for (size_t i = 0; i < np; ++i) simg[3 * i] = simg[3 * i + 1] = simg[3 * i + 2] = scatter[i];
-        const std::string path = a.aov + "_scatter.ppm";
-        if (write_ppm(simg, d.width, d.height, fopen(path.c_str(), "wb"), path.c_str())) return 1;
-      }
-    }
-  }
-
-  // camera.go:160 header + PrintColor per pixel, then main.go:477's single write
-  if (write_ppm(rgb, d.width, d.height, out, out_name.c_str())) return 1;
-  double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  std::string js = stats_json(st, d, scene, wall, aov_samples, ms_aov, ms_denoise, accumulate ? &ai : nullptr,
-                              ms_accum, a.denoise_var, a.adaptive_set ? &adi : nullptr, a.split_emitters,
-                              a.accum_features, numbered ? frame : -1, a.temporal, ms_reproject, a.temporal_emit,
-                              a.aov_media);
-  if (a.stats || a.denoise || a.denoise_var || a.temporal) fprintf(stderr, "%s\n", js.c_str());
-  if (!a.cpuprofile.empty()) {
-    FILE* p = fopen(a.cpuprofile.c_str(), "w");
-    if (!p) {
-      fprintf(stderr, "rtbench: cannot create %s\n", a.cpuprofile.c_str());
-      return 1;
-    }
-    fprintf(p, "%s\n", js.c_str());
-    fclose(p);
-  }
-  if (acc && (rc = rt_accum_destroy(acc)) != RT_OK) return fail("rt_accum_destroy", rc);
-  }  // frames
-  rt_scene_destroy(sc);
-  rt_tree_destroy(tree);
   return 0;
 }

@@ -11,8 +11,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.cli import CLI
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "go_raytracer_amd", "rtbench")
 AOV = ("rt_render_aov_emit", "rt_render_aov_emit_device")
 DN = ("rt_denoise_emit", "rt_denoise_emit_device")
 DV = ("rt_denoise_var_emit", "rt_denoise_var_emit_device")

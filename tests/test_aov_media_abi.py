@@ -12,8 +12,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.cli import CLI
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "go_raytracer_amd", "rtbench")
 AOV = ("rt_render_aov_media", "rt_render_aov_media_device")
 ACC = ("rt_accum_resolve_aov_media", "rt_accum_resolve_aov_media_device")
 

@@ -39,12 +39,12 @@ import pytest
 import torch  # before the library's HIP runtime initialises (one runtime per process)
 
 from tests import scenes
+from tests.cli import CLI
 from tests.test_aov_gpu import Flat, _shape, expected
 
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "go_raytracer_amd", "rtbench")
 ISOTROPIC = 4
 SURF = ("albedo", "normal", "depth", "material")
 EMIT = ("emission", "surface_albedo", "coverage")

@@ -5,21 +5,20 @@ CPU tests pin the flag handling the reference gets from Go's flag package
 defaultScene behaviour (the output file is created and left empty).  The GPU
 test checks that the CLI's image is byte-identical to the Python harness's
 render of the same scene, seed and overrides (same library, same kernels)."""
+import functools
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "go_raytracer_amd", "rtbench")
+from tests import cli
+from tests.cli import CLI
 
 pytestmark = pytest.mark.skipif(not os.path.exists(CLI), reason="rtbench not built (make -C go_raytracer_amd/csrc)")
 
 
-def run(*args, cwd=None, timeout=120):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, cwd=cwd, timeout=timeout)
+run = functools.partial(cli.run, timeout=120)
 
 
 def test_help_lists_the_reference_flags():

@@ -1,18 +1,12 @@
 """rtbench -passes / -until: the image as the pass accumulator's mean, from the command line
 (child processes with a time limit)."""
 import json
-import os
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "go_raytracer_amd", "rtbench")
+from tests.cli import run
+
 COMMON = ["-S", "6", "-width", "32", "-spp", "4"]
-
-
-def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=60)
 
 
 def test_help_lists_the_flags():

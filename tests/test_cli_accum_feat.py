@@ -2,21 +2,14 @@
 passes, from the command line (child processes with a time limit), against the
 same pipeline through the Python wrappers.  The usage error needs no GPU."""
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.cli import run
 from tests.test_cli_denoise_var import read_p3
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "go_raytracer_amd", "rtbench")
 SHAPE = ["-S", "6", "-width", "40", "-spp", "4"]
-
-
-def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=60)
 
 
 def test_help_lists_the_flag():

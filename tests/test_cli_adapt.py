@@ -1,19 +1,13 @@
 """rtbench -adaptive / -counts: adaptive passes from the command line (child processes with a
 time limit).  The argument errors need no GPU."""
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "go_raytracer_amd", "rtbench")
+from tests.cli import run
+
 COMMON = ["-S", "6", "-width", "40", "-spp", "4"]
-
-
-def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=60)
 
 
 def test_help_lists_the_flags():

@@ -1,23 +1,16 @@
 """rtbench -denoise / -aov: render -> feature pass -> denoise -> PPM from the command line,
 in a child process with a time limit."""
+import functools
 import json
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "go_raytracer_amd", "rtbench")
+from tests import cli
+from tests.cli import CLI
 
-
-def read_p3(path, w=32):
-    lines = path.read_text().split("\n")
-    assert lines[0] == "P3" and lines[2] == "255" and lines[-1] == ""
-    pw, ph = map(int, lines[1].split())
-    body = np.array([list(map(int, ln.split())) for ln in lines[3:-1]])
-    assert pw == w and body.shape == (pw * ph, 3) and body.min() >= 0 and body.max() <= 255
-    return body.reshape(ph, pw, 3)
+read_p3 = functools.partial(cli.read_p3, w=32)
 
 
 def test_help_lists_the_flags():

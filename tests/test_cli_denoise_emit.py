@@ -1,23 +1,16 @@
 """rtbench -split-emitters: the split feature pass and the split filter from the command line
 (child processes with a time limit), against the same pipeline through the Python wrappers."""
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.cli import run
 from tests.test_cli_denoise_var import read_p3
 
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "go_raytracer_amd", "rtbench")
 COMMON = ["-S", "6", "-width", "40", "-spp", "4", "-passes", "4", "-denoise-var"]
-
-
-def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=60)
 
 
 _py = {}

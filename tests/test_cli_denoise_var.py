@@ -1,29 +1,18 @@
 """rtbench -denoise-var: the accumulator's mean through the variance-guided filter, from the
 command line (child processes with a time limit)."""
+import functools
 import json
 import os
-import subprocess
 
-import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "go_raytracer_amd", "rtbench")
+from tests import cli
+from tests.cli import REPO, run
+
 GOLDEN = os.path.join(REPO, "tests", "golden", "cli_passes3_denoise_cornell40.ppm")
 COMMON = ["-S", "6", "-width", "40", "-spp", "4"]
 
-
-def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=60)
-
-
-def read_p3(path, w=40):
-    lines = path.read_text().split("\n")
-    assert lines[0] == "P3" and lines[2] == "255" and lines[-1] == ""
-    pw, ph = map(int, lines[1].split())
-    body = np.array([list(map(int, ln.split())) for ln in lines[3:-1]])
-    assert pw == w and body.shape == (pw * ph, 3) and body.min() >= 0 and body.max() <= 255
-    return body.reshape(ph, pw, 3)
+read_p3 = functools.partial(cli.read_p3, w=40)
 
 
 def test_help_lists_the_flag():

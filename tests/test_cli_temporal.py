@@ -2,35 +2,12 @@
 (child processes with a time limit), against the same sequence through Temporal.push in Python.
 The usage errors need no GPU."""
 import json
-import math
-import os
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "go_raytracer_amd", "rtbench")
+from tests.cli import orbit, run
+
 SHAPE = ["-S", "6", "-width", "32", "-spp", "4"]
-
-
-def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=60)
-
-
-def orbit(cam, degrees):
-    """rtbench's -orbit, operation for operation: look_from turned about the vup axis through
-    look_at (Rodrigues' formula) -> a positioned copy of cam"""
-    frm, at, up = cam._pos
-    th = degrees * math.pi / 180.0
-    co, si = math.cos(th), math.sin(th)
-    ul = math.sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2])
-    k = [up[0] / ul, up[1] / ul, up[2] / ul]
-    v = [frm[0] - at[0], frm[1] - at[1], frm[2] - at[2]]
-    kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2]
-    kxv = [k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]]
-    out = type(cam).from_c(cam.to_c())
-    out.PositionCamera([at[i] + (v[i] * co + kxv[i] * si + k[i] * kv * (1.0 - co)) for i in range(3)], at, up)
-    return out
 
 
 def test_help_lists_the_flags():

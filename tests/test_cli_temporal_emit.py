@@ -5,7 +5,8 @@ import json
 
 import pytest
 
-from tests.test_cli_temporal import SHAPE, orbit, run
+from tests.cli import orbit, run
+from tests.test_cli_temporal import SHAPE
 
 
 def test_help_lists_the_flag():
