@@ -15,7 +15,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (RT_FT_ALL, RT_FT_BOX, RT_NOISE_MARBLE, RT_NOISE_PERLIN,  # noqa: F401
-                   RT_NOISE_TURBULENT, RtAccumInfo, RtAov, RtAovEmit, RtAovMedia, RtCamera, RtDenoiseOpts,
+                   RT_NOISE_TURBULENT, RtAccumInfo, RtAov, RtAovEmit, RtAovMedia, RtAovSpec, RtAovSpecOpts,
+                   RtCamera, RtDenoiseOpts,
                    RtDenoiseVarOpts, RtCameraDerived, RtError, RtRenderOpts, RtSceneInfo, RtStats, RtTreeView,
                    check, lib)
 
@@ -565,7 +566,8 @@ class Scene:
                                      C.byref(st)))
         return _as_dict(st)
 
-    def render_aov(self, camera, n_samples=1, seed=1, device=0, rank=0, nranks=1, emit=False, media=False):
+    def render_aov(self, camera, n_samples=1, seed=1, device=0, rank=0, nranks=1, emit=False, media=False,
+                   specular=False, max_bounces=0, max_fuzz=0.0):
         """Feature buffers of this rank's rows (rt_render_aov): the first hit of the camera
         rays render() gives samples 0 .. n_samples-1 of every pixel, averaged.  Returns
         {"albedo": float32 [rows, W, 3], "normal": float32 [rows, W, 3] (world space, facing
@@ -578,7 +580,14 @@ class Scene:
         traces the constant media as the render's camera vertex does: every buffer is then of the
         sample's first event, a scatter inside a volume included (the phase material's albedo,
         no normal, the scatter's depth), and "scatter" float32 [rows, W] is the fraction of
-        samples whose first event is a scatter.  With emit=True it returns both sets."""
+        samples whose first event is a scatter.  With emit=True it returns both sets.
+        specular=True (rt_render_aov_spec) follows dielectrics and metals of fuzz <= max_fuzz as
+        the render's paths do, up to vertex max_bounces (0 = 8): the four buffers are then of the
+        first non-specular vertex, the albedo times the mirrors' on the way and the depth summed
+        along the chain, and "bounces" float32 [rows, W] is the mean number of specular vertices
+        passed (0: the pixel has the first hit's bits).  It combines with neither emit nor media."""
+        if specular and (emit or media):
+            raise ValueError("render_aov: specular=True does not combine with emit=True or media=True")
         d = camera.derived()
         rows = len(range(rank, d.height, nranks))
         res = {"albedo": np.zeros((rows, d.width, 3), np.float32),
@@ -597,8 +606,22 @@ class Scene:
             res["scatter"] = np.zeros((rows, d.width), np.float32)
             m = RtAovMedia(res["scatter"].ctypes.data)
         o = self._opts(seed, device, rank, nranks, 0, 0, False, None)
+        if specular:
+            res["bounces"] = np.zeros((rows, d.width), np.float32)
+            res["stats"] = self._aov_spec(camera, o, n_samples, a, RtAovSpec(res["bounces"].ctypes.data),
+                                          max_bounces, max_fuzz, False)
+            return res
         res["stats"] = self._aov(camera, o, n_samples, a, e, False, m)
         return res
+
+    def _aov_spec(self, camera, o, n_samples, a, sp, max_bounces, max_fuzz, device):
+        """One of the two rt_render_aov_spec entries -> the stats dict."""
+        st = RtStats()
+        c = camera.to_c()
+        so = RtAovSpecOpts(max_bounces, max_fuzz)
+        fn = lib().rt_render_aov_spec_device if device else lib().rt_render_aov_spec
+        check(fn(self._p, C.byref(c), C.byref(o), n_samples, C.byref(so), C.byref(a), C.byref(sp), C.byref(st)))
+        return _as_dict(st)
 
     def _aov(self, camera, o, n_samples, a, e, device, m=None):
         """One of the six rt_render_aov entries: the emit ones with an RtAovEmit `e`, the media
@@ -620,11 +643,21 @@ class Scene:
 
     def render_aov_device(self, camera, albedo=None, normal=None, depth=None, material=None,
                           n_samples=1, seed=1, device=0, rank=0, nranks=1, stream=None,
-                          emission=None, surface_albedo=None, coverage=None, media=False, scatter=None):
+                          emission=None, surface_albedo=None, coverage=None, media=False, scatter=None,
+                          specular=False, bounces=None, max_bounces=0, max_fuzz=0.0):
         """rt_render_aov_device: the same buffers written to device pointers (e.g. torch
         tensors' .data_ptr(); None = not wanted) on `stream`.  With any of emission /
         surface_albedo / coverage the call is rt_render_aov_emit_device; with media=True or a
-        `scatter` pointer it is rt_render_aov_media_device.  Returns the stats dict."""
+        `scatter` pointer it is rt_render_aov_media_device.  With specular=True or a `bounces`
+        pointer it is rt_render_aov_spec_device, which takes none of the emit or media buffers.
+        Returns the stats dict."""
+        if specular or bounces is not None:
+            if (media or scatter is not None or emission is not None or surface_albedo is not None
+                    or coverage is not None):
+                raise ValueError("render_aov_device: specular does not combine with the emit or media buffers")
+            o = self._opts(seed, device, rank, nranks, 0, 0, False, stream)
+            return self._aov_spec(camera, o, n_samples, RtAov(albedo, normal, depth, material), RtAovSpec(bounces),
+                                  max_bounces, max_fuzz, True)
         e = None
         if emission is not None or surface_albedo is not None or coverage is not None:
             e = RtAovEmit(emission, surface_albedo, coverage)

@@ -110,6 +110,14 @@ class RtAovMedia(C.Structure):  # rt_aov_media: the media mode's plane (may be N
     _fields_ = [("scatter", C.c_void_p)]
 
 
+class RtAovSpecOpts(C.Structure):  # rt_aov_spec_opts: the specular chains' limits (0 = defaults)
+    _fields_ = [("max_bounces", C.c_int32), ("max_fuzz", C.c_float)]
+
+
+class RtAovSpec(C.Structure):  # rt_aov_spec: the specular mode's plane (may be NULL)
+    _fields_ = [("bounces", C.c_void_p)]
+
+
 class RtDenoiseOpts(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32),
                 ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
@@ -292,6 +300,12 @@ SIGNATURES = {
     "rt_render_aov_media_device": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
                                         C.POINTER(RtAov), C.POINTER(RtAovEmit), C.POINTER(RtAovMedia),
                                         C.POINTER(RtStats)]),
+    "rt_render_aov_spec": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
+                                C.POINTER(RtAovSpecOpts), C.POINTER(RtAov), C.POINTER(RtAovSpec),
+                                C.POINTER(RtStats)]),
+    "rt_render_aov_spec_device": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_int32,
+                                       C.POINTER(RtAovSpecOpts), C.POINTER(RtAov), C.POINTER(RtAovSpec),
+                                       C.POINTER(RtStats)]),
     "rt_denoise_emit": (_I, [C.c_void_p, C.POINTER(RtAov), C.POINTER(RtAovEmit), _I, _I,
                              C.POINTER(RtDenoiseOpts), C.c_void_p]),
     "rt_denoise_emit_device": (_I, [C.c_void_p, C.POINTER(RtAov), C.POINTER(RtAovEmit), _I, _I,

@@ -27,6 +27,15 @@
 // the instructions they were (profiles/aov_media_device_code.txt); the dispatcher takes a MEDIA
 // instance only for a scene that has media.
 //
+// k_aov<TREE, false, false, true> (rt_render_aov_spec): the first DIFFUSE hit of the
+// sample.  While the hit is a dielectric or a metal of fuzz <= max_fuzz the lane scatters as the
+// render's vertex k does (the same rt_rng_draw(seed, gpix, j, RT_STREAM(k, 0)), shade_core's
+// expressions restated) and traces the next segment, a per-lane loop around the one
+// trace-and-evaluate block; the planes are of the chain's terminal vertex, the albedo times the
+// metals' on the way, the depth summed along the chain, and `bounces` counts the specular vertices
+// passed.  SPEC only with EMIT = MEDIA = false; the SPEC = false instances are the instructions
+// they were (profiles/aov_specular_device_code.txt).
+//
 // k_aov_fold<TREE, EMIT, PX, MEDIA>: the pass accumulator's feature fold (rt_accum.hip),
 // the same samples (aov_sample is the one text of both kernels) summed into the accumulator's
 // fp64 planes for all spp_sqrt^2 samples of a pass's seed, over a whole pass or its active pixels.
@@ -82,8 +91,16 @@ struct AovEmitMedia : AovEmit {
 struct FeatPlanesMedia : FeatPlanes {
   uint32_t* nscatter;  // [npix], as nlight
 };
-template <bool MEDIA>
-using AovEmitArg = std::conditional_t<MEDIA, AovEmitMedia, AovEmit>;
+// The specular mode's plane, its chain limits and the count of the chain segments traced (one
+// device word, added to once by each wave that traced any), behind the same argument for the same reason
+struct AovEmitSpec : AovEmit {
+  float* bounces;                      // may be null
+  unsigned long long* chain_segments;  // never null
+  int32_t max_k;   // the last vertex a chain may reach: min(max_bounces, MaxDepth - 1)
+  float max_fuzz;  // a metal is specular up to this fuzz
+};
+template <bool MEDIA, bool SPEC = false>
+using AovEmitArg = std::conditional_t<SPEC, AovEmitSpec, std::conditional_t<MEDIA, AovEmitMedia, AovEmit>>;
 template <bool MEDIA>
 using FeatPlanesArg = std::conditional_t<MEDIA, FeatPlanesMedia, FeatPlanes>;
 
@@ -95,9 +112,10 @@ struct AovSums {
   f3 esum, ssum;  // EMIT only, as nlight
   uint32_t nlight;
   uint32_t nscatter;  // MEDIA only: the samples whose first event is a scatter in a medium
+  uint32_t nspec;     // SPEC only: the specular vertices the samples' chains passed
 };
 RT_D AovSums aov_sums_zero() {
-  return {mk3(0, 0, 0), mk3(0, 0, 0), 0.0f, -1, mk3(0, 0, 0), mk3(0, 0, 0), 0u, 0u};
+  return {mk3(0, 0, 0), mk3(0, 0, 0), 0.0f, -1, mk3(0, 0, 0), mk3(0, 0, 0), 0u, 0u, 0u};
 }
 
 // The camera ids of local pixel lp of the share, for `count` samples from sample 0
@@ -119,8 +137,19 @@ RT_D Ids aov_ids(const Params& P, uint32_t lp, uint32_t count) {
 // 2 BVH2, 4 BVH4, 5 compressed BVH4 (any feature)
 // MEDIA: the first event, not the first surface: the render's vertex-0 trace_media on top of
 // the world hit (finish_hit's order: the triangle refinement, then the media)
-template <int TREE, bool EMIT, bool MEDIA>
-RT_D void aov_sample(const Params& P, const Ids& id, uint32_t j, const TravStack& ts, AovSums& s) {
+// SPEC (rt_abi.h rt_render_aov_spec): the loop below goes round again while the vertex is
+// specular: vertex k < max_k, a dielectric or a metal of fuzz <= max_fuzz that does not scatter
+// into its own surface.  The next ray is shade_core's for that vertex: the same draw, the same
+// expressions, the snapped point (eta off a sphere) as the origin.  Only a hit is evaluated, and
+// its material is the surface's own (MEDIA = false: no medium wins), so a chain lane reads no
+// record of a PRIM_NONE hit and no material through a medium's id.  The evaluation stays in the
+// loop's body, one text for the first hit and for every chain vertex, and is not a function of
+// its own: as a callee with reference results it changed the register allocation of every
+// existing instance; in place they are the instructions they were.
+template <int TREE, bool EMIT, bool MEDIA, bool SPEC = false>
+RT_D void aov_sample(const Params& P, const Ids& id, uint32_t j, const TravStack& ts, AovSums& s,
+                     int32_t max_k = 0, float max_fuzz = 0.0f) {
+  static_assert(!SPEC || (!EMIT && !MEDIA), "the specular mode: neither the emission split nor media");
   constexpr uint32_t FT = TREE == 0 ? (uint32_t)FT_MEDIA : (uint32_t)FT_ALL;
   const DevScene& sc = P.sc;
   (void)ts;
@@ -128,130 +157,181 @@ RT_D void aov_sample(const Params& P, const Ids& id, uint32_t j, const TravStack
   f3 o, d;
   float time;
   camera_ray_r<0>(P, id, j, r, o, d, time);
-  Trav tr;
-  trav_init<FT>(sc, o, d, time, tr);
-  if constexpr (TREE == 0) {
-    trav_brute<FT, true>(sc, nullptr, o, d, time, 0.001f, tr);
-  } else {
-    do {  // a near-edge rejection ends a round early (retest_near), as trace_world
-      trav_steps<false, FT, TREE != 2, TREE == 5>(sc, nullptr, false, ts, o, d, time, 0.001f, tr,
-                                                  0x7FFFFFFF);
-      retest_near<FT>(sc, o, d, 0.001f, tr);
-    } while (tr.cur != TRAV_DONE);
-  }
-  Hit h = tr.best;
-  if constexpr (MEDIA) {
-    if (HAS(FT_TRI) && h.ref != PRIM_NONE && (h.ref >> 30) == PRIM_TRI)
-      refine_tri_hit(sc, h.ref & 0x3FFFFFFFu, o, d, h.t, h.u, h.v);
-    trace_media(P, o, d, time, 0.001f, id.gpix, j, 0u, rt_spare24(r), h);
-  }
-  const uint32_t ref = h.ref;
-  f3 alb = mk3(P.bg[0], P.bg[1], P.bg[2]), n = mk3(0, 0, 0);  // a miss: camera.go:300-302
-  float depth = 0.0f;
-  int32_t kind = -1;
-  bool lit = false;  // L_j
-  if (ref != PRIM_NONE) {
-    // finish_hit's refinements of the winning hit (no media, no trace)
-    if constexpr (!MEDIA)
-      if (HAS(FT_TRI) && (ref >> 30) == PRIM_TRI)
-        refine_tri_hit(sc, ref & 0x3FFFFFFFu, o, d, h.t, h.u, h.v);
-    // shade_core's hit record: r.At(t) snapped onto the surface, the outward normal,
-    // setFaceNormal (hittable.go:27-34), and the texture coordinates
-    const float t = h.t;
-    float u = h.u, v = h.v;
-    f3 p = o + d * t;
-    const uint32_t type = ref >> 30, idx = ref & 0x3FFFFFFFu;
-    f3 nout;
-    int mat;
-    const bool medium = MEDIA && type == PRIM_MEDIUM;
-    if (medium) {
-      // a scatter inside a volume, as shade_core takes a medium hit: p = r.At(t) as it is, the
-      // phase material at u = v = 0.  The reference's (1,0,0) normal (medium.go:162-166) is a
-      // placeholder: a volume has no shading normal, the guide gets none
-      nout = mk3(0, 0, 0);
-      mat = sc.media[idx].phase_mat;
-      u = v = 0.0f;
-    } else if (HAS(FT_SPHERE) && type == PRIM_SPHERE) {
-      const F4 cr = sc.sph_cr[idx], mv = sc.sph_mv[idx];
-      const f3 cc = xyz(cr) + xyz(mv) * time;
-      const double cx = (double)cr.x + (double)time * (double)mv.x;
-      const double cy = (double)cr.y + (double)time * (double)mv.y;
-      const double cz = (double)cr.z + (double)time * (double)mv.z;
-      const double ex = (double)p.x - cx, ey = (double)p.y - cy, ez = (double)p.z - cz;
-      const double rr = (double)cr.w;
-      const float dn = (float)(rr * rr - (ex * ex + ey * ey + ez * ez));
-      const f3 e = p - cc;
-      const float le = length(e);
-      const f3 nu = e * rcp(le);
-      p = p + nu * (dn * rcp(fabsf(cr.w) + le));
-      nout = cr.w < 0.0f ? -nu : nu;  // (p - c) / r objects.go:102
-      mat = (int)fbits(mv.w);
-      if (sc.mats[mat]._pad != 0.0f) {  // calculateSphereUV objects.go:44-50
-        const F2 rs = sc.sph_uv[idx];
-        const f3 no = mk3(rs.x * nout.x - rs.y * nout.z, nout.y, rs.y * nout.x + rs.x * nout.z);
-        const float theta = acosf(-no.y);
-        const float phi = atan2f(-no.z, no.x) + kPi;
-        u = phi * (0.5f * kInvPi);
-        v = theta * kInvPi;
-      }
-    } else if (!HAS(FT_TRI) || type == PRIM_QUAD) {
-      const F4* q = sc.quad + 5 * (size_t)idx;
-      nout = xyz(q[3]);
-      p = p - nout * (dot(nout, p) - q[0].w);  // onto the plane n.p = D
-      mat = (int)fbits(q[2].w);
-      if (HAS(FT_BOX) && u < 0.0f) {  // a box leaf's face: alpha, beta at this p
-        if (sc.mats[mat]._pad != 0.0f) {
-          const f3 pp = p - xyz(q[0]), w = xyz(q[4]);
-          u = dot(w, cross(pp, xyz(q[2])));
-          v = dot(w, cross(xyz(q[1]), pp));
-        } else {
-          u = v = 0.0f;
+  // SPEC: the chain so far: the specular vertices passed, their attenuations' product T and the
+  // length of their segments
+  uint32_t k = 0u;
+  f3 T = mk3(1, 1, 1);
+  float dpre = 0.0f;
+  for (;;) {  // (SPEC: once per segment of the chain; else once)
+    Trav tr;
+    trav_init<FT>(sc, o, d, time, tr);
+    if constexpr (TREE == 0) {
+      trav_brute<FT, true>(sc, nullptr, o, d, time, 0.001f, tr);
+    } else {
+      do {  // a near-edge rejection ends a round early (retest_near), as trace_world
+        trav_steps<false, FT, TREE != 2, TREE == 5>(sc, nullptr, false, ts, o, d, time, 0.001f, tr,
+                                                    0x7FFFFFFF);
+        retest_near<FT>(sc, o, d, 0.001f, tr);
+      } while (tr.cur != TRAV_DONE);
+    }
+    Hit h = tr.best;
+    if constexpr (MEDIA) {
+      if (HAS(FT_TRI) && h.ref != PRIM_NONE && (h.ref >> 30) == PRIM_TRI)
+        refine_tri_hit(sc, h.ref & 0x3FFFFFFFu, o, d, h.t, h.u, h.v);
+      trace_media(P, o, d, time, 0.001f, id.gpix, j, 0u, rt_spare24(r), h);
+    }
+    const uint32_t ref = h.ref;
+    f3 alb = mk3(P.bg[0], P.bg[1], P.bg[2]), n = mk3(0, 0, 0);  // a miss: camera.go:300-302
+    float depth = 0.0f;
+    int32_t kind = -1;
+    bool lit = false;  // L_j
+    if (ref != PRIM_NONE) {
+      // finish_hit's refinements of the winning hit (no media, no trace)
+      if constexpr (!MEDIA)
+        if (HAS(FT_TRI) && (ref >> 30) == PRIM_TRI)
+          refine_tri_hit(sc, ref & 0x3FFFFFFFu, o, d, h.t, h.u, h.v);
+      // shade_core's hit record: r.At(t) snapped onto the surface, the outward normal,
+      // setFaceNormal (hittable.go:27-34), and the texture coordinates
+      const float t = h.t;
+      float eta = 0.0f;  // SPEC, spheres: shade_core's offset of the next origin off the surface
+      float u = h.u, v = h.v;
+      f3 p = o + d * t;
+      const uint32_t type = ref >> 30, idx = ref & 0x3FFFFFFFu;
+      f3 nout;
+      int mat;
+      const bool medium = MEDIA && type == PRIM_MEDIUM;
+      if (medium) {
+        // a scatter inside a volume, as shade_core takes a medium hit: p = r.At(t) as it is, the
+        // phase material at u = v = 0.  The reference's (1,0,0) normal (medium.go:162-166) is a
+        // placeholder: a volume has no shading normal, the guide gets none
+        nout = mk3(0, 0, 0);
+        mat = sc.media[idx].phase_mat;
+        u = v = 0.0f;
+      } else if (HAS(FT_SPHERE) && type == PRIM_SPHERE) {
+        const F4 cr = sc.sph_cr[idx], mv = sc.sph_mv[idx];
+        const f3 cc = xyz(cr) + xyz(mv) * time;
+        const double cx = (double)cr.x + (double)time * (double)mv.x;
+        const double cy = (double)cr.y + (double)time * (double)mv.y;
+        const double cz = (double)cr.z + (double)time * (double)mv.z;
+        const double ex = (double)p.x - cx, ey = (double)p.y - cy, ez = (double)p.z - cz;
+        const double rr = (double)cr.w;
+        const float dn = (float)(rr * rr - (ex * ex + ey * ey + ez * ez));
+        const f3 e = p - cc;
+        const float le = length(e);
+        const f3 nu = e * rcp(le);
+        p = p + nu * (dn * rcp(fabsf(cr.w) + le));
+        nout = cr.w < 0.0f ? -nu : nu;  // (p - c) / r objects.go:102
+        if constexpr (SPEC) eta = 0x1p-22f * (fabsf(p.x * nu.x) + fabsf(p.y * nu.y) + fabsf(p.z * nu.z));
+        mat = (int)fbits(mv.w);
+        if (sc.mats[mat]._pad != 0.0f) {  // calculateSphereUV objects.go:44-50
+          const F2 rs = sc.sph_uv[idx];
+          const f3 no = mk3(rs.x * nout.x - rs.y * nout.z, nout.y, rs.y * nout.x + rs.x * nout.z);
+          const float theta = acosf(-no.y);
+          const float phi = atan2f(-no.z, no.x) + kPi;
+          u = phi * (0.5f * kInvPi);
+          v = theta * kInvPi;
+        }
+      } else if (!HAS(FT_TRI) || type == PRIM_QUAD) {
+        const F4* q = sc.quad + 5 * (size_t)idx;
+        nout = xyz(q[3]);
+        p = p - nout * (dot(nout, p) - q[0].w);  // onto the plane n.p = D
+        mat = (int)fbits(q[2].w);
+        if (HAS(FT_BOX) && u < 0.0f) {  // a box leaf's face: alpha, beta at this p
+          if (sc.mats[mat]._pad != 0.0f) {
+            const f3 pp = p - xyz(q[0]), w = xyz(q[4]);
+            u = dot(w, cross(pp, xyz(q[2])));
+            v = dot(w, cross(xyz(q[1]), pp));
+          } else {
+            u = v = 0.0f;
+          }
+        }
+      } else {
+        nout = tri_normal(sc, idx, u, v);
+        mat = (int)fbits(sc.tri[3 * (size_t)idx].w);
+        const uint32_t tf = fbits(sc.tri[3 * (size_t)idx + 2].w);
+        if (tf & TRI_HAS_UV) {  // objects.go:437-446
+          const F4* at = sc.tri_attr + 6 * (size_t)idx;
+          const float w = 1.0f - u - v;
+          const float tu = w * at[4].x + u * at[4].z + v * at[5].x;
+          const float tv = w * at[4].y + u * at[4].w + v * at[5].y;
+          u = tu;
+          v = tv;
         }
       }
-    } else {
-      nout = tri_normal(sc, idx, u, v);
-      mat = (int)fbits(sc.tri[3 * (size_t)idx].w);
-      const uint32_t tf = fbits(sc.tri[3 * (size_t)idx + 2].w);
-      if (tf & TRI_HAS_UV) {  // objects.go:437-446
-        const F4* at = sc.tri_attr + 6 * (size_t)idx;
-        const float w = 1.0f - u - v;
-        const float tu = w * at[4].x + u * at[4].z + v * at[5].x;
-        const float tv = w * at[4].y + u * at[4].w + v * at[5].y;
-        u = tu;
-        v = tv;
+      const bool ff = dot(d, nout) < 0;
+      n = ff ? nout : -nout;
+      if (medium) n = mk3(0, 0, 0);
+      const DevMaterial M = sc.mats[mat];
+      kind = M.kind;
+      if (M.kind == RT_MAT_METAL) alb = xyz(M.albedo);
+      else if (M.kind == RT_MAT_DIELECTRIC) alb = mk3(1, 1, 1);
+      else if (M.kind == RT_MAT_DIFFUSE_LIGHT && !ff) alb = mk3(0, 0, 0);  // materials.go:150-155
+      else alb = tex_value<FT>(sc, M.tex, u, v, p);
+      depth = t * length(d);
+      if constexpr (EMIT) lit = M.kind == RT_MAT_DIFFUSE_LIGHT && ff;
+      if constexpr (MEDIA) s.nscatter += medium ? 1u : 0u;
+      if constexpr (SPEC) {
+        const bool metal = kind == RT_MAT_METAL;
+        if ((int32_t)k < max_k && (kind == RT_MAT_DIELECTRIC || (metal && M.param <= max_fuzz))) {
+          const rt_u32x4 rk = rt_rng_draw(P.seed, id.gpix, j, RT_STREAM(k, 0));
+          f3 ndir;
+          if (metal) {  // materials.go:70-79
+            const f3 refl = unit(reflect(d, n));
+            ndir = refl + uniform_sphere(rt_unit_f(rk.v[2]), rt_unit_f(rk.v[3])) * M.param;
+          } else {  // materials.go:94-130, Schlick's fifth power as shade_core's three multiplies
+            const float ior = M.param;
+            const float ri = ff ? rcp(ior) : ior;
+            const f3 ud = unit(d);
+            const float cs = fminf(dot(-ud, n), 1.0f);
+            const float sn = fsqrt(1.0f - cs * cs);
+            bool refl = ri * sn > 1.0f;
+            if (!refl) {
+              float r0 = (1.0f - ior) * rcp(1.0f + ior);
+              r0 = r0 * r0;
+              const float x = 1.0f - cs, x2 = x * x;
+              refl = r0 + (1.0f - r0) * (x2 * x2 * x) > rt_unit_f(rk.v[0]);
+            }
+            ndir = refl ? reflect(ud, n) : refract(ud, n, ri);
+          }
+          const float side = dot(ndir, n);
+          if (!metal || side > 0.0f) {  // (a metal that scatters into itself absorbs: a terminal)
+            T = T * alb;  // the metal's albedo; 1 for glass
+            dpre += depth;
+            ++k;
+            o = p + n * copysignf(eta, side);
+            d = ndir;
+            continue;  // the next segment
+          }
+        }
       }
     }
-    const bool ff = dot(d, nout) < 0;
-    n = ff ? nout : -nout;
-    if (medium) n = mk3(0, 0, 0);
-    const DevMaterial M = sc.mats[mat];
-    kind = M.kind;
-    if (M.kind == RT_MAT_METAL) alb = xyz(M.albedo);
-    else if (M.kind == RT_MAT_DIELECTRIC) alb = mk3(1, 1, 1);
-    else if (M.kind == RT_MAT_DIFFUSE_LIGHT && !ff) alb = mk3(0, 0, 0);  // materials.go:150-155
-    else alb = tex_value<FT>(sc, M.tex, u, v, p);
-    depth = t * length(d);
-    if constexpr (EMIT) lit = M.kind == RT_MAT_DIFFUSE_LIGHT && ff;
-    if constexpr (MEDIA) s.nscatter += medium ? 1u : 0u;
-  }
-  if constexpr (EMIT) {
-    if (lit) {
-      // what the render adds for this sample: a light does not scatter, so rayColor returns
-      // its emission (camera.go:312-314) before the clampContribution of camera.go:330
-      s.esum = s.esum + alb;
-      ++s.nlight;
-    } else {
-      s.ssum = s.ssum + alb;
+    if constexpr (SPEC) {
+      if (k > 0u) {  // (k == 0: the first hit's values as they are)
+        alb = T * alb;
+        depth = kind < 0 ? 0.0f : dpre + depth;
+        s.nspec += k;
+      }
     }
+    if constexpr (EMIT) {
+      if (lit) {
+        // what the render adds for this sample: a light does not scatter, so rayColor returns
+        // its emission (camera.go:312-314) before the clampContribution of camera.go:330
+        s.esum = s.esum + alb;
+        ++s.nlight;
+      } else {
+        s.ssum = s.ssum + alb;
+      }
+    }
+    s.asum = s.asum + alb;
+    s.nsum = s.nsum + n;
+    s.dsum += depth;
+    if (j == 0) s.kind0 = kind;
+    break;
   }
-  s.asum = s.asum + alb;
-  s.nsum = s.nsum + n;
-  s.dsum += depth;
-  if (j == 0) s.kind0 = kind;
 }
 
-template <int TREE, bool EMIT, bool MEDIA>
-__global__ __launch_bounds__(256) void k_aov(Params P, AovOut out, AovEmitArg<MEDIA> em) {
+template <int TREE, bool EMIT, bool MEDIA, bool SPEC>
+__global__ __launch_bounds__(256) void k_aov(Params P, AovOut out, AovEmitArg<MEDIA, SPEC> em) {
   constexpr uint32_t FT = TREE == 0 ? (uint32_t)FT_MEDIA : (uint32_t)FT_ALL;
   __shared__ uint32_t lstack[kShortStack * 256];
   if constexpr (HAS(FT_NOISE)) stage_perlin(P.sc);
@@ -259,10 +339,15 @@ __global__ __launch_bounds__(256) void k_aov(Params P, AovOut out, AovEmitArg<ME
   const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
   const TravStack ts = {&lstack[threadIdx.x], P.ostack + gtid, P.stack_cols, kShortStack};
   const uint32_t stride = gridDim.x * blockDim.x;
+  uint32_t chain_total = 0u;  // SPEC: the chain segments this lane traced
   for (uint32_t lp = gtid; lp < P.npix; lp += stride) {
     const Ids id = aov_ids(P, lp, out.n);
     AovSums s = aov_sums_zero();
-    for (uint32_t j = 0; j < out.n; ++j) aov_sample<TREE, EMIT, MEDIA>(P, id, j, ts, s);
+    if constexpr (SPEC) {
+      for (uint32_t j = 0; j < out.n; ++j) aov_sample<TREE, EMIT, MEDIA, true>(P, id, j, ts, s, em.max_k, em.max_fuzz);
+    } else {
+      for (uint32_t j = 0; j < out.n; ++j) aov_sample<TREE, EMIT, MEDIA>(P, id, j, ts, s);
+    }
     const float inv = 1.0f / (float)out.n;
     if (out.albedo) {
       out.albedo[3 * (size_t)lp + 0] = s.asum.x * inv;
@@ -294,7 +379,16 @@ __global__ __launch_bounds__(256) void k_aov(Params P, AovOut out, AovEmitArg<ME
     if constexpr (MEDIA) {  // as coverage: exactly 0 and exactly 1 at the ends
       if (em.scatter) em.scatter[lp] = (float)((double)s.nscatter / (double)out.n);
     }
+    if constexpr (SPEC) {  // the same division: exactly 0 where no chain left the first hit
+      if (em.bounces) em.bounces[lp] = (float)((double)s.nspec / (double)out.n);
+      chain_total += s.nspec;
+    }
   }
+  if constexpr (SPEC) {  // one atomic per wave that traced any, not one per pixel
+    for (int off = 32; off > 0; off >>= 1) chain_total += __shfl_down(chain_total, off);
+    if ((threadIdx.x & 63u) == 0u && chain_total) atomicAdd(em.chain_segments, (unsigned long long)chain_total);
+  }
+  (void)chain_total;
 }
 
 // The accumulator's feature fold: k_aov's loop over the P.npix pixels of one
@@ -347,7 +441,7 @@ namespace {
 // one feature pass at a time: the scratch buffers (overflow stacks, host staging) and the
 // library stream are shared
 std::mutex g_mu;
-DeviceScratch g_stacks, g_stage;
+DeviceScratch g_stacks, g_stage, g_count;  // (g_count: the specular mode's chain-segment word)
 // the library stream of each device ordinal.  Process lifetime: the list is never destroyed, so
 // no stream is released while the runtime unloads.
 std::vector<Stream>& g_streams = *new std::vector<Stream>();
@@ -360,21 +454,48 @@ void launch_aov(bool split, dim3 grid, hipStream_t stream, const Params& p, cons
   AovEmitMedia md;
   (AovEmit&)md = ae;
   md.scatter = scatter;
-  if (media && split) hipLaunchKernelGGL((k_aov<TREE, true, true>), grid, b, 0, stream, p, ao, md);
-  else if (media) hipLaunchKernelGGL((k_aov<TREE, false, true>), grid, b, 0, stream, p, ao, md);
-  else if (split) hipLaunchKernelGGL((k_aov<TREE, true, false>), grid, b, 0, stream, p, ao, ae);
-  else hipLaunchKernelGGL((k_aov<TREE, false, false>), grid, b, 0, stream, p, ao, ae);
+  if (media && split) hipLaunchKernelGGL((k_aov<TREE, true, true, false>), grid, b, 0, stream, p, ao, md);
+  else if (media) hipLaunchKernelGGL((k_aov<TREE, false, true, false>), grid, b, 0, stream, p, ao, md);
+  else if (split) hipLaunchKernelGGL((k_aov<TREE, true, false, false>), grid, b, 0, stream, p, ao, ae);
+  else hipLaunchKernelGGL((k_aov<TREE, false, false, false>), grid, b, 0, stream, p, ao, ae);
+}
+
+void launch_aov_spec(int tree, dim3 grid, hipStream_t stream, const Params& p, const AovOut& ao, const AovEmitSpec& sp) {
+  const dim3 b(256);
+  switch (tree) {
+    case 0: hipLaunchKernelGGL((k_aov<0, false, false, true>), grid, b, 0, stream, p, ao, sp); break;
+    case 2: hipLaunchKernelGGL((k_aov<2, false, false, true>), grid, b, 0, stream, p, ao, sp); break;
+    case 5: hipLaunchKernelGGL((k_aov<5, false, false, true>), grid, b, 0, stream, p, ao, sp); break;
+    default: hipLaunchKernelGGL((k_aov<4, false, false, true>), grid, b, 0, stream, p, ao, sp); break;
+  }
 }
 
 // split: the rt_render_aov_emit entries (outp may be null, emitp is required); else emitp is null.
 // mediap: the rt_render_aov_media entries (required there; outp and emitp may be null), which
-// are the split ones when emitp is given
+// are the split ones when emitp is given.  spec: the rt_render_aov_spec entries (specp required,
+// sopts null = the defaults; neither split nor media)
 int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
              const rt_aov* outp, const rt_aov_emit* emitp, const rt_aov_media* mediap, bool split, bool media,
-             bool host, rt_stats* stats) {
+             bool host, rt_stats* stats, bool spec = false, const rt_aov_spec_opts* sopts = nullptr,
+             const rt_aov_spec* specp = nullptr) {
   if (!scene || !cam) return set_error(RT_ERR_INVALID, "rt_render_aov: null scene/camera");
   const rt_aov no_out{nullptr, nullptr, nullptr, nullptr};
-  if (media) {
+  int32_t max_bounces = 8;
+  float max_fuzz = 0.0f;
+  if (spec) {
+    if (!specp) return set_error(RT_ERR_INVALID, "rt_render_aov_spec: null spec");
+    if (!outp) outp = &no_out;
+    if (!outp->albedo && !outp->normal && !outp->depth && !outp->material && !specp->bounces)
+      return set_error(RT_ERR_INVALID, "rt_render_aov_spec: no buffer wanted");
+    if (sopts) {
+      if (sopts->max_bounces < 0 || sopts->max_bounces > 64)
+        return set_error(RT_ERR_INVALID, "rt_render_aov_spec: max_bounces %d not in 0 .. 64", sopts->max_bounces);
+      if (!(sopts->max_fuzz >= 0.0f) || !std::isfinite(sopts->max_fuzz))
+        return set_error(RT_ERR_INVALID, "rt_render_aov_spec: max_fuzz must be finite and >= 0");
+      if (sopts->max_bounces > 0) max_bounces = sopts->max_bounces;
+      max_fuzz = sopts->max_fuzz;
+    }
+  } else if (media) {
     if (!mediap) return set_error(RT_ERR_INVALID, "rt_render_aov_media: null media");
     if (!outp) outp = &no_out;
     split = emitp != nullptr;
@@ -420,6 +541,7 @@ int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, 
 
   const int blocks = (int)std::min<uint32_t>((npix + 255u) / 256u,
                                              (uint32_t)(view.tree == 0 ? kAovMaxBlocks : kAovMaxTreeBlocks));
+  unsigned long long chain_segments = 0;  // spec: the segments traced behind the camera rays'
   if (npix > 0) {
     Params p{};
     p.sc = view.sc;
@@ -444,8 +566,9 @@ int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, 
     } planes[8] = {{outp->albedo, 3 * (size_t)npix * 4},     {outp->normal, 3 * (size_t)npix * 4},
                    {outp->depth, (size_t)npix * 4},          {outp->material, (size_t)npix * 4},
                    {em.emission, 3 * (size_t)npix * 4},      {em.surface_albedo, 3 * (size_t)npix * 4},
-                   {em.coverage, (size_t)npix * 4},          {media ? mediap->scatter : nullptr, (size_t)npix * 4}};
-    const int n_planes = media ? 8 : split ? 7 : 4;
+                   {em.coverage, (size_t)npix * 4},
+                   {media ? mediap->scatter : spec ? specp->bounces : nullptr, (size_t)npix * 4}};  // (one slot)
+    const int n_planes = media || spec ? 8 : split ? 7 : 4;
     void* dev[8];  // where the kernel writes: the caller's device buffer or the plane's staging slot
     for (int i = 0; i < 8; ++i) dev[i] = host ? nullptr : planes[i].user;
     if (host) {  // one scratch buffer; an absent plane keeps its slot
@@ -464,13 +587,29 @@ int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, 
     const bool mk = media && view.sc.n_media > 0;
     float* const scat = (float*)dev[7];
     if (media && !mk && scat) HIP_OK(hipMemsetAsync(scat, 0, planes[7].bytes, stream));
-    switch (view.tree) {
-      case 0: launch_aov<0>(split, g, stream, p, ao, ae, mk, scat); break;
-      case 2: launch_aov<2>(split, g, stream, p, ao, ae, mk, scat); break;
-      case 5: launch_aov<5>(split, g, stream, p, ao, ae, mk, scat); break;
-      default: launch_aov<4>(split, g, stream, p, ao, ae, mk, scat); break;
+    if (spec) {
+      // the last vertex a chain may reach; the chain segments are counted on the device
+      void* cnt = nullptr;
+      if ((rc = g_count.get(o.device, sizeof(unsigned long long), &cnt, "rt_render_aov_spec"))) return rc;
+      HIP_OK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), stream));
+      AovEmitSpec sp;
+      (AovEmit&)sp = ae;
+      sp.bounces = scat;
+      sp.chain_segments = (unsigned long long*)cnt;
+      sp.max_k = std::max(0, std::min(max_bounces, cd.max_depth - 1));
+      sp.max_fuzz = max_fuzz;
+      launch_aov_spec(view.tree, g, stream, p, ao, sp);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipMemcpyAsync(&chain_segments, cnt, sizeof chain_segments, hipMemcpyDeviceToHost, stream));
+    } else {
+      switch (view.tree) {
+        case 0: launch_aov<0>(split, g, stream, p, ao, ae, mk, scat); break;
+        case 2: launch_aov<2>(split, g, stream, p, ao, ae, mk, scat); break;
+        case 5: launch_aov<5>(split, g, stream, p, ao, ae, mk, scat); break;
+        default: launch_aov<4>(split, g, stream, p, ao, ae, mk, scat); break;
+      }
+      HIP_OK(hipGetLastError());
     }
-    HIP_OK(hipGetLastError());
     for (int k = 0; host && k < n_planes; ++k) {
       const int i = ((split ? 4 : 0) + k) % n_planes;  // the emit planes first
       if (planes[i].user)
@@ -481,7 +620,8 @@ int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, 
   if (stats) {
     memset(stats, 0, sizeof *stats);
     stats->samples = (uint64_t)npix * n;
-    stats->segments = (uint64_t)npix * n;  // one closest-hit query per feature ray
+    // one closest-hit query per feature ray, and per specular vertex passed in the specular mode
+    stats->segments = (uint64_t)npix * n + chain_segments;
     stats->rows = (int32_t)rows;
     stats->tree_width = view.tree;
     stats->scene_features = (int32_t)scene->s.h.features;
@@ -602,6 +742,20 @@ int rt_render_aov_media_device(rt_scene* s, const rt_camera* cam, const rt_rende
                                int32_t n_samples, const rt_aov* out_device, const rt_aov_emit* emit_device,
                                const rt_aov_media* media_device, rt_stats* stats) {
   return rt::aov_impl(s, cam, opts, n_samples, out_device, emit_device, media_device, false, true, false, stats);
+}
+
+int rt_render_aov_spec(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
+                       const rt_aov_spec_opts* spec_opts, const rt_aov* out_host, const rt_aov_spec* spec_host,
+                       rt_stats* stats) {
+  return rt::aov_impl(s, cam, opts, n_samples, out_host, nullptr, nullptr, false, false, true, stats, true,
+                      spec_opts, spec_host);
+}
+
+int rt_render_aov_spec_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
+                              const rt_aov_spec_opts* spec_opts, const rt_aov* out_device,
+                              const rt_aov_spec* spec_device, rt_stats* stats) {
+  return rt::aov_impl(s, cam, opts, n_samples, out_device, nullptr, nullptr, false, false, false, stats, true,
+                      spec_opts, spec_device);
 }
 
 }  // extern "C"

@@ -54,8 +54,9 @@ struct Args {
   bool adaptive_set = false;
   unsigned long long seed = 1, tree_seed = 1;
   bool progress = false, stats = false, denoise = false, denoise_var = false, split_emitters = false;
-  bool accum_features = false, temporal = false, temporal_emit = false, aov_media = false;
-  long long frames = 0;
+  bool accum_features = false, temporal = false, temporal_emit = false, aov_media = false, aov_specular = false;
+  long long frames = 0, spec_bounces = 0;
+  double spec_fuzz = 0.0;
   double orbit = 0.0;
 };
 
@@ -70,6 +71,8 @@ std::vector<Flag> flags(Args& a) {
        Flag::F64, &a.adaptive, ""},
       {"aov-media", "with -aov, -denoise[-var] or -accum-features: trace constant media in the feature buffers (first-event guides); -aov also writes PREFIX_scatter.ppm",
        Flag::BOOL, &a.aov_media, ""},
+      {"aov-specular", "with -aov, -denoise or -denoise-var: follow mirrors and glass in the feature buffers (first diffuse-hit guides, see -spec-bounces and -spec-fuzz); -aov also writes PREFIX_bounces.ppm",
+       Flag::BOOL, &a.aov_specular, ""},
       {"aov", "write PREFIX_albedo.ppm, PREFIX_normal.ppm and PREFIX_depth.ppm (first-hit feature buffers)",
        Flag::STR, &a.aov, ""},
       {"assets", "directory holding earthmap.jpg / dragon.obj (default: <exe dir>/../assets)",
@@ -96,6 +99,10 @@ std::vector<Flag> flags(Args& a) {
       {"seed", "render seed (Philox key)", Flag::U64, &a.seed, "1"},
       {"slices", "progress granularity: launches per render (0 = 20 with -progress)", Flag::INT,
        &a.slices, "0"},
+      {"spec-bounces", "with -aov-specular: the last vertex a specular chain may reach (0 = 8, at most 64)", Flag::INT,
+       &a.spec_bounces, "0"},
+      {"spec-fuzz", "with -aov-specular: follow metals up to this fuzz (0 = perfect mirrors only)", Flag::F64,
+       &a.spec_fuzz, "0"},
       {"split-emitters", "with -denoise or -denoise-var: keep directly seen lights out of the filter (emission split); -aov also writes PREFIX_emission.ppm and PREFIX_coverage.ppm",
        Flag::BOOL, &a.split_emitters, ""},
       {"spp", "override Camera.SamplesPerPixel (0 = the scene's)", Flag::INT, &a.spp, "0"},
@@ -227,6 +234,7 @@ struct Job {
   int32_t pass_cap = 0;
   Features source = Features::NONE;
   bool accum_features = false, emit = false, media = false;  // the planes beyond the guides
+  bool specular = false;  // the guides are of the first diffuse hit (rt_render_aov_spec)
   Filter filter = Filter::NONE;
   bool temporal = false, temporal_emit = false, want_var = false;
   bool counts = false, aov = false, print_stats = false;
@@ -252,6 +260,14 @@ int make_job(const Args& a, const char* prog, Job& j) {
        "-temporal-emit needs -split-emitters, -accum-features and -passes, -until or -adaptive"},
       {a.aov_media && !(filtered || !a.aov.empty() || a.accum_features),  // no feature buffers
        "-aov-media needs -aov, -denoise, -denoise-var or -accum-features"},
+      {a.aov_specular && !(filtered || !a.aov.empty()), "-aov-specular needs -aov, -denoise or -denoise-var"},
+      // its own entry: no emit or media structure, and the accumulator keeps first-hit sums
+      {a.aov_specular && a.aov_media, "-aov-specular does not combine with -aov-media"},
+      {a.aov_specular && a.split_emitters, "-aov-specular does not combine with -split-emitters"},
+      {a.aov_specular && a.accum_features, "-aov-specular does not combine with -accum-features"},
+      {(a.spec_bounces != 0 || a.spec_fuzz != 0.0) && !a.aov_specular, "-spec-bounces and -spec-fuzz need -aov-specular"},
+      {a.spec_bounces < 0 || a.spec_bounces > 64 || !(a.spec_fuzz >= 0.0) || !(a.spec_fuzz <= 3.0e38),
+       "invalid value for flag -spec-bounces (0..64) / -spec-fuzz (finite, >= 0)"},
       {a.frames < 0 || a.frames > 999 || !(a.orbit == a.orbit), "invalid value for flag -frames (0..999) / -orbit"},
   };
   for (const auto& c : checks)
@@ -268,6 +284,7 @@ int make_job(const Args& a, const char* prog, Job& j) {
   j.accum_features = a.accum_features;
   j.emit = a.split_emitters;
   j.media = a.aov_media;
+  j.specular = a.aov_specular;
   j.filter = a.denoise_var ? Filter::VAR : a.denoise ? Filter::PLAIN : Filter::NONE;
   j.want_var = a.denoise_var || j.temporal;
   j.counts = !a.counts.empty();
@@ -326,7 +343,7 @@ struct Ctx {
   std::string out_name, aov;  // the frame's image and -aov prefix
   Owned<FILE> out;
   Owned<rt_accum> acc;
-  std::vector<float> rgb, var, albedo, normal, depth, emission, salbedo, coverage, scatter;
+  std::vector<float> rgb, var, albedo, normal, depth, emission, salbedo, coverage, scatter, bounces;
   rt_stats st;
   rt_accum_info ai;
   rt_adapt_info adi;
@@ -380,7 +397,7 @@ struct Stats {
   int aov_samples;
   const rt_accum_info* acc;    // -passes / -until / -adaptive, else null
   const rt_adapt_info* adapt;  // -adaptive, else null
-  bool denoise_var, split_emitters, accum_features, temporal, temporal_emit, aov_media;
+  bool denoise_var, split_emitters, accum_features, temporal, temporal_emit, aov_media, aov_specular;
   int frame;  // -frames, else -1
 };
 
@@ -421,6 +438,7 @@ std::string stats_json(const Stats& s) {
   if (s.temporal) appendf(b, "\"temporal\": 1, \"ms_reproject\": %.3f, ", s.ms_reproject);
   if (s.temporal_emit) b += "\"temporal_emit\": 1, ";
   if (s.aov_media) b += "\"aov_media\": 1, ";
+  if (s.aov_specular) b += "\"aov_specular\": 1, ";
   appendf(b, "\"wall_s\": %.3f}", s.wall_s);
   return b;
 }
@@ -571,11 +589,14 @@ int feature_planes(const Job& j, Ctx& c) {
   c.albedo.assign(3 * np, 0.0f), c.normal.assign(3 * np, 0.0f), c.depth.assign(np, 0.0f);
   c.emission.assign(j.emit ? 3 * np : 0, 0.0f), c.salbedo.assign(j.emit ? 3 * np : 0, 0.0f);
   c.coverage.assign(j.emit ? np : 0, 0.0f), c.scatter.assign(j.media ? np : 0, 0.0f);
+  c.bounces.assign(j.specular ? np : 0, 0.0f);
   const bool pass = j.source == Features::PASS;
   const int n = c.aov_samples = pass && c.spp() >= 16 ? 16 : c.spp();
   const rt_aov f = c.guides();
   const rt_aov_emit fe = c.emit_planes(), *split = j.emit ? &fe : nullptr;
   const rt_aov_media fm = {c.scatter.data()};
+  const rt_aov_spec fs = {c.bounces.data()};
+  const rt_aov_spec_opts so = {(int32_t)j.a.spec_bounces, (float)j.a.spec_fuzz};
   rt_stats sa;
   Call s;
   const auto ta = std::chrono::steady_clock::now();
@@ -583,6 +604,8 @@ int feature_planes(const Job& j, Ctx& c) {
     s.ok("rt_accum_resolve_aov_media", rt_accum_resolve_aov_media(c.acc.get(), &f, split, &fm));
   else if (!pass)
     s.ok("rt_accum_resolve_aov", rt_accum_resolve_aov(c.acc.get(), &f, split));
+  else if (j.specular)  // (make_job: a feature pass, neither -split-emitters nor -aov-media)
+    s.ok("rt_render_aov_spec", rt_render_aov_spec(c.sc, &c.cam, &c.o, n, &so, &f, &fs, &sa));
   else if (j.media)
     s.ok("rt_render_aov_media", rt_render_aov_media(c.sc, &c.cam, &c.o, n, &f, split, &fm, &sa));
   else if (j.emit)
@@ -648,7 +671,7 @@ int filter(const Job& j, Ctx& c) {
 }
 
 // -aov: PREFIX_albedo, _normal as n * 0.5 + 0.5, _depth over the image maximum; the emission as it
-// is; coverage and scatter as grey
+// is; coverage and scatter as grey, bounces over the image maximum
 int write_aovs(const Job& j, const Ctx& c) {
   if (!j.aov) return 0;
   float dmax = 0.0f;
@@ -659,6 +682,9 @@ int write_aovs(const Job& j, const Ctx& c) {
   if (put("_albedo.ppm", c.albedo) || put("_normal.ppm", nimg) || put("_depth.ppm", grey(c.depth, dmax))) return 1;
   if (j.emit && (put("_emission.ppm", c.emission) || put("_coverage.ppm", grey(c.coverage, 1.0f)))) return 1;
   if (j.media && put("_scatter.ppm", grey(c.scatter, 1.0f))) return 1;
+  float bmax = 0.0f;
+  for (float v : c.bounces) bmax = v > bmax ? v : bmax;
+  if (j.specular && put("_bounces.ppm", grey(c.bounces, bmax))) return 1;
   return 0;
 }
 
@@ -673,7 +699,7 @@ int finish_frame(const Job& j, Ctx& c) {
   s.acc = j.accumulate ? &c.ai : nullptr;
   s.adapt = j.adaptive ? &c.adi : nullptr;
   s.denoise_var = j.filter == Filter::VAR, s.split_emitters = j.emit, s.accum_features = j.accum_features;
-  s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.aov_media = j.media;
+  s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.aov_media = j.media, s.aov_specular = j.specular;
   s.frame = j.numbered ? c.frame : -1;
   const std::string js = stats_json(s);
   if (j.print_stats) fprintf(stderr, "%s\n", js.c_str());

@@ -685,6 +685,61 @@ int rt_render_aov_media_device(rt_scene* s, const rt_camera* cam, const rt_rende
                                const rt_aov_emit* emit_device, const rt_aov_media* media_device,
                                rt_stats* stats);
 
+/* ------------------------------------------------------------------------ */
+/* Specular chains in the feature pass (DESIGN.md "First diffuse-hit         */
+/* guides"): the features of the first non-specular vertex behind mirrors    */
+/* and glass.  Opt-in and added without an ABI version change: detect by the */
+/* symbols.                                                                  */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  int32_t max_bounces;      /* the last vertex a chain may reach; 0 -> 8; 0 .. 64 */
+  float max_fuzz;           /* a metal is specular up to this fuzz; 0: perfect mirrors only */
+} rt_aov_spec_opts;
+
+typedef struct {
+  float* bounces;           /* [rows][W]; may be NULL */
+} rt_aov_spec;
+
+/* rt_render_aov following perfectly specular vertices.  Sample j starts as rt_render_aov's: the
+ * same camera ray, the same closest world hit, the same triangle refinement, constant media
+ * transparent.  That hit is vertex 0 (the vertex the render's camera ray hits, whose scatter
+ * draw is RT_STREAM(0, 0)).
+ * Chain rule.  While vertex k is specular -- a dielectric, or a metal whose fuzz is <= max_fuzz
+ * -- the sample scatters there exactly as the render's path does and the next segment is traced
+ * with t_min = 0.001 from the hit point snapped onto its surface:
+ *   dielectric: ri = 1 / ior on a front face, ior on a back face; total internal reflection, or
+ *               Schlick's reflectance > word [0] of rt_rng_draw(seed, gpix, j, RT_STREAM(k, 0))
+ *               as a unit float, reflects the unit direction; else it is refracted.
+ *   metal:      unit(reflect(d, n)) + fuzz * the unit vector of words [2] and [3] of that call.
+ * The chain's terminal vertex is the first of: a vertex that is not specular; a miss; a metal
+ * whose scattered direction s has dot(s, n) <= 0 (it absorbs); vertex K = max(0, min(max_bounces,
+ * MaxDepth - 1)), whatever it is.  With T the product of the attenuations of the specular
+ * vertices passed (the metal's albedo; 1 for a dielectric), sample j contributes
+ *   albedo   = T * the terminal's albedo by rt_render_aov's rules (lights and back faces
+ *              included); T * the background on a miss
+ *   normal   = the terminal's normal facing its own ray; 0 on a miss
+ *   depth    = the sum of t |d| over the chain's segments up to the terminal; 0 when the terminal
+ *              is a miss (no surface, as for the first hit)
+ *   material = sample 0's terminal kind, -1 on a miss
+ *   bounces  = the number of specular vertices passed
+ * and the buffers are the means over samples 0 .. n-1 summed in fp32 in sample order (bounces: an
+ * exact count divided once, exactly 0 where no sample left its first hit).  A sample that passed
+ * no vertex contributes rt_render_aov's values, so a pixel with bounces == 0 has rt_render_aov's
+ * bits in all four planes.  Two calls give identical bits.
+ * spec must not be NULL (it selects the mode); spec_opts NULL = the defaults; out may be NULL.
+ * RT_ERR_INVALID, before any device is touched: a NULL spec; no buffer wanted at all;
+ * max_bounces < 0 or > 64; a negative or non-finite max_fuzz; then rt_render_aov's refusals.
+ * The emission split and the media mode do not combine with this one.  The structures traversed
+ * and the stats are rt_render_aov's, except that segments counts every segment traced: the
+ * camera rays' and one per specular vertex passed. */
+int rt_render_aov_spec(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
+                       int32_t n_samples, const rt_aov_spec_opts* spec_opts, const rt_aov* out_host,
+                       const rt_aov_spec* spec_host, rt_stats* stats);
+int rt_render_aov_spec_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
+                              int32_t n_samples, const rt_aov_spec_opts* spec_opts,
+                              const rt_aov* out_device, const rt_aov_spec* spec_device,
+                              rt_stats* stats);
+
 /* rt_denoise / rt_denoise_var in split mode: the emission is subtracted before the filter and
  * added back after it, and the filter demodulates by the albedo of the surfaces the pixel
  * covers.  All three emit buffers are required (else RT_ERR_INVALID); feat->albedo is not read
