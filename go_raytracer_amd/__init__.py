@@ -24,7 +24,7 @@ __all__ = ["Tree", "Camera", "Scene", "Accumulator", "quantize", "format_ppm", "
            "tune", "untune", "tuning", "tune_knobs", "tune_from_env",
            "demo_scene", "DEMO_SCENES", "build_bvh_boxes", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
            "format_ppm_device", "denoise", "denoise_device", "denoise_var", "denoise_var_device",
-           "RtDenoiseVarOpts", "reproject", "reproject_device", "reproject_emit", "reproject_emit_device",
+           "RtDenoiseVarOpts", "reproject", "reproject_device", "reproject_emit", "reproject_emit_device", "reproject_light", "reproject_light_device",
            "Temporal"]
 
 DEMO_SCENES = ("book1", "book2", "book3", "simple_light", "quads", "cornell", "cornell_smoke",
@@ -1259,9 +1259,13 @@ def _frame_emit(who, name, f, h, w, conv, ptr):
     return RtAovEmit(ptr(keep[0]), None, ptr(keep[1])), keep
 
 
-def _reproject_host(emit, cam_prev, prev, cam_cur, cur, opts):
-    """reproject and reproject_emit (emit): rt_reproject[_emit] on host arrays"""
-    who = "reproject_emit" if emit else "reproject"
+_LIGHT_KEYS = (("emission", 3), ("coverage", 0))
+
+
+def _reproject_host(emit, cam_prev, prev, cam_cur, cur, opts, light=False):
+    """reproject, reproject_emit (emit) and reproject_light (emit, light): rt_reproject[_emit |
+    _light] on host arrays"""
+    who = "reproject_light" if light else "reproject_emit" if emit else "reproject"
     if not isinstance(cur, dict) or cur.get("rgb") is None:
         raise ValueError(f"{who}: cur['rgb'] is required")
     h, w = np.shape(cur["rgb"])[:2]
@@ -1284,6 +1288,12 @@ def _reproject_host(emit, cam_prev, prev, cam_cur, cur, opts):
     fo = _lib.RtFrame(rgb.ctypes.data, var.ctypes.data, cnt.ctypes.data, None, None, 0.0, 0)
     o = _reproject_opts(**opts)
     cp, cc = cam_prev.to_c(), cam_cur.to_c()
+    if light:
+        emission, coverage = np.empty((h, w, 3), np.float32), np.empty((h, w), np.float32)
+        eo = RtAovEmit(emission.ctypes.data, None, coverage.ctypes.data)
+        check(lib().rt_reproject_light(C.byref(cp), C.byref(fp), C.byref(ep), C.byref(cc), C.byref(fc), C.byref(ec),
+                                       w, h, C.byref(o), C.byref(fo), C.byref(eo)))
+        return rgb, var, cnt, emission, coverage
     if emit:
         check(lib().rt_reproject_emit(C.byref(cp), C.byref(fp), C.byref(ep), C.byref(cc), C.byref(fc), C.byref(ec),
                                       w, h, C.byref(o), C.byref(fo)))
@@ -1293,11 +1303,11 @@ def _reproject_host(emit, cam_prev, prev, cam_cur, cur, opts):
     return rgb, var, cnt
 
 
-def _reproject_dev(emit, cam_prev, prev, cam_cur, cur, out, opts):
-    """reproject_device and reproject_emit_device (emit): rt_reproject[_emit]_device on torch
-    tensors"""
+def _reproject_dev(emit, cam_prev, prev, cam_cur, cur, out, opts, light=False):
+    """reproject_device, reproject_emit_device (emit) and reproject_light_device (emit, light):
+    rt_reproject[_emit | _light]_device on torch tensors"""
     import torch
-    who = "reproject_emit_device" if emit else "reproject_device"
+    who = "reproject_light_device" if light else "reproject_emit_device" if emit else "reproject_device"
     if not isinstance(cur, dict) or not torch.is_tensor(cur.get("rgb")) or cur["rgb"].dim() != 3:
         raise ValueError(f"{who}: cur['rgb'] must be a [H, W, 3] tensor")
     a = cur["rgb"]
@@ -1319,17 +1329,22 @@ def _reproject_dev(emit, cam_prev, prev, cam_cur, cur, out, opts):
         ec, keep_ec = _frame_emit(who, "cur", cur, h, w, conv, ptr)
         keep_p = keep_p + keep_ep
     res = []
-    for k, ch in _FRAME_KEYS[:3]:
+    for k, ch in _FRAME_KEYS[:3] + (_LIGHT_KEYS if light else ()):
         shape = (h, w, ch) if ch else (h, w)
         t = (out or {}).get(k)
         t = torch.empty(shape, dtype=torch.float32, device=a.device) if t is None else conv(f"out[{k!r}]", t, shape)
         if any(t.data_ptr() == p.data_ptr() for p in keep_p):
             raise ValueError(f"{who}: out[{k!r}] is a buffer of prev (the taps gather from prev)")
         res.append(t)
-    fo = _lib.RtFrame(*[t.data_ptr() for t in res], None, None, 0.0, 0)
+    fo = _lib.RtFrame(*[t.data_ptr() for t in res[:3]], None, None, 0.0, 0)
     o = _reproject_opts(**opts)
     cp, cc = cam_prev.to_c(), cam_cur.to_c()
-    if emit:
+    if light:
+        eo = RtAovEmit(res[3].data_ptr(), None, res[4].data_ptr())
+        check(lib().rt_reproject_light_device(C.byref(cp), C.byref(fp), C.byref(ep), C.byref(cc), C.byref(fc),
+                                              C.byref(ec), w, h, C.byref(o), C.byref(fo), C.byref(eo),
+                                              a.device.index or 0, _stream_of(a)))
+    elif emit:
         check(lib().rt_reproject_emit_device(C.byref(cp), C.byref(fp), C.byref(ep), C.byref(cc), C.byref(fc),
                                              C.byref(ec), w, h, C.byref(o), C.byref(fo), a.device.index or 0,
                                              _stream_of(a)))
@@ -1374,6 +1389,25 @@ def reproject_emit_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
     return _reproject_dev(True, cam_prev, prev, cam_cur, cur, out, opts)
 
 
+def reproject_light(cam_prev, prev, cam_cur, cur, **opts):
+    """reproject_emit with emission and coverage carried as history planes of their own
+    (rt_reproject_light): frames as reproject_emit's, prev's "emission" and "coverage" being the
+    planes an earlier call returned (or the first frame's own).  Both are reprojected and blended
+    with the surface radiance's weights and the pixel is re-lit from the blend, so the rim of a
+    light, where coverage is a few samples' estimate, gains from the history too.  Returns new
+    arrays (rgb, var, count, emission, coverage): the last two are the next call's prev planes and
+    the planes to hand the split filter."""
+    return _reproject_host(True, cam_prev, prev, cam_cur, cur, opts, light=True)
+
+
+def reproject_light_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
+    """rt_reproject_light_device on torch tensors: frames as reproject_light's, every buffer a
+    contiguous float32 tensor on cur["rgb"]'s device; `out` as reproject_device's and may also name
+    "emission" and "coverage" (cur's own allowed, never a buffer of prev).  Returns (rgb, var,
+    count, emission, coverage)."""
+    return _reproject_dev(True, cam_prev, prev, cam_cur, cur, out, opts, light=True)
+
+
 class Temporal:
     """The history of a moving camera (DESIGN.md "Temporal reprojection"): ``push(acc)`` takes the
     accumulator of the next frame, reprojects the stored history into its camera
@@ -1382,18 +1416,28 @@ class Temporal:
     (max_history, depth_tol, normal_tol, min_weight).  The scene is static and the cameras have
     no defocus; ``reset()`` drops the history (a cut, a changed scene).  split_emitters=True
     (reproject_emit_device) keeps directly seen lights out of the history: the accumulators must
-    then have features="emit", whose emission and coverage are kept with the history."""
+    then have features="emit", whose emission and coverage are kept with the history.
+    light_history=True (reproject_light_device; needs split_emitters) carries emission and
+    coverage as history planes too: ``light`` is then the dict {"emission", "coverage"} of the
+    tensors the last push wrote, the planes to hand the split filter in place of the frame's own:
+    ``denoise_var_device(rgb, var, dict(acc.resolve_aov_device(), **temporal.light),
+    split_emitters=True)``."""
 
-    def __init__(self, split_emitters=False, **opts):
+    def __init__(self, split_emitters=False, light_history=False, **opts):
         _reproject_opts(**opts)  # a wrong name fails here, not at the second push
+        if light_history and not split_emitters:
+            raise ValueError("Temporal: light_history needs split_emitters=True (the history of the emission "
+                             "split's planes)")
         self._opts = opts
         self._split = bool(split_emitters)
+        self._light = bool(light_history)
         self._sets = [None, None]
         self.reset()
 
     def reset(self):
         """Drop the history: the next push returns its frame unchanged."""
         self._prev, self._cam = None, None
+        self.light = None
 
     def push(self, acc):
         """`acc`: an Accumulator with features ("guides" or "emit") of the whole image
@@ -1401,7 +1445,8 @@ class Temporal:
         the device, every pixel weighing acc.passes, and blends the history into them.  Returns
         the tensors (rgb [H, W, 3], var [H, W], count [H, W]) ready for denoise_var_device; they
         belong to this object and are overwritten by the push after the next.  The first push
-        (and the first after reset()) returns the current frame unchanged."""
+        (and the first after reset()) returns the current frame unchanged.  With light_history the
+        blended emission and coverage are left in ``light`` (the first push: the frame's own)."""
         import torch
         if acc.features is None:
             raise ValueError("Temporal.push: needs an accumulator with features (the normal and depth guides)")
@@ -1429,9 +1474,12 @@ class Temporal:
         if p is None or p["depth"].shape != (h, w) or p["depth"].device != dev:
             s["count"].fill_(float(passes))
         else:
-            fn = reproject_emit_device if self._split else reproject_device
+            fn = (reproject_light_device if self._light else reproject_emit_device if self._split
+                  else reproject_device)
             fn(self._cam, p, acc.camera, dict(s, count=float(passes)), out=s, **self._opts)
         self._prev, self._cam = k, acc.camera
+        if self._light:
+            self.light = {"emission": s["emission"], "coverage": s["coverage"]}
         return s["rgb"], s["var"], s["count"]
 
 

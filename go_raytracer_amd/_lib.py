@@ -352,6 +352,13 @@ SIGNATURES = {
                                       C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
                                       _I, _I, C.POINTER(RtReprojectOpts), C.POINTER(RtFrame), _I,
                                       C.c_void_p]),
+    "rt_reproject_light": (_I, [C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
+                                C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtAovEmit), _I, _I,
+                                C.POINTER(RtReprojectOpts), C.POINTER(RtFrame), C.POINTER(RtAovEmit)]),
+    "rt_reproject_light_device": (_I, [C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
+                                       C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
+                                       _I, _I, C.POINTER(RtReprojectOpts), C.POINTER(RtFrame),
+                                       C.POINTER(RtAovEmit), _I, C.c_void_p]),
     "rt_demo_scene": (_I, [_P, C.c_char_p, C.c_char_p, C.POINTER(RtCamera), C.POINTER(_I),
                            C.POINTER(_I)]),
     "rt_demo_scene_name": (_I, [_I, C.POINTER(C.c_char_p)]),

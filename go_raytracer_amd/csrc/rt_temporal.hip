@@ -25,9 +25,18 @@
 //                 and the division.  Emit = false is rt_reproject's kernel, instruction for
 //                 instruction (profiles/temporal_emit_device_code.txt).
 //
+//   k_reproject<true, Light> : the third instance, rt_reproject_light's.  Emission and coverage
+//                 are history planes of their own: a second weight sum runs over the light taps
+//                 (the surface taps and the fully covered ones), which blends the taps' emission
+//                 and coverage by the same bilinear weights, and the pixel is re-lit from the
+//                 blended planes, which are written out as the next history's.  It gathers no
+//                 byte that <true, false> does not gather and writes 16 more per pixel.  The two
+//                 other instances are what they were, instruction for instruction
+//                 (profiles/temporal_light_device_code.txt).
+//
 // Bytes per pixel: 36 read of the current frame (28 without var and count planes), up to 4 x 36
 // gathered from the previous one (L1/L2-resident: adjacent lanes share three of four taps), 20
-// written.  Emit: 16 more of the current pixel, 4 x 16 more gathered.
+// written.  Emit: 16 more of the current pixel, 4 x 16 more gathered.  Light: 16 more written.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -63,24 +72,35 @@ struct Planes {  // an rt_frame's buffers
 };
 
 // the emission split's planes of both frames (rt_aov_emit's emission and coverage); no member
-// without it, so that k_reproject<false> takes rt_reproject's arguments
-template <bool Emit>
+// without it, so that k_reproject<false, false> takes rt_reproject's arguments.  Light: the two
+// planes of the new history (either may be NULL)
+template <bool Emit, bool Light>
 struct EmitPlanes {};
 template <>
-struct EmitPlanes<true> {
+struct EmitPlanes<true, false> {
   const float* prev_emission;
   const float* prev_coverage;
   const float* cur_emission;
   const float* cur_coverage;
+};
+template <>
+struct EmitPlanes<true, true> {
+  const float* prev_emission;
+  const float* prev_coverage;
+  const float* cur_emission;
+  const float* cur_coverage;
+  float* out_emission;
+  float* out_coverage;
 };
 
 __device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 __device__ __forceinline__ V3 load3(const float* p, size_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
 __device__ __forceinline__ bool finite3(V3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
 
-template <bool Emit>
+template <bool Emit, bool Light>
 __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Planes cur, Planes out,
-                                                   EmitPlanes<Emit> em) {
+                                                   EmitPlanes<Emit, Light> em) {
+  static_assert(Emit || !Light, "the light history is a history of the emission split's planes");
   const int tile_y = blockIdx.x / P.tiles_x, tile_x = blockIdx.x - tile_y * P.tiles_x;
   const int x = tile_x * kTW + (threadIdx.x & (kTW - 1)), y = tile_y * kTH + (threadIdx.x >> 6);
   if (x >= P.w || y >= P.h) return;
@@ -95,11 +115,19 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
   // samples all saw the light (k = 0) carries no surface radiance and is not valid
   V3 e = {0.0f, 0.0f, 0.0f}, z = c;
   float kc = 1.0f, vz = v;
+  float covc = 0.0f, wc = nc;  // Light: the current coverage, and the weight of the current z
   if constexpr (Emit) {
     e = load3(em.cur_emission, pi);
     const float cov = em.cur_coverage[pi];
-    valid = valid && finite3(e) && cov >= 0.0f && cov < 1.0f;
-    kc = valid ? 1.0f - cov : 1.0f;
+    if constexpr (Light) {  // a fully covered pixel is valid: no surface sample (w_c = 0, divisor 1)
+      valid = valid && finite3(e) && cov >= 0.0f && cov <= 1.0f;
+      covc = cov;
+      wc = cov < 1.0f ? nc : 0.0f;
+      kc = valid && cov < 1.0f ? 1.0f - cov : 1.0f;
+    } else {
+      valid = valid && finite3(e) && cov >= 0.0f && cov < 1.0f;
+      kc = valid ? 1.0f - cov : 1.0f;
+    }
     z = {(c.x - e.x) / kc, (c.y - e.y) / kc, (c.z - e.z) / kc};
     vz = v / (kc * kc);
   }
@@ -128,6 +156,7 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
   const float tol_d = P.depth_tol * d1;
 
   float S = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f, sn = 0.0f;
+  float Sl = 0.0f, ser = 0.0f, seg = 0.0f, seb = 0.0f, sk = 0.0f, sm = 0.0f;  // Light: the light taps' sums
 #pragma unroll
   for (int b = 0; b < 2; ++b) {
 #pragma unroll
@@ -145,10 +174,16 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
                 nx * nx + ny * ny + nz * nz <= P.normal_tol;
       V3 eq = {0.0f, 0.0f, 0.0f};
       float covq = 0.0f;
+      bool okl = false;  // Light: a light tap (a surface tap, or a fully covered one)
       if constexpr (Emit) {
         eq = load3(em.prev_emission, qi);
         covq = em.prev_coverage[qi];
-        ok = ok && finite3(eq) && covq >= 0.0f && covq < 1.0f;  // a NaN coverage fails both
+        if constexpr (Light) {
+          okl = ok && finite3(eq) && covq >= 0.0f && covq <= 1.0f;
+          ok = okl && covq < 1.0f;
+        } else {
+          ok = ok && finite3(eq) && covq >= 0.0f && covq < 1.0f;  // a NaN coverage fails both
+        }
       }
       const float beta = ok ? bu[a] * bv[b] : 0.0f;
       V3 tq = {ok ? cq.x : 0.0f, ok ? cq.y : 0.0f, ok ? cq.z : 0.0f};
@@ -165,7 +200,54 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
       sb += beta * tq.z;
       sv += beta * beta * tv;
       sn += beta * (ok ? cntq : 0.0f);
+      if constexpr (Light) {
+        const float bl = okl ? bu[a] * bv[b] : 0.0f;
+        Sl += bl;
+        ser += bl * (okl ? eq.x : 0.0f);
+        seg += bl * (okl ? eq.y : 0.0f);
+        seb += bl * (okl ? eq.z : 0.0f);
+        sk += bl * (okl ? covq : 0.0f);
+        sm += bl * (okl ? cntq : 0.0f);
+      }
     }
+  }
+  if constexpr (Light) {
+    // n_h from the surface taps, m_h from the light taps; a sum below min_weight is no history of
+    // its kind.  Nothing to blend: neither history, or a pixel covered now (w_c = 0) without
+    // surface history: the inside of a light
+    const bool hs = hist && S >= P.min_weight, hl = hist && Sl >= P.min_weight;
+    V3 o = c, oe = e;
+    float ov = v, on = nc, oc = covc;
+    if ((hs || hl) && (hs || wc > 0.0f)) {
+      // a sum that is no history divides by min_weight (> 0: resolve()) and its weight below is 0;
+      // the maximum leaves a sum that is one untouched, and the division is the other instances'
+      const float inv = 1.0f / fmaxf(S, P.min_weight), invl = 1.0f / fmaxf(Sl, P.min_weight);
+      const float cap = P.max_history > 0.0f ? P.max_history : 8.0f * nc;
+      const float nh = hs ? fminf(sn * inv, cap) : 0.0f, vh = sv * (inv * inv);
+      const float mh = hl ? fminf(sm * invl, cap) : 0.0f;
+      const float n = nh + wc, in = 1.0f / n;
+      // the blend below, with its one fused multiply-add written out as the compiler contracts it in
+      // the two other instances: zero emission and coverage must give rt_reproject's bits
+      o.x = fmaf(wc, z.x, nh * (sr * inv)) * in;
+      o.y = fmaf(wc, z.y, nh * (sg * inv)) * in;
+      o.z = fmaf(wc, z.z, nh * (sb * inv)) * in;
+      ov = fmaf(wc * wc, vz, nh * nh * vh) * (in * in);
+      on = fmaxf(nh, mh) + nc;
+      const float im = 1.0f / (mh + nc);
+      oc = (mh * (sk * invl) + nc * covc) * im;
+      oe = {(mh * (ser * invl) + nc * e.x) * im, (mh * (seg * invl) + nc * e.y) * im,
+            (mh * (seb * invl) + nc * e.z) * im};
+      const float ko = 1.0f - oc;  // re-lit from the blended planes; the light adds no variance
+      o = {ko * o.x + oe.x, ko * o.y + oe.y, ko * o.z + oe.z};
+      ov = ko * ko * ov;
+    }
+    if (out.rgb) out.rgb[3 * pi] = o.x, out.rgb[3 * pi + 1] = o.y, out.rgb[3 * pi + 2] = o.z;
+    if (out.var) out.var[pi] = ov;
+    if (out.count) out.count[pi] = on;
+    if (em.out_emission)
+      em.out_emission[3 * pi] = oe.x, em.out_emission[3 * pi + 1] = oe.y, em.out_emission[3 * pi + 2] = oe.z;
+    if (em.out_coverage) em.out_coverage[pi] = oc;
+    return;
   }
   hist = hist && S >= P.min_weight;
 
@@ -204,14 +286,16 @@ V3 v3_diff(const double* a, const double* b) {  // the difference in fp64, then 
 Planes planes_of(const rt_frame* f) { return {f->rgb, f->var, f->count, f->normal, f->depth}; }
 
 // argument checks of every entry point (before any device is touched) -> the kernel's parameters;
-// emit: the _emit entries, which need both rt_aov_emit with emission and coverage
-int resolve(const char* who, bool emit, const rt_camera* cam_prev, const rt_frame* prev,
+// emit: the _emit and _light entries, which need both rt_aov_emit with emission and coverage;
+// light: the _light entries, which need out_emit (NULL for the others)
+int resolve(const char* who, bool emit, bool light, const rt_camera* cam_prev, const rt_frame* prev,
             const rt_aov_emit* prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
             const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts, const rt_frame* out,
-            TpParams* P) {
+            const rt_aov_emit* out_emit, TpParams* P) {
   if (!cam_prev || !cam_cur) return set_error(RT_ERR_INVALID, "%s: null camera", who);
   if (!prev || !cur || !out) return set_error(RT_ERR_INVALID, "%s: null frame", who);
   if (emit && (!prev_emit || !cur_emit)) return set_error(RT_ERR_INVALID, "%s: null emit", who);
+  if (light && !out_emit) return set_error(RT_ERR_INVALID, "%s: null out_emit", who);
   if (!prev->rgb || !prev->normal || !prev->depth || !cur->rgb || !cur->normal || !cur->depth)
     return set_error(RT_ERR_INVALID, "%s: prev and cur need rgb, normal and depth", who);
   if (emit && (!prev_emit->emission || !prev_emit->coverage || !cur_emit->emission || !cur_emit->coverage))
@@ -232,6 +316,16 @@ int resolve(const char* who, bool emit, const rt_camera* cam_prev, const rt_fram
       for (const float* pb : {prev_emit->emission, prev_emit->surface_albedo, prev_emit->coverage})
         if (ob && ob == pb)
           return set_error(RT_ERR_INVALID, "%s: out aliases a buffer of prev_emit (the taps gather from prev)", who);
+  if (light)
+    for (const float* ob : {out_emit->emission, out_emit->coverage}) {
+      for (const float* pb : prev_bufs)
+        if (ob && ob == pb)
+          return set_error(RT_ERR_INVALID, "%s: out_emit aliases a buffer of prev (the taps gather from prev)", who);
+      for (const float* pb : {prev_emit->emission, prev_emit->surface_albedo, prev_emit->coverage})
+        if (ob && ob == pb)
+          return set_error(RT_ERR_INVALID, "%s: out_emit aliases a buffer of prev_emit (the taps gather from prev)",
+                           who);
+    }
   rt_camera_derived dp, dc;
   int rc = rt_camera_derive(cam_prev, &dp);
   if (rc == RT_OK) rc = rt_camera_derive(cam_cur, &dc);
@@ -260,45 +354,54 @@ int resolve(const char* who, bool emit, const rt_camera* cam_prev, const rt_fram
   return RT_OK;
 }
 
-// emit: the frames' rt_aov_emit (both NULL for rt_reproject's kernel, both checked by resolve)
+// emit: the frames' rt_aov_emit (both NULL for rt_reproject's kernel, both checked by resolve);
+// out_emit: the new history's light planes (rt_reproject_light's kernel), NULL for the others
 int launch(const TpParams& P, const Planes& prev, const Planes& cur, const Planes& out,
-           const rt_aov_emit* prev_emit, const rt_aov_emit* cur_emit, hipStream_t s) {
+           const rt_aov_emit* prev_emit, const rt_aov_emit* cur_emit, const rt_aov_emit* out_emit, hipStream_t s) {
   const int64_t tiles = (int64_t)P.tiles_x * ((P.h + kTH - 1) / kTH);  // < 2^31 / 3: w h is
-  if (prev_emit) {
-    const EmitPlanes<true> em = {prev_emit->emission, prev_emit->coverage, cur_emit->emission, cur_emit->coverage};
-    hipLaunchKernelGGL(k_reproject<true>, dim3((unsigned)tiles), dim3(256), 0, s, P, prev, cur, out, em);
+  if (out_emit) {
+    const EmitPlanes<true, true> em = {prev_emit->emission, prev_emit->coverage, cur_emit->emission,
+                                       cur_emit->coverage,  out_emit->emission,  out_emit->coverage};
+    hipLaunchKernelGGL((k_reproject<true, true>), dim3((unsigned)tiles), dim3(256), 0, s, P, prev, cur, out, em);
+  } else if (prev_emit) {
+    const EmitPlanes<true, false> em = {prev_emit->emission, prev_emit->coverage, cur_emit->emission,
+                                        cur_emit->coverage};
+    hipLaunchKernelGGL((k_reproject<true, false>), dim3((unsigned)tiles), dim3(256), 0, s, P, prev, cur, out, em);
   } else {
-    hipLaunchKernelGGL(k_reproject<false>, dim3((unsigned)tiles), dim3(256), 0, s, P, prev, cur, out,
-                       EmitPlanes<false>{});
+    hipLaunchKernelGGL((k_reproject<false, false>), dim3((unsigned)tiles), dim3(256), 0, s, P, prev, cur, out,
+                       EmitPlanes<false, false>{});
   }
   HIP_OK(hipGetLastError());
   return RT_OK;
 }
 
-// rt_reproject_device and rt_reproject_emit_device (emit)
-int reproject_device(const char* who, bool emit, const rt_camera* cam_prev, const rt_frame* prev,
+// rt_reproject_device, rt_reproject_emit_device (emit) and rt_reproject_light_device (emit, light)
+int reproject_device(const char* who, bool emit, bool light, const rt_camera* cam_prev, const rt_frame* prev,
                      const rt_aov_emit* prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
                      const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
-                     const rt_frame* out, int device, void* stream) {
+                     const rt_frame* out, const rt_aov_emit* out_emit, int device, void* stream) {
   TpParams P;
-  int rc = resolve(who, emit, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out, &P);
+  int rc = resolve(who, emit, light, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out, out_emit,
+                   &P);
   if (rc) return rc;
   if ((rc = device_ok(who, device))) return rc;
   DeviceGuard dg;
   HIP_OK(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  rc = launch(P, planes_of(prev), planes_of(cur), planes_of(out), prev_emit, cur_emit, s);
+  rc = launch(P, planes_of(prev), planes_of(cur), planes_of(out), prev_emit, cur_emit, out_emit, s);
   HIP_OK(hipStreamSynchronize(s));
   return rc;
 }
 
-// rt_reproject and rt_reproject_emit (emit): host pointers, staged through device 0
-int reproject_host(const char* who, bool emit, const rt_camera* cam_prev, const rt_frame* prev,
+// rt_reproject, rt_reproject_emit (emit) and rt_reproject_light (emit, light): host pointers, staged
+// through device 0
+int reproject_host(const char* who, bool emit, bool light, const rt_camera* cam_prev, const rt_frame* prev,
                    const rt_aov_emit* prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
                    const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
-                   const rt_frame* out) {
+                   const rt_frame* out, const rt_aov_emit* out_emit) {
   TpParams P;
-  int rc = resolve(who, emit, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out, &P);
+  int rc = resolve(who, emit, light, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out, out_emit,
+                   &P);
   if (rc) return rc;
   if ((rc = device_ok(who, 0))) return rc;
   DeviceGuard dg;
@@ -307,7 +410,7 @@ int reproject_host(const char* who, bool emit, const rt_camera* cam_prev, const 
   hipStream_t s = nullptr;
   // both frames as 9 planes-floats per pixel each: rgb, var, count, normal, depth, and with emit 4
   // more: emission, coverage.  out is written over cur's copy (out may alias cur), into the var
-  // and count slots also when cur has neither
+  // and count slots also when cur has neither; out_emit over cur_emit's copy
   const size_t n = (size_t)w * h;
   constexpr int kOff[8] = {0, 3, 4, 5, 8, 9, 12, 13};
   const int nbuf = emit ? 7 : 5, per = kOff[nbuf];
@@ -334,10 +437,16 @@ int reproject_host(const char* who, bool emit, const rt_camera* cam_prev, const 
   float* cbase = (float*)stg + (size_t)per * n;
   const Planes o = {out->rgb ? cbase : nullptr, out->var ? cbase + kOff[1] * n : nullptr,
                     out->count ? cbase + kOff[2] * n : nullptr, nullptr, nullptr};
-  rc = launch(P, d[0], d[1], o, emit ? &de[0] : nullptr, emit ? &de[1] : nullptr, s);
+  rt_aov_emit oe = {};
+  if (light) oe = {out_emit->emission ? de[1].emission : nullptr, nullptr, out_emit->coverage ? de[1].coverage : nullptr};
+  rc = launch(P, d[0], d[1], o, emit ? &de[0] : nullptr, emit ? &de[1] : nullptr, light ? &oe : nullptr, s);
   if (!rc && ((o.rgb && hipMemcpyAsync(out->rgb, o.rgb, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess) ||
               (o.var && hipMemcpyAsync(out->var, o.var, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-              (o.count && hipMemcpyAsync(out->count, o.count, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)))
+              (o.count && hipMemcpyAsync(out->count, o.count, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+              (oe.emission &&
+               hipMemcpyAsync(out_emit->emission, oe.emission, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+              (oe.coverage &&
+               hipMemcpyAsync(out_emit->coverage, oe.coverage, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)))
     rc = set_error(RT_ERR_DEVICE, "%s: copy to host failed", who);
   HIP_OK(hipStreamSynchronize(s));  // also after an error: nothing in flight on the staging buffer
   return rc;
@@ -353,28 +462,44 @@ extern "C" {
 int rt_reproject_device(const rt_camera* cam_prev, const rt_frame* prev_dev, const rt_camera* cam_cur,
                         const rt_frame* cur_dev, int w, int h, const rt_reproject_opts* opts,
                         const rt_frame* out_dev, int device, void* stream) {
-  return reproject_device("rt_reproject_device", false, cam_prev, prev_dev, nullptr, cam_cur, cur_dev, nullptr, w, h,
-                          opts, out_dev, device, stream);
+  return reproject_device("rt_reproject_device", false, false, cam_prev, prev_dev, nullptr, cam_cur, cur_dev, nullptr,
+                          w, h, opts, out_dev, nullptr, device, stream);
 }
 
 int rt_reproject(const rt_camera* cam_prev, const rt_frame* prev, const rt_camera* cam_cur,
                  const rt_frame* cur, int w, int h, const rt_reproject_opts* opts, const rt_frame* out) {
-  return reproject_host("rt_reproject", false, cam_prev, prev, nullptr, cam_cur, cur, nullptr, w, h, opts, out);
+  return reproject_host("rt_reproject", false, false, cam_prev, prev, nullptr, cam_cur, cur, nullptr, w, h, opts, out,
+                        nullptr);
 }
 
 int rt_reproject_emit_device(const rt_camera* cam_prev, const rt_frame* prev_dev, const rt_aov_emit* prev_emit_dev,
                              const rt_camera* cam_cur, const rt_frame* cur_dev, const rt_aov_emit* cur_emit_dev,
                              int w, int h, const rt_reproject_opts* opts, const rt_frame* out_dev, int device,
                              void* stream) {
-  return reproject_device("rt_reproject_emit_device", true, cam_prev, prev_dev, prev_emit_dev, cam_cur, cur_dev,
-                          cur_emit_dev, w, h, opts, out_dev, device, stream);
+  return reproject_device("rt_reproject_emit_device", true, false, cam_prev, prev_dev, prev_emit_dev, cam_cur,
+                          cur_dev, cur_emit_dev, w, h, opts, out_dev, nullptr, device, stream);
 }
 
 int rt_reproject_emit(const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
                       const rt_camera* cam_cur, const rt_frame* cur, const rt_aov_emit* cur_emit, int w, int h,
                       const rt_reproject_opts* opts, const rt_frame* out) {
-  return reproject_host("rt_reproject_emit", true, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts,
-                        out);
+  return reproject_host("rt_reproject_emit", true, false, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h,
+                        opts, out, nullptr);
+}
+
+int rt_reproject_light_device(const rt_camera* cam_prev, const rt_frame* prev_dev, const rt_aov_emit* prev_emit_dev,
+                              const rt_camera* cam_cur, const rt_frame* cur_dev, const rt_aov_emit* cur_emit_dev,
+                              int w, int h, const rt_reproject_opts* opts, const rt_frame* out_dev,
+                              const rt_aov_emit* out_emit_dev, int device, void* stream) {
+  return reproject_device("rt_reproject_light_device", true, true, cam_prev, prev_dev, prev_emit_dev, cam_cur,
+                          cur_dev, cur_emit_dev, w, h, opts, out_dev, out_emit_dev, device, stream);
+}
+
+int rt_reproject_light(const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
+                       const rt_camera* cam_cur, const rt_frame* cur, const rt_aov_emit* cur_emit, int w, int h,
+                       const rt_reproject_opts* opts, const rt_frame* out, const rt_aov_emit* out_emit) {
+  return reproject_host("rt_reproject_light", true, true, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h,
+                        opts, out, out_emit);
 }
 
 }  // extern "C"

@@ -13,7 +13,7 @@
 //                   rt_accum_add or rt_accum_select + rt_accum_add_active, rt_accum_info_get,
 //                   rt_accum_resolve, rt_accum_adapt_info, rt_accum_counts; rt_progress on a thread
 //   feature_planes  rt_render_aov[_emit|_media] or rt_accum_resolve_aov[_media]
-//   temporal_step   rt_reproject[_emit] (the host entries: this client links no HIP runtime)
+//   temporal_step   rt_reproject[_emit | _light] (the host entries: this client links no HIP runtime)
 //   filter          rt_denoise[_var][_emit]
 //   write_aovs      rt_format_ppm per plane
 //   finish_frame    rt_format_ppm, the statistics line (-cpuprofile has no pprof to drive on the
@@ -55,6 +55,7 @@ struct Args {
   unsigned long long seed = 1, tree_seed = 1;
   bool progress = false, stats = false, denoise = false, denoise_var = false, split_emitters = false;
   bool accum_features = false, temporal = false, temporal_emit = false, aov_media = false, aov_specular = false;
+  bool temporal_light = false;
   long long frames = 0, spec_bounces = 0;
   double spec_fuzz = 0.0;
   double orbit = 0.0;
@@ -111,6 +112,8 @@ std::vector<Flag> flags(Args& a) {
        Flag::BOOL, &a.temporal, ""},
       {"temporal-emit", "as -temporal, with directly seen lights kept out of the history (rt_reproject_emit); needs -split-emitters too",
        Flag::BOOL, &a.temporal_emit, ""},
+      {"temporal-light", "as -temporal-emit, with emission and coverage carried as history planes too and the blended planes handed to the split filter (rt_reproject_light); instead of -temporal / -temporal-emit",
+       Flag::BOOL, &a.temporal_light, ""},
       {"tree-seed", "seed of the scene builder's rand (main.go's math/rand)", Flag::U64,
        &a.tree_seed, "1"},
       {"until", "add passes until the image's relative standard error is <= E (at most -passes, default 1024)",
@@ -237,6 +240,7 @@ struct Job {
   bool specular = false;  // the guides are of the first diffuse hit (rt_render_aov_spec)
   Filter filter = Filter::NONE;
   bool temporal = false, temporal_emit = false, want_var = false;
+  bool temporal_light = false;  // the temporal stage through rt_reproject_light
   bool counts = false, aov = false, print_stats = false;
   bool numbered = false;  // -frames: frame k goes to the -o name with _00k before the extension
   int n_frames = 1;
@@ -258,6 +262,10 @@ int make_job(const Args& a, const char* prog, Job& j) {
        "-temporal needs -accum-features and -passes, -until or -adaptive"},
       {a.temporal_emit && !(a.split_emitters && a.accum_features && acc),  // no emit planes
        "-temporal-emit needs -split-emitters, -accum-features and -passes, -until or -adaptive"},
+      // the emit planes as -temporal-emit; a stage of its own, not a modifier of the two others
+      {a.temporal_light && (!(a.split_emitters && a.accum_features && acc) || a.temporal || a.temporal_emit),
+       "-temporal-light needs -split-emitters, -accum-features and -passes, -until or -adaptive, and neither -temporal "
+       "nor -temporal-emit"},
       {a.aov_media && !(filtered || !a.aov.empty() || a.accum_features),  // no feature buffers
        "-aov-media needs -aov, -denoise, -denoise-var or -accum-features"},
       {a.aov_specular && !(filtered || !a.aov.empty()), "-aov-specular needs -aov, -denoise or -denoise-var"},
@@ -278,7 +286,8 @@ int make_job(const Args& a, const char* prog, Job& j) {
   j.passes_ok = !(a.passes < 0 || a.passes > 0x7FFFFFFF || !(a.until >= 0.0));  // reported once the scene is built
   j.pass_cap = (int32_t)(a.passes > 0 ? a.passes : 1024);
   j.temporal_emit = a.temporal_emit;
-  j.temporal = a.temporal || a.temporal_emit;  // the same stage, through rt_reproject_emit
+  j.temporal_light = a.temporal_light;
+  j.temporal = a.temporal || a.temporal_emit || a.temporal_light;  // the same stage, through rt_reproject_emit / _light
   j.aov = !a.aov.empty();
   if (filtered || j.aov || j.temporal) j.source = a.accum_features ? Features::ACCUM : Features::PASS;
   j.accum_features = a.accum_features;
@@ -351,6 +360,7 @@ struct Ctx {
   double ms_accum = 0.0, ms_aov = 0.0, ms_denoise = 0.0, ms_reproject = 0.0;
   // -temporal: the history (the frames before this one, reprojected and blended) and its camera
   std::vector<float> h_rgb, h_var, h_count, h_normal, h_depth, h_emission, h_coverage, count;
+  std::vector<float> l_emission, l_coverage;  // -temporal-light: the blended light planes of this frame
   rt_camera h_cam;
   bool have_history = false;
 
@@ -397,7 +407,7 @@ struct Stats {
   int aov_samples;
   const rt_accum_info* acc;    // -passes / -until / -adaptive, else null
   const rt_adapt_info* adapt;  // -adaptive, else null
-  bool denoise_var, split_emitters, accum_features, temporal, temporal_emit, aov_media, aov_specular;
+  bool denoise_var, split_emitters, accum_features, temporal, temporal_emit, temporal_light, aov_media, aov_specular;
   int frame;  // -frames, else -1
 };
 
@@ -437,6 +447,7 @@ std::string stats_json(const Stats& s) {
   if (s.frame >= 0) appendf(b, "\"frame\": %d, ", s.frame);
   if (s.temporal) appendf(b, "\"temporal\": 1, \"ms_reproject\": %.3f, ", s.ms_reproject);
   if (s.temporal_emit) b += "\"temporal_emit\": 1, ";
+  if (s.temporal_light) b += "\"temporal_light\": 1, ";
   if (s.aov_media) b += "\"aov_media\": 1, ";
   if (s.aov_specular) b += "\"aov_specular\": 1, ";
   appendf(b, "\"wall_s\": %.3f}", s.wall_s);
@@ -622,14 +633,19 @@ int temporal_step(const Job& j, Ctx& c) {
   const auto tr = std::chrono::steady_clock::now();
   const int w = c.d.width, h = c.d.height;
   c.count.assign(c.n_px(), (float)c.ai.passes);
+  if (j.temporal_light) c.l_emission = c.emission, c.l_coverage = c.coverage;  // the first frame's are its own
   if (c.have_history) {
     const rt_frame prev = {c.h_rgb.data(), c.h_var.data(), c.h_count.data(), c.h_normal.data(), c.h_depth.data(), 0.0f, 0};
     const rt_frame cur = {c.rgb.data(), c.var.data(), nullptr, c.normal.data(), c.depth.data(), (float)c.ai.passes, 0};
     const rt_frame res = {c.rgb.data(), c.var.data(), c.count.data(), nullptr, nullptr, 0.0f, 0};
     const rt_aov_emit prev_emit = {c.h_emission.data(), nullptr, c.h_coverage.data()};
     const rt_aov_emit cur_emit = {c.emission.data(), nullptr, c.coverage.data()};
+    const rt_aov_emit res_emit = {c.l_emission.data(), nullptr, c.l_coverage.data()};
     Call s;
-    if (j.temporal_emit)
+    if (j.temporal_light)
+      s.ok("rt_reproject_light",
+           rt_reproject_light(&c.h_cam, &prev, &prev_emit, &c.cam, &cur, &cur_emit, w, h, nullptr, &res, &res_emit));
+    else if (j.temporal_emit)
       s.ok("rt_reproject_emit",
            rt_reproject_emit(&c.h_cam, &prev, &prev_emit, &c.cam, &cur, &cur_emit, w, h, nullptr, &res));
     else
@@ -638,6 +654,7 @@ int temporal_step(const Job& j, Ctx& c) {
   }
   c.h_rgb = c.rgb, c.h_var = c.var, c.h_count = c.count, c.h_normal = c.normal, c.h_depth = c.depth;
   if (j.temporal_emit) c.h_emission = c.emission, c.h_coverage = c.coverage;
+  if (j.temporal_light) c.h_emission = c.l_emission, c.h_coverage = c.l_coverage;
   c.h_cam = c.cam;
   c.have_history = true;
   c.ms_reproject = ms_since(tr);
@@ -649,7 +666,10 @@ int filter(const Job& j, Ctx& c) {
   if (j.filter == Filter::NONE) return 0;
   const int w = c.d.width, h = c.d.height;
   const rt_aov f = c.guides();
-  const rt_aov_emit fe = c.emit_planes();
+  // -temporal-light: rgb was re-lit from the blended planes, so rgb - emission is the surface part
+  // only with them
+  const rt_aov_emit fe = j.temporal_light ? rt_aov_emit{c.l_emission.data(), c.salbedo.data(), c.l_coverage.data()}
+                                          : c.emit_planes();
   float* rgb = c.rgb.data();
   rt_denoise_var_opts vopt;
   rt_denoise_opts dopt;
@@ -699,7 +719,7 @@ int finish_frame(const Job& j, Ctx& c) {
   s.acc = j.accumulate ? &c.ai : nullptr;
   s.adapt = j.adaptive ? &c.adi : nullptr;
   s.denoise_var = j.filter == Filter::VAR, s.split_emitters = j.emit, s.accum_features = j.accum_features;
-  s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.aov_media = j.media, s.aov_specular = j.specular;
+  s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.temporal_light = j.temporal_light, s.aov_media = j.media, s.aov_specular = j.specular;
   s.frame = j.numbered ? c.frame : -1;
   const std::string js = stats_json(s);
   if (j.print_stats) fprintf(stderr, "%s\n", js.c_str());

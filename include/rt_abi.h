@@ -1037,6 +1037,61 @@ int rt_reproject_emit_device(const rt_camera* cam_prev, const rt_frame* prev_dev
                              const rt_reproject_opts* opts, const rt_frame* out_dev, int device,
                              void* stream);
 
+/* rt_reproject_emit with emission and coverage carried as history planes of their own (DESIGN.md
+ * "Light history").  rt_reproject_emit re-lights a pixel with the current frame's emission and
+ * coverage, so on the rim of a light, where coverage is a fraction estimated from a few samples, no
+ * history improves the pixel.  Here both planes are reprojected and blended with the weights of the
+ * surface radiance, and the pixel is re-lit from the blend.  Added without an ABI version change:
+ * detect by the symbols.  out_emit: the new history's light planes, emission and coverage; either
+ * may be NULL = not wanted; surface_albedo is never read or written.
+ * The definition is rt_reproject_emit's with exactly these changes.  Per frame and pixel let
+ * kappa = coverage, E = emission, z = (rgb - E) / (1 - kappa), v_z = var / (1 - kappa)^2.
+ *   current pixel valid: rgb and var finite, n_c finite and > 0, E_c finite, 0 <= kappa_c <= 1: a
+ *     fully covered pixel is valid.  It has no surface sample: its weight in the surface blend is
+ *     w_c = 0 and the divisor of its z_c and v_z,c is taken as 1; otherwise w_c = n_c.  An invalid
+ *     pixel passes through: out takes its rgb, var and count, out_emit its emission and coverage,
+ *     bit for bit.
+ *   history lookup: rt_reproject's (depth, normal, s, the four taps and their beta).
+ *   light tap: rt_reproject's tap rule (inside the image, rgb_q and var_q finite, n_q finite and
+ *     > 0, depth_q > 0, the depth and normal tolerances), and E_q finite and 0 <= kappa_q <= 1.
+ *   surface tap: a light tap with kappa_q < 1: exactly rt_reproject_emit's tap.  A fully covered
+ *     previous pixel is a light tap and not a surface tap.
+ *   An invalid tap's values are selected to 0 (its divisor to 1) before any arithmetic.
+ *   surface history, over the surface taps: S_z = sum beta, z_h = sum beta z_q / S_z, v_h = sum
+ *     beta^2 v_z,q / S_z^2, n_h = min(sum beta n_q / S_z, cap), cap = max_history or 8 n_c;
+ *     n_h = 0 when S_z < min_weight.
+ *   light history, over the light taps: S_l = sum beta, E_h = sum beta E_q / S_l, kappa_h = sum
+ *     beta kappa_q / S_l, m_h = min(sum beta n_q / S_l, cap); m_h = 0 when S_l < min_weight.
+ *   pass-through, all five planes bit for bit: n_h = 0 and m_h = 0 (no history); or n_h + w_c = 0
+ *     (covered now and no surface history: the inside of a light).
+ *   blend, every other pixel:
+ *     z_blend = (n_h z_h + w_c z_c) / (n_h + w_c),
+ *     v_blend = (n_h^2 v_h + w_c^2 v_z,c) / (n_h + w_c)^2,
+ *     kappa_out = (m_h kappa_h + n_c kappa_c) / (m_h + n_c),
+ *     E_out = (m_h E_h + n_c E_c) / (m_h + n_c),
+ *     out.rgb = (1 - kappa_out) z_blend + E_out,   out.var = (1 - kappa_out)^2 v_blend,
+ *     out.count = max(n_h, m_h) + n_c,   out_emit = E_out, kappa_out.
+ *   out.var is rt_reproject_emit's rule: the light adds no variance.  Where coverage is a
+ *   fraction (a rim) the blended coverage is itself an estimate whose variance is not counted:
+ *   out.var is knowingly too small there.
+ * The operations run in rt_reproject_emit's order: subtract, divide, then multiply-add.  With
+ * emission = 0 and coverage = 0 in both frames every light tap is a surface tap, m_h = n_h, and
+ * rgb, var and count are rt_reproject's bit for bit; out_emit is all zero.
+ * Argument checks, before any device is touched: rt_reproject_emit's, and RT_ERR_INVALID for a
+ * NULL out_emit and for an out_emit emission or coverage that is a buffer of prev or prev_emit.
+ * out and out_emit may alias cur's and cur_emit's buffers (the current pixel is read whole before
+ * any write).  Host and device forms as rt_reproject's; rt_reproject_light stages 104 bytes per
+ * pixel.  Two calls give identical bits. */
+int rt_reproject_light(const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
+                       const rt_camera* cam_cur, const rt_frame* cur, const rt_aov_emit* cur_emit,
+                       int w, int h, const rt_reproject_opts* opts, const rt_frame* out,
+                       const rt_aov_emit* out_emit);
+int rt_reproject_light_device(const rt_camera* cam_prev, const rt_frame* prev_dev,
+                              const rt_aov_emit* prev_emit_dev, const rt_camera* cam_cur,
+                              const rt_frame* cur_dev, const rt_aov_emit* cur_emit_dev, int w, int h,
+                              const rt_reproject_opts* opts, const rt_frame* out_dev,
+                              const rt_aov_emit* out_emit_dev, int device, void* stream);
+
 /* Demo scenes mirroring main.go (by name or the main.go -S number).
  * names: book1, book2, book3, simple_light, quads, cornell, cornell_smoke, model
  * The camera receives the scene's settings; override fields afterwards. */

@@ -6,7 +6,8 @@ rt_denoise_var_device (5 iterations, all guides) on the same frame and against a
 copy of the bytes the reprojection moves (about 100 per pixel, read and written: 50 copied),
 alternated call by call: HIP events around each blocking call, 5 warm-up rounds, then the median
 (min, max) of 25.  rt_reproject_emit_device (the accumulators with features="emit", their emission
-and coverage planes in both frames) is timed in the same alternation.
+and coverage planes in both frames) is timed in the same alternation, and so is
+rt_reproject_light_device (the same reads, 16 more bytes written per pixel).
 
 quality: Cornell 128 x 128, an 8-frame orbit of 1 degree per frame, 2 passes x 4 spp per frame
 (features="emit"), against a 1024-spp render of the last camera: mean squared error of the last
@@ -15,7 +16,10 @@ guided filter on the temporal result, over every pixel, over the rim pixels of d
 lights (0 < coverage < 1), over the pixels that found history, and split into the pixels within
 2 of a directly seen light (the bilinear taps mix the emitter into its coplanar surroundings:
 depth and normal cannot tell them apart) and the pixels elsewhere.  The same orbit is pushed through
-Temporal(split_emitters=True) as well: the columns temporal_emit and temporal_emit_guided_filter.
+Temporal(split_emitters=True) as well: the columns temporal_emit and temporal_emit_guided_filter;
+and through Temporal(split_emitters=True, light_history=True), whose filter is given the blended
+emission and coverage: the columns temporal_light and temporal_light_guided_filter.  rim_share_of_
+squared_error is, per column, the rim pixels' part of the summed squared error over all pixels.
 
 Prints one JSON object; -o FILE also writes it.
 """
@@ -80,6 +84,8 @@ def bench_time(width, rounds, warm):
     out = {k: torch.empty_like(cur[k]) for k in ("rgb", "var")}
     out["count"] = torch.empty((width, width), device=dev)
     out_e = {k: torch.empty_like(v) for k, v in out.items()}
+    out_l = {k: torch.empty_like(v) for k, v in out.items()}
+    out_l.update({k: torch.empty_like(cur[k]) for k in ("emission", "coverage")})
     plain = [{k: v for k, v in f.items() if k not in ("emission", "coverage")} for f in (prev, cur)]
     n = width * width
     src = torch.empty(n * 50 // 4, dtype=torch.float32, device=dev).normal_()
@@ -88,6 +94,7 @@ def bench_time(width, rounds, warm):
     calls = {
         "reproject": lambda: rt.reproject_device(cams[0], plain[0], cams[1], dict(plain[1], count=2.0), out=out),
         "reproject_emit": lambda: rt.reproject_emit_device(cams[0], prev, cams[1], dict(cur, count=2.0), out=out_e),
+        "reproject_light": lambda: rt.reproject_light_device(cams[0], prev, cams[1], dict(cur, count=2.0), out=out_l),
         "denoise_var": lambda: rt.denoise_var_device(cur["rgb"], cur["var"], aov, out=den, var_out=vout),
         "copy_50_bytes_per_pixel": lambda: (dst.copy_(src), torch.cuda.synchronize()),
     }
@@ -100,7 +107,9 @@ def bench_time(width, rounds, warm):
     found = float((out["count"] > 2.0).float().mean().item())
     return {"image": f"cornell {width}x{width}", "rounds": rounds, "warmup_rounds": warm,
             "ms_median_min_max": {k: stat(v) for k, v in ms.items()},
-            "bytes_per_pixel_nominal": 100, "bytes_per_pixel_nominal_emit": 180, "history_found_share": found,
+            "bytes_per_pixel_nominal": 100, "bytes_per_pixel_nominal_emit": 180, "bytes_per_pixel_nominal_light": 196,
+            "history_found_share": found,
+            "history_found_share_light": float((out_l["count"] > 2.0).float().mean().item()),
             "history_found_share_emit": float((out_e["count"] > 2.0).float().mean().item()),
             "note": "HIP events around each blocking call (launch, kernel and the stream synchronise)"}
 
@@ -109,6 +118,7 @@ def bench_quality(width, frames, degrees, ref_spp):
     t, cam, w, l = rt.demo_scene("cornell")
     cam.Width, cam.SamplesPerPixel = width, 4
     temporal, split = rt.Temporal(), rt.Temporal(split_emitters=True)
+    light = rt.Temporal(split_emitters=True, light_history=True)
     with rt.Scene(t, w, l) as sc:
         for k in range(frames):
             camk = orbit(cam, degrees * k)
@@ -117,6 +127,7 @@ def bench_quality(width, frames, degrees, ref_spp):
                 acc.add(10 * k + 2)
                 rgb, var, count = temporal.push(acc)
                 rgb_e, var_e, count_e = split.push(acc)
+                rgb_l, var_l, count_l = light.push(acc)
                 if k == frames - 1:
                     mean, _ = acc.resolve()
                     aov = acc.resolve_aov_device()
@@ -126,6 +137,9 @@ def bench_quality(width, frames, degrees, ref_spp):
                     both_e = rt.denoise_var_device(rgb_e, var_e, aov, split_emitters=True).cpu().numpy()
                     temp, cnt = rgb.cpu().numpy(), count.cpu().numpy()
                     temp_e, cnt_e = rgb_e.cpu().numpy(), count_e.cpu().numpy()
+                    both_l = rt.denoise_var_device(rgb_l, var_l, dict(aov, **light.light),
+                                                   split_emitters=True).cpu().numpy()
+                    temp_l, cnt_l = rgb_l.cpu().numpy(), count_l.cpu().numpy()
         camk.SamplesPerPixel = ref_spp
         ref, _ = sc.render(camk, seed=977)
     fin = np.isfinite(mean).all(-1) & np.isfinite(ref).all(-1)
@@ -135,13 +149,17 @@ def bench_quality(width, frames, degrees, ref_spp):
         near = np.logical_or.reduce([pad[dy:dy + width, dx:dx + width] for dy in range(3) for dx in range(3)])
     sets = {"all": fin, "rim": fin & (cover > 0) & (cover < 1), "with_history": fin & (cnt > 2.0),
             "within_2_of_a_light": fin & near, "elsewhere": fin & ~near}
-    cols = {"per_frame_mean": mean, "temporal": temp, "temporal_emit": temp_e, "guided_filter": only,
-            "temporal_guided_filter": both, "temporal_emit_guided_filter": both_e}
+    cols = {"per_frame_mean": mean, "temporal": temp, "temporal_emit": temp_e, "temporal_light": temp_l,
+            "guided_filter": only, "temporal_guided_filter": both, "temporal_emit_guided_filter": both_e,
+            "temporal_light_guided_filter": both_l}
+    sq = {c: (x.astype(np.float64) - ref) ** 2 for c, x in cols.items()}
     return {"image": f"cornell {width}x{width}", "frames": frames, "degrees_per_frame": degrees,
             "passes_per_frame": 2, "spp_per_pass": 4, "reference_spp": ref_spp,
             "pixels": {k: int(m.sum()) for k, m in sets.items()},
             "history_found_share": float((cnt > 2.0).mean()), "mean_count": float(cnt.mean()),
             "history_found_share_emit": float((cnt_e > 2.0).mean()), "mean_count_emit": float(cnt_e.mean()),
+            "history_found_share_light": float((cnt_l > 2.0).mean()), "mean_count_light": float(cnt_l.mean()),
+            "rim_share_of_squared_error": {c: float(v[sets["rim"]].sum() / v[fin].sum()) for c, v in sq.items()},
             "mse": {s: {c: float(((x[m].astype(np.float64) - ref[m]) ** 2).mean()) if m.any() else None
                         for c, x in cols.items()} for s, m in sets.items()}}
 
