@@ -494,6 +494,13 @@ class Scene:
         check(lib().rt_scene_plan_early(self._p, device, C.byref(k)))
         return k.value
 
+    def plan_cost(self, device=0):
+        """1 when that launch takes the early-draw kernel's lean-cost twin (rt_scene_plan_cost;
+        honours RT_LEAN_COST), else 0."""
+        k = C.c_int32()
+        check(lib().rt_scene_plan_cost(self._p, device, C.byref(k)))
+        return k.value
+
     MODES = {"auto": 0, "wavefront": 1, "fused": 2}
 
     @staticmethod

@@ -261,6 +261,7 @@ SIGNATURES = {
     "rt_scene_plan_light": (_I, [_P, _I, C.POINTER(C.c_int32)]),
     "rt_scene_lean_emitter": (_I, [_P, C.POINTER(C.c_int32)]),
     "rt_scene_plan_early": (_I, [_P, _I, C.POINTER(C.c_int32)]),
+    "rt_scene_plan_cost": (_I, [_P, _I, C.POINTER(C.c_int32)]),
     "rt_render": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_void_p,
                        C.POINTER(RtStats)]),
     "rt_render_device": (_I, [_P, C.POINTER(RtCamera), C.POINTER(RtRenderOpts), C.c_void_p,

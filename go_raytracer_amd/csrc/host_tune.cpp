@@ -56,7 +56,8 @@ constexpr Knob kKnobs[] = {
     {"RT_BRUTE_SHAPE", false, 'i', 0, 1},      // 0: the generic record loop for listed layouts too
     {"RT_LEAN_LIGHT", false, 'i', 0, 1},       // 0: the general light code for lean light kinds too
     {"RT_LEAN_EARLY_DRAW", false, 'i', 0, 1},  // 0: the lean light kernel that draws after the winner is resolved
-    {"RT_QBVH", false, 'i', 0, 1},           // 0: 128-B BVH4 nodes instead of the compressed 64-B ones
+    {"RT_LEAN_COST", false, 'i', 0, 1},        // 0: the early-draw kernel without the round-10 per-round cuts
+    {"RT_QBVH", false, 'i', 0, 1},          // 0: 128-B BVH4 nodes instead of the compressed 64-B ones
     {"RT_CHUNK_NEED", false, 'i', 1, 1048576},      // chunks per lane that pick the chunk size
     {"RT_TAIL_FRAC", false, 'i', -1, 1024},       // tail phase: 1 / fraction of the samples
     {"RT_TAIL_K", false, 'i', 1, 4096},          // tail phase chunk size

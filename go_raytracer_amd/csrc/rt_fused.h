@@ -154,9 +154,15 @@ __shared__ unsigned long long g_dinfo[4][3];  // ... and then: samples left, bus
 // EARLY (a listed SHAPE with a lean light kind only; the kernel table has it for shape 1): the vertex's
 // Philox draw is issued before the record loop's winner is resolved (rt_path.h shade_core);
 // P.ll.f[11] is the emitter slot (rt_device.h LeanLight)
-template <bool LDS, uint32_t FT, int TREE, int SHAPE = 0, int LIGHT = 0, bool MAP = false, bool EARLY = false>
+// COST (the early-draw kernel only; RT_LEAN_COST=0 takes its COST = false twin): the per-round
+// path without the tree scheduler's state (below), DESIGN.md §4 "The round without the tree
+// scheduler's state".  The same operations on the same operands: the same image, segments and
+// samples bit for bit.
+template <bool LDS, uint32_t FT, int TREE, int SHAPE = 0, int LIGHT = 0, bool MAP = false, bool EARLY = false,
+          bool COST = false>
 __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) {
   static_assert(!EARLY || (SHAPE != 0 && LIGHT != 0 && !MAP), "early draw: a listed shape with a lean light kind");
+  static_assert(!COST || (EARLY && TREE == 0), "lean cost cuts: the early-draw record-loop kernel only");
   static_assert(SHAPE == 0 || (LDS && FT == 0u && TREE == 0), "shapes: the lean LDS record loop only");
   static_assert(LIGHT == 0 || (LDS && FT == 0u && TREE == 0), "light kinds: the lean LDS record loop only");
   static_assert(LIGHT >= 0 && LIGHT < kLeanLightCount, "light kinds: unlisted kind");
@@ -210,7 +216,7 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
     if (c != 0xFFFFFFFFu) {
       start_sample<false, cam_mode(FT), FT == 0u && TREE == 0, MAP>(P, slot, s, c, j0);
       if (j0) s.flags = F_SPLIT | (n0 << kCountShift);
-      trav_init<FT>(P.sc, s.o, s.d, s.time, tr);
+      if constexpr (!COST) trav_init<FT>(P.sc, s.o, s.d, s.time, tr);
       has = true;
     }
     PH_ADD(PH_GRAB, t_grab);
@@ -232,6 +238,25 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
     }
 #endif
     if (!__any(has)) break;
+    if constexpr (COST) {
+      // The record loop always finishes in its one call, so a lane with a path is traversing
+      // and ready in the same round: no tr.cur to carry and test, no ready ballot, count or
+      // busy vote, no shade_min compare, no copy of tr.best, and no trav_init after a vertex
+      // (its reciprocals and stack resets feed the tree steps only; trav_brute takes its own
+      // rcp(d.y) and starts from the {inf, 0, 0, none} hit set here).
+      if (has) {
+        tr.best = {kInf, 0.0f, 0.0f, PRIM_NONE};
+        trav_brute<FT, !LDS, SHAPE, EARLY>(P.sc, lnodes, s.o, s.d, s.time, 0.001f, tr);
+      }
+      // (nothing scheduled across: with the loop's tail and the vertex's head interleaved the
+      // kernel took 77 VGPRs and 11 SGPR spills, with the barrier 75 and 8)
+      __builtin_amdgcn_sched_barrier(0);
+      if (has) {
+        ++s.segs;
+        if (shade_core<false, FT, LIGHT, SHAPE>(P, slot, s, tr.best, ws, sa, lnodes) == OUT_NEED_CHUNK) has = false;
+      }
+      continue;
+    }
     PH_T(t_trav);
     if (has && tr.cur != TRAV_DONE)
     {
@@ -315,7 +340,7 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
 
 // ------------------------------------------------------------ the kernel table ---
 // Every k_fused instance the library compiles, once: X(LDS, FT, TREE, SHAPE, LIGHT, MAP, EARLY,
-// unit).  `unit` is the translation unit that compiles the row: DEF rt_render.hip (instantiated
+// COST, unit).  `unit` is the translation unit that compiles the row: DEF rt_render.hip (instantiated
 // by the dispatcher), ILP rt_fused_sets.hip (LLVM's iterative-ILP machine scheduler, Makefile),
 // MAP rt_fused_map.hip (the default scheduler; a unit of its own so the build stays parallel).
 // The explicit instantiations of the ILP and MAP units, rt_render.hip's `extern template`
@@ -325,88 +350,90 @@ __global__ __launch_bounds__(256, fused_waves(FT, TREE)) void k_fused(Params P) 
 //
 // The record loop (TREE 0) and its lean LDS kernels: per listed layout (SHAPE, rt_device.h
 // brute_shape), per lean light kind (LIGHT), and the early-draw variant (EARLY) for shape 1 with
-// light kind 1 only.  Shape 2 has no early-draw kernel: it compiled to 9 SGPR spills against
-// the 8 of its (2, 1) kernel and was not measured, DESIGN.md §9.  The generic loop has no
-// light-kind kernel: the dispatcher returns nullptr and the planner takes kind 0.
-#define RT_FUSED_ROWS_RECORD_LOOP(X)                           \
-  X(true, kFtSets[0], 0, 1, 1, false, true, DEF)               \
-  X(true, kFtSets[0], 0, 1, 1, false, false, DEF)              \
-  X(true, kFtSets[0], 0, 2, 1, false, false, DEF)              \
-  X(true, kFtSets[0], 0, 1, 0, false, false, DEF)              \
-  X(true, kFtSets[0], 0, 2, 0, false, false, DEF)              \
-  X(true, kFtSets[0], 0, 0, 0, false, false, DEF)              \
-  X(true, kFtSets[1], 0, 0, 0, false, false, DEF)              \
-  X(false, kFtSets[0], 0, 0, 0, false, false, DEF)             \
-  X(false, kFtSets[1], 0, 0, 0, false, false, DEF)
+// light kind 1 only, and that kernel's lean-cost twin (COST, the default).  Shape 2 has no
+// early-draw kernel: it compiled to 9 SGPR spills against the 8 of its (2, 1) kernel and was not
+// measured, DESIGN.md §9.  The generic loop has no light-kind kernel: the dispatcher returns
+// nullptr and the planner takes kind 0.
+#define RT_FUSED_ROWS_RECORD_LOOP(X)                                  \
+  X(true, kFtSets[0], 0, 1, 1, false, true, true, DEF)                \
+  X(true, kFtSets[0], 0, 1, 1, false, true, false, DEF)               \
+  X(true, kFtSets[0], 0, 1, 1, false, false, false, DEF)              \
+  X(true, kFtSets[0], 0, 2, 1, false, false, false, DEF)              \
+  X(true, kFtSets[0], 0, 1, 0, false, false, false, DEF)              \
+  X(true, kFtSets[0], 0, 2, 0, false, false, false, DEF)              \
+  X(true, kFtSets[0], 0, 0, 0, false, false, false, DEF)              \
+  X(true, kFtSets[1], 0, 0, 0, false, false, false, DEF)              \
+  X(false, kFtSets[0], 0, 0, 0, false, false, false, DEF)             \
+  X(false, kFtSets[1], 0, 0, 0, false, false, false, DEF)
 // BVH2 kernels exist for the two smallest sets with the tree in LDS (tiny scenes)
-#define RT_FUSED_ROWS_BVH2(X)                                  \
-  X(true, kFtSets[0], 2, 0, 0, false, false, DEF)              \
-  X(true, kFtSets[1], 2, 0, 0, false, false, DEF)
+#define RT_FUSED_ROWS_BVH2(X)                                         \
+  X(true, kFtSets[0], 2, 0, 0, false, false, false, DEF)              \
+  X(true, kFtSets[1], 2, 0, 0, false, false, false, DEF)
 // The BVH4, every set.  The C5 mesh set ([2]) and the C3 sphere set ([3]) take the ILP
 // scheduler: C5 -0.6 / -1.0 %, C3 -0.8 %, images bit-identical; the same strategy costs the C2
 // kernel 3.5 % (profiles/r3_sched_strategy_ab.jsonl, r3_split_ilp_ab.jsonl).
-#define RT_FUSED_ROWS_BVH4(X)                                  \
-  X(true, kFtSets[0], 4, 0, 0, false, false, DEF)              \
-  X(false, kFtSets[0], 4, 0, 0, false, false, DEF)             \
-  X(true, kFtSets[1], 4, 0, 0, false, false, DEF)              \
-  X(false, kFtSets[1], 4, 0, 0, false, false, DEF)             \
-  X(true, kFtSets[2], 4, 0, 0, false, false, ILP)              \
-  X(false, kFtSets[2], 4, 0, 0, false, false, ILP)             \
-  X(true, kFtSets[3], 4, 0, 0, false, false, ILP)              \
-  X(false, kFtSets[3], 4, 0, 0, false, false, ILP)             \
-  X(true, kFtSets[4], 4, 0, 0, false, false, DEF)              \
-  X(false, kFtSets[4], 4, 0, 0, false, false, DEF)             \
-  X(true, FT_ALL, 4, 0, 0, false, false, DEF)                  \
-  X(false, FT_ALL, 4, 0, 0, false, false, DEF)
+#define RT_FUSED_ROWS_BVH4(X)                                         \
+  X(true, kFtSets[0], 4, 0, 0, false, false, false, DEF)              \
+  X(false, kFtSets[0], 4, 0, 0, false, false, false, DEF)             \
+  X(true, kFtSets[1], 4, 0, 0, false, false, false, DEF)              \
+  X(false, kFtSets[1], 4, 0, 0, false, false, false, DEF)             \
+  X(true, kFtSets[2], 4, 0, 0, false, false, false, ILP)              \
+  X(false, kFtSets[2], 4, 0, 0, false, false, false, ILP)             \
+  X(true, kFtSets[3], 4, 0, 0, false, false, false, ILP)              \
+  X(false, kFtSets[3], 4, 0, 0, false, false, false, ILP)             \
+  X(true, kFtSets[4], 4, 0, 0, false, false, false, DEF)              \
+  X(false, kFtSets[4], 4, 0, 0, false, false, false, DEF)             \
+  X(true, FT_ALL, 4, 0, 0, false, false, false, DEF)                  \
+  X(false, FT_ALL, 4, 0, 0, false, false, false, DEF)
 // The compressed BVH4 (TREE 5): trees read through L1/L2 only.  Not in the ILP unit: at 5 waves
 // per SIMD the ILP scheduler spilled 6 / 26 VGPRs in the [2] / [3] kernels against 1 / 2 with the
 // default one, and the default one renders C3 5.5 % and C5 0.3 % faster (bit-identical,
 // profiles/r5_q_sched_ab.jsonl).  (book2's kernel with the ILP scheduler: C4 +0.7 %,
 // r5_book2_sched_ab.jsonl)
-#define RT_FUSED_ROWS_QBVH(X)                                  \
-  X(false, kFtSets[2], 5, 0, 0, false, false, DEF)             \
-  X(false, kFtSets[3], 5, 0, 0, false, false, DEF)             \
-  X(false, kFtSets[4], 5, 0, 0, false, false, DEF)             \
-  X(false, FT_ALL, 5, 0, 0, false, false, DEF)
+#define RT_FUSED_ROWS_QBVH(X)                                         \
+  X(false, kFtSets[2], 5, 0, 0, false, false, false, DEF)             \
+  X(false, kFtSets[3], 5, 0, 0, false, false, false, DEF)             \
+  X(false, kFtSets[4], 5, 0, 0, false, false, false, DEF)             \
+  X(false, FT_ALL, 5, 0, 0, false, false, false, DEF)
 // The BVH8 (measured slower than the BVH4): A/B builds only.  Large trees read
 // through L1/L2, the three tree sets.
 #ifdef RT_BVH8_KERNELS
-#define RT_FUSED_ROWS_BVH8(X)                                  \
-  X(false, kFtSets[2], 8, 0, 0, false, false, DEF)             \
-  X(false, kFtSets[3], 8, 0, 0, false, false, DEF)             \
-  X(false, kFtSets[4], 8, 0, 0, false, false, DEF)
+#define RT_FUSED_ROWS_BVH8(X)                                         \
+  X(false, kFtSets[2], 8, 0, 0, false, false, false, DEF)             \
+  X(false, kFtSets[3], 8, 0, 0, false, false, false, DEF)             \
+  X(false, kFtSets[4], 8, 0, 0, false, false, false, DEF)
 #else
 #define RT_FUSED_ROWS_BVH8(X)
 #endif
 // The MAP twins (active-pixel passes): one for every kernel the dispatcher
 // selects with no knob set, but the record loop's SHAPE / LIGHT kernels (the generic record
 // loop renders the same bits).  None for the opt-in trees 2 and 8.
-#define RT_FUSED_ROWS_MAP(X)                                   \
-  X(true, kFtSets[0], 0, 0, 0, true, false, MAP)               \
-  X(false, kFtSets[0], 0, 0, 0, true, false, MAP)              \
-  X(true, kFtSets[1], 0, 0, 0, true, false, MAP)               \
-  X(false, kFtSets[1], 0, 0, 0, true, false, MAP)              \
-  X(true, kFtSets[0], 4, 0, 0, true, false, MAP)               \
-  X(false, kFtSets[0], 4, 0, 0, true, false, MAP)              \
-  X(true, kFtSets[1], 4, 0, 0, true, false, MAP)               \
-  X(false, kFtSets[1], 4, 0, 0, true, false, MAP)              \
-  X(true, kFtSets[2], 4, 0, 0, true, false, MAP)               \
-  X(false, kFtSets[2], 4, 0, 0, true, false, MAP)              \
-  X(true, kFtSets[3], 4, 0, 0, true, false, MAP)               \
-  X(false, kFtSets[3], 4, 0, 0, true, false, MAP)              \
-  X(true, kFtSets[4], 4, 0, 0, true, false, MAP)               \
-  X(false, kFtSets[4], 4, 0, 0, true, false, MAP)              \
-  X(true, FT_ALL, 4, 0, 0, true, false, MAP)                   \
-  X(false, FT_ALL, 4, 0, 0, true, false, MAP)                  \
-  X(false, kFtSets[2], 5, 0, 0, true, false, MAP)              \
-  X(false, kFtSets[3], 5, 0, 0, true, false, MAP)              \
-  X(false, kFtSets[4], 5, 0, 0, true, false, MAP)              \
-  X(false, FT_ALL, 5, 0, 0, true, false, MAP)
+#define RT_FUSED_ROWS_MAP(X)                                          \
+  X(true, kFtSets[0], 0, 0, 0, true, false, false, MAP)               \
+  X(false, kFtSets[0], 0, 0, 0, true, false, false, MAP)              \
+  X(true, kFtSets[1], 0, 0, 0, true, false, false, MAP)               \
+  X(false, kFtSets[1], 0, 0, 0, true, false, false, MAP)              \
+  X(true, kFtSets[0], 4, 0, 0, true, false, false, MAP)               \
+  X(false, kFtSets[0], 4, 0, 0, true, false, false, MAP)              \
+  X(true, kFtSets[1], 4, 0, 0, true, false, false, MAP)               \
+  X(false, kFtSets[1], 4, 0, 0, true, false, false, MAP)              \
+  X(true, kFtSets[2], 4, 0, 0, true, false, false, MAP)               \
+  X(false, kFtSets[2], 4, 0, 0, true, false, false, MAP)              \
+  X(true, kFtSets[3], 4, 0, 0, true, false, false, MAP)               \
+  X(false, kFtSets[3], 4, 0, 0, true, false, false, MAP)              \
+  X(true, kFtSets[4], 4, 0, 0, true, false, false, MAP)               \
+  X(false, kFtSets[4], 4, 0, 0, true, false, false, MAP)              \
+  X(true, FT_ALL, 4, 0, 0, true, false, false, MAP)                   \
+  X(false, FT_ALL, 4, 0, 0, true, false, false, MAP)                  \
+  X(false, kFtSets[2], 5, 0, 0, true, false, false, MAP)              \
+  X(false, kFtSets[3], 5, 0, 0, true, false, false, MAP)              \
+  X(false, kFtSets[4], 5, 0, 0, true, false, false, MAP)              \
+  X(false, FT_ALL, 5, 0, 0, true, false, false, MAP)
 #define RT_FUSED_KERNELS(X)                                                                  \
   RT_FUSED_ROWS_RECORD_LOOP(X) RT_FUSED_ROWS_BVH2(X) RT_FUSED_ROWS_BVH4(X) RT_FUSED_ROWS_QBVH(X) \
   RT_FUSED_ROWS_BVH8(X) RT_FUSED_ROWS_MAP(X)
-// A unit picks its rows by defining RT_FUSED_IN_DEF / _ILP / _MAP (L, F, T, S, G, M, E) and
+// A unit picks its rows by defining RT_FUSED_IN_DEF / _ILP / _MAP (L, F, T, S, G, M, E, C) and
 // expanding RT_FUSED_KERNELS(RT_FUSED_BY_UNIT); the units it leaves out expand to nothing.
-#define RT_FUSED_BY_UNIT(L, F, T, S, G, M, E, U) RT_FUSED_IN_##U(L, F, T, S, G, M, E)
-#define RT_FUSED_SKIP(L, F, T, S, G, M, E)
-#define RT_FUSED_INSTANTIATE(L, F, T, S, G, M, E) template __global__ void k_fused<L, F, T, S, G, M, E>(Params);
+#define RT_FUSED_BY_UNIT(L, F, T, S, G, M, E, C, U) RT_FUSED_IN_##U(L, F, T, S, G, M, E, C)
+#define RT_FUSED_SKIP(L, F, T, S, G, M, E, C)
+#define RT_FUSED_INSTANTIATE(L, F, T, S, G, M, E, C) template __global__ void k_fused<L, F, T, S, G, M, E, C>(Params);

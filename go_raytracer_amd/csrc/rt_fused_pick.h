@@ -7,18 +7,20 @@
 namespace rt {
 
 // the table's kernel of exactly these template arguments, nullptr when it has no such row
-static const void* find_fused(bool lds, uint32_t set, int tree, int shape, int light, bool map, bool early) {
-#define RT_FUSED_FIND(L, F, T, S, G, M, E, U)                                                    \
-  if (lds == L && set == (F) && tree == T && shape == S && light == G && map == M && early == E) \
-    return (const void*)k_fused<L, F, T, S, G, M, E>;
+static const void* find_fused(bool lds, uint32_t set, int tree, int shape, int light, bool map, bool early,
+                              bool cost = false) {
+#define RT_FUSED_FIND(L, F, T, S, G, M, E, C, U)                                                 \
+  if (lds == L && set == (F) && tree == T && shape == S && light == G && map == M && early == E && \
+      cost == C)                                                                                 \
+    return (const void*)k_fused<L, F, T, S, G, M, E, C>;
   RT_FUSED_KERNELS(RT_FUSED_FIND)
 #undef RT_FUSED_FIND
   return nullptr;
 }
 
 // one record-loop kernel per listed shape, and one per listed shape and lean light kind
-#define RT_FUSED_COUNT_SHAPES(L, F, T, S, G, M, E, U) +(T == 0 && L && (F) == kFtSets[0] && G == 0 && !M ? 1 : 0)
-#define RT_FUSED_COUNT_LIGHTS(L, F, T, S, G, M, E, U) +(G != 0 && !E ? 1 : 0)
+#define RT_FUSED_COUNT_SHAPES(L, F, T, S, G, M, E, C, U) +(T == 0 && L && (F) == kFtSets[0] && G == 0 && !M ? 1 : 0)
+#define RT_FUSED_COUNT_LIGHTS(L, F, T, S, G, M, E, C, U) +(G != 0 && !E ? 1 : 0)
 static_assert(0 RT_FUSED_KERNELS(RT_FUSED_COUNT_SHAPES) == kBruteShapeCount, "kernel table: one kernel per listed shape");
 static_assert(0 RT_FUSED_KERNELS(RT_FUSED_COUNT_LIGHTS) == (kBruteShapeCount - 1) * (kLeanLightCount - 1),
               "kernel table: one kernel per listed shape and light kind");
@@ -32,13 +34,14 @@ static_assert(0 RT_FUSED_KERNELS(RT_FUSED_COUNT_LIGHTS) == (kBruteShapeCount - 1
 // listed shapes have such kernels, the generic loop does not: nullptr, the caller takes kind 0)
 // (early: the lean light kind's kernel that draws a vertex's numbers before it resolves the
 // winner, rt_path.h shade_core<.., EARLY_SHAPE>; nullptr without a light kind)
+// (cost: the early-draw kernel's lean-cost twin, k_fused<.., COST>; nullptr without early)
 // nullptr too for a tree without a kernel of the set: tree 5 in LDS, tree 2 outside the two
 // small sets in LDS, tree 8 outside an RT_BVH8_KERNELS build.  At tree 4 a set without a kernel
 // of its own runs the all-features one.
 static const void* pick_fused(bool lds, uint32_t set, int tree, int shape = 0, int light = 0,
-                              bool early = false) {
-  const void* k = find_fused(lds, set, tree, shape, light, false, early);
-  if (k || light != 0 || early) return k;
+                              bool early = false, bool cost = false) {
+  const void* k = find_fused(lds, set, tree, shape, light, false, early, cost);
+  if (k || light != 0 || early || cost) return k;
   if (shape != 0) k = find_fused(lds, set, tree, 0, 0, false, false);
   if (!k && tree == 4) k = find_fused(lds, FT_ALL, 4, 0, 0, false, false);
   return k;

@@ -499,7 +499,7 @@ static_assert(FT_SPHERE == RT_FT_SPHERE && FT_TRI == RT_FT_TRI && FT_METAL == RT
 
 // the table's rows other units compile (rt_fused_sets.hip, rt_fused_map.hip); this unit's are
 // instantiated by the dispatcher
-#define RT_FUSED_EXTERN(L, F, T, S, G, M, E) extern template __global__ void k_fused<L, F, T, S, G, M, E>(Params);
+#define RT_FUSED_EXTERN(L, F, T, S, G, M, E, C) extern template __global__ void k_fused<L, F, T, S, G, M, E, C>(Params);
 #define RT_FUSED_IN_DEF RT_FUSED_SKIP
 #define RT_FUSED_IN_ILP RT_FUSED_EXTERN
 #define RT_FUSED_IN_MAP RT_FUSED_EXTERN
@@ -581,6 +581,7 @@ struct StructurePlan {
   int shape;         // the record layout the kernel is compiled for (rt_device.h brute_shape), 0 = any
   int light;         // the lean light kind its light code is compiled for (rt_device.h), 0 = any list
   bool early;        // ... and that kernel's early-draw variant (the scene has an emitter slot)
+  bool cost;         // ... and that variant's lean-cost twin (RT_LEAN_COST)
   const void* kernel;
   size_t lds_bytes;  // dynamic LDS of the kernel
   bool wants_qbvh;   // a BVH4 read through L1/L2 whose set has a compressed-BVH4 kernel
@@ -653,7 +654,11 @@ static int plan_structure(const Scene* s, const DeviceScene* ds, uint32_t ft_set
   const bool early = light != 0 && ds->emitter_slot >= 0 && shade_tab && f_recs &&
                      tune_int("RT_LEAN_EARLY_DRAW", 1) != 0 &&
                      pick_fused(f_lds, ft_set, tree, brute_shape_id, light, true) != nullptr;
-  const void* fused_kernel = pick_fused(f_lds, ft_set, tree, brute_shape_id, light, early);
+  // ... and that variant's lean-cost twin (DESIGN.md §4 "The cost-weighted census").
+  // RT_LEAN_COST=0: the early-draw kernel as it was (A/B; the same image bit for bit).
+  const bool cost = early && tune_int("RT_LEAN_COST", 1) != 0 &&
+                    pick_fused(f_lds, ft_set, tree, brute_shape_id, light, true, true) != nullptr;
+  const void* fused_kernel = pick_fused(f_lds, ft_set, tree, brute_shape_id, light, early, cost);
   if (!fused_kernel) return set_error(RT_ERR_UNSUPPORTED, "internal: no fused kernel for this scene");
   const size_t fused_lds = f_lds ? 64 * (node_slots * n_nodes + (f_recs ? rec_slots : 0)) : 0;
   out->tree = tree;
@@ -663,6 +668,7 @@ static int plan_structure(const Scene* s, const DeviceScene* ds, uint32_t ft_set
   out->shape = brute_shape_id;
   out->light = light;
   out->early = early;
+  out->cost = cost;
   out->kernel = fused_kernel;
   out->lds_bytes = fused_lds;
   return RT_OK;
@@ -696,12 +702,12 @@ static int plan_kernel(Scene* s, DeviceScene* ds, uint32_t ft_set, int mode, con
                                  (float)background[2] >= 0.0f);
   if (sp->light != 0 && !sp->merge_bg) {
     sp->light = 0;
-    sp->early = false;
+    sp->early = sp->cost = false;
     sp->kernel = pick_fused(sp->f_lds, ft_set, sp->tree, sp->shape, 0);
   }
   if (map) {  // the structure's MAP twin; the record loop's is the generic one (the same bits)
     sp->shape = sp->light = 0;
-    sp->early = false;
+    sp->early = sp->cost = false;
     sp->kernel = pick_fused_map(sp->f_lds, ft_set, sp->tree);
     if (!sp->kernel)
       return set_error(RT_ERR_UNSUPPORTED, "an active-pixel pass has no kernel for tree %d, chosen by RT_TREE / RT_BVH8", sp->tree);
@@ -1480,6 +1486,13 @@ int rt_scene_plan_early(rt_scene* sc, int device, int32_t* early) {
   rt::StructurePlan sp;
   const int rc = rt::scene_plan("rt_scene_plan_early", sc, device, early, &sp);
   if (rc == RT_OK) *early = sp.early ? 1 : 0;
+  return rc;
+}
+
+int rt_scene_plan_cost(rt_scene* sc, int device, int32_t* cost) {
+  rt::StructurePlan sp;
+  const int rc = rt::scene_plan("rt_scene_plan_cost", sc, device, cost, &sp);
+  if (rc == RT_OK) *cost = sp.cost ? 1 : 0;
   return rc;
 }
 

@@ -384,6 +384,9 @@ int rt_scene_lean_emitter(const rt_scene* s, int32_t* slot);
  * one layout with such a kernel) and RT_LEAN_EARLY_DRAW is not 0; else 0.  A render whose background has a negative channel takes the general kernel whatever
  * this returns. */
 int rt_scene_plan_early(rt_scene* s, int device, int32_t* early);
+/* ... and 1 when that launch takes the early-draw kernel's lean-cost twin (the default where the
+   early-draw kernel is taken; RT_LEAN_COST=0 keeps the early-draw kernel itself), else 0 */
+int rt_scene_plan_cost(rt_scene* s, int device, int32_t* cost);
 
 enum {
   RT_FLAG_PROFILE = 1,     /* time every kernel with HIP events */

@@ -16,7 +16,8 @@
 #define RT_FUSED_TABLE_ONLY
 namespace rt {
 struct Params {};
-template <bool LDS, uint32_t FT, int TREE, int SHAPE = 0, int LIGHT = 0, bool MAP = false, bool EARLY = false>
+template <bool LDS, uint32_t FT, int TREE, int SHAPE = 0, int LIGHT = 0, bool MAP = false, bool EARLY = false,
+          bool COST = false>
 void k_fused(Params) {}
 }  // namespace rt
 #include "rt_fused_pick.h"
@@ -25,8 +26,10 @@ using namespace rt;
 
 static const char* name_of(const void* k) {
   if (!k) return "-";
-#define ROW(L, F, T, S, G, M, E, U) \
-  if (k == (const void*)k_fused<L, F, T, S, G, M, E>) return "k_fused<" #L ", " #F ", " #T ", " #S ", " #G ", " #M ", " #E "> " #U;
+#define ROW(L, F, T, S, G, M, E, C, U) \
+  if (k == (const void*)k_fused<L, F, T, S, G, M, E, C>)   \
+    return C ? "k_fused<" #L ", " #F ", " #T ", " #S ", " #G ", " #M ", " #E ", " #C "> " #U \
+             : "k_fused<" #L ", " #F ", " #T ", " #S ", " #G ", " #M ", " #E "> " #U;
   RT_FUSED_KERNELS(ROW)
 #undef ROW
   return "NOT IN THE TABLE";
@@ -42,6 +45,10 @@ int main() {
             for (int early = 0; early < 2; ++early)
               printf("lds %d set %3u tree %d shape %d light %d early %d : %s\n", lds, set, tree, shape, light,
                      early, name_of(pick_fused(lds != 0, set, tree, shape, light, early != 0)));
+        // the early-draw kernel's lean-cost twin (RT_LEAN_COST, the default where it exists)
+        for (int shape = 1; shape < 3; ++shape)
+          printf("lds %d set %3u tree %d shape %d light 1 early 1 cost 1 : %s\n", lds, set, tree, shape,
+                 name_of(pick_fused(lds != 0, set, tree, shape, 1, true, true)));
         printf("lds %d set %3u tree %d map : %s\n", lds, set, tree, name_of(pick_fused_map(lds != 0, set, tree)));
       }
   return 0;
