@@ -595,56 +595,29 @@ class Scene:
         passed (0: the pixel has the first hit's bits).  It combines with neither emit nor media."""
         if specular and (emit or media):
             raise ValueError("render_aov: specular=True does not combine with emit=True or media=True")
+        mode = _aov_mode(emit, media, specular)
         d = camera.derived()
-        rows = len(range(rank, d.height, nranks))
-        res = {"albedo": np.zeros((rows, d.width, 3), np.float32),
-               "normal": np.zeros((rows, d.width, 3), np.float32),
-               "depth": np.zeros((rows, d.width), np.float32),
-               "material": np.full((rows, d.width), -1, np.int32)}
-        a = RtAov(*[res[k].ctypes.data for k in ("albedo", "normal", "depth", "material")])
-        e = None
-        if emit:
-            res["emission"] = np.zeros((rows, d.width, 3), np.float32)
-            res["surface_albedo"] = np.zeros((rows, d.width, 3), np.float32)
-            res["coverage"] = np.zeros((rows, d.width), np.float32)
-            e = RtAovEmit(*[res[k].ctypes.data for k in ("emission", "surface_albedo", "coverage")])
-        m = None
-        if media:
-            res["scatter"] = np.zeros((rows, d.width), np.float32)
-            m = RtAovMedia(res["scatter"].ctypes.data)
+        shape = (len(range(rank, d.height, nranks)), d.width)
+        planes = [kc for _, keys in _AOV_MODES[mode][1] for kc in keys]
+        res = {k: np.zeros(shape + ((3,) if ch else ()), np.float32) for k, ch in planes}
+        res["material"] = np.full(shape, -1, np.int32)  # (the key keeps its place)
         o = self._opts(seed, device, rank, nranks, 0, 0, False, None)
-        if specular:
-            res["bounces"] = np.zeros((rows, d.width), np.float32)
-            res["stats"] = self._aov_spec(camera, o, n_samples, a, RtAovSpec(res["bounces"].ctypes.data),
-                                          max_bounces, max_fuzz, False)
-            return res
-        res["stats"] = self._aov(camera, o, n_samples, a, e, False, m)
+        res["stats"] = self._aov(camera, o, n_samples, mode, False, {k: v.ctypes.data for k, v in res.items()},
+                                 (max_bounces, max_fuzz))
         return res
 
-    def _aov_spec(self, camera, o, n_samples, a, sp, max_bounces, max_fuzz, device):
-        """One of the two rt_render_aov_spec entries -> the stats dict."""
+    def _aov(self, camera, o, n_samples, mode, device, ptr, spec_opts):
+        """One of the eight rt_render_aov entries, by _AOV_MODES' mode and `device` -> the stats
+        dict.  ptr: plane name -> pointer (missing or None: not wanted); spec_opts: the "spec"
+        mode's (max_bounces, max_fuzz)."""
+        suffix, structs = _AOV_MODES[mode]
+        keep = [None if cls is None else cls(*[ptr.get(k) for k, _ in keys]) for cls, keys in structs]
+        if mode == "spec":
+            keep.insert(0, RtAovSpecOpts(*spec_opts))
         st = RtStats()
         c = camera.to_c()
-        so = RtAovSpecOpts(max_bounces, max_fuzz)
-        fn = lib().rt_render_aov_spec_device if device else lib().rt_render_aov_spec
-        check(fn(self._p, C.byref(c), C.byref(o), n_samples, C.byref(so), C.byref(a), C.byref(sp), C.byref(st)))
-        return _as_dict(st)
-
-    def _aov(self, camera, o, n_samples, a, e, device, m=None):
-        """One of the six rt_render_aov entries: the emit ones with an RtAovEmit `e`, the media
-        ones with an RtAovMedia `m` (e may then be None), the _device ones with `device` -> the
-        stats dict."""
-        st = RtStats()
-        c = camera.to_c()
-        L = lib()
-        if m is not None:
-            fn, args = ((L.rt_render_aov_media_device if device else L.rt_render_aov_media),
-                        (C.byref(a), None if e is None else C.byref(e), C.byref(m)))
-        elif e is None:
-            fn, args = (L.rt_render_aov_device if device else L.rt_render_aov), (C.byref(a),)
-        else:
-            fn, args = ((L.rt_render_aov_emit_device if device else L.rt_render_aov_emit),
-                        (C.byref(a), C.byref(e)))
+        fn = getattr(lib(), "rt_render_aov" + suffix + ("_device" if device else ""))
+        args = [None if s is None else C.byref(s) for s in keep]
         check(fn(self._p, C.byref(c), C.byref(o), n_samples, *args, C.byref(st)))
         return _as_dict(st)
 
@@ -658,19 +631,15 @@ class Scene:
         `scatter` pointer it is rt_render_aov_media_device.  With specular=True or a `bounces`
         pointer it is rt_render_aov_spec_device, which takes none of the emit or media buffers.
         Returns the stats dict."""
-        if specular or bounces is not None:
-            if (media or scatter is not None or emission is not None or surface_albedo is not None
-                    or coverage is not None):
-                raise ValueError("render_aov_device: specular does not combine with the emit or media buffers")
-            o = self._opts(seed, device, rank, nranks, 0, 0, False, stream)
-            return self._aov_spec(camera, o, n_samples, RtAov(albedo, normal, depth, material), RtAovSpec(bounces),
-                                  max_bounces, max_fuzz, True)
-        e = None
-        if emission is not None or surface_albedo is not None or coverage is not None:
-            e = RtAovEmit(emission, surface_albedo, coverage)
-        m = RtAovMedia(scatter) if media or scatter is not None else None
+        ptr = {"albedo": albedo, "normal": normal, "depth": depth, "material": material, "emission": emission,
+               "surface_albedo": surface_albedo, "coverage": coverage, "scatter": scatter, "bounces": bounces}
+        emit = any(ptr[k] is not None for k, _ in _EMIT_KEYS)
+        media = media or scatter is not None
+        specular = specular or bounces is not None
+        if specular and (emit or media):
+            raise ValueError("render_aov_device: specular does not combine with the emit or media buffers")
         o = self._opts(seed, device, rank, nranks, 0, 0, False, stream)
-        return self._aov(camera, o, n_samples, RtAov(albedo, normal, depth, material), e, True, m)
+        return self._aov(camera, o, n_samples, _aov_mode(emit, media, specular), True, ptr, (max_bounces, max_fuzz))
 
     def accumulator(self, camera, max_passes=0, device=0, rank=0, nranks=1, path_slots=0, chunk=0,
                     profile=False, stream=None, mode="auto", progress_slices=0, features=None):
@@ -1085,6 +1054,21 @@ def _denoise_opts(var, iterations=0, demodulate=None, sigma_normal=0.0, sigma_de
 
 
 _EMIT_KEYS = (("emission", 3), ("surface_albedo", 3), ("coverage", 0))
+_OUT = (RtAov, (("albedo", 3), ("normal", 3), ("depth", 0), ("material", 0)))
+_EMIT = (RtAovEmit, _EMIT_KEYS)
+_MEDIA = (RtAovMedia, (("scatter", 0),))
+# The feature pass's modes (Scene.render_aov, render_aov_device): the suffix of the mode's
+# rt_render_aov entries and the pointer structs they take, each with its planes (name, channels)
+# in field order.  (None: a NULL struct.)
+_AOV_MODES = {"first": ("", (_OUT,)),
+              "emit": ("_emit", (_OUT, _EMIT)),
+              "media": ("_media", (_OUT, (None, ()), _MEDIA)),
+              "emit+media": ("_media", (_OUT, _EMIT, _MEDIA)),
+              "spec": ("_spec", (_OUT, (RtAovSpec, (("bounces", 0),))))}
+
+
+def _aov_mode(emit, media, specular):
+    return "spec" if specular else "+".join(m for m, on in (("emit", emit), ("media", media)) if on) or "first"
 
 
 def _emit_host(who, aov, h, w):

@@ -39,6 +39,10 @@
 // k_aov_fold<TREE, EMIT, PX, MEDIA>: the pass accumulator's feature fold (rt_accum.hip),
 // the same samples (aov_sample is the one text of both kernels) summed into the accumulator's
 // fp64 planes for all spp_sqrt^2 samples of a pass's seed, over a whole pass or its active pixels.
+//
+// The host half (DESIGN.md §11 "Host path"): the eight entries fill an AovRequest and aov_impl
+// runs aov_check -> aov_plan -> aov_bind -> aov_launch -> aov_collect; aov_launch and
+// aov_fold_enqueue choose the kernel instance through with_tree and with_flag.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -446,261 +450,262 @@ DeviceScratch g_stacks, g_stage, g_count;  // (g_count: the specular mode's chai
 // no stream is released while the runtime unloads.
 std::vector<Stream>& g_streams = *new std::vector<Stream>();
 
-// scatter: the media mode's plane, null for the kernels without it
-template <int TREE>
-void launch_aov(bool split, dim3 grid, hipStream_t stream, const Params& p, const AovOut& ao, const AovEmit& ae,
-                bool media, float* scatter) {
-  const dim3 b(256);
-  AovEmitMedia md;
-  (AovEmit&)md = ae;
-  md.scatter = scatter;
-  if (media && split) hipLaunchKernelGGL((k_aov<TREE, true, true, false>), grid, b, 0, stream, p, ao, md);
-  else if (media) hipLaunchKernelGGL((k_aov<TREE, false, true, false>), grid, b, 0, stream, p, ao, md);
-  else if (split) hipLaunchKernelGGL((k_aov<TREE, true, false, false>), grid, b, 0, stream, p, ao, ae);
-  else hipLaunchKernelGGL((k_aov<TREE, false, false, false>), grid, b, 0, stream, p, ao, ae);
-}
-
-void launch_aov_spec(int tree, dim3 grid, hipStream_t stream, const Params& p, const AovOut& ao, const AovEmitSpec& sp) {
-  const dim3 b(256);
+// A runtime tree id (0 record loop, 2 BVH2, 5 compressed BVH4, anything else BVH4) or flag as a
+// compile-time constant, f(std::integral_constant<..>{}): every kernel choice below goes through these
+template <class F>
+void with_tree(int tree, F&& f) {
   switch (tree) {
-    case 0: hipLaunchKernelGGL((k_aov<0, false, false, true>), grid, b, 0, stream, p, ao, sp); break;
-    case 2: hipLaunchKernelGGL((k_aov<2, false, false, true>), grid, b, 0, stream, p, ao, sp); break;
-    case 5: hipLaunchKernelGGL((k_aov<5, false, false, true>), grid, b, 0, stream, p, ao, sp); break;
-    default: hipLaunchKernelGGL((k_aov<4, false, false, true>), grid, b, 0, stream, p, ao, sp); break;
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    default: return f(std::integral_constant<int, 4>{});
   }
 }
+template <class F>
+void with_flag(bool v, F&& f) { v ? f(std::true_type{}) : f(std::false_type{}); }
 
-// split: the rt_render_aov_emit entries (outp may be null, emitp is required); else emitp is null.
-// mediap: the rt_render_aov_media entries (required there; outp and emitp may be null), which
-// are the split ones when emitp is given.  spec: the rt_render_aov_spec entries (specp required,
-// sopts null = the defaults; neither split nor media)
-int aov_impl(rt_scene* scene, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
-             const rt_aov* outp, const rt_aov_emit* emitp, const rt_aov_media* mediap, bool split, bool media,
-             bool host, rt_stats* stats, bool spec = false, const rt_aov_spec_opts* sopts = nullptr,
-             const rt_aov_spec* specp = nullptr) {
-  if (!scene || !cam) return set_error(RT_ERR_INVALID, "rt_render_aov: null scene/camera");
-  const rt_aov no_out{nullptr, nullptr, nullptr, nullptr};
-  int32_t max_bounces = 8;
-  float max_fuzz = 0.0f;
-  if (spec) {
-    if (!specp) return set_error(RT_ERR_INVALID, "rt_render_aov_spec: null spec");
-    if (!outp) outp = &no_out;
-    if (!outp->albedo && !outp->normal && !outp->depth && !outp->material && !specp->bounces)
-      return set_error(RT_ERR_INVALID, "rt_render_aov_spec: no buffer wanted");
-    if (sopts) {
-      if (sopts->max_bounces < 0 || sopts->max_bounces > 64)
-        return set_error(RT_ERR_INVALID, "rt_render_aov_spec: max_bounces %d not in 0 .. 64", sopts->max_bounces);
-      if (!(sopts->max_fuzz >= 0.0f) || !std::isfinite(sopts->max_fuzz))
-        return set_error(RT_ERR_INVALID, "rt_render_aov_spec: max_fuzz must be finite and >= 0");
-      if (sopts->max_bounces > 0) max_bounces = sopts->max_bounces;
-      max_fuzz = sopts->max_fuzz;
-    }
-  } else if (media) {
-    if (!mediap) return set_error(RT_ERR_INVALID, "rt_render_aov_media: null media");
-    if (!outp) outp = &no_out;
-    split = emitp != nullptr;
-    if (!outp->albedo && !outp->normal && !outp->depth && !outp->material && !mediap->scatter &&
-        !(emitp && (emitp->emission || emitp->surface_albedo || emitp->coverage)))
-      return set_error(RT_ERR_INVALID, "rt_render_aov_media: no buffer wanted");
-  } else if (split) {
-    if (!emitp) return set_error(RT_ERR_INVALID, "rt_render_aov_emit: null emit");
-    if (!outp) outp = &no_out;
-    if (!outp->albedo && !outp->normal && !outp->depth && !outp->material && !emitp->emission &&
-        !emitp->surface_albedo && !emitp->coverage)
-      return set_error(RT_ERR_INVALID, "rt_render_aov_emit: no buffer wanted");
-  }
-  if (!outp) return set_error(RT_ERR_INVALID, "rt_render_aov: null output");
-  rt_render_opts o{};
-  if (opts) o = *opts;
-  if (o.nranks <= 0) o.nranks = 1;
-  if (o.rank < 0 || o.rank >= o.nranks) return set_error(RT_ERR_INVALID, "rt_render_aov: bad rank");
+// What a launch of k_aov or k_aov_fold over npix pixels of a view needs beside its planes: the grid,
+// the Params with an overflow-stack column per launched thread, and what chooses the kernel instance
+struct AovLaunch {
+  Params p;
+  int blocks, tree;
+  bool has_media;
+};
+// (g_mu held: the stacks are shared; *L is written once nothing can fail any more)
+int aov_setup(const AovView& view, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t npix,
+              const char* who, AovLaunch* L) {
+  const uint32_t blocks = std::min<uint32_t>((npix + 255u) / 256u, view.tree == 0 ? kAovMaxBlocks : kAovMaxTreeBlocks);
+  const uint32_t cols = blocks * 256u;
+  void* ost = nullptr;
+  const size_t depth = view.tree == 0 ? 1 : kStack - kShortStack;
+  if (int rc = g_stacks.get(o.device, depth * cols * sizeof(uint32_t), &ost, who)) return rc;
+  L->blocks = (int)blocks;
+  L->tree = view.tree;
+  L->has_media = view.sc.n_media > 0;
+  L->p = Params{};
+  L->p.sc = view.sc;
+  set_camera_params(L->p, cd, o, npix);
+  L->p.ostack = (uint32_t*)ost;
+  L->p.stack_cols = cols;
+  return RT_OK;
+}
+
+enum class AovMode { First, Emit, Media, Spec };
+
+// What an entry asks for: the mode, whether its buffers are host memory, its name for the mode's
+// own messages, and its arguments as they came in (null: a struct the entry does not take)
+struct AovRequest {
+  AovMode mode;
+  bool host;
+  const char* name;
+  rt_scene* scene;
+  const rt_camera* cam;
+  const rt_render_opts* opts;
+  int32_t n_samples;
+  rt_stats* stats;
+  const rt_aov* out;
+  const rt_aov_emit* emit;
+  const rt_aov_media* media;
+  const rt_aov_spec* spec;
+  const rt_aov_spec_opts* spec_opts;
+};
+
+struct AovPlane {
+  void* user;  // the caller's pointer, null: not wanted
+  size_t bpp;  // bytes per pixel: 3 or 1 floats or ints
+  void* dev;   // where the kernel writes it (aov_bind)
+};
+
+struct AovJob {
+  rt_render_opts o;  // the defaults resolved
   rt_camera_derived cd;
-  int rc = rt_camera_derive(cam, &cd);
-  if (rc) return rc;
-  const uint32_t ss = (uint32_t)cd.spp_sqrt * (uint32_t)cd.spp_sqrt;
-  if (n_samples < 0 || (uint32_t)n_samples > ss)
-    return set_error(RT_ERR_INVALID, "rt_render_aov: %d samples of %u", n_samples, ss);
-  const uint32_t n = n_samples == 0 ? 1u : (uint32_t)n_samples;
-  const auto t_start = std::chrono::steady_clock::now();
-  if ((rc = device_ok("rt_render_aov", o.device))) return rc;
-  DeviceGuard dg;
-  HIP_OK(hipSetDevice(o.device));
-  AovView view;
-  if ((rc = aov_view(&scene->s, o.device, &view))) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-
-  const uint32_t W = (uint32_t)cd.width, H = (uint32_t)cd.height;
-  const uint32_t rows = rank_rows(H, o.rank, o.nranks);
-  const uint64_t npix64 = (uint64_t)rows * W;
-  if (npix64 >= 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_render_aov: image too large");
-  const uint32_t npix = (uint32_t)npix64;
-
+  rt_aov_spec_opts spec{8, 0.0f};
+  uint32_t n;    // samples per pixel
+  bool emit;     // the EMIT kernels: the emit entries, and the media entries given an emit struct
+  int n_planes;  // the slots the mode stages: 4, 7 or 8
+  AovPlane planes[8];  // in staging order: AovOut's pointers, AovEmit's, the mode's own plane
+  std::chrono::steady_clock::time_point t_start;  // the checks done
+  uint32_t rows, npix;                            // this rank's share
   hipStream_t stream;
-  if ((int)g_streams.size() <= o.device) g_streams.resize(o.device + 1);
-  if ((rc = g_streams[o.device].pick(o.stream, &stream))) return rc;
+  AovLaunch l;
+  unsigned long long chain_segments;  // the specular mode: those behind the camera rays'
+};
 
-  const int blocks = (int)std::min<uint32_t>((npix + 255u) / 256u,
-                                             (uint32_t)(view.tree == 0 ? kAovMaxBlocks : kAovMaxTreeBlocks));
-  unsigned long long chain_segments = 0;  // spec: the segments traced behind the camera rays'
-  if (npix > 0) {
-    Params p{};
-    p.sc = view.sc;
-    set_camera_params(p, cd, o, npix);
-    // traversal-stack overflow columns, one per launched thread
-    const uint32_t cols = (uint32_t)blocks * 256u;
-    void* ost = nullptr;
-    if ((rc = g_stacks.get(o.device, (size_t)(view.tree == 0 ? 1 : kStack - kShortStack) * cols * sizeof(uint32_t), &ost,
-                           "rt_render_aov")))
-      return rc;
-    p.ostack = (uint32_t*)ost;
-    p.stack_cols = cols;
-
-    // the output planes in the order of the staging buffer, which is the order of AovOut's and
-    // then AovEmit's pointers: the caller's pointer and the plane's size (3 or 1 floats or ints
-    // per pixel)
-    const rt_aov_emit no_emit{nullptr, nullptr, nullptr};
-    const rt_aov_emit& em = split ? *emitp : no_emit;
-    const struct {
-      void* user;
-      size_t bytes;
-    } planes[8] = {{outp->albedo, 3 * (size_t)npix * 4},     {outp->normal, 3 * (size_t)npix * 4},
-                   {outp->depth, (size_t)npix * 4},          {outp->material, (size_t)npix * 4},
-                   {em.emission, 3 * (size_t)npix * 4},      {em.surface_albedo, 3 * (size_t)npix * 4},
-                   {em.coverage, (size_t)npix * 4},
-                   {media ? mediap->scatter : spec ? specp->bounces : nullptr, (size_t)npix * 4}};  // (one slot)
-    const int n_planes = media || spec ? 8 : split ? 7 : 4;
-    void* dev[8];  // where the kernel writes: the caller's device buffer or the plane's staging slot
-    for (int i = 0; i < 8; ++i) dev[i] = host ? nullptr : planes[i].user;
-    if (host) {  // one scratch buffer; an absent plane keeps its slot
-      size_t total = 0;
-      for (int i = 0; i < n_planes; ++i) total += planes[i].bytes;
-      void* stg = nullptr;
-      if ((rc = g_stage.get(o.device, total, &stg, "rt_render_aov"))) return rc;
-      size_t off = 0;
-      for (int i = 0; i < n_planes; off += planes[i++].bytes)
-        if (planes[i].user) dev[i] = (char*)stg + off;
-    }
-    const AovOut ao{(float*)dev[0], (float*)dev[1], (float*)dev[2], (int32_t*)dev[3], n};
-    const AovEmit ae{(float*)dev[4], (float*)dev[5], (float*)dev[6]};
-    const dim3 g((unsigned)blocks);
-    // a scene without media: the kernels without the mode (rt_render_aov_emit's bits), scatter = 0
-    const bool mk = media && view.sc.n_media > 0;
-    float* const scat = (float*)dev[7];
-    if (media && !mk && scat) HIP_OK(hipMemsetAsync(scat, 0, planes[7].bytes, stream));
-    if (spec) {
-      // the last vertex a chain may reach; the chain segments are counted on the device
-      void* cnt = nullptr;
-      if ((rc = g_count.get(o.device, sizeof(unsigned long long), &cnt, "rt_render_aov_spec"))) return rc;
-      HIP_OK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), stream));
-      AovEmitSpec sp;
-      (AovEmit&)sp = ae;
-      sp.bounces = scat;
-      sp.chain_segments = (unsigned long long*)cnt;
-      sp.max_k = std::max(0, std::min(max_bounces, cd.max_depth - 1));
-      sp.max_fuzz = max_fuzz;
-      launch_aov_spec(view.tree, g, stream, p, ao, sp);
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipMemcpyAsync(&chain_segments, cnt, sizeof chain_segments, hipMemcpyDeviceToHost, stream));
-    } else {
-      switch (view.tree) {
-        case 0: launch_aov<0>(split, g, stream, p, ao, ae, mk, scat); break;
-        case 2: launch_aov<2>(split, g, stream, p, ao, ae, mk, scat); break;
-        case 5: launch_aov<5>(split, g, stream, p, ao, ae, mk, scat); break;
-        default: launch_aov<4>(split, g, stream, p, ao, ae, mk, scat); break;
-      }
-      HIP_OK(hipGetLastError());
-    }
-    for (int k = 0; host && k < n_planes; ++k) {
-      const int i = ((split ? 4 : 0) + k) % n_planes;  // the emit planes first
-      if (planes[i].user)
-        HIP_OK(hipMemcpyAsync(planes[i].user, dev[i], planes[i].bytes, hipMemcpyDeviceToHost, stream));
-    }
-    HIP_OK(hipStreamSynchronize(stream));
+// Every argument test, in the entries' fixed order; no device is touched
+int aov_check(const AovRequest& rq, AovJob* j) {
+  if (!rq.scene || !rq.cam) return set_error(RT_ERR_INVALID, "rt_render_aov: null scene/camera");
+  // per mode: the slots it stages and the struct that selects it (required; `out` may be null beside it)
+  const char* missing = nullptr;
+  switch (rq.mode) {
+    case AovMode::First: j->n_planes = 4, missing = rq.out ? nullptr : "output"; break;
+    case AovMode::Emit: j->n_planes = 7, missing = rq.emit ? nullptr : "emit"; break;
+    case AovMode::Media: j->n_planes = 8, missing = rq.media ? nullptr : "media"; break;
+    case AovMode::Spec: j->n_planes = 8, missing = rq.spec ? nullptr : "spec"; break;
   }
-  if (stats) {
+  if (missing) return set_error(RT_ERR_INVALID, "%s: null %s", rq.name, missing);
+  void* own = nullptr;  // the mode's own plane, in the last slot
+  if (rq.mode == AovMode::Media) own = rq.media->scatter;
+  if (rq.mode == AovMode::Spec) own = rq.spec->bounces;
+  j->emit = rq.mode == AovMode::Emit || (rq.mode == AovMode::Media && rq.emit);
+  const rt_aov out = rq.out ? *rq.out : rt_aov{};
+  const rt_aov_emit em = j->emit ? *rq.emit : rt_aov_emit{};
+  const AovPlane planes[8] = {{out.albedo, 12},  {out.normal, 12},        {out.depth, 4},   {out.material, 4},
+                              {em.emission, 12}, {em.surface_albedo, 12}, {em.coverage, 4}, {own, 4}};
+  std::copy(planes, planes + 8, j->planes);
+  // (rt_render_aov itself has always taken an `out` without a buffer)
+  if (rq.mode != AovMode::First && std::none_of(planes, planes + 8, [](const AovPlane& p) { return p.user; }))
+    return set_error(RT_ERR_INVALID, "%s: no buffer wanted", rq.name);
+  if (const rt_aov_spec_opts* so = rq.mode == AovMode::Spec ? rq.spec_opts : nullptr) {
+    if (so->max_bounces < 0 || so->max_bounces > 64)
+      return set_error(RT_ERR_INVALID, "%s: max_bounces %d not in 0 .. 64", rq.name, so->max_bounces);
+    if (!(so->max_fuzz >= 0.0f) || !std::isfinite(so->max_fuzz))
+      return set_error(RT_ERR_INVALID, "%s: max_fuzz must be finite and >= 0", rq.name);
+    if (so->max_bounces > 0) j->spec.max_bounces = so->max_bounces;
+    j->spec.max_fuzz = so->max_fuzz;
+  }
+  j->o = rq.opts ? *rq.opts : rt_render_opts{};
+  if (j->o.nranks <= 0) j->o.nranks = 1;
+  if (j->o.rank < 0 || j->o.rank >= j->o.nranks) return set_error(RT_ERR_INVALID, "rt_render_aov: bad rank");
+  if (int rc = rt_camera_derive(rq.cam, &j->cd)) return rc;
+  const uint32_t ss = (uint32_t)j->cd.spp_sqrt * (uint32_t)j->cd.spp_sqrt;
+  if (rq.n_samples < 0 || (uint32_t)rq.n_samples > ss)
+    return set_error(RT_ERR_INVALID, "rt_render_aov: %d samples of %u", rq.n_samples, ss);
+  j->n = rq.n_samples == 0 ? 1u : (uint32_t)rq.n_samples;
+  j->t_start = std::chrono::steady_clock::now();
+  return RT_OK;
+}
+
+int aov_plan(const AovView& view, AovJob* j) {
+  j->rows = rank_rows((uint32_t)j->cd.height, j->o.rank, j->o.nranks);
+  const uint64_t npix64 = (uint64_t)j->rows * (uint32_t)j->cd.width;
+  if (npix64 >= 0x7FFFFFFFull) return set_error(RT_ERR_UNSUPPORTED, "rt_render_aov: image too large");
+  j->npix = (uint32_t)npix64;
+  if ((int)g_streams.size() <= j->o.device) g_streams.resize(j->o.device + 1);
+  if (int rc = g_streams[j->o.device].pick(j->o.stream, &j->stream)) return rc;
+  return aov_setup(view, j->cd, j->o, j->npix, "rt_render_aov", &j->l);  // (no pixels: no blocks, nothing allocated)
+}
+
+// A device entry's planes are written in place, a host entry's in their slots of one staging buffer
+// (an absent plane keeps its slot)
+int aov_bind(bool host, AovJob* j) {
+  for (AovPlane& p : j->planes) p.dev = host ? nullptr : p.user;
+  if (!host) return RT_OK;
+  size_t total = 0;
+  for (int i = 0; i < j->n_planes; ++i) total += j->planes[i].bpp * j->npix;
+  void* stg = nullptr;
+  if (int rc = g_stage.get(j->o.device, total, &stg, "rt_render_aov")) return rc;
+  size_t off = 0;
+  for (int i = 0; i < j->n_planes; off += j->planes[i++].bpp * j->npix)
+    if (j->planes[i].user) j->planes[i].dev = (char*)stg + off;
+  return RT_OK;
+}
+
+// The mode's kernel on the job's stream: k_aov of (emit x media | spec) x tree, its 20 instances
+int aov_launch(AovMode mode, AovJob* j) {
+  const AovPlane* pl = j->planes;
+  const AovOut ao{(float*)pl[0].dev, (float*)pl[1].dev, (float*)pl[2].dev, (int32_t*)pl[3].dev, j->n};
+  const AovEmitMedia md{{(float*)pl[4].dev, (float*)pl[5].dev, (float*)pl[6].dev}, (float*)pl[7].dev};
+  const dim3 g((unsigned)j->l.blocks), b(256);
+  if (mode == AovMode::Spec) {  // (with neither flag)
+    // the chain segments are counted on the device; max_k: the last vertex a chain may reach
+    void* cnt = nullptr;
+    if (int rc = g_count.get(j->o.device, sizeof j->chain_segments, &cnt, "rt_render_aov_spec")) return rc;
+    HIP_OK(hipMemsetAsync(cnt, 0, sizeof j->chain_segments, j->stream));
+    const int32_t max_k = std::max(0, std::min(j->spec.max_bounces, j->cd.max_depth - 1));
+    const AovEmitSpec sp{md, md.scatter, (unsigned long long*)cnt, max_k, j->spec.max_fuzz};
+    with_tree(j->l.tree, [&](auto t) {
+      hipLaunchKernelGGL((k_aov<decltype(t)::value, false, false, true>), g, b, 0, j->stream, j->l.p, ao, sp);
+    });
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(&j->chain_segments, cnt, sizeof j->chain_segments, hipMemcpyDeviceToHost, j->stream));
+    return RT_OK;
+  }
+  // a scene without media: the kernels without the mode (rt_render_aov_emit's bits), scatter = 0
+  const bool media = mode == AovMode::Media && j->l.has_media;
+  if (mode == AovMode::Media && !media && md.scatter)
+    HIP_OK(hipMemsetAsync(md.scatter, 0, pl[7].bpp * j->npix, j->stream));
+  with_tree(j->l.tree, [&](auto t) {
+    constexpr int T = decltype(t)::value;
+    with_flag(j->emit, [&](auto e) {
+      with_flag(media, [&](auto m) {
+        constexpr bool E = decltype(e)::value, M = decltype(m)::value;
+        hipLaunchKernelGGL((k_aov<T, E, M, false>), g, b, 0, j->stream, j->l.p, ao, (const AovEmitArg<M>&)md);
+      });
+    });
+  });
+  HIP_OK(hipGetLastError());
+  return RT_OK;
+}
+
+int aov_collect(const AovRequest& rq, const AovJob& j) {
+  for (int i = 0; rq.host && j.npix > 0 && i < j.n_planes; ++i)
+    if (const AovPlane& p = j.planes[i]; p.user)
+      HIP_OK(hipMemcpyAsync(p.user, p.dev, p.bpp * j.npix, hipMemcpyDeviceToHost, j.stream));
+  if (j.npix > 0) HIP_OK(hipStreamSynchronize(j.stream));
+  if (rt_stats* stats = rq.stats) {
     memset(stats, 0, sizeof *stats);
-    stats->samples = (uint64_t)npix * n;
+    stats->samples = (uint64_t)j.npix * j.n;
     // one closest-hit query per feature ray, and per specular vertex passed in the specular mode
-    stats->segments = (uint64_t)npix * n + chain_segments;
-    stats->rows = (int32_t)rows;
-    stats->tree_width = view.tree;
-    stats->scene_features = (int32_t)scene->s.h.features;
-    stats->kernel_features = view.tree == 0 ? (int32_t)FT_MEDIA : (int32_t)FT_ALL;
-    stats->path_slots = blocks * 256;
+    stats->segments = (uint64_t)j.npix * j.n + j.chain_segments;
+    stats->rows = (int32_t)j.rows;
+    stats->tree_width = j.l.tree;
+    stats->scene_features = (int32_t)rq.scene->s.h.features;
+    stats->kernel_features = j.l.tree == 0 ? (int32_t)FT_MEDIA : (int32_t)FT_ALL;
+    stats->path_slots = j.l.blocks * 256;
     stats->tuned = tune_count();
     stats->ms_total =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - j.t_start).count();
   }
   return RT_OK;
 }
 
+int aov_impl(const AovRequest& rq) {
+  AovJob j{};
+  int rc;
+  if ((rc = aov_check(rq, &j)) || (rc = device_ok("rt_render_aov", j.o.device))) return rc;
+  DeviceGuard dg;
+  HIP_OK(hipSetDevice(j.o.device));
+  AovView view;
+  if ((rc = aov_view(&rq.scene->s, j.o.device, &view))) return rc;
+  std::lock_guard<std::mutex> lk(g_mu);
+  if ((rc = aov_plan(view, &j))) return rc;
+  if (j.npix > 0 && ((rc = aov_bind(rq.host, &j)) || (rc = aov_launch(rq.mode, &j)))) return rc;
+  return aov_collect(rq, j);
+}
+
 // the pass aov_fold_begin prepared, valid while it holds g_mu
-struct {
-  Params p;
-  int tree, blocks;
-  bool has_media;
-} g_fold;
-
-template <int TREE, bool MEDIA>
-void launch_fold(bool emit, bool px, hipStream_t stream, const FeatPlanesArg<MEDIA>& F, const uint32_t* map) {
-  const dim3 g((unsigned)g_fold.blocks), b(256);
-  if (emit && px) hipLaunchKernelGGL((k_aov_fold<TREE, true, true, MEDIA>), g, b, 0, stream, g_fold.p, F, map);
-  else if (emit) hipLaunchKernelGGL((k_aov_fold<TREE, true, false, MEDIA>), g, b, 0, stream, g_fold.p, F, map);
-  else if (px) hipLaunchKernelGGL((k_aov_fold<TREE, false, true, MEDIA>), g, b, 0, stream, g_fold.p, F, map);
-  else hipLaunchKernelGGL((k_aov_fold<TREE, false, false, MEDIA>), g, b, 0, stream, g_fold.p, F, map);
-}
-
-template <int TREE>
-void launch_fold(bool emit, bool px, hipStream_t stream, const FeatPlanes& F, const uint32_t* map, uint32_t* nscatter) {
-  if (nscatter) {
-    FeatPlanesMedia fm;
-    (FeatPlanes&)fm = F;
-    fm.nscatter = nscatter;
-    launch_fold<TREE, true>(emit, px, stream, fm, map);
-  } else {
-    launch_fold<TREE, false>(emit, px, stream, F, map);
-  }
-}
+AovLaunch g_fold;
 
 }  // namespace
 
 int aov_fold_begin(rt_scene* scene, const rt_camera_derived& cd, const rt_render_opts& o, uint32_t n_pass) {
-  int rc;
-  if ((rc = device_ok("rt_accum_add", o.device))) return rc;
+  if (int rc = device_ok("rt_accum_add", o.device)) return rc;
   DeviceGuard dg;
   HIP_OK(hipSetDevice(o.device));
   AovView view;
-  if ((rc = aov_view(&scene->s, o.device, &view))) return rc;
+  if (int rc = aov_view(&scene->s, o.device, &view)) return rc;
   std::unique_lock<std::mutex> lk(g_mu);
-  const int blocks = (int)std::min<uint32_t>((n_pass + 255u) / 256u,
-                                             (uint32_t)(view.tree == 0 ? kAovMaxBlocks : kAovMaxTreeBlocks));
-  const uint32_t cols = (uint32_t)blocks * 256u;  // an overflow-stack column per launched thread
-  void* ost = nullptr;
-  if ((rc = g_stacks.get(o.device, (size_t)(view.tree == 0 ? 1 : kStack - kShortStack) * cols * sizeof(uint32_t), &ost,
-                         "rt_accum_add")))
-    return rc;
-  g_fold.p = Params{};
-  g_fold.p.sc = view.sc;
-  set_camera_params(g_fold.p, cd, o, n_pass);
-  g_fold.p.ostack = (uint32_t*)ost;
-  g_fold.p.stack_cols = cols;
-  g_fold.tree = view.tree;
-  g_fold.blocks = blocks;
-  g_fold.has_media = view.sc.n_media > 0;
+  if (int rc = aov_setup(view, cd, o, n_pass, "rt_accum_add", &g_fold)) return rc;
   lk.release();  // held until aov_fold_end
   return RT_OK;
 }
 
+// k_aov_fold of emit x px x media x tree, its 32 instances
 int aov_fold_enqueue(const FeatPlanes& F, uint32_t* nscatter, bool px, const uint32_t* map, hipStream_t stream) {
-  const bool emit = F.emission != nullptr;
   // a scene without media: the kernels without the mode, the counts stay 0
-  uint32_t* const ns = g_fold.has_media ? nscatter : nullptr;
-  switch (g_fold.tree) {
-    case 0: launch_fold<0>(emit, px, stream, F, map, ns); break;
-    case 2: launch_fold<2>(emit, px, stream, F, map, ns); break;
-    case 5: launch_fold<5>(emit, px, stream, F, map, ns); break;
-    default: launch_fold<4>(emit, px, stream, F, map, ns); break;
-  }
+  const FeatPlanesMedia fm{F, g_fold.has_media ? nscatter : nullptr};
+  const dim3 g((unsigned)g_fold.blocks), b(256);
+  with_tree(g_fold.tree, [&](auto t) {
+    with_flag(F.emission != nullptr, [&](auto e) {
+      with_flag(px, [&](auto x) {
+        with_flag(fm.nscatter != nullptr, [&](auto m) {
+          constexpr bool M = decltype(m)::value;
+          hipLaunchKernelGGL((k_aov_fold<decltype(t)::value, decltype(e)::value, decltype(x)::value, M>), g, b, 0,
+                             stream, g_fold.p, (const FeatPlanesArg<M>&)fm, map);
+        });
+      });
+    });
+  });
   HIP_OK(hipGetLastError());
   return RT_OK;
 }
@@ -713,49 +718,54 @@ extern "C" {
 
 int rt_render_aov(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
                   const rt_aov* out_host, rt_stats* stats) {
-  return rt::aov_impl(s, cam, opts, n_samples, out_host, nullptr, nullptr, false, false, true, stats);
+  return rt::aov_impl({rt::AovMode::First, /*host=*/true, "rt_render_aov", s, cam, opts, n_samples, stats, out_host});
 }
 
 int rt_render_aov_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
                          int32_t n_samples, const rt_aov* out_device, rt_stats* stats) {
-  return rt::aov_impl(s, cam, opts, n_samples, out_device, nullptr, nullptr, false, false, false, stats);
+  return rt::aov_impl(
+      {rt::AovMode::First, /*host=*/false, "rt_render_aov", s, cam, opts, n_samples, stats, out_device});
 }
 
 int rt_render_aov_emit(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
                        const rt_aov* out_host, const rt_aov_emit* emit_host, rt_stats* stats) {
-  return rt::aov_impl(s, cam, opts, n_samples, out_host, emit_host, nullptr, true, false, true, stats);
+  return rt::aov_impl({rt::AovMode::Emit, /*host=*/true, "rt_render_aov_emit", s, cam, opts, n_samples, stats,
+                       out_host, emit_host});
 }
 
 int rt_render_aov_emit_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
                               int32_t n_samples, const rt_aov* out_device,
                               const rt_aov_emit* emit_device, rt_stats* stats) {
-  return rt::aov_impl(s, cam, opts, n_samples, out_device, emit_device, nullptr, true, false, false, stats);
+  return rt::aov_impl({rt::AovMode::Emit, /*host=*/false, "rt_render_aov_emit", s, cam, opts, n_samples, stats,
+                       out_device, emit_device});
 }
 
 int rt_render_aov_media(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
                         const rt_aov* out_host, const rt_aov_emit* emit_host, const rt_aov_media* media_host,
                         rt_stats* stats) {
-  return rt::aov_impl(s, cam, opts, n_samples, out_host, emit_host, media_host, false, true, true, stats);
+  return rt::aov_impl({rt::AovMode::Media, /*host=*/true, "rt_render_aov_media", s, cam, opts, n_samples, stats,
+                       out_host, emit_host, media_host});
 }
 
 int rt_render_aov_media_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
                                int32_t n_samples, const rt_aov* out_device, const rt_aov_emit* emit_device,
                                const rt_aov_media* media_device, rt_stats* stats) {
-  return rt::aov_impl(s, cam, opts, n_samples, out_device, emit_device, media_device, false, true, false, stats);
+  return rt::aov_impl({rt::AovMode::Media, /*host=*/false, "rt_render_aov_media", s, cam, opts, n_samples, stats,
+                       out_device, emit_device, media_device});
 }
 
 int rt_render_aov_spec(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
                        const rt_aov_spec_opts* spec_opts, const rt_aov* out_host, const rt_aov_spec* spec_host,
                        rt_stats* stats) {
-  return rt::aov_impl(s, cam, opts, n_samples, out_host, nullptr, nullptr, false, false, true, stats, true,
-                      spec_opts, spec_host);
+  return rt::aov_impl({rt::AovMode::Spec, /*host=*/true, "rt_render_aov_spec", s, cam, opts, n_samples, stats,
+                       out_host, nullptr, nullptr, spec_host, spec_opts});
 }
 
 int rt_render_aov_spec_device(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts, int32_t n_samples,
                               const rt_aov_spec_opts* spec_opts, const rt_aov* out_device,
                               const rt_aov_spec* spec_device, rt_stats* stats) {
-  return rt::aov_impl(s, cam, opts, n_samples, out_device, nullptr, nullptr, false, false, false, stats, true,
-                      spec_opts, spec_device);
+  return rt::aov_impl({rt::AovMode::Spec, /*host=*/false, "rt_render_aov_spec", s, cam, opts, n_samples, stats,
+                       out_device, nullptr, nullptr, spec_device, spec_opts});
 }
 
 }  // extern "C"

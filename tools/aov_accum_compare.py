@@ -22,7 +22,6 @@ import torch  # before the library's HIP runtime initialises
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import go_raytracer_amd as rt  # noqa: E402
-from go_raytracer_amd import _lib  # noqa: E402
 
 PLANES = {"albedo": 3, "normal": 3, "depth": 0, "material": 0, "emission": 3, "surface_albedo": 3, "coverage": 0}
 FEATURE = ("albedo", "normal", "depth", "material")
@@ -49,11 +48,10 @@ def aov_calls(out):
                         else:
                             bufs[k] = np.full(shape, -7, np.int32 if k == "material" else np.float32)
                     ptr = {k: (v.data_ptr() if device else v.ctypes.data) for k, v in bufs.items()}
-                    a = _lib.RtAov(*[ptr.get(k) for k in FEATURE])
-                    e = _lib.RtAovEmit(*[ptr.get(k) for k in EMIT]) if any(k in ptr for k in EMIT) else None
+                    emit = any(k in ptr for k in EMIT)
                     o = sc._opts(3, 0, rank, nranks, 0, 0, False, None)
-                    sc._aov(cam, o, n, a, e, device)
-                    entry = "rt_render_aov" + ("_emit" if e is not None else "") + ("_device" if device else "")
+                    sc._aov(cam, o, n, "emit" if emit else "first", device, ptr, (0, 0.0))
+                    entry = "rt_render_aov" + ("_emit" if emit else "") + ("_device" if device else "")
                     for k, v in bufs.items():
                         label = f"{entry:26s} {name:12s} {w:3d} x {h:3d} n {n} rank {rank}/{nranks} wanted " \
                                 f"{'+'.join(want) if len(want) < 7 else 'all':38s} {k}"
