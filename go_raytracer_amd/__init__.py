@@ -24,7 +24,7 @@ __all__ = ["Tree", "Camera", "Scene", "Accumulator", "quantize", "format_ppm", "
            "tune", "untune", "tuning", "tune_knobs", "tune_from_env",
            "demo_scene", "DEMO_SCENES", "build_bvh_boxes", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
            "format_ppm_device", "denoise", "denoise_device", "denoise_var", "denoise_var_device",
-           "RtDenoiseVarOpts", "reproject", "reproject_device", "reproject_emit", "reproject_emit_device", "reproject_light", "reproject_light_device",
+           "RtDenoiseVarOpts", "reproject", "reproject_device", "reproject_emit", "reproject_emit_device", "reproject_light", "reproject_light_device", "reproject_moments", "reproject_moments_device",
            "Temporal"]
 
 DEMO_SCENES = ("book1", "book2", "book3", "simple_light", "quads", "cornell", "cornell_smoke",
@@ -1399,6 +1399,120 @@ def reproject_light_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
     return _reproject_dev(True, cam_prev, prev, cam_cur, cur, out, opts, light=True)
 
 
+_MOMENT_MODES = {"plain": 0, "emit": 1, "light": 2, 0: 0, 1: 1, 2: 2}
+
+
+def _moments_opts(min_frames=0.0, var_radius=0):
+    return _lib.RtMomentsOpts(float(min_frames), int(var_radius))
+
+
+def _reproject_moments(device, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts):
+    """reproject_moments and reproject_moments_device (device): rt_reproject_moments[_device] on host
+    arrays or torch tensors"""
+    who = "reproject_moments_device" if device else "reproject_moments"
+    if isinstance(mode, bool) or mode not in _MOMENT_MODES:
+        raise ValueError(f"{who}: mode must be 'plain', 'emit' or 'light' (or 0, 1, 2), not {mode!r}")
+    mode = _MOMENT_MODES[mode]
+    emit, light = mode >= 1, mode == 2
+    if device:
+        import torch
+        if not isinstance(cur, dict) or not torch.is_tensor(cur.get("rgb")) or cur["rgb"].dim() != 3:
+            raise ValueError(f"{who}: cur['rgb'] must be a [H, W, 3] tensor")
+        a = cur["rgb"]
+        h, w = a.shape[:2]
+
+        def conv(name, t, shape):
+            if (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous()
+                    or tuple(t.shape) != shape or t.device != a.device):
+                raise ValueError(f"{who}: {name} must be a contiguous float32 tensor of shape {shape} "
+                                 "on cur['rgb']'s device")
+            return t
+
+        def ptr(t):
+            return t.data_ptr()
+
+        def new(shape):
+            return torch.empty(shape, dtype=torch.float32, device=a.device)
+    else:
+        if not isinstance(cur, dict) or cur.get("rgb") is None:
+            raise ValueError(f"{who}: cur['rgb'] is required")
+        h, w = np.shape(cur["rgb"])[:2]
+
+        def conv(name, t, shape):
+            t = np.ascontiguousarray(t, dtype=np.float32)
+            if t.shape != shape:
+                raise ValueError(f"{who}: {name} must have shape {shape}, not {t.shape}")
+            return t
+
+        def ptr(t):
+            return t.ctypes.data
+
+        def new(shape):
+            return np.empty(shape, np.float32)
+    fc, keep_c = _frame(who, "cur", cur, h, w, conv, ptr)
+    ec = None
+    if emit:
+        ec, keep_ec = _frame_emit(who, "cur", cur, h, w, conv, ptr)
+        keep_c = keep_c + keep_ec
+    cp = fp = ep = lp = None
+    keep_p = []
+    if prev is not None:
+        if cam_prev is None:
+            raise ValueError(f"{who}: prev without cam_prev")
+        fp, keep_p = _frame(who, "prev", prev, h, w, conv, ptr)
+        if emit:
+            ep, keep_ep = _frame_emit(who, "prev", prev, h, w, conv, ptr)
+            keep_p = keep_p + keep_ep
+        if prev.get("lum2") is None:
+            raise ValueError(f"{who}: prev['lum2'] is required (the lum2 plane an earlier call returned)")
+        keep_p.append(conv("prev['lum2']", prev["lum2"], (h, w)))
+        lp, cp = ptr(keep_p[-1]), cam_prev.to_c()
+    res = []
+    for k, ch in _FRAME_KEYS[:3] + (_LIGHT_KEYS if light else ()) + (("lum2", 0),):
+        shape = (h, w, ch) if ch else (h, w)
+        t = (out or {}).get(k)
+        t = new(shape) if t is None else conv(f"out[{k!r}]", t, shape)
+        if device:
+            if any(t.data_ptr() == p.data_ptr() for p in keep_p):
+                raise ValueError(f"{who}: out[{k!r}] is a buffer of prev (the taps gather from prev)")
+            if any(t.data_ptr() == p.data_ptr() for p in keep_c):
+                raise ValueError(f"{who}: out[{k!r}] is a buffer of cur (the window reads the current frame's "
+                                 "neighbours)")
+        res.append(t)
+    fo = _lib.RtFrame(*[ptr(t) for t in res[:3]], None, None, 0.0, 0)
+    eo = RtAovEmit(ptr(res[3]), None, ptr(res[4])) if light else None
+    o, mo = _reproject_opts(**opts), _moments_opts(min_frames, var_radius)
+    cc = cam_cur.to_c()
+    r = lambda x: None if x is None else C.byref(x)  # noqa: E731
+    args = [mode, r(cp), r(fp), r(ep), lp, r(cc), r(fc), r(ec), w, h, r(o), r(mo), r(fo), r(eo), ptr(res[-1])]
+    if device:
+        check(lib().rt_reproject_moments_device(*args, a.device.index or 0, _stream_of(a)))
+    else:
+        check(lib().rt_reproject_moments(*args))
+    return tuple(res)
+
+
+def reproject_moments(mode, cam_prev, prev, cam_cur, cur, min_frames=0.0, var_radius=0, **opts):
+    """reproject ('plain'), reproject_emit ('emit') or reproject_light ('light') with the second
+    moment of luminance carried through the history and the variance taken from the moments
+    (rt_reproject_moments; DESIGN.md "Luminance moments"), so that frames of ONE pass, whose own
+    variance is 0, come out with a variance rt_denoise_var can use.  Frames as the mode's, prev also
+    with "lum2" [H, W], the plane an earlier call returned.  prev=None (and cam_prev=None): no
+    history at all, a sequence's first frame.  A pixel whose history is at least min_frames frames
+    long (0: 4) takes the variance of its moments, any other the variance of the current frame's
+    window of var_radius (0: 3; -1: none, the mode's own variance).  Returns new arrays (rgb, var,
+    count, lum2), in the 'light' mode (rgb, var, count, emission, coverage, lum2)."""
+    return _reproject_moments(False, mode, cam_prev, prev, cam_cur, cur, None, min_frames, var_radius, opts)
+
+
+def reproject_moments_device(mode, cam_prev, prev, cam_cur, cur, out=None, min_frames=0.0, var_radius=0, **opts):
+    """rt_reproject_moments_device on torch tensors: frames as reproject_moments', every buffer a
+    contiguous float32 tensor on cur["rgb"]'s device.  `out` as reproject_device's, with "lum2" (and
+    "emission", "coverage" in the 'light' mode); here no out tensor may be one of cur's either: the
+    window reads the current frame's neighbours.  Returns reproject_moments' tuple."""
+    return _reproject_moments(True, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts)
+
+
 class Temporal:
     """The history of a moving camera (DESIGN.md "Temporal reprojection"): ``push(acc)`` takes the
     accumulator of the next frame, reprojects the stored history into its camera
@@ -1412,10 +1526,21 @@ class Temporal:
     coverage as history planes too: ``light`` is then the dict {"emission", "coverage"} of the
     tensors the last push wrote, the planes to hand the split filter in place of the frame's own:
     ``denoise_var_device(rgb, var, dict(acc.resolve_aov_device(), **temporal.light),
-    split_emitters=True)``."""
+    split_emitters=True)``.
+    moments=True (reproject_moments_device, DESIGN.md "Luminance moments"; combines with both
+    flags above) also carries the second moment of luminance and returns the variance of the
+    moments, or of a window of the frame while the history is shorter than min_frames (0: 4)
+    frames; var_radius is the window's (0: 3, -1: none).  The accumulators may then hold ONE pass
+    each: the returned variance is not 0 as the accumulator's own is, the first push's included."""
 
-    def __init__(self, split_emitters=False, light_history=False, **opts):
+    def __init__(self, split_emitters=False, light_history=False, moments=False, min_frames=0.0, var_radius=0,
+                 **opts):
         _reproject_opts(**opts)  # a wrong name fails here, not at the second push
+        if not moments and (min_frames or var_radius):
+            raise ValueError("Temporal: min_frames and var_radius are options of moments=True")
+        self._moments = bool(moments)
+        self._mopts = dict(min_frames=float(min_frames), var_radius=int(var_radius))
+        self._cur = None
         if light_history and not split_emitters:
             raise ValueError("Temporal: light_history needs split_emitters=True (the history of the emission "
                              "split's planes)")
@@ -1437,7 +1562,12 @@ class Temporal:
         the tensors (rgb [H, W, 3], var [H, W], count [H, W]) ready for denoise_var_device; they
         belong to this object and are overwritten by the push after the next.  The first push
         (and the first after reset()) returns the current frame unchanged.  With light_history the
-        blended emission and coverage are left in ``light`` (the first push: the frame's own)."""
+        blended emission and coverage are left in ``light`` (the first push: the frame's own).
+        With moments=True the returned var is not the accumulator's: it is the variance of the
+        history's luminance moments, or of a window of the frame where the history is shorter than
+        min_frames, so the first push returns the frame's colour and count with the window's
+        variance; the tensors then come from the object's own sets, never the accumulator's
+        resolve targets."""
         import torch
         if acc.features is None:
             raise ValueError("Temporal.push: needs an accumulator with features (the normal and depth guides)")
@@ -1452,6 +1582,8 @@ class Temporal:
         k = 0 if self._prev != 0 else 1  # the set the history is not in
         h, w = acc.shape
         dev = torch.device("cuda", acc._device)
+        if self._moments:
+            return self._push_moments(acc, k, h, w, dev, float(passes))
         s = self._sets[k]
         keys = _FRAME_KEYS + ((("emission", 3), ("coverage", 0)) if self._split else ())
         if s is None or s["depth"].shape != (h, w) or s["depth"].device != dev:
@@ -1468,6 +1600,42 @@ class Temporal:
             fn = (reproject_light_device if self._light else reproject_emit_device if self._split
                   else reproject_device)
             fn(self._cam, p, acc.camera, dict(s, count=float(passes)), out=s, **self._opts)
+        self._prev, self._cam = k, acc.camera
+        if self._light:
+            self.light = {"emission": s["emission"], "coverage": s["coverage"]}
+        return s["rgb"], s["var"], s["count"]
+
+    def _push_moments(self, acc, k, h, w, dev, passes):
+        """push with moments=True.  out may not be cur here (the window reads the frame's
+        neighbours), so the planes the kernel writes are resolved into a third set, `_cur`; normal
+        and depth, which it only reads, go straight into the new history's set, as do emission and
+        coverage unless the light history writes them."""
+        import torch
+
+        def tensors(keys):
+            return {key: torch.empty((h, w, ch) if ch else (h, w), dtype=torch.float32, device=dev) for key, ch in keys}
+        split = (("emission", 3), ("coverage", 0)) if self._split else ()
+        s = self._sets[k]
+        if s is None or "lum2" not in s or s["depth"].shape != (h, w) or s["depth"].device != dev:
+            s = self._sets[k] = tensors(_FRAME_KEYS + split + (("lum2", 0),))
+        c = self._cur
+        if c is None or c["var"].shape != (h, w) or c["var"].device != dev:
+            c = self._cur = tensors((("rgb", 3), ("var", 0)) + (split if self._light else ()))
+        acc.resolve_device(c["rgb"], c["var"])
+        guides = RtAov(None, s["normal"].data_ptr(), s["depth"].data_ptr(), None)
+        e = c if self._light else s
+        emit = RtAovEmit(e["emission"].data_ptr(), None, e["coverage"].data_ptr()) if self._split else None
+        check(lib().rt_accum_resolve_aov_device(acc._h(), C.byref(guides), emit and C.byref(emit)))
+        cur = dict(c, count=passes, normal=s["normal"], depth=s["depth"])
+        if self._split:
+            cur.update(emission=e["emission"], coverage=e["coverage"])
+        p = None if self._prev is None else self._sets[self._prev]
+        if p is not None and (p["depth"].shape != (h, w) or p["depth"].device != dev):
+            p = None
+        out = {key: s[key] for key in ("rgb", "var", "count", "lum2") + (("emission", "coverage") if self._light else ())}
+        mode = "light" if self._light else "emit" if self._split else "plain"
+        reproject_moments_device(mode, None if p is None else self._cam, p, acc.camera, cur, out=out, **self._mopts,
+                                 **self._opts)
         self._prev, self._cam = k, acc.camera
         if self._light:
             self.light = {"emission": s["emission"], "coverage": s["coverage"]}

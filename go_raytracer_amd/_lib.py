@@ -141,6 +141,13 @@ class RtReprojectOpts(C.Structure):  # rt_reproject_opts (0 = the library defaul
                 ("normal_tol", C.c_float), ("min_weight", C.c_float)]
 
 
+class RtMomentsOpts(C.Structure):  # rt_moments_opts (0 = the library default; radius -1: no window)
+    _fields_ = [("min_frames", C.c_float), ("radius", C.c_int32)]
+
+
+RT_REPROJECT_PLAIN, RT_REPROJECT_EMIT, RT_REPROJECT_LIGHT = 0, 1, 2
+
+
 class RtAccumInfo(C.Structure):  # rt_accum_info
     _fields_ = [("passes", C.c_int32), ("max_passes", C.c_int32),
                 ("samples_per_pixel", C.c_uint64), ("nonfinite_pixels", C.c_uint64),
@@ -360,6 +367,16 @@ SIGNATURES = {
                                        C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
                                        _I, _I, C.POINTER(RtReprojectOpts), C.POINTER(RtFrame),
                                        C.POINTER(RtAovEmit), _I, C.c_void_p]),
+    "rt_reproject_moments": (_I, [_I, C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
+                                  C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtFrame),
+                                  C.POINTER(RtAovEmit), _I, _I, C.POINTER(RtReprojectOpts),
+                                  C.POINTER(RtMomentsOpts), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
+                                  C.c_void_p]),
+    "rt_reproject_moments_device": (_I, [_I, C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
+                                         C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtFrame),
+                                         C.POINTER(RtAovEmit), _I, _I, C.POINTER(RtReprojectOpts),
+                                         C.POINTER(RtMomentsOpts), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
+                                         C.c_void_p, _I, C.c_void_p]),
     "rt_demo_scene": (_I, [_P, C.c_char_p, C.c_char_p, C.POINTER(RtCamera), C.POINTER(_I),
                            C.POINTER(_I)]),
     "rt_demo_scene_name": (_I, [_I, C.POINTER(C.c_char_p)]),

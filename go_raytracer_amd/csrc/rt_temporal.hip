@@ -34,6 +34,19 @@
 //                 other instances are what they were, instruction for instruction
 //                 (profiles/temporal_light_device_code.txt).
 //
+//   k_reproject<Emit, Light, true> : rt_reproject_moments' three instances.  The second raw moment of
+//                 luminance is one more history plane, gathered and blended with the colour's taps
+//                 and weights; the variance comes from the moments (q - y^2) / (K - 1) once the
+//                 history is min_frames long, and before that from an unweighted, depth- and
+//                 normal-gated window of the current frame.  The window loop runs only in the lanes
+//                 that need it (a first frame: all; a steady orbit: disocclusions), over clamped
+//                 addresses, as L1/L2 gathers like the taps: lanes of a row read one row segment
+//                 per step, shifted by one pixel from step to step.  LDS would need every lane of
+//                 the tile, halo included, to stage Y, depth, normal and validity before a barrier,
+//                 whether or not any lane needs the window.  out never aliases cur here.  The three
+//                 Mom = false instances are what they were, instruction for instruction
+//                 (profiles/temporal_moments_device_code.txt).
+//
 // Bytes per pixel: 36 read of the current frame (28 without var and count planes), up to 4 x 36
 // gathered from the previous one (L1/L2-resident: adjacent lanes share three of four taps), 20
 // written.  Emit: 16 more of the current pixel, 4 x 16 more gathered.  Light: 16 more written.
@@ -97,9 +110,72 @@ __device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y 
 __device__ __forceinline__ V3 load3(const float* p, size_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
 __device__ __forceinline__ bool finite3(V3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
 
+// rt_reproject_moments' own arguments (the moment planes and the resolved rt_moments_opts); no
+// member without it, as EmitPlanes
+template <bool Mom>
+struct MomPlanes {};
+template <>
+struct MomPlanes<true> {
+  const float* prev_lum2;  // NULL: no history at all (prev = NULL; the kernel's prev is then cur, never a tap)
+  float* out_lum2;
+  float min_frames;
+  int radius;  // < 0: no spatial estimate
+};
+
+// a kernel's last argument: both sets as bases, so that an empty one takes no kernel argument space
+template <bool Emit, bool Light, bool Mom>
+struct Extra : EmitPlanes<Emit, Light>, MomPlanes<Mom> {};
+
+__device__ __forceinline__ float lum(V3 a) { return 0.2126f * a.x + 0.7152f * a.y + 0.0722f * a.z; }
+
+// the spatial estimate's b - a^2 with Bessel's factor, max(b - a^2, 0) T / (T - 1) (0 when T < 2),
+// over the current frame's window around (x, y): rows then columns in ascending order, addresses
+// clamped, a pixel outside the image or the rules selected to 0 before any arithmetic.  Called by
+// the lanes that need it only: neighbouring lanes read neighbouring addresses, L1/L2 gathers as
+// the taps'
 template <bool Emit, bool Light>
+__device__ __forceinline__ float window_var(const TpParams& P, const Planes& cur, const EmitPlanes<Emit, Light>& em,
+                                            int x, int y, V3 np, float dp, int R) {
+  const float tol_d = P.depth_tol * dp;
+  float a = 0.0f, b = 0.0f, T = 0.0f;
+  for (int dy = -R; dy <= R; ++dy) {
+    const int ty = y + dy, cy = min(max(ty, 0), P.h - 1);
+    for (int dx = -R; dx <= R; ++dx) {
+      const int tx = x + dx, cx = min(max(tx, 0), P.w - 1);
+      const size_t ti = (size_t)cy * P.w + cx;
+      const V3 ct = load3(cur.rgb, ti), nt = load3(cur.normal, ti);
+      const float vt = cur.var ? cur.var[ti] : 0.0f;
+      const float cntt = cur.count ? cur.count[ti] : P.cur_count;
+      const float dt = cur.depth[ti];
+      const float nx = np.x - nt.x, ny = np.y - nt.y, nz = np.z - nt.z;
+      bool ok = cx == tx && cy == ty && finite3(ct) && isfinite(vt) && isfinite(cntt) && cntt > 0.0f &&
+                ((dx == 0 && dy == 0) ||
+                 (fabsf(dt - dp) <= tol_d && nx * nx + ny * ny + nz * nz <= P.normal_tol));
+      V3 xt = {ok ? ct.x : 0.0f, ok ? ct.y : 0.0f, ok ? ct.z : 0.0f};
+      if constexpr (Emit) {
+        const V3 et = load3(em.cur_emission, ti);
+        const float covt = em.cur_coverage[ti];
+        ok = ok && finite3(et) && covt >= 0.0f && covt < 1.0f;
+        const float kt = ok ? 1.0f - covt : 1.0f;
+        xt = {((ok ? ct.x : 0.0f) - (ok ? et.x : 0.0f)) / kt, ((ok ? ct.y : 0.0f) - (ok ? et.y : 0.0f)) / kt,
+              ((ok ? ct.z : 0.0f) - (ok ? et.z : 0.0f)) / kt};
+      }
+      const float yt = lum(xt);
+      a += yt;
+      b += yt * yt;
+      T += ok ? 1.0f : 0.0f;
+    }
+  }
+  if (T < 2.0f) return 0.0f;
+  const float am = a / T, bm = b / T;
+  return fmaxf(bm - am * am, 0.0f) * (T / (T - 1.0f));
+}
+
+template <bool Emit, bool Light, bool Mom>
 __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Planes cur, Planes out,
-                                                   EmitPlanes<Emit, Light> em) {
+                                                   Extra<Emit, Light, Mom> ex) {
+  const EmitPlanes<Emit, Light>& em = ex;
+  const MomPlanes<Mom>& mo = ex;
   static_assert(Emit || !Light, "the light history is a history of the emission split's planes");
   const int tile_y = blockIdx.x / P.tiles_x, tile_x = blockIdx.x - tile_y * P.tiles_x;
   const int x = tile_x * kTW + (threadIdx.x & (kTW - 1)), y = tile_y * kTH + (threadIdx.x >> 6);
@@ -132,6 +208,12 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
     vz = v / (kc * kc);
   }
   bool hist = valid && isfinite(dp) && dp > 0.0f && finite3(np);
+  float qc = 0.0f, sq = 0.0f;  // Mom: the current pixel's second moment Y(z)^2, and the taps' sum
+  if constexpr (Mom) {
+    hist = hist && mo.prev_lum2 != nullptr;
+    const float yc = lum(z);
+    qc = yc * yc;
+  }
 
   // the hit point relative to the previous centre, and its pixel in the previous camera
   const float fx = (float)x, fy = (float)y;
@@ -172,6 +254,11 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
       bool ok = hist && cx == qx && cy == qy && finite3(cq) && isfinite(vq) && isfinite(cntq) &&
                 cntq > 0.0f && dq > 0.0f && fabsf(dq - d1) <= tol_d &&
                 nx * nx + ny * ny + nz * nz <= P.normal_tol;
+      float lq = 0.0f;
+      if constexpr (Mom) {  // one more term of the tap rule: a finite second moment
+        lq = mo.prev_lum2 ? mo.prev_lum2[qi] : 0.0f;
+        ok = ok && isfinite(lq);
+      }
       V3 eq = {0.0f, 0.0f, 0.0f};
       float covq = 0.0f;
       bool okl = false;  // Light: a light tap (a surface tap, or a fully covered one)
@@ -200,6 +287,7 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
       sb += beta * tq.z;
       sv += beta * beta * tv;
       sn += beta * (ok ? cntq : 0.0f);
+      if constexpr (Mom) sq += beta * (ok ? lq : 0.0f);
       if constexpr (Light) {
         const float bl = okl ? bu[a] * bv[b] : 0.0f;
         Sl += bl;
@@ -210,6 +298,70 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
         sm += bl * (okl ? cntq : 0.0f);
       }
     }
+  }
+  if constexpr (Mom) {
+    // the three modes' blend in k_reproject<true, true>'s form (for the two others h_l = h_s and
+    // w_c = n_c, and the written-out multiply-add is theirs), with the second moment blended by the
+    // colour's weights and the variance taken from the moments or from the window
+    const bool hs = hist && S >= P.min_weight;
+    bool hl = hs;
+    if constexpr (Light) hl = hist && Sl >= P.min_weight;
+    const bool blend = (hs || hl) && (hs || wc > 0.0f);
+    const bool surf = valid && wc > 0.0f;  // the current pixel has a surface sample
+    const float inv = 1.0f / fmaxf(S, P.min_weight);
+    const float cap = P.max_history > 0.0f ? P.max_history : 8.0f * nc;
+    const float nh = hs ? fminf(sn * inv, cap) : 0.0f;
+    const float n = nh + wc;
+    const float K = hs && surf ? n / wc : 1.0f;  // the history length in frames
+    const bool use_t = hs && surf && K >= mo.min_frames;
+    float vs = 0.0f;
+    if (mo.radius >= 0 && surf && !use_t) vs = window_var<Emit, Light>(P, cur, em, x, y, np, dp, mo.radius) / K;
+    V3 o = c, oe = e;
+    float ov = v, on = nc, oc = covc, oq = 0.0f;
+    if (blend) {
+      const float in = 1.0f / n, vh = sv * (inv * inv);
+      o.x = fmaf(wc, z.x, nh * (sr * inv)) * in;
+      o.y = fmaf(wc, z.y, nh * (sg * inv)) * in;
+      o.z = fmaf(wc, z.z, nh * (sb * inv)) * in;
+      ov = fmaf(wc * wc, vz, nh * nh * vh) * (in * in);
+      oq = (nh * (sq * inv) + wc * qc) * in;  // q before the blend, then the colour's weights
+      if (mo.radius >= 0 && surf) {
+        const float yo = lum(o);
+        ov = use_t ? fmaxf(oq - yo * yo, 0.0f) / (K - 1.0f) : vs;
+      }
+      float ko = kc;
+      if constexpr (Light) {
+        const float invl = 1.0f / fmaxf(Sl, P.min_weight);
+        const float mh = hl ? fminf(sm * invl, cap) : 0.0f;
+        on = fmaxf(nh, mh) + nc;
+        const float im = 1.0f / (mh + nc);
+        oc = (mh * (sk * invl) + nc * covc) * im;
+        oe = {(mh * (ser * invl) + nc * e.x) * im, (mh * (seg * invl) + nc * e.y) * im,
+              (mh * (seb * invl) + nc * e.z) * im};
+        ko = 1.0f - oc;
+        o = {ko * o.x + oe.x, ko * o.y + oe.y, ko * o.z + oe.z};
+        ov = ko * ko * ov;
+      } else {
+        on = n;
+        if constexpr (Emit) {
+          o = {kc * o.x + e.x, kc * o.y + e.y, kc * o.z + e.z};
+          ov = kc * kc * ov;
+        }
+      }
+    } else if (surf) {  // no history: the pixel's own colour, its own moment, the window's variance
+      oq = qc;
+      if (mo.radius >= 0) ov = kc * kc * vs;
+    }
+    if (out.rgb) out.rgb[3 * pi] = o.x, out.rgb[3 * pi + 1] = o.y, out.rgb[3 * pi + 2] = o.z;
+    if (out.var) out.var[pi] = ov;
+    if (out.count) out.count[pi] = on;
+    if constexpr (Light) {
+      if (em.out_emission)
+        em.out_emission[3 * pi] = oe.x, em.out_emission[3 * pi + 1] = oe.y, em.out_emission[3 * pi + 2] = oe.z;
+      if (em.out_coverage) em.out_coverage[pi] = oc;
+    }
+    mo.out_lum2[pi] = oq;
+    return;
   }
   if constexpr (Light) {
     // n_h from the surface taps, m_h from the light taps; a sum below min_weight is no history of
@@ -226,6 +378,7 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
       const float nh = hs ? fminf(sn * inv, cap) : 0.0f, vh = sv * (inv * inv);
       const float mh = hl ? fminf(sm * invl, cap) : 0.0f;
       const float n = nh + wc, in = 1.0f / n;
+      // (restated in the Mom branch above: a change here goes there too)
       // the blend below, with its one fused multiply-add written out as the compiler contracts it in
       // the two other instances: zero emission and coverage must give rt_reproject's bits
       o.x = fmaf(wc, z.x, nh * (sr * inv)) * in;
@@ -258,6 +411,8 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
     const float cap = P.max_history > 0.0f ? P.max_history : 8.0f * nc;
     const float nh = fminf(sn * inv, cap), vh = sv * (inv * inv);
     const float n = nh + nc, in = 1.0f / n;
+    // (the Mom branch above restates this blend and the Light one: a change here goes there too, or
+    // tests/test_reproject_moments_gpu.py's bit identity with these instances fails)
     o.x = (nh * (sr * inv) + nc * z.x) * in;
     o.y = (nh * (sg * inv) + nc * z.y) * in;
     o.z = (nh * (sb * inv) + nc * z.z) * in;
@@ -276,7 +431,8 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
 // ---- host -------------------------------------------------------------------------------------
 
 std::mutex g_mu;        // one host-staged call at a time: the staging buffer is shared
-DeviceScratch g_stage;  // the host entries' staged frames (72 B per pixel, 104 with the emit planes)
+DeviceScratch g_stage;  // the host entries' staged frames (72 B per pixel, 104 with the emit planes;
+                        // rt_reproject_moments: 100, 132 and in the light mode 148)
 
 V3 v3(const double* a) { return {(float)a[0], (float)a[1], (float)a[2]}; }
 V3 v3_diff(const double* a, const double* b) {  // the difference in fp64, then rounded
@@ -354,22 +510,94 @@ int resolve(const char* who, bool emit, bool light, const rt_camera* cam_prev, c
   return RT_OK;
 }
 
+// rt_reproject_moments' arguments beyond its mode's
+struct Moments {
+  const float* prev_lum2;
+  const rt_moments_opts* mopts;
+  float* out_lum2;
+};
+
+// the moments entries' own checks, then the mode's (resolve).  prev == NULL is no history at all:
+// the three prev arguments come back as the current frame's, which the kernel reads (clamped
+// addresses need memory behind them) and never takes a tap from
+int resolve_moments(const char* who, bool emit, bool light, const rt_camera** cam_prev, const rt_frame** prev,
+                    const rt_aov_emit** prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
+                    const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts, const Moments& m,
+                    const rt_frame* out, const rt_aov_emit* out_emit, TpParams* P, MomPlanes<true>* mo) {
+  if (!m.out_lum2) return set_error(RT_ERR_INVALID, "%s: null out_lum2", who);
+  const bool no_prev = !*prev;
+  if (!no_prev && !m.prev_lum2) return set_error(RT_ERR_INVALID, "%s: prev without prev_lum2", who);
+  const rt_moments_opts mop = m.mopts ? *m.mopts : rt_moments_opts{};
+  if (mop.radius < -1 || mop.radius > 8)
+    return set_error(RT_ERR_INVALID, "%s: radius %d (-1: no spatial estimate; at most 8)", who, mop.radius);
+  if (!(mop.min_frames >= 0.0f) || !isfinite(mop.min_frames) || (mop.min_frames > 0.0f && mop.min_frames < 2.0f))
+    return set_error(RT_ERR_INVALID, "%s: min_frames must be 0 (the default) or a finite number >= 2", who);
+  const float* in[17] = {};  // every input plane
+  int ni = 0;
+  if (!no_prev) {
+    for (const float* b : {(const float*)(*prev)->rgb, (const float*)(*prev)->var, (const float*)(*prev)->count,
+                           (const float*)(*prev)->normal, (const float*)(*prev)->depth, m.prev_lum2})
+      in[ni++] = b;
+    if (emit && *prev_emit)
+      for (const float* b : {(*prev_emit)->emission, (*prev_emit)->surface_albedo, (*prev_emit)->coverage}) in[ni++] = b;
+  }
+  const int first_cur = ni;
+  if (cur)
+    for (const float* b : {cur->rgb, cur->var, cur->count, cur->normal, cur->depth}) in[ni++] = b;
+  if (emit && cur_emit)
+    for (const float* b : {cur_emit->emission, cur_emit->surface_albedo, cur_emit->coverage}) in[ni++] = b;
+  for (int i = 0; i < ni; ++i)
+    if (in[i] == m.out_lum2) return set_error(RT_ERR_INVALID, "%s: out_lum2 aliases an input plane", who);
+  const float* ob[5] = {out ? out->rgb : nullptr, out ? out->var : nullptr, out ? out->count : nullptr,
+                        light && out_emit ? out_emit->emission : nullptr,
+                        light && out_emit ? out_emit->coverage : nullptr};
+  for (const float* o : ob) {
+    if (o && o == m.out_lum2) return set_error(RT_ERR_INVALID, "%s: out_lum2 aliases a buffer of out", who);
+    if (o && !no_prev && o == m.prev_lum2)
+      return set_error(RT_ERR_INVALID, "%s: out aliases prev_lum2 (the taps gather from prev)", who);
+  }
+  for (const float* o : ob)
+    for (int i = first_cur; i < ni; ++i)
+      if (o && o == in[i])
+        return set_error(RT_ERR_INVALID,
+                         "%s: out aliases a buffer of cur (the window reads the current frame's neighbours)", who);
+  if (no_prev) *cam_prev = cam_cur, *prev = cur, *prev_emit = cur_emit;
+  const int rc = resolve(who, emit, light, *cam_prev, *prev, *prev_emit, cam_cur, cur, cur_emit, w, h, opts, out,
+                         out_emit, P);
+  if (rc) return rc;
+  *mo = {no_prev ? nullptr : m.prev_lum2, m.out_lum2, mop.min_frames > 0.0f ? mop.min_frames : 4.0f,
+         mop.radius == 0 ? 3 : mop.radius};
+  return RT_OK;
+}
+
+// one instance's launch; mom: rt_reproject_moments' arguments, NULL for the older entries' kernels
+template <bool Emit, bool Light>
+void launch_as(unsigned tiles, hipStream_t s, const TpParams& P, const Planes& prev, const Planes& cur,
+               const Planes& out, const EmitPlanes<Emit, Light>& em, const MomPlanes<true>* mom) {
+  if (mom)
+    hipLaunchKernelGGL((k_reproject<Emit, Light, true>), dim3(tiles), dim3(256), 0, s, P, prev, cur, out,
+                       Extra<Emit, Light, true>{em, *mom});
+  else
+    hipLaunchKernelGGL((k_reproject<Emit, Light, false>), dim3(tiles), dim3(256), 0, s, P, prev, cur, out,
+                       Extra<Emit, Light, false>{em, {}});
+}
+
 // emit: the frames' rt_aov_emit (both NULL for rt_reproject's kernel, both checked by resolve);
 // out_emit: the new history's light planes (rt_reproject_light's kernel), NULL for the others
 int launch(const TpParams& P, const Planes& prev, const Planes& cur, const Planes& out,
-           const rt_aov_emit* prev_emit, const rt_aov_emit* cur_emit, const rt_aov_emit* out_emit, hipStream_t s) {
-  const int64_t tiles = (int64_t)P.tiles_x * ((P.h + kTH - 1) / kTH);  // < 2^31 / 3: w h is
+           const rt_aov_emit* prev_emit, const rt_aov_emit* cur_emit, const rt_aov_emit* out_emit, hipStream_t s,
+           const MomPlanes<true>* mom = nullptr) {
+  const unsigned tiles = (unsigned)((int64_t)P.tiles_x * ((P.h + kTH - 1) / kTH));  // < 2^31 / 3: w h is
   if (out_emit) {
     const EmitPlanes<true, true> em = {prev_emit->emission, prev_emit->coverage, cur_emit->emission,
                                        cur_emit->coverage,  out_emit->emission,  out_emit->coverage};
-    hipLaunchKernelGGL((k_reproject<true, true>), dim3((unsigned)tiles), dim3(256), 0, s, P, prev, cur, out, em);
+    launch_as(tiles, s, P, prev, cur, out, em, mom);
   } else if (prev_emit) {
     const EmitPlanes<true, false> em = {prev_emit->emission, prev_emit->coverage, cur_emit->emission,
                                         cur_emit->coverage};
-    hipLaunchKernelGGL((k_reproject<true, false>), dim3((unsigned)tiles), dim3(256), 0, s, P, prev, cur, out, em);
+    launch_as(tiles, s, P, prev, cur, out, em, mom);
   } else {
-    hipLaunchKernelGGL((k_reproject<false, false>), dim3((unsigned)tiles), dim3(256), 0, s, P, prev, cur, out,
-                       EmitPlanes<false, false>{});
+    launch_as(tiles, s, P, prev, cur, out, EmitPlanes<false, false>{}, mom);
   }
   HIP_OK(hipGetLastError());
   return RT_OK;
@@ -379,16 +607,20 @@ int launch(const TpParams& P, const Planes& prev, const Planes& cur, const Plane
 int reproject_device(const char* who, bool emit, bool light, const rt_camera* cam_prev, const rt_frame* prev,
                      const rt_aov_emit* prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
                      const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
-                     const rt_frame* out, const rt_aov_emit* out_emit, int device, void* stream) {
+                     const rt_frame* out, const rt_aov_emit* out_emit, int device, void* stream,
+                     const Moments* m = nullptr) {
   TpParams P;
-  int rc = resolve(who, emit, light, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out, out_emit,
-                   &P);
+  MomPlanes<true> mo;
+  int rc = m ? resolve_moments(who, emit, light, &cam_prev, &prev, &prev_emit, cam_cur, cur, cur_emit, w, h, opts,
+                               *m, out, out_emit, &P, &mo)
+             : resolve(who, emit, light, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out,
+                       out_emit, &P);
   if (rc) return rc;
   if ((rc = device_ok(who, device))) return rc;
   DeviceGuard dg;
   HIP_OK(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  rc = launch(P, planes_of(prev), planes_of(cur), planes_of(out), prev_emit, cur_emit, out_emit, s);
+  rc = launch(P, planes_of(prev), planes_of(cur), planes_of(out), prev_emit, cur_emit, out_emit, s, m ? &mo : nullptr);
   HIP_OK(hipStreamSynchronize(s));
   return rc;
 }
@@ -398,10 +630,14 @@ int reproject_device(const char* who, bool emit, bool light, const rt_camera* ca
 int reproject_host(const char* who, bool emit, bool light, const rt_camera* cam_prev, const rt_frame* prev,
                    const rt_aov_emit* prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
                    const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
-                   const rt_frame* out, const rt_aov_emit* out_emit) {
+                   const rt_frame* out, const rt_aov_emit* out_emit, const Moments* m = nullptr) {
   TpParams P;
-  int rc = resolve(who, emit, light, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out, out_emit,
-                   &P);
+  MomPlanes<true> mo;
+  const bool no_prev = m && !prev;
+  int rc = m ? resolve_moments(who, emit, light, &cam_prev, &prev, &prev_emit, cam_cur, cur, cur_emit, w, h, opts,
+                               *m, out, out_emit, &P, &mo)
+             : resolve(who, emit, light, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out,
+                       out_emit, &P);
   if (rc) return rc;
   if ((rc = device_ok(who, 0))) return rc;
   DeviceGuard dg;
@@ -410,17 +646,19 @@ int reproject_host(const char* who, bool emit, bool light, const rt_camera* cam_
   hipStream_t s = nullptr;
   // both frames as 9 planes-floats per pixel each: rgb, var, count, normal, depth, and with emit 4
   // more: emission, coverage.  out is written over cur's copy (out may alias cur), into the var
-  // and count slots also when cur has neither; out_emit over cur_emit's copy
+  // and count slots also when cur has neither; out_emit over cur_emit's copy.  The moments entries
+  // write beside the frames instead (the window reads cur's copy): prev's lum2, then out as rgb,
+  // var, count, lum2 and in the light mode emission, coverage: 7 or 11 floats more
   const size_t n = (size_t)w * h;
   constexpr int kOff[8] = {0, 3, 4, 5, 8, 9, 12, 13};
   const int nbuf = emit ? 7 : 5, per = kOff[nbuf];
   void* stg = nullptr;
-  if ((rc = g_stage.get(0, n * 4 * 2 * per, &stg, who))) return rc;
+  if ((rc = g_stage.get(0, n * 4 * (2 * per + (m ? (light ? 11 : 7) : 0)), &stg, who))) return rc;
   Planes d[2];
   rt_aov_emit de[2];
   const rt_frame* src[2] = {prev, cur};
   const rt_aov_emit* esrc[2] = {prev_emit, cur_emit};
-  for (int f = 0; f < 2; ++f) {
+  for (int f = no_prev ? 1 : 0; f < 2; ++f) {
     float* base = (float*)stg + (size_t)f * per * n;
     const float* host[7] = {src[f]->rgb,    src[f]->var,   src[f]->count,
                             src[f]->normal, src[f]->depth, emit ? esrc[f]->emission : nullptr,
@@ -434,12 +672,27 @@ int reproject_host(const char* who, bool emit, bool light, const rt_camera* cam_
     d[f] = {dev[0], dev[1], dev[2], dev[3], dev[4]};
     de[f] = {dev[5], nullptr, dev[6]};
   }
-  float* cbase = (float*)stg + (size_t)per * n;
+  if (no_prev) d[0] = d[1], de[0] = de[1];  // read through clamped addresses, never a tap
+  float* mbase = (float*)stg + (size_t)2 * per * n;  // the moments entries' planes
+  float* cbase = m ? mbase + n : (float*)stg + (size_t)per * n;
   const Planes o = {out->rgb ? cbase : nullptr, out->var ? cbase + kOff[1] * n : nullptr,
                     out->count ? cbase + kOff[2] * n : nullptr, nullptr, nullptr};
   rt_aov_emit oe = {};
-  if (light) oe = {out_emit->emission ? de[1].emission : nullptr, nullptr, out_emit->coverage ? de[1].coverage : nullptr};
-  rc = launch(P, d[0], d[1], o, emit ? &de[0] : nullptr, emit ? &de[1] : nullptr, light ? &oe : nullptr, s);
+  if (light && m)
+    oe = {out_emit->emission ? cbase + 6 * n : nullptr, nullptr, out_emit->coverage ? cbase + 9 * n : nullptr};
+  else if (light)
+    oe = {out_emit->emission ? de[1].emission : nullptr, nullptr, out_emit->coverage ? de[1].coverage : nullptr};
+  if (m) {
+    if (mo.prev_lum2) {
+      HIP_OK(hipMemcpyAsync(mbase, mo.prev_lum2, n * 4, hipMemcpyHostToDevice, s));
+      mo.prev_lum2 = mbase;
+    }
+    mo.out_lum2 = cbase + 5 * n;
+  }
+  rc = launch(P, d[0], d[1], o, emit ? &de[0] : nullptr, emit ? &de[1] : nullptr, light ? &oe : nullptr, s,
+              m ? &mo : nullptr);
+  if (!rc && m && hipMemcpyAsync(m->out_lum2, mo.out_lum2, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
+    rc = set_error(RT_ERR_DEVICE, "%s: copy to host failed", who);
   if (!rc && ((o.rgb && hipMemcpyAsync(out->rgb, o.rgb, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess) ||
               (o.var && hipMemcpyAsync(out->var, o.var, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
               (o.count && hipMemcpyAsync(out->count, o.count, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
@@ -500,6 +753,34 @@ int rt_reproject_light(const rt_camera* cam_prev, const rt_frame* prev, const rt
                        const rt_reproject_opts* opts, const rt_frame* out, const rt_aov_emit* out_emit) {
   return reproject_host("rt_reproject_light", true, true, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h,
                         opts, out, out_emit);
+}
+
+int rt_reproject_moments_device(int mode, const rt_camera* cam_prev, const rt_frame* prev_dev,
+                                const rt_aov_emit* prev_emit_dev, const float* prev_lum2_dev,
+                                const rt_camera* cam_cur, const rt_frame* cur_dev, const rt_aov_emit* cur_emit_dev,
+                                int w, int h, const rt_reproject_opts* opts, const rt_moments_opts* mopts,
+                                const rt_frame* out_dev, const rt_aov_emit* out_emit_dev, float* out_lum2_dev,
+                                int device, void* stream) {
+  const char* who = "rt_reproject_moments_device";
+  if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
+  const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
+  const Moments m = {prev_lum2_dev, mopts, out_lum2_dev};
+  return reproject_device(who, emit, light, cam_prev, prev_dev, emit ? prev_emit_dev : nullptr, cam_cur, cur_dev,
+                          emit ? cur_emit_dev : nullptr, w, h, opts, out_dev, light ? out_emit_dev : nullptr, device,
+                          stream, &m);
+}
+
+int rt_reproject_moments(int mode, const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
+                         const float* prev_lum2, const rt_camera* cam_cur, const rt_frame* cur,
+                         const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
+                         const rt_moments_opts* mopts, const rt_frame* out, const rt_aov_emit* out_emit,
+                         float* out_lum2) {
+  const char* who = "rt_reproject_moments";
+  if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
+  const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
+  const Moments m = {prev_lum2, mopts, out_lum2};
+  return reproject_host(who, emit, light, cam_prev, prev, emit ? prev_emit : nullptr, cam_cur, cur,
+                        emit ? cur_emit : nullptr, w, h, opts, out, light ? out_emit : nullptr, &m);
 }
 
 }  // extern "C"

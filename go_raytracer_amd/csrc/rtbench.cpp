@@ -13,7 +13,7 @@
 //                   rt_accum_add or rt_accum_select + rt_accum_add_active, rt_accum_info_get,
 //                   rt_accum_resolve, rt_accum_adapt_info, rt_accum_counts; rt_progress on a thread
 //   feature_planes  rt_render_aov[_emit|_media] or rt_accum_resolve_aov[_media]
-//   temporal_step   rt_reproject[_emit | _light] (the host entries: this client links no HIP runtime)
+//   temporal_step   rt_reproject[_emit | _light | _moments] (the host entries: this client links no HIP runtime)
 //   filter          rt_denoise[_var][_emit]
 //   write_aovs      rt_format_ppm per plane
 //   finish_frame    rt_format_ppm, the statistics line (-cpuprofile has no pprof to drive on the
@@ -55,8 +55,9 @@ struct Args {
   unsigned long long seed = 1, tree_seed = 1;
   bool progress = false, stats = false, denoise = false, denoise_var = false, split_emitters = false;
   bool accum_features = false, temporal = false, temporal_emit = false, aov_media = false, aov_specular = false;
-  bool temporal_light = false;
-  long long frames = 0, spec_bounces = 0;
+  bool temporal_light = false, temporal_moments = false;
+  long long frames = 0, spec_bounces = 0, moments_radius = 0;
+  double moments_frames = 0.0;
   double spec_fuzz = 0.0;
   double orbit = 0.0;
 };
@@ -91,6 +92,10 @@ std::vector<Flag> flags(Args& a) {
       {"frames", "render N frames, frame k to the -o name with _00k before the extension (see -orbit)", Flag::INT,
        &a.frames, "0"},
       {"mode", "kernel strategy: auto, fused or wavefront", Flag::STR, &a.mode, "auto"},
+      {"moments-frames", "with -temporal-moments: the history length in frames from which the moments are trusted (0 = 4; at least 2)",
+       Flag::F64, &a.moments_frames, "0"},
+      {"moments-radius", "with -temporal-moments: the radius of the window for shorter histories (0 = 3, a 7 x 7 window; -1 = no window; at most 8)",
+       Flag::INT, &a.moments_radius, "0"},
       {"o", "Specify a custom output file", Flag::STR, &a.out, "image.ppm"},
       {"orbit", "with -frames: turn the camera's look_from about the vup axis through look_at by DEG degrees per frame",
        Flag::F64, &a.orbit, "0"},
@@ -114,6 +119,8 @@ std::vector<Flag> flags(Args& a) {
        Flag::BOOL, &a.temporal_emit, ""},
       {"temporal-light", "as -temporal-emit, with emission and coverage carried as history planes too and the blended planes handed to the split filter (rt_reproject_light); instead of -temporal / -temporal-emit",
        Flag::BOOL, &a.temporal_light, ""},
+      {"temporal-moments", "with -temporal, -temporal-emit or -temporal-light: carry the second moment of luminance through the history and take the variance from it, or from a window of the frame (rt_reproject_moments); makes -denoise-var valid with -passes 1, e.g. -S 6 -passes 1 -accum-features -split-emitters -denoise-var -temporal-emit -temporal-moments -frames 8 -orbit 1",
+       Flag::BOOL, &a.temporal_moments, ""},
       {"tree-seed", "seed of the scene builder's rand (main.go's math/rand)", Flag::U64,
        &a.tree_seed, "1"},
       {"until", "add passes until the image's relative standard error is <= E (at most -passes, default 1024)",
@@ -241,6 +248,7 @@ struct Job {
   Filter filter = Filter::NONE;
   bool temporal = false, temporal_emit = false, want_var = false;
   bool temporal_light = false;  // the temporal stage through rt_reproject_light
+  bool temporal_moments = false;  // ... through rt_reproject_moments in the stage's mode
   bool counts = false, aov = false, print_stats = false;
   bool numbered = false;  // -frames: frame k goes to the -o name with _00k before the extension
   int n_frames = 1;
@@ -254,7 +262,17 @@ int make_job(const Args& a, const char* prog, Job& j) {
       {a.adaptive_set && !(a.adaptive > 0.0), "invalid value for flag -adaptive: the error threshold must be > 0"},
       {!a.counts.empty() && !a.adaptive_set, "-counts needs -adaptive"},
       // the variance comes from the passes: one pass has none
-      {a.denoise_var && !(a.passes >= 2 || ((a.until > 0.0 || a.adaptive_set) && a.passes == 0)),
+      // -temporal-moments modifies one of the three temporal stages
+      {a.temporal_moments && !(a.temporal || a.temporal_emit || a.temporal_light),
+       "-temporal-moments needs -temporal, -temporal-emit or -temporal-light"},
+      {(a.moments_frames != 0.0 || a.moments_radius != 0) && !a.temporal_moments,
+       "-moments-frames and -moments-radius need -temporal-moments"},
+      {a.moments_radius < -1 || a.moments_radius > 8 || !(a.moments_frames >= 0.0) || !(a.moments_frames <= 3.0e38) ||
+           (a.moments_frames > 0.0 && a.moments_frames < 2.0),
+       "invalid value for flag -moments-radius (-1..8) / -moments-frames (0, or finite and >= 2)"},
+      // ... unless the history brings one (-temporal-moments)
+      {a.denoise_var && !(a.passes >= 2 || ((a.until > 0.0 || a.adaptive_set) && a.passes == 0) ||
+                          (a.temporal_moments && a.passes == 1)),
        "-denoise-var needs -passes N with N >= 2, or -until / -adaptive"},
       {a.split_emitters && !filtered, "-split-emitters needs -denoise or -denoise-var"},  // nothing to split for
       {a.accum_features && !acc, "-accum-features needs -passes, -until or -adaptive"},  // no accumulator to keep them
@@ -287,6 +305,7 @@ int make_job(const Args& a, const char* prog, Job& j) {
   j.pass_cap = (int32_t)(a.passes > 0 ? a.passes : 1024);
   j.temporal_emit = a.temporal_emit;
   j.temporal_light = a.temporal_light;
+  j.temporal_moments = a.temporal_moments;
   j.temporal = a.temporal || a.temporal_emit || a.temporal_light;  // the same stage, through rt_reproject_emit / _light
   j.aov = !a.aov.empty();
   if (filtered || j.aov || j.temporal) j.source = a.accum_features ? Features::ACCUM : Features::PASS;
@@ -361,6 +380,9 @@ struct Ctx {
   // -temporal: the history (the frames before this one, reprojected and blended) and its camera
   std::vector<float> h_rgb, h_var, h_count, h_normal, h_depth, h_emission, h_coverage, count;
   std::vector<float> l_emission, l_coverage;  // -temporal-light: the blended light planes of this frame
+  // -temporal-moments: the history's second moment of luminance, and the frame's result (rt_reproject_moments
+  // never writes into the current frame's buffers)
+  std::vector<float> h_lum2, m_rgb, m_var, m_count, m_lum2;
   rt_camera h_cam;
   bool have_history = false;
 
@@ -408,6 +430,7 @@ struct Stats {
   const rt_accum_info* acc;    // -passes / -until / -adaptive, else null
   const rt_adapt_info* adapt;  // -adaptive, else null
   bool denoise_var, split_emitters, accum_features, temporal, temporal_emit, temporal_light, aov_media, aov_specular;
+  bool temporal_moments;
   int frame;  // -frames, else -1
 };
 
@@ -448,6 +471,7 @@ std::string stats_json(const Stats& s) {
   if (s.temporal) appendf(b, "\"temporal\": 1, \"ms_reproject\": %.3f, ", s.ms_reproject);
   if (s.temporal_emit) b += "\"temporal_emit\": 1, ";
   if (s.temporal_light) b += "\"temporal_light\": 1, ";
+  if (s.temporal_moments) b += "\"temporal_moments\": 1, ";
   if (s.aov_media) b += "\"aov_media\": 1, ";
   if (s.aov_specular) b += "\"aov_specular\": 1, ";
   appendf(b, "\"wall_s\": %.3f}", s.wall_s);
@@ -634,7 +658,27 @@ int temporal_step(const Job& j, Ctx& c) {
   const int w = c.d.width, h = c.d.height;
   c.count.assign(c.n_px(), (float)c.ai.passes);
   if (j.temporal_light) c.l_emission = c.emission, c.l_coverage = c.coverage;  // the first frame's are its own
-  if (c.have_history) {
+  if (j.temporal_moments) {
+    // every frame, the first without a history (prev = NULL): its variance is the window's
+    const size_t n = c.n_px();
+    c.m_rgb.resize(3 * n), c.m_var.resize(n), c.m_count.resize(n), c.m_lum2.resize(n);
+    const rt_frame prev = {c.h_rgb.data(), c.h_var.data(), c.h_count.data(), c.h_normal.data(), c.h_depth.data(), 0.0f, 0};
+    const rt_frame cur = {c.rgb.data(), c.var.data(), nullptr, c.normal.data(), c.depth.data(), (float)c.ai.passes, 0};
+    const rt_frame res = {c.m_rgb.data(), c.m_var.data(), c.m_count.data(), nullptr, nullptr, 0.0f, 0};
+    const rt_aov_emit prev_emit = {c.h_emission.data(), nullptr, c.h_coverage.data()};
+    const rt_aov_emit cur_emit = {c.emission.data(), nullptr, c.coverage.data()};
+    const rt_aov_emit res_emit = {c.l_emission.data(), nullptr, c.l_coverage.data()};
+    const rt_moments_opts mo = {(float)j.a.moments_frames, (int32_t)j.a.moments_radius};
+    const int mode = j.temporal_light ? RT_REPROJECT_LIGHT : j.temporal_emit ? RT_REPROJECT_EMIT : RT_REPROJECT_PLAIN;
+    const bool hh = c.have_history;
+    Call s;
+    s.ok("rt_reproject_moments",
+         rt_reproject_moments(mode, hh ? &c.h_cam : nullptr, hh ? &prev : nullptr, hh ? &prev_emit : nullptr,
+                              hh ? c.h_lum2.data() : nullptr, &c.cam, &cur, &cur_emit, w, h, nullptr, &mo, &res,
+                              &res_emit, c.m_lum2.data()));
+    if (s.rc != RT_OK) return fail(s.what, s.rc);
+    c.rgb = c.m_rgb, c.var = c.m_var, c.count = c.m_count, c.h_lum2 = c.m_lum2;
+  } else if (c.have_history) {
     const rt_frame prev = {c.h_rgb.data(), c.h_var.data(), c.h_count.data(), c.h_normal.data(), c.h_depth.data(), 0.0f, 0};
     const rt_frame cur = {c.rgb.data(), c.var.data(), nullptr, c.normal.data(), c.depth.data(), (float)c.ai.passes, 0};
     const rt_frame res = {c.rgb.data(), c.var.data(), c.count.data(), nullptr, nullptr, 0.0f, 0};
@@ -719,7 +763,7 @@ int finish_frame(const Job& j, Ctx& c) {
   s.acc = j.accumulate ? &c.ai : nullptr;
   s.adapt = j.adaptive ? &c.adi : nullptr;
   s.denoise_var = j.filter == Filter::VAR, s.split_emitters = j.emit, s.accum_features = j.accum_features;
-  s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.temporal_light = j.temporal_light, s.aov_media = j.media, s.aov_specular = j.specular;
+  s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.temporal_light = j.temporal_light, s.temporal_moments = j.temporal_moments, s.aov_media = j.media, s.aov_specular = j.specular;
   s.frame = j.numbered ? c.frame : -1;
   const std::string js = stats_json(s);
   if (j.print_stats) fprintf(stderr, "%s\n", js.c_str());

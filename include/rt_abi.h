@@ -1095,6 +1095,88 @@ int rt_reproject_light_device(const rt_camera* cam_prev, const rt_frame* prev_de
                               const rt_reproject_opts* opts, const rt_frame* out_dev,
                               const rt_aov_emit* out_emit_dev, int device, void* stream);
 
+/* The three reprojections above with the second raw moment of luminance carried as one more
+ * history plane, and the variance taken from the moments (DESIGN.md "Luminance moments"; Schied et
+ * al.'s temporal and spatial variance estimates).  The accumulator's variance is an estimate
+ * across the passes of one frame: 0 for a frame of one pass, however long its history.  Here the
+ * variance comes from the history itself once it is long enough, and below that from a window of
+ * the current frame, so frames of one pass can be filtered by rt_denoise_var.  Added without an
+ * ABI version change: detect by the symbols.
+ * mode selects the definition this one is a delta on: RT_REPROJECT_PLAIN rt_reproject's (prev_emit,
+ * cur_emit and out_emit are not read), RT_REPROJECT_EMIT rt_reproject_emit's (out_emit is not read),
+ * RT_REPROJECT_LIGHT rt_reproject_light's.  prev_lum2 and out_lum2 are [h][w] float planes; mopts
+ * NULL: the defaults.  Call x the colour the mode carries and blends: rgb in PLAIN, z = (rgb - E) /
+ * (1 - kappa) in EMIT and LIGHT exactly as those modes form it; w_c the weight of the current x
+ * in the blend: n_c in PLAIN and EMIT, rt_reproject_light's w_c in LIGHT; Y the luminance of
+ * rt_denoise_var, evaluated in fp32 as (0.2126 r + 0.7152 g) + 0.0722 b.
+ * The first raw moment needs no plane: Y is linear and the moment is blended by the weights the
+ * colour is blended with, so it is Y of the blended colour.
+ * Everything not named here is the selected mode's definition: the history lookup, tap validity,
+ * S, the cap, c_h, n_h, the blends of colour, count, emission and coverage, the pass-through sets.
+ *   current pixel: y_c = Y(x_c), q_c = y_c^2.
+ *   tap valid: the mode's rule (in LIGHT: the light tap's, so the surface tap's too), and the tap's
+ *     lum2 finite.  An invalid tap's lum2 is selected to 0 before any arithmetic.
+ *   history: q_h = sum beta q_tap / S over the taps of the surface colour.
+ *   blend: q_out = (n_h q_h + w_c q_c) / (n_h + w_c),   y_out = Y(x_blend).
+ *   history length in frames: K = (n_h + w_c) / w_c, for a pixel with surface history and w_c > 0.
+ *   temporal estimate: v_t = max(q_out - y_out^2, 0) / (K - 1): the variance of the blended mean
+ *     when K equally weighted frames are independent.  Exact while the cap has not bitten;
+ *     knowingly approximate once it has (old frames then weigh less than K says), or when the
+ *     frames bring different counts.
+ *   spatial estimate (radius >= 0): over the pixels t of the CURRENT frame with |t - p| <= radius
+ *     in both coordinates that are inside the image, valid by the mode's current-pixel rule with
+ *     kappa_t < 1 where the mode has a coverage, and within |depth_t - depth_p| <= depth_tol
+ *     depth_p and |n_p - n_t|^2 <= normal_tol (rt_reproject_opts'; p itself always counts).  T is
+ *     their number, a = sum Y(x_t) / T, b = sum Y(x_t)^2 / T, an unweighted box summed in fp32 row
+ *     by row in ascending order;  v_s = max(b - a^2, 0) (T / (T - 1)) / K, and 0 when T < 2.  It
+ *     counts texture detail inside the window as noise, as SVGF's spatial estimate does.
+ *   the variance v the mode carries on in place of its v_blend, for a pixel with w_c > 0:
+ *     v_t when the pixel found surface history and K >= min_frames; otherwise v_s, with K = 1 for
+ *     a pixel without surface history.  radius = -1: the mode's v_blend, unchanged (and the
+ *     current pixel's var where the mode passes it through).  A pixel of LIGHT with w_c = 0 that
+ *     blends (covered now, surface history behind it) keeps the mode's v_blend, and q_out = q_h.
+ *   re-lighting: what the mode does to v_blend is unchanged: out.var = k_c^2 v in EMIT,
+ *     (1 - kappa_out)^2 v in LIGHT, v in PLAIN.
+ *   pixels without surface history that are valid by the mode's rule with w_c > 0: rgb, count (and
+ *     LIGHT's blend of emission and coverage, where it has light history) as the mode writes them,
+ *     out_lum2 = q_c, out.var = the re-lit v_s (K = 1): k_c^2 v_s where the mode passes the pixel
+ *     through.  The one departure from "passes through bit for bit"; none with radius = -1.
+ *   invalid pixels, and covered pixels without surface history (LIGHT's inside of a light, EMIT's
+ *     kappa = 1): every plane passes through as the mode does, out_lum2 = 0.  Never taps.
+ *   no history at all: prev == NULL (cam_prev, prev_emit and prev_lum2 are then not read): every
+ *     pixel takes the no-history path, which is also what a prev of zero counts gives.  This makes
+ *     the first frame of a sequence filterable.
+ * Order of operations, in fp32: q of every frame is formed before the blend (q_c = y_c y_c; the
+ * taps bring theirs); q_out as written, a sum of two products times 1 / (n_h + w_c); then the
+ * subtraction q_out - y_out y_out, which cancels against y^2 and not against the variance: its
+ * rounding error is a few 2^-24 of lum2, whatever the variance.
+ * Argument checks, before any device is touched: the selected mode's own; RT_ERR_INVALID for an
+ * unknown mode; a NULL out_lum2; a prev given without prev_lum2; radius < -1 or > 8; min_frames
+ * negative, not finite or in (0, 2) (it would divide by K - 1 <= 0); out_lum2 equal to any input
+ * plane (of prev, prev_emit, prev_lum2, cur or cur_emit) or to an out or out_emit buffer; an out or
+ * out_emit buffer equal to prev_lum2 (a plane the taps gather, like prev's); and ANY out or out_emit
+ * buffer that is a buffer of cur or cur_emit: the window reads the current frame's neighbours, so the "out may
+ * alias cur" of the older entries cannot hold here.  Host and device forms as rt_reproject's;
+ * rt_reproject_moments stages 100 bytes per pixel in PLAIN, 132 in EMIT and 148 in LIGHT.  Two
+ * calls give identical bits. */
+enum { RT_REPROJECT_PLAIN = 0, RT_REPROJECT_EMIT = 1, RT_REPROJECT_LIGHT = 2 };
+typedef struct {
+  float   min_frames;       /* 0 -> 4: the history length, in frames, from which the moments are trusted */
+  int32_t radius;           /* 0 -> 3 (a 7 x 7 window); -1: no spatial estimate; at most 8 */
+} rt_moments_opts;
+int rt_reproject_moments(int mode, const rt_camera* cam_prev, const rt_frame* prev,
+                         const rt_aov_emit* prev_emit, const float* prev_lum2,
+                         const rt_camera* cam_cur, const rt_frame* cur, const rt_aov_emit* cur_emit,
+                         int w, int h, const rt_reproject_opts* opts, const rt_moments_opts* mopts,
+                         const rt_frame* out, const rt_aov_emit* out_emit, float* out_lum2);
+int rt_reproject_moments_device(int mode, const rt_camera* cam_prev, const rt_frame* prev_dev,
+                                const rt_aov_emit* prev_emit_dev, const float* prev_lum2_dev,
+                                const rt_camera* cam_cur, const rt_frame* cur_dev,
+                                const rt_aov_emit* cur_emit_dev, int w, int h,
+                                const rt_reproject_opts* opts, const rt_moments_opts* mopts,
+                                const rt_frame* out_dev, const rt_aov_emit* out_emit_dev,
+                                float* out_lum2_dev, int device, void* stream);
+
 /* Demo scenes mirroring main.go (by name or the main.go -S number).
  * names: book1, book2, book3, simple_light, quads, cornell, cornell_smoke, model
  * The camera receives the scene's settings; override fields afterwards. */

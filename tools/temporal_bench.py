@@ -21,6 +21,13 @@ and through Temporal(split_emitters=True, light_history=True), whose filter is g
 emission and coverage: the columns temporal_light and temporal_light_guided_filter.  rim_share_of_
 squared_error is, per column, the rim pixels' part of the summed squared error over all pixels.
 
+moments: rt_reproject_moments_device joins the time alternation in each mode, once
+with its defaults (both frames count 2, so K = 2 < min_frames and every pixel runs the 7 x 7
+window: the worst case) and once with var_radius = -1 (no window: what the moment plane alone
+costs).  quality_one_pass is the same orbit with ONE pass x 4 spp per frame through
+Temporal(split_emitters=True) and Temporal(split_emitters=True, moments=True), each followed by
+the guided filter.
+
 Prints one JSON object; -o FILE also writes it.
 """
 import argparse
@@ -91,6 +98,17 @@ def bench_time(width, rounds, warm):
     src = torch.empty(n * 50 // 4, dtype=torch.float32, device=dev).normal_()
     dst = torch.empty_like(src)
     den, vout = torch.empty_like(cur["rgb"]), torch.empty_like(cur["var"])
+    with torch.no_grad():
+        z = (prev["rgb"] - prev["emission"]) / (1.0 - prev["coverage"]).clamp_min(0.125)[..., None]
+        lum2 = torch.nan_to_num((z * torch.tensor([0.2126, 0.7152, 0.0722], device=dev)).sum(-1) ** 2).contiguous()
+    mplain = [dict(plain[0], lum2=lum2), dict(plain[1], count=2.0)]
+    mfull = [dict(prev, lum2=lum2), dict(cur, count=2.0)]
+    out_m = {m: dict({k: torch.empty_like(v) for k, v in (out_l if m == "light" else out).items()},
+                     lum2=torch.empty_like(lum2)) for m in ("plain", "emit", "light")}
+
+    def moments(mode, **kw):
+        f = mplain if mode == "plain" else mfull
+        return lambda: rt.reproject_moments_device(mode, cams[0], f[0], cams[1], f[1], out=out_m[mode], **kw)
     calls = {
         "reproject": lambda: rt.reproject_device(cams[0], plain[0], cams[1], dict(plain[1], count=2.0), out=out),
         "reproject_emit": lambda: rt.reproject_emit_device(cams[0], prev, cams[1], dict(cur, count=2.0), out=out_e),
@@ -98,6 +116,9 @@ def bench_time(width, rounds, warm):
         "denoise_var": lambda: rt.denoise_var_device(cur["rgb"], cur["var"], aov, out=den, var_out=vout),
         "copy_50_bytes_per_pixel": lambda: (dst.copy_(src), torch.cuda.synchronize()),
     }
+    for m in ("plain", "emit", "light"):
+        calls[f"moments_{m}"] = moments(m)
+        calls[f"moments_{m}_no_window"] = moments(m, var_radius=-1)
     ms = {k: [] for k in calls}
     for r in range(warm + rounds):
         for k, fn in calls.items():
@@ -164,6 +185,43 @@ def bench_quality(width, frames, degrees, ref_spp):
                         for c, x in cols.items()} for s, m in sets.items()}}
 
 
+def bench_quality_one_pass(width, frames, degrees, ref_spp):
+    t, cam, w, l = rt.demo_scene("cornell")
+    cam.Width, cam.SamplesPerPixel = width, 4
+    today, moments = rt.Temporal(split_emitters=True), rt.Temporal(split_emitters=True, moments=True)
+    with rt.Scene(t, w, l) as sc:
+        for k in range(frames):
+            camk = orbit(cam, degrees * k)
+            with sc.accumulator(camk, max_passes=1, features="emit") as acc:
+                acc.add(10 * k + 1)
+                a, b = today.push(acc), moments.push(acc)
+                if k == frames - 1:
+                    mean, _ = acc.resolve()
+                    aov = acc.resolve_aov_device()
+                    cover = aov["coverage"].cpu().numpy()
+                    cols = {"per_frame_mean": mean, "temporal_emit": a[0].cpu().numpy(),
+                            "temporal_emit_guided_filter":
+                                rt.denoise_var_device(a[0], a[1], aov, split_emitters=True).cpu().numpy(),
+                            "temporal_emit_moments_guided_filter":
+                                rt.denoise_var_device(b[0], b[1], aov, split_emitters=True).cpu().numpy()}
+                    var, cnt = b[1].cpu().numpy(), b[2].cpu().numpy()
+        camk.SamplesPerPixel = ref_spp
+        ref, _ = sc.render(camk, seed=977)
+    fin = np.isfinite(mean).all(-1) & np.isfinite(ref).all(-1)
+    near = cover > 0
+    for _ in range(2):
+        pad = np.pad(near, 1)
+        near = np.logical_or.reduce([pad[dy:dy + width, dx:dx + width] for dy in range(3) for dx in range(3)])
+    sets = {"all": fin, "rim": fin & (cover > 0) & (cover < 1), "with_history": fin & (cnt > 1.0),
+            "within_2_of_a_light": fin & near, "elsewhere": fin & ~near}
+    return {"image": f"cornell {width}x{width}", "frames": frames, "degrees_per_frame": degrees,
+            "passes_per_frame": 1, "spp_per_pass": 4, "reference_spp": ref_spp,
+            "pixels": {k: int(m.sum()) for k, m in sets.items()},
+            "moments_var_positive_share_with_history": float((var[sets["with_history"]] > 0).mean()),
+            "mse": {s: {c: float(((x[m].astype(np.float64) - ref[m]) ** 2).mean()) if m.any() else None
+                        for c, x in cols.items()} for s, m in sets.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-o", default=None)
@@ -176,7 +234,8 @@ def main():
     if rt.device_count() <= 0:
         raise SystemExit("temporal_bench: no HIP device visible")
     res = {"device": torch.cuda.get_device_name(0), "time": bench_time(a.width, a.rounds, 5),
-           "quality": bench_quality(a.quality_width, a.frames, 1.0, a.ref_spp)}
+           "quality": bench_quality(a.quality_width, a.frames, 1.0, a.ref_spp),
+           "quality_one_pass": bench_quality_one_pass(a.quality_width, a.frames, 1.0, a.ref_spp)}
     text = json.dumps(res, indent=1)
     print(text)
     if a.o:
