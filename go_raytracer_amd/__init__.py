@@ -9,6 +9,7 @@ through the HIP path (camera.go:156).  There is no CPU render path here: the
 HIP library must be built and a GPU present, otherwise calls raise.
 """
 import ctypes as C
+import math
 import weakref
 
 import numpy as np
@@ -24,7 +25,7 @@ __all__ = ["Tree", "Camera", "Scene", "Accumulator", "quantize", "format_ppm", "
            "tune", "untune", "tuning", "tune_knobs", "tune_from_env",
            "demo_scene", "DEMO_SCENES", "build_bvh_boxes", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
            "format_ppm_device", "denoise", "denoise_device", "denoise_var", "denoise_var_device",
-           "RtDenoiseVarOpts", "reproject", "reproject_device", "reproject_emit", "reproject_emit_device", "reproject_light", "reproject_light_device", "reproject_moments", "reproject_moments_device",
+           "RtDenoiseVarOpts", "reproject", "reproject_device", "reproject_emit", "reproject_emit_device", "reproject_light", "reproject_light_device", "reproject_moments", "reproject_moments_device", "reproject_clip", "reproject_clip_device",
            "Temporal"]
 
 DEMO_SCENES = ("book1", "book2", "book3", "simple_light", "quads", "cornell", "cornell_smoke",
@@ -1406,10 +1407,11 @@ def _moments_opts(min_frames=0.0, var_radius=0):
     return _lib.RtMomentsOpts(float(min_frames), int(var_radius))
 
 
-def _reproject_moments(device, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts):
+def _reproject_moments(device, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts, gamma=None):
     """reproject_moments and reproject_moments_device (device): rt_reproject_moments[_device] on host
-    arrays or torch tensors"""
-    who = "reproject_moments_device" if device else "reproject_moments"
+    arrays or torch tensors; with gamma (not None) reproject_clip and reproject_clip_device:
+    rt_reproject_clip[_device]"""
+    who = ("reproject_clip" if gamma is not None else "reproject_moments") + ("_device" if device else "")
     if isinstance(mode, bool) or mode not in _MOMENT_MODES:
         raise ValueError(f"{who}: mode must be 'plain', 'emit' or 'light' (or 0, 1, 2), not {mode!r}")
     mode = _MOMENT_MODES[mode]
@@ -1485,10 +1487,16 @@ def _reproject_moments(device, mode, cam_prev, prev, cam_cur, cur, out, min_fram
     cc = cam_cur.to_c()
     r = lambda x: None if x is None else C.byref(x)  # noqa: E731
     args = [mode, r(cp), r(fp), r(ep), lp, r(cc), r(fc), r(ec), w, h, r(o), r(mo), r(fo), r(eo), ptr(res[-1])]
+    entry = "rt_reproject_moments"
+    if gamma is not None:
+        if gamma > 0 and C.c_float(gamma).value == 0.0:
+            raise ValueError(f"{who}: gamma {gamma!r} rounds to 0 as a float, which selects the default")
+        args.insert(12, r(_lib.RtClipOpts(float(gamma))))  # copts follows mopts
+        entry = "rt_reproject_clip"
     if device:
-        check(lib().rt_reproject_moments_device(*args, a.device.index or 0, _stream_of(a)))
+        check(getattr(lib(), entry + "_device")(*args, a.device.index or 0, _stream_of(a)))
     else:
-        check(lib().rt_reproject_moments(*args))
+        check(getattr(lib(), entry)(*args))
     return tuple(res)
 
 
@@ -1513,6 +1521,22 @@ def reproject_moments_device(mode, cam_prev, prev, cam_cur, cur, out=None, min_f
     return _reproject_moments(True, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts)
 
 
+def reproject_clip(mode, cam_prev, prev, cam_cur, cur, min_frames=0.0, var_radius=0, gamma=0.0, **opts):
+    """reproject_moments with the history colour clamped, per channel, to mean +- gamma sigma of
+    the current frame's window before the blend (rt_reproject_clip; DESIGN.md "Clamping the
+    history"): a history the current frame contradicts, as a reflection that moved over a mirror
+    whose depth and normal did not, is overruled.  Arguments and result as reproject_moments';
+    gamma 0: the library default; var_radius = -1 is refused (there is no window)."""
+    return _reproject_moments(False, mode, cam_prev, prev, cam_cur, cur, None, min_frames, var_radius, opts, gamma)
+
+
+def reproject_clip_device(mode, cam_prev, prev, cam_cur, cur, out=None, min_frames=0.0, var_radius=0, gamma=0.0,
+                          **opts):
+    """rt_reproject_clip_device on torch tensors: reproject_moments_device with reproject_clip's
+    gamma."""
+    return _reproject_moments(True, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts, gamma)
+
+
 class Temporal:
     """The history of a moving camera (DESIGN.md "Temporal reprojection"): ``push(acc)`` takes the
     accumulator of the next frame, reprojects the stored history into its camera
@@ -1531,13 +1555,27 @@ class Temporal:
     flags above) also carries the second moment of luminance and returns the variance of the
     moments, or of a window of the frame while the history is shorter than min_frames (0: 4)
     frames; var_radius is the window's (0: 3, -1: none).  The accumulators may then hold ONE pass
-    each: the returned variance is not 0 as the accumulator's own is, the first push's included."""
+    each: the returned variance is not 0 as the accumulator's own is, the first push's included.
+    clip=True (reproject_clip_device, DESIGN.md "Clamping the history"; needs moments=True and a
+    window) clamps the reprojected colour to the current frame's neighbourhood before the blend,
+    mean +- clip_gamma sigma (0: the library default), so that a stale reflection on metal or glass
+    is overruled."""
 
     def __init__(self, split_emitters=False, light_history=False, moments=False, min_frames=0.0, var_radius=0,
-                 **opts):
+                 clip=False, clip_gamma=0.0, **opts):
         _reproject_opts(**opts)  # a wrong name fails here, not at the second push
         if not moments and (min_frames or var_radius):
             raise ValueError("Temporal: min_frames and var_radius are options of moments=True")
+        if clip and not moments:
+            raise ValueError("Temporal: clip=True needs moments=True (the clamp is a step of reproject_moments)")
+        if clip and int(var_radius) == -1:
+            raise ValueError("Temporal: clip=True needs a window: var_radius >= 0, not -1")
+        if not clip and clip_gamma:
+            raise ValueError("Temporal: clip_gamma is an option of clip=True")
+        if clip and (not (math.isfinite(clip_gamma) and clip_gamma >= 0)
+                     or (clip_gamma > 0 and C.c_float(clip_gamma).value == 0.0)):
+            raise ValueError("Temporal: clip_gamma must be 0 (the default) or a finite positive float")
+        self._clip = float(clip_gamma) if clip else None
         self._moments = bool(moments)
         self._mopts = dict(min_frames=float(min_frames), var_radius=int(var_radius))
         self._cur = None
@@ -1634,8 +1672,12 @@ class Temporal:
             p = None
         out = {key: s[key] for key in ("rgb", "var", "count", "lum2") + (("emission", "coverage") if self._light else ())}
         mode = "light" if self._light else "emit" if self._split else "plain"
-        reproject_moments_device(mode, None if p is None else self._cam, p, acc.camera, cur, out=out, **self._mopts,
-                                 **self._opts)
+        if self._clip is None:
+            reproject_moments_device(mode, None if p is None else self._cam, p, acc.camera, cur, out=out,
+                                     **self._mopts, **self._opts)
+        else:
+            reproject_clip_device(mode, None if p is None else self._cam, p, acc.camera, cur, out=out,
+                                  gamma=self._clip, **self._mopts, **self._opts)
         self._prev, self._cam = k, acc.camera
         if self._light:
             self.light = {"emission": s["emission"], "coverage": s["coverage"]}

@@ -145,6 +145,10 @@ class RtMomentsOpts(C.Structure):  # rt_moments_opts (0 = the library default; r
     _fields_ = [("min_frames", C.c_float), ("radius", C.c_int32)]
 
 
+class RtClipOpts(C.Structure):  # rt_clip_opts (0 = the library default)
+    _fields_ = [("gamma", C.c_float)]
+
+
 RT_REPROJECT_PLAIN, RT_REPROJECT_EMIT, RT_REPROJECT_LIGHT = 0, 1, 2
 
 
@@ -377,6 +381,16 @@ SIGNATURES = {
                                          C.POINTER(RtAovEmit), _I, _I, C.POINTER(RtReprojectOpts),
                                          C.POINTER(RtMomentsOpts), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
                                          C.c_void_p, _I, C.c_void_p]),
+    "rt_reproject_clip": (_I, [_I, C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
+                               C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtFrame),
+                               C.POINTER(RtAovEmit), _I, _I, C.POINTER(RtReprojectOpts),
+                               C.POINTER(RtMomentsOpts), C.POINTER(RtClipOpts), C.POINTER(RtFrame),
+                               C.POINTER(RtAovEmit), C.c_void_p]),
+    "rt_reproject_clip_device": (_I, [_I, C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
+                                      C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtFrame),
+                                      C.POINTER(RtAovEmit), _I, _I, C.POINTER(RtReprojectOpts),
+                                      C.POINTER(RtMomentsOpts), C.POINTER(RtClipOpts), C.POINTER(RtFrame),
+                                      C.POINTER(RtAovEmit), C.c_void_p, _I, C.c_void_p]),
     "rt_demo_scene": (_I, [_P, C.c_char_p, C.c_char_p, C.POINTER(RtCamera), C.POINTER(_I),
                            C.POINTER(_I)]),
     "rt_demo_scene_name": (_I, [_I, C.POINTER(C.c_char_p)]),

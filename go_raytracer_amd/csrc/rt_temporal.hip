@@ -47,6 +47,20 @@
 //                 Mom = false instances are what they were, instruction for instruction
 //                 (profiles/temporal_moments_device_code.txt).
 //
+//   k_reproject<Emit, Light, true, true> : rt_reproject_clip's three instances.  Before the blend the
+//                 history colour is clamped per channel to mean +- gamma sigma of the current frame's
+//                 gated window (variance clipping; Salvi, GDC 2016).  One window pass per pixel
+//                 (window_sums): the luminance sums of the spatial estimate and the six shifted
+//                 colour sums come from the same loads, in every lane with a surface sample, so in
+//                 a steady orbit nearly all of them.  That turns section 21's choice round: the
+//                 block stages its 64 x 4 tile plus a halo of radius in LDS (the window's colour,
+//                 depth, normal and a validity flag, from clamped addresses, all 256 lanes, one
+//                 barrier) and the window reads LDS.  Measured against the gather loop it is 0.04 to
+//                 0.09 ms faster at radius 3 and up to 2 x at radius 8.
+//                 The clamp is fminf(fmaxf()) between the tap loop and the blend, on sums formed
+//                 from selected values only.  The six other instances are what they were,
+//                 instruction for instruction (profiles/temporal_clip_device_code.txt).
+//
 // Bytes per pixel: 36 read of the current frame (28 without var and count planes), up to 4 x 36
 // gathered from the previous one (L1/L2-resident: adjacent lanes share three of four taps), 20
 // written.  Emit: 16 more of the current pixel, 4 x 16 more gathered.  Light: 16 more written.
@@ -122,9 +136,17 @@ struct MomPlanes<true> {
   int radius;  // < 0: no spatial estimate
 };
 
-// a kernel's last argument: both sets as bases, so that an empty one takes no kernel argument space
-template <bool Emit, bool Light, bool Mom>
-struct Extra : EmitPlanes<Emit, Light>, MomPlanes<Mom> {};
+// rt_reproject_clip's own argument (the resolved rt_clip_opts); no member without it
+template <bool Clip>
+struct ClipArgs {};
+template <>
+struct ClipArgs<true> {
+  float gamma;
+};
+
+// a kernel's last argument: the sets as bases, so that an empty one takes no kernel argument space
+template <bool Emit, bool Light, bool Mom, bool Clip>
+struct Extra : EmitPlanes<Emit, Light>, MomPlanes<Mom>, ClipArgs<Clip> {};
 
 __device__ __forceinline__ float lum(V3 a) { return 0.2126f * a.x + 0.7152f * a.y + 0.0722f * a.z; }
 
@@ -171,12 +193,85 @@ __device__ __forceinline__ float window_var(const TpParams& P, const Planes& cur
   return fmaxf(bm - am * am, 0.0f) * (T / (T - 1.0f));
 }
 
-template <bool Emit, bool Light, bool Mom>
+// rt_reproject_clip's window sums: window_var's luminance sums (the same statements in the same
+// order, so v_s has window_var's bits) and, per channel, the sums of the deviations d = x_t - x_p
+// from the current pixel's colour and of their squares.  An excluded pixel's d is selected to 0
+struct WindowSums {
+  float a, b, T;
+  V3 A, B;
+};
+
+// over the tile k_reproject<.., true, true> stages in LDS: eight planes of npx = tw x th floats (x,
+// depth, normal, validity without the gates), the lane at (lx, ly) of the tile.  A plane's row is
+// read by the lanes of a wave at consecutive dwords: no bank conflict
+__device__ __forceinline__ WindowSums window_sums(const TpParams& P, const float* s, int tw, int npx, int lx,
+                                                      int ly, V3 np, float dp, V3 xp, int R) {
+  const float tol_d = P.depth_tol * dp;
+  float a = 0.0f, b = 0.0f, T = 0.0f;
+  V3 A = {0.0f, 0.0f, 0.0f}, B = {0.0f, 0.0f, 0.0f};
+  for (int dy = -R; dy <= R; ++dy) {
+    for (int dx = -R; dx <= R; ++dx) {
+      const int i = (ly + dy) * tw + lx + dx;
+      const V3 st = {s[i], s[npx + i], s[2 * npx + i]}, nt = {s[4 * npx + i], s[5 * npx + i], s[6 * npx + i]};
+      const float dt = s[3 * npx + i];
+      const float nx = np.x - nt.x, ny = np.y - nt.y, nz = np.z - nt.z;
+      const bool ok = s[7 * npx + i] > 0.0f &&
+                      ((dx == 0 && dy == 0) ||
+                       (fabsf(dt - dp) <= tol_d && nx * nx + ny * ny + nz * nz <= P.normal_tol));
+      const V3 xt = {ok ? st.x : 0.0f, ok ? st.y : 0.0f, ok ? st.z : 0.0f};
+      const float yt = lum(xt);
+      a += yt;
+      b += yt * yt;
+      T += ok ? 1.0f : 0.0f;
+      const V3 d = {ok ? xt.x - xp.x : 0.0f, ok ? xt.y - xp.y : 0.0f, ok ? xt.z - xp.z : 0.0f};
+      A.x += d.x, A.y += d.y, A.z += d.z;
+      B.x += d.x * d.x, B.y += d.y * d.y, B.z += d.z * d.z;
+    }
+  }
+  return {a, b, T, A, B};
+}
+
+template <bool Emit, bool Light, bool Mom, bool Clip>
 __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Planes cur, Planes out,
-                                                   Extra<Emit, Light, Mom> ex) {
+                                                   Extra<Emit, Light, Mom, Clip> ex) {
   const EmitPlanes<Emit, Light>& em = ex;
   const MomPlanes<Mom>& mo = ex;
+  [[maybe_unused]] const float* tile = nullptr;
+  [[maybe_unused]] int tile_w = 0, tile_n = 0;
+  if constexpr (Clip) {
+    // stage the 64 x 4 tile plus a halo of radius: the window's colour, depth, normal and validity
+    // without the gates, from clamped addresses; every lane of the block takes part, one barrier
+    extern __shared__ float s_tile[];
+    const int R = mo.radius, tw = kTW + 2 * R, npx = tw * (kTH + 2 * R);
+    const int ty0 = blockIdx.x / P.tiles_x, tx0 = blockIdx.x - ty0 * P.tiles_x;
+    for (int i = threadIdx.x; i < npx; i += 256) {
+      const int ly = i / tw, lx = i - ly * tw;
+      const int gx = tx0 * kTW + lx - R, gy = ty0 * kTH + ly - R;
+      const int cx = min(max(gx, 0), P.w - 1), cy = min(max(gy, 0), P.h - 1);
+      const size_t ti = (size_t)cy * P.w + cx;
+      const V3 ct = load3(cur.rgb, ti), nt = load3(cur.normal, ti);
+      const float vt = cur.var ? cur.var[ti] : 0.0f;
+      const float cntt = cur.count ? cur.count[ti] : P.cur_count;
+      bool ok = cx == gx && cy == gy && finite3(ct) && isfinite(vt) && isfinite(cntt) && cntt > 0.0f;
+      V3 xt = {ok ? ct.x : 0.0f, ok ? ct.y : 0.0f, ok ? ct.z : 0.0f};
+      if constexpr (Emit) {
+        const V3 et = load3(em.cur_emission, ti);
+        const float covt = em.cur_coverage[ti];
+        ok = ok && finite3(et) && covt >= 0.0f && covt < 1.0f;
+        const float kt = ok ? 1.0f - covt : 1.0f;
+        xt = {((ok ? ct.x : 0.0f) - (ok ? et.x : 0.0f)) / kt, ((ok ? ct.y : 0.0f) - (ok ? et.y : 0.0f)) / kt,
+              ((ok ? ct.z : 0.0f) - (ok ? et.z : 0.0f)) / kt};
+      }
+      s_tile[i] = xt.x, s_tile[npx + i] = xt.y, s_tile[2 * npx + i] = xt.z;
+      s_tile[3 * npx + i] = cur.depth[ti];
+      s_tile[4 * npx + i] = nt.x, s_tile[5 * npx + i] = nt.y, s_tile[6 * npx + i] = nt.z;
+      s_tile[7 * npx + i] = ok ? 1.0f : 0.0f;
+    }
+    __syncthreads();
+    tile = s_tile, tile_w = tw, tile_n = npx;
+  }
   static_assert(Emit || !Light, "the light history is a history of the emission split's planes");
+  static_assert(Mom || !Clip, "the clip entries are the moments entries with one more step");
   const int tile_y = blockIdx.x / P.tiles_x, tile_x = blockIdx.x - tile_y * P.tiles_x;
   const int x = tile_x * kTW + (threadIdx.x & (kTW - 1)), y = tile_y * kTH + (threadIdx.x >> 6);
   if (x >= P.w || y >= P.h) return;
@@ -315,18 +410,53 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
     const float K = hs && surf ? n / wc : 1.0f;  // the history length in frames
     const bool use_t = hs && surf && K >= mo.min_frames;
     float vs = 0.0f;
-    if (mo.radius >= 0 && surf && !use_t) vs = window_var<Emit, Light>(P, cur, em, x, y, np, dp, mo.radius) / K;
+    [[maybe_unused]] V3 lo = {-INFINITY, -INFINITY, -INFINITY}, hi = {INFINITY, INFINITY, INFINITY};  // Clip: the box
+    if constexpr (Clip) {
+      // one window pass in every lane with a surface sample (radius >= 0: resolve_moments): v_s where
+      // the pixel takes it, and the box mean +- gamma sigma, which overrules the history colour of a
+      // pixel with surface history and at least two window pixels.  Any other pixel's box is the
+      // whole line, which leaves xh's bits alone
+      const ClipArgs<true>& cl = ex;
+      if (surf) {
+        const WindowSums ws = window_sums(P, tile, tile_w, tile_n, (int)(threadIdx.x & (kTW - 1)) + mo.radius,
+                                          (int)(threadIdx.x >> 6) + mo.radius, np, dp, z, mo.radius);
+        if (ws.T >= 2.0f) {
+          const float am = ws.a / ws.T, bm = ws.b / ws.T;
+          if (!use_t) vs = fmaxf(bm - am * am, 0.0f) * (ws.T / (ws.T - 1.0f)) / K;
+          if (hs) {
+            const V3 mA = {ws.A.x / ws.T, ws.A.y / ws.T, ws.A.z / ws.T};
+            const V3 sd = {cl.gamma * sqrtf(fmaxf(ws.B.x / ws.T - mA.x * mA.x, 0.0f)),
+                           cl.gamma * sqrtf(fmaxf(ws.B.y / ws.T - mA.y * mA.y, 0.0f)),
+                           cl.gamma * sqrtf(fmaxf(ws.B.z / ws.T - mA.z * mA.z, 0.0f))};
+            const V3 m = {z.x + mA.x, z.y + mA.y, z.z + mA.z};
+            lo = {m.x - sd.x, m.y - sd.y, m.z - sd.z};
+            hi = {m.x + sd.x, m.y + sd.y, m.z + sd.z};
+          }
+        }
+      }
+    } else {
+      if (mo.radius >= 0 && surf && !use_t) vs = window_var<Emit, Light>(P, cur, em, x, y, np, dp, mo.radius) / K;
+    }
     V3 o = c, oe = e;
     float ov = v, on = nc, oc = covc, oq = 0.0f;
     if (blend) {
       const float in = 1.0f / n, vh = sv * (inv * inv);
-      o.x = fmaf(wc, z.x, nh * (sr * inv)) * in;
-      o.y = fmaf(wc, z.y, nh * (sg * inv)) * in;
-      o.z = fmaf(wc, z.z, nh * (sb * inv)) * in;
+      if constexpr (Clip) {  // the history colour, clamped to the box; the blend is the one below
+        o.x = fmaf(wc, z.x, nh * fminf(fmaxf(sr * inv, lo.x), hi.x)) * in;
+        o.y = fmaf(wc, z.y, nh * fminf(fmaxf(sg * inv, lo.y), hi.y)) * in;
+        o.z = fmaf(wc, z.z, nh * fminf(fmaxf(sb * inv, lo.z), hi.z)) * in;
+      } else {
+        o.x = fmaf(wc, z.x, nh * (sr * inv)) * in;
+        o.y = fmaf(wc, z.y, nh * (sg * inv)) * in;
+        o.z = fmaf(wc, z.z, nh * (sb * inv)) * in;
+      }
       ov = fmaf(wc * wc, vz, nh * nh * vh) * (in * in);
       oq = (nh * (sq * inv) + wc * qc) * in;  // q before the blend, then the colour's weights
       if (mo.radius >= 0 && surf) {
-        const float yo = lum(o);
+        float yo = lum(o);
+        // Clip: Y with its contraction written out as the moments instances have it (the 0.7152 g
+        // product rounded, the two others fused), so that an unclamped pixel keeps their bits
+        if constexpr (Clip) yo = fmaf(0.0722f, o.z, fmaf(0.2126f, o.x, 0.7152f * o.y));
         ov = use_t ? fmaxf(oq - yo * yo, 0.0f) / (K - 1.0f) : vs;
       }
       float ko = kc;
@@ -515,7 +645,10 @@ struct Moments {
   const float* prev_lum2;
   const rt_moments_opts* mopts;
   float* out_lum2;
+  const rt_clip_opts* copts = nullptr;  // rt_reproject_clip's; NULL: no clipping, the moments entries' kernels
 };
+
+constexpr float kClipGamma = 0.75f;  // rt_clip_opts' default gamma (DESIGN.md section 22's sweep)
 
 // the moments entries' own checks, then the mode's (resolve).  prev == NULL is no history at all:
 // the three prev arguments come back as the current frame's, which the kernel reads (clamped
@@ -523,7 +656,8 @@ struct Moments {
 int resolve_moments(const char* who, bool emit, bool light, const rt_camera** cam_prev, const rt_frame** prev,
                     const rt_aov_emit** prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
                     const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts, const Moments& m,
-                    const rt_frame* out, const rt_aov_emit* out_emit, TpParams* P, MomPlanes<true>* mo) {
+                    const rt_frame* out, const rt_aov_emit* out_emit, TpParams* P, MomPlanes<true>* mo,
+                    ClipArgs<true>* cl) {
   if (!m.out_lum2) return set_error(RT_ERR_INVALID, "%s: null out_lum2", who);
   const bool no_prev = !*prev;
   if (!no_prev && !m.prev_lum2) return set_error(RT_ERR_INVALID, "%s: prev without prev_lum2", who);
@@ -532,6 +666,12 @@ int resolve_moments(const char* who, bool emit, bool light, const rt_camera** ca
     return set_error(RT_ERR_INVALID, "%s: radius %d (-1: no spatial estimate; at most 8)", who, mop.radius);
   if (!(mop.min_frames >= 0.0f) || !isfinite(mop.min_frames) || (mop.min_frames > 0.0f && mop.min_frames < 2.0f))
     return set_error(RT_ERR_INVALID, "%s: min_frames must be 0 (the default) or a finite number >= 2", who);
+  if (m.copts) {  // the clip entries' own: the box is the window's
+    if (mop.radius == -1)
+      return set_error(RT_ERR_INVALID, "%s: clipping needs the window (radius -1 has none)", who);
+    if (!(m.copts->gamma >= 0.0f) || !isfinite(m.copts->gamma))
+      return set_error(RT_ERR_INVALID, "%s: gamma must be 0 (the default) or a finite positive number", who);
+  }
   const float* in[17] = {};  // every input plane
   int ni = 0;
   if (!no_prev) {
@@ -567,37 +707,44 @@ int resolve_moments(const char* who, bool emit, bool light, const rt_camera** ca
   if (rc) return rc;
   *mo = {no_prev ? nullptr : m.prev_lum2, m.out_lum2, mop.min_frames > 0.0f ? mop.min_frames : 4.0f,
          mop.radius == 0 ? 3 : mop.radius};
+  if (m.copts) cl->gamma = m.copts->gamma > 0.0f ? m.copts->gamma : kClipGamma;
   return RT_OK;
 }
 
-// one instance's launch; mom: rt_reproject_moments' arguments, NULL for the older entries' kernels
+// one instance's launch; mom: rt_reproject_moments' arguments, NULL for the older entries' kernels;
+// clip: rt_reproject_clip's (with mom), NULL for every other entry's
 template <bool Emit, bool Light>
 void launch_as(unsigned tiles, hipStream_t s, const TpParams& P, const Planes& prev, const Planes& cur,
-               const Planes& out, const EmitPlanes<Emit, Light>& em, const MomPlanes<true>* mom) {
-  if (mom)
-    hipLaunchKernelGGL((k_reproject<Emit, Light, true>), dim3(tiles), dim3(256), 0, s, P, prev, cur, out,
-                       Extra<Emit, Light, true>{em, *mom});
+               const Planes& out, const EmitPlanes<Emit, Light>& em, const MomPlanes<true>* mom,
+               const ClipArgs<true>* clip) {
+  if (mom && clip) {  // the tile and its halo: 8 floats a pixel, 22 KB at radius 3, 51 KB at radius 8
+    const int tw = kTW + 2 * mom->radius, th = kTH + 2 * mom->radius;
+    hipLaunchKernelGGL((k_reproject<Emit, Light, true, true>), dim3(tiles), dim3(256), (size_t)tw * th * 32, s, P,
+                       prev, cur, out, Extra<Emit, Light, true, true>{em, *mom, *clip});
+  } else if (mom)
+    hipLaunchKernelGGL((k_reproject<Emit, Light, true, false>), dim3(tiles), dim3(256), 0, s, P, prev, cur, out,
+                       Extra<Emit, Light, true, false>{em, *mom, {}});
   else
-    hipLaunchKernelGGL((k_reproject<Emit, Light, false>), dim3(tiles), dim3(256), 0, s, P, prev, cur, out,
-                       Extra<Emit, Light, false>{em, {}});
+    hipLaunchKernelGGL((k_reproject<Emit, Light, false, false>), dim3(tiles), dim3(256), 0, s, P, prev, cur, out,
+                       Extra<Emit, Light, false, false>{em, {}, {}});
 }
 
 // emit: the frames' rt_aov_emit (both NULL for rt_reproject's kernel, both checked by resolve);
 // out_emit: the new history's light planes (rt_reproject_light's kernel), NULL for the others
 int launch(const TpParams& P, const Planes& prev, const Planes& cur, const Planes& out,
            const rt_aov_emit* prev_emit, const rt_aov_emit* cur_emit, const rt_aov_emit* out_emit, hipStream_t s,
-           const MomPlanes<true>* mom = nullptr) {
+           const MomPlanes<true>* mom = nullptr, const ClipArgs<true>* clip = nullptr) {
   const unsigned tiles = (unsigned)((int64_t)P.tiles_x * ((P.h + kTH - 1) / kTH));  // < 2^31 / 3: w h is
   if (out_emit) {
     const EmitPlanes<true, true> em = {prev_emit->emission, prev_emit->coverage, cur_emit->emission,
                                        cur_emit->coverage,  out_emit->emission,  out_emit->coverage};
-    launch_as(tiles, s, P, prev, cur, out, em, mom);
+    launch_as(tiles, s, P, prev, cur, out, em, mom, clip);
   } else if (prev_emit) {
     const EmitPlanes<true, false> em = {prev_emit->emission, prev_emit->coverage, cur_emit->emission,
                                         cur_emit->coverage};
-    launch_as(tiles, s, P, prev, cur, out, em, mom);
+    launch_as(tiles, s, P, prev, cur, out, em, mom, clip);
   } else {
-    launch_as(tiles, s, P, prev, cur, out, EmitPlanes<false, false>{}, mom);
+    launch_as(tiles, s, P, prev, cur, out, EmitPlanes<false, false>{}, mom, clip);
   }
   HIP_OK(hipGetLastError());
   return RT_OK;
@@ -611,8 +758,9 @@ int reproject_device(const char* who, bool emit, bool light, const rt_camera* ca
                      const Moments* m = nullptr) {
   TpParams P;
   MomPlanes<true> mo;
+  ClipArgs<true> cl;
   int rc = m ? resolve_moments(who, emit, light, &cam_prev, &prev, &prev_emit, cam_cur, cur, cur_emit, w, h, opts,
-                               *m, out, out_emit, &P, &mo)
+                               *m, out, out_emit, &P, &mo, &cl)
              : resolve(who, emit, light, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out,
                        out_emit, &P);
   if (rc) return rc;
@@ -620,7 +768,8 @@ int reproject_device(const char* who, bool emit, bool light, const rt_camera* ca
   DeviceGuard dg;
   HIP_OK(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  rc = launch(P, planes_of(prev), planes_of(cur), planes_of(out), prev_emit, cur_emit, out_emit, s, m ? &mo : nullptr);
+  rc = launch(P, planes_of(prev), planes_of(cur), planes_of(out), prev_emit, cur_emit, out_emit, s, m ? &mo : nullptr,
+              m && m->copts ? &cl : nullptr);
   HIP_OK(hipStreamSynchronize(s));
   return rc;
 }
@@ -633,9 +782,10 @@ int reproject_host(const char* who, bool emit, bool light, const rt_camera* cam_
                    const rt_frame* out, const rt_aov_emit* out_emit, const Moments* m = nullptr) {
   TpParams P;
   MomPlanes<true> mo;
+  ClipArgs<true> cl;
   const bool no_prev = m && !prev;
   int rc = m ? resolve_moments(who, emit, light, &cam_prev, &prev, &prev_emit, cam_cur, cur, cur_emit, w, h, opts,
-                               *m, out, out_emit, &P, &mo)
+                               *m, out, out_emit, &P, &mo, &cl)
              : resolve(who, emit, light, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out,
                        out_emit, &P);
   if (rc) return rc;
@@ -690,7 +840,7 @@ int reproject_host(const char* who, bool emit, bool light, const rt_camera* cam_
     mo.out_lum2 = cbase + 5 * n;
   }
   rc = launch(P, d[0], d[1], o, emit ? &de[0] : nullptr, emit ? &de[1] : nullptr, light ? &oe : nullptr, s,
-              m ? &mo : nullptr);
+              m ? &mo : nullptr, m && m->copts ? &cl : nullptr);
   if (!rc && m && hipMemcpyAsync(m->out_lum2, mo.out_lum2, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
     rc = set_error(RT_ERR_DEVICE, "%s: copy to host failed", who);
   if (!rc && ((o.rgb && hipMemcpyAsync(out->rgb, o.rgb, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess) ||
@@ -779,6 +929,34 @@ int rt_reproject_moments(int mode, const rt_camera* cam_prev, const rt_frame* pr
   if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
   const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
   const Moments m = {prev_lum2, mopts, out_lum2};
+  return reproject_host(who, emit, light, cam_prev, prev, emit ? prev_emit : nullptr, cam_cur, cur,
+                        emit ? cur_emit : nullptr, w, h, opts, out, light ? out_emit : nullptr, &m);
+}
+
+int rt_reproject_clip_device(int mode, const rt_camera* cam_prev, const rt_frame* prev_dev,
+                             const rt_aov_emit* prev_emit_dev, const float* prev_lum2_dev, const rt_camera* cam_cur,
+                             const rt_frame* cur_dev, const rt_aov_emit* cur_emit_dev, int w, int h,
+                             const rt_reproject_opts* opts, const rt_moments_opts* mopts, const rt_clip_opts* copts,
+                             const rt_frame* out_dev, const rt_aov_emit* out_emit_dev, float* out_lum2_dev,
+                             int device, void* stream) {
+  const char* who = "rt_reproject_clip_device";
+  if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
+  const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
+  const Moments m = {prev_lum2_dev, mopts, out_lum2_dev, copts};
+  return reproject_device(who, emit, light, cam_prev, prev_dev, emit ? prev_emit_dev : nullptr, cam_cur, cur_dev,
+                          emit ? cur_emit_dev : nullptr, w, h, opts, out_dev, light ? out_emit_dev : nullptr, device,
+                          stream, &m);
+}
+
+int rt_reproject_clip(int mode, const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
+                      const float* prev_lum2, const rt_camera* cam_cur, const rt_frame* cur,
+                      const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
+                      const rt_moments_opts* mopts, const rt_clip_opts* copts, const rt_frame* out,
+                      const rt_aov_emit* out_emit, float* out_lum2) {
+  const char* who = "rt_reproject_clip";
+  if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
+  const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
+  const Moments m = {prev_lum2, mopts, out_lum2, copts};
   return reproject_host(who, emit, light, cam_prev, prev, emit ? prev_emit : nullptr, cam_cur, cur,
                         emit ? cur_emit : nullptr, w, h, opts, out, light ? out_emit : nullptr, &m);
 }

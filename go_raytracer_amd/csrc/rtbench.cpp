@@ -13,7 +13,7 @@
 //                   rt_accum_add or rt_accum_select + rt_accum_add_active, rt_accum_info_get,
 //                   rt_accum_resolve, rt_accum_adapt_info, rt_accum_counts; rt_progress on a thread
 //   feature_planes  rt_render_aov[_emit|_media] or rt_accum_resolve_aov[_media]
-//   temporal_step   rt_reproject[_emit | _light | _moments] (the host entries: this client links no HIP runtime)
+//   temporal_step   rt_reproject[_emit | _light | _moments | _clip] (the host entries: this client links no HIP runtime)
 //   filter          rt_denoise[_var][_emit]
 //   write_aovs      rt_format_ppm per plane
 //   finish_frame    rt_format_ppm, the statistics line (-cpuprofile has no pprof to drive on the
@@ -55,7 +55,8 @@ struct Args {
   unsigned long long seed = 1, tree_seed = 1;
   bool progress = false, stats = false, denoise = false, denoise_var = false, split_emitters = false;
   bool accum_features = false, temporal = false, temporal_emit = false, aov_media = false, aov_specular = false;
-  bool temporal_light = false, temporal_moments = false;
+  bool temporal_light = false, temporal_moments = false, temporal_clip = false;
+  double clip_gamma = 0.0;
   long long frames = 0, spec_bounces = 0, moments_radius = 0;
   double moments_frames = 0.0;
   double spec_fuzz = 0.0;
@@ -79,6 +80,8 @@ std::vector<Flag> flags(Args& a) {
        Flag::STR, &a.aov, ""},
       {"assets", "directory holding earthmap.jpg / dragon.obj (default: <exe dir>/../assets)",
        Flag::STR, &a.assets, ""},
+      {"clip-gamma", "with -temporal-clip: the box is mean +- G sigma per channel (0 = the library's default; finite, >= 0)",
+       Flag::F64, &a.clip_gamma, "0"},
       {"counts", "with -adaptive: write the passes per pixel as a grey image (count / largest count)", Flag::STR,
        &a.counts, ""},
       {"cpuprofile", "Write cpu profile to file (here: render statistics as JSON)", Flag::STR,
@@ -115,6 +118,8 @@ std::vector<Flag> flags(Args& a) {
       {"stats", "print render statistics (JSON) on stderr", Flag::BOOL, &a.stats, ""},
       {"temporal", "with -accum-features and -passes / -until / -adaptive: blend each frame with the reprojected history of the frames before it (rt_reproject)",
        Flag::BOOL, &a.temporal, ""},
+      {"temporal-clip", "with -temporal-moments: clamp the reprojected colour to the current frame's neighbourhood before the blend (rt_reproject_clip, see -clip-gamma), which overrules a stale reflection on metal or glass",
+       Flag::BOOL, &a.temporal_clip, ""},
       {"temporal-emit", "as -temporal, with directly seen lights kept out of the history (rt_reproject_emit); needs -split-emitters too",
        Flag::BOOL, &a.temporal_emit, ""},
       {"temporal-light", "as -temporal-emit, with emission and coverage carried as history planes too and the blended planes handed to the split filter (rt_reproject_light); instead of -temporal / -temporal-emit",
@@ -249,6 +254,7 @@ struct Job {
   bool temporal = false, temporal_emit = false, want_var = false;
   bool temporal_light = false;  // the temporal stage through rt_reproject_light
   bool temporal_moments = false;  // ... through rt_reproject_moments in the stage's mode
+  bool temporal_clip = false;     // ... through rt_reproject_clip instead
   bool counts = false, aov = false, print_stats = false;
   bool numbered = false;  // -frames: frame k goes to the -o name with _00k before the extension
   int n_frames = 1;
@@ -270,6 +276,13 @@ int make_job(const Args& a, const char* prog, Job& j) {
       {a.moments_radius < -1 || a.moments_radius > 8 || !(a.moments_frames >= 0.0) || !(a.moments_frames <= 3.0e38) ||
            (a.moments_frames > 0.0 && a.moments_frames < 2.0),
        "invalid value for flag -moments-radius (-1..8) / -moments-frames (0, or finite and >= 2)"},
+      // -temporal-clip modifies -temporal-moments, and needs its window
+      {a.temporal_clip && !a.temporal_moments, "-temporal-clip needs -temporal-moments"},
+      {a.clip_gamma != 0.0 && !a.temporal_clip, "-clip-gamma needs -temporal-clip"},
+      {a.temporal_clip && a.moments_radius == -1, "-temporal-clip needs the window: -moments-radius -1 has none"},
+      // (a positive G that rounds to 0 as a float would silently select the default)
+      {!(a.clip_gamma >= 0.0) || !(a.clip_gamma <= 3.0e38) || (a.clip_gamma > 0.0 && (float)a.clip_gamma == 0.0f),
+       "invalid value for flag -clip-gamma (0, or a finite positive float)"},
       // ... unless the history brings one (-temporal-moments)
       {a.denoise_var && !(a.passes >= 2 || ((a.until > 0.0 || a.adaptive_set) && a.passes == 0) ||
                           (a.temporal_moments && a.passes == 1)),
@@ -306,6 +319,7 @@ int make_job(const Args& a, const char* prog, Job& j) {
   j.temporal_emit = a.temporal_emit;
   j.temporal_light = a.temporal_light;
   j.temporal_moments = a.temporal_moments;
+  j.temporal_clip = a.temporal_clip;
   j.temporal = a.temporal || a.temporal_emit || a.temporal_light;  // the same stage, through rt_reproject_emit / _light
   j.aov = !a.aov.empty();
   if (filtered || j.aov || j.temporal) j.source = a.accum_features ? Features::ACCUM : Features::PASS;
@@ -430,7 +444,7 @@ struct Stats {
   const rt_accum_info* acc;    // -passes / -until / -adaptive, else null
   const rt_adapt_info* adapt;  // -adaptive, else null
   bool denoise_var, split_emitters, accum_features, temporal, temporal_emit, temporal_light, aov_media, aov_specular;
-  bool temporal_moments;
+  bool temporal_moments, temporal_clip;
   int frame;  // -frames, else -1
 };
 
@@ -472,6 +486,7 @@ std::string stats_json(const Stats& s) {
   if (s.temporal_emit) b += "\"temporal_emit\": 1, ";
   if (s.temporal_light) b += "\"temporal_light\": 1, ";
   if (s.temporal_moments) b += "\"temporal_moments\": 1, ";
+  if (s.temporal_clip) b += "\"temporal_clip\": 1, ";
   if (s.aov_media) b += "\"aov_media\": 1, ";
   if (s.aov_specular) b += "\"aov_specular\": 1, ";
   appendf(b, "\"wall_s\": %.3f}", s.wall_s);
@@ -671,11 +686,18 @@ int temporal_step(const Job& j, Ctx& c) {
     const rt_moments_opts mo = {(float)j.a.moments_frames, (int32_t)j.a.moments_radius};
     const int mode = j.temporal_light ? RT_REPROJECT_LIGHT : j.temporal_emit ? RT_REPROJECT_EMIT : RT_REPROJECT_PLAIN;
     const bool hh = c.have_history;
+    const rt_clip_opts co = {(float)j.a.clip_gamma};
     Call s;
-    s.ok("rt_reproject_moments",
-         rt_reproject_moments(mode, hh ? &c.h_cam : nullptr, hh ? &prev : nullptr, hh ? &prev_emit : nullptr,
-                              hh ? c.h_lum2.data() : nullptr, &c.cam, &cur, &cur_emit, w, h, nullptr, &mo, &res,
-                              &res_emit, c.m_lum2.data()));
+    if (j.temporal_clip)
+      s.ok("rt_reproject_clip",
+           rt_reproject_clip(mode, hh ? &c.h_cam : nullptr, hh ? &prev : nullptr, hh ? &prev_emit : nullptr,
+                             hh ? c.h_lum2.data() : nullptr, &c.cam, &cur, &cur_emit, w, h, nullptr, &mo, &co, &res,
+                             &res_emit, c.m_lum2.data()));
+    else
+      s.ok("rt_reproject_moments",
+           rt_reproject_moments(mode, hh ? &c.h_cam : nullptr, hh ? &prev : nullptr, hh ? &prev_emit : nullptr,
+                                hh ? c.h_lum2.data() : nullptr, &c.cam, &cur, &cur_emit, w, h, nullptr, &mo, &res,
+                                &res_emit, c.m_lum2.data()));
     if (s.rc != RT_OK) return fail(s.what, s.rc);
     c.rgb = c.m_rgb, c.var = c.m_var, c.count = c.m_count, c.h_lum2 = c.m_lum2;
   } else if (c.have_history) {
@@ -763,7 +785,7 @@ int finish_frame(const Job& j, Ctx& c) {
   s.acc = j.accumulate ? &c.ai : nullptr;
   s.adapt = j.adaptive ? &c.adi : nullptr;
   s.denoise_var = j.filter == Filter::VAR, s.split_emitters = j.emit, s.accum_features = j.accum_features;
-  s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.temporal_light = j.temporal_light, s.temporal_moments = j.temporal_moments, s.aov_media = j.media, s.aov_specular = j.specular;
+  s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.temporal_light = j.temporal_light, s.temporal_moments = j.temporal_moments, s.temporal_clip = j.temporal_clip, s.aov_media = j.media, s.aov_specular = j.specular;
   s.frame = j.numbered ? c.frame : -1;
   const std::string js = stats_json(s);
   if (j.print_stats) fprintf(stderr, "%s\n", js.c_str());

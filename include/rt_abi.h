@@ -1177,6 +1177,61 @@ int rt_reproject_moments_device(int mode, const rt_camera* cam_prev, const rt_fr
                                 const rt_frame* out_dev, const rt_aov_emit* out_emit_dev,
                                 float* out_lum2_dev, int device, void* stream);
 
+/* rt_reproject_moments with the history colour rectified before the blend: variance clipping
+ * (Salvi, "An excursion in temporal supersampling", GDC 2016; DESIGN.md "Clamping the history").
+ * The history is accepted on the first hit's depth and normal alone; on a mirror or behind glass
+ * these agree from frame to frame while the reflection moves under them.  Here the reprojected
+ * colour is clamped per channel to mean +- gamma sigma of the current frame's gated neighbourhood,
+ * so a history the current frame contradicts is overruled.  Added without an ABI version change:
+ * detect by the symbols.  copts follows mopts; copts == NULL is OFF: rt_reproject_moments' result bit
+ * for bit in every plane.  With copts given, everything not named here is rt_reproject_moments'
+ * definition in the selected mode (x, w_c, Y as there).
+ *   window: the spatial estimate's, with the same mopts.radius: the pixels t of the current frame
+ *     with |t - p| <= radius in both coordinates that are inside the image, valid by the mode's
+ *     current-pixel rule with kappa_t < 1 where the mode has a coverage, and within depth_tol and
+ *     normal_tol of p (p itself always counts).  T is their number.
+ *   shifted sums, per channel j: d_t,j = x_t,j - x_p,j, x_p the current pixel's colour;
+ *     A_j = sum d_t,j, B_j = sum d_t,j^2, in fp32 row by row in ascending order; an excluded
+ *     pixel's d is selected to 0 before any arithmetic.
+ *   box: m_j = x_p,j + A_j / T,   s_j = sqrt(max(B_j / T - (A_j / T)^2, 0)).  The deviations are
+ *     taken from x_p so that a noise-free neighbourhood gives s = 0 exactly, and so that the
+ *     subtraction cancels against the spread and not against the magnitude.
+ *   clamp, for a pixel with surface history, w_c > 0 and T >= 2:
+ *     x_h'_j = min(max(x_h,j, m_j - gamma s_j), m_j + gamma s_j);  x_h' stands in for the mode's
+ *     history colour c_h in the blend and so in y_out = Y(x_blend).  Nothing else changes: n_h,
+ *     v_h, q_h, the cap, LIGHT's emission and coverage history are rt_reproject_moments'.
+ *     q_h is NOT rectified: a clamped pixel's y_out moves away from the mean its moments were
+ *     collected around, so its v_t = max(q_out - y_out^2, 0) / (K - 1) is no longer the variance
+ *     of its mean.  Where the clamp lowers the history's luminance (a bright stale history over a
+ *     darker frame) y_out^2 falls and v_t can only grow.  That is intended: a pixel whose history
+ *     was overruled is filtered harder.  Where the clamp raises it (a dark stale history over a
+ *     brighter frame) v_t shrinks, at the least to 0, and the filter leaves the pixel more alone.
+ *   not clamped, rt_reproject_moments' bits: pixels without surface history, pixels with T < 2,
+ *     LIGHT's pixels with w_c = 0, every pass-through set.
+ * The previous frame's values reach the clamp as the taps' sums, formed from selected values only:
+ * a NaN of the previous frame never meets arithmetic here either.
+ * Argument checks, before any device is touched: rt_reproject_moments' own; RT_ERR_INVALID for
+ * copts given with mopts.radius resolving to -1 (there is no window); gamma negative or not finite.
+ * Host and device forms as rt_reproject_moments'; rt_reproject_clip stages what it stages; the
+ * device entry allocates nothing.  Two calls give identical bits. */
+typedef struct {
+  float   gamma;            /* 0 -> 0.75 (DESIGN.md section 22's sweep): the box is mean +- gamma * sigma per channel */
+} rt_clip_opts;
+int rt_reproject_clip(int mode, const rt_camera* cam_prev, const rt_frame* prev,
+                      const rt_aov_emit* prev_emit, const float* prev_lum2,
+                      const rt_camera* cam_cur, const rt_frame* cur, const rt_aov_emit* cur_emit,
+                      int w, int h, const rt_reproject_opts* opts, const rt_moments_opts* mopts,
+                      const rt_clip_opts* copts, const rt_frame* out, const rt_aov_emit* out_emit,
+                      float* out_lum2);
+int rt_reproject_clip_device(int mode, const rt_camera* cam_prev, const rt_frame* prev_dev,
+                             const rt_aov_emit* prev_emit_dev, const float* prev_lum2_dev,
+                             const rt_camera* cam_cur, const rt_frame* cur_dev,
+                             const rt_aov_emit* cur_emit_dev, int w, int h,
+                             const rt_reproject_opts* opts, const rt_moments_opts* mopts,
+                             const rt_clip_opts* copts, const rt_frame* out_dev,
+                             const rt_aov_emit* out_emit_dev, float* out_lum2_dev, int device,
+                             void* stream);
+
 /* Demo scenes mirroring main.go (by name or the main.go -S number).
  * names: book1, book2, book3, simple_light, quads, cornell, cornell_smoke, model
  * The camera receives the scene's settings; override fields afterwards. */

@@ -28,7 +28,17 @@ costs).  quality_one_pass is the same orbit with ONE pass x 4 spp per frame thro
 Temporal(split_emitters=True) and Temporal(split_emitters=True, moments=True), each followed by
 the guided filter.
 
-Prints one JSON object; -o FILE also writes it.
+clip: rt_reproject_clip_device joins the time alternation in each mode with the
+moments' worst-case frames (clip_*), and both entries once more with a previous count of 16, a
+steady orbit's (K = 9 >= min_frames: the moments entry skips the window wherever it finds history,
+the clip entry runs it in every lane: *_steady).  quality_clip holds, per scene and orbit step, the
+one-pass orbit through Temporal(split_emitters=True, moments=True) without and with clip=True at
+every gamma of the sweep, with and without the guided filter: `quads` (rows: all pixels, the pixels
+whose first hit is the metal quad, the rest) at 1 and 3 degrees per frame, and `cornell` (§21's
+rows) at 1 degree.  gamma_sweep sums, per gamma, the all-pixel MSE after the filter over the two
+orbits (quads at --sweep-degrees, cornell at 1 degree); the lowest sum names the default.
+
+Prints one JSON object; -o FILE also writes it.  --only time|quality|clip runs one part.
 """
 import argparse
 import json
@@ -109,6 +119,12 @@ def bench_time(width, rounds, warm):
     def moments(mode, **kw):
         f = mplain if mode == "plain" else mfull
         return lambda: rt.reproject_moments_device(mode, cams[0], f[0], cams[1], f[1], out=out_m[mode], **kw)
+    steady = [dict(f[0], count=torch.full((width, width), 16.0, device=dev)) for f in (mplain, mfull)]
+
+    def clip(mode, prev_steady=False, entry=rt.reproject_clip_device, **kw):
+        f = mplain if mode == "plain" else mfull
+        p = steady[mode != "plain"] if prev_steady else f[0]
+        return lambda: entry(mode, cams[0], p, cams[1], f[1], out=out_m[mode], **kw)
     calls = {
         "reproject": lambda: rt.reproject_device(cams[0], plain[0], cams[1], dict(plain[1], count=2.0), out=out),
         "reproject_emit": lambda: rt.reproject_emit_device(cams[0], prev, cams[1], dict(cur, count=2.0), out=out_e),
@@ -119,6 +135,9 @@ def bench_time(width, rounds, warm):
     for m in ("plain", "emit", "light"):
         calls[f"moments_{m}"] = moments(m)
         calls[f"moments_{m}_no_window"] = moments(m, var_radius=-1)
+        calls[f"clip_{m}"] = clip(m)
+        calls[f"moments_{m}_steady"] = clip(m, True, rt.reproject_moments_device)
+        calls[f"clip_{m}_steady"] = clip(m, True)
     ms = {k: [] for k in calls}
     for r in range(warm + rounds):
         for k, fn in calls.items():
@@ -222,6 +241,49 @@ def bench_quality_one_pass(width, frames, degrees, ref_spp):
                         for c, x in cols.items()} for s, m in sets.items()}}
 
 
+GAMMAS = (0.25, 0.5, 0.75, 1.0, 1.5, 2.0, 3.0)
+
+
+def bench_quality_clip(scene, width, frames, degrees, ref_spp, gammas=GAMMAS):
+    t, cam, w, l = rt.demo_scene(scene)
+    cam.Width, cam.SamplesPerPixel = width, 4
+    kw = dict(split_emitters=True, moments=True)
+    paths = {"history": rt.Temporal(**kw)}
+    paths.update({f"clip_gamma_{g:g}": rt.Temporal(clip=True, clip_gamma=g, **kw) for g in gammas})
+    with rt.Scene(t, w, l) as sc:
+        for k in range(frames):
+            camk = orbit(cam, degrees * k)
+            with sc.accumulator(camk, max_passes=1, features="emit") as acc:
+                acc.add(10 * k + 1)
+                res = {name: tp.push(acc) for name, tp in paths.items()}
+                if k == frames - 1:
+                    mean, _ = acc.resolve()
+                    aov = acc.resolve_aov_device()
+                    cover = aov["coverage"].cpu().numpy()
+                    cols = {"frame": mean}
+                    for name, r in res.items():
+                        cols[name] = r[0].cpu().numpy()
+                        cols[name + "_filtered"] = rt.denoise_var_device(r[0], r[1], aov, split_emitters=True).cpu().numpy()
+                    cnt = res["history"][2].cpu().numpy()
+                    var = {name: float(r[1].mean().item()) for name, r in res.items()}
+        material = sc.render_aov(camk)["material"]
+        camk.SamplesPerPixel = ref_spp
+        ref, _ = sc.render(camk, seed=977)
+    fin = np.isfinite(mean).all(-1) & np.isfinite(ref).all(-1)
+    metal = material == rt._lib.RT_MAT_METAL
+    near = cover > 0
+    for _ in range(2):
+        pad = np.pad(near, 1)
+        near = np.logical_or.reduce([pad[dy:dy + width, dx:dx + width] for dy in range(3) for dx in range(3)])
+    sets = {"all": fin, "metal": fin & metal, "rest": fin & ~metal, "rim": fin & (cover > 0) & (cover < 1),
+            "with_history": fin & (cnt > 1.0), "within_2_of_a_light": fin & near, "elsewhere": fin & ~near}
+    return {"image": f"{scene} {width}x{width}", "frames": frames, "degrees_per_frame": degrees,
+            "passes_per_frame": 1, "spp_per_pass": 4, "reference_spp": ref_spp,
+            "pixels": {k: int(m.sum()) for k, m in sets.items()}, "mean_var": var,
+            "mse": {s: {c: float(((x[m].astype(np.float64) - ref[m]) ** 2).mean()) if m.any() else None
+                        for c, x in cols.items()} for s, m in sets.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-o", default=None)
@@ -230,12 +292,28 @@ def main():
     ap.add_argument("--quality-width", type=int, default=128)
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--ref-spp", type=int, default=1024)
+    ap.add_argument("--only", choices=("time", "quality", "clip"), default=None)
+    ap.add_argument("--sweep-degrees", type=float, default=3.0, help="the quads orbit's step in the gamma sweep")
     a = ap.parse_args()
     if rt.device_count() <= 0:
         raise SystemExit("temporal_bench: no HIP device visible")
-    res = {"device": torch.cuda.get_device_name(0), "time": bench_time(a.width, a.rounds, 5),
-           "quality": bench_quality(a.quality_width, a.frames, 1.0, a.ref_spp),
-           "quality_one_pass": bench_quality_one_pass(a.quality_width, a.frames, 1.0, a.ref_spp)}
+    res = {"device": torch.cuda.get_device_name(0)}
+    if a.only in (None, "time"):
+        res["time"] = bench_time(a.width, a.rounds, 5)
+    if a.only in (None, "quality"):
+        res["quality"] = bench_quality(a.quality_width, a.frames, 1.0, a.ref_spp)
+        res["quality_one_pass"] = bench_quality_one_pass(a.quality_width, a.frames, 1.0, a.ref_spp)
+    if a.only in (None, "clip"):
+        q = {f"{scene}_{deg:g}deg": bench_quality_clip(scene, a.quality_width, a.frames, deg, a.ref_spp)
+             for scene, deg in dict.fromkeys((("quads", 1.0), ("quads", 3.0), ("quads", a.sweep_degrees), ("cornell", 1.0)))}
+        res["quality_clip"] = q
+        res["gamma_sweep"] = {
+            "orbits": [f"quads_{a.sweep_degrees:g}deg", "cornell_1deg"],
+            "summed_all_pixel_mse_filtered": {
+                f"{g:g}": sum(q[o]["mse"]["all"][f"clip_gamma_{g:g}_filtered"]
+                              for o in (f"quads_{a.sweep_degrees:g}deg", "cornell_1deg")) for g in GAMMAS},
+            "without_clip": sum(q[o]["mse"]["all"]["history_filtered"]
+                                for o in (f"quads_{a.sweep_degrees:g}deg", "cornell_1deg"))}
     text = json.dumps(res, indent=1)
     print(text)
     if a.o:
