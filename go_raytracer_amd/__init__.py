@@ -25,7 +25,7 @@ __all__ = ["Tree", "Camera", "Scene", "Accumulator", "quantize", "format_ppm", "
            "tune", "untune", "tuning", "tune_knobs", "tune_from_env",
            "demo_scene", "DEMO_SCENES", "build_bvh_boxes", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
            "format_ppm_device", "denoise", "denoise_device", "denoise_var", "denoise_var_device",
-           "RtDenoiseVarOpts", "reproject", "reproject_device", "reproject_emit", "reproject_emit_device", "reproject_light", "reproject_light_device", "reproject_moments", "reproject_moments_device", "reproject_clip", "reproject_clip_device",
+           "RtDenoiseVarOpts", "reproject", "reproject_device", "reproject_emit", "reproject_emit_device", "reproject_light", "reproject_light_device", "reproject_moments", "reproject_moments_device", "reproject_clip", "reproject_clip_device", "reproject_spec", "reproject_spec_device",
            "Temporal"]
 
 DEMO_SCENES = ("book1", "book2", "book3", "simple_light", "quads", "cornell", "cornell_smoke",
@@ -643,15 +643,18 @@ class Scene:
         return self._aov(camera, o, n_samples, _aov_mode(emit, media, specular), True, ptr, (max_bounces, max_fuzz))
 
     def accumulator(self, camera, max_passes=0, device=0, rank=0, nranks=1, path_slots=0, chunk=0,
-                    profile=False, stream=None, mode="auto", progress_slices=0, features=None):
+                    profile=False, stream=None, mode="auto", progress_slices=0, features=None,
+                    spec_bounces=0, spec_fuzz=0.0):
         """A progressive pass accumulator (rt_accum_create) for this rank's rows of `camera`:
         see Accumulator.  max_passes=0 means 1024.  features="guides" keeps the albedo, normal
         and depth of the passes' own camera samples next to the image sums, "emit" also the
         emission split (rt_accum_set_features): see Accumulator.resolve_aov.  "guides+media" and
         "emit+media" keep the same planes of the samples' first events, constant media traced
-        (Scene.render_aov(media=True)), and a scatter plane."""
+        (Scene.render_aov(media=True)), and a scatter plane.  "guides+spec" and "emit+spec" also
+        keep the specular chains' normal, depth and bounces (Scene.render_aov(specular=True) with
+        max_bounces=spec_bounces, max_fuzz=spec_fuzz): see Accumulator.resolve_aov_spec."""
         return Accumulator(self, camera, max_passes, device, rank, nranks, path_slots, chunk,
-                           profile, stream, mode, progress_slices, features)
+                           profile, stream, mode, progress_slices, features, spec_bounces, spec_fuzz)
 
 
 class Accumulator:
@@ -669,21 +672,34 @@ class Accumulator:
     returns their means, the guides of exactly the samples in the image, and
     ``denoise_device()`` then needs no ``aov``.  ``"guides+media"`` / ``"emit+media"`` trace the
     constant media in those feature rays (``Scene.render_aov(media=True)``): the planes are of the
-    samples' first events and ``resolve_aov()`` adds ``"scatter"``."""
+    samples' first events and ``resolve_aov()`` adds ``"scatter"``.  ``"guides+spec"`` /
+    ``"emit+spec"`` also sum, in a second fold, the planes of the passes' specular chains
+    (``Scene.render_aov(specular=True)``): ``resolve_aov_spec()`` returns them, the planes
+    ``Temporal(specular=True)`` looks a mirror's history up with; ``resolve_aov()`` and
+    ``denoise_device()`` keep the first-hit guides."""
 
     FEATURES = {None: 0, "guides": _lib.RT_ACCUM_FEAT_GUIDES,
                 "emit": _lib.RT_ACCUM_FEAT_GUIDES | _lib.RT_ACCUM_FEAT_EMIT,
                 "guides+media": _lib.RT_ACCUM_FEAT_GUIDES | _lib.RT_ACCUM_FEAT_MEDIA,
                 "emit+media": _lib.RT_ACCUM_FEAT_GUIDES | _lib.RT_ACCUM_FEAT_EMIT | _lib.RT_ACCUM_FEAT_MEDIA}
+    # ... and with the specular chains' planes (rt_accum_set_features_spec), a table of their own
+    SPEC_FEATURES = {"guides+spec": _lib.RT_ACCUM_FEAT_GUIDES | _lib.RT_ACCUM_FEAT_SPEC,
+                     "emit+spec": _lib.RT_ACCUM_FEAT_GUIDES | _lib.RT_ACCUM_FEAT_EMIT | _lib.RT_ACCUM_FEAT_SPEC}
 
     def __init__(self, scene, camera, max_passes=0, device=0, rank=0, nranks=1, path_slots=0,
-                 chunk=0, profile=False, stream=None, mode="auto", progress_slices=0, features=None):
+                 chunk=0, profile=False, stream=None, mode="auto", progress_slices=0, features=None,
+                 spec_bounces=0, spec_fuzz=0.0):
         self._p = None
         self._device, self._mean, self._var = device, None, None  # denoise_device's tensors
         self._aov = None  # resolve_aov_device's
-        if features not in self.FEATURES:
-            raise ValueError("Accumulator: features must be None, 'guides', 'emit', 'guides+media' or "
-                             f"'emit+media', not {features!r}")
+        self._aov_spec = None  # resolve_aov_spec_device's
+        if features not in self.FEATURES and features not in self.SPEC_FEATURES:
+            raise ValueError("Accumulator: features must be None, 'guides', 'emit', 'guides+media', "
+                             f"'emit+media', 'guides+spec' or 'emit+spec', not {features!r}")
+        spec = features in self.SPEC_FEATURES
+        if not spec and (spec_bounces or spec_fuzz):
+            raise ValueError("Accumulator: spec_bounces and spec_fuzz are options of features='guides+spec' "
+                             "or 'emit+spec'")
         d = camera.derived()
         self.shape = (len(range(rank, d.height, nranks)), d.width)
         c = camera.to_c()
@@ -698,7 +714,11 @@ class Accumulator:
         scene._accums.add(self)
         if features is not None:
             try:
-                check(lib().rt_accum_set_features(self._p, self.FEATURES[features]))
+                if spec:
+                    so = RtAovSpecOpts(int(spec_bounces), float(spec_fuzz))
+                    check(lib().rt_accum_set_features_spec(self._p, self.SPEC_FEATURES[features], C.byref(so)))
+                else:
+                    check(lib().rt_accum_set_features(self._p, self.FEATURES[features]))
             except BaseException:
                 self.close()
                 raise
@@ -710,11 +730,11 @@ class Accumulator:
 
     @property
     def features(self):
-        """None, "guides", "emit", "guides+media" or "emit+media": the feature planes the passes
-        keep (rt_accum_get_features)."""
+        """None, "guides", "emit", "guides+media", "emit+media", "guides+spec" or "emit+spec": the
+        feature planes the passes keep (rt_accum_get_features)."""
         m = C.c_uint32()
         check(lib().rt_accum_get_features(self._h(), C.byref(m)))
-        return {v: k for k, v in self.FEATURES.items()}.get(m.value, m.value)
+        return {v: k for k, v in {**self.FEATURES, **self.SPEC_FEATURES}.items()}.get(m.value, m.value)
 
     def _aov_keys(self):
         f = self.features
@@ -763,6 +783,40 @@ class Accumulator:
         media, args, _keep = self._aov_args(keys, lambda k: t[k].data_ptr())
         check((lib().rt_accum_resolve_aov_media_device if media else lib().rt_accum_resolve_aov_device)(
             self._h(), *args))
+        return t
+
+    def _spec_check(self):
+        if not str(self.features).endswith("+spec"):
+            raise ValueError("Accumulator: no chain planes (Scene.accumulator(features='guides+spec' or "
+                             f"'emit+spec')), features={self.features!r}")
+
+    def resolve_aov_spec(self):
+        """The specular chains' planes of exactly the camera samples the passes rendered
+        (rt_accum_resolve_aov_spec): {"normal", "depth", "bounces"} as
+        Scene.render_aov(specular=True) gives them, per pixel the mean over its passes' samples
+        (bounces exactly: a pixel whose samples all passed k vertices has float32(k)), zeros
+        without a pass.  Needs features "guides+spec" or "emit+spec"."""
+        self._spec_check()
+        res = {"normal": np.zeros(self.shape + (3,), np.float32), "depth": np.zeros(self.shape, np.float32),
+               "bounces": np.zeros(self.shape, np.float32)}
+        a = RtAov(None, res["normal"].ctypes.data, res["depth"].ctypes.data, None)
+        sp = RtAovSpec(res["bounces"].ctypes.data)
+        check(lib().rt_accum_resolve_aov_spec(self._h(), C.byref(a), C.byref(sp)))
+        return res
+
+    def resolve_aov_spec_device(self):
+        """resolve_aov_spec() into torch tensors on the accumulator's device, which the accumulator
+        owns (allocated on first use, overwritten by the next call)."""
+        import torch
+        self._spec_check()
+        if self._aov_spec is None:
+            dev = torch.device("cuda", self._device)
+            self._aov_spec = {k: torch.empty(self.shape + ((3,) if k == "normal" else ()), dtype=torch.float32,
+                                             device=dev) for k in ("normal", "depth", "bounces")}
+        t = self._aov_spec
+        a = RtAov(None, t["normal"].data_ptr(), t["depth"].data_ptr(), None)
+        sp = RtAovSpec(t["bounces"].data_ptr())
+        check(lib().rt_accum_resolve_aov_spec_device(self._h(), C.byref(a), C.byref(sp)))
         return t
 
     __del__ = close
@@ -1407,11 +1461,14 @@ def _moments_opts(min_frames=0.0, var_radius=0):
     return _lib.RtMomentsOpts(float(min_frames), int(var_radius))
 
 
-def _reproject_moments(device, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts, gamma=None):
+def _reproject_moments(device, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts, gamma=None,
+                       spec=False):
     """reproject_moments and reproject_moments_device (device): rt_reproject_moments[_device] on host
     arrays or torch tensors; with gamma (not None) reproject_clip and reproject_clip_device:
-    rt_reproject_clip[_device]"""
-    who = ("reproject_clip" if gamma is not None else "reproject_moments") + ("_device" if device else "")
+    rt_reproject_clip[_device]; with spec reproject_spec and reproject_spec_device:
+    rt_reproject_spec[_device], gamma None meaning its copts == NULL"""
+    who = ("reproject_spec" if spec else "reproject_clip" if gamma is not None else "reproject_moments") + (
+        "_device" if device else "")
     if isinstance(mode, bool) or mode not in _MOMENT_MODES:
         raise ValueError(f"{who}: mode must be 'plain', 'emit' or 'light' (or 0, 1, 2), not {mode!r}")
     mode = _MOMENT_MODES[mode]
@@ -1469,6 +1526,17 @@ def _reproject_moments(device, mode, cam_prev, prev, cam_cur, cur, out, min_fram
             raise ValueError(f"{who}: prev['lum2'] is required (the lum2 plane an earlier call returned)")
         keep_p.append(conv("prev['lum2']", prev["lum2"], (h, w)))
         lp, cp = ptr(keep_p[-1]), cam_prev.to_c()
+    sp = None
+    if spec:  # the frames' chain lengths: inputs as the rest, never an out buffer
+        if cur.get("bounces") is None:
+            raise ValueError(f"{who}: cur['bounces'] is required (resolve_aov_spec / resolve_aov_spec_device)")
+        keep_c = keep_c + [conv("cur['bounces']", cur["bounces"], (h, w))]
+        sp = _lib.RtSpecPlanes(None, ptr(keep_c[-1]))
+        if prev is not None:
+            if prev.get("bounces") is None:
+                raise ValueError(f"{who}: prev['bounces'] is required (the bounces plane of the previous frame)")
+            keep_p.append(conv("prev['bounces']", prev["bounces"], (h, w)))
+            sp.prev_bounces = ptr(keep_p[-1])
     res = []
     for k, ch in _FRAME_KEYS[:3] + (_LIGHT_KEYS if light else ()) + (("lum2", 0),):
         shape = (h, w, ch) if ch else (h, w)
@@ -1493,6 +1561,11 @@ def _reproject_moments(device, mode, cam_prev, prev, cam_cur, cur, out, min_fram
             raise ValueError(f"{who}: gamma {gamma!r} rounds to 0 as a float, which selects the default")
         args.insert(12, r(_lib.RtClipOpts(float(gamma))))  # copts follows mopts
         entry = "rt_reproject_clip"
+    if spec:
+        if gamma is None:
+            args.insert(12, None)
+        args.insert(13, r(sp))  # spec follows copts
+        entry = "rt_reproject_spec"
     if device:
         check(getattr(lib(), entry + "_device")(*args, a.device.index or 0, _stream_of(a)))
     else:
@@ -1537,6 +1610,24 @@ def reproject_clip_device(mode, cam_prev, prev, cam_cur, cur, out=None, min_fram
     return _reproject_moments(True, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts, gamma)
 
 
+def reproject_spec(mode, cam_prev, prev, cam_cur, cur, min_frames=0.0, var_radius=0, gamma=0.0, **opts):
+    """reproject_clip for mirrors (rt_reproject_spec; DESIGN.md "Temporal history for mirrors"): the
+    frames' "normal" and "depth" are the specular chains' (Accumulator.resolve_aov_spec), so the
+    history is looked up through the mirror's virtual point, and both frames also hold "bounces"
+    [H, W]: a pixel whose bounces value is not a whole number has no history, and a tap is taken
+    only where its bounces value equals the pixel's.  Arguments and result as reproject_clip's;
+    gamma=None: no clamp (reproject_moments' blend)."""
+    return _reproject_moments(False, mode, cam_prev, prev, cam_cur, cur, None, min_frames, var_radius, opts, gamma,
+                              spec=True)
+
+
+def reproject_spec_device(mode, cam_prev, prev, cam_cur, cur, out=None, min_frames=0.0, var_radius=0, gamma=0.0,
+                          **opts):
+    """rt_reproject_spec_device on torch tensors: reproject_clip_device with reproject_spec's frames."""
+    return _reproject_moments(True, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts, gamma,
+                              spec=True)
+
+
 class Temporal:
     """The history of a moving camera (DESIGN.md "Temporal reprojection"): ``push(acc)`` takes the
     accumulator of the next frame, reprojects the stored history into its camera
@@ -1559,11 +1650,19 @@ class Temporal:
     clip=True (reproject_clip_device, DESIGN.md "Clamping the history"; needs moments=True and a
     window) clamps the reprojected colour to the current frame's neighbourhood before the blend,
     mean +- clip_gamma sigma (0: the library default), so that a stale reflection on metal or glass
-    is overruled."""
+    is overruled.
+    specular=True (reproject_spec_device, DESIGN.md "Temporal history for mirrors"; needs
+    moments=True, combines with clip) looks the history of a mirror up through its virtual point: the
+    accumulators must have features "guides+spec" or "emit+spec", and the history's normal, depth
+    and bounces are their chain planes (resolve_aov_spec_device), not the first hit's."""
 
     def __init__(self, split_emitters=False, light_history=False, moments=False, min_frames=0.0, var_radius=0,
-                 clip=False, clip_gamma=0.0, **opts):
+                 clip=False, clip_gamma=0.0, specular=False, **opts):
         _reproject_opts(**opts)  # a wrong name fails here, not at the second push
+        if specular and not moments:
+            raise ValueError("Temporal: specular=True needs moments=True (the chain gate is a step of "
+                             "reproject_moments): Temporal(moments=True, specular=True)")
+        self._specular = bool(specular)
         if not moments and (min_frames or var_radius):
             raise ValueError("Temporal: min_frames and var_radius are options of moments=True")
         if clip and not moments:
@@ -1612,6 +1711,10 @@ class Temporal:
         if self._split and not str(acc.features).startswith("emit"):
             raise ValueError("Temporal.push: split_emitters needs an accumulator with features='emit' "
                              f"(Scene.accumulator(..., features='emit')), not features={acc.features!r}")
+        if self._specular and not str(acc.features).endswith("+spec"):
+            raise ValueError("Temporal.push: specular=True needs an accumulator with the chain planes "
+                             "(Scene.accumulator(..., features='guides+spec' or 'emit+spec')), not "
+                             f"features={acc.features!r}")
         if acc.nranks != 1:
             raise ValueError("Temporal.push: needs the whole image (nranks == 1)")
         passes = acc.passes
@@ -1654,8 +1757,9 @@ class Temporal:
             return {key: torch.empty((h, w, ch) if ch else (h, w), dtype=torch.float32, device=dev) for key, ch in keys}
         split = (("emission", 3), ("coverage", 0)) if self._split else ()
         s = self._sets[k]
+        spec = (("bounces", 0),) if self._specular else ()
         if s is None or "lum2" not in s or s["depth"].shape != (h, w) or s["depth"].device != dev:
-            s = self._sets[k] = tensors(_FRAME_KEYS + split + (("lum2", 0),))
+            s = self._sets[k] = tensors(_FRAME_KEYS + split + (("lum2", 0),) + spec)
         c = self._cur
         if c is None or c["var"].shape != (h, w) or c["var"].device != dev:
             c = self._cur = tensors((("rgb", 3), ("var", 0)) + (split if self._light else ()))
@@ -1663,8 +1767,16 @@ class Temporal:
         guides = RtAov(None, s["normal"].data_ptr(), s["depth"].data_ptr(), None)
         e = c if self._light else s
         emit = RtAovEmit(e["emission"].data_ptr(), None, e["coverage"].data_ptr()) if self._split else None
-        check(lib().rt_accum_resolve_aov_device(acc._h(), C.byref(guides), emit and C.byref(emit)))
+        if self._specular:  # the chain's normal, depth and bounces in the first hit's place
+            chain = RtAovSpec(s["bounces"].data_ptr())
+            check(lib().rt_accum_resolve_aov_spec_device(acc._h(), C.byref(guides), C.byref(chain)))
+            if emit:
+                check(lib().rt_accum_resolve_aov_device(acc._h(), None, C.byref(emit)))
+        else:
+            check(lib().rt_accum_resolve_aov_device(acc._h(), C.byref(guides), emit and C.byref(emit)))
         cur = dict(c, count=passes, normal=s["normal"], depth=s["depth"])
+        if self._specular:
+            cur["bounces"] = s["bounces"]
         if self._split:
             cur.update(emission=e["emission"], coverage=e["coverage"])
         p = None if self._prev is None else self._sets[self._prev]
@@ -1672,7 +1784,10 @@ class Temporal:
             p = None
         out = {key: s[key] for key in ("rgb", "var", "count", "lum2") + (("emission", "coverage") if self._light else ())}
         mode = "light" if self._light else "emit" if self._split else "plain"
-        if self._clip is None:
+        if self._specular:
+            reproject_spec_device(mode, None if p is None else self._cam, p, acc.camera, cur, out=out,
+                                  gamma=self._clip, **self._mopts, **self._opts)
+        elif self._clip is None:
             reproject_moments_device(mode, None if p is None else self._cam, p, acc.camera, cur, out=out,
                                      **self._mopts, **self._opts)
         else:

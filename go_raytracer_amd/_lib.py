@@ -32,6 +32,7 @@ RT_FT_ALL = 511
 RT_MODE_AUTO, RT_MODE_WAVEFRONT, RT_MODE_FUSED = 0, 1, 2
 RT_ACCUM_FEAT_GUIDES, RT_ACCUM_FEAT_EMIT = 1, 2  # rt_accum_set_features' plane groups
 RT_ACCUM_FEAT_MEDIA = 4  # ... and the modifier that makes them first-event sums (with a scatter count)
+RT_ACCUM_FEAT_SPEC = 8  # ... and the specular chains' normal, depth and bounces (not with MEDIA)
 
 D3 = C.c_double * 3
 
@@ -147,6 +148,10 @@ class RtMomentsOpts(C.Structure):  # rt_moments_opts (0 = the library default; r
 
 class RtClipOpts(C.Structure):  # rt_clip_opts (0 = the library default)
     _fields_ = [("gamma", C.c_float)]
+
+
+class RtSpecPlanes(C.Structure):  # rt_spec_planes: the chain lengths of rt_reproject_spec's two frames
+    _fields_ = [("prev_bounces", C.c_void_p), ("cur_bounces", C.c_void_p)]
 
 
 RT_REPROJECT_PLAIN, RT_REPROJECT_EMIT, RT_REPROJECT_LIGHT = 0, 1, 2
@@ -391,6 +396,19 @@ SIGNATURES = {
                                       C.POINTER(RtAovEmit), _I, _I, C.POINTER(RtReprojectOpts),
                                       C.POINTER(RtMomentsOpts), C.POINTER(RtClipOpts), C.POINTER(RtFrame),
                                       C.POINTER(RtAovEmit), C.c_void_p, _I, C.c_void_p]),
+    "rt_reproject_spec": (_I, [_I, C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
+                               C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtFrame),
+                               C.POINTER(RtAovEmit), _I, _I, C.POINTER(RtReprojectOpts),
+                               C.POINTER(RtMomentsOpts), C.POINTER(RtClipOpts), C.POINTER(RtSpecPlanes),
+                               C.POINTER(RtFrame), C.POINTER(RtAovEmit), C.c_void_p]),
+    "rt_reproject_spec_device": (_I, [_I, C.POINTER(RtCamera), C.POINTER(RtFrame), C.POINTER(RtAovEmit),
+                                      C.c_void_p, C.POINTER(RtCamera), C.POINTER(RtFrame),
+                                      C.POINTER(RtAovEmit), _I, _I, C.POINTER(RtReprojectOpts),
+                                      C.POINTER(RtMomentsOpts), C.POINTER(RtClipOpts), C.POINTER(RtSpecPlanes),
+                                      C.POINTER(RtFrame), C.POINTER(RtAovEmit), C.c_void_p, _I, C.c_void_p]),
+    "rt_accum_set_features_spec": (_I, [_P, C.c_uint32, C.POINTER(RtAovSpecOpts)]),
+    "rt_accum_resolve_aov_spec": (_I, [_P, C.POINTER(RtAov), C.POINTER(RtAovSpec)]),
+    "rt_accum_resolve_aov_spec_device": (_I, [_P, C.POINTER(RtAov), C.POINTER(RtAovSpec)]),
     "rt_demo_scene": (_I, [_P, C.c_char_p, C.c_char_p, C.POINTER(RtCamera), C.POINTER(_I),
                            C.POINTER(_I)]),
     "rt_demo_scene_name": (_I, [_I, C.POINTER(C.c_char_p)]),

@@ -34,6 +34,9 @@
 // with the scatter plane) of staging for rt_accum_resolve_aov.  A pass then
 // also runs rt_aov.hip's k_aov_fold for the same seed and pixels on the same stream;
 // k_feat_resolve<PX> maps the sums to the rt_aov / rt_aov_emit planes.
+// RT_ACCUM_FEAT_SPEC adds the chain sums (SpecPlanes: 40 B per pixel, fp64 normal and
+// depth and a 64-bit count of specular vertices) and 20 B of staging; a pass then also runs
+// k_aov_spec_fold, and k_spec_resolve<PX> maps the sums to rt_accum_resolve_aov_spec's planes.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -188,6 +191,22 @@ __global__ __launch_bounds__(256) void k_scatter_resolve(const uint32_t* nscatte
   if (lp >= npix) return;
   const double den = (double)passes_of(c, lp) * (double)ss;
   scatter[lp] = den > 0.0 ? (float)((double)nscatter[lp] / den) : 0.0f;
+}
+
+// The chain planes (RT_ACCUM_FEAT_SPEC), a kernel of its own as k_scatter_resolve: the normal and
+// depth sums over the pixel's n_p * ss samples, divided in fp64 and rounded once, and bounces = the
+// specular vertices passed over the same number (a pixel whose samples all passed k: exactly k).
+template <bool PX>
+__global__ __launch_bounds__(256) void k_spec_resolve(SpecPlanes S, uint32_t ss, Passes<PX> c, float* normal,
+                                                      float* depth, float* bounces) {
+  const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
+  if (lp >= S.npix) return;
+  const double den = (double)passes_of(c, lp) * (double)ss;
+  const size_t n = S.npix;
+  if (normal)
+    for (int ch = 0; ch < 3; ++ch) normal[3 * (size_t)lp + ch] = den > 0.0 ? (float)(S.normal[ch * n + lp] / den) : 0.0f;
+  if (depth) depth[lp] = den > 0.0 ? (float)(S.depth[lp] / den) : 0.0f;
+  if (bounces) bounces[lp] = den > 0.0 ? (float)((double)S.nspec[lp] / den) : 0.0f;
 }
 
 constexpr int kInfoBlocks = 256;  // at most: stage 2 is one block over the partials
@@ -404,6 +423,8 @@ struct rt_accum {
   rt::FeatPlanes F{};
   uint32_t* nscatter = nullptr;  // [npix] RT_ACCUM_FEAT_MEDIA: samples whose first event is a scatter (exact)
   float* feat_stage = nullptr;  // [14][npix] floats: rt_accum_resolve_aov's planes in FeatOut's order, then scatter's
+  rt::SpecPlanes S{};           // RT_ACCUM_FEAT_SPEC: the chain sums and the chain limits
+  float* spec_stage = nullptr;  // [5][npix] floats: rt_accum_resolve_aov_spec's normal, depth, bounces
 };
 
 namespace rt {
@@ -435,7 +456,11 @@ int fold_pass(void* ctx, const Params& p, double scale, hipStream_t stream) {
                        px_counts(a, a->pass_map));
   }
   HIP_OK(hipGetLastError());
-  if (a->features) return aov_fold_enqueue(a->F, a->nscatter, a->per_pixel || a->pass_map, a->pass_map, stream);
+  if (a->features) {
+    if (int rc = aov_fold_enqueue(a->F, a->nscatter, a->per_pixel || a->pass_map, a->pass_map, stream)) return rc;
+    if (a->features & RT_ACCUM_FEAT_SPEC)  // the chain fold: the same seed and pixels, after the first-hit fold
+      return aov_spec_fold_enqueue(a->S, a->per_pixel || a->pass_map, a->pass_map, stream);
+  }
   return RT_OK;
 }
 
@@ -555,6 +580,14 @@ size_t carve_features(rt_accum* a, uint32_t planes, void* base) {
   };
   a->F = FeatPlanes{};
   a->F.npix = a->npix;
+  const SpecPlanes lim = a->S;  // (the chain limits are accum_set_features', not this function's)
+  a->S = SpecPlanes{};
+  a->S.npix = a->npix, a->S.max_k = lim.max_k, a->S.max_fuzz = lim.max_fuzz;
+  if (planes & RT_ACCUM_FEAT_SPEC) {  // first: 8-byte elements, before the groups' 4-byte counts
+    take(a->S.normal, 3 * n);
+    take(a->S.depth, n);
+    take(a->S.nspec, n);
+  }
   if (planes & RT_ACCUM_FEAT_GUIDES) {
     take(a->F.albedo, 3 * n);
     take(a->F.normal, 3 * n);
@@ -569,6 +602,8 @@ size_t carve_features(rt_accum* a, uint32_t planes, void* base) {
   if (planes & RT_ACCUM_FEAT_MEDIA) take(a->nscatter, n);
   a->feat_state_bytes = off;
   take(a->feat_stage, (planes & RT_ACCUM_FEAT_MEDIA ? 15 : 14) * n);
+  a->spec_stage = nullptr;
+  if (planes & RT_ACCUM_FEAT_SPEC) take(a->spec_stage, 5 * n);
   return off;
 }
 
@@ -579,6 +614,8 @@ void drop_features(rt_accum* a) {
   a->F = FeatPlanes{};
   a->nscatter = nullptr;
   a->feat_stage = nullptr;
+  a->S = SpecPlanes{};
+  a->spec_stage = nullptr;
 }
 
 void free_accum(rt_accum* a) {
@@ -817,33 +854,110 @@ int rt_accum_reset(rt_accum* a) {
   return RT_OK;
 }
 
-int rt_accum_set_features(rt_accum* a, uint32_t planes) {
-  using namespace rt;
-  if (!a) return set_error(RT_ERR_INVALID, "rt_accum_set_features: null accumulator");
-  if (planes & ~(RT_ACCUM_FEAT_GUIDES | RT_ACCUM_FEAT_EMIT | RT_ACCUM_FEAT_MEDIA))
-    return set_error(RT_ERR_INVALID, "rt_accum_set_features: unknown planes 0x%x", planes);
+}  // extern "C"
+
+namespace rt {
+namespace {
+// rt_accum_set_features and rt_accum_set_features_spec (spec: that entry, which alone knows
+// RT_ACCUM_FEAT_SPEC; spec_opts: the chain limits, null: the defaults)
+int accum_set_features(const char* who, bool spec, rt_accum* a, uint32_t planes, const rt_aov_spec_opts* spec_opts) {
+  if (!a) return set_error(RT_ERR_INVALID, "%s: null accumulator", who);
+  // rt_accum_set_features takes the planes it always took: to it the chain group is an unknown bit
+  if (planes & ~(RT_ACCUM_FEAT_GUIDES | RT_ACCUM_FEAT_EMIT | RT_ACCUM_FEAT_MEDIA | (spec ? RT_ACCUM_FEAT_SPEC : 0u)))
+    return set_error(RT_ERR_INVALID, "%s: unknown planes 0x%x%s", who, planes,
+                     planes & RT_ACCUM_FEAT_SPEC ? " (RT_ACCUM_FEAT_SPEC: rt_accum_set_features_spec)" : "");
   if (planes == RT_ACCUM_FEAT_MEDIA)
-    return set_error(RT_ERR_INVALID, "rt_accum_set_features: RT_ACCUM_FEAT_MEDIA modifies GUIDES / EMIT, it needs one");
+    return set_error(RT_ERR_INVALID, "%s: RT_ACCUM_FEAT_MEDIA modifies GUIDES / EMIT, it needs one", who);
+  if (planes == RT_ACCUM_FEAT_SPEC)
+    return set_error(RT_ERR_INVALID, "%s: RT_ACCUM_FEAT_SPEC goes with GUIDES / EMIT, it needs one", who);
+  if ((planes & RT_ACCUM_FEAT_SPEC) && (planes & RT_ACCUM_FEAT_MEDIA))
+    return set_error(RT_ERR_INVALID, "%s: RT_ACCUM_FEAT_SPEC does not combine with RT_ACCUM_FEAT_MEDIA (a chain traces no media)", who);
+  rt_aov_spec_opts so{8, 0.0f};  // rt_render_aov_spec's defaults and range checks
+  if (spec_opts) {
+    if (spec_opts->max_bounces < 0 || spec_opts->max_bounces > 64)
+      return set_error(RT_ERR_INVALID, "%s: max_bounces %d not in 0 .. 64", who, spec_opts->max_bounces);
+    if (!(spec_opts->max_fuzz >= 0.0f) || !std::isfinite(spec_opts->max_fuzz))
+      return set_error(RT_ERR_INVALID, "%s: max_fuzz must be finite and >= 0", who);
+    if (spec_opts->max_bounces > 0) so.max_bounces = spec_opts->max_bounces;
+    so.max_fuzz = spec_opts->max_fuzz;
+  }
   std::lock_guard<std::mutex> lk(a->mu);
   if (a->passes > 0)
-    return set_error(RT_ERR_INVALID, "rt_accum_set_features: the accumulator holds %d passes (rt_accum_reset first)",
-                     a->passes);
-  if (planes == a->features) return RT_OK;
+    return set_error(RT_ERR_INVALID, "%s: the accumulator holds %d passes (rt_accum_reset first)", who, a->passes);
+  const int32_t max_k = std::max(0, std::min(so.max_bounces, a->cd.max_depth - 1));
+  if (planes == a->features) {  // the same planes: only the chain limits may change
+    if (planes & RT_ACCUM_FEAT_SPEC) a->S.max_k = max_k, a->S.max_fuzz = so.max_fuzz;
+    return RT_OK;
+  }
   DeviceGuard dg;
   HIP_OK(hipSetDevice(a->opts.device));
   drop_features(a);
   if (planes == 0) return RT_OK;
   const size_t total = carve_features(a, planes, nullptr);
-  int rc = a->feat_buf.grow(total, "rt_accum_set_features");
+  int rc = a->feat_buf.grow(total, who);
   if (rc == RT_OK && hipMemset(a->feat_buf.p, 0, total) != hipSuccess)
-    rc = set_error(RT_ERR_DEVICE, "rt_accum_set_features: clearing %zu bytes", total);
+    rc = set_error(RT_ERR_DEVICE, "%s: clearing %zu bytes", who, total);
   if (rc) {
     drop_features(a);
     return rc;
   }
+  if (planes & RT_ACCUM_FEAT_SPEC) a->S.max_k = max_k, a->S.max_fuzz = so.max_fuzz;
   carve_features(a, planes, a->feat_buf.p);
   a->features = planes;
   return RT_OK;
+}
+
+int accum_resolve_aov_spec(rt_accum* a, const rt_aov* outp, const rt_aov_spec* specp, bool host) {
+  const char* who = host ? "rt_accum_resolve_aov_spec" : "rt_accum_resolve_aov_spec_device";
+  if (!a) return set_error(RT_ERR_INVALID, "%s: null accumulator", who);
+  if (outp && (outp->albedo || outp->material))
+    return set_error(RT_ERR_INVALID, "%s: the accumulator keeps no albedo or material plane of the chain", who);
+  float* const user[3] = {outp ? outp->normal : nullptr, outp ? outp->depth : nullptr, specp ? specp->bounces : nullptr};
+  if (!user[0] && !user[1] && !user[2]) return set_error(RT_ERR_INVALID, "%s: no buffer wanted", who);
+  std::lock_guard<std::mutex> lk(a->mu);
+  if (!(a->features & RT_ACCUM_FEAT_SPEC))
+    return set_error(RT_ERR_INVALID, "%s: the chain planes are not enabled (rt_accum_set_features_spec)", who);
+  if (a->npix == 0) return RT_OK;
+  DeviceGuard dg;
+  hipStream_t stream;
+  int rc;
+  if ((rc = accum_device(a, &stream))) return rc;
+  const size_t n = a->npix;
+  const size_t floats[3] = {3 * n, n, n};
+  float* dev[3];
+  size_t off = 0;
+  for (int i = 0; i < 3; off += floats[i++]) dev[i] = !user[i] ? nullptr : host ? a->spec_stage + off : user[i];
+  if (a->per_pixel)
+    hipLaunchKernelGGL(k_spec_resolve<true>, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->S, a->ss,
+                       px_counts(a), dev[0], dev[1], dev[2]);
+  else
+    hipLaunchKernelGGL(k_spec_resolve<false>, dim3((a->npix + 255) / 256), dim3(256), 0, stream, a->S, a->ss,
+                       Passes<false>{(uint32_t)a->passes}, dev[0], dev[1], dev[2]);
+  HIP_OK(hipGetLastError());
+  for (int i = 0; host && i < 3; ++i)
+    if (user[i]) HIP_OK(hipMemcpyAsync(user[i], dev[i], floats[i] * sizeof(float), hipMemcpyDeviceToHost, stream));
+  HIP_OK(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+}  // namespace
+}  // namespace rt
+
+extern "C" {
+
+int rt_accum_set_features(rt_accum* a, uint32_t planes) {
+  return rt::accum_set_features("rt_accum_set_features", false, a, planes, nullptr);
+}
+
+int rt_accum_set_features_spec(rt_accum* a, uint32_t planes, const rt_aov_spec_opts* spec_opts) {
+  return rt::accum_set_features("rt_accum_set_features_spec", true, a, planes, spec_opts);
+}
+
+int rt_accum_resolve_aov_spec(rt_accum* a, const rt_aov* out_host, const rt_aov_spec* spec_host) {
+  return rt::accum_resolve_aov_spec(a, out_host, spec_host, true);
+}
+
+int rt_accum_resolve_aov_spec_device(rt_accum* a, const rt_aov* out_dev, const rt_aov_spec* spec_dev) {
+  return rt::accum_resolve_aov_spec(a, out_dev, spec_dev, false);
 }
 
 int rt_accum_get_features(rt_accum* a, uint32_t* planes) {

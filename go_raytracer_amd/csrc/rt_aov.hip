@@ -440,6 +440,35 @@ __global__ __launch_bounds__(256) void k_aov_fold(Params P, FeatPlanesArg<MEDIA>
   }
 }
 
+// The accumulator's chain fold (RT_ACCUM_FEAT_SPEC): k_aov_fold's loop with the
+// specular mode's samples (aov_sample<TREE, false, false, true>, rt_render_aov_spec's), the pass's
+// fp32 normal and depth sums added to the fp64 planes S and its specular vertices to an exact 64-bit
+// count.  No albedo is kept.  A kernel of its own, so that k_aov_fold's instances stay what they
+// were (profiles/accum_spec_device_code.txt).  v < P.npix <= S.npix and map[v] < S.npix, as there.
+template <int TREE, bool PX>
+__global__ __launch_bounds__(256) void k_aov_spec_fold(Params P, SpecPlanes S, const uint32_t* map) {
+  constexpr uint32_t FT = TREE == 0 ? (uint32_t)FT_MEDIA : (uint32_t)FT_ALL;
+  __shared__ uint32_t lstack[kShortStack * 256];
+  if constexpr (HAS(FT_NOISE)) stage_perlin(P.sc);
+  __syncthreads();
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const TravStack ts = {&lstack[threadIdx.x], P.ostack + gtid, P.stack_cols, kShortStack};
+  const uint32_t stride = gridDim.x * blockDim.x;
+  const size_t n = S.npix;
+  for (uint32_t v = gtid; v < P.npix; v += stride) {
+    uint32_t p = v;
+    if constexpr (PX) p = map ? map[v] : v;
+    const Ids id = aov_ids(P, p, P.ss);
+    AovSums s = aov_sums_zero();
+    for (uint32_t j = 0; j < P.ss; ++j) aov_sample<TREE, false, false, true>(P, id, j, ts, s, S.max_k, S.max_fuzz);
+    S.normal[p] += (double)s.nsum.x;
+    S.normal[n + p] += (double)s.nsum.y;
+    S.normal[2 * n + p] += (double)s.nsum.z;
+    S.depth[p] += (double)s.dsum;
+    S.nspec[p] += (unsigned long long)s.nspec;
+  }
+}
+
 namespace {
 
 // one feature pass at a time: the scratch buffers (overflow stacks, host staging) and the
@@ -704,6 +733,18 @@ int aov_fold_enqueue(const FeatPlanes& F, uint32_t* nscatter, bool px, const uin
                              stream, g_fold.p, (const FeatPlanesArg<M>&)fm, map);
         });
       });
+    });
+  });
+  HIP_OK(hipGetLastError());
+  return RT_OK;
+}
+
+// k_aov_spec_fold of px x tree, its 8 instances
+int aov_spec_fold_enqueue(const SpecPlanes& S, bool px, const uint32_t* map, hipStream_t stream) {
+  const dim3 g((unsigned)g_fold.blocks), b(256);
+  with_tree(g_fold.tree, [&](auto t) {
+    with_flag(px, [&](auto x) {
+      hipLaunchKernelGGL((k_aov_spec_fold<decltype(t)::value, decltype(x)::value>), g, b, 0, stream, g_fold.p, S, map);
     });
   });
   HIP_OK(hipGetLastError());

@@ -75,4 +75,20 @@ int aov_fold_begin(rt_scene* scene, const rt_camera_derived& cd, const rt_render
 int aov_fold_enqueue(const FeatPlanes& F, uint32_t* nscatter, bool px, const uint32_t* map, hipStream_t stream);
 void aov_fold_end();
 
+// The accumulator's chain sums (RT_ACCUM_FEAT_SPEC): the per-pass fp32 sums of the
+// specular chains' terminal normal and summed depth (rt_render_aov_spec's samples), added in fp64,
+// and the specular vertices passed as an exact integer (at most 64 a sample: 64 bits hold
+// max_passes x spp_sqrt^2 x 64).  max_k and max_fuzz are the chain limits the kernel takes.
+struct SpecPlanes {
+  double* normal;             // [3][npix]
+  double* depth;              // [npix]
+  unsigned long long* nspec;  // [npix]
+  uint32_t npix;
+  int32_t max_k;
+  float max_fuzz;
+};
+// The chain fold of the pass aov_fold_begin prepared, after aov_fold_enqueue on the same stream (the
+// two share the overflow stacks): k_aov_spec_fold for the same seed and pixels.
+int aov_spec_fold_enqueue(const SpecPlanes& S, bool px, const uint32_t* map, hipStream_t stream);
+
 }  // namespace rt

@@ -61,6 +61,16 @@
 //                 from selected values only.  The six other instances are what they were,
 //                 instruction for instruction (profiles/temporal_clip_device_code.txt).
 //
+//   k_reproject<Emit, Light, true, Clip, true> : rt_reproject_spec's six instances.  The caller hands
+//                 the specular chain's depth and normal for both frames (rt_accum_resolve_aov_spec), so
+//                 the hit point rebuilt above is the virtual point behind the mirror, and one more
+//                 plane, the chain's length: a pixel whose bounces value is not a whole number has no
+//                 history, and a tap is taken only where its bounces value equals the pixel's, one
+//                 more term of the tap rule and one more gathered dword per tap.  The tap loop stays
+//                 branch-free and the Clip instances' LDS tile is what it was.  The nine other
+//                 instances are what they were, instruction for instruction
+//                 (profiles/temporal_spec_device_code.txt).
+//
 // Bytes per pixel: 36 read of the current frame (28 without var and count planes), up to 4 x 36
 // gathered from the previous one (L1/L2-resident: adjacent lanes share three of four taps), 20
 // written.  Emit: 16 more of the current pixel, 4 x 16 more gathered.  Light: 16 more written.
@@ -144,9 +154,19 @@ struct ClipArgs<true> {
   float gamma;
 };
 
+// rt_reproject_spec's own arguments (rt_spec_planes); no member without it.  prev_bounces is the
+// current plane when there is no previous frame (read through clamped addresses, never a tap)
+template <bool Spec>
+struct SpecArgs {};
+template <>
+struct SpecArgs<true> {
+  const float* prev_bounces;
+  const float* cur_bounces;
+};
+
 // a kernel's last argument: the sets as bases, so that an empty one takes no kernel argument space
-template <bool Emit, bool Light, bool Mom, bool Clip>
-struct Extra : EmitPlanes<Emit, Light>, MomPlanes<Mom>, ClipArgs<Clip> {};
+template <bool Emit, bool Light, bool Mom, bool Clip, bool Spec = false>
+struct Extra : EmitPlanes<Emit, Light>, MomPlanes<Mom>, ClipArgs<Clip>, SpecArgs<Spec> {};
 
 __device__ __forceinline__ float lum(V3 a) { return 0.2126f * a.x + 0.7152f * a.y + 0.0722f * a.z; }
 
@@ -231,9 +251,9 @@ __device__ __forceinline__ WindowSums window_sums(const TpParams& P, const float
   return {a, b, T, A, B};
 }
 
-template <bool Emit, bool Light, bool Mom, bool Clip>
+template <bool Emit, bool Light, bool Mom, bool Clip, bool Spec = false>
 __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Planes cur, Planes out,
-                                                   Extra<Emit, Light, Mom, Clip> ex) {
+                                                   Extra<Emit, Light, Mom, Clip, Spec> ex) {
   const EmitPlanes<Emit, Light>& em = ex;
   const MomPlanes<Mom>& mo = ex;
   [[maybe_unused]] const float* tile = nullptr;
@@ -272,6 +292,7 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
   }
   static_assert(Emit || !Light, "the light history is a history of the emission split's planes");
   static_assert(Mom || !Clip, "the clip entries are the moments entries with one more step");
+  static_assert(Mom || !Spec, "the specular entries are the clip entries with one more plane");
   const int tile_y = blockIdx.x / P.tiles_x, tile_x = blockIdx.x - tile_y * P.tiles_x;
   const int x = tile_x * kTW + (threadIdx.x & (kTW - 1)), y = tile_y * kTH + (threadIdx.x >> 6);
   if (x >= P.w || y >= P.h) return;
@@ -308,6 +329,12 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
     hist = hist && mo.prev_lum2 != nullptr;
     const float yc = lum(z);
     qc = yc * yc;
+  }
+  [[maybe_unused]] float bc = 0.0f;  // Spec: the chain length of the current pixel
+  if constexpr (Spec) {  // no history unless every sample of the pixel took a chain of the same length
+    const SpecArgs<true>& sp = ex;
+    bc = sp.cur_bounces[pi];
+    hist = hist && isfinite(bc) && bc >= 0.0f && bc == floorf(bc);
   }
 
   // the hit point relative to the previous centre, and its pixel in the previous camera
@@ -353,6 +380,10 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
       if constexpr (Mom) {  // one more term of the tap rule: a finite second moment
         lq = mo.prev_lum2 ? mo.prev_lum2[qi] : 0.0f;
         ok = ok && isfinite(lq);
+      }
+      if constexpr (Spec) {  // one more: the tap's chain is as long as the pixel's (a NaN fails)
+        const SpecArgs<true>& sp = ex;
+        ok = ok && sp.prev_bounces[qi] == bc;
       }
       V3 eq = {0.0f, 0.0f, 0.0f};
       float covq = 0.0f;
@@ -646,6 +677,7 @@ struct Moments {
   const rt_moments_opts* mopts;
   float* out_lum2;
   const rt_clip_opts* copts = nullptr;  // rt_reproject_clip's; NULL: no clipping, the moments entries' kernels
+  const rt_spec_planes* spec = nullptr;  // rt_reproject_spec's; NULL: no chain gate, the kernels without it
 };
 
 constexpr float kClipGamma = 0.75f;  // rt_clip_opts' default gamma (DESIGN.md section 22's sweep)
@@ -657,10 +689,20 @@ int resolve_moments(const char* who, bool emit, bool light, const rt_camera** ca
                     const rt_aov_emit** prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
                     const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts, const Moments& m,
                     const rt_frame* out, const rt_aov_emit* out_emit, TpParams* P, MomPlanes<true>* mo,
-                    ClipArgs<true>* cl) {
+                    ClipArgs<true>* cl, SpecArgs<true>* sp) {
   if (!m.out_lum2) return set_error(RT_ERR_INVALID, "%s: null out_lum2", who);
   const bool no_prev = !*prev;
   if (!no_prev && !m.prev_lum2) return set_error(RT_ERR_INVALID, "%s: prev without prev_lum2", who);
+  if (m.spec) {  // the specular entries' own: the chain lengths of both frames, inputs only
+    if (!m.spec->cur_bounces) return set_error(RT_ERR_INVALID, "%s: spec without cur_bounces", who);
+    if (!no_prev && !m.spec->prev_bounces) return set_error(RT_ERR_INVALID, "%s: prev without spec's prev_bounces", who);
+    const float* obs[6] = {out ? out->rgb : nullptr, out ? out->var : nullptr, out ? out->count : nullptr,
+                           light && out_emit ? out_emit->emission : nullptr,
+                           light && out_emit ? out_emit->coverage : nullptr, m.out_lum2};
+    for (const float* o : obs)
+      if (o && (o == m.spec->cur_bounces || (!no_prev && o == m.spec->prev_bounces)))
+        return set_error(RT_ERR_INVALID, "%s: a bounces plane is an out buffer", who);
+  }
   const rt_moments_opts mop = m.mopts ? *m.mopts : rt_moments_opts{};
   if (mop.radius < -1 || mop.radius > 8)
     return set_error(RT_ERR_INVALID, "%s: radius %d (-1: no spatial estimate; at most 8)", who, mop.radius);
@@ -708,6 +750,7 @@ int resolve_moments(const char* who, bool emit, bool light, const rt_camera** ca
   *mo = {no_prev ? nullptr : m.prev_lum2, m.out_lum2, mop.min_frames > 0.0f ? mop.min_frames : 4.0f,
          mop.radius == 0 ? 3 : mop.radius};
   if (m.copts) cl->gamma = m.copts->gamma > 0.0f ? m.copts->gamma : kClipGamma;
+  if (m.spec) *sp = {no_prev ? m.spec->cur_bounces : m.spec->prev_bounces, m.spec->cur_bounces};
   return RT_OK;
 }
 
@@ -716,8 +759,16 @@ int resolve_moments(const char* who, bool emit, bool light, const rt_camera** ca
 template <bool Emit, bool Light>
 void launch_as(unsigned tiles, hipStream_t s, const TpParams& P, const Planes& prev, const Planes& cur,
                const Planes& out, const EmitPlanes<Emit, Light>& em, const MomPlanes<true>* mom,
-               const ClipArgs<true>* clip) {
-  if (mom && clip) {  // the tile and its halo: 8 floats a pixel, 22 KB at radius 3, 51 KB at radius 8
+               const ClipArgs<true>* clip, const SpecArgs<true>* spec) {
+  if (mom && spec) {  // rt_reproject_spec's instances: the two branches below with the chain gate
+    if (clip) {
+      const int tw = kTW + 2 * mom->radius, th = kTH + 2 * mom->radius;
+      hipLaunchKernelGGL((k_reproject<Emit, Light, true, true, true>), dim3(tiles), dim3(256), (size_t)tw * th * 32,
+                         s, P, prev, cur, out, Extra<Emit, Light, true, true, true>{em, *mom, *clip, *spec});
+    } else
+      hipLaunchKernelGGL((k_reproject<Emit, Light, true, false, true>), dim3(tiles), dim3(256), 0, s, P, prev, cur,
+                         out, Extra<Emit, Light, true, false, true>{em, *mom, {}, *spec});
+  } else if (mom && clip) {  // the tile and its halo: 8 floats a pixel, 22 KB at radius 3, 51 KB at radius 8
     const int tw = kTW + 2 * mom->radius, th = kTH + 2 * mom->radius;
     hipLaunchKernelGGL((k_reproject<Emit, Light, true, true>), dim3(tiles), dim3(256), (size_t)tw * th * 32, s, P,
                        prev, cur, out, Extra<Emit, Light, true, true>{em, *mom, *clip});
@@ -733,18 +784,19 @@ void launch_as(unsigned tiles, hipStream_t s, const TpParams& P, const Planes& p
 // out_emit: the new history's light planes (rt_reproject_light's kernel), NULL for the others
 int launch(const TpParams& P, const Planes& prev, const Planes& cur, const Planes& out,
            const rt_aov_emit* prev_emit, const rt_aov_emit* cur_emit, const rt_aov_emit* out_emit, hipStream_t s,
-           const MomPlanes<true>* mom = nullptr, const ClipArgs<true>* clip = nullptr) {
+           const MomPlanes<true>* mom = nullptr, const ClipArgs<true>* clip = nullptr,
+           const SpecArgs<true>* spec = nullptr) {
   const unsigned tiles = (unsigned)((int64_t)P.tiles_x * ((P.h + kTH - 1) / kTH));  // < 2^31 / 3: w h is
   if (out_emit) {
     const EmitPlanes<true, true> em = {prev_emit->emission, prev_emit->coverage, cur_emit->emission,
                                        cur_emit->coverage,  out_emit->emission,  out_emit->coverage};
-    launch_as(tiles, s, P, prev, cur, out, em, mom, clip);
+    launch_as(tiles, s, P, prev, cur, out, em, mom, clip, spec);
   } else if (prev_emit) {
     const EmitPlanes<true, false> em = {prev_emit->emission, prev_emit->coverage, cur_emit->emission,
                                         cur_emit->coverage};
-    launch_as(tiles, s, P, prev, cur, out, em, mom, clip);
+    launch_as(tiles, s, P, prev, cur, out, em, mom, clip, spec);
   } else {
-    launch_as(tiles, s, P, prev, cur, out, EmitPlanes<false, false>{}, mom, clip);
+    launch_as(tiles, s, P, prev, cur, out, EmitPlanes<false, false>{}, mom, clip, spec);
   }
   HIP_OK(hipGetLastError());
   return RT_OK;
@@ -759,8 +811,9 @@ int reproject_device(const char* who, bool emit, bool light, const rt_camera* ca
   TpParams P;
   MomPlanes<true> mo;
   ClipArgs<true> cl;
+  SpecArgs<true> sp;
   int rc = m ? resolve_moments(who, emit, light, &cam_prev, &prev, &prev_emit, cam_cur, cur, cur_emit, w, h, opts,
-                               *m, out, out_emit, &P, &mo, &cl)
+                               *m, out, out_emit, &P, &mo, &cl, &sp)
              : resolve(who, emit, light, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out,
                        out_emit, &P);
   if (rc) return rc;
@@ -769,7 +822,7 @@ int reproject_device(const char* who, bool emit, bool light, const rt_camera* ca
   HIP_OK(hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   rc = launch(P, planes_of(prev), planes_of(cur), planes_of(out), prev_emit, cur_emit, out_emit, s, m ? &mo : nullptr,
-              m && m->copts ? &cl : nullptr);
+              m && m->copts ? &cl : nullptr, m && m->spec ? &sp : nullptr);
   HIP_OK(hipStreamSynchronize(s));
   return rc;
 }
@@ -783,9 +836,10 @@ int reproject_host(const char* who, bool emit, bool light, const rt_camera* cam_
   TpParams P;
   MomPlanes<true> mo;
   ClipArgs<true> cl;
+  SpecArgs<true> sp;
   const bool no_prev = m && !prev;
   int rc = m ? resolve_moments(who, emit, light, &cam_prev, &prev, &prev_emit, cam_cur, cur, cur_emit, w, h, opts,
-                               *m, out, out_emit, &P, &mo, &cl)
+                               *m, out, out_emit, &P, &mo, &cl, &sp)
              : resolve(who, emit, light, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out,
                        out_emit, &P);
   if (rc) return rc;
@@ -803,7 +857,10 @@ int reproject_host(const char* who, bool emit, bool light, const rt_camera* cam_
   constexpr int kOff[8] = {0, 3, 4, 5, 8, 9, 12, 13};
   const int nbuf = emit ? 7 : 5, per = kOff[nbuf];
   void* stg = nullptr;
-  if ((rc = g_stage.get(0, n * 4 * (2 * per + (m ? (light ? 11 : 7) : 0)), &stg, who))) return rc;
+  // (rt_reproject_spec: the two bounces planes behind the moments entries' planes, 2 floats more)
+  const bool spec = m && m->spec;
+  const int nmom = m ? (light ? 11 : 7) : 0;
+  if ((rc = g_stage.get(0, n * 4 * (2 * per + nmom + (spec ? 2 : 0)), &stg, who))) return rc;
   Planes d[2];
   rt_aov_emit de[2];
   const rt_frame* src[2] = {prev, cur};
@@ -839,8 +896,14 @@ int reproject_host(const char* who, bool emit, bool light, const rt_camera* cam_
     }
     mo.out_lum2 = cbase + 5 * n;
   }
+  if (spec) {
+    float* sbase = mbase + (size_t)nmom * n;
+    HIP_OK(hipMemcpyAsync(sbase + n, sp.cur_bounces, n * 4, hipMemcpyHostToDevice, s));
+    if (!no_prev) HIP_OK(hipMemcpyAsync(sbase, sp.prev_bounces, n * 4, hipMemcpyHostToDevice, s));
+    sp = {no_prev ? sbase + n : sbase, sbase + n};
+  }
   rc = launch(P, d[0], d[1], o, emit ? &de[0] : nullptr, emit ? &de[1] : nullptr, light ? &oe : nullptr, s,
-              m ? &mo : nullptr, m && m->copts ? &cl : nullptr);
+              m ? &mo : nullptr, m && m->copts ? &cl : nullptr, spec ? &sp : nullptr);
   if (!rc && m && hipMemcpyAsync(m->out_lum2, mo.out_lum2, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
     rc = set_error(RT_ERR_DEVICE, "%s: copy to host failed", who);
   if (!rc && ((o.rgb && hipMemcpyAsync(out->rgb, o.rgb, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess) ||
@@ -957,6 +1020,34 @@ int rt_reproject_clip(int mode, const rt_camera* cam_prev, const rt_frame* prev,
   if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
   const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
   const Moments m = {prev_lum2, mopts, out_lum2, copts};
+  return reproject_host(who, emit, light, cam_prev, prev, emit ? prev_emit : nullptr, cam_cur, cur,
+                        emit ? cur_emit : nullptr, w, h, opts, out, light ? out_emit : nullptr, &m);
+}
+
+int rt_reproject_spec_device(int mode, const rt_camera* cam_prev, const rt_frame* prev_dev,
+                             const rt_aov_emit* prev_emit_dev, const float* prev_lum2_dev, const rt_camera* cam_cur,
+                             const rt_frame* cur_dev, const rt_aov_emit* cur_emit_dev, int w, int h,
+                             const rt_reproject_opts* opts, const rt_moments_opts* mopts, const rt_clip_opts* copts,
+                             const rt_spec_planes* spec_dev, const rt_frame* out_dev, const rt_aov_emit* out_emit_dev,
+                             float* out_lum2_dev, int device, void* stream) {
+  const char* who = "rt_reproject_spec_device";
+  if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
+  const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
+  const Moments m = {prev_lum2_dev, mopts, out_lum2_dev, copts, spec_dev};
+  return reproject_device(who, emit, light, cam_prev, prev_dev, emit ? prev_emit_dev : nullptr, cam_cur, cur_dev,
+                          emit ? cur_emit_dev : nullptr, w, h, opts, out_dev, light ? out_emit_dev : nullptr, device,
+                          stream, &m);
+}
+
+int rt_reproject_spec(int mode, const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
+                      const float* prev_lum2, const rt_camera* cam_cur, const rt_frame* cur,
+                      const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
+                      const rt_moments_opts* mopts, const rt_clip_opts* copts, const rt_spec_planes* spec,
+                      const rt_frame* out, const rt_aov_emit* out_emit, float* out_lum2) {
+  const char* who = "rt_reproject_spec";
+  if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
+  const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
+  const Moments m = {prev_lum2, mopts, out_lum2, copts, spec};
   return reproject_host(who, emit, light, cam_prev, prev, emit ? prev_emit : nullptr, cam_cur, cur,
                         emit ? cur_emit : nullptr, w, h, opts, out, light ? out_emit : nullptr, &m);
 }

@@ -55,7 +55,7 @@ struct Args {
   unsigned long long seed = 1, tree_seed = 1;
   bool progress = false, stats = false, denoise = false, denoise_var = false, split_emitters = false;
   bool accum_features = false, temporal = false, temporal_emit = false, aov_media = false, aov_specular = false;
-  bool temporal_light = false, temporal_moments = false, temporal_clip = false;
+  bool temporal_light = false, temporal_moments = false, temporal_clip = false, temporal_specular = false;
   double clip_gamma = 0.0;
   long long frames = 0, spec_bounces = 0, moments_radius = 0;
   double moments_frames = 0.0;
@@ -108,9 +108,9 @@ std::vector<Flag> flags(Args& a) {
       {"seed", "render seed (Philox key)", Flag::U64, &a.seed, "1"},
       {"slices", "progress granularity: launches per render (0 = 20 with -progress)", Flag::INT,
        &a.slices, "0"},
-      {"spec-bounces", "with -aov-specular: the last vertex a specular chain may reach (0 = 8, at most 64)", Flag::INT,
+      {"spec-bounces", "with -aov-specular or -temporal-specular: the last vertex a specular chain may reach (0 = 8, at most 64)", Flag::INT,
        &a.spec_bounces, "0"},
-      {"spec-fuzz", "with -aov-specular: follow metals up to this fuzz (0 = perfect mirrors only)", Flag::F64,
+      {"spec-fuzz", "with -aov-specular or -temporal-specular: follow metals up to this fuzz (0 = perfect mirrors only)", Flag::F64,
        &a.spec_fuzz, "0"},
       {"split-emitters", "with -denoise or -denoise-var: keep directly seen lights out of the filter (emission split); -aov also writes PREFIX_emission.ppm and PREFIX_coverage.ppm",
        Flag::BOOL, &a.split_emitters, ""},
@@ -126,6 +126,8 @@ std::vector<Flag> flags(Args& a) {
        Flag::BOOL, &a.temporal_light, ""},
       {"temporal-moments", "with -temporal, -temporal-emit or -temporal-light: carry the second moment of luminance through the history and take the variance from it, or from a window of the frame (rt_reproject_moments); makes -denoise-var valid with -passes 1, e.g. -S 6 -passes 1 -accum-features -split-emitters -denoise-var -temporal-emit -temporal-moments -frames 8 -orbit 1",
        Flag::BOOL, &a.temporal_moments, ""},
+      {"temporal-specular", "with -temporal-moments and -accum-features: look the history of mirrors up through the virtual point (rt_reproject_spec): the accumulator also keeps the specular chains' normal, depth and bounces (see -spec-bounces and -spec-fuzz), which stand in for the first hit's in the history; not with -aov-media",
+       Flag::BOOL, &a.temporal_specular, ""},
       {"tree-seed", "seed of the scene builder's rand (main.go's math/rand)", Flag::U64,
        &a.tree_seed, "1"},
       {"until", "add passes until the image's relative standard error is <= E (at most -passes, default 1024)",
@@ -255,6 +257,7 @@ struct Job {
   bool temporal_light = false;  // the temporal stage through rt_reproject_light
   bool temporal_moments = false;  // ... through rt_reproject_moments in the stage's mode
   bool temporal_clip = false;     // ... through rt_reproject_clip instead
+  bool temporal_specular = false;  // ... through rt_reproject_spec, fed the accumulator's chain planes
   bool counts = false, aov = false, print_stats = false;
   bool numbered = false;  // -frames: frame k goes to the -o name with _00k before the extension
   int n_frames = 1;
@@ -283,6 +286,10 @@ int make_job(const Args& a, const char* prog, Job& j) {
       // (a positive G that rounds to 0 as a float would silently select the default)
       {!(a.clip_gamma >= 0.0) || !(a.clip_gamma <= 3.0e38) || (a.clip_gamma > 0.0 && (float)a.clip_gamma == 0.0f),
        "invalid value for flag -clip-gamma (0, or a finite positive float)"},
+      // -temporal-specular modifies -temporal-moments, and its planes are the accumulator's
+      {a.temporal_specular && !a.temporal_moments, "-temporal-specular needs -temporal-moments"},
+      {a.temporal_specular && !a.accum_features, "-temporal-specular needs -accum-features"},
+      {a.temporal_specular && a.aov_media, "-temporal-specular does not combine with -aov-media"},
       // ... unless the history brings one (-temporal-moments)
       {a.denoise_var && !(a.passes >= 2 || ((a.until > 0.0 || a.adaptive_set) && a.passes == 0) ||
                           (a.temporal_moments && a.passes == 1)),
@@ -304,7 +311,8 @@ int make_job(const Args& a, const char* prog, Job& j) {
       {a.aov_specular && a.aov_media, "-aov-specular does not combine with -aov-media"},
       {a.aov_specular && a.split_emitters, "-aov-specular does not combine with -split-emitters"},
       {a.aov_specular && a.accum_features, "-aov-specular does not combine with -accum-features"},
-      {(a.spec_bounces != 0 || a.spec_fuzz != 0.0) && !a.aov_specular, "-spec-bounces and -spec-fuzz need -aov-specular"},
+      {(a.spec_bounces != 0 || a.spec_fuzz != 0.0) && !(a.aov_specular || a.temporal_specular),
+       "-spec-bounces and -spec-fuzz need -aov-specular or -temporal-specular"},
       {a.spec_bounces < 0 || a.spec_bounces > 64 || !(a.spec_fuzz >= 0.0) || !(a.spec_fuzz <= 3.0e38),
        "invalid value for flag -spec-bounces (0..64) / -spec-fuzz (finite, >= 0)"},
       {a.frames < 0 || a.frames > 999 || !(a.orbit == a.orbit), "invalid value for flag -frames (0..999) / -orbit"},
@@ -320,6 +328,7 @@ int make_job(const Args& a, const char* prog, Job& j) {
   j.temporal_light = a.temporal_light;
   j.temporal_moments = a.temporal_moments;
   j.temporal_clip = a.temporal_clip;
+  j.temporal_specular = a.temporal_specular;
   j.temporal = a.temporal || a.temporal_emit || a.temporal_light;  // the same stage, through rt_reproject_emit / _light
   j.aov = !a.aov.empty();
   if (filtered || j.aov || j.temporal) j.source = a.accum_features ? Features::ACCUM : Features::PASS;
@@ -397,6 +406,8 @@ struct Ctx {
   // -temporal-moments: the history's second moment of luminance, and the frame's result (rt_reproject_moments
   // never writes into the current frame's buffers)
   std::vector<float> h_lum2, m_rgb, m_var, m_count, m_lum2;
+  // -temporal-specular: the frame's chain planes (the history keeps them in h_normal, h_depth and h_bounces)
+  std::vector<float> s_normal, s_depth, s_bounces, h_bounces;
   rt_camera h_cam;
   bool have_history = false;
 
@@ -444,7 +455,7 @@ struct Stats {
   const rt_accum_info* acc;    // -passes / -until / -adaptive, else null
   const rt_adapt_info* adapt;  // -adaptive, else null
   bool denoise_var, split_emitters, accum_features, temporal, temporal_emit, temporal_light, aov_media, aov_specular;
-  bool temporal_moments, temporal_clip;
+  bool temporal_moments, temporal_clip, temporal_specular;
   int frame;  // -frames, else -1
 };
 
@@ -487,6 +498,7 @@ std::string stats_json(const Stats& s) {
   if (s.temporal_light) b += "\"temporal_light\": 1, ";
   if (s.temporal_moments) b += "\"temporal_moments\": 1, ";
   if (s.temporal_clip) b += "\"temporal_clip\": 1, ";
+  if (s.temporal_specular) b += "\"temporal_specular\": 1, ";
   if (s.aov_media) b += "\"aov_media\": 1, ";
   if (s.aov_specular) b += "\"aov_specular\": 1, ";
   appendf(b, "\"wall_s\": %.3f}", s.wall_s);
@@ -609,7 +621,11 @@ int render(const Job& j, Ctx& c) {
     c.acc.reset(acc);
   }
   const uint32_t planes = RT_ACCUM_FEAT_GUIDES | (j.emit ? RT_ACCUM_FEAT_EMIT : 0u) | (j.media ? RT_ACCUM_FEAT_MEDIA : 0u);
-  if (j.accum_features && !s.ok("rt_accum_set_features", rt_accum_set_features(c.acc.get(), planes)))
+  const rt_aov_spec_opts chain = {(int32_t)j.a.spec_bounces, (float)j.a.spec_fuzz};
+  if (j.accum_features && j.temporal_specular) {
+    if (!s.ok("rt_accum_set_features_spec", rt_accum_set_features_spec(c.acc.get(), planes | RT_ACCUM_FEAT_SPEC, &chain)))
+      return fail(s.what, s.rc);
+  } else if (j.accum_features && !s.ok("rt_accum_set_features", rt_accum_set_features(c.acc.get(), planes)))
     return fail(s.what, s.rc);
 
   bool counts_failed = false;
@@ -662,6 +678,12 @@ int feature_planes(const Job& j, Ctx& c) {
     s.ok("rt_render_aov_emit", rt_render_aov_emit(c.sc, &c.cam, &c.o, n, &f, &fe, &sa));
   else
     s.ok("rt_render_aov", rt_render_aov(c.sc, &c.cam, &c.o, n, &f, &sa));
+  if (s.rc == RT_OK && j.temporal_specular) {  // (make_job: the accumulator's) the history's planes, not the filter's
+    c.s_normal.assign(3 * np, 0.0f), c.s_depth.assign(np, 0.0f), c.s_bounces.assign(np, 0.0f);
+    const rt_aov fc = {nullptr, c.s_normal.data(), c.s_depth.data(), nullptr};
+    const rt_aov_spec fb = {c.s_bounces.data()};
+    s.ok("rt_accum_resolve_aov_spec", rt_accum_resolve_aov_spec(c.acc.get(), &fc, &fb));
+  }
   c.ms_aov = ms_since(ta);
   return s.rc == RT_OK ? 0 : fail(s.what, s.rc);
 }
@@ -678,7 +700,11 @@ int temporal_step(const Job& j, Ctx& c) {
     const size_t n = c.n_px();
     c.m_rgb.resize(3 * n), c.m_var.resize(n), c.m_count.resize(n), c.m_lum2.resize(n);
     const rt_frame prev = {c.h_rgb.data(), c.h_var.data(), c.h_count.data(), c.h_normal.data(), c.h_depth.data(), 0.0f, 0};
-    const rt_frame cur = {c.rgb.data(), c.var.data(), nullptr, c.normal.data(), c.depth.data(), (float)c.ai.passes, 0};
+    // -temporal-specular: the chain's normal and depth in the first hit's place, in both frames
+    const bool sp = j.temporal_specular;
+    const rt_frame cur = {c.rgb.data(), c.var.data(), nullptr, sp ? c.s_normal.data() : c.normal.data(),
+                          sp ? c.s_depth.data() : c.depth.data(), (float)c.ai.passes, 0};
+    const rt_spec_planes chain = {c.h_bounces.data(), c.s_bounces.data()};
     const rt_frame res = {c.m_rgb.data(), c.m_var.data(), c.m_count.data(), nullptr, nullptr, 0.0f, 0};
     const rt_aov_emit prev_emit = {c.h_emission.data(), nullptr, c.h_coverage.data()};
     const rt_aov_emit cur_emit = {c.emission.data(), nullptr, c.coverage.data()};
@@ -688,7 +714,12 @@ int temporal_step(const Job& j, Ctx& c) {
     const bool hh = c.have_history;
     const rt_clip_opts co = {(float)j.a.clip_gamma};
     Call s;
-    if (j.temporal_clip)
+    if (sp)
+      s.ok("rt_reproject_spec",
+           rt_reproject_spec(mode, hh ? &c.h_cam : nullptr, hh ? &prev : nullptr, hh ? &prev_emit : nullptr,
+                             hh ? c.h_lum2.data() : nullptr, &c.cam, &cur, &cur_emit, w, h, nullptr, &mo,
+                             j.temporal_clip ? &co : nullptr, &chain, &res, &res_emit, c.m_lum2.data()));
+    else if (j.temporal_clip)
       s.ok("rt_reproject_clip",
            rt_reproject_clip(mode, hh ? &c.h_cam : nullptr, hh ? &prev : nullptr, hh ? &prev_emit : nullptr,
                              hh ? c.h_lum2.data() : nullptr, &c.cam, &cur, &cur_emit, w, h, nullptr, &mo, &co, &res,
@@ -719,6 +750,7 @@ int temporal_step(const Job& j, Ctx& c) {
     if (s.rc != RT_OK) return fail(s.what, s.rc);
   }
   c.h_rgb = c.rgb, c.h_var = c.var, c.h_count = c.count, c.h_normal = c.normal, c.h_depth = c.depth;
+  if (j.temporal_specular) c.h_normal = c.s_normal, c.h_depth = c.s_depth, c.h_bounces = c.s_bounces;
   if (j.temporal_emit) c.h_emission = c.emission, c.h_coverage = c.coverage;
   if (j.temporal_light) c.h_emission = c.l_emission, c.h_coverage = c.l_coverage;
   c.h_cam = c.cam;
@@ -785,7 +817,7 @@ int finish_frame(const Job& j, Ctx& c) {
   s.acc = j.accumulate ? &c.ai : nullptr;
   s.adapt = j.adaptive ? &c.adi : nullptr;
   s.denoise_var = j.filter == Filter::VAR, s.split_emitters = j.emit, s.accum_features = j.accum_features;
-  s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.temporal_light = j.temporal_light, s.temporal_moments = j.temporal_moments, s.temporal_clip = j.temporal_clip, s.aov_media = j.media, s.aov_specular = j.specular;
+  s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.temporal_light = j.temporal_light, s.temporal_moments = j.temporal_moments, s.temporal_clip = j.temporal_clip, s.temporal_specular = j.temporal_specular, s.aov_media = j.media, s.aov_specular = j.specular;
   s.frame = j.numbered ? c.frame : -1;
   const std::string js = stats_json(s);
   if (j.print_stats) fprintf(stderr, "%s\n", js.c_str());

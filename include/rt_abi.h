@@ -930,6 +930,36 @@ int rt_accum_resolve_aov_media(rt_accum* a, const rt_aov* out_host, const rt_aov
 int rt_accum_resolve_aov_media_device(rt_accum* a, const rt_aov* out_dev, const rt_aov_emit* emit_dev,
                                       const rt_aov_media* media_dev);
 
+/* Accumulator-owned chain sums (DESIGN.md "Temporal history for mirrors"): the planes of
+ * rt_render_aov_spec for exactly the camera samples the passes rendered, which rt_reproject_spec
+ * consumes.  Added without an ABI version change: detect by the symbols.
+ * RT_ACCUM_FEAT_SPEC is a plane group of its own that goes with GUIDES and/or EMIT: alone it is
+ * RT_ERR_INVALID, and so it is together with MEDIA (a chain traces no media).
+ * rt_accum_set_features_spec is rt_accum_set_features with the chain limits, and the one entry
+ * that takes the bit: spec_opts NULL means rt_render_aov_spec's defaults, with that entry's range
+ * checks (RT_ERR_INVALID for max_bounces < 0 or > 64, a negative or non-finite max_fuzz).
+ * rt_accum_set_features itself is unchanged: to it 8 stays an unknown bit, RT_ERR_INVALID, as every
+ * caller of it has seen so far; rt_accum_get_features reports the bit.  The same rules: only while the accumulator holds no pass; RT_ERR_OOM leaves the
+ * features off.  The group is 40 more bytes per pixel of the share (three fp64 normal sums, one
+ * fp64 depth sum, one 64-bit count of specular vertices) and 20 of staging; no albedo is kept.
+ * With the bit on, every rt_accum_add / rt_accum_add_active also runs, on the same stream for the
+ * same seed and pixels, the chain fold: rt_render_aov_spec's samples for ALL spp_sqrt^2 samples,
+ * summed per pass in fp32 in sample order, the pass's normal and depth sums added to the fp64
+ * planes and its specular vertices to the exact count.  The first hit is traced twice, once by the
+ * GUIDES / EMIT fold and once by the chain fold; an accumulator without the bit launches and
+ * allocates exactly what it did.
+ * rt_accum_resolve_aov_spec writes out->normal and out->depth as (float)(sum / N) with the division
+ * in fp64 and spec->bounces as (float)((double)vertices / N), zeros where n = 0.  RT_ERR_INVALID
+ * when out->albedo or out->material is not NULL, when the group is not enabled, or when no buffer
+ * is wanted.  One pass of seed s gives rt_render_aov_spec(n_samples = spp_sqrt^2, seed s) in normal
+ * and depth to within the rounding of that call's reciprocal (bit-equal when spp_sqrt^2 is a power
+ * of two); bounces always exactly, so a pixel all of whose samples passed k vertices resolves to
+ * exactly (float)k over any number of passes. */
+#define RT_ACCUM_FEAT_SPEC   8u   /* the specular chains' normal, depth and bounces; with GUIDES / EMIT, not MEDIA */
+int rt_accum_set_features_spec(rt_accum* a, uint32_t planes, const rt_aov_spec_opts* spec_opts);
+int rt_accum_resolve_aov_spec(rt_accum* a, const rt_aov* out_host, const rt_aov_spec* spec_host);
+int rt_accum_resolve_aov_spec_device(rt_accum* a, const rt_aov* out_dev, const rt_aov_spec* spec_dev);
+
 /* ------------------------------------------------------------------------ */
 /* Temporal reprojection (DESIGN.md "Temporal reprojection"): the previous   */
 /* frame's colour, variance and history length carried into a new camera     */
@@ -1231,6 +1261,54 @@ int rt_reproject_clip_device(int mode, const rt_camera* cam_prev, const rt_frame
                              const rt_clip_opts* copts, const rt_frame* out_dev,
                              const rt_aov_emit* out_emit_dev, float* out_lum2_dev, int device,
                              void* stream);
+
+/* rt_reproject_clip with the history of a mirror looked up through the virtual point (DESIGN.md
+ * "Temporal history for mirrors").  Added without an ABI version change: detect by the symbols.
+ * For a planar perfect mirror, C + D d^ (C the camera centre, d^ the unit camera ray, D the depth
+ * summed along the specular chain) is the mirror image of the chain's terminal vertex, and any
+ * other camera sees that vertex, through the mirror, at exactly its distance to that point.  So
+ * the whole history lookup of rt_reproject is kept, formula for formula (r = D + depth dir/|dir|,
+ * d' = |r|, the projection, the depth and normal tests against the tap), and is FED the chain's
+ * planes: the entry does not know what `normal` and `depth` hold.  The caller passes, for both
+ * frames, rt_accum_resolve_aov_spec's (or rt_render_aov_spec's) normal and depth; for a pixel with
+ * bounces == 0 these have the first hit's bits.
+ * The arguments are rt_reproject_clip's with one more struct after copts.  copts == NULL stays "no
+ * clamp" (rt_reproject_moments' definition).  spec == NULL: rt_reproject_clip's result bit for bit
+ * in every plane.  With spec given, the definition is rt_reproject_clip's with two changes:
+ *   current pixel: b_c = cur_bounces(p).  b is WHOLE when it is finite, >= 0 and b == floorf(b).
+ *     There is no history unless b_c is whole (a pixel whose samples took chains of different
+ *     lengths has meaningless mean planes); such a pixel takes the mode's no-history path exactly
+ *     as a miss does: v_s with K = 1, out_lum2 = q_c.
+ *   tap valid: the mode's rule, and b_q == b_c, an exact float comparison that a NaN fails.  The
+ *     tap's bounces value is used in the comparison only, never in arithmetic.  Without it a
+ *     mirror pixel's virtual point could accept a directly seen surface that lies at that depth.
+ * The window, the spatial estimate and the clip box gate on depth and normal as before.  On frames
+ * whose two bounces planes are all zero the result is rt_reproject_clip's bit for bit.
+ * RT_ERR_INVALID, before any device is touched: spec without cur_bounces; prev given without
+ * prev_bounces; a bounces plane that is an out buffer; then rt_reproject_clip's refusals.  The
+ * host entry stages 8 more bytes per pixel.  Two calls give identical bits.
+ * Not covered: curved mirrors (the virtual point is exact for planes only; the gates and the
+ * optional clip decide), glass whose samples mix reflection and refraction (fractional bounces:
+ * the history is dropped, not stale), fuzzy metals above the chain's max_fuzz, media along the
+ * chain, the emission split along the chain, moving geometry, defocus cameras. */
+typedef struct {
+  const float* prev_bounces;  /* [h][w]; required when prev is given */
+  const float* cur_bounces;   /* [h][w]; required */
+} rt_spec_planes;
+int rt_reproject_spec(int mode, const rt_camera* cam_prev, const rt_frame* prev,
+                      const rt_aov_emit* prev_emit, const float* prev_lum2,
+                      const rt_camera* cam_cur, const rt_frame* cur, const rt_aov_emit* cur_emit,
+                      int w, int h, const rt_reproject_opts* opts, const rt_moments_opts* mopts,
+                      const rt_clip_opts* copts, const rt_spec_planes* spec, const rt_frame* out,
+                      const rt_aov_emit* out_emit, float* out_lum2);
+int rt_reproject_spec_device(int mode, const rt_camera* cam_prev, const rt_frame* prev_dev,
+                             const rt_aov_emit* prev_emit_dev, const float* prev_lum2_dev,
+                             const rt_camera* cam_cur, const rt_frame* cur_dev,
+                             const rt_aov_emit* cur_emit_dev, int w, int h,
+                             const rt_reproject_opts* opts, const rt_moments_opts* mopts,
+                             const rt_clip_opts* copts, const rt_spec_planes* spec_dev,
+                             const rt_frame* out_dev, const rt_aov_emit* out_emit_dev,
+                             float* out_lum2_dev, int device, void* stream);
 
 /* Demo scenes mirroring main.go (by name or the main.go -S number).
  * names: book1, book2, book3, simple_light, quads, cornell, cornell_smoke, model
