@@ -26,7 +26,7 @@ __all__ = ["Tree", "Camera", "Scene", "Accumulator", "quantize", "format_ppm", "
            "demo_scene", "DEMO_SCENES", "build_bvh_boxes", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
            "format_ppm_device", "denoise", "denoise_device", "denoise_var", "denoise_var_device",
            "RtDenoiseVarOpts", "reproject", "reproject_device", "reproject_emit", "reproject_emit_device", "reproject_light", "reproject_light_device", "reproject_moments", "reproject_moments_device", "reproject_clip", "reproject_clip_device", "reproject_spec", "reproject_spec_device",
-           "Temporal"]
+           "Temporal", "Pipeline"]
 
 DEMO_SCENES = ("book1", "book2", "book3", "simple_light", "quads", "cornell", "cornell_smoke",
                "model")
@@ -1797,6 +1797,130 @@ class Temporal:
         if self._light:
             self.light = {"emission": s["emission"], "coverage": s["coverage"]}
         return s["rgb"], s["var"], s["count"]
+
+
+class _DevicePlane:
+    """A borrowed float32 device plane for torch.as_tensor (the CUDA array interface): no copy."""
+
+    def __init__(self, addr, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4", "data": (int(addr), False),
+                                         "version": 2, "strides": None}
+
+
+class Pipeline:
+    """rt_pipeline (DESIGN.md "Frame pipeline"): Temporal and the spatial filter behind one object
+    of the C ABI that owns its device buffers, the form a C or cgo client uses.  ``push(acc)``
+    does what ``temporal.push(acc)`` followed by ``denoise_var_device`` (filter="var"),
+    ``denoise_device`` (filter="plain") or nothing (filter=None) over ``acc.resolve_aov_device()``
+    does, bit for bit; temporal=False skips the history.  split_emitters, light_history, moments,
+    clip, specular: Temporal's flags.  filter_split (None: as split_emitters) selects the filter's
+    split entries.  opts: Temporal's (max_history, depth_tol, normal_tol, min_weight, min_frames,
+    var_radius, clip_gamma) and the filter's (iterations, demodulate (default on, as the filter
+    functions' with an albedo), sigma_lum or sigma_color, sigma_normal, sigma_depth)."""
+
+    _FILTERS = {None: _lib.RT_PIPE_FILTER_NONE, "plain": _lib.RT_PIPE_FILTER_PLAIN, "var": _lib.RT_PIPE_FILTER_VAR}
+
+    def __init__(self, temporal=True, split_emitters=False, light_history=False, moments=False, clip=False,
+                 specular=False, filter="var", filter_split=None, **opts):
+        self._p = None
+        if filter not in self._FILTERS:
+            raise ValueError(f"Pipeline: filter must be 'var', 'plain' or None, not {filter!r}")
+        if light_history and not split_emitters:
+            raise ValueError("Pipeline: light_history needs split_emitters=True (the history of the emission "
+                             "split's planes)")
+        o = _lib.RtPipelineOpts()
+        o.temporal, o.moments, o.clip, o.specular = int(bool(temporal)), int(bool(moments)), int(bool(clip)), \
+            int(bool(specular))
+        o.mode = (_lib.RT_REPROJECT_LIGHT if light_history else _lib.RT_REPROJECT_EMIT if split_emitters
+                  else _lib.RT_REPROJECT_PLAIN)
+        o.reproject = _reproject_opts(**{k: opts.pop(k) for k in ("max_history", "depth_tol", "normal_tol",
+                                                                  "min_weight") if k in opts})
+        o.mopts = _moments_opts(opts.pop("min_frames", 0.0), opts.pop("var_radius", 0))
+        o.copts = _lib.RtClipOpts(float(opts.pop("clip_gamma", 0.0)))
+        o.filter = self._FILTERS[filter]
+        o.split_emitters = int(bool(split_emitters if filter_split is None else filter_split))
+        if filter == "plain":
+            o.dopts = _denoise_opts(False, has_albedo=True, **opts)
+        else:
+            o.vopts = _denoise_opts(True, has_albedo=True, **opts)
+        p = C.c_void_p()
+        check(lib().rt_pipeline_create(C.byref(o), C.byref(p)))
+        self._p = p
+        self._destroy = lib().rt_pipeline_destroy  # usable at interpreter shutdown
+        self.opts = o
+
+    def close(self):
+        if getattr(self, "_p", None):
+            self._destroy(self._p)
+            self._p = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _h(self):
+        if not self._p:
+            raise ValueError("Pipeline is closed")
+        return self._p
+
+    def push(self, acc):
+        """The next frame: `acc` as Temporal.push's (rt_pipeline_push).  Returns self."""
+        check(lib().rt_pipeline_push(self._h(), acc._h()))
+        return self
+
+    def reset(self):
+        """Drop the history (a cut); the buffers stay."""
+        check(lib().rt_pipeline_reset(self._h()))
+
+    def info(self):
+        """rt_pipeline_info as a dict: width, height, device, frames, had_history, device_bytes,
+        allocations."""
+        i = _lib.RtPipelineInfo()
+        check(lib().rt_pipeline_info_get(self._h(), C.byref(i)))
+        d = _as_dict(i)
+        d.pop("_pad")
+        return d
+
+    def image(self):
+        """The last push's image as a host float32 [H, W, 3] array: one copy."""
+        i = self.info()
+        out = np.empty((i["height"], i["width"], 3), np.float32)
+        check(lib().rt_pipeline_image(self._h(), out.ctypes.data))
+        return out
+
+    def ppm(self):
+        """The last push's image as P3 text (bytes), formatted on the device: one copy."""
+        n = int(lib().rt_pipeline_ppm(self._h(), None, 0))
+        check(n)
+        buf = C.create_string_buffer(n)
+        check(int(lib().rt_pipeline_ppm(self._h(), buf, n)))
+        return buf.raw[:n]
+
+    def planes_device(self):
+        """The last push's planes as borrowed device pointers, valid until the push after the
+        next: a dict of zero-copy float32 torch tensors "rgb" [H, W, 3], "var", "count" [H, W],
+        "normal" [H, W, 3], "depth" and "image" [H, W, 3], with "emission" [H, W, 3] and "coverage"
+        where the pipeline holds them (the blended ones with light_history) and "lum2" with
+        moments.  Without torch: the same keys with (address, shape) pairs."""
+        f, e = _lib.RtFrame(), RtAovEmit()
+        lum2, image = C.c_void_p(), C.c_void_p()
+        check(lib().rt_pipeline_planes_device(self._h(), C.byref(f), C.byref(e), C.byref(lum2), C.byref(image)))
+        i = self.info()
+        h, w = i["height"], i["width"]
+        raw = {"rgb": (f.rgb, (h, w, 3)), "var": (f.var, (h, w)), "count": (f.count, (h, w)),
+               "normal": (f.normal, (h, w, 3)), "depth": (f.depth, (h, w)), "emission": (e.emission, (h, w, 3)),
+               "coverage": (e.coverage, (h, w)), "lum2": (lum2.value, (h, w)), "image": (image.value, (h, w, 3))}
+        raw = {k: v for k, v in raw.items() if v[0]}
+        try:
+            import torch
+        except ImportError:
+            return raw
+        dev = torch.device("cuda", i["device"])
+        return {k: torch.as_tensor(_DevicePlane(a, s), device=dev) for k, (a, s) in raw.items()}
 
 
 def device_count():

@@ -155,6 +155,20 @@ class RtSpecPlanes(C.Structure):  # rt_spec_planes: the chain lengths of rt_repr
 
 
 RT_REPROJECT_PLAIN, RT_REPROJECT_EMIT, RT_REPROJECT_LIGHT = 0, 1, 2
+RT_PIPE_FILTER_NONE, RT_PIPE_FILTER_PLAIN, RT_PIPE_FILTER_VAR = 0, 1, 2
+
+
+class RtPipelineOpts(C.Structure):  # rt_pipeline_opts (zeros in an option struct: the entries' defaults)
+    _fields_ = [("temporal", C.c_int32), ("mode", C.c_int32), ("moments", C.c_int32), ("clip", C.c_int32),
+                ("specular", C.c_int32), ("reproject", RtReprojectOpts), ("mopts", RtMomentsOpts),
+                ("copts", RtClipOpts), ("filter", C.c_int32), ("split_emitters", C.c_int32),
+                ("dopts", RtDenoiseOpts), ("vopts", RtDenoiseVarOpts)]
+
+
+class RtPipelineInfo(C.Structure):  # rt_pipeline_info
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("device", C.c_int32), ("frames", C.c_int32),
+                ("had_history", C.c_int32), ("_pad", C.c_int32), ("device_bytes", C.c_uint64),
+                ("allocations", C.c_uint64)]
 
 
 class RtAccumInfo(C.Structure):  # rt_accum_info
@@ -409,6 +423,15 @@ SIGNATURES = {
     "rt_accum_set_features_spec": (_I, [_P, C.c_uint32, C.POINTER(RtAovSpecOpts)]),
     "rt_accum_resolve_aov_spec": (_I, [_P, C.POINTER(RtAov), C.POINTER(RtAovSpec)]),
     "rt_accum_resolve_aov_spec_device": (_I, [_P, C.POINTER(RtAov), C.POINTER(RtAovSpec)]),
+    "rt_pipeline_create": (_I, [C.POINTER(RtPipelineOpts), C.POINTER(_P)]),
+    "rt_pipeline_destroy": (_I, [_P]),
+    "rt_pipeline_reset": (_I, [_P]),
+    "rt_pipeline_push": (_I, [_P, _P]),
+    "rt_pipeline_image": (_I, [_P, C.c_void_p]),
+    "rt_pipeline_ppm": (C.c_int64, [_P, C.c_void_p, C.c_int64]),
+    "rt_pipeline_planes_device": (_I, [_P, C.POINTER(RtFrame), C.POINTER(RtAovEmit), C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p)]),
+    "rt_pipeline_info_get": (_I, [_P, C.POINTER(RtPipelineInfo)]),
     "rt_demo_scene": (_I, [_P, C.c_char_p, C.c_char_p, C.POINTER(RtCamera), C.POINTER(_I),
                            C.POINTER(_I)]),
     "rt_demo_scene_name": (_I, [_I, C.POINTER(C.c_char_p)]),

@@ -751,6 +751,14 @@ void release_accums(Scene* s) {
   for (rt_accum* a : own) free_accum(a);
 }
 
+// rt_pipeline_push: a copy of what it needs (rt_host_units.h)
+int accum_view(rt_accum* a, AccumView* out) {
+  std::lock_guard<std::mutex> lk(a->mu);
+  *out = {a->cam,   (int32_t)a->W, (int32_t)a->rows, a->opts.device, a->opts.nranks, a->passes, a->features,
+          a->opts.stream ? a->opts.stream : (void*)a->own_stream.s};
+  return RT_OK;
+}
+
 }  // namespace rt
 
 extern "C" {

@@ -91,4 +91,17 @@ struct SpecPlanes {
 // two share the overflow stacks): k_aov_spec_fold for the same seed and pixels.
 int aov_spec_fold_enqueue(const SpecPlanes& S, bool px, const uint32_t* map, hipStream_t stream);
 
+// rt_accum.hip, for the frame pipeline (rt_pipeline.hip): what a push has to know of the
+// accumulator it is handed, copied under the accumulator's lock so that the pipeline keeps no
+// pointer into it.  cam is the camera rt_accum_create took; width x rows the share's image;
+// stream the one the accumulator's own entries enqueue on (the caller's, else its own, which
+// exists once a pass ran; valid for the duration of the call that asked).  Touches no device.
+struct AccumView {
+  rt_camera cam;
+  int32_t width, rows, device, nranks, passes;
+  uint32_t features;  // RT_ACCUM_FEAT_*
+  void* stream;
+};
+int accum_view(rt_accum* a, AccumView* out);
+
 }  // namespace rt

@@ -1,0 +1,454 @@
+// rt_pipeline.hip — rt_pipeline (include/rt_abi.h; DESIGN.md "Frame pipeline"): the owner, on the
+// device side of the C ABI, of what the low-sample pipeline keeps between frames.  A push is the
+// sequence rt.Temporal.push + the guides' resolve + the spatial filter, restated buffer for buffer
+// over the public _device entries: this unit launches no kernel and has no device code.  Its own
+// work is the bookkeeping (which plane lives in which set), two runtime fills and the copies to
+// the host.  Device memory comes from rt_hip_util.h's owners only.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <mutex>
+
+#include "rt_hip_util.h"
+#include "rt_host_units.h"
+
+namespace rt {
+namespace {
+
+constexpr size_t kAlign = 256;  // every plane starts on a 256-byte boundary of its allocation
+
+// a history set (DESIGN.md "Frame pipeline", the buffer plan): one allocation, carved
+struct HistSet {
+  DeviceBuffer buf;
+  float *rgb = nullptr, *var = nullptr, *count = nullptr, *normal = nullptr, *depth = nullptr;
+  float *emission = nullptr, *coverage = nullptr, *lum2 = nullptr, *bounces = nullptr;
+  float* image = nullptr;  // the filter's output for the frame whose blend the set holds
+};
+// the current frame's planes the moments entries may not have as out (the window reads them)
+struct CurSet {
+  DeviceBuffer buf;
+  float *rgb = nullptr, *var = nullptr, *emission = nullptr, *coverage = nullptr;
+};
+// the filter's guides that are no history plane, and rt_pipeline_ppm's text
+struct GuideSet {
+  DeviceBuffer buf;
+  float *albedo = nullptr, *surface_albedo = nullptr, *normal = nullptr, *depth = nullptr;
+  char* ppm = nullptr;
+  int64_t ppm_cap = 0;
+};
+
+// planes of `floats` floats each, one after the other from `base` (null: sizing only)
+struct Carver {
+  char* base;
+  size_t off = 0;
+  float* take(size_t floats) { return (float*)take_bytes(floats * sizeof(float)); }
+  char* take_bytes(size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += (bytes + kAlign - 1) / kAlign * kAlign;
+    return p;
+  }
+};
+
+}  // namespace
+}  // namespace rt
+
+struct rt_pipeline {
+  rt_pipeline_opts o{};
+  std::mutex mu;  // one call per pipeline at a time
+  // what the flags mean for the buffer plan
+  bool emit = false;      // the sets hold emission and coverage (a non-plain mode, or the split filter)
+  bool light = false;     // mode == RT_REPROJECT_LIGHT
+  bool filtered = false;  // filter != RT_PIPE_FILTER_NONE
+  bool split = false;     // the filter's _emit entry
+  // the buffers: all of one size on one device, dropped together when either changes
+  int32_t w = 0, h = 0, device = -1;
+  rt::HistSet set[2];
+  rt::CurSet cur;
+  rt::GuideSet guide;
+  rt::Stream own_stream;  // rt_pipeline_image's and rt_pipeline_ppm's
+  uint64_t allocations = 0;
+  // the history: which set holds it and the camera that saw it
+  int prev = -1;  // -1: none
+  rt_camera cam_prev{};
+  int last = -1;  // the set of the last successful push (rt_pipeline_image, _ppm, _planes_device)
+  int32_t frames = 0, had_history = 0;
+  int64_t ppm_len = -1;  // the length of the text in guide.ppm when it is `last`'s, else -1
+};
+
+namespace rt {
+namespace {
+
+size_t npix(const rt_pipeline* p) { return (size_t)p->w * (size_t)p->h; }
+
+size_t carve(const rt_pipeline* p, HistSet* s, char* base) {
+  const size_t n = npix(p);
+  Carver c{base};
+  s->rgb = c.take(3 * n), s->var = c.take(n), s->count = c.take(n), s->normal = c.take(3 * n), s->depth = c.take(n);
+  s->emission = p->emit ? c.take(3 * n) : nullptr;
+  s->coverage = p->emit ? c.take(n) : nullptr;
+  s->lum2 = p->o.moments ? c.take(n) : nullptr;
+  s->bounces = p->o.specular ? c.take(n) : nullptr;
+  s->image = p->filtered ? c.take(3 * n) : s->rgb;
+  return c.off;
+}
+size_t carve(const rt_pipeline* p, CurSet* s, char* base) {
+  const size_t n = npix(p);
+  Carver c{base};
+  s->rgb = c.take(3 * n), s->var = c.take(n);
+  s->emission = p->light ? c.take(3 * n) : nullptr;
+  s->coverage = p->light ? c.take(n) : nullptr;
+  return c.off;
+}
+// rt_format_ppm_device's text is at most the header and "255 255 255\n" per pixel
+int64_t ppm_bound(const rt_pipeline* p) { return 64 + 12 * (int64_t)npix(p); }
+size_t carve(const rt_pipeline* p, GuideSet* s, char* base) {
+  const size_t n = npix(p);
+  Carver c{base};
+  s->albedo = p->filtered ? c.take(3 * n) : nullptr;
+  s->surface_albedo = p->split ? c.take(3 * n) : nullptr;
+  s->normal = p->filtered && p->o.specular ? c.take(3 * n) : nullptr;
+  s->depth = p->filtered && p->o.specular ? c.take(n) : nullptr;
+  s->ppm_cap = ppm_bound(p);
+  s->ppm = c.take_bytes((size_t)s->ppm_cap);
+  return c.off;
+}
+
+// the group's allocation for the current size, made once (the pipeline's device is current)
+template <class Set>
+int ensure(rt_pipeline* p, Set* s) {
+  if (s->buf.p) return RT_OK;
+  const int rc = s->buf.grow(carve(p, s, nullptr), "rt_pipeline_push");
+  if (rc) return rc;
+  ++p->allocations;
+  carve(p, s, (char*)s->buf.p);
+  return RT_OK;
+}
+
+// frees everything with the owners' device current; the history goes with the buffers
+void drop_buffers(rt_pipeline* p) {
+  const bool any = p->set[0].buf.p || p->set[1].buf.p || p->cur.buf.p || p->guide.buf.p || p->own_stream.s;
+  if (any) {  // a pipeline that never pushed touches no device here either
+    DeviceGuard dg;
+    (void)hipSetDevice(p->device);
+    for (HistSet& s : p->set) s.buf.reset();
+    p->cur.buf.reset();
+    p->guide.buf.reset();
+    p->own_stream.reset();
+  }
+  p->prev = p->last = -1;
+  p->frames = p->had_history = 0;
+  p->ppm_len = -1;
+}
+
+bool bad(float f) { return !(f >= 0.0f) || !std::isfinite(f); }
+
+int check_opts(const rt_pipeline_opts& o) {
+  const char* who = "rt_pipeline_create";
+  if (o.mode < RT_REPROJECT_PLAIN || o.mode > RT_REPROJECT_LIGHT)
+    return set_error(RT_ERR_INVALID, "%s: mode %d (RT_REPROJECT_PLAIN, _EMIT or _LIGHT)", who, o.mode);
+  if (o.filter < RT_PIPE_FILTER_NONE || o.filter > RT_PIPE_FILTER_VAR)
+    return set_error(RT_ERR_INVALID, "%s: filter %d (RT_PIPE_FILTER_NONE, _PLAIN or _VAR)", who, o.filter);
+  if (o.clip && !o.moments)
+    return set_error(RT_ERR_INVALID, "%s: clip needs moments = 1 (the clamp is a step of rt_reproject_moments)", who);
+  if (o.specular && !o.moments)
+    return set_error(RT_ERR_INVALID, "%s: specular needs moments = 1 (the chain gate is a step of rt_reproject_moments)", who);
+  if (!o.temporal && (o.moments || o.clip || o.specular || o.mode != RT_REPROJECT_PLAIN))
+    return set_error(RT_ERR_INVALID,
+                     "%s: moments, clip, specular and a non-plain mode are the temporal stage's: set temporal = 1", who);
+  const rt_reproject_opts& r = o.reproject;
+  if (bad(r.max_history) || bad(r.depth_tol) || bad(r.normal_tol) || bad(r.min_weight))
+    return set_error(RT_ERR_INVALID, "%s: negative or non-finite reproject option (0 selects the default)", who);
+  if (o.mopts.radius < -1 || o.mopts.radius > 8)
+    return set_error(RT_ERR_INVALID, "%s: mopts.radius %d (-1: no spatial estimate; at most 8)", who, o.mopts.radius);
+  if (bad(o.mopts.min_frames) || (o.mopts.min_frames > 0.0f && o.mopts.min_frames < 2.0f))
+    return set_error(RT_ERR_INVALID, "%s: mopts.min_frames must be 0 (the default) or a finite number >= 2", who);
+  if (o.clip && o.mopts.radius == -1)
+    return set_error(RT_ERR_INVALID, "%s: clip needs the window: mopts.radius >= 0, not -1", who);
+  if (bad(o.copts.gamma))
+    return set_error(RT_ERR_INVALID, "%s: copts.gamma must be 0 (the default) or a finite positive number", who);
+  if (o.dopts.iterations < 0 || o.dopts.iterations > 8 || o.vopts.iterations < 0 || o.vopts.iterations > 8)
+    return set_error(RT_ERR_INVALID, "%s: filter iterations must be 0 (the default) or 1..8", who);
+  // the filters refuse a negative or NaN sigma (+Inf is theirs to take); so does the object
+  for (float f : {o.dopts.sigma_color, o.dopts.sigma_normal, o.dopts.sigma_depth, o.vopts.sigma_lum,
+                  o.vopts.sigma_normal, o.vopts.sigma_depth})
+    if (!(f >= 0.0f)) return set_error(RT_ERR_INVALID, "%s: negative or NaN filter sigma (0 selects the default)", who);
+  return RT_OK;
+}
+
+// set k as an rt_frame; count: the plane, or null with `scalar` for every pixel
+rt_frame frame_of(const float* rgb, const float* var, const float* count, const HistSet& nd, float scalar) {
+  return {(float*)rgb, (float*)var, (float*)count, nd.normal, nd.depth, scalar, 0};
+}
+
+// the temporal half: Temporal.push / Temporal._push_moments.  k: the set the history is not in
+int push_temporal(rt_pipeline* p, rt_accum* acc, const AccumView& v, int k, bool has_prev) {
+  const rt_pipeline_opts& o = p->o;
+  HistSet& s = p->set[k];
+  GuideSet& g = p->guide;
+  const bool mom = o.moments != 0;
+  int rc;
+  // the frame: without moments straight into the new history's set (out aliases cur); with them
+  // into the third set, since no out buffer of the moments entries may be one of cur's
+  float* frgb = mom ? p->cur.rgb : s.rgb;
+  float* fvar = mom ? p->cur.var : s.var;
+  if ((rc = rt_accum_resolve_device(acc, frgb, fvar))) return rc;
+  // the frame's emission and coverage: the kernel writes them only with the light history
+  float* femi = !p->emit ? nullptr : (mom && p->light) ? p->cur.emission : s.emission;
+  float* fcov = !p->emit ? nullptr : (mom && p->light) ? p->cur.coverage : s.coverage;
+  const rt_aov_emit emit_out = {femi, g.surface_albedo, fcov};
+  const rt_aov_emit* ep = p->emit ? &emit_out : nullptr;
+  if (o.specular) {  // the chain's normal, depth and bounces in the first hit's place
+    const rt_aov chain = {nullptr, s.normal, s.depth, nullptr};
+    const rt_aov_spec sp = {s.bounces};
+    if ((rc = rt_accum_resolve_aov_spec_device(acc, &chain, &sp))) return rc;
+    const rt_aov first = {g.albedo, g.normal, g.depth, nullptr};  // the filter's guides stay the first hit's
+    if (p->filtered || ep)
+      if ((rc = rt_accum_resolve_aov_device(acc, p->filtered ? &first : nullptr, ep))) return rc;
+  } else {
+    const rt_aov first = {g.albedo, s.normal, s.depth, nullptr};
+    if ((rc = rt_accum_resolve_aov_device(acc, &first, ep))) return rc;
+  }
+  const float passes = (float)v.passes;
+  const int mode = o.mode;
+  const HistSet& q = p->set[has_prev ? p->prev : k];
+  const rt_frame prev = frame_of(q.rgb, q.var, q.count, q, 0.0f);
+  const rt_aov_emit prev_emit = {q.emission, nullptr, q.coverage};
+  const rt_frame cur = frame_of(frgb, fvar, nullptr, s, passes);
+  const rt_aov_emit cur_emit = {femi, nullptr, fcov};
+  const rt_frame out = {s.rgb, s.var, s.count, nullptr, nullptr, 0.0f, 0};
+  const rt_aov_emit out_emit = {s.emission, nullptr, s.coverage};
+  if (!mom) {
+    if (!has_prev) {  // the frame itself with its count filled
+      uint32_t bits;
+      memcpy(&bits, &passes, sizeof bits);
+      HIP_OK(hipMemsetD32Async((hipDeviceptr_t)s.count, (int)bits, npix(p), (hipStream_t)v.stream));
+      HIP_OK(hipStreamSynchronize((hipStream_t)v.stream));
+      return RT_OK;
+    }
+    if (mode == RT_REPROJECT_LIGHT)
+      return rt_reproject_light_device(&p->cam_prev, &prev, &prev_emit, &v.cam, &cur, &cur_emit, p->w, p->h,
+                                       &o.reproject, &out, &out_emit, p->device, v.stream);
+    if (mode == RT_REPROJECT_EMIT)
+      return rt_reproject_emit_device(&p->cam_prev, &prev, &prev_emit, &v.cam, &cur, &cur_emit, p->w, p->h,
+                                      &o.reproject, &out, p->device, v.stream);
+    return rt_reproject_device(&p->cam_prev, &prev, &v.cam, &cur, p->w, p->h, &o.reproject, &out, p->device,
+                               v.stream);
+  }
+  // moments: a first frame goes through the entry too, with prev = NULL
+  const rt_camera* cp = has_prev ? &p->cam_prev : nullptr;
+  const rt_frame* pp = has_prev ? &prev : nullptr;
+  const rt_aov_emit* pe = has_prev && mode != RT_REPROJECT_PLAIN ? &prev_emit : nullptr;
+  const float* pl = has_prev ? q.lum2 : nullptr;
+  const rt_aov_emit* ce = mode != RT_REPROJECT_PLAIN ? &cur_emit : nullptr;
+  const rt_aov_emit* oe = mode == RT_REPROJECT_LIGHT ? &out_emit : nullptr;
+  const rt_clip_opts* co = o.clip ? &o.copts : nullptr;
+  if (o.specular) {
+    const rt_spec_planes sp = {has_prev ? q.bounces : nullptr, s.bounces};
+    return rt_reproject_spec_device(mode, cp, pp, pe, pl, &v.cam, &cur, ce, p->w, p->h, &o.reproject, &o.mopts, co,
+                                    &sp, &out, oe, s.lum2, p->device, v.stream);
+  }
+  if (o.clip)
+    return rt_reproject_clip_device(mode, cp, pp, pe, pl, &v.cam, &cur, ce, p->w, p->h, &o.reproject, &o.mopts, co,
+                                    &out, oe, s.lum2, p->device, v.stream);
+  return rt_reproject_moments_device(mode, cp, pp, pe, pl, &v.cam, &cur, ce, p->w, p->h, &o.reproject, &o.mopts,
+                                     &out, oe, s.lum2, p->device, v.stream);
+}
+
+// temporal = 0: the frame is the accumulator's resolve and count the pass count
+int push_frame(rt_pipeline* p, rt_accum* acc, const AccumView& v, int k) {
+  HistSet& s = p->set[k];
+  GuideSet& g = p->guide;
+  int rc;
+  if ((rc = rt_accum_resolve_device(acc, s.rgb, s.var))) return rc;
+  const rt_aov first = {g.albedo, s.normal, s.depth, nullptr};
+  const rt_aov_emit emit_out = {s.emission, g.surface_albedo, s.coverage};
+  if ((rc = rt_accum_resolve_aov_device(acc, &first, p->emit ? &emit_out : nullptr))) return rc;
+  const float passes = (float)v.passes;
+  uint32_t bits;
+  memcpy(&bits, &passes, sizeof bits);
+  HIP_OK(hipMemsetD32Async((hipDeviceptr_t)s.count, (int)bits, npix(p), (hipStream_t)v.stream));
+  HIP_OK(hipStreamSynchronize((hipStream_t)v.stream));
+  return RT_OK;
+}
+
+// the filter half: set k's blend into set k's image.  In the light mode the set's emission and
+// coverage are the blended ones; in every other they are the frame's own
+int push_filter(rt_pipeline* p, const AccumView& v, int k) {
+  const rt_pipeline_opts& o = p->o;
+  HistSet& s = p->set[k];
+  GuideSet& g = p->guide;
+  const bool own_guides = o.specular != 0;  // the set's normal and depth are the chain's then
+  const rt_aov feat = {g.albedo, own_guides ? g.normal : s.normal, own_guides ? g.depth : s.depth, nullptr};
+  const rt_aov_emit emit = {s.emission, g.surface_albedo, s.coverage};
+  if (o.filter == RT_PIPE_FILTER_VAR)
+    return p->split ? rt_denoise_var_emit_device(s.rgb, s.var, &feat, &emit, p->w, p->h, &o.vopts, s.image, nullptr,
+                                                 p->device, v.stream)
+                    : rt_denoise_var_device(s.rgb, s.var, &feat, p->w, p->h, &o.vopts, s.image, nullptr, p->device,
+                                            v.stream);
+  return p->split
+             ? rt_denoise_emit_device(s.rgb, &feat, &emit, p->w, p->h, &o.dopts, s.image, p->device, v.stream)
+             : rt_denoise_device(s.rgb, &feat, p->w, p->h, &o.dopts, s.image, p->device, v.stream);
+}
+
+// rt_pipeline_image's and rt_pipeline_ppm's prologue (p->mu held, DeviceGuard in the caller)
+int last_frame(rt_pipeline* p, const char* who, hipStream_t* stream) {
+  if (p->last < 0)
+    return set_error(RT_ERR_INVALID, "%s: no frame yet: call rt_pipeline_push first", who);
+  HIP_OK(hipSetDevice(p->device));
+  return p->own_stream.pick(nullptr, stream);
+}
+
+}  // namespace
+}  // namespace rt
+
+using namespace rt;
+
+extern "C" {
+
+int rt_pipeline_create(const rt_pipeline_opts* opts, rt_pipeline** out) {
+  if (!opts || !out) return set_error(RT_ERR_INVALID, "rt_pipeline_create: null opts/out");
+  *out = nullptr;
+  const int rc = check_opts(*opts);
+  if (rc) return rc;
+  rt_pipeline* p = new rt_pipeline();
+  p->o = *opts;
+  p->filtered = opts->filter != RT_PIPE_FILTER_NONE;
+  p->split = p->filtered && opts->split_emitters;
+  p->light = opts->mode == RT_REPROJECT_LIGHT;
+  p->emit = opts->mode != RT_REPROJECT_PLAIN || p->split;
+  *out = p;
+  return RT_OK;
+}
+
+int rt_pipeline_destroy(rt_pipeline* p) {
+  if (!p) return RT_OK;
+  {
+    std::lock_guard<std::mutex> lk(p->mu);  // a call in flight on another thread ends first
+    drop_buffers(p);
+  }
+  delete p;
+  return RT_OK;
+}
+
+int rt_pipeline_reset(rt_pipeline* p) {
+  if (!p) return set_error(RT_ERR_INVALID, "rt_pipeline_reset: null pipeline");
+  std::lock_guard<std::mutex> lk(p->mu);
+  p->prev = -1;
+  p->frames = 0;
+  return RT_OK;
+}
+
+int rt_pipeline_push(rt_pipeline* p, rt_accum* acc) {
+  const char* who = "rt_pipeline_push";
+  if (!p || !acc) return set_error(RT_ERR_INVALID, "%s: null pipeline/accumulator", who);
+  std::lock_guard<std::mutex> lk(p->mu);
+  const rt_pipeline_opts& o = p->o;
+  AccumView v;
+  int rc = accum_view(acc, &v);
+  if (rc) return rc;
+  if (v.passes < 1) return set_error(RT_ERR_INVALID, "%s: the accumulator holds no pass (rt_accum_add first)", who);
+  if (!v.features)
+    return set_error(RT_ERR_INVALID, "%s: needs an accumulator with features (rt_accum_set_features: the normal and "
+                     "depth guides)", who);
+  if (!(v.features & RT_ACCUM_FEAT_GUIDES))
+    return set_error(RT_ERR_INVALID, "%s: needs RT_ACCUM_FEAT_GUIDES (the normal and depth guides), the accumulator "
+                     "has planes 0x%x", who, v.features);
+  if (p->emit && !(v.features & RT_ACCUM_FEAT_EMIT))
+    return set_error(RT_ERR_INVALID, "%s: a non-plain mode and split_emitters need an accumulator with "
+                     "RT_ACCUM_FEAT_EMIT (rt_accum_set_features), this one has planes 0x%x", who, v.features);
+  if (o.specular && !(v.features & RT_ACCUM_FEAT_SPEC))
+    return set_error(RT_ERR_INVALID, "%s: specular needs an accumulator with RT_ACCUM_FEAT_SPEC "
+                     "(rt_accum_set_features_spec), this one has planes 0x%x", who, v.features);
+  if (v.nranks != 1)
+    return set_error(RT_ERR_INVALID, "%s: needs the whole image (an accumulator with nranks == 1, not %d)", who,
+                     v.nranks);
+  if (v.width <= 0 || v.rows <= 0 || (int64_t)v.width * v.rows >= ((int64_t)1 << 31) / 3)
+    return set_error(RT_ERR_INVALID, "%s: %d x %d image", who, v.width, v.rows);
+  if ((rc = device_ok(who, v.device))) return rc;
+
+  DeviceGuard dg;
+  if (v.width != p->w || v.rows != p->h || v.device != p->device) {  // another size or device: no history
+    drop_buffers(p);
+    p->w = v.width, p->h = v.rows, p->device = v.device;
+  }
+  HIP_OK(hipSetDevice(p->device));
+  const int k = p->last == 0 ? 1 : 0;  // never the set of the last frame: its planes stay valid for one more push
+  const bool has_prev = o.temporal && p->prev >= 0;
+  if ((rc = ensure(p, &p->set[k]))) return rc;
+  if (o.moments && (rc = ensure(p, &p->cur))) return rc;
+  if ((rc = ensure(p, &p->guide))) return rc;
+  rc = o.temporal ? push_temporal(p, acc, v, k, has_prev) : push_frame(p, acc, v, k);
+  if (rc) return rc;
+  if (p->filtered && (rc = push_filter(p, v, k))) return rc;
+  // the frame is complete: it becomes the history and the last frame
+  p->prev = o.temporal ? k : -1;
+  p->cam_prev = v.cam;
+  p->last = k;
+  p->ppm_len = -1;
+  p->had_history = has_prev;
+  ++p->frames;
+  return RT_OK;
+}
+
+int rt_pipeline_image(rt_pipeline* p, float* rgb_host) {
+  const char* who = "rt_pipeline_image";
+  if (!p || !rgb_host) return set_error(RT_ERR_INVALID, "%s: null pipeline/image", who);
+  std::lock_guard<std::mutex> lk(p->mu);
+  DeviceGuard dg;
+  hipStream_t s;
+  const int rc = last_frame(p, who, &s);
+  if (rc) return rc;
+  HIP_OK(hipMemcpyAsync(rgb_host, p->set[p->last].image, 3 * npix(p) * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  return RT_OK;
+}
+
+int64_t rt_pipeline_ppm(rt_pipeline* p, char* out_host, int64_t cap) {
+  const char* who = "rt_pipeline_ppm";
+  if (!p) return set_error(RT_ERR_INVALID, "%s: null pipeline", who);
+  if (cap < 0) return set_error(RT_ERR_INVALID, "%s: negative cap", who);
+  std::lock_guard<std::mutex> lk(p->mu);
+  DeviceGuard dg;
+  hipStream_t s;
+  const int rc = last_frame(p, who, &s);
+  if (rc) return rc;
+  if (p->ppm_len < 0) {  // the text is formatted once per frame, whoever asks first
+    const int64_t n =
+        rt_format_ppm_device(p->set[p->last].image, p->w, p->h, p->guide.ppm, p->guide.ppm_cap, p->device, s);
+    if (n < 0) return n;
+    p->ppm_len = n;
+  }
+  if (!out_host || cap == 0) return p->ppm_len;
+  if (p->ppm_len > cap) return set_error(RT_ERR_INVALID, "%s: buffer too small (%lld bytes, the text has %lld)", who,
+                                         (long long)cap, (long long)p->ppm_len);
+  HIP_OK(hipMemcpyAsync(out_host, p->guide.ppm, (size_t)p->ppm_len, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  return p->ppm_len;
+}
+
+int rt_pipeline_planes_device(rt_pipeline* p, rt_frame* blended, rt_aov_emit* light, float** lum2, float** image) {
+  const char* who = "rt_pipeline_planes_device";
+  if (!p) return set_error(RT_ERR_INVALID, "%s: null pipeline", who);
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->last < 0) return set_error(RT_ERR_INVALID, "%s: no frame yet: call rt_pipeline_push first", who);
+  const HistSet& s = p->set[p->last];
+  if (blended) *blended = {s.rgb, s.var, s.count, s.normal, s.depth, 0.0f, 0};
+  if (light) *light = {s.emission, nullptr, s.coverage};
+  if (lum2) *lum2 = s.lum2;
+  if (image) *image = s.image;
+  return RT_OK;
+}
+
+int rt_pipeline_info_get(rt_pipeline* p, rt_pipeline_info* out) {
+  if (!p || !out) return set_error(RT_ERR_INVALID, "rt_pipeline_info_get: null");
+  std::lock_guard<std::mutex> lk(p->mu);
+  *out = rt_pipeline_info{};
+  out->width = p->w, out->height = p->h, out->device = p->device;
+  out->frames = p->frames, out->had_history = p->had_history;
+  out->device_bytes = p->set[0].buf.bytes + p->set[1].buf.bytes + p->cur.buf.bytes + p->guide.buf.bytes;
+  out->allocations = p->allocations;
+  return RT_OK;
+}
+
+}  // extern "C"

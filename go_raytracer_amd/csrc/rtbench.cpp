@@ -16,6 +16,8 @@
 //   temporal_step   rt_reproject[_emit | _light | _moments | _clip] (the host entries: this client links no HIP runtime)
 //   filter          rt_denoise[_var][_emit]
 //   write_aovs      rt_format_ppm per plane
+//   pipeline_step   -on-device: rt_pipeline_push + rt_pipeline_ppm in place of the three stages above (the
+//                   frame stays on the device; what comes back is the image's text)
 //   finish_frame    rt_format_ppm, the statistics line (-cpuprofile has no pprof to drive on the
 //                   GPU path: the file receives the same line), rt_accum_destroy
 #include <unistd.h>
@@ -56,6 +58,7 @@ struct Args {
   bool progress = false, stats = false, denoise = false, denoise_var = false, split_emitters = false;
   bool accum_features = false, temporal = false, temporal_emit = false, aov_media = false, aov_specular = false;
   bool temporal_light = false, temporal_moments = false, temporal_clip = false, temporal_specular = false;
+  bool on_device = false;
   double clip_gamma = 0.0;
   long long frames = 0, spec_bounces = 0, moments_radius = 0;
   double moments_frames = 0.0;
@@ -100,6 +103,8 @@ std::vector<Flag> flags(Args& a) {
       {"moments-radius", "with -temporal-moments: the radius of the window for shorter histories (0 = 3, a 7 x 7 window; -1 = no window; at most 8)",
        Flag::INT, &a.moments_radius, "0"},
       {"o", "Specify a custom output file", Flag::STR, &a.out, "image.ppm"},
+      {"on-device", "with -accum-features and -passes / -until / -adaptive: keep the frame on the device: the temporal stage, the filter and the image's text go through one rt_pipeline (rt_pipeline_push, rt_pipeline_ppm) instead of the host entries; the files are the same bytes; not with -aov-media",
+       Flag::BOOL, &a.on_device, ""},
       {"orbit", "with -frames: turn the camera's look_from about the vup axis through look_at by DEG degrees per frame",
        Flag::F64, &a.orbit, "0"},
       {"passes", "render N passes of -spp samples each (seeds seed .. seed+N-1) and write their exact mean",
@@ -258,6 +263,7 @@ struct Job {
   bool temporal_moments = false;  // ... through rt_reproject_moments in the stage's mode
   bool temporal_clip = false;     // ... through rt_reproject_clip instead
   bool temporal_specular = false;  // ... through rt_reproject_spec, fed the accumulator's chain planes
+  bool on_device = false;  // temporal_step, filter and the image's text through one rt_pipeline
   bool counts = false, aov = false, print_stats = false;
   bool numbered = false;  // -frames: frame k goes to the -o name with _00k before the extension
   int n_frames = 1;
@@ -315,6 +321,9 @@ int make_job(const Args& a, const char* prog, Job& j) {
        "-spec-bounces and -spec-fuzz need -aov-specular or -temporal-specular"},
       {a.spec_bounces < 0 || a.spec_bounces > 64 || !(a.spec_fuzz >= 0.0) || !(a.spec_fuzz <= 3.0e38),
        "invalid value for flag -spec-bounces (0..64) / -spec-fuzz (finite, >= 0)"},
+      // -on-device: the pipeline's frames are an accumulator's with feature planes (first-hit sums, no media)
+      {a.on_device && !(a.accum_features && acc), "-on-device needs -accum-features and -passes, -until or -adaptive"},
+      {a.on_device && a.aov_media, "-on-device does not combine with -aov-media"},
       {a.frames < 0 || a.frames > 999 || !(a.orbit == a.orbit), "invalid value for flag -frames (0..999) / -orbit"},
   };
   for (const auto& c : checks)
@@ -338,8 +347,9 @@ int make_job(const Args& a, const char* prog, Job& j) {
   j.specular = a.aov_specular;
   j.filter = a.denoise_var ? Filter::VAR : a.denoise ? Filter::PLAIN : Filter::NONE;
   j.want_var = a.denoise_var || j.temporal;
+  j.on_device = a.on_device;
   j.counts = !a.counts.empty();
-  j.print_stats = a.stats || filtered || j.temporal;
+  j.print_stats = a.stats || filtered || j.temporal || a.on_device;
   j.numbered = a.frames > 0;
   j.n_frames = j.numbered ? (int)a.frames : 1;
   return -1;
@@ -358,6 +368,7 @@ struct Release {
   void operator()(rt_tree* p) const { rt_tree_destroy(p); }
   void operator()(rt_scene* p) const { rt_scene_destroy(p); }
   void operator()(rt_accum* p) const { rt_accum_destroy(p); }
+  void operator()(rt_pipeline* p) const { rt_pipeline_destroy(p); }
   void operator()(FILE* p) const { fclose(p); }
 };
 template <class T>
@@ -410,6 +421,10 @@ struct Ctx {
   std::vector<float> s_normal, s_depth, s_bounces, h_bounces;
   rt_camera h_cam;
   bool have_history = false;
+  // -on-device: the object that owns all of the above on the device, the frame's text and the time of both calls
+  Owned<rt_pipeline> pipe;
+  std::vector<char> text;
+  double ms_pipeline = 0.0;
 
   size_t n_px() const { return (size_t)d.width * d.height; }
   int spp() const { return d.spp_sqrt * d.spp_sqrt; }
@@ -456,6 +471,8 @@ struct Stats {
   const rt_adapt_info* adapt;  // -adaptive, else null
   bool denoise_var, split_emitters, accum_features, temporal, temporal_emit, temporal_light, aov_media, aov_specular;
   bool temporal_moments, temporal_clip, temporal_specular;
+  bool on_device;
+  double ms_pipeline;
   int frame;  // -frames, else -1
 };
 
@@ -501,6 +518,7 @@ std::string stats_json(const Stats& s) {
   if (s.temporal_specular) b += "\"temporal_specular\": 1, ";
   if (s.aov_media) b += "\"aov_media\": 1, ";
   if (s.aov_specular) b += "\"aov_specular\": 1, ";
+  if (s.on_device) appendf(b, "\"on_device\": 1, \"ms_pipeline\": %.3f, ", s.ms_pipeline);
   appendf(b, "\"wall_s\": %.3f}", s.wall_s);
   return b;
 }
@@ -557,7 +575,7 @@ rt_camera orbit_camera(const rt_camera& cam0, double degrees) {
 int begin_frame(const Job& j, Ctx& c, int frame) {
   c.frame = frame;
   c.aov_samples = 0;
-  c.ms_accum = c.ms_aov = c.ms_denoise = c.ms_reproject = 0.0;
+  c.ms_accum = c.ms_aov = c.ms_denoise = c.ms_reproject = c.ms_pipeline = 0.0;
   c.out_name = j.numbered ? frame_name(j.a.out, frame, true) : j.a.out;
   c.aov = j.numbered && j.aov ? frame_name(j.a.aov, frame, false) : j.a.aov;
   if (frame > 0) c.out.reset(fopen(c.out_name.c_str(), "wb"));
@@ -598,7 +616,9 @@ void add_passes(const Job& j, Ctx& c, std::atomic<int>& pass_no, Call& s) {
 
 // the accumulator's mean (and variance), its figures, and -counts: the passes per pixel as grey, count / max
 void resolve_passes(const Job& j, Ctx& c, Call& s, bool& counts_failed) {
-  if (s.ok("rt_accum_resolve", rt_accum_resolve(c.acc.get(), c.rgb.data(), j.want_var ? c.var.data() : nullptr)))
+  // -on-device: the mean stays where it is (rt_pipeline_push resolves it on the device)
+  if (s.ok("rt_accum_resolve", rt_accum_resolve(c.acc.get(), j.on_device ? nullptr : c.rgb.data(),
+                                                j.want_var && !j.on_device ? c.var.data() : nullptr)))
     s.ok("rt_accum_resolve", rt_accum_info_get(c.acc.get(), &c.ai));
   if (s.rc != RT_OK || !j.adaptive) return;
   if (!s.ok("rt_accum_adapt_info", rt_accum_adapt_info(c.acc.get(), &c.adi)) || !j.counts) return;
@@ -650,7 +670,7 @@ int render(const Job& j, Ctx& c) {
 // -denoise / -aov / -temporal: the feature planes of the same camera rays, from a feature pass at
 // min(spp, 16) samples or from the accumulator (the guides of every pass the pixel took)
 int feature_planes(const Job& j, Ctx& c) {
-  if (j.source == Features::NONE) return 0;
+  if (j.source == Features::NONE || (j.on_device && !j.aov)) return 0;  // -on-device: only -aov reads them on the host
   const size_t np = c.n_px();
   c.albedo.assign(3 * np, 0.0f), c.normal.assign(3 * np, 0.0f), c.depth.assign(np, 0.0f);
   c.emission.assign(j.emit ? 3 * np : 0, 0.0f), c.salbedo.assign(j.emit ? 3 * np : 0, 0.0f);
@@ -690,7 +710,7 @@ int feature_planes(const Job& j, Ctx& c) {
 
 // -temporal: the history into this frame's camera, then this frame as the new history
 int temporal_step(const Job& j, Ctx& c) {
-  if (!j.temporal) return 0;
+  if (!j.temporal || j.on_device) return 0;
   const auto tr = std::chrono::steady_clock::now();
   const int w = c.d.width, h = c.d.height;
   c.count.assign(c.n_px(), (float)c.ai.passes);
@@ -761,7 +781,7 @@ int temporal_step(const Job& j, Ctx& c) {
 
 // -denoise / -denoise-var, with -split-emitters their _emit entries; in place, the library's defaults
 int filter(const Job& j, Ctx& c) {
-  if (j.filter == Filter::NONE) return 0;
+  if (j.filter == Filter::NONE || j.on_device) return 0;
   const int w = c.d.width, h = c.d.height;
   const rt_aov f = c.guides();
   // -temporal-light: rgb was re-lit from the blended planes, so rgb - emission is the surface part
@@ -788,6 +808,40 @@ int filter(const Job& j, Ctx& c) {
   return s.rc == RT_OK ? 0 : fail(s.what, s.rc);
 }
 
+// -on-device: the object temporal_step and filter are restated in, with their options: the library's defaults,
+// the filters demodulating
+int make_pipeline(const Job& j, Ctx& c) {
+  if (!j.on_device) return 0;
+  rt_pipeline_opts po;
+  memset(&po, 0, sizeof po);
+  po.temporal = j.temporal;
+  po.mode = j.temporal_light ? RT_REPROJECT_LIGHT : j.temporal_emit ? RT_REPROJECT_EMIT : RT_REPROJECT_PLAIN;
+  po.moments = j.temporal_moments, po.clip = j.temporal_clip, po.specular = j.temporal_specular;
+  po.mopts.min_frames = (float)j.a.moments_frames, po.mopts.radius = (int32_t)j.a.moments_radius;
+  po.copts.gamma = (float)j.a.clip_gamma;
+  po.filter = j.filter == Filter::VAR ? RT_PIPE_FILTER_VAR : j.filter == Filter::PLAIN ? RT_PIPE_FILTER_PLAIN : RT_PIPE_FILTER_NONE;
+  po.split_emitters = j.emit;
+  po.dopts.demodulate = po.vopts.demodulate = 1;
+  rt_pipeline* p = nullptr;
+  const int rc = rt_pipeline_create(&po, &p);
+  if (rc != RT_OK) return fail("rt_pipeline_create", rc);
+  c.pipe.reset(p);
+  return 0;
+}
+
+// -on-device: the frame through the pipeline, and its text straight into the buffer the file is written from
+int pipeline_step(const Job& j, Ctx& c) {
+  if (!j.on_device) return 0;
+  const auto tp = std::chrono::steady_clock::now();
+  int rc = rt_pipeline_push(c.pipe.get(), c.acc.get());
+  if (rc != RT_OK) return fail("rt_pipeline_push", rc);
+  const int64_t n = rt_pipeline_ppm(c.pipe.get(), nullptr, 0);
+  c.text.resize((size_t)(n > 0 ? n : 0));
+  if (n < 0 || rt_pipeline_ppm(c.pipe.get(), c.text.data(), n) != n) return fail("rt_pipeline_ppm", (int)n);
+  c.ms_pipeline = ms_since(tp);
+  return 0;
+}
+
 // -aov: PREFIX_albedo, _normal as n * 0.5 + 0.5, _depth over the image maximum; the emission as it
 // is; coverage and scatter as grey, bounces over the image maximum
 int write_aovs(const Job& j, const Ctx& c) {
@@ -808,7 +862,15 @@ int write_aovs(const Job& j, const Ctx& c) {
 
 // camera.go:160 header + PrintColor per pixel, then main.go:477's single write; the statistics
 int finish_frame(const Job& j, Ctx& c) {
-  if (write_ppm(c.rgb, c.d.width, c.d.height, std::move(c.out), c.out_name.c_str())) return 1;
+  if (j.on_device) {  // the text is there already
+    Owned<FILE> f = std::move(c.out);
+    if (!f || fwrite(c.text.data(), 1, c.text.size(), f.get()) != c.text.size() || fclose(f.release()) != 0) {
+      fprintf(stderr, "rtbench: writing %s failed\n", c.out_name.c_str());
+      return 1;
+    }
+  } else if (write_ppm(c.rgb, c.d.width, c.d.height, std::move(c.out), c.out_name.c_str())) {
+    return 1;
+  }
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - c.t0).count();
   Stats s;
   s.st = &c.st, s.d = &c.d, s.scene = c.scene, s.wall_s = wall;
@@ -818,6 +880,7 @@ int finish_frame(const Job& j, Ctx& c) {
   s.adapt = j.adaptive ? &c.adi : nullptr;
   s.denoise_var = j.filter == Filter::VAR, s.split_emitters = j.emit, s.accum_features = j.accum_features;
   s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.temporal_light = j.temporal_light, s.temporal_moments = j.temporal_moments, s.temporal_clip = j.temporal_clip, s.temporal_specular = j.temporal_specular, s.aov_media = j.media, s.aov_specular = j.specular;
+  s.on_device = j.on_device, s.ms_pipeline = c.ms_pipeline;
   s.frame = j.numbered ? c.frame : -1;
   const std::string js = stats_json(s);
   if (j.print_stats) fprintf(stderr, "%s\n", js.c_str());
@@ -903,6 +966,7 @@ int main(int argc, char** argv) {
   c.o.mode = mode;
   c.o.trace_pixel = -1;
   c.o.progress_slices = (int32_t)(a.slices > 0 ? a.slices : a.progress ? 20 : 0);
+  if ((rc = make_pipeline(j, c)) != 0) return rc;
 
   for (int frame = 0; frame < j.n_frames; ++frame) {
     if ((rc = begin_frame(j, c, frame)) != 0) return rc;
@@ -910,6 +974,7 @@ int main(int argc, char** argv) {
     if ((rc = feature_planes(j, c)) != 0) return rc;
     if ((rc = temporal_step(j, c)) != 0) return rc;
     if ((rc = filter(j, c)) != 0) return rc;
+    if ((rc = pipeline_step(j, c)) != 0) return rc;
     if ((rc = write_aovs(j, c)) != 0) return rc;
     if ((rc = finish_frame(j, c)) != 0) return rc;
   }

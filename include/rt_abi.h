@@ -1310,6 +1310,95 @@ int rt_reproject_spec_device(int mode, const rt_camera* cam_prev, const rt_frame
                              const rt_frame* out_dev, const rt_aov_emit* out_emit_dev,
                              float* out_lum2_dev, int device, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Frame pipeline (DESIGN.md "Frame pipeline"): an object that owns, on the  */
+/* accumulator's device, everything the low-sample pipeline keeps between    */
+/* frames, so that a client with no device allocator of its own (C, cgo)     */
+/* runs resolve -> reproject -> filter -> PPM without the frame leaving the  */
+/* device.  Added without an ABI version change: detect by the symbols.      */
+/* ------------------------------------------------------------------------ */
+typedef struct rt_pipeline rt_pipeline;
+
+#define RT_PIPE_FILTER_NONE  0   /* the blended frame is the image */
+#define RT_PIPE_FILTER_PLAIN 1   /* rt_denoise[_emit]_device */
+#define RT_PIPE_FILTER_VAR   2   /* rt_denoise_var[_emit]_device */
+
+typedef struct {            /* 104 bytes, every field 4 bytes wide: no padding */
+  int32_t temporal;         /* 0: no history (resolve -> filter only); 1: reproject */
+  int32_t mode;             /* RT_REPROJECT_PLAIN | _EMIT | _LIGHT */
+  int32_t moments;          /* rt_reproject_moments_device: lum2 carried, the variance from the moments */
+  int32_t clip;             /* rt_reproject_clip_device (needs moments and a window) */
+  int32_t specular;         /* rt_reproject_spec_device over the accumulator's chain planes (needs moments) */
+  rt_reproject_opts reproject;  /* zeros: the entries' defaults */
+  rt_moments_opts   mopts;
+  rt_clip_opts      copts;  /* read with clip */
+  int32_t filter;           /* RT_PIPE_FILTER_* */
+  int32_t split_emitters;   /* the filter's _emit entry */
+  rt_denoise_opts     dopts;    /* RT_PIPE_FILTER_PLAIN's; zeros: the defaults (demodulate 0) */
+  rt_denoise_var_opts vopts;    /* RT_PIPE_FILTER_VAR's */
+} rt_pipeline_opts;
+
+typedef struct {            /* 40 bytes */
+  int32_t width, height, device;  /* of the buffers held: 0, 0, -1 before the first push */
+  int32_t frames;           /* pushes since create / reset / a dropped history */
+  int32_t had_history;      /* the last push found a history to reproject */
+  int32_t _pad;
+  uint64_t device_bytes;    /* held now */
+  uint64_t allocations;     /* device allocations made since create */
+} rt_pipeline_info;
+
+/* rt_pipeline_push(p, acc) runs, on the accumulator's device and stream, with exactly the
+ * aliasing rt.Temporal uses, the sequence a Python caller writes today:
+ *   the temporal half (temporal = 1): rt_accum_resolve_device and rt_accum_resolve_aov_device
+ *     (with specular: rt_accum_resolve_aov_spec_device for the history's normal, depth and
+ *     bounces) of acc, then the reproject entry the flags select with the stored history as prev,
+ *     the accumulator's camera (the one rt_accum_create took) as cam_cur and its pass count as
+ *     the current frame's count_scalar.  Two history sets are used in turn.  Without moments out
+ *     aliases cur, and a first frame is the frame itself with count filled; with moments the
+ *     frame is resolved into a third set (no out buffer of those entries may be cur's) and a
+ *     first frame goes through the entry with prev = NULL.  temporal = 0: the frame is the
+ *     accumulator's resolve, count the pass count.
+ *   the filter half: the entry `filter` and `split_emitters` select, over the blended rgb (and
+ *     var), guided by the albedo (split: surface_albedo), normal and depth of the FIRST hit
+ *     (rt_accum_resolve_aov_device; with specular these have buffers of their own), and in split
+ *     mode by the set's emission and coverage: the blended planes in RT_REPROJECT_LIGHT, the
+ *     frame's own otherwise.  It writes an image buffer of the object's own, never the history.
+ * Every stage is one of the public _device entries, so its definition, its argument checks and
+ * its bits are that entry's; the call blocks as they do.  Device memory is allocated on the first
+ * push and when the image size or the device changes (the history is then dropped, as after
+ * rt_pipeline_reset); once both history sets are warm no call allocates.  Per pixel and set 40
+ * bytes (+16 with emission and coverage, +4 lum2, +4 bounces, +12 the image), 16 (+16 in LIGHT)
+ * for the moments' third set, and 12..40 of guides plus 12 for rt_pipeline_ppm's text.
+ * The object holds no pointer into an accumulator or a scene between calls: destroying the scene
+ * first is legal.
+ * RT_ERR_INVALID from rt_pipeline_create, before any device is touched: a NULL argument; an unknown
+ * mode or filter; clip or specular without moments; clip with mopts.radius == -1; moments, clip,
+ * specular or a non-plain mode with temporal = 0; an option the entries refuse (negative or
+ * non-finite reproject options and gamma, radius outside -1..8, min_frames in (0, 2), iterations
+ * outside 0..8, a negative or NaN sigma).
+ * RT_ERR_INVALID from rt_pipeline_push, before anything is written: a NULL argument; an accumulator
+ * with no pass, with no features, without RT_ACCUM_FEAT_GUIDES, without RT_ACCUM_FEAT_EMIT when
+ * mode != PLAIN or split_emitters is set, without RT_ACCUM_FEAT_SPEC when specular is set, or of a
+ * row share (nranks != 1).  RT_ERR_UNSUPPORTED for a defocus camera comes from the reproject entry.
+ * A refused or failed push leaves the history and the last image as they were.
+ * rt_pipeline_image: the last push's image [h][w][3] in one copy of 12 bytes per pixel.
+ * rt_pipeline_ppm: rt_format_ppm_device of it into a device buffer of the object's, then one copy;
+ * returns the byte count; out_host NULL or cap 0 asks the size (the text is formatted once per
+ * frame); a cap smaller than the size is RT_ERR_INVALID, as rt_format_ppm's.
+ * rt_pipeline_planes_device: borrowed device pointers of the last push, valid until the push after
+ * the next (or a push at another size or on another device): blended rgb, var, count and the
+ * history's normal and depth; light: emission and coverage as the filter took them (NULL without
+ * them); lum2 (NULL without moments); image.  Any out pointer may be NULL.
+ * The last three return RT_ERR_INVALID before the first successful push. */
+int rt_pipeline_create(const rt_pipeline_opts* opts, rt_pipeline** out);   /* touches no device */
+int rt_pipeline_destroy(rt_pipeline* p);
+int rt_pipeline_reset(rt_pipeline* p);                                      /* a cut: drop the history, keep the buffers */
+int rt_pipeline_push(rt_pipeline* p, rt_accum* acc);
+int rt_pipeline_image(rt_pipeline* p, float* rgb_host);
+int64_t rt_pipeline_ppm(rt_pipeline* p, char* out_host, int64_t cap);
+int rt_pipeline_planes_device(rt_pipeline* p, rt_frame* blended, rt_aov_emit* light, float** lum2, float** image);
+int rt_pipeline_info_get(rt_pipeline* p, rt_pipeline_info* out);
+
 /* Demo scenes mirroring main.go (by name or the main.go -S number).
  * names: book1, book2, book3, simple_light, quads, cornell, cornell_smoke, model
  * The camera receives the scene's settings; override fields afterwards. */
