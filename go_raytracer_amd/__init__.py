@@ -1308,10 +1308,16 @@ def _frame_emit(who, name, f, h, w, conv, ptr):
 _LIGHT_KEYS = (("emission", 3), ("coverage", 0))
 
 
-def _reproject_host(emit, cam_prev, prev, cam_cur, cur, opts, light=False):
-    """reproject, reproject_emit (emit) and reproject_light (emit, light): rt_reproject[_emit |
-    _light] on host arrays"""
-    who = "reproject_light" if light else "reproject_emit" if emit else "reproject"
+_MOMENT_MODES = {"plain": 0, "emit": 1, "light": 2, 0: 0, 1: 1, 2: 2}
+
+
+def _moments_opts(min_frames=0.0, var_radius=0):
+    return _lib.RtMomentsOpts(float(min_frames), int(var_radius))
+
+
+def _host_buffers(who, cur):
+    """The host entries' buffers: (h, w, conv, ptr, new) for _frame over numpy arrays of the size
+    of cur["rgb"]; new(shape) is a new float32 array"""
     if not isinstance(cur, dict) or cur.get("rgb") is None:
         raise ValueError(f"{who}: cur['rgb'] is required")
     h, w = np.shape(cur["rgb"])[:2]
@@ -1321,39 +1327,12 @@ def _reproject_host(emit, cam_prev, prev, cam_cur, cur, opts, light=False):
         if a.shape != shape:
             raise ValueError(f"{who}: {name} must have shape {shape}, not {a.shape}")
         return a
-
-    def ptr(a):
-        return a.ctypes.data
-    fp, keep_p = _frame(who, "prev", prev, h, w, conv, ptr)
-    fc, keep_c = _frame(who, "cur", cur, h, w, conv, ptr)
-    if emit:
-        ep, keep_ep = _frame_emit(who, "prev", prev, h, w, conv, ptr)
-        ec, keep_ec = _frame_emit(who, "cur", cur, h, w, conv, ptr)
-    rgb, var, cnt = (np.empty((h, w, 3), np.float32), np.empty((h, w), np.float32),
-                     np.empty((h, w), np.float32))
-    fo = _lib.RtFrame(rgb.ctypes.data, var.ctypes.data, cnt.ctypes.data, None, None, 0.0, 0)
-    o = _reproject_opts(**opts)
-    cp, cc = cam_prev.to_c(), cam_cur.to_c()
-    if light:
-        emission, coverage = np.empty((h, w, 3), np.float32), np.empty((h, w), np.float32)
-        eo = RtAovEmit(emission.ctypes.data, None, coverage.ctypes.data)
-        check(lib().rt_reproject_light(C.byref(cp), C.byref(fp), C.byref(ep), C.byref(cc), C.byref(fc), C.byref(ec),
-                                       w, h, C.byref(o), C.byref(fo), C.byref(eo)))
-        return rgb, var, cnt, emission, coverage
-    if emit:
-        check(lib().rt_reproject_emit(C.byref(cp), C.byref(fp), C.byref(ep), C.byref(cc), C.byref(fc), C.byref(ec),
-                                      w, h, C.byref(o), C.byref(fo)))
-    else:
-        check(lib().rt_reproject(C.byref(cp), C.byref(fp), C.byref(cc), C.byref(fc), w, h, C.byref(o),
-                                 C.byref(fo)))
-    return rgb, var, cnt
+    return h, w, conv, (lambda a: a.ctypes.data), (lambda shape: np.empty(shape, np.float32))
 
 
-def _reproject_dev(emit, cam_prev, prev, cam_cur, cur, out, opts, light=False):
-    """reproject_device, reproject_emit_device (emit) and reproject_light_device (emit, light):
-    rt_reproject[_emit | _light]_device on torch tensors"""
+def _device_buffers(who, cur):
+    """The device entries' buffers: _host_buffers' tuple over torch tensors on cur["rgb"]'s device"""
     import torch
-    who = "reproject_light_device" if light else "reproject_emit_device" if emit else "reproject_device"
     if not isinstance(cur, dict) or not torch.is_tensor(cur.get("rgb")) or cur["rgb"].dim() != 3:
         raise ValueError(f"{who}: cur['rgb'] must be a [H, W, 3] tensor")
     a = cur["rgb"]
@@ -1366,37 +1345,94 @@ def _reproject_dev(emit, cam_prev, prev, cam_cur, cur, out, opts, light=False):
                              "on cur['rgb']'s device")
         return t
 
-    def ptr(t):
-        return t.data_ptr()
-    fp, keep_p = _frame(who, "prev", prev, h, w, conv, ptr)
-    fc, keep_c = _frame(who, "cur", cur, h, w, conv, ptr)
-    if emit:
-        ep, keep_ep = _frame_emit(who, "prev", prev, h, w, conv, ptr)
-        ec, keep_ec = _frame_emit(who, "cur", cur, h, w, conv, ptr)
-        keep_p = keep_p + keep_ep
+    def new(shape):
+        return torch.empty(shape, dtype=torch.float32, device=a.device)
+    return h, w, conv, (lambda t: t.data_ptr()), new
+
+
+def _reproject_call(family, device, mode, cam_prev, prev, cam_cur, cur, out, opts, min_frames=0.0, var_radius=0,
+                    gamma=None):
+    """The twelve reproject functions: rt_reproject[_emit | _light | _moments | _clip | _spec][_device]
+    by `family` ("plain", "emit", "light", whose mode is their own, or "moments", "clip", "spec" in
+    the caller's mode) on host arrays or, with device, torch tensors.  gamma None: copts == NULL"""
+    mom = family in ("moments", "clip", "spec")
+    who = "reproject" + ("" if family == "plain" else "_" + family) + ("_device" if device else "")
+    if not mom:
+        mode = ("plain", "emit", "light").index(family)
+    elif isinstance(mode, bool) or mode not in _MOMENT_MODES:
+        raise ValueError(f"{who}: mode must be 'plain', 'emit' or 'light' (or 0, 1, 2), not {mode!r}")
+    else:
+        mode = _MOMENT_MODES[mode]
+    emit, light = mode >= 1, mode == 2
+    h, w, conv, ptr, new = (_device_buffers if device else _host_buffers)(who, cur)
+    # the frames' structs.  The moments family checks frame by frame, cur first, and takes prev=None
+    # (no history at all); the older entries check both frames, then both emit structs
+    frames = {"prev": prev, "cur": cur}
+    kinds = (_frame, _frame_emit) if emit else (_frame,)
+    if mom:
+        steps = [(s, kind) for s in ("cur", "prev") if frames[s] is not None for kind in kinds]
+    else:
+        steps = [(s, kind) for kind in kinds for s in ("prev", "cur")]
+    c = {}  # (frame, kind) -> its struct
+    keep = {"prev": [], "cur": []}  # the buffers the structs point into
+    for s, kind in steps:
+        if mom and s == "prev" and kind is _frame and cam_prev is None:
+            raise ValueError(f"{who}: prev without cam_prev")
+        c[s, kind], bufs = kind(who, s, frames[s], h, w, conv, ptr)
+        keep[s] += bufs
+    lp = sp = None
+    if mom and prev is not None:
+        if prev.get("lum2") is None:
+            raise ValueError(f"{who}: prev['lum2'] is required (the lum2 plane an earlier call returned)")
+        keep["prev"].append(conv("prev['lum2']", prev["lum2"], (h, w)))
+        lp = ptr(keep["prev"][-1])
+    if family == "spec":  # the frames' chain lengths: inputs as the rest, never an out buffer
+        if cur.get("bounces") is None:
+            raise ValueError(f"{who}: cur['bounces'] is required (resolve_aov_spec / resolve_aov_spec_device)")
+        keep["cur"].append(conv("cur['bounces']", cur["bounces"], (h, w)))
+        sp = _lib.RtSpecPlanes(None, ptr(keep["cur"][-1]))
+        if prev is not None:
+            if prev.get("bounces") is None:
+                raise ValueError(f"{who}: prev['bounces'] is required (the bounces plane of the previous frame)")
+            keep["prev"].append(conv("prev['bounces']", prev["bounces"], (h, w)))
+            sp.prev_bounces = ptr(keep["prev"][-1])
     res = []
-    for k, ch in _FRAME_KEYS[:3] + (_LIGHT_KEYS if light else ()):
+    taken = {s: {ptr(p) for p in keep[s]} if device else () for s in keep}  # (a host call's out arrays are new)
+    for k, ch in _FRAME_KEYS[:3] + (_LIGHT_KEYS if light else ()) + ((("lum2", 0),) if mom else ()):
         shape = (h, w, ch) if ch else (h, w)
         t = (out or {}).get(k)
-        t = torch.empty(shape, dtype=torch.float32, device=a.device) if t is None else conv(f"out[{k!r}]", t, shape)
-        if any(t.data_ptr() == p.data_ptr() for p in keep_p):
+        t = new(shape) if t is None else conv(f"out[{k!r}]", t, shape)
+        if ptr(t) in taken["prev"]:
             raise ValueError(f"{who}: out[{k!r}] is a buffer of prev (the taps gather from prev)")
+        if mom and ptr(t) in taken["cur"]:
+            raise ValueError(f"{who}: out[{k!r}] is a buffer of cur (the window reads the current frame's "
+                             "neighbours)")
         res.append(t)
-    fo = _lib.RtFrame(*[t.data_ptr() for t in res[:3]], None, None, 0.0, 0)
-    o = _reproject_opts(**opts)
-    cp, cc = cam_prev.to_c(), cam_cur.to_c()
-    if light:
-        eo = RtAovEmit(res[3].data_ptr(), None, res[4].data_ptr())
-        check(lib().rt_reproject_light_device(C.byref(cp), C.byref(fp), C.byref(ep), C.byref(cc), C.byref(fc),
-                                              C.byref(ec), w, h, C.byref(o), C.byref(fo), C.byref(eo),
-                                              a.device.index or 0, _stream_of(a)))
-    elif emit:
-        check(lib().rt_reproject_emit_device(C.byref(cp), C.byref(fp), C.byref(ep), C.byref(cc), C.byref(fc),
-                                             C.byref(ec), w, h, C.byref(o), C.byref(fo), a.device.index or 0,
-                                             _stream_of(a)))
-    else:
-        check(lib().rt_reproject_device(C.byref(cp), C.byref(fp), C.byref(cc), C.byref(fc), w, h,
-                                        C.byref(o), C.byref(fo), a.device.index or 0, _stream_of(a)))
+    fo = _lib.RtFrame(*[ptr(t) for t in res[:3]], None, None, 0.0, 0)
+    eo = RtAovEmit(ptr(res[3]), None, ptr(res[4])) if light else None
+    o, mo = _reproject_opts(**opts), _moments_opts(min_frames, var_radius)
+    co = None
+    if mom and gamma is not None:
+        if gamma > 0 and C.c_float(gamma).value == 0.0:
+            raise ValueError(f"{who}: gamma {gamma!r} rounds to 0 as a float, which selects the default")
+        co = _lib.RtClipOpts(float(gamma))
+    r = lambda x: None if x is None else C.byref(x)  # noqa: E731
+    cp = cam_prev.to_c() if not mom or prev is not None else None
+    cc = cam_cur.to_c()
+    cp, fp, ep, cc, fc, ec, o, mo, co, sp, fo, eo = map(r, (
+        cp, c.get(("prev", _frame)), c.get(("prev", _frame_emit)), cc, c["cur", _frame], c.get(("cur", _frame_emit)),
+        o, mo, co, sp, fo, eo))
+    head = (mode, cp, fp, ep, lp, cc, fc, ec, w, h, o, mo)  # the moments family's, up to mopts
+    tail = (fo, eo, ptr(res[-1]))  # ... and from out on
+    args = {"plain": (cp, fp, cc, fc, w, h, o, fo),
+            "emit": (cp, fp, ep, cc, fc, ec, w, h, o, fo),
+            "light": (cp, fp, ep, cc, fc, ec, w, h, o, fo, eo),
+            "moments": head + tail,
+            "clip": head + (co,) + tail,
+            "spec": head + (co, sp) + tail}[family]
+    if device:
+        args += (cur["rgb"].device.index or 0, _stream_of(cur["rgb"]))
+    check(getattr(lib(), "rt_" + who)(*args))
     return tuple(res)
 
 
@@ -1408,7 +1444,7 @@ def reproject(cam_prev, prev, cam_cur, cur, **opts):
     "count" ([H, W], or one number for every pixel; missing: 0, which marks every pixel
     invalid).  opts: max_history, depth_tol, normal_tol, min_weight (0 = the library defaults).
     Returns new arrays (rgb, var, count)."""
-    return _reproject_host(False, cam_prev, prev, cam_cur, cur, opts)
+    return _reproject_call("plain", False, None, cam_prev, prev, cam_cur, cur, None, opts)
 
 
 def reproject_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
@@ -1416,7 +1452,7 @@ def reproject_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
     float32 tensor on cur["rgb"]'s device.  `out`: a dict of the "rgb" / "var" / "count" tensors
     to write (missing or None: a new tensor); they may be cur's own (in place), never prev's.
     Runs on the tensors' current stream and returns (rgb, var, count) after the work completes."""
-    return _reproject_dev(False, cam_prev, prev, cam_cur, cur, out, opts)
+    return _reproject_call("plain", True, None, cam_prev, prev, cam_cur, cur, out, opts)
 
 
 def reproject_emit(cam_prev, prev, cam_cur, cur, **opts):
@@ -1425,14 +1461,14 @@ def reproject_emit(cam_prev, prev, cam_cur, cur, **opts):
     accumulator with features="emit").  The history carries (rgb - emission) / (1 - coverage),
     the current frame's own emission is added back, and a fully covered pixel neither gives nor
     takes history.  Returns new arrays (rgb, var, count)."""
-    return _reproject_host(True, cam_prev, prev, cam_cur, cur, opts)
+    return _reproject_call("emit", False, None, cam_prev, prev, cam_cur, cur, None, opts)
 
 
 def reproject_emit_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
     """rt_reproject_emit_device on torch tensors: frames as reproject_emit's, every buffer a
     contiguous float32 tensor on cur["rgb"]'s device; `out` as reproject_device's (never a buffer
     of prev, its emission and coverage included)."""
-    return _reproject_dev(True, cam_prev, prev, cam_cur, cur, out, opts)
+    return _reproject_call("emit", True, None, cam_prev, prev, cam_cur, cur, out, opts)
 
 
 def reproject_light(cam_prev, prev, cam_cur, cur, **opts):
@@ -1443,7 +1479,7 @@ def reproject_light(cam_prev, prev, cam_cur, cur, **opts):
     light, where coverage is a few samples' estimate, gains from the history too.  Returns new
     arrays (rgb, var, count, emission, coverage): the last two are the next call's prev planes and
     the planes to hand the split filter."""
-    return _reproject_host(True, cam_prev, prev, cam_cur, cur, opts, light=True)
+    return _reproject_call("light", False, None, cam_prev, prev, cam_cur, cur, None, opts)
 
 
 def reproject_light_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
@@ -1451,126 +1487,7 @@ def reproject_light_device(cam_prev, prev, cam_cur, cur, out=None, **opts):
     contiguous float32 tensor on cur["rgb"]'s device; `out` as reproject_device's and may also name
     "emission" and "coverage" (cur's own allowed, never a buffer of prev).  Returns (rgb, var,
     count, emission, coverage)."""
-    return _reproject_dev(True, cam_prev, prev, cam_cur, cur, out, opts, light=True)
-
-
-_MOMENT_MODES = {"plain": 0, "emit": 1, "light": 2, 0: 0, 1: 1, 2: 2}
-
-
-def _moments_opts(min_frames=0.0, var_radius=0):
-    return _lib.RtMomentsOpts(float(min_frames), int(var_radius))
-
-
-def _reproject_moments(device, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts, gamma=None,
-                       spec=False):
-    """reproject_moments and reproject_moments_device (device): rt_reproject_moments[_device] on host
-    arrays or torch tensors; with gamma (not None) reproject_clip and reproject_clip_device:
-    rt_reproject_clip[_device]; with spec reproject_spec and reproject_spec_device:
-    rt_reproject_spec[_device], gamma None meaning its copts == NULL"""
-    who = ("reproject_spec" if spec else "reproject_clip" if gamma is not None else "reproject_moments") + (
-        "_device" if device else "")
-    if isinstance(mode, bool) or mode not in _MOMENT_MODES:
-        raise ValueError(f"{who}: mode must be 'plain', 'emit' or 'light' (or 0, 1, 2), not {mode!r}")
-    mode = _MOMENT_MODES[mode]
-    emit, light = mode >= 1, mode == 2
-    if device:
-        import torch
-        if not isinstance(cur, dict) or not torch.is_tensor(cur.get("rgb")) or cur["rgb"].dim() != 3:
-            raise ValueError(f"{who}: cur['rgb'] must be a [H, W, 3] tensor")
-        a = cur["rgb"]
-        h, w = a.shape[:2]
-
-        def conv(name, t, shape):
-            if (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous()
-                    or tuple(t.shape) != shape or t.device != a.device):
-                raise ValueError(f"{who}: {name} must be a contiguous float32 tensor of shape {shape} "
-                                 "on cur['rgb']'s device")
-            return t
-
-        def ptr(t):
-            return t.data_ptr()
-
-        def new(shape):
-            return torch.empty(shape, dtype=torch.float32, device=a.device)
-    else:
-        if not isinstance(cur, dict) or cur.get("rgb") is None:
-            raise ValueError(f"{who}: cur['rgb'] is required")
-        h, w = np.shape(cur["rgb"])[:2]
-
-        def conv(name, t, shape):
-            t = np.ascontiguousarray(t, dtype=np.float32)
-            if t.shape != shape:
-                raise ValueError(f"{who}: {name} must have shape {shape}, not {t.shape}")
-            return t
-
-        def ptr(t):
-            return t.ctypes.data
-
-        def new(shape):
-            return np.empty(shape, np.float32)
-    fc, keep_c = _frame(who, "cur", cur, h, w, conv, ptr)
-    ec = None
-    if emit:
-        ec, keep_ec = _frame_emit(who, "cur", cur, h, w, conv, ptr)
-        keep_c = keep_c + keep_ec
-    cp = fp = ep = lp = None
-    keep_p = []
-    if prev is not None:
-        if cam_prev is None:
-            raise ValueError(f"{who}: prev without cam_prev")
-        fp, keep_p = _frame(who, "prev", prev, h, w, conv, ptr)
-        if emit:
-            ep, keep_ep = _frame_emit(who, "prev", prev, h, w, conv, ptr)
-            keep_p = keep_p + keep_ep
-        if prev.get("lum2") is None:
-            raise ValueError(f"{who}: prev['lum2'] is required (the lum2 plane an earlier call returned)")
-        keep_p.append(conv("prev['lum2']", prev["lum2"], (h, w)))
-        lp, cp = ptr(keep_p[-1]), cam_prev.to_c()
-    sp = None
-    if spec:  # the frames' chain lengths: inputs as the rest, never an out buffer
-        if cur.get("bounces") is None:
-            raise ValueError(f"{who}: cur['bounces'] is required (resolve_aov_spec / resolve_aov_spec_device)")
-        keep_c = keep_c + [conv("cur['bounces']", cur["bounces"], (h, w))]
-        sp = _lib.RtSpecPlanes(None, ptr(keep_c[-1]))
-        if prev is not None:
-            if prev.get("bounces") is None:
-                raise ValueError(f"{who}: prev['bounces'] is required (the bounces plane of the previous frame)")
-            keep_p.append(conv("prev['bounces']", prev["bounces"], (h, w)))
-            sp.prev_bounces = ptr(keep_p[-1])
-    res = []
-    for k, ch in _FRAME_KEYS[:3] + (_LIGHT_KEYS if light else ()) + (("lum2", 0),):
-        shape = (h, w, ch) if ch else (h, w)
-        t = (out or {}).get(k)
-        t = new(shape) if t is None else conv(f"out[{k!r}]", t, shape)
-        if device:
-            if any(t.data_ptr() == p.data_ptr() for p in keep_p):
-                raise ValueError(f"{who}: out[{k!r}] is a buffer of prev (the taps gather from prev)")
-            if any(t.data_ptr() == p.data_ptr() for p in keep_c):
-                raise ValueError(f"{who}: out[{k!r}] is a buffer of cur (the window reads the current frame's "
-                                 "neighbours)")
-        res.append(t)
-    fo = _lib.RtFrame(*[ptr(t) for t in res[:3]], None, None, 0.0, 0)
-    eo = RtAovEmit(ptr(res[3]), None, ptr(res[4])) if light else None
-    o, mo = _reproject_opts(**opts), _moments_opts(min_frames, var_radius)
-    cc = cam_cur.to_c()
-    r = lambda x: None if x is None else C.byref(x)  # noqa: E731
-    args = [mode, r(cp), r(fp), r(ep), lp, r(cc), r(fc), r(ec), w, h, r(o), r(mo), r(fo), r(eo), ptr(res[-1])]
-    entry = "rt_reproject_moments"
-    if gamma is not None:
-        if gamma > 0 and C.c_float(gamma).value == 0.0:
-            raise ValueError(f"{who}: gamma {gamma!r} rounds to 0 as a float, which selects the default")
-        args.insert(12, r(_lib.RtClipOpts(float(gamma))))  # copts follows mopts
-        entry = "rt_reproject_clip"
-    if spec:
-        if gamma is None:
-            args.insert(12, None)
-        args.insert(13, r(sp))  # spec follows copts
-        entry = "rt_reproject_spec"
-    if device:
-        check(getattr(lib(), entry + "_device")(*args, a.device.index or 0, _stream_of(a)))
-    else:
-        check(getattr(lib(), entry)(*args))
-    return tuple(res)
+    return _reproject_call("light", True, None, cam_prev, prev, cam_cur, cur, out, opts)
 
 
 def reproject_moments(mode, cam_prev, prev, cam_cur, cur, min_frames=0.0, var_radius=0, **opts):
@@ -1583,7 +1500,7 @@ def reproject_moments(mode, cam_prev, prev, cam_cur, cur, min_frames=0.0, var_ra
     long (0: 4) takes the variance of its moments, any other the variance of the current frame's
     window of var_radius (0: 3; -1: none, the mode's own variance).  Returns new arrays (rgb, var,
     count, lum2), in the 'light' mode (rgb, var, count, emission, coverage, lum2)."""
-    return _reproject_moments(False, mode, cam_prev, prev, cam_cur, cur, None, min_frames, var_radius, opts)
+    return _reproject_call("moments", False, mode, cam_prev, prev, cam_cur, cur, None, opts, min_frames, var_radius)
 
 
 def reproject_moments_device(mode, cam_prev, prev, cam_cur, cur, out=None, min_frames=0.0, var_radius=0, **opts):
@@ -1591,7 +1508,7 @@ def reproject_moments_device(mode, cam_prev, prev, cam_cur, cur, out=None, min_f
     contiguous float32 tensor on cur["rgb"]'s device.  `out` as reproject_device's, with "lum2" (and
     "emission", "coverage" in the 'light' mode); here no out tensor may be one of cur's either: the
     window reads the current frame's neighbours.  Returns reproject_moments' tuple."""
-    return _reproject_moments(True, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts)
+    return _reproject_call("moments", True, mode, cam_prev, prev, cam_cur, cur, out, opts, min_frames, var_radius)
 
 
 def reproject_clip(mode, cam_prev, prev, cam_cur, cur, min_frames=0.0, var_radius=0, gamma=0.0, **opts):
@@ -1600,14 +1517,14 @@ def reproject_clip(mode, cam_prev, prev, cam_cur, cur, min_frames=0.0, var_radiu
     history"): a history the current frame contradicts, as a reflection that moved over a mirror
     whose depth and normal did not, is overruled.  Arguments and result as reproject_moments';
     gamma 0: the library default; var_radius = -1 is refused (there is no window)."""
-    return _reproject_moments(False, mode, cam_prev, prev, cam_cur, cur, None, min_frames, var_radius, opts, gamma)
+    return _reproject_call("clip", False, mode, cam_prev, prev, cam_cur, cur, None, opts, min_frames, var_radius, gamma)
 
 
 def reproject_clip_device(mode, cam_prev, prev, cam_cur, cur, out=None, min_frames=0.0, var_radius=0, gamma=0.0,
                           **opts):
     """rt_reproject_clip_device on torch tensors: reproject_moments_device with reproject_clip's
     gamma."""
-    return _reproject_moments(True, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts, gamma)
+    return _reproject_call("clip", True, mode, cam_prev, prev, cam_cur, cur, out, opts, min_frames, var_radius, gamma)
 
 
 def reproject_spec(mode, cam_prev, prev, cam_cur, cur, min_frames=0.0, var_radius=0, gamma=0.0, **opts):
@@ -1617,15 +1534,13 @@ def reproject_spec(mode, cam_prev, prev, cam_cur, cur, min_frames=0.0, var_radiu
     [H, W]: a pixel whose bounces value is not a whole number has no history, and a tap is taken
     only where its bounces value equals the pixel's.  Arguments and result as reproject_clip's;
     gamma=None: no clamp (reproject_moments' blend)."""
-    return _reproject_moments(False, mode, cam_prev, prev, cam_cur, cur, None, min_frames, var_radius, opts, gamma,
-                              spec=True)
+    return _reproject_call("spec", False, mode, cam_prev, prev, cam_cur, cur, None, opts, min_frames, var_radius, gamma)
 
 
 def reproject_spec_device(mode, cam_prev, prev, cam_cur, cur, out=None, min_frames=0.0, var_radius=0, gamma=0.0,
                           **opts):
     """rt_reproject_spec_device on torch tensors: reproject_clip_device with reproject_spec's frames."""
-    return _reproject_moments(True, mode, cam_prev, prev, cam_cur, cur, out, min_frames, var_radius, opts, gamma,
-                              spec=True)
+    return _reproject_call("spec", True, mode, cam_prev, prev, cam_cur, cur, out, opts, min_frames, var_radius, gamma)
 
 
 class Temporal:

@@ -479,8 +479,9 @@ DeviceScratch g_stacks, g_stage, g_count;  // (g_count: the specular mode's chai
 // no stream is released while the runtime unloads.
 std::vector<Stream>& g_streams = *new std::vector<Stream>();
 
-// A runtime tree id (0 record loop, 2 BVH2, 5 compressed BVH4, anything else BVH4) or flag as a
-// compile-time constant, f(std::integral_constant<..>{}): every kernel choice below goes through these
+// A runtime tree id (0 record loop, 2 BVH2, 5 compressed BVH4, anything else BVH4) as a compile-time
+// constant, f(std::integral_constant<..>{}): every kernel choice below goes through this and
+// rt_hip_util.h's with_flag
 template <class F>
 void with_tree(int tree, F&& f) {
   switch (tree) {
@@ -490,8 +491,6 @@ void with_tree(int tree, F&& f) {
     default: return f(std::integral_constant<int, 4>{});
   }
 }
-template <class F>
-void with_flag(bool v, F&& f) { v ? f(std::true_type{}) : f(std::false_type{}); }
 
 // What a launch of k_aov or k_aov_fold over npix pixels of a view needs beside its planes: the grid,
 // the Params with an overflow-stack column per launched thread, and what chooses the kernel instance

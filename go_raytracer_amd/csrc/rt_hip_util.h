@@ -1,5 +1,5 @@
 // rt_hip_util.h — the generic host-side HIP helpers of every HIP translation unit: the error
-// macro, the current-device guard, and the owners of device memory, streams and events.  No
+// macro, the current-device guard, with_flag, and the owners of device memory, streams and events.  No
 // other unit calls hipMalloc, hipFree, hipStreamCreate*, hipStreamDestroy, hipEventCreate* or
 // hipEventDestroy (DESIGN.md "Device resources"; tests/test_hip_resources.py).  What the render,
 // the accumulator and the feature pass declare for one another is rt_host_units.h.
@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "rt_internal.h"
 
@@ -42,6 +43,11 @@ inline int device_ok(const char* who, int device) {
     return set_error(RT_ERR_INVALID, "%s: device %d of %d", who, device, ndev);
   return RT_OK;
 }
+
+// A runtime flag as a compile-time constant, f(std::true_type{}) or f(std::false_type{}): how a
+// host path picks a kernel instance by its template arguments (rt_aov.hip, rt_temporal.hip)
+template <class F>
+void with_flag(bool v, F&& f) { v ? f(std::true_type{}) : f(std::false_type{}); }
 
 // ------------------------------------------------------------------- owners ---
 // Device memory, streams and events belong to one of the types below, and each frees what it

@@ -1,6 +1,7 @@
 // rt_host_units.h — what the host sides of the render (rt_render.hip), the feature pass
-// (rt_aov.hip), the accumulator (rt_accum.hip) and rt_render_multi (rt_multi.hip) declare for
-// one another.  The generic HIP helpers and the resource owners are rt_hip_util.h.
+// (rt_aov.hip), the accumulator (rt_accum.hip), rt_render_multi (rt_multi.hip), the temporal
+// reprojection (rt_temporal.hip) and the frame pipeline (rt_pipeline.hip) declare for one
+// another.  The generic HIP helpers and the resource owners are rt_hip_util.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -103,5 +104,36 @@ struct AccumView {
   void* stream;
 };
 int accum_view(rt_accum* a, AccumView* out);
+
+// rt_temporal.hip, for the frame pipeline (rt_pipeline.hip): what one of the twelve rt_reproject
+// entries asks for, as it came in, and the one path they all take.  name: the entry's, for the
+// messages; host: the buffers are host memory, staged through device 0 (device and stream are
+// not read); moments: an entry of the moments family (_moments, _clip, _spec), which has
+// prev_lum2, mopts and out_lum2, clips when copts is given and gates on the chain length when
+// spec is.  A struct the entry does not take is NULL, and so, for reproject_impl, is one the mode
+// does not take.  The fields stand in the order of rt_reproject_spec_device's parameters.
+struct ReprojectRequest {
+  const char* name;
+  bool host, moments;
+  int mode;  // RT_REPROJECT_PLAIN, _EMIT or _LIGHT
+  const rt_camera* cam_prev;
+  const rt_frame* prev;
+  const rt_aov_emit* prev_emit;
+  const float* prev_lum2;
+  const rt_camera* cam_cur;
+  const rt_frame* cur;
+  const rt_aov_emit* cur_emit;
+  int w, h;
+  const rt_reproject_opts* opts;
+  const rt_moments_opts* mopts;
+  const rt_clip_opts* copts;
+  const rt_spec_planes* spec;
+  const rt_frame* out;
+  const rt_aov_emit* out_emit;
+  float* out_lum2;
+  int device;
+  void* stream;
+};
+int reproject_impl(const ReprojectRequest& rq);
 
 }  // namespace rt

@@ -1,7 +1,8 @@
 // rt_pipeline.hip — rt_pipeline (include/rt_abi.h; DESIGN.md "Frame pipeline"): the owner, on the
 // device side of the C ABI, of what the low-sample pipeline keeps between frames.  A push is the
 // sequence rt.Temporal.push + the guides' resolve + the spatial filter, restated buffer for buffer
-// over the public _device entries: this unit launches no kernel and has no device code.  Its own
+// over the public _device entries and, for the reprojection, the one path they all take
+// (rt_temporal.hip's reproject_impl): this unit launches no kernel and has no device code.  Its own
 // work is the bookkeeping (which plane lives in which set), two runtime fills and the copies to
 // the host.  Device memory comes from rt_hip_util.h's owners only.
 #include <hip/hip_runtime.h>
@@ -181,6 +182,16 @@ rt_frame frame_of(const float* rgb, const float* var, const float* count, const 
   return {(float*)rgb, (float*)var, (float*)count, nd.normal, nd.depth, scalar, 0};
 }
 
+// a frame without history: set k's count filled with the accumulator's pass count
+int fill_count(rt_pipeline* p, const AccumView& v, int k) {
+  const float passes = (float)v.passes;
+  uint32_t bits;
+  memcpy(&bits, &passes, sizeof bits);
+  HIP_OK(hipMemsetD32Async((hipDeviceptr_t)p->set[k].count, (int)bits, npix(p), (hipStream_t)v.stream));
+  HIP_OK(hipStreamSynchronize((hipStream_t)v.stream));
+  return RT_OK;
+}
+
 // the temporal half: Temporal.push / Temporal._push_moments.  k: the set the history is not in
 int push_temporal(rt_pipeline* p, rt_accum* acc, const AccumView& v, int k, bool has_prev) {
   const rt_pipeline_opts& o = p->o;
@@ -209,50 +220,33 @@ int push_temporal(rt_pipeline* p, rt_accum* acc, const AccumView& v, int k, bool
     const rt_aov first = {g.albedo, s.normal, s.depth, nullptr};
     if ((rc = rt_accum_resolve_aov_device(acc, &first, ep))) return rc;
   }
-  const float passes = (float)v.passes;
-  const int mode = o.mode;
+  if (!mom && !has_prev) return fill_count(p, v, k);  // the frame itself
+  // the entry the configuration stands for: its name is in every message the call can raise
+  const char* name = o.specular ? "rt_reproject_spec_device"
+                     : o.clip   ? "rt_reproject_clip_device"
+                     : mom      ? "rt_reproject_moments_device"
+                     : o.mode == RT_REPROJECT_LIGHT ? "rt_reproject_light_device"
+                     : o.mode == RT_REPROJECT_EMIT  ? "rt_reproject_emit_device"
+                                                    : "rt_reproject_device";
   const HistSet& q = p->set[has_prev ? p->prev : k];
   const rt_frame prev = frame_of(q.rgb, q.var, q.count, q, 0.0f);
   const rt_aov_emit prev_emit = {q.emission, nullptr, q.coverage};
-  const rt_frame cur = frame_of(frgb, fvar, nullptr, s, passes);
+  const rt_frame cur = frame_of(frgb, fvar, nullptr, s, (float)v.passes);
   const rt_aov_emit cur_emit = {femi, nullptr, fcov};
   const rt_frame out = {s.rgb, s.var, s.count, nullptr, nullptr, 0.0f, 0};
   const rt_aov_emit out_emit = {s.emission, nullptr, s.coverage};
-  if (!mom) {
-    if (!has_prev) {  // the frame itself with its count filled
-      uint32_t bits;
-      memcpy(&bits, &passes, sizeof bits);
-      HIP_OK(hipMemsetD32Async((hipDeviceptr_t)s.count, (int)bits, npix(p), (hipStream_t)v.stream));
-      HIP_OK(hipStreamSynchronize((hipStream_t)v.stream));
-      return RT_OK;
-    }
-    if (mode == RT_REPROJECT_LIGHT)
-      return rt_reproject_light_device(&p->cam_prev, &prev, &prev_emit, &v.cam, &cur, &cur_emit, p->w, p->h,
-                                       &o.reproject, &out, &out_emit, p->device, v.stream);
-    if (mode == RT_REPROJECT_EMIT)
-      return rt_reproject_emit_device(&p->cam_prev, &prev, &prev_emit, &v.cam, &cur, &cur_emit, p->w, p->h,
-                                      &o.reproject, &out, p->device, v.stream);
-    return rt_reproject_device(&p->cam_prev, &prev, &v.cam, &cur, p->w, p->h, &o.reproject, &out, p->device,
-                               v.stream);
-  }
-  // moments: a first frame goes through the entry too, with prev = NULL
-  const rt_camera* cp = has_prev ? &p->cam_prev : nullptr;
-  const rt_frame* pp = has_prev ? &prev : nullptr;
-  const rt_aov_emit* pe = has_prev && mode != RT_REPROJECT_PLAIN ? &prev_emit : nullptr;
-  const float* pl = has_prev ? q.lum2 : nullptr;
-  const rt_aov_emit* ce = mode != RT_REPROJECT_PLAIN ? &cur_emit : nullptr;
-  const rt_aov_emit* oe = mode == RT_REPROJECT_LIGHT ? &out_emit : nullptr;
-  const rt_clip_opts* co = o.clip ? &o.copts : nullptr;
-  if (o.specular) {
-    const rt_spec_planes sp = {has_prev ? q.bounces : nullptr, s.bounces};
-    return rt_reproject_spec_device(mode, cp, pp, pe, pl, &v.cam, &cur, ce, p->w, p->h, &o.reproject, &o.mopts, co,
-                                    &sp, &out, oe, s.lum2, p->device, v.stream);
-  }
-  if (o.clip)
-    return rt_reproject_clip_device(mode, cp, pp, pe, pl, &v.cam, &cur, ce, p->w, p->h, &o.reproject, &o.mopts, co,
-                                    &out, oe, s.lum2, p->device, v.stream);
-  return rt_reproject_moments_device(mode, cp, pp, pe, pl, &v.cam, &cur, ce, p->w, p->h, &o.reproject, &o.mopts,
-                                     &out, oe, s.lum2, p->device, v.stream);
+  const rt_spec_planes sp = {has_prev ? q.bounces : nullptr, s.bounces};
+  // moments: a first frame goes through the entry too, with prev = NULL.  reproject_impl drops the
+  // emit structs the mode does not take
+  ReprojectRequest rq = {name, /*host=*/false, mom, o.mode};
+  if (has_prev) rq.cam_prev = &p->cam_prev, rq.prev = &prev, rq.prev_emit = &prev_emit, rq.prev_lum2 = q.lum2;
+  rq.cam_cur = &v.cam, rq.cur = &cur, rq.cur_emit = &cur_emit;
+  rq.w = p->w, rq.h = p->h;
+  rq.opts = &o.reproject;
+  rq.mopts = &o.mopts, rq.copts = o.clip ? &o.copts : nullptr, rq.spec = o.specular ? &sp : nullptr;
+  rq.out = &out, rq.out_emit = &out_emit, rq.out_lum2 = s.lum2;
+  rq.device = p->device, rq.stream = v.stream;
+  return reproject_impl(rq);
 }
 
 // temporal = 0: the frame is the accumulator's resolve and count the pass count
@@ -264,12 +258,7 @@ int push_frame(rt_pipeline* p, rt_accum* acc, const AccumView& v, int k) {
   const rt_aov first = {g.albedo, s.normal, s.depth, nullptr};
   const rt_aov_emit emit_out = {s.emission, g.surface_albedo, s.coverage};
   if ((rc = rt_accum_resolve_aov_device(acc, &first, p->emit ? &emit_out : nullptr))) return rc;
-  const float passes = (float)v.passes;
-  uint32_t bits;
-  memcpy(&bits, &passes, sizeof bits);
-  HIP_OK(hipMemsetD32Async((hipDeviceptr_t)s.count, (int)bits, npix(p), (hipStream_t)v.stream));
-  HIP_OK(hipStreamSynchronize((hipStream_t)v.stream));
-  return RT_OK;
+  return fill_count(p, v, k);
 }
 
 // the filter half: set k's blend into set k's image.  In the light mode the set's emission and

@@ -80,6 +80,7 @@
 #include <mutex>
 
 #include "rt_hip_util.h"
+#include "rt_host_units.h"
 
 namespace rt {
 namespace {
@@ -590,6 +591,9 @@ __global__ __launch_bounds__(256) void k_reproject(TpParams P, Planes prev, Plan
 }
 
 // ---- host -------------------------------------------------------------------------------------
+// The twelve entries fill a ReprojectRequest (rt_host_units.h) and reproject_impl runs the stages
+// reproject_check -> reproject_bind -> reproject_launch -> reproject_collect over one ReprojectJob,
+// as rt_aov.hip's entries do (DESIGN.md section 17 "Host path").
 
 std::mutex g_mu;        // one host-staged call at a time: the staging buffer is shared
 DeviceScratch g_stage;  // the host entries' staged frames (72 B per pixel, 104 with the emit planes;
@@ -600,16 +604,64 @@ V3 v3_diff(const double* a, const double* b) {  // the difference in fp64, then 
   return {(float)(a[0] - b[0]), (float)(a[1] - b[1]), (float)(a[2] - b[2])};
 }
 
-Planes planes_of(const rt_frame* f) { return {f->rgb, f->var, f->count, f->normal, f->depth}; }
+constexpr float kClipGamma = 0.75f;  // rt_clip_opts' default gamma (DESIGN.md section 22's sweep)
+
+// a frame's planes in staging order, rt_frame's five and the emit struct's emission and coverage,
+// and the floats per pixel of each
+constexpr int kFloats[7] = {3, 1, 1, 3, 1, 3, 1};
+struct UserFrame {
+  float* p[7];
+};
+UserFrame user_frame(const rt_frame* f, const rt_aov_emit* e) {
+  UserFrame u = {{f->rgb, f->var, f->count, f->normal, f->depth}};
+  if (e) u.p[5] = e->emission, u.p[6] = e->coverage;
+  return u;
+}
+
+// One plane of a call: the caller's pointer and the kernel's pointer to the plane, as read (src,
+// in) and as written (dst, out); cur's rgb is both when out goes over it.  A device entry's planes
+// are used in place.  A host entry's take `floats` per pixel of the staging buffer each, in the
+// order listed: dev is the slot, which an absent plane keeps, filled from src and copied back to dst
+struct TpPlane {
+  int floats;
+  const float* src;
+  const float** in;
+  float* dst;
+  float** out;
+  float* dev;
+};
+
+// What the stages derive from a request
+struct ReprojectJob {
+  bool emit, light;      // the mode: the _emit and _light kernels
+  bool mom, clip, spec;  // the moments family, and its copts and spec given
+  bool no_prev;          // the moments family's prev == NULL: no history at all
+  // the request's structs the mode takes (NULL: dropped), and the history the kernel reads: the
+  // current frame's when there is none (clamped addresses need memory behind them; never a tap)
+  const rt_camera* cam_prev;
+  const rt_frame* prev;
+  const rt_aov_emit *prev_emit, *cur_emit, *out_emit;
+  TpParams P;
+  MomPlanes<true> mo;
+  ClipArgs<true> cl;
+  SpecArgs<true> sp;
+  hipStream_t stream;
+  const float *d_prev[7], *d_cur[7];  // the kernel's planes, in UserFrame's order (reproject_bind)
+  float* d_out[7];
+  TpPlane planes[24];  // 14 of the frames, 7 of the moments family, 2 of spec
+  int n_planes;
+};
 
 // argument checks of every entry point (before any device is touched) -> the kernel's parameters;
 // emit: the _emit and _light entries, which need both rt_aov_emit with emission and coverage;
 // light: the _light entries, which need out_emit (NULL for the others)
-int resolve(const char* who, bool emit, bool light, const rt_camera* cam_prev, const rt_frame* prev,
-            const rt_aov_emit* prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
-            const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts, const rt_frame* out,
-            const rt_aov_emit* out_emit, TpParams* P) {
-  if (!cam_prev || !cam_cur) return set_error(RT_ERR_INVALID, "%s: null camera", who);
+int resolve(const ReprojectRequest& rq, ReprojectJob* j) {
+  const char* who = rq.name;
+  const bool emit = j->emit, light = j->light;
+  const rt_frame *prev = j->prev, *cur = rq.cur, *out = rq.out;
+  const rt_aov_emit *prev_emit = j->prev_emit, *cur_emit = j->cur_emit, *out_emit = j->out_emit;
+  const int w = rq.w, h = rq.h;
+  if (!j->cam_prev || !rq.cam_cur) return set_error(RT_ERR_INVALID, "%s: null camera", who);
   if (!prev || !cur || !out) return set_error(RT_ERR_INVALID, "%s: null frame", who);
   if (emit && (!prev_emit || !cur_emit)) return set_error(RT_ERR_INVALID, "%s: null emit", who);
   if (light && !out_emit) return set_error(RT_ERR_INVALID, "%s: null out_emit", who);
@@ -620,7 +672,7 @@ int resolve(const char* who, bool emit, bool light, const rt_camera* cam_prev, c
   if (!out->rgb && !out->var && !out->count) return set_error(RT_ERR_INVALID, "%s: out has no buffer", who);
   if (w <= 0 || h <= 0 || (int64_t)w * h >= ((int64_t)1 << 31) / 3)
     return set_error(RT_ERR_INVALID, "%s: %d x %d image", who, w, h);
-  const rt_reproject_opts o = opts ? *opts : rt_reproject_opts{};
+  const rt_reproject_opts o = rq.opts ? *rq.opts : rt_reproject_opts{};
   for (float f : {o.max_history, o.depth_tol, o.normal_tol, o.min_weight})
     if (!(f >= 0.0f) || !isfinite(f)) return set_error(RT_ERR_INVALID, "%s: negative or non-finite option", who);
   const float* const prev_bufs[5] = {prev->rgb, prev->var, prev->count, prev->normal, prev->depth};
@@ -644,14 +696,15 @@ int resolve(const char* who, bool emit, bool light, const rt_camera* cam_prev, c
                            who);
     }
   rt_camera_derived dp, dc;
-  int rc = rt_camera_derive(cam_prev, &dp);
-  if (rc == RT_OK) rc = rt_camera_derive(cam_cur, &dc);
+  int rc = rt_camera_derive(j->cam_prev, &dp);
+  if (rc == RT_OK) rc = rt_camera_derive(rq.cam_cur, &dc);
   if (rc != RT_OK) return rc;
   if (dp.width != w || dp.height != h || dc.width != w || dc.height != h)
     return set_error(RT_ERR_INVALID, "%s: cameras of %d x %d and %d x %d for a %d x %d image", who, dp.width,
                      dp.height, dc.width, dc.height, w, h);
   if (dp.defocus_angle > 0.0 || dc.defocus_angle > 0.0)
     return set_error(RT_ERR_UNSUPPORTED, "%s: a defocus camera measures depth from the lens sample", who);
+  TpParams* P = &j->P;
   P->w = w;
   P->h = h;
   P->tiles_x = (w + kTW - 1) / kTW;
@@ -671,71 +724,53 @@ int resolve(const char* who, bool emit, bool light, const rt_camera* cam_prev, c
   return RT_OK;
 }
 
-// rt_reproject_moments' arguments beyond its mode's
-struct Moments {
-  const float* prev_lum2;
-  const rt_moments_opts* mopts;
-  float* out_lum2;
-  const rt_clip_opts* copts = nullptr;  // rt_reproject_clip's; NULL: no clipping, the moments entries' kernels
-  const rt_spec_planes* spec = nullptr;  // rt_reproject_spec's; NULL: no chain gate, the kernels without it
-};
-
-constexpr float kClipGamma = 0.75f;  // rt_clip_opts' default gamma (DESIGN.md section 22's sweep)
-
-// the moments entries' own checks, then the mode's (resolve).  prev == NULL is no history at all:
-// the three prev arguments come back as the current frame's, which the kernel reads (clamped
-// addresses need memory behind them) and never takes a tap from
-int resolve_moments(const char* who, bool emit, bool light, const rt_camera** cam_prev, const rt_frame** prev,
-                    const rt_aov_emit** prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
-                    const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts, const Moments& m,
-                    const rt_frame* out, const rt_aov_emit* out_emit, TpParams* P, MomPlanes<true>* mo,
-                    ClipArgs<true>* cl, SpecArgs<true>* sp) {
-  if (!m.out_lum2) return set_error(RT_ERR_INVALID, "%s: null out_lum2", who);
-  const bool no_prev = !*prev;
-  if (!no_prev && !m.prev_lum2) return set_error(RT_ERR_INVALID, "%s: prev without prev_lum2", who);
-  if (m.spec) {  // the specular entries' own: the chain lengths of both frames, inputs only
-    if (!m.spec->cur_bounces) return set_error(RT_ERR_INVALID, "%s: spec without cur_bounces", who);
-    if (!no_prev && !m.spec->prev_bounces) return set_error(RT_ERR_INVALID, "%s: prev without spec's prev_bounces", who);
-    const float* obs[6] = {out ? out->rgb : nullptr, out ? out->var : nullptr, out ? out->count : nullptr,
-                           light && out_emit ? out_emit->emission : nullptr,
-                           light && out_emit ? out_emit->coverage : nullptr, m.out_lum2};
-    for (const float* o : obs)
-      if (o && (o == m.spec->cur_bounces || (!no_prev && o == m.spec->prev_bounces)))
+// the moments entries' own checks, ahead of the mode's (resolve).  prev == NULL is no history at
+// all: the job's history becomes the current frame, which the kernel reads and never takes a tap from
+int resolve_moments(const ReprojectRequest& rq, ReprojectJob* j) {
+  const char* who = rq.name;
+  const rt_frame *prev = rq.prev, *cur = rq.cur, *out = rq.out;
+  if (!rq.out_lum2) return set_error(RT_ERR_INVALID, "%s: null out_lum2", who);
+  const bool no_prev = !prev;
+  if (!no_prev && !rq.prev_lum2) return set_error(RT_ERR_INVALID, "%s: prev without prev_lum2", who);
+  const float* ob[5] = {out ? out->rgb : nullptr, out ? out->var : nullptr, out ? out->count : nullptr,
+                        j->out_emit ? j->out_emit->emission : nullptr, j->out_emit ? j->out_emit->coverage : nullptr};
+  if (j->spec) {  // the specular entries' own: the chain lengths of both frames, inputs only
+    if (!rq.spec->cur_bounces) return set_error(RT_ERR_INVALID, "%s: spec without cur_bounces", who);
+    if (!no_prev && !rq.spec->prev_bounces) return set_error(RT_ERR_INVALID, "%s: prev without spec's prev_bounces", who);
+    for (const float* o : {ob[0], ob[1], ob[2], ob[3], ob[4], (const float*)rq.out_lum2})
+      if (o && (o == rq.spec->cur_bounces || (!no_prev && o == rq.spec->prev_bounces)))
         return set_error(RT_ERR_INVALID, "%s: a bounces plane is an out buffer", who);
   }
-  const rt_moments_opts mop = m.mopts ? *m.mopts : rt_moments_opts{};
+  const rt_moments_opts mop = rq.mopts ? *rq.mopts : rt_moments_opts{};
   if (mop.radius < -1 || mop.radius > 8)
     return set_error(RT_ERR_INVALID, "%s: radius %d (-1: no spatial estimate; at most 8)", who, mop.radius);
   if (!(mop.min_frames >= 0.0f) || !isfinite(mop.min_frames) || (mop.min_frames > 0.0f && mop.min_frames < 2.0f))
     return set_error(RT_ERR_INVALID, "%s: min_frames must be 0 (the default) or a finite number >= 2", who);
-  if (m.copts) {  // the clip entries' own: the box is the window's
+  if (j->clip) {  // the clip entries' own: the box is the window's
     if (mop.radius == -1)
       return set_error(RT_ERR_INVALID, "%s: clipping needs the window (radius -1 has none)", who);
-    if (!(m.copts->gamma >= 0.0f) || !isfinite(m.copts->gamma))
+    if (!(rq.copts->gamma >= 0.0f) || !isfinite(rq.copts->gamma))
       return set_error(RT_ERR_INVALID, "%s: gamma must be 0 (the default) or a finite positive number", who);
   }
   const float* in[17] = {};  // every input plane
   int ni = 0;
   if (!no_prev) {
-    for (const float* b : {(const float*)(*prev)->rgb, (const float*)(*prev)->var, (const float*)(*prev)->count,
-                           (const float*)(*prev)->normal, (const float*)(*prev)->depth, m.prev_lum2})
+    for (const float* b : {(const float*)prev->rgb, (const float*)prev->var, (const float*)prev->count,
+                           (const float*)prev->normal, (const float*)prev->depth, rq.prev_lum2})
       in[ni++] = b;
-    if (emit && *prev_emit)
-      for (const float* b : {(*prev_emit)->emission, (*prev_emit)->surface_albedo, (*prev_emit)->coverage}) in[ni++] = b;
+    if (j->prev_emit)
+      for (const float* b : {j->prev_emit->emission, j->prev_emit->surface_albedo, j->prev_emit->coverage}) in[ni++] = b;
   }
   const int first_cur = ni;
   if (cur)
     for (const float* b : {cur->rgb, cur->var, cur->count, cur->normal, cur->depth}) in[ni++] = b;
-  if (emit && cur_emit)
-    for (const float* b : {cur_emit->emission, cur_emit->surface_albedo, cur_emit->coverage}) in[ni++] = b;
+  if (j->cur_emit)
+    for (const float* b : {j->cur_emit->emission, j->cur_emit->surface_albedo, j->cur_emit->coverage}) in[ni++] = b;
   for (int i = 0; i < ni; ++i)
-    if (in[i] == m.out_lum2) return set_error(RT_ERR_INVALID, "%s: out_lum2 aliases an input plane", who);
-  const float* ob[5] = {out ? out->rgb : nullptr, out ? out->var : nullptr, out ? out->count : nullptr,
-                        light && out_emit ? out_emit->emission : nullptr,
-                        light && out_emit ? out_emit->coverage : nullptr};
+    if (in[i] == rq.out_lum2) return set_error(RT_ERR_INVALID, "%s: out_lum2 aliases an input plane", who);
   for (const float* o : ob) {
-    if (o && o == m.out_lum2) return set_error(RT_ERR_INVALID, "%s: out_lum2 aliases a buffer of out", who);
-    if (o && !no_prev && o == m.prev_lum2)
+    if (o && o == rq.out_lum2) return set_error(RT_ERR_INVALID, "%s: out_lum2 aliases a buffer of out", who);
+    if (o && !no_prev && o == rq.prev_lum2)
       return set_error(RT_ERR_INVALID, "%s: out aliases prev_lum2 (the taps gather from prev)", who);
   }
   for (const float* o : ob)
@@ -743,229 +778,206 @@ int resolve_moments(const char* who, bool emit, bool light, const rt_camera** ca
       if (o && o == in[i])
         return set_error(RT_ERR_INVALID,
                          "%s: out aliases a buffer of cur (the window reads the current frame's neighbours)", who);
-  if (no_prev) *cam_prev = cam_cur, *prev = cur, *prev_emit = cur_emit;
-  const int rc = resolve(who, emit, light, *cam_prev, *prev, *prev_emit, cam_cur, cur, cur_emit, w, h, opts, out,
-                         out_emit, P);
-  if (rc) return rc;
-  *mo = {no_prev ? nullptr : m.prev_lum2, m.out_lum2, mop.min_frames > 0.0f ? mop.min_frames : 4.0f,
-         mop.radius == 0 ? 3 : mop.radius};
-  if (m.copts) cl->gamma = m.copts->gamma > 0.0f ? m.copts->gamma : kClipGamma;
-  if (m.spec) *sp = {no_prev ? m.spec->cur_bounces : m.spec->prev_bounces, m.spec->cur_bounces};
+  j->no_prev = no_prev;
+  if (no_prev) j->cam_prev = rq.cam_cur, j->prev = cur, j->prev_emit = j->cur_emit;
+  j->mo.min_frames = mop.min_frames > 0.0f ? mop.min_frames : 4.0f;
+  j->mo.radius = mop.radius == 0 ? 3 : mop.radius;
+  if (j->clip) j->cl.gamma = rq.copts->gamma > 0.0f ? rq.copts->gamma : kClipGamma;
   return RT_OK;
 }
 
-// one instance's launch; mom: rt_reproject_moments' arguments, NULL for the older entries' kernels;
-// clip: rt_reproject_clip's (with mom), NULL for every other entry's
-template <bool Emit, bool Light>
-void launch_as(unsigned tiles, hipStream_t s, const TpParams& P, const Planes& prev, const Planes& cur,
-               const Planes& out, const EmitPlanes<Emit, Light>& em, const MomPlanes<true>* mom,
-               const ClipArgs<true>* clip, const SpecArgs<true>* spec) {
-  if (mom && spec) {  // rt_reproject_spec's instances: the two branches below with the chain gate
-    if (clip) {
-      const int tw = kTW + 2 * mom->radius, th = kTH + 2 * mom->radius;
-      hipLaunchKernelGGL((k_reproject<Emit, Light, true, true, true>), dim3(tiles), dim3(256), (size_t)tw * th * 32,
-                         s, P, prev, cur, out, Extra<Emit, Light, true, true, true>{em, *mom, *clip, *spec});
-    } else
-      hipLaunchKernelGGL((k_reproject<Emit, Light, true, false, true>), dim3(tiles), dim3(256), 0, s, P, prev, cur,
-                         out, Extra<Emit, Light, true, false, true>{em, *mom, {}, *spec});
-  } else if (mom && clip) {  // the tile and its halo: 8 floats a pixel, 22 KB at radius 3, 51 KB at radius 8
-    const int tw = kTW + 2 * mom->radius, th = kTH + 2 * mom->radius;
-    hipLaunchKernelGGL((k_reproject<Emit, Light, true, true>), dim3(tiles), dim3(256), (size_t)tw * th * 32, s, P,
-                       prev, cur, out, Extra<Emit, Light, true, true>{em, *mom, *clip});
-  } else if (mom)
-    hipLaunchKernelGGL((k_reproject<Emit, Light, true, false>), dim3(tiles), dim3(256), 0, s, P, prev, cur, out,
-                       Extra<Emit, Light, true, false>{em, *mom, {}});
-  else
-    hipLaunchKernelGGL((k_reproject<Emit, Light, false, false>), dim3(tiles), dim3(256), 0, s, P, prev, cur, out,
-                       Extra<Emit, Light, false, false>{em, {}, {}});
+// Every argument test, in the entries' fixed order; no device is touched.  The mode decides which
+// of the request's emit structs are read: the others are dropped here, once
+int reproject_check(const ReprojectRequest& rq, ReprojectJob* j) {
+  if (rq.mode < RT_REPROJECT_PLAIN || rq.mode > RT_REPROJECT_LIGHT)
+    return set_error(RT_ERR_INVALID, "%s: mode %d", rq.name, rq.mode);
+  j->emit = rq.mode != RT_REPROJECT_PLAIN, j->light = rq.mode == RT_REPROJECT_LIGHT;
+  j->mom = rq.moments, j->clip = rq.moments && rq.copts, j->spec = rq.moments && rq.spec;
+  j->cam_prev = rq.cam_prev, j->prev = rq.prev;
+  j->prev_emit = j->emit ? rq.prev_emit : nullptr;
+  j->cur_emit = j->emit ? rq.cur_emit : nullptr;
+  j->out_emit = j->light ? rq.out_emit : nullptr;
+  if (int rc = j->mom ? resolve_moments(rq, j) : RT_OK) return rc;
+  return resolve(rq, j);
 }
 
-// emit: the frames' rt_aov_emit (both NULL for rt_reproject's kernel, both checked by resolve);
-// out_emit: the new history's light planes (rt_reproject_light's kernel), NULL for the others
-int launch(const TpParams& P, const Planes& prev, const Planes& cur, const Planes& out,
-           const rt_aov_emit* prev_emit, const rt_aov_emit* cur_emit, const rt_aov_emit* out_emit, hipStream_t s,
-           const MomPlanes<true>* mom = nullptr, const ClipArgs<true>* clip = nullptr,
-           const SpecArgs<true>* spec = nullptr) {
-  const unsigned tiles = (unsigned)((int64_t)P.tiles_x * ((P.h + kTH - 1) / kTH));  // < 2^31 / 3: w h is
-  if (out_emit) {
-    const EmitPlanes<true, true> em = {prev_emit->emission, prev_emit->coverage, cur_emit->emission,
-                                       cur_emit->coverage,  out_emit->emission,  out_emit->coverage};
-    launch_as(tiles, s, P, prev, cur, out, em, mom, clip, spec);
-  } else if (prev_emit) {
-    const EmitPlanes<true, false> em = {prev_emit->emission, prev_emit->coverage, cur_emit->emission,
-                                        cur_emit->coverage};
-    launch_as(tiles, s, P, prev, cur, out, em, mom, clip, spec);
-  } else {
-    launch_as(tiles, s, P, prev, cur, out, EmitPlanes<false, false>{}, mom, clip, spec);
+// The call's planes, listed in the host entries' staging order (the results depend on which slots
+// alias), then bound: device pointers in place, host pointers to their slots and copied in
+int reproject_bind(const ReprojectRequest& rq, ReprojectJob* j) {
+  const size_t n = (size_t)rq.w * rq.h;
+  const UserFrame pv = j->no_prev ? UserFrame{} : user_frame(j->prev, j->prev_emit);  // not copied without history
+  const UserFrame cu = user_frame(rq.cur, j->cur_emit);
+  UserFrame ou = user_frame(rq.out, j->out_emit);
+  ou.p[3] = ou.p[4] = nullptr;  // no normal or depth is written
+  const int nf = j->emit ? 7 : 5;
+  TpPlane* p = j->planes;
+  for (int k = 0; k < nf; ++k) *p++ = {kFloats[k], pv.p[k], &j->d_prev[k]};
+  // without moments out is written over cur's copy (out may alias cur), into the var and count slots
+  // also when cur has neither, and out_emit over cur_emit's copy
+  for (int k = 0; k < nf; ++k)
+    *p++ = {kFloats[k], cu.p[k], &j->d_cur[k], j->mom ? nullptr : ou.p[k], j->mom ? nullptr : &j->d_out[k]};
+  if (j->mom) {  // beside the frames instead (the window reads cur's copy): prev's lum2, then out
+    *p++ = {1, j->no_prev ? nullptr : rq.prev_lum2, &j->mo.prev_lum2};
+    for (int k : {0, 1, 2}) *p++ = {kFloats[k], nullptr, nullptr, ou.p[k], &j->d_out[k]};
+    *p++ = {1, nullptr, nullptr, rq.out_lum2, &j->mo.out_lum2};
+    if (j->light)
+      for (int k : {5, 6}) *p++ = {kFloats[k], nullptr, nullptr, ou.p[k], &j->d_out[k]};
   }
+  if (j->spec) {  // last: the two bounces planes
+    *p++ = {1, j->no_prev ? nullptr : rq.spec->prev_bounces, &j->sp.prev_bounces};
+    *p++ = {1, rq.spec->cur_bounces, &j->sp.cur_bounces};
+  }
+  j->n_planes = (int)(p - j->planes);
+  float* slot = nullptr;
+  if (rq.host) {
+    size_t floats = 0;
+    for (int i = 0; i < j->n_planes; ++i) floats += j->planes[i].floats;
+    void* stg = nullptr;
+    if (int rc = g_stage.get(0, n * 4 * floats, &stg, rq.name)) return rc;
+    slot = (float*)stg;
+  }
+  for (p = j->planes; p != j->planes + j->n_planes; ++p) {
+    if (rq.host) p->dev = p->src || p->dst ? slot : nullptr, slot += p->floats * n;
+    if (p->in) *p->in = rq.host && p->src ? p->dev : p->src;
+    if (p->out) *p->out = rq.host && p->dst ? p->dev : p->dst;
+    if (rq.host && p->src) HIP_OK(hipMemcpyAsync(p->dev, p->src, n * 4 * p->floats, hipMemcpyHostToDevice, j->stream));
+  }
+  if (j->no_prev) {  // read through clamped addresses, never a tap
+    std::copy(j->d_cur, j->d_cur + 7, j->d_prev);
+    j->sp.prev_bounces = j->sp.cur_bounces;
+  }
+  return RT_OK;
+}
+
+Planes planes_of(const float* const* p) {
+  return {(float*)p[0], (float*)p[1], (float*)p[2], (float*)p[3], (float*)p[4]};
+}
+template <bool Emit, bool Light>
+EmitPlanes<Emit, Light> emit_planes_of(const ReprojectJob& j) {
+  if constexpr (Light)
+    return {j.d_prev[5], j.d_prev[6], j.d_cur[5], j.d_cur[6], j.d_out[5], j.d_out[6]};
+  else if constexpr (Emit)
+    return {j.d_prev[5], j.d_prev[6], j.d_cur[5], j.d_cur[6]};
+  else
+    return {};
+}
+// an argument set of Extra: the job's when the instance takes it, else the empty one
+template <template <bool> class Set, bool On>
+Set<On> set_if(const Set<true>& v) {
+  if constexpr (On)
+    return v;
+  else
+    return {};
+}
+
+// The kernel table: k_reproject<Emit, Light, Mom, Clip, Spec> by the job's five flags.  Light needs
+// Emit, Clip and Spec need Mom: 3 plain + 3 moments + 3 clip + 6 spec = 15 instances and no other
+int reproject_launch(const ReprojectJob& j) {
+  const unsigned tiles = (unsigned)((int64_t)j.P.tiles_x * ((j.P.h + kTH - 1) / kTH));  // < 2^31 / 3: w h is
+  const Planes prev = planes_of(j.d_prev), cur = planes_of(j.d_cur), out = planes_of(j.d_out);
+  // Clip: the tile and its halo in LDS, 8 floats a pixel, 22 KB at radius 3, 51 KB at radius 8
+  const size_t lds = j.clip ? (size_t)(kTW + 2 * j.mo.radius) * (kTH + 2 * j.mo.radius) * 32 : 0;
+  with_flag(j.emit, [&](auto e) {
+    with_flag(j.light, [&](auto l) {
+      with_flag(j.mom, [&](auto m) {
+        with_flag(j.clip, [&](auto c) {
+          with_flag(j.spec, [&](auto s) {
+            constexpr bool E = decltype(e)::value, L = decltype(l)::value, M = decltype(m)::value,
+                           C = decltype(c)::value, S = decltype(s)::value;
+            if constexpr ((E || !L) && (M || (!C && !S)))
+              hipLaunchKernelGGL((k_reproject<E, L, M, C, S>), dim3(tiles), dim3(256), lds, j.stream, j.P, prev, cur, out,
+                                 Extra<E, L, M, C, S>{emit_planes_of<E, L>(j), set_if<MomPlanes, M>(j.mo),
+                                                      set_if<ClipArgs, C>(j.cl), set_if<SpecArgs, S>(j.sp)});
+          });
+        });
+      });
+    });
+  });
   HIP_OK(hipGetLastError());
   return RT_OK;
 }
 
-// rt_reproject_device, rt_reproject_emit_device (emit) and rt_reproject_light_device (emit, light)
-int reproject_device(const char* who, bool emit, bool light, const rt_camera* cam_prev, const rt_frame* prev,
-                     const rt_aov_emit* prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
-                     const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
-                     const rt_frame* out, const rt_aov_emit* out_emit, int device, void* stream,
-                     const Moments* m = nullptr) {
-  TpParams P;
-  MomPlanes<true> mo;
-  ClipArgs<true> cl;
-  SpecArgs<true> sp;
-  int rc = m ? resolve_moments(who, emit, light, &cam_prev, &prev, &prev_emit, cam_cur, cur, cur_emit, w, h, opts,
-                               *m, out, out_emit, &P, &mo, &cl, &sp)
-             : resolve(who, emit, light, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out,
-                       out_emit, &P);
-  if (rc) return rc;
-  if ((rc = device_ok(who, device))) return rc;
-  DeviceGuard dg;
-  HIP_OK(hipSetDevice(device));
-  hipStream_t s = (hipStream_t)stream;
-  rc = launch(P, planes_of(prev), planes_of(cur), planes_of(out), prev_emit, cur_emit, out_emit, s, m ? &mo : nullptr,
-              m && m->copts ? &cl : nullptr, m && m->spec ? &sp : nullptr);
-  HIP_OK(hipStreamSynchronize(s));
-  return rc;
-}
-
-// rt_reproject, rt_reproject_emit (emit) and rt_reproject_light (emit, light): host pointers, staged
-// through device 0
-int reproject_host(const char* who, bool emit, bool light, const rt_camera* cam_prev, const rt_frame* prev,
-                   const rt_aov_emit* prev_emit, const rt_camera* cam_cur, const rt_frame* cur,
-                   const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
-                   const rt_frame* out, const rt_aov_emit* out_emit, const Moments* m = nullptr) {
-  TpParams P;
-  MomPlanes<true> mo;
-  ClipArgs<true> cl;
-  SpecArgs<true> sp;
-  const bool no_prev = m && !prev;
-  int rc = m ? resolve_moments(who, emit, light, &cam_prev, &prev, &prev_emit, cam_cur, cur, cur_emit, w, h, opts,
-                               *m, out, out_emit, &P, &mo, &cl, &sp)
-             : resolve(who, emit, light, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h, opts, out,
-                       out_emit, &P);
-  if (rc) return rc;
-  if ((rc = device_ok(who, 0))) return rc;
-  DeviceGuard dg;
-  HIP_OK(hipSetDevice(0));
-  std::lock_guard<std::mutex> lk(g_mu);
-  hipStream_t s = nullptr;
-  // both frames as 9 planes-floats per pixel each: rgb, var, count, normal, depth, and with emit 4
-  // more: emission, coverage.  out is written over cur's copy (out may alias cur), into the var
-  // and count slots also when cur has neither; out_emit over cur_emit's copy.  The moments entries
-  // write beside the frames instead (the window reads cur's copy): prev's lum2, then out as rgb,
-  // var, count, lum2 and in the light mode emission, coverage: 7 or 11 floats more
-  const size_t n = (size_t)w * h;
-  constexpr int kOff[8] = {0, 3, 4, 5, 8, 9, 12, 13};
-  const int nbuf = emit ? 7 : 5, per = kOff[nbuf];
-  void* stg = nullptr;
-  // (rt_reproject_spec: the two bounces planes behind the moments entries' planes, 2 floats more)
-  const bool spec = m && m->spec;
-  const int nmom = m ? (light ? 11 : 7) : 0;
-  if ((rc = g_stage.get(0, n * 4 * (2 * per + nmom + (spec ? 2 : 0)), &stg, who))) return rc;
-  Planes d[2];
-  rt_aov_emit de[2];
-  const rt_frame* src[2] = {prev, cur};
-  const rt_aov_emit* esrc[2] = {prev_emit, cur_emit};
-  for (int f = no_prev ? 1 : 0; f < 2; ++f) {
-    float* base = (float*)stg + (size_t)f * per * n;
-    const float* host[7] = {src[f]->rgb,    src[f]->var,   src[f]->count,
-                            src[f]->normal, src[f]->depth, emit ? esrc[f]->emission : nullptr,
-                            emit ? esrc[f]->coverage : nullptr};
-    float* dev[7] = {};
-    for (int k = 0; k < nbuf; ++k) {
-      dev[k] = host[k] ? base + kOff[k] * n : nullptr;
-      if (host[k])
-        HIP_OK(hipMemcpyAsync(dev[k], host[k], n * 4 * (kOff[k + 1] - kOff[k]), hipMemcpyHostToDevice, s));
-    }
-    d[f] = {dev[0], dev[1], dev[2], dev[3], dev[4]};
-    de[f] = {dev[5], nullptr, dev[6]};
-  }
-  if (no_prev) d[0] = d[1], de[0] = de[1];  // read through clamped addresses, never a tap
-  float* mbase = (float*)stg + (size_t)2 * per * n;  // the moments entries' planes
-  float* cbase = m ? mbase + n : (float*)stg + (size_t)per * n;
-  const Planes o = {out->rgb ? cbase : nullptr, out->var ? cbase + kOff[1] * n : nullptr,
-                    out->count ? cbase + kOff[2] * n : nullptr, nullptr, nullptr};
-  rt_aov_emit oe = {};
-  if (light && m)
-    oe = {out_emit->emission ? cbase + 6 * n : nullptr, nullptr, out_emit->coverage ? cbase + 9 * n : nullptr};
-  else if (light)
-    oe = {out_emit->emission ? de[1].emission : nullptr, nullptr, out_emit->coverage ? de[1].coverage : nullptr};
-  if (m) {
-    if (mo.prev_lum2) {
-      HIP_OK(hipMemcpyAsync(mbase, mo.prev_lum2, n * 4, hipMemcpyHostToDevice, s));
-      mo.prev_lum2 = mbase;
-    }
-    mo.out_lum2 = cbase + 5 * n;
-  }
-  if (spec) {
-    float* sbase = mbase + (size_t)nmom * n;
-    HIP_OK(hipMemcpyAsync(sbase + n, sp.cur_bounces, n * 4, hipMemcpyHostToDevice, s));
-    if (!no_prev) HIP_OK(hipMemcpyAsync(sbase, sp.prev_bounces, n * 4, hipMemcpyHostToDevice, s));
-    sp = {no_prev ? sbase + n : sbase, sbase + n};
-  }
-  rc = launch(P, d[0], d[1], o, emit ? &de[0] : nullptr, emit ? &de[1] : nullptr, light ? &oe : nullptr, s,
-              m ? &mo : nullptr, m && m->copts ? &cl : nullptr, spec ? &sp : nullptr);
-  if (!rc && m && hipMemcpyAsync(m->out_lum2, mo.out_lum2, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
-    rc = set_error(RT_ERR_DEVICE, "%s: copy to host failed", who);
-  if (!rc && ((o.rgb && hipMemcpyAsync(out->rgb, o.rgb, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-              (o.var && hipMemcpyAsync(out->var, o.var, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-              (o.count && hipMemcpyAsync(out->count, o.count, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-              (oe.emission &&
-               hipMemcpyAsync(out_emit->emission, oe.emission, n * 12, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-              (oe.coverage &&
-               hipMemcpyAsync(out_emit->coverage, oe.coverage, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)))
-    rc = set_error(RT_ERR_DEVICE, "%s: copy to host failed", who);
-  HIP_OK(hipStreamSynchronize(s));  // also after an error: nothing in flight on the staging buffer
+// rc: the launch's.  A host entry's results are copied back; the one synchronise also runs after an
+// error, so that nothing is in flight on the staging buffer
+int reproject_collect(const ReprojectRequest& rq, const ReprojectJob& j, int rc) {
+  const size_t n = (size_t)rq.w * rq.h;
+  for (int i = 0; rq.host && !rc && i < j.n_planes; ++i)
+    if (const TpPlane& p = j.planes[i];
+        p.dst && hipMemcpyAsync(p.dst, p.dev, n * 4 * p.floats, hipMemcpyDeviceToHost, j.stream) != hipSuccess)
+      rc = set_error(RT_ERR_DEVICE, "%s: copy to host failed", rq.name);
+  HIP_OK(hipStreamSynchronize(j.stream));
   return rc;
 }
 
 }  // namespace
+
+// host entries: staged through device 0 on the null stream, one at a time
+int reproject_impl(const ReprojectRequest& rq) {
+  ReprojectJob j{};
+  const int device = rq.host ? 0 : rq.device;
+  int rc;
+  if ((rc = reproject_check(rq, &j)) || (rc = device_ok(rq.name, device))) return rc;
+  DeviceGuard dg;
+  HIP_OK(hipSetDevice(device));
+  std::unique_lock<std::mutex> lk(g_mu, std::defer_lock);
+  if (rq.host) lk.lock();
+  j.stream = rq.host ? nullptr : (hipStream_t)rq.stream;
+  if ((rc = reproject_bind(rq, &j))) return rc;
+  return reproject_collect(rq, j, reproject_launch(j));
+}
+
 }  // namespace rt
 
 using namespace rt;
 
+// a request's fields: name, host, moments, mode; cam_prev, prev, prev_emit, prev_lum2; cam_cur, cur,
+// cur_emit; w, h; opts, mopts, copts, spec; out, out_emit, out_lum2; device, stream
 extern "C" {
 
 int rt_reproject_device(const rt_camera* cam_prev, const rt_frame* prev_dev, const rt_camera* cam_cur,
                         const rt_frame* cur_dev, int w, int h, const rt_reproject_opts* opts,
                         const rt_frame* out_dev, int device, void* stream) {
-  return reproject_device("rt_reproject_device", false, false, cam_prev, prev_dev, nullptr, cam_cur, cur_dev, nullptr,
-                          w, h, opts, out_dev, nullptr, device, stream);
+  return reproject_impl({"rt_reproject_device", false, false, RT_REPROJECT_PLAIN, cam_prev, prev_dev, nullptr, nullptr,
+                         cam_cur, cur_dev, nullptr, w, h, opts, nullptr, nullptr, nullptr, out_dev, nullptr, nullptr,
+                         device, stream});
 }
 
 int rt_reproject(const rt_camera* cam_prev, const rt_frame* prev, const rt_camera* cam_cur,
                  const rt_frame* cur, int w, int h, const rt_reproject_opts* opts, const rt_frame* out) {
-  return reproject_host("rt_reproject", false, false, cam_prev, prev, nullptr, cam_cur, cur, nullptr, w, h, opts, out,
-                        nullptr);
+  return reproject_impl({"rt_reproject", true, false, RT_REPROJECT_PLAIN, cam_prev, prev, nullptr, nullptr, cam_cur, cur,
+                         nullptr, w, h, opts, nullptr, nullptr, nullptr, out});
 }
 
 int rt_reproject_emit_device(const rt_camera* cam_prev, const rt_frame* prev_dev, const rt_aov_emit* prev_emit_dev,
                              const rt_camera* cam_cur, const rt_frame* cur_dev, const rt_aov_emit* cur_emit_dev,
                              int w, int h, const rt_reproject_opts* opts, const rt_frame* out_dev, int device,
                              void* stream) {
-  return reproject_device("rt_reproject_emit_device", true, false, cam_prev, prev_dev, prev_emit_dev, cam_cur,
-                          cur_dev, cur_emit_dev, w, h, opts, out_dev, nullptr, device, stream);
+  return reproject_impl({"rt_reproject_emit_device", false, false, RT_REPROJECT_EMIT, cam_prev, prev_dev, prev_emit_dev,
+                         nullptr, cam_cur, cur_dev, cur_emit_dev, w, h, opts, nullptr, nullptr, nullptr, out_dev,
+                         nullptr, nullptr, device, stream});
 }
 
 int rt_reproject_emit(const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
                       const rt_camera* cam_cur, const rt_frame* cur, const rt_aov_emit* cur_emit, int w, int h,
                       const rt_reproject_opts* opts, const rt_frame* out) {
-  return reproject_host("rt_reproject_emit", true, false, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h,
-                        opts, out, nullptr);
+  return reproject_impl({"rt_reproject_emit", true, false, RT_REPROJECT_EMIT, cam_prev, prev, prev_emit, nullptr,
+                         cam_cur, cur, cur_emit, w, h, opts, nullptr, nullptr, nullptr, out});
 }
 
 int rt_reproject_light_device(const rt_camera* cam_prev, const rt_frame* prev_dev, const rt_aov_emit* prev_emit_dev,
                               const rt_camera* cam_cur, const rt_frame* cur_dev, const rt_aov_emit* cur_emit_dev,
                               int w, int h, const rt_reproject_opts* opts, const rt_frame* out_dev,
                               const rt_aov_emit* out_emit_dev, int device, void* stream) {
-  return reproject_device("rt_reproject_light_device", true, true, cam_prev, prev_dev, prev_emit_dev, cam_cur,
-                          cur_dev, cur_emit_dev, w, h, opts, out_dev, out_emit_dev, device, stream);
+  return reproject_impl({"rt_reproject_light_device", false, false, RT_REPROJECT_LIGHT, cam_prev, prev_dev,
+                         prev_emit_dev, nullptr, cam_cur, cur_dev, cur_emit_dev, w, h, opts, nullptr, nullptr, nullptr,
+                         out_dev, out_emit_dev, nullptr, device, stream});
 }
 
 int rt_reproject_light(const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
                        const rt_camera* cam_cur, const rt_frame* cur, const rt_aov_emit* cur_emit, int w, int h,
                        const rt_reproject_opts* opts, const rt_frame* out, const rt_aov_emit* out_emit) {
-  return reproject_host("rt_reproject_light", true, true, cam_prev, prev, prev_emit, cam_cur, cur, cur_emit, w, h,
-                        opts, out, out_emit);
+  return reproject_impl({"rt_reproject_light", true, false, RT_REPROJECT_LIGHT, cam_prev, prev, prev_emit, nullptr,
+                         cam_cur, cur, cur_emit, w, h, opts, nullptr, nullptr, nullptr, out, out_emit});
 }
 
 int rt_reproject_moments_device(int mode, const rt_camera* cam_prev, const rt_frame* prev_dev,
@@ -974,13 +986,9 @@ int rt_reproject_moments_device(int mode, const rt_camera* cam_prev, const rt_fr
                                 int w, int h, const rt_reproject_opts* opts, const rt_moments_opts* mopts,
                                 const rt_frame* out_dev, const rt_aov_emit* out_emit_dev, float* out_lum2_dev,
                                 int device, void* stream) {
-  const char* who = "rt_reproject_moments_device";
-  if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
-  const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
-  const Moments m = {prev_lum2_dev, mopts, out_lum2_dev};
-  return reproject_device(who, emit, light, cam_prev, prev_dev, emit ? prev_emit_dev : nullptr, cam_cur, cur_dev,
-                          emit ? cur_emit_dev : nullptr, w, h, opts, out_dev, light ? out_emit_dev : nullptr, device,
-                          stream, &m);
+  return reproject_impl({"rt_reproject_moments_device", false, true, mode, cam_prev, prev_dev, prev_emit_dev,
+                         prev_lum2_dev, cam_cur, cur_dev, cur_emit_dev, w, h, opts, mopts, nullptr, nullptr, out_dev,
+                         out_emit_dev, out_lum2_dev, device, stream});
 }
 
 int rt_reproject_moments(int mode, const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
@@ -988,12 +996,8 @@ int rt_reproject_moments(int mode, const rt_camera* cam_prev, const rt_frame* pr
                          const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
                          const rt_moments_opts* mopts, const rt_frame* out, const rt_aov_emit* out_emit,
                          float* out_lum2) {
-  const char* who = "rt_reproject_moments";
-  if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
-  const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
-  const Moments m = {prev_lum2, mopts, out_lum2};
-  return reproject_host(who, emit, light, cam_prev, prev, emit ? prev_emit : nullptr, cam_cur, cur,
-                        emit ? cur_emit : nullptr, w, h, opts, out, light ? out_emit : nullptr, &m);
+  return reproject_impl({"rt_reproject_moments", true, true, mode, cam_prev, prev, prev_emit, prev_lum2, cam_cur, cur,
+                         cur_emit, w, h, opts, mopts, nullptr, nullptr, out, out_emit, out_lum2});
 }
 
 int rt_reproject_clip_device(int mode, const rt_camera* cam_prev, const rt_frame* prev_dev,
@@ -1002,13 +1006,9 @@ int rt_reproject_clip_device(int mode, const rt_camera* cam_prev, const rt_frame
                              const rt_reproject_opts* opts, const rt_moments_opts* mopts, const rt_clip_opts* copts,
                              const rt_frame* out_dev, const rt_aov_emit* out_emit_dev, float* out_lum2_dev,
                              int device, void* stream) {
-  const char* who = "rt_reproject_clip_device";
-  if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
-  const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
-  const Moments m = {prev_lum2_dev, mopts, out_lum2_dev, copts};
-  return reproject_device(who, emit, light, cam_prev, prev_dev, emit ? prev_emit_dev : nullptr, cam_cur, cur_dev,
-                          emit ? cur_emit_dev : nullptr, w, h, opts, out_dev, light ? out_emit_dev : nullptr, device,
-                          stream, &m);
+  return reproject_impl({"rt_reproject_clip_device", false, true, mode, cam_prev, prev_dev, prev_emit_dev,
+                         prev_lum2_dev, cam_cur, cur_dev, cur_emit_dev, w, h, opts, mopts, copts, nullptr, out_dev,
+                         out_emit_dev, out_lum2_dev, device, stream});
 }
 
 int rt_reproject_clip(int mode, const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
@@ -1016,12 +1016,8 @@ int rt_reproject_clip(int mode, const rt_camera* cam_prev, const rt_frame* prev,
                       const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
                       const rt_moments_opts* mopts, const rt_clip_opts* copts, const rt_frame* out,
                       const rt_aov_emit* out_emit, float* out_lum2) {
-  const char* who = "rt_reproject_clip";
-  if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
-  const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
-  const Moments m = {prev_lum2, mopts, out_lum2, copts};
-  return reproject_host(who, emit, light, cam_prev, prev, emit ? prev_emit : nullptr, cam_cur, cur,
-                        emit ? cur_emit : nullptr, w, h, opts, out, light ? out_emit : nullptr, &m);
+  return reproject_impl({"rt_reproject_clip", true, true, mode, cam_prev, prev, prev_emit, prev_lum2, cam_cur, cur,
+                         cur_emit, w, h, opts, mopts, copts, nullptr, out, out_emit, out_lum2});
 }
 
 int rt_reproject_spec_device(int mode, const rt_camera* cam_prev, const rt_frame* prev_dev,
@@ -1030,13 +1026,9 @@ int rt_reproject_spec_device(int mode, const rt_camera* cam_prev, const rt_frame
                              const rt_reproject_opts* opts, const rt_moments_opts* mopts, const rt_clip_opts* copts,
                              const rt_spec_planes* spec_dev, const rt_frame* out_dev, const rt_aov_emit* out_emit_dev,
                              float* out_lum2_dev, int device, void* stream) {
-  const char* who = "rt_reproject_spec_device";
-  if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
-  const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
-  const Moments m = {prev_lum2_dev, mopts, out_lum2_dev, copts, spec_dev};
-  return reproject_device(who, emit, light, cam_prev, prev_dev, emit ? prev_emit_dev : nullptr, cam_cur, cur_dev,
-                          emit ? cur_emit_dev : nullptr, w, h, opts, out_dev, light ? out_emit_dev : nullptr, device,
-                          stream, &m);
+  return reproject_impl({"rt_reproject_spec_device", false, true, mode, cam_prev, prev_dev, prev_emit_dev,
+                         prev_lum2_dev, cam_cur, cur_dev, cur_emit_dev, w, h, opts, mopts, copts, spec_dev, out_dev,
+                         out_emit_dev, out_lum2_dev, device, stream});
 }
 
 int rt_reproject_spec(int mode, const rt_camera* cam_prev, const rt_frame* prev, const rt_aov_emit* prev_emit,
@@ -1044,12 +1036,8 @@ int rt_reproject_spec(int mode, const rt_camera* cam_prev, const rt_frame* prev,
                       const rt_aov_emit* cur_emit, int w, int h, const rt_reproject_opts* opts,
                       const rt_moments_opts* mopts, const rt_clip_opts* copts, const rt_spec_planes* spec,
                       const rt_frame* out, const rt_aov_emit* out_emit, float* out_lum2) {
-  const char* who = "rt_reproject_spec";
-  if (mode < RT_REPROJECT_PLAIN || mode > RT_REPROJECT_LIGHT) return set_error(RT_ERR_INVALID, "%s: mode %d", who, mode);
-  const bool emit = mode != RT_REPROJECT_PLAIN, light = mode == RT_REPROJECT_LIGHT;
-  const Moments m = {prev_lum2, mopts, out_lum2, copts, spec};
-  return reproject_host(who, emit, light, cam_prev, prev, emit ? prev_emit : nullptr, cam_cur, cur,
-                        emit ? cur_emit : nullptr, w, h, opts, out, light ? out_emit : nullptr, &m);
+  return reproject_impl({"rt_reproject_spec", true, true, mode, cam_prev, prev, prev_emit, prev_lum2, cam_cur, cur,
+                         cur_emit, w, h, opts, mopts, copts, spec, out, out_emit, out_lum2});
 }
 
 }  // extern "C"
