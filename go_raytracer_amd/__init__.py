@@ -26,7 +26,7 @@ __all__ = ["Tree", "Camera", "Scene", "Accumulator", "quantize", "format_ppm", "
            "demo_scene", "DEMO_SCENES", "build_bvh_boxes", "LoadObjOptions", "DefaultLoadOptions", "quantize_device",
            "format_ppm_device", "denoise", "denoise_device", "denoise_var", "denoise_var_device",
            "RtDenoiseVarOpts", "reproject", "reproject_device", "reproject_emit", "reproject_emit_device", "reproject_light", "reproject_light_device", "reproject_moments", "reproject_moments_device", "reproject_clip", "reproject_clip_device", "reproject_spec", "reproject_spec_device",
-           "Temporal", "Pipeline"]
+           "Temporal", "Pipeline", "AccumulatorShares"]
 
 DEMO_SCENES = ("book1", "book2", "book3", "simple_light", "quads", "cornell", "cornell_smoke",
                "model")
@@ -656,6 +656,14 @@ class Scene:
         return Accumulator(self, camera, max_passes, device, rank, nranks, path_slots, chunk,
                            profile, stream, mode, progress_slices, features, spec_bounces, spec_fuzz)
 
+    def accumulator_shares(self, camera, devices, max_passes=0, features=None, spec_bounces=0, spec_fuzz=0.0,
+                           path_slots=0, chunk=0, profile=False, mode="auto"):
+        """One frame of `camera` accumulated as len(devices) row-interleaved shares: rank i of
+        len(devices) on devices[i] (a device may repeat).  See AccumulatorShares; the other
+        arguments are Scene.accumulator's."""
+        return AccumulatorShares(self, camera, devices, max_passes, features, spec_bounces, spec_fuzz,
+                                 path_slots, chunk, profile, mode)
+
 
 class Accumulator:
     """The exact running sum of render passes of one camera, kept on the device (rt_accum).
@@ -980,6 +988,71 @@ class Accumulator:
             self.add_active(seed + p)
             p += 1
         return dict(self.adapt_info(), passes=p)
+
+
+def _share_array(accs):
+    """rt_accum* const* for the share entries, and the handles it points at"""
+    hs = [a._h() for a in accs]
+    return (C.c_void_p * len(hs))(*[h.value for h in hs]), len(hs)
+
+
+class AccumulatorShares:
+    """The accumulators of one frame held as row shares: ``shares[i]`` is the
+    Accumulator of rank i of n on ``devices[i]``.  ``add(seed)`` takes one pass on every share, a
+    host thread each (rt_accum_add_shares), and returns the combined stats; each share ends up with
+    exactly the state its own ``add(seed)`` leaves.  ``resolve()`` interleaves the shares' rows on
+    the host; ``Pipeline.push`` takes the object as one frame.  A context manager owning its
+    accumulators."""
+
+    def __init__(self, scene, camera, devices, max_passes=0, features=None, spec_bounces=0, spec_fuzz=0.0,
+                 path_slots=0, chunk=0, profile=False, mode="auto"):
+        devices = [int(d) for d in devices]
+        if not devices:
+            raise ValueError("AccumulatorShares: needs at least one device")
+        self.shares, self.devices = [], devices
+        self.height = camera.derived().height
+        try:
+            for i, d in enumerate(devices):
+                self.shares.append(Accumulator(scene, camera, max_passes, d, i, len(devices), path_slots, chunk,
+                                               profile, None, mode, 0, features, spec_bounces, spec_fuzz))
+        except BaseException:
+            self.close()
+            raise
+
+    def close(self):
+        for a in getattr(self, "shares", ()):
+            a.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __len__(self):
+        return len(self.shares)
+
+    def add(self, seed):
+        """One pass with render seed `seed` on every share -> the combined stats dict."""
+        arr, n = _share_array(self.shares)
+        st = RtStats()
+        check(lib().rt_accum_add_shares(arr, n, seed, C.byref(st)))
+        return _as_dict(st)
+
+    @property
+    def passes(self):
+        return self.shares[0].passes
+
+    def resolve(self):
+        """(rgb float32 [H, W, 3], var float32 [H, W]) of the whole image: the shares' resolve()
+        rows interleaved (row r is local row r // n of share r % n)."""
+        from .shard import rows_of_rank
+        n, w = len(self.shares), self.shares[0].shape[1]
+        rgb, var = np.zeros((self.height, w, 3), np.float32), np.zeros((self.height, w), np.float32)
+        for i, a in enumerate(self.shares):
+            rows = list(rows_of_rank(self.height, i, n))
+            rgb[rows], var[rows] = a.resolve()
+        return rgb, var
 
 
 def _multi(scene, camera, devices, out_ptr, seed, path_slots, chunk, profile, mode, rccl=False):
@@ -1783,8 +1856,16 @@ class Pipeline:
         return self._p
 
     def push(self, acc):
-        """The next frame: `acc` as Temporal.push's (rt_pipeline_push).  Returns self."""
-        check(lib().rt_pipeline_push(self._h(), acc._h()))
+        """The next frame: `acc` as Temporal.push's (rt_pipeline_push), or a frame held as row
+        shares, an AccumulatorShares or a list or tuple of the shares' Accumulators in rank order
+        (rt_pipeline_push_shares: the same bits as the whole accumulator's push).  Returns self."""
+        if isinstance(acc, AccumulatorShares):
+            acc = acc.shares
+        if isinstance(acc, (list, tuple)):
+            arr, n = _share_array(acc)
+            check(lib().rt_pipeline_push_shares(self._h(), arr, n))
+        else:
+            check(lib().rt_pipeline_push(self._h(), acc._h()))
         return self
 
     def reset(self):

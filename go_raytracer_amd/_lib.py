@@ -432,6 +432,8 @@ SIGNATURES = {
     "rt_pipeline_planes_device": (_I, [_P, C.POINTER(RtFrame), C.POINTER(RtAovEmit), C.POINTER(C.c_void_p),
                                        C.POINTER(C.c_void_p)]),
     "rt_pipeline_info_get": (_I, [_P, C.POINTER(RtPipelineInfo)]),
+    "rt_accum_add_shares": (_I, [C.POINTER(_P), C.c_int32, C.c_uint64, C.POINTER(RtStats)]),
+    "rt_pipeline_push_shares": (_I, [_P, C.POINTER(_P), C.c_int32]),
     "rt_demo_scene": (_I, [_P, C.c_char_p, C.c_char_p, C.POINTER(RtCamera), C.POINTER(_I),
                            C.POINTER(_I)]),
     "rt_demo_scene_name": (_I, [_I, C.POINTER(C.c_char_p)]),

@@ -755,7 +755,9 @@ void release_accums(Scene* s) {
 int accum_view(rt_accum* a, AccumView* out) {
   std::lock_guard<std::mutex> lk(a->mu);
   *out = {a->cam,   (int32_t)a->W, (int32_t)a->rows, a->opts.device, a->opts.nranks, a->passes, a->features,
-          a->opts.stream ? a->opts.stream : (void*)a->own_stream.s};
+          a->opts.stream ? a->opts.stream : (void*)a->own_stream.s,
+          a->opts.rank, (int32_t)a->cd.height, a->scene,
+          (a->features & RT_ACCUM_FEAT_SPEC) ? a->S.max_k : 0, (a->features & RT_ACCUM_FEAT_SPEC) ? a->S.max_fuzz : 0.0f};
   return RT_OK;
 }
 

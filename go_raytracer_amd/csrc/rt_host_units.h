@@ -1,7 +1,7 @@
 // rt_host_units.h — what the host sides of the render (rt_render.hip), the feature pass
 // (rt_aov.hip), the accumulator (rt_accum.hip), rt_render_multi (rt_multi.hip), the temporal
-// reprojection (rt_temporal.hip) and the frame pipeline (rt_pipeline.hip) declare for one
-// another.  The generic HIP helpers and the resource owners are rt_hip_util.h.
+// reprojection (rt_temporal.hip), the frame pipeline (rt_pipeline.hip) and its gather kernel
+// (rt_gather.hip) declare for one another.  The generic HIP helpers and the resource owners are rt_hip_util.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -102,8 +102,25 @@ struct AccumView {
   int32_t width, rows, device, nranks, passes;
   uint32_t features;  // RT_ACCUM_FEAT_*
   void* stream;
+  // what rt_pipeline_push_shares compares between the shares of one frame: the share's rank, the
+  // whole image's height, the scene, and the chain limits of RT_ACCUM_FEAT_SPEC (0, 0 without it)
+  int32_t rank, height;
+  const void* scene;
+  int32_t spec_bounces;
+  float spec_fuzz;
 };
 int accum_view(rt_accum* a, AccumView* out);
+
+// rt_multi.hip, for the frame pipeline's shares (rt_pipeline.hip): xGMI peer access from -> to
+// ("already enabled" is success), and between devices[0] and every other device of a list that
+// reports a peer path, which leaves devices[0] current.  who: the entry's name for the message.
+int enable_peer(const char* who, int from, int to);
+int enable_peers(const char* who, const int32_t* devices, int n);
+
+// rt_gather.hip, for the frame pipeline's shares: one launch of k_gather_planes on `stream` (the
+// lead device is current), from the gather buffer into the table's destinations (rt_gather_map.h)
+struct GatherTable;
+int gather_planes_launch(const char* who, const float* gather, const GatherTable& t, hipStream_t stream);
 
 // rt_temporal.hip, for the frame pipeline (rt_pipeline.hip): what one of the twelve rt_reproject
 // entries asks for, as it came in, and the one path they all take.  name: the entry's, for the

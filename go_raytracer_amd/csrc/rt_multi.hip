@@ -2,6 +2,7 @@
 // camera.go:119-122) renders on devices[i] through rt_render.hip's render_share, one host
 // thread and stream per share, each with its own render slot; the shares are peer-copied (or
 // gathered by RCCL, RT_FLAG_GATHER_RCCL) to devices[0] and de-interleaved there.
+// rt_accum_add_shares: one accumulator pass per share on the same kind of host threads.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -81,7 +82,7 @@ static int ensure_gather_buffer(MultiState* ms, int d0, size_t need) {
 // xGMI peer access both ways.  "Already enabled" is success; any other failure is
 // an error (the copies would silently fall back to staging through host memory).
 // Devices that report no peer path copy through the runtime's staged path.
-static int enable_peer(int from, int to) {
+int enable_peer(const char* who, int from, int to) {
   HIP_OK(hipSetDevice(from));
   const hipError_t e = hipDeviceEnablePeerAccess(to, 0);
   if (e == hipErrorPeerAccessAlreadyEnabled) {
@@ -89,12 +90,11 @@ static int enable_peer(int from, int to) {
     return RT_OK;
   }
   if (e != hipSuccess)
-    return set_error(RT_ERR_DEVICE, "rt_render_multi: peer access %d -> %d: %s", from, to,
-                     hipGetErrorString(e));
+    return set_error(RT_ERR_DEVICE, "%s: peer access %d -> %d: %s", who, from, to, hipGetErrorString(e));
   return RT_OK;
 }
 // ... between devices[0] and every other device of the list; leaves devices[0] current
-static int enable_peers(const int32_t* devices, int n) {
+int enable_peers(const char* who, const int32_t* devices, int n) {
   const int d0 = devices[0];
   int rc;
   for (int i = 1; i < n; ++i)
@@ -102,8 +102,8 @@ static int enable_peers(const int32_t* devices, int n) {
       int can_a = 0, can_b = 0;
       HIP_OK(hipDeviceCanAccessPeer(&can_a, devices[i], d0));
       HIP_OK(hipDeviceCanAccessPeer(&can_b, d0, devices[i]));
-      if (can_a && (rc = enable_peer(devices[i], d0))) return rc;
-      if (can_b && (rc = enable_peer(d0, devices[i]))) return rc;
+      if (can_a && (rc = enable_peer(who, devices[i], d0))) return rc;
+      if (can_b && (rc = enable_peer(who, d0, devices[i]))) return rc;
     }
   HIP_OK(hipSetDevice(d0));
   return RT_OK;
@@ -218,7 +218,7 @@ static int render_multi(rt_scene* scene, const rt_camera* cam, const rt_render_o
   if ((rc = ensure_gather_buffer(s->multi, d0, (gather_floats + img_floats) * sizeof(float)))) return rc;
   float* gbuf = (float*)s->multi->gather.p;
   float* img = out_dev ? out_dev : gbuf + gather_floats;
-  if ((rc = enable_peers(devices, n))) return rc;
+  if ((rc = enable_peers("rt_render_multi", devices, n))) return rc;
   // RT_FLAG_GATHER_RCCL: the shares gathered by one collective
   RcclGather* rg = (o.flags & RT_FLAG_GATHER_RCCL) ? &s->multi->rccl : nullptr;
   if (rg && (rc = setup_rccl(rg, devices, n, share_floats))) return rc;
@@ -270,9 +270,37 @@ static int render_multi(rt_scene* scene, const rt_camera* cam, const rt_render_o
   return RT_OK;
 }
 
+// rt_accum_add_shares: one pass of every share, a host thread each as render_multi's shares have
+static int accum_add_shares(rt_accum* const* accs, int32_t n, uint64_t seed, rt_stats* stats) {
+  const char* who = "rt_accum_add_shares";
+  if (!accs) return set_error(RT_ERR_INVALID, "%s: null accumulator array", who);
+  if (n < 1) return set_error(RT_ERR_INVALID, "%s: n = %d shares (at least 1)", who, n);
+  for (int i = 0; i < n; ++i)
+    if (!accs[i]) return set_error(RT_ERR_INVALID, "%s: accs[%d] is null", who, i);
+  std::vector<rt_stats> st(n);
+  std::vector<int> rcs(n, RT_OK);
+  std::vector<std::string> errs(n);
+  std::vector<std::thread> th;
+  for (int i = 0; i < n; ++i)
+    th.emplace_back([&, i] {
+      rcs[i] = rt_accum_add(accs[i], seed, &st[i]);
+      if (rcs[i] != RT_OK) errs[i] = rt_last_error();
+    });
+  for (auto& t : th) t.join();
+  // the lowest failing share's code and message; the others keep the pass they took
+  for (int i = 0; i < n; ++i)
+    if (rcs[i] != RT_OK) return set_error(rcs[i], "%s share %d: %s", who, i, errs[i].c_str());
+  if (stats) sum_stats(stats, st);
+  return RT_OK;
+}
+
 }  // namespace rt
 
 extern "C" {
+
+int rt_accum_add_shares(rt_accum* const* accs, int32_t n, uint64_t seed, rt_stats* stats) {
+  return rt::accum_add_shares(accs, n, seed, stats);
+}
 
 int rt_render_multi(rt_scene* s, const rt_camera* cam, const rt_render_opts* opts,
                     const int32_t* devices, int32_t n, float* out_rgb, rt_stats* stats) {

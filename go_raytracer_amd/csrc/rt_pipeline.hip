@@ -5,12 +5,19 @@
 // (rt_temporal.hip's reproject_impl): this unit launches no kernel and has no device code.  Its own
 // work is the bookkeeping (which plane lives in which set), two runtime fills and the copies to
 // the host.  Device memory comes from rt_hip_util.h's owners only.
+// rt_pipeline_push_shares feeds the same stages from a frame held as row shares:
+// the stages take a FrameSource, which for shares resolves into a staging block per share, copies
+// the blocks to the lead device and has rt_gather.hip's kernel write the planes where the single
+// accumulator's resolves would have.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <mutex>
+#include <vector>
 
+#include "rt_gather_map.h"
 #include "rt_hip_util.h"
 #include "rt_host_units.h"
 
@@ -37,6 +44,14 @@ struct GuideSet {
   float *albedo = nullptr, *surface_albedo = nullptr, *normal = nullptr, *depth = nullptr;
   char* ppm = nullptr;
   int64_t ppm_cap = 0;
+};
+
+// a share's resolve staging on the share's own device: one block in rt_gather_map.h's layout, and
+// the event that follows the block's copy to the lead device (created on the share's device)
+struct ShareStage {
+  DeviceBuffer buf;
+  Events ev;
+  int device = -1;
 };
 
 // planes of `floats` floats each, one after the other from `base` (null: sizing only)
@@ -69,6 +84,11 @@ struct rt_pipeline {
   rt::GuideSet guide;
   rt::Stream own_stream;  // rt_pipeline_image's and rt_pipeline_ppm's
   uint64_t allocations = 0;
+  // rt_pipeline_push_shares: the shares' blocks on the lead device and their staging on their own,
+  // kept while the size, the share count and the shares' devices stay the same
+  rt::DeviceBuffer gather;
+  std::vector<std::unique_ptr<rt::ShareStage>> stage;
+  uint64_t share_stride = 0;  // floats of a share's block
   // the history: which set holds it and the camera that saw it
   int prev = -1;  // -1: none
   rt_camera cam_prev{};
@@ -126,8 +146,24 @@ int ensure(rt_pipeline* p, Set* s) {
   return RT_OK;
 }
 
+// the gather buffer and the shares' staging, each freed with its device current
+void drop_shares(rt_pipeline* p) {
+  if (p->gather.p || !p->stage.empty()) {
+    DeviceGuard dg;
+    for (auto& st : p->stage) {
+      (void)hipSetDevice(st->device);
+      st.reset();
+    }
+    p->stage.clear();
+    (void)hipSetDevice(p->device);
+    p->gather.reset();
+  }
+  p->share_stride = 0;
+}
+
 // frees everything with the owners' device current; the history goes with the buffers
 void drop_buffers(rt_pipeline* p) {
+  drop_shares(p);
   const bool any = p->set[0].buf.p || p->set[1].buf.p || p->cur.buf.p || p->guide.buf.p || p->own_stream.s;
   if (any) {  // a pipeline that never pushed touches no device here either
     DeviceGuard dg;
@@ -192,8 +228,156 @@ int fill_count(rt_pipeline* p, const AccumView& v, int k) {
   return RT_OK;
 }
 
+// Where a push's frame comes from: one whole accumulator, whose _device resolves write the
+// pipeline's planes directly, or n row shares (accs[i] rank i of n, views their AccumViews), whose
+// same resolves write the share's staging block; gather() then brings the planes to where the
+// whole accumulator's would be.  The stages below ask a source and never an accumulator.
+struct FrameSource {
+  rt_pipeline* p;
+  rt_accum* acc;           // the whole accumulator, or null: shares
+  rt_accum* const* accs;
+  const AccumView* views;
+  int n;
+  GatherTable t;
+
+  // the plane's address in share i's staging block (null stays null: no plane of the configuration)
+  float* staged(int i, float* dst, uint64_t off) const { return dst ? (float*)p->stage[i]->buf.p + off : nullptr; }
+  int full() const {
+    return set_error(RT_ERR_INVALID, "rt_pipeline_push_shares: the configuration's planes do not fit the share block");
+  }
+  int resolve(float* rgb, float* var) {
+    if (acc) return rt_accum_resolve_device(acc, rgb, var);
+    uint64_t o[2] = {0, 0};
+    if (!gather_add(&t, 3, rgb, &o[0]) || !gather_add(&t, 1, var, &o[1])) return full();
+    int rc;
+    for (int i = 0; i < n; ++i)
+      if ((rc = rt_accum_resolve_device(accs[i], staged(i, rgb, o[0]), staged(i, var, o[1])))) return rc;
+    return RT_OK;
+  }
+  int resolve_aov(const rt_aov* out, const rt_aov_emit* emit) {
+    if (acc) return rt_accum_resolve_aov_device(acc, out, emit);
+    uint64_t o[6] = {0, 0, 0, 0, 0, 0};
+    if (out && (!gather_add(&t, 3, out->albedo, &o[0]) || !gather_add(&t, 3, out->normal, &o[1]) ||
+                !gather_add(&t, 1, out->depth, &o[2])))
+      return full();
+    if (emit && (!gather_add(&t, 3, emit->emission, &o[3]) || !gather_add(&t, 3, emit->surface_albedo, &o[4]) ||
+                 !gather_add(&t, 1, emit->coverage, &o[5])))
+      return full();
+    int rc;
+    for (int i = 0; i < n; ++i) {
+      rt_aov so{};
+      rt_aov_emit se{};
+      if (out) so = {staged(i, out->albedo, o[0]), staged(i, out->normal, o[1]), staged(i, out->depth, o[2]), nullptr};
+      if (emit)
+        se = {staged(i, emit->emission, o[3]), staged(i, emit->surface_albedo, o[4]), staged(i, emit->coverage, o[5])};
+      if ((rc = rt_accum_resolve_aov_device(accs[i], out ? &so : nullptr, emit ? &se : nullptr))) return rc;
+    }
+    return RT_OK;
+  }
+  int resolve_aov_spec(const rt_aov* out, const rt_aov_spec* spec) {
+    if (acc) return rt_accum_resolve_aov_spec_device(acc, out, spec);
+    uint64_t o[3] = {0, 0, 0};
+    if (!gather_add(&t, 3, out->normal, &o[0]) || !gather_add(&t, 1, out->depth, &o[1]) ||
+        !gather_add(&t, 1, spec->bounces, &o[2]))
+      return full();
+    int rc;
+    for (int i = 0; i < n; ++i) {
+      const rt_aov so = {nullptr, staged(i, out->normal, o[0]), staged(i, out->depth, o[1]), nullptr};
+      const rt_aov_spec ss = {staged(i, spec->bounces, o[2])};
+      if ((rc = rt_accum_resolve_aov_spec_device(accs[i], &so, &ss))) return rc;
+    }
+    return RT_OK;
+  }
+
+  // After the last resolve (each blocks: the staging blocks are complete).  Every share's block is
+  // copied to the lead device on the share's own stream and followed by the share's event; the
+  // lead stream waits for the events, runs k_gather_planes and is synchronised.  `issued` shares
+  // have work in flight: whatever fails, their streams are drained before the call returns.
+  int gather() {
+    if (acc) return RT_OK;
+    int issued = 0;
+    const int rc = gather_enqueue(&issued);
+    if (rc) {
+      for (int i = 0; i < issued; ++i)
+        if (hipSetDevice(views[i].device) == hipSuccess) (void)hipStreamSynchronize((hipStream_t)views[i].stream);
+      (void)hipSetDevice(p->device);
+      (void)hipStreamSynchronize((hipStream_t)views[0].stream);
+    }
+    return rc;
+  }
+  int gather_enqueue(int* issued) {
+    const char* who = "rt_pipeline_push_shares";
+    const size_t bytes = (size_t)t.used * sizeof(float);
+    float* const gbuf = (float*)p->gather.p;
+    for (int i = 0; i < n; ++i) {
+      const int d = views[i].device;
+      const hipStream_t s = (hipStream_t)views[i].stream;
+      float* const dst = gbuf + (size_t)i * t.stride;
+      HIP_OK(hipSetDevice(d));
+      *issued = i + 1;
+      if (d == p->device)
+        HIP_OK(hipMemcpyAsync(dst, p->stage[i]->buf.p, bytes, hipMemcpyDeviceToDevice, s));
+      else
+        HIP_OK(hipMemcpyPeerAsync(dst, p->device, p->stage[i]->buf.p, d, bytes, s));
+      HIP_OK(hipEventRecord(p->stage[i]->ev.ev[0], s));
+    }
+    HIP_OK(hipSetDevice(p->device));
+    const hipStream_t lead = (hipStream_t)views[0].stream;
+    for (int i = 0; i < n; ++i) HIP_OK(hipStreamWaitEvent(lead, p->stage[i]->ev.ev[0], 0));
+    const int rc = gather_planes_launch(who, gbuf, t, lead);
+    if (rc) return rc;
+    HIP_OK(hipStreamSynchronize(lead));
+    return RT_OK;
+  }
+};
+
+// the floats of a share's block: the planes the configuration's resolves write (push_temporal and
+// push_frame below), each padded as rt_gather_map.h pads it
+uint64_t share_block_floats(const rt_pipeline* p, uint32_t W, uint32_t rows_per) {
+  const rt_pipeline_opts& o = p->o;
+  int threes = 1, ones = 1;                                   // rgb, var
+  if (p->emit) threes += 1 + (p->split ? 1 : 0), ones += 1;   // emission, surface_albedo, coverage
+  threes += 1, ones += 1;                                     // the history's normal and depth
+  if (o.temporal && o.specular) ones += 1;                    // bounces
+  if (p->filtered) threes += 1;                               // albedo
+  if (o.temporal && o.specular && p->filtered) threes += 1, ones += 1;  // the first hit's normal and depth
+  return threes * gather_plane_floats(3, W, rows_per) + ones * gather_plane_floats(1, W, rows_per);
+}
+
+// the gather buffer and the staging for these shares, made once per size, share count and devices
+int ensure_shares(rt_pipeline* p, const AccumView* views, int n) {
+  const char* who = "rt_pipeline_push_shares";
+  const uint32_t rows_per = gather_rows_per((uint32_t)p->h, (uint32_t)n);
+  const uint64_t stride = share_block_floats(p, (uint32_t)p->w, rows_per);
+  bool same = p->gather.p && (int)p->stage.size() == n && p->share_stride == stride;
+  for (int i = 0; same && i < n; ++i) same = p->stage[i]->device == views[i].device;
+  if (same) return RT_OK;
+  drop_shares(p);
+  std::vector<int32_t> devs(n);
+  for (int i = 0; i < n; ++i) devs[i] = views[i].device;
+  int rc = enable_peers(who, devs.data(), n);  // leaves the lead device current
+  if (rc == RT_OK && (rc = p->gather.grow((size_t)n * stride * sizeof(float), who)) == RT_OK) ++p->allocations;
+  for (int i = 0; rc == RT_OK && i < n; ++i) {
+    if (hipSetDevice(devs[i]) != hipSuccess) {
+      rc = set_error(RT_ERR_DEVICE, "%s: device %d", who, devs[i]);
+      break;
+    }
+    p->stage.emplace_back(new ShareStage());
+    p->stage[i]->device = devs[i];
+    if ((rc = p->stage[i]->buf.grow((size_t)stride * sizeof(float), who))) break;
+    rc = p->stage[i]->ev.ensure(1, hipEventDisableTiming);
+  }
+  if (rc) {
+    drop_shares(p);
+    return rc;
+  }
+  p->share_stride = stride;
+  HIP_OK(hipSetDevice(p->device));
+  return RT_OK;
+}
+
 // the temporal half: Temporal.push / Temporal._push_moments.  k: the set the history is not in
-int push_temporal(rt_pipeline* p, rt_accum* acc, const AccumView& v, int k, bool has_prev) {
+int push_temporal(rt_pipeline* p, FrameSource& src, const AccumView& v, int k, bool has_prev) {
   const rt_pipeline_opts& o = p->o;
   HistSet& s = p->set[k];
   GuideSet& g = p->guide;
@@ -203,7 +387,7 @@ int push_temporal(rt_pipeline* p, rt_accum* acc, const AccumView& v, int k, bool
   // into the third set, since no out buffer of the moments entries may be one of cur's
   float* frgb = mom ? p->cur.rgb : s.rgb;
   float* fvar = mom ? p->cur.var : s.var;
-  if ((rc = rt_accum_resolve_device(acc, frgb, fvar))) return rc;
+  if ((rc = src.resolve(frgb, fvar))) return rc;
   // the frame's emission and coverage: the kernel writes them only with the light history
   float* femi = !p->emit ? nullptr : (mom && p->light) ? p->cur.emission : s.emission;
   float* fcov = !p->emit ? nullptr : (mom && p->light) ? p->cur.coverage : s.coverage;
@@ -212,14 +396,15 @@ int push_temporal(rt_pipeline* p, rt_accum* acc, const AccumView& v, int k, bool
   if (o.specular) {  // the chain's normal, depth and bounces in the first hit's place
     const rt_aov chain = {nullptr, s.normal, s.depth, nullptr};
     const rt_aov_spec sp = {s.bounces};
-    if ((rc = rt_accum_resolve_aov_spec_device(acc, &chain, &sp))) return rc;
+    if ((rc = src.resolve_aov_spec(&chain, &sp))) return rc;
     const rt_aov first = {g.albedo, g.normal, g.depth, nullptr};  // the filter's guides stay the first hit's
     if (p->filtered || ep)
-      if ((rc = rt_accum_resolve_aov_device(acc, p->filtered ? &first : nullptr, ep))) return rc;
+      if ((rc = src.resolve_aov(p->filtered ? &first : nullptr, ep))) return rc;
   } else {
     const rt_aov first = {g.albedo, s.normal, s.depth, nullptr};
-    if ((rc = rt_accum_resolve_aov_device(acc, &first, ep))) return rc;
+    if ((rc = src.resolve_aov(&first, ep))) return rc;
   }
+  if ((rc = src.gather())) return rc;  // shares: the planes are where the lines above name them
   if (!mom && !has_prev) return fill_count(p, v, k);  // the frame itself
   // the entry the configuration stands for: its name is in every message the call can raise
   const char* name = o.specular ? "rt_reproject_spec_device"
@@ -250,14 +435,15 @@ int push_temporal(rt_pipeline* p, rt_accum* acc, const AccumView& v, int k, bool
 }
 
 // temporal = 0: the frame is the accumulator's resolve and count the pass count
-int push_frame(rt_pipeline* p, rt_accum* acc, const AccumView& v, int k) {
+int push_frame(rt_pipeline* p, FrameSource& src, const AccumView& v, int k) {
   HistSet& s = p->set[k];
   GuideSet& g = p->guide;
   int rc;
-  if ((rc = rt_accum_resolve_device(acc, s.rgb, s.var))) return rc;
+  if ((rc = src.resolve(s.rgb, s.var))) return rc;
   const rt_aov first = {g.albedo, s.normal, s.depth, nullptr};
   const rt_aov_emit emit_out = {s.emission, g.surface_albedo, s.coverage};
-  if ((rc = rt_accum_resolve_aov_device(acc, &first, p->emit ? &emit_out : nullptr))) return rc;
+  if ((rc = src.resolve_aov(&first, p->emit ? &emit_out : nullptr))) return rc;
+  if ((rc = src.gather())) return rc;
   return fill_count(p, v, k);
 }
 
@@ -278,6 +464,62 @@ int push_filter(rt_pipeline* p, const AccumView& v, int k) {
   return p->split
              ? rt_denoise_emit_device(s.rgb, &feat, &emit, p->w, p->h, &o.dopts, s.image, p->device, v.stream)
              : rt_denoise_device(s.rgb, &feat, p->w, p->h, &o.dopts, s.image, p->device, v.stream);
+}
+
+// what both push entries ask of an accumulator (a share's or the whole image's), in this order
+int check_accum(const char* who, const rt_pipeline* p, const AccumView& v) {
+  if (v.passes < 1) return set_error(RT_ERR_INVALID, "%s: the accumulator holds no pass (rt_accum_add first)", who);
+  if (!v.features)
+    return set_error(RT_ERR_INVALID, "%s: needs an accumulator with features (rt_accum_set_features: the normal and "
+                     "depth guides)", who);
+  if (!(v.features & RT_ACCUM_FEAT_GUIDES))
+    return set_error(RT_ERR_INVALID, "%s: needs RT_ACCUM_FEAT_GUIDES (the normal and depth guides), the accumulator "
+                     "has planes 0x%x", who, v.features);
+  if (p->emit && !(v.features & RT_ACCUM_FEAT_EMIT))
+    return set_error(RT_ERR_INVALID, "%s: a non-plain mode and split_emitters need an accumulator with "
+                     "RT_ACCUM_FEAT_EMIT (rt_accum_set_features), this one has planes 0x%x", who, v.features);
+  if (p->o.specular && !(v.features & RT_ACCUM_FEAT_SPEC))
+    return set_error(RT_ERR_INVALID, "%s: specular needs an accumulator with RT_ACCUM_FEAT_SPEC "
+                     "(rt_accum_set_features_spec), this one has planes 0x%x", who, v.features);
+  return RT_OK;
+}
+int check_image(const char* who, int32_t w, int32_t h) {
+  if (w <= 0 || h <= 0 || (int64_t)w * h >= ((int64_t)1 << 31) / 3)
+    return set_error(RT_ERR_INVALID, "%s: %d x %d image", who, w, h);
+  return RT_OK;
+}
+
+// A checked push (p->mu held): v is the frame as the stages see it, the whole image on the lead
+// device and stream, whichever source it comes from
+int push_source(rt_pipeline* p, FrameSource& src, const AccumView& v) {
+  const rt_pipeline_opts& o = p->o;
+  int rc;
+  DeviceGuard dg;
+  if (v.width != p->w || v.rows != p->h || v.device != p->device) {  // another size or device: no history
+    drop_buffers(p);
+    p->w = v.width, p->h = v.rows, p->device = v.device;
+  }
+  HIP_OK(hipSetDevice(p->device));
+  const int k = p->last == 0 ? 1 : 0;  // never the set of the last frame: its planes stay valid for one more push
+  const bool has_prev = o.temporal && p->prev >= 0;
+  if ((rc = ensure(p, &p->set[k]))) return rc;
+  if (o.moments && (rc = ensure(p, &p->cur))) return rc;
+  if ((rc = ensure(p, &p->guide))) return rc;
+  if (!src.acc) {
+    if ((rc = ensure_shares(p, src.views, src.n))) return rc;
+    gather_begin(&src.t, (uint32_t)p->w, (uint32_t)p->h, (uint32_t)src.n, p->share_stride);
+  }
+  rc = o.temporal ? push_temporal(p, src, v, k, has_prev) : push_frame(p, src, v, k);
+  if (rc) return rc;
+  if (p->filtered && (rc = push_filter(p, v, k))) return rc;
+  // the frame is complete: it becomes the history and the last frame
+  p->prev = o.temporal ? k : -1;
+  p->cam_prev = v.cam;
+  p->last = k;
+  p->ppm_len = -1;
+  p->had_history = has_prev;
+  ++p->frames;
+  return RT_OK;
 }
 
 // rt_pipeline_image's and rt_pipeline_ppm's prologue (p->mu held, DeviceGuard in the caller)
@@ -332,52 +574,59 @@ int rt_pipeline_push(rt_pipeline* p, rt_accum* acc) {
   const char* who = "rt_pipeline_push";
   if (!p || !acc) return set_error(RT_ERR_INVALID, "%s: null pipeline/accumulator", who);
   std::lock_guard<std::mutex> lk(p->mu);
-  const rt_pipeline_opts& o = p->o;
   AccumView v;
   int rc = accum_view(acc, &v);
   if (rc) return rc;
-  if (v.passes < 1) return set_error(RT_ERR_INVALID, "%s: the accumulator holds no pass (rt_accum_add first)", who);
-  if (!v.features)
-    return set_error(RT_ERR_INVALID, "%s: needs an accumulator with features (rt_accum_set_features: the normal and "
-                     "depth guides)", who);
-  if (!(v.features & RT_ACCUM_FEAT_GUIDES))
-    return set_error(RT_ERR_INVALID, "%s: needs RT_ACCUM_FEAT_GUIDES (the normal and depth guides), the accumulator "
-                     "has planes 0x%x", who, v.features);
-  if (p->emit && !(v.features & RT_ACCUM_FEAT_EMIT))
-    return set_error(RT_ERR_INVALID, "%s: a non-plain mode and split_emitters need an accumulator with "
-                     "RT_ACCUM_FEAT_EMIT (rt_accum_set_features), this one has planes 0x%x", who, v.features);
-  if (o.specular && !(v.features & RT_ACCUM_FEAT_SPEC))
-    return set_error(RT_ERR_INVALID, "%s: specular needs an accumulator with RT_ACCUM_FEAT_SPEC "
-                     "(rt_accum_set_features_spec), this one has planes 0x%x", who, v.features);
+  if ((rc = check_accum(who, p, v))) return rc;
   if (v.nranks != 1)
     return set_error(RT_ERR_INVALID, "%s: needs the whole image (an accumulator with nranks == 1, not %d)", who,
                      v.nranks);
-  if (v.width <= 0 || v.rows <= 0 || (int64_t)v.width * v.rows >= ((int64_t)1 << 31) / 3)
-    return set_error(RT_ERR_INVALID, "%s: %d x %d image", who, v.width, v.rows);
-  if ((rc = device_ok(who, v.device))) return rc;
+  if ((rc = check_image(who, v.width, v.rows)) || (rc = device_ok(who, v.device))) return rc;
+  FrameSource src{p, acc, nullptr, nullptr, 0, {}};
+  return push_source(p, src, v);
+}
 
-  DeviceGuard dg;
-  if (v.width != p->w || v.rows != p->h || v.device != p->device) {  // another size or device: no history
-    drop_buffers(p);
-    p->w = v.width, p->h = v.rows, p->device = v.device;
+int rt_pipeline_push_shares(rt_pipeline* p, rt_accum* const* accs, int32_t n) {
+  const char* who = "rt_pipeline_push_shares";
+  if (!p || !accs) return set_error(RT_ERR_INVALID, "%s: null pipeline/accumulator array", who);
+  if (n < 1) return set_error(RT_ERR_INVALID, "%s: n = %d shares (at least 1)", who, n);
+  for (int i = 0; i < n; ++i) {
+    if (!accs[i]) return set_error(RT_ERR_INVALID, "%s: accs[%d] is null", who, i);
+    for (int j = 0; j < i; ++j)
+      if (accs[j] == accs[i]) return set_error(RT_ERR_INVALID, "%s: accs[%d] and accs[%d] are the same accumulator", who, j, i);
   }
-  HIP_OK(hipSetDevice(p->device));
-  const int k = p->last == 0 ? 1 : 0;  // never the set of the last frame: its planes stay valid for one more push
-  const bool has_prev = o.temporal && p->prev >= 0;
-  if ((rc = ensure(p, &p->set[k]))) return rc;
-  if (o.moments && (rc = ensure(p, &p->cur))) return rc;
-  if ((rc = ensure(p, &p->guide))) return rc;
-  rc = o.temporal ? push_temporal(p, acc, v, k, has_prev) : push_frame(p, acc, v, k);
-  if (rc) return rc;
-  if (p->filtered && (rc = push_filter(p, v, k))) return rc;
-  // the frame is complete: it becomes the history and the last frame
-  p->prev = o.temporal ? k : -1;
-  p->cam_prev = v.cam;
-  p->last = k;
-  p->ppm_len = -1;
-  p->had_history = has_prev;
-  ++p->frames;
-  return RT_OK;
+  std::lock_guard<std::mutex> lk(p->mu);
+  std::vector<AccumView> views(n);
+  int rc;
+  for (int i = 0; i < n; ++i)
+    if ((rc = accum_view(accs[i], &views[i]))) return rc;
+  const AccumView& v0 = views[0];
+  if (n > v0.height)
+    return set_error(RT_ERR_INVALID, "%s: %d shares of an image of %d rows (an empty share is not supported)", who, n,
+                     v0.height);
+  for (int i = 0; i < n; ++i) {
+    const AccumView& v = views[i];
+    if (v.rank != i || v.nranks != n)
+      return set_error(RT_ERR_INVALID, "%s: accs[%d] is rank %d of %d, not rank %d of %d", who, i, v.rank, v.nranks, i, n);
+    if ((rc = check_accum(who, p, v))) return rc;
+    const char* what = v.scene != v0.scene                             ? "scene"
+                       : memcmp(&v.cam, &v0.cam, sizeof(rt_camera))    ? "camera"
+                       : v.width != v0.width || v.height != v0.height  ? "image size"
+                       : v.features != v0.features                     ? "feature planes"
+                       : v.spec_bounces != v0.spec_bounces || memcmp(&v.spec_fuzz, &v0.spec_fuzz, sizeof(float))
+                           ? "chain limits (rt_accum_set_features_spec)"
+                       : v.passes != v0.passes                         ? "pass count"
+                                                                       : nullptr;
+    if (what) return set_error(RT_ERR_INVALID, "%s: accs[%d] differs from accs[0] in its %s", who, i, what);
+  }
+  if ((rc = check_image(who, v0.width, v0.height))) return rc;
+  for (int i = 0; i < n; ++i)
+    if ((rc = device_ok(who, views[i].device))) return rc;
+  // the frame as the stages see it: the whole image on the lead share's device and stream
+  AccumView v = v0;
+  v.rows = v0.height, v.rank = 0, v.nranks = 1;
+  FrameSource src{p, nullptr, accs, views.data(), n, {}};
+  return push_source(p, src, v);
 }
 
 int rt_pipeline_image(rt_pipeline* p, float* rgb_host) {
@@ -435,7 +684,8 @@ int rt_pipeline_info_get(rt_pipeline* p, rt_pipeline_info* out) {
   *out = rt_pipeline_info{};
   out->width = p->w, out->height = p->h, out->device = p->device;
   out->frames = p->frames, out->had_history = p->had_history;
-  out->device_bytes = p->set[0].buf.bytes + p->set[1].buf.bytes + p->cur.buf.bytes + p->guide.buf.bytes;
+  out->device_bytes =
+      p->set[0].buf.bytes + p->set[1].buf.bytes + p->cur.buf.bytes + p->guide.buf.bytes + p->gather.bytes;
   out->allocations = p->allocations;
   return RT_OK;
 }

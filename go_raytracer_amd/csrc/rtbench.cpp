@@ -16,6 +16,7 @@
 //   temporal_step   rt_reproject[_emit | _light | _moments | _clip] (the host entries: this client links no HIP runtime)
 //   filter          rt_denoise[_var][_emit]
 //   write_aovs      rt_format_ppm per plane
+//                   (-shares N: N accumulators, rt_accum_add_shares per pass, rt_pipeline_push_shares below)
 //   pipeline_step   -on-device: rt_pipeline_push + rt_pipeline_ppm in place of the three stages above (the
 //                   frame stays on the device; what comes back is the image's text)
 //   finish_frame    rt_format_ppm, the statistics line (-cpuprofile has no pprof to drive on the
@@ -64,6 +65,8 @@ struct Args {
   double moments_frames = 0.0;
   double spec_fuzz = 0.0;
   double orbit = 0.0;
+  long long shares = 0;
+  std::string devices;  // -devices a,b,...
 };
 
 std::vector<Flag> flags(Args& a) {
@@ -95,6 +98,8 @@ std::vector<Flag> flags(Args& a) {
        Flag::BOOL, &a.denoise_var, ""},
       {"depth", "override Camera.MaxDepth (0 = the scene's)", Flag::INT, &a.depth, "0"},
       {"device", "HIP device ordinal", Flag::INT, &a.device, "0"},
+      {"devices", "with -shares N: the N devices the shares run on, a,b,... (a device may repeat); default: share i on device i % the device count",
+       Flag::STR, &a.devices, ""},
       {"frames", "render N frames, frame k to the -o name with _00k before the extension (see -orbit)", Flag::INT,
        &a.frames, "0"},
       {"mode", "kernel strategy: auto, fused or wavefront", Flag::STR, &a.mode, "auto"},
@@ -111,6 +116,8 @@ std::vector<Flag> flags(Args& a) {
        Flag::INT, &a.passes, "0"},
       {"progress", "print render progress on stderr", Flag::BOOL, &a.progress, ""},
       {"seed", "render seed (Philox key)", Flag::U64, &a.seed, "1"},
+      {"shares", "with -on-device and -passes: accumulate each frame as N row-interleaved shares (rt_accum_add_shares) and push them into the pipeline (rt_pipeline_push_shares); the files are the same bytes; not with -adaptive, -until, -aov or -counts",
+       Flag::INT, &a.shares, "0"},
       {"slices", "progress granularity: launches per render (0 = 20 with -progress)", Flag::INT,
        &a.slices, "0"},
       {"spec-bounces", "with -aov-specular or -temporal-specular: the last vertex a specular chain may reach (0 = 8, at most 64)", Flag::INT,
@@ -267,12 +274,34 @@ struct Job {
   bool counts = false, aov = false, print_stats = false;
   bool numbered = false;  // -frames: frame k goes to the -o name with _00k before the extension
   int n_frames = 1;
+  int shares = 0;            // -shares: the frame's accumulator is this many row shares (0: one whole accumulator)
+  std::vector<int> devices;  // -devices: the shares' devices (empty: share i on device i % the device count)
 };
+
+// -devices: "a,b,..." as non-negative integers; false for anything else
+bool parse_devices(const std::string& text, std::vector<int>& out) {
+  out.clear();
+  size_t at = 0;
+  while (at <= text.size()) {
+    const size_t end = std::min(text.find(',', at), text.size());
+    if (end == at || end - at > 4) return false;
+    int v = 0;
+    for (size_t i = at; i < end; ++i) {
+      if (text[i] < '0' || text[i] > '9') return false;
+      v = 10 * v + (text[i] - '0');
+    }
+    out.push_back(v);
+    at = end + 1;
+  }
+  return true;
+}
 
 // the "flag X needs flag Y" checks in their precedence: the first that fails is reported.
 // Returns the exit code, or -1 with `j` filled.
 int make_job(const Args& a, const char* prog, Job& j) {
   const bool acc = a.passes > 0 || a.until > 0.0 || a.adaptive_set, filtered = a.denoise || a.denoise_var;
+  std::vector<int> devices;
+  const bool devices_ok = a.devices.empty() || parse_devices(a.devices, devices);
   const struct { bool bad; const char* msg; } checks[] = {
       {a.adaptive_set && !(a.adaptive > 0.0), "invalid value for flag -adaptive: the error threshold must be > 0"},
       {!a.counts.empty() && !a.adaptive_set, "-counts needs -adaptive"},
@@ -325,6 +354,15 @@ int make_job(const Args& a, const char* prog, Job& j) {
       {a.on_device && !(a.accum_features && acc), "-on-device needs -accum-features and -passes, -until or -adaptive"},
       {a.on_device && a.aov_media, "-on-device does not combine with -aov-media"},
       {a.frames < 0 || a.frames > 999 || !(a.orbit == a.orbit), "invalid value for flag -frames (0..999) / -orbit"},
+      // -shares: the pipeline is the one consumer of a frame held as shares
+      {a.shares < 0 || a.shares > 4096, "invalid value for flag -shares (1..4096)"},
+      {a.shares > 0 && !a.on_device, "-shares needs -on-device"},
+      {!a.devices.empty() && a.shares == 0, "-devices needs -shares"},
+      // (the selection and the error figure are one accumulator's)
+      {a.shares > 0 && (a.adaptive_set || a.until > 0.0), "-shares does not combine with -adaptive or -until"},
+      {a.shares > 0 && (!a.aov.empty() || !a.counts.empty()), "-shares does not combine with -aov or -counts"},
+      {!devices_ok || (!a.devices.empty() && (long long)devices.size() != a.shares),
+       "invalid value for flag -devices: one non-negative device number per share, a,b,..."},
   };
   for (const auto& c : checks)
     if (c.bad) return usage_error(prog, "%s", c.msg);
@@ -352,6 +390,8 @@ int make_job(const Args& a, const char* prog, Job& j) {
   j.print_stats = a.stats || filtered || j.temporal || a.on_device;
   j.numbered = a.frames > 0;
   j.n_frames = j.numbered ? (int)a.frames : 1;
+  j.shares = (int)a.shares;
+  j.devices = devices;
   return -1;
 }
 
@@ -405,6 +445,8 @@ struct Ctx {
   std::string out_name, aov;  // the frame's image and -aov prefix
   Owned<FILE> out;
   Owned<rt_accum> acc;
+  std::vector<Owned<rt_accum>> shares;  // -shares: the frame's accumulators, rank i of shares.size()
+  std::vector<rt_accum*> share_ptrs;
   std::vector<float> rgb, var, albedo, normal, depth, emission, salbedo, coverage, scatter, bounces;
   rt_stats st;
   rt_accum_info ai;
@@ -473,6 +515,7 @@ struct Stats {
   bool temporal_moments, temporal_clip, temporal_specular;
   bool on_device;
   double ms_pipeline;
+  int shares;  // -shares, else 0
   int frame;  // -frames, else -1
 };
 
@@ -519,6 +562,7 @@ std::string stats_json(const Stats& s) {
   if (s.aov_media) b += "\"aov_media\": 1, ";
   if (s.aov_specular) b += "\"aov_specular\": 1, ";
   if (s.on_device) appendf(b, "\"on_device\": 1, \"ms_pipeline\": %.3f, ", s.ms_pipeline);
+  if (s.shares > 0) appendf(b, "\"shares\": %d, ", s.shares);
   appendf(b, "\"wall_s\": %.3f}", s.wall_s);
   return b;
 }
@@ -599,6 +643,10 @@ void add_passes(const Job& j, Ctx& c, std::atomic<int>& pass_no, Call& s) {
       uint64_t n_active = 0;
       if (!s.ok("rt_accum_select", rt_accum_select(c.acc.get(), &ado, &n_active)) || n_active == 0) break;
       if (!s.ok("rt_accum_add_active", rt_accum_add_active(c.acc.get(), j.a.seed + (uint64_t)p, &sp))) break;
+    } else if (j.shares) {  // one pass of every share, side by side
+      if (!s.ok("rt_accum_add_shares",
+                rt_accum_add_shares(c.share_ptrs.data(), (int32_t)c.share_ptrs.size(), j.a.seed + (uint64_t)p, &sp)))
+        break;
     } else if (!s.ok("rt_accum_add", rt_accum_add(c.acc.get(), j.a.seed + (uint64_t)p, &sp))) {
       break;
     }
@@ -617,6 +665,10 @@ void add_passes(const Job& j, Ctx& c, std::atomic<int>& pass_no, Call& s) {
 // the accumulator's mean (and variance), its figures, and -counts: the passes per pixel as grey, count / max
 void resolve_passes(const Job& j, Ctx& c, Call& s, bool& counts_failed) {
   // -on-device: the mean stays where it is (rt_pipeline_push resolves it on the device)
+  if (j.shares) {  // the figures of the statistics line are share 0's: a third of the rows, say, of the same image
+    s.ok("rt_accum_info_get", rt_accum_info_get(c.share_ptrs[0], &c.ai));
+    return;
+  }
   if (s.ok("rt_accum_resolve", rt_accum_resolve(c.acc.get(), j.on_device ? nullptr : c.rgb.data(),
                                                 j.want_var && !j.on_device ? c.var.data() : nullptr)))
     s.ok("rt_accum_resolve", rt_accum_info_get(c.acc.get(), &c.ai));
@@ -635,18 +687,30 @@ int render(const Job& j, Ctx& c) {
   memset(&c.ai, 0, sizeof c.ai);
   memset(&c.adi, 0, sizeof c.adi);
   Call s;
-  if (j.accumulate) {
-    rt_accum* acc = nullptr;
-    if (!s.ok("rt_accum_create", rt_accum_create(c.sc, &c.cam, &c.o, j.pass_cap, &acc))) return fail(s.what, s.rc);
-    c.acc.reset(acc);
-  }
   const uint32_t planes = RT_ACCUM_FEAT_GUIDES | (j.emit ? RT_ACCUM_FEAT_EMIT : 0u) | (j.media ? RT_ACCUM_FEAT_MEDIA : 0u);
   const rt_aov_spec_opts chain = {(int32_t)j.a.spec_bounces, (float)j.a.spec_fuzz};
-  if (j.accum_features && j.temporal_specular) {
-    if (!s.ok("rt_accum_set_features_spec", rt_accum_set_features_spec(c.acc.get(), planes | RT_ACCUM_FEAT_SPEC, &chain)))
+  // the frame's accumulators: the whole image's, or with -shares rank i of N on the share's device
+  const int n_acc = !j.accumulate ? 0 : j.shares ? j.shares : 1;
+  const int n_dev = j.shares && j.devices.empty() ? rt_device_count() : 0;
+  for (int i = 0; i < n_acc; ++i) {
+    rt_render_opts o = c.o;
+    if (j.shares) {
+      o.rank = i, o.nranks = j.shares;
+      o.device = j.devices.empty() ? (n_dev > 0 ? i % n_dev : 0) : j.devices[i];
+      o.progress_slices = 0;
+    }
+    rt_accum* acc = nullptr;
+    if (!s.ok("rt_accum_create", rt_accum_create(c.sc, &c.cam, &o, j.pass_cap, &acc))) return fail(s.what, s.rc);
+    if (j.shares)
+      c.shares.emplace_back(acc), c.share_ptrs.push_back(acc);
+    else
+      c.acc.reset(acc);
+    if (j.accum_features && j.temporal_specular) {
+      if (!s.ok("rt_accum_set_features_spec", rt_accum_set_features_spec(acc, planes | RT_ACCUM_FEAT_SPEC, &chain)))
+        return fail(s.what, s.rc);
+    } else if (j.accum_features && !s.ok("rt_accum_set_features", rt_accum_set_features(acc, planes)))
       return fail(s.what, s.rc);
-  } else if (j.accum_features && !s.ok("rt_accum_set_features", rt_accum_set_features(c.acc.get(), planes)))
-    return fail(s.what, s.rc);
+  }
 
   bool counts_failed = false;
   Progress bar(j, c);
@@ -833,8 +897,9 @@ int make_pipeline(const Job& j, Ctx& c) {
 int pipeline_step(const Job& j, Ctx& c) {
   if (!j.on_device) return 0;
   const auto tp = std::chrono::steady_clock::now();
-  int rc = rt_pipeline_push(c.pipe.get(), c.acc.get());
-  if (rc != RT_OK) return fail("rt_pipeline_push", rc);
+  int rc = j.shares ? rt_pipeline_push_shares(c.pipe.get(), c.share_ptrs.data(), (int32_t)c.share_ptrs.size())
+                    : rt_pipeline_push(c.pipe.get(), c.acc.get());
+  if (rc != RT_OK) return fail(j.shares ? "rt_pipeline_push_shares" : "rt_pipeline_push", rc);
   const int64_t n = rt_pipeline_ppm(c.pipe.get(), nullptr, 0);
   c.text.resize((size_t)(n > 0 ? n : 0));
   if (n < 0 || rt_pipeline_ppm(c.pipe.get(), c.text.data(), n) != n) return fail("rt_pipeline_ppm", (int)n);
@@ -881,6 +946,7 @@ int finish_frame(const Job& j, Ctx& c) {
   s.denoise_var = j.filter == Filter::VAR, s.split_emitters = j.emit, s.accum_features = j.accum_features;
   s.temporal = j.temporal, s.temporal_emit = j.temporal_emit, s.temporal_light = j.temporal_light, s.temporal_moments = j.temporal_moments, s.temporal_clip = j.temporal_clip, s.temporal_specular = j.temporal_specular, s.aov_media = j.media, s.aov_specular = j.specular;
   s.on_device = j.on_device, s.ms_pipeline = c.ms_pipeline;
+  s.shares = j.shares;
   s.frame = j.numbered ? c.frame : -1;
   const std::string js = stats_json(s);
   if (j.print_stats) fprintf(stderr, "%s\n", js.c_str());
@@ -892,7 +958,11 @@ int finish_frame(const Job& j, Ctx& c) {
     }
     fprintf(p.get(), "%s\n", js.c_str());
   }
-  const int rc = c.acc ? rt_accum_destroy(c.acc.release()) : RT_OK;
+  int rc = c.acc ? rt_accum_destroy(c.acc.release()) : RT_OK;
+  c.share_ptrs.clear();
+  for (Owned<rt_accum>& sh : c.shares)
+    if (const int r = rt_accum_destroy(sh.release()); rc == RT_OK) rc = r;
+  c.shares.clear();
   return rc == RT_OK ? 0 : fail("rt_accum_destroy", rc);
 }
 

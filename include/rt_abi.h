@@ -1399,6 +1399,45 @@ int64_t rt_pipeline_ppm(rt_pipeline* p, char* out_host, int64_t cap);
 int rt_pipeline_planes_device(rt_pipeline* p, rt_frame* blended, rt_aov_emit* light, float** lum2, float** image);
 int rt_pipeline_info_get(rt_pipeline* p, rt_pipeline_info* out);
 
+/* ------------------------------------------------------------------------ */
+/* Frame pipeline over row shares: a frame accumulated as n  */
+/* row-interleaved shares (rt_accum_create with opts.rank i of opts.nranks   */
+/* n, each on any device) pushed into one pipeline.  Added without an ABI    */
+/* version change: detect by the symbols.                                    */
+/* ------------------------------------------------------------------------ */
+/* rt_accum_add_shares does rt_accum_add(accs[i], seed, ...) for every i, one host thread per share,
+ * so that shares on different devices render at the same time; each share's state afterwards is
+ * bit for bit what n sequential rt_accum_add calls leave.  stats (may be NULL) is the shares'
+ * combined as rt_render_multi combines them: counts and rows summed, the kernel times of the
+ * slowest share.  When shares fail, the code and message of the one with the lowest index are
+ * returned; the other shares keep the pass they took (their pass counts then differ, which
+ * rt_pipeline_push_shares refuses: add the missing pass or rt_accum_reset them all).
+ * RT_ERR_INVALID before anything runs: accs NULL, n < 1, a NULL element.
+ *
+ * rt_pipeline_push_shares is rt_pipeline_push for a frame held as n shares; accs[i] must be the
+ * accumulator of rank i of n.  Every plane the stages read equals, bit for bit, what a single
+ * nranks == 1 accumulator with the same passes would have resolved, so history, image and PPM are
+ * those of rt_pipeline_push.  The lead device is accs[0]'s: the pipeline's buffers live there and
+ * the stages run on accs[0]'s stream.  Each share resolves, with the _device resolves
+ * rt_pipeline_push calls, into a staging block on its own device; the blocks are copied to a gather
+ * buffer on the lead device (a peer copy between devices) and one kernel writes the planes where
+ * rt_pipeline_push's resolves write them.  The call blocks, and nothing is in flight on a staging
+ * buffer when it returns, failed or not.  A pipeline may be fed by either entry from frame to
+ * frame; a push at another size or on another lead device starts over, as rt_pipeline_push's does.
+ * rt_pipeline_info.device_bytes and allocations include the gather buffer (one allocation per
+ * size, share count and device list); the staging blocks on the shares' devices, at most 96 bytes
+ * per pixel of a share, are not in the struct.
+ * RT_ERR_INVALID, before anything is written: a NULL argument; n < 1; n greater than the image
+ * height (an empty share is not supported); a NULL element; the same accumulator twice; accs[i]
+ * whose rank is not i or whose nranks is not n; shares that differ in scene, in camera (a byte
+ * compare of rt_camera, which holds width, aspect ratio, samples and max_depth), in feature planes
+ * or chain limits, or in pass count; a share that fails a test rt_pipeline_push makes of its
+ * accumulator (no pass, missing feature groups).  Active-pixel passes (rt_accum_add_active) are
+ * what they are to rt_pipeline_push, which makes no test of them: the resolves divide each pixel by
+ * its own count and the frame's count is the accumulator's pass count. */
+int rt_accum_add_shares(rt_accum* const* accs, int32_t n, uint64_t seed, rt_stats* stats);
+int rt_pipeline_push_shares(rt_pipeline* p, rt_accum* const* accs, int32_t n);
+
 /* Demo scenes mirroring main.go (by name or the main.go -S number).
  * names: book1, book2, book3, simple_light, quads, cornell, cornell_smoke, model
  * The camera receives the scene's settings; override fields afterwards. */

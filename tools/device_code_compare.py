@@ -21,9 +21,9 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 UNITS = ["rt_render", "rt_fused_sets", "rt_fused_map", "rt_aov", "rt_accum", "rt_multi", "rt_output", "rt_build",
-         "rt_denoise", "rt_temporal", "rt_pipeline"]
+         "rt_denoise", "rt_temporal", "rt_pipeline", "rt_gather"]
 # units without the kernel headers: no build switch reaches them, the default build is all there is
-PLAIN_UNITS = ["rt_output", "rt_build", "rt_denoise", "rt_temporal", "rt_pipeline"]
+PLAIN_UNITS = ["rt_output", "rt_build", "rt_denoise", "rt_temporal", "rt_pipeline", "rt_gather"]
 NAME_MAX = 160  # a printed kernel name is cut here (hipCUB's run to kilobytes)
 BUILDS = {"default": [], "bvh8": ["-DRT_BVH8_KERNELS"], "sweep": ["-DRT_SWEEP_ORDER"]}
 # rt_fused_sets.hip's own flags (Makefile FUSED_SETS_FLAGS)
